@@ -36,6 +36,11 @@ Adds to the JSON line:
   config.sustained_*     the headline decomposition stepped back to back for >= --sustained-seconds (6 s): env-steps/s, the
                  shader clock the chip held (s_memtime cycles / 100 MHz s_memrealtime ticks around the run, cn_device_clock) and
                  the burst / sustained ratio.  Runs right after the headline legs, long before the CPU baseline.
+  config.dumped_outputs  with --dump-outputs DIR: what the headline leg's last timed step returned (obs, reward, done, topk_idx)
+                 is written as DIR/<name>.npy (float32), so that two builds can be compared output for output: the actions and
+                 initial states are seeded, and at 20 pedestrians x 360 rays every leg eligible as the headline has stepped the
+                 same actions the same number of times when its timed samples end (at other shapes the last candidate also
+                 runs the unreported ramp-up burst, so its outputs are K + min(W, 3) steps further on).
 """
 import argparse
 import json
@@ -130,6 +135,29 @@ def median_index(vals):
     return order[(len(vals) - 1) // 2]
 
 
+DUMP_LIMIT = 64 << 20     # bytes --dump-outputs may write in all (every rank's files together)
+
+
+def dump_outputs(d, outputs, suffix="", limit=DUMP_LIMIT):
+    """--dump-outputs: the caller-visible outputs of the headline leg's last timed step as d/<name><suffix>.npy, float32 (done and
+    the top-K indices are small integers, exact in float32).  Above `limit` bytes only a fixed sample of env rows is written
+    (numpy default_rng(0), sorted), their indices in d/rows<suffix>.npy (float64).  -> the names written."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    host = {k: v.cpu().numpy().astype(np.float32) for k, v in outputs.items()}
+    n = next(iter(host.values())).shape[0]
+    row_bytes = sum(v[0].nbytes for v in host.values())
+    names = sorted(host)
+    if n * row_bytes + 4096 > limit:        # 4096: the .npy headers
+        rows = np.sort(np.random.default_rng(0).choice(n, (limit - 4096) // (row_bytes + 8), replace=False))
+        host = {k: v[rows] for k, v in host.items()}
+        host["rows"] = rows.astype(np.float64)
+        names.append("rows")
+    for k in names:
+        np.save(os.path.join(d, "%s%s.npy" % (k, suffix)), host[k])
+    return names
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -153,6 +181,9 @@ def main():
     ap.add_argument("--no-sequence-traj", action="store_true", help="skip the sequence_traj leg (profiling passes: one kind of launch per kernel)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline leg's last timed step returned (obs, reward, done, topk_idx) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed seeded sample of env rows beyond that)")
     a = ap.parse_args()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))
@@ -411,11 +442,12 @@ def main():
         out = [(float(mx[i, 0]), float(sm[i, 1]) / world, float(sm[i, 2])) for i in range(len(samples))]
         return out, [x.cpu().tolist() for x in allr]
 
-    def measure(lcfg, candidates, lacts=None, agent=None, mode="next", repeats=R, probe=True, sequence_leg=False):
+    def measure(lcfg, candidates, lacts=None, agent=None, mode="next", repeats=R, probe=True, sequence_leg=False, keep_outputs=False):
         """Every candidate decomposition of one config: pre-roll + warm-up, one probe of K steps each (the best probe among the
         ELIGIBLE ones decides the headline), then `repeats` timed samples each.  Eligible = can serve a policy in the loop: stream
         groups / one launch per step (integers) and cn_rollout_policy; the open-loop cn_step_sequence forms and the A/B legs are
-        comparables only.  Returns a dict with the chosen decomposition's median sample and all legs."""
+        comparables only.  Returns a dict with the chosen decomposition's median sample and all legs; keep_outputs: also the
+        chosen leg's output tensors as its last timed step left them (`outputs`, device tensors, no copy made here)."""
         legs = {}
         if sequence_leg:
             # + the A/B of cn_set_arbitration on one launch per step (only where the library's default is the fair kernel)
@@ -453,11 +485,14 @@ def main():
             out["legs"][G] = {"median": vals[mi], "samples": vals, "wall": red[mi][0], "kernel_ms": red[mi][1],
                               "taken": red[mi][2], "enq_ms": legs[G].enq_ms, "arbitration": legs[G].arbitration, "kernel": legs[G].kernel,
                               "per_rank": [pr[mi] for pr in per_rank] if per_rank else None}
+            if keep_outputs and G == chosen:
+                g_ = legs[G].grp          # the tensors outlive the handles; no later launch writes them
+                out["outputs"] = {"obs": g_.obs, "reward": g_.reward, "done": g_.done, "topk_idx": g_.topk_idx}
             legs[G].close()
         return out
 
     cands = [Gmax] + [g for g in (2, 1) if g < Gmax and N % g == 0]
-    main_m = measure(cfg, cands, lacts=acts, sequence_leg=(a.peds, a.rays) == (20, 360))
+    main_m = measure(cfg, cands, lacts=acts, sequence_leg=(a.peds, a.rays) == (20, 360), keep_outputs=a.dump_outputs is not None)
     same_m = measure(cfg, [1], lacts=acts, mode="same", repeats=min(R, 3), probe=False)
     def leg_name(g):
         return g if isinstance(g, str) else "%d_groups" % g
@@ -765,6 +800,9 @@ def main():
                                # virtualised) cannot travel to the GPU box; BASELINE.md's figure, measured in the container
                                "reference_python": {"value": 102.0, "unit": "env-steps/s", "cores": 1, "where": "container",
                                                     "source": "BASELINE.md"}}
+    if a.dump_outputs is not None:
+        out["config"]["dumped_outputs"] = dump_outputs(a.dump_outputs, main_m["outputs"], "" if world == 1 else "_rank%d" % rank,
+                                                      DUMP_LIMIT // world)
     if rank == 0:
         print(json.dumps(out))
     if use_dist:

@@ -3,12 +3,14 @@
 own TD3 classes (turtlebot3_rl_sim/src/td3.py -- imports only torch/numpy, so it runs here unmodified) are
 imported from /root/reference and driven on seeded inputs:
 
-  actor_*    Actor(398, 2, 256).forward on 32 observations, weights from torch.manual_seed(7)
+  actor_*    Actor(398, 2, 256).forward on 32 observations, weights from torch.manual_seed(7) (actor_out_f64: the same
+             forward in float64)
   upd_*      four consecutive Agent.learn(step) calls (step = 0..3, policy_update = 2 -> both branches) of a small
              agent (46 -> 32 -> 32), batch 16, with the replay sample order and the target-policy noise pinned:
              initial parameters of the six networks, the batch, the noise, and every parameter after each call.
 
 Writes tests/golden/td3.npz (data only).  Usage: python oracle/make_goldens_td3.py"""
+import copy
 import importlib.util
 import os
 import random
@@ -45,6 +47,9 @@ def main():
     with torch.no_grad():
         act = actor(torch.from_numpy(obs)).numpy()
     out["actor_seed"] = np.int64(7); out["actor_obs"] = obs; out["actor_out"] = act
+    # the same weights and inputs in float64: float32 sgemm rounds differently from one CPU to the next, float64 agrees to ~1e-16
+    with torch.no_grad():
+        out["actor_out_f64"] = copy.deepcopy(actor).double()(torch.from_numpy(obs).double()).numpy()
     # ---- Agent.act clip bounds (noise off) ----
     ag = ref.Agent(398, 2, 256, 3e-4, 3e-4, 128, 1000, 0.99, 0.005, 0.22, 2.0, 0.2, 0.5, 2)
     ag.actor_local.load_state_dict(actor.state_dict())
