@@ -1116,10 +1116,12 @@ def test_graphed_rollout_replays():
 def test_mfma_actor_matches_the_torch_actor():
     """cn_actor_forward (one kernel, f32 matrix cores) vs the PyTorch fp32 actor of td3.py:81-106: same actions
     up to float32 summation order; ragged batch sizes; input widths that are not multiples of 32 (zero-padded rows of the
-    packed first layer: 398 -> 416, 382 -> 384, 370 -> 384) and one that is (384)."""
+    packed first layer: 398 -> 416, 382 -> 384, 370 -> 384) and one that is (384), and the narrow 1, 31, 33.  Both float32
+    results are also held to a float64 evaluation of the same actor: the kernel is at least as accurate as a float32 order
+    should be (within twice PyTorch's float32 error, plus 1e-7)."""
     import torch
     from crowdnav.td3 import Agent
-    for obs_dim, n in ((398, 4096), (398, 37), (382, 1000), (370, 16), (384, 100)):
+    for obs_dim, n in ((398, 4096), (398, 37), (382, 1000), (370, 16), (384, 100), (1, 64), (31, 64), (33, 64)):
         agent = Agent(obs_dim=obs_dim, device="cuda", seed=obs_dim, memory_size=16)
         with torch.no_grad():   # asymmetric, non-trivial weights so a transposed tile would show
             for p_ in agent.actor.parameters():
@@ -1130,6 +1132,14 @@ def test_mfma_actor_matches_the_torch_actor():
         torch.cuda.synchronize()
         assert got.shape == ref.shape
         assert torch.allclose(got, ref, atol=3e-5, rtol=1e-4), float((got - ref).abs().max())
+        with torch.no_grad():
+            f = {k: v.double() for k, v in agent.actor.state_dict().items()}
+            h = torch.relu(obs.double() @ f["linear1.weight"].T + f["linear1.bias"])
+            h = torch.relu(h @ f["linear2.weight"].T + f["linear2.bias"])
+            lg = h @ f["linear3.weight"].T + f["linear3.bias"]
+            f64 = torch.stack([torch.sigmoid(lg[:, 0]) * agent.max_v, torch.tanh(lg[:, 1]) * agent.max_w], 1)
+        err_mfma, err_torch = float((got.double() - f64).abs().max()), float((ref.double() - f64).abs().max())
+        assert err_mfma <= 2 * err_torch + 1e-7, (obs_dim, n, err_mfma, err_torch)
         noisy = agent.act_mfma(obs, add_noise=True)
         assert float(noisy[:, 0].min()) >= 0.0 and float(noisy[:, 0].max()) <= 0.22 and float(noisy[:, 1].abs().max()) <= 2.0
         assert not torch.equal(noisy, got)
