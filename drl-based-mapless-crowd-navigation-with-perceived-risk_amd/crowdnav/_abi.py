@@ -12,6 +12,9 @@ LIB_PATH = os.path.join(_PKG, "lib", "libcrowdnav.so")
 BUILD_SH = os.path.join(_PKG, "csrc", "build.sh")
 
 CN_MAX_TRACKS = 64
+CN_MAX_TRACKS_WIDE = 1024   # the wide tracker table (track_capacity 128 ... 1024, include/crowdnav.h)
+TRACK_CAPACITIES = (0, 32, 64, 128, 256, 512, 1024)      # what cn_create accepts for cn_config.track_capacity
+STATUS_BITS = {"track_overflow": 1, "ttc_zero": 2, "dt_zero": 4, "conf_overflow": 8, "track_wide": 16}   # include/crowdnav.h CN_ST_*
 EXPECTED_ABI = 7       # the version the ctypes structs below were written against (include/crowdnav.h CN_ABI_VERSION)
 CN_PHASE_ALL, CN_PHASE_PRE, CN_PHASE_GET_STATE, CN_PHASE_REWARD = 0, 1, 2, 4
 CN_SD_COUNT = 24

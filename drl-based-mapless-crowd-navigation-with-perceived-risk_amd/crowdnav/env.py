@@ -392,21 +392,33 @@ class VecEnv:
         _abi.check(self.L.cn_get_returns(self.h, _ptr(self._ret), _ptr(self._run), self._stream()))
         return self._ret, self._run
 
-    STATUS_BITS = {"track_overflow": 1, "ttc_zero": 2, "dt_zero": 4, "conf_overflow": 8}      # include/crowdnav.h CN_ST_*
+    STATUS_BITS = dict(_abi.STATUS_BITS)      # include/crowdnav.h CN_ST_*
+
+    @property
+    def track_capacity(self):
+        """Tracker slots per env of this handle: cn_config.track_capacity as cn_create resolves it (0 = auto: 32 up to 40
+        pedestrians -- up to 32 with risk_mode 1 --, else 64)."""
+        tc = int(self.cfg.track_capacity)
+        if tc:
+            return tc
+        return 32 if (self.P <= 40 and not (self.cfg.risk_mode == 1 and self.P > 32)) else 64
 
     def status_counts(self):
         """How many environments carry each bit of the per-env status word (sticky until the handle is re-created): a host read.
         track_overflow / conf_overflow: the env outgrew track_capacity (32 / 64 tracks) or the confirmed-object table -- the
         reference's Python lists are unbounded (its tracker keeps the tracks of earlier episodes and duplicates them at a reset), so
         from that step on the env's risk features are computed from the tracks that fit and no longer equal the reference's;
-        ttc_zero / dt_zero: a zero time to collision / a repeated time stamp (the reference divides by zero there too)."""
+        ttc_zero / dt_zero: a zero time to collision / a repeated time stamp (the reference divides by zero there too);
+        track_wide (informational): the env's track list has once held more than 64 tracks -- a handle with a wide table
+        (track_capacity 128 ... 1024) kept them all (track_overflow is only raised past ITS capacity), a 64-slot one would
+        have overflowed there."""
         st = self.counters()[:, 6]
         return {k: int(((st & b) != 0).sum().item()) for k, b in self.STATUS_BITS.items()}
 
 
     def debug_env(self, env=0):
         sd = np.zeros(_abi.CN_SD_COUNT); rp = np.zeros(5 + 4 * self.P)
-        tr = np.zeros((_abi.CN_MAX_TRACKS, _abi.CN_TF_COUNT)); si = np.zeros(_abi.CN_SI_COUNT, dtype=np.int32)
+        tr = np.zeros((self.track_capacity, _abi.CN_TF_COUNT)); si = np.zeros(_abi.CN_SI_COUNT, dtype=np.int32)
         _abi.check(self.L.cn_debug_env(self.h, int(env), sd.ctypes.data, rp.ctypes.data, tr.ctypes.data, si.ctypes.data))
         tr = np.ascontiguousarray(tr.T)   # -> [field, slot]
         n = int(si[_abi.SI["NTRACKS"]])

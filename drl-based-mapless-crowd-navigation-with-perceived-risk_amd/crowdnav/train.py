@@ -136,7 +136,7 @@ def train(a):
     dev = a.device
     torch.cuda.set_device(dev)        # policy kernels and torch ops of this process all target the env's GPU
     env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, waypoint_reward=a.waypoint_reward,
-                   scan_f32=a.scan_f32, wheel_accel=a.wheel_accel)
+                   scan_f32=a.scan_f32, wheel_accel=a.wheel_accel, track_capacity=getattr(a, "track_capacity", None))
     agent = Agent(obs_dim=env.D, device="cuda:%d" % dev, seed=a.seed, batch_size=a.batch, memory_size=a.memory,
                   actor_final_init=getattr(a, "actor_final_init", None))
     if a.load:
@@ -211,7 +211,8 @@ def train(a):
                     warned_overflow = True
                     line = ("WARNING: %d env(s) outgrew the track table and %d the confirmed-object table (status bits CN_ST_TRACK_OVERFLOW / "
                             "CN_ST_CONF_OVERFLOW): their risk features use the tracks that fit and differ from the reference's unbounded "
-                            "lists from there on; Config(track_capacity=64) doubles the table" % (sc_["track_overflow"], sc_["conf_overflow"]))
+                            "lists from there on; --track-capacity 256 (or 128 / 512 / 1024: a wide table in HBM, slower) keeps the "
+                            "track list equal to the reference's up to that many tracks" % (sc_["track_overflow"], sc_["conf_overflow"]))
                     print(line, flush=True); log.write(line + "\n"); log.flush()
             if a.csv:
                 stats.append_csv(a.out, "td3_training", resume=resumed)   # incremental: a killed run keeps its rows up to here
@@ -241,7 +242,7 @@ def train(a):
 def run_evaluation(a):
     torch.cuda.set_device(a.device)
     env = make_env(a.scenario, a.envs, a.max_steps, a.seed, a.device, a.ped_vmax, waypoint_reward=a.waypoint_reward,
-                   scan_f32=a.scan_f32, wheel_accel=a.wheel_accel)
+                   scan_f32=a.scan_f32, wheel_accel=a.wheel_accel, track_capacity=getattr(a, "track_capacity", None))
     agent = Agent(obs_dim=env.D, device="cuda:%d" % a.device, seed=a.seed, memory_size=16)
     a.load_episode = resolve_load_episode(a.load, a.load_episode)
     agent.load_models(*[os.path.join(a.load, "td3_%s_model_ep%d.pt" % (n, a.load_episode)) for n in ("actor", "critic1", "critic2")])
@@ -272,6 +273,9 @@ def main(argv=None):
     ap.add_argument("--waypoint-reward", type=int, default=None, help="cn_config.waypoint_reward: ENV:1116's 200 (default) or 0 = the published log's reward")
     ap.add_argument("--scan-f32", type=int, default=None, help="cn_config.scan_f32")
     ap.add_argument("--wheel-accel", type=float, default=None, help="cn_config.wheel_accel (XACRO:70: 1.0)")
+    ap.add_argument("--track-capacity", type=int, default=None, choices=[0, 32, 64, 128, 256, 512, 1024],
+                    help="cn_config.track_capacity: 0 = auto (32 / 64, LDS); 128 ... 1024 = a wide table in HBM for long runs whose track "
+                         "list outgrows 64 (slower; CN_ST_TRACK_OVERFLOW otherwise)")
     ap.add_argument("--reset-mode", default="next", choices=["next", "same"], help="next: the fast kernel, reset launches masked out of the replay; same: same-call reset + final_obs")
     ap.add_argument("--graphs", type=int, default=1, help="1: capture the TD3 update into hipGraphs (Agent.enable_graphs)")
     ap.add_argument("--learner", default="torch", choices=["torch", "fused"], help="torch: the PyTorch update (eager / hipGraph); fused: cn_td3_update (csrc/crowdnav_td3.hip)")

@@ -78,6 +78,11 @@ extern "C" __global__ void cn_policy_kernel_ct(CnKParams p);
 extern "C" __global__ void cn_policy_kernel_gt_ct(CnKParams p);
 extern "C" __global__ void cn_policy_kernel_orig(CnKParams p);
 extern "C" __global__ void cn_policy_kernel_rw(CnKParams p);
+extern "C" __global__ void cn_env_kernel_wide(CnKParams p);
+extern "C" __global__ void cn_env_kernel_wide_same(CnKParams p);
+extern "C" __global__ void cn_env_kernel_wide_ext(CnKParams p);
+extern "C" __global__ void cn_env_kernel_seq_wide(CnKParams p);
+extern "C" __global__ void cn_policy_kernel_wide(CnKParams p);
 // every kernel launched with cn_create's dynamic LDS size (hipFuncAttributeMaxDynamicSharedMemorySize above 64 KiB)
 static const void* const kDynamicLdsKernels[] = {
     (const void*)cn_env_kernel, (const void*)cn_env_kernel_fair, (const void*)cn_env_kernel_ext, (const void*)cn_env_kernel_same,
@@ -92,12 +97,14 @@ static const void* const kDynamicLdsKernels[] = {
     (const void*)cn_env_kernel_seq_sf, (const void*)cn_env_kernel_seq_sfd, (const void*)cn_env_kernel_seq_wa,
     (const void*)cn_env_kernel_gt_seq_sf, (const void*)cn_env_kernel_gt_seq_sfd, (const void*)cn_env_kernel_gt_seq_wa,
     (const void*)cn_env_kernel_s360_w4, (const void*)cn_env_kernel_fair_s360_w4, (const void*)cn_env_kernel_s360_x2,
-    (const void*)cn_env_kernel_seq_ct, (const void*)cn_env_kernel_gt_seq_ct, (const void*)cn_env_kernel_seq_orig, (const void*)cn_env_kernel_seq_rw};
+    (const void*)cn_env_kernel_seq_ct, (const void*)cn_env_kernel_gt_seq_ct, (const void*)cn_env_kernel_seq_orig, (const void*)cn_env_kernel_seq_rw,
+    (const void*)cn_env_kernel_wide, (const void*)cn_env_kernel_wide_same, (const void*)cn_env_kernel_wide_ext, (const void*)cn_env_kernel_seq_wide};
 static const void* const kPolicyKernels[] = {
     (const void*)cn_policy_kernel, (const void*)cn_policy_kernel_s360, (const void*)cn_policy_kernel_gt, (const void*)cn_policy_kernel_s720,
     (const void*)cn_policy_kernel_sf, (const void*)cn_policy_kernel_sfd, (const void*)cn_policy_kernel_wa,
     (const void*)cn_policy_kernel_gt_sf, (const void*)cn_policy_kernel_gt_sfd, (const void*)cn_policy_kernel_gt_wa,
-    (const void*)cn_policy_kernel_ct, (const void*)cn_policy_kernel_gt_ct, (const void*)cn_policy_kernel_orig, (const void*)cn_policy_kernel_rw};
+    (const void*)cn_policy_kernel_ct, (const void*)cn_policy_kernel_gt_ct, (const void*)cn_policy_kernel_orig, (const void*)cn_policy_kernel_rw,
+    (const void*)cn_policy_kernel_wide};
 extern "C" __global__ void cn_bbox_kernel(CnKParams p, double* out);
 extern "C" __global__ void cn_gather_kernel(CnKParams p, float* last_ret, float* run_ret, int32_t* counters);
 
@@ -111,6 +118,7 @@ struct cn_env_s {
     cn_config cfg;
     int device;
     int D, max_conf, trk_cap;
+    bool wide = false;                // trk_cap > CN_MAX_TRACKS: the tracker table stays in HBM (the _wide kernels)
     size_t lds;
     CnKParams kp;        // template with state/table pointers filled in
     double *d_lidar = nullptr, *d_poly = nullptr, *d_ped_init = nullptr, *d_ped_preset = nullptr, *d_trk = nullptr;
@@ -177,10 +185,12 @@ static void build_assoc_table(CnKParams& k, int16_t* tab)
 }
 
 // regions A + B of the carve below: the simulators' scratch (idle while the world advances)
+// (a wide table, trk_cap > CN_MAX_TRACKS, lives in HBM: region A holds the end points only -- env_kernel_body, WIDE)
+static size_t lds_trk_slots(int trk_cap) { return trk_cap > CN_MAX_TRACKS ? 0 : (size_t)trk_cap; }
 static size_t lds_scratch_bytes(int R, int P, int K, int max_conf, int trk_cap, bool near_separate)
 {
     size_t n = (size_t)(R - 1), mc = (size_t)max_conf;
-    size_t szA_pts = (10 * n + 7) & ~(size_t)7, szA_trk = 8 * (size_t)(CN_TF_COUNT * trk_cap);
+    size_t szA_pts = (10 * n + 7) & ~(size_t)7, szA_trk = 8 * (size_t)CN_TF_COUNT * lds_trk_slots(trk_cap);
     size_t szA = szA_pts > szA_trk ? szA_pts : szA_trk;
     size_t szB_g = (6 * n + 7) & ~(size_t)7;
     size_t szB_c = 32 * mc + 8 * 64 + 8 * (size_t)(8 + 4 * K) + 4 * (size_t)CN_MAX_K;
@@ -194,7 +204,7 @@ static size_t lds_bytes_impl(int R, int P, int K, int max_conf, int trk_cap, boo
     // must mirror the carve in cn_env_kernel (compact: the 720-ray shape kernels' layout -- int16 end points, 12-byte confirmed
     // objects, the pedestrians' velocities overlaid on region A)
     size_t n = (size_t)(R - 1), mc = (size_t)max_conf;
-    size_t szA_pts = ((compact ? 6 : 10) * n + 7) & ~(size_t)7, szA_trk = 8 * (size_t)(CN_TF_COUNT * trk_cap);
+    size_t szA_pts = ((compact ? 6 : 10) * n + 7) & ~(size_t)7, szA_trk = 8 * (size_t)CN_TF_COUNT * lds_trk_slots(trk_cap);
     size_t szA = szA_pts > szA_trk ? szA_pts : szA_trk;
     size_t szB_g = (6 * n + 7) & ~(size_t)7;
     size_t szC = compact ? ((12 * mc + 7) & ~(size_t)7) : 32 * mc;
@@ -322,12 +332,24 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
     const cn_config& c = *cfg;
     if (c.n_envs < 1 || c.n_peds < 0 || c.n_peds > 4096 || c.n_rays < 8 || c.n_rays > 1025 || c.k_obstacles < 1 ||
         c.k_obstacles > CN_MAX_K || c.ped_cycle_ms < 1 || c.dt_ms < 1 || c.scan_latency_ms < 1 || c.settle_ms < 0 ||
-        c.max_steps < 1 || !(c.track_capacity == 0 || c.track_capacity == 32 || c.track_capacity == 64) ||
+        c.max_steps < 1 ||
         !(c.obs_layout == CN_LAYOUT_RISK || c.obs_layout == CN_LAYOUT_ORIGINAL || c.obs_layout == CN_LAYOUT_REALWORLD) ||
         !(c.geos_untyped_empty == 0 || c.geos_untyped_empty == 1) || !(c.ped_contact == 0 || c.ped_contact == 1) ||
         !(c.risk_mode == CN_RISK_LIDAR_TRACKER || c.risk_mode == CN_RISK_GT) || !(c.py2_round == 0 || c.py2_round == 1) ||
         c.ped_mode < 0 || c.ped_mode > 2 || !(c.scan_f32 == 0 || c.scan_f32 == 1))
         return fail(CN_ERR_CONFIG, "cn_create: config out of range");
+    const int tc = c.track_capacity;
+    if (!(tc == 0 || tc == 32 || tc == 64 || tc == 128 || tc == 256 || tc == 512 || tc == 1024))
+        return fail(CN_ERR_CONFIG, "cn_create: track_capacity must be one of 0 (auto), 32, 64 (LDS table) or 128, 256, 512, 1024 "
+                                   "(wide table in HBM); got " + std::to_string(tc));
+    if (tc > CN_MAX_TRACKS) {
+        if (c.risk_mode == CN_RISK_GT)
+            return fail(CN_ERR_CONFIG, "cn_create: a wide track_capacity (> 64) is for risk_mode lidar_tracker: in gt mode the entries are "
+                                       "the pedestrians in range, rebuilt every observation, and track_capacity 64 already holds them");
+        if (c.obs_layout != CN_LAYOUT_RISK || c.ped_contact || c.ped_mode == 2 || c.wheel_accel > 0.0)
+            return fail(CN_ERR_CONFIG, "cn_create: a wide track_capacity (> 64) is built for obs_layout 0 with the plain simulator "
+                                       "(ped_mode 0 / 1, ped_contact 0, wheel_accel 0) only");
+    }
     if (!(c.wheel_accel >= 0.0) || (c.wheel_accel > 0.0 && (c.ped_contact || c.ped_mode == 2 || c.obs_layout != CN_LAYOUT_RISK || !(c.wheel_separation > 0.0))))
         return fail(CN_ERR_CONFIG, "cn_create: wheel_accel must be >= 0 and needs obs_layout 0, the plain simulator (ped_contact 0, ped_mode 0 / 1) "
                                    "and a positive wheel_separation");
@@ -361,6 +383,7 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
     // (risk_mode gt lists the simulator's own pedestrians in range: up to P entries, so 33-40 pedestrians take the larger table there --
     // tools/fuzz_parity.py found a 36-pedestrian gt world with more than 32 of them in range)
     h->trk_cap = c.track_capacity ? c.track_capacity : ((P <= 40 && !(c.risk_mode == CN_RISK_GT && P > 32)) ? 32 : 64);
+    h->wide = h->trk_cap > CN_MAX_TRACKS;
     h->lds = lds_bytes_impl(R, P, K, h->max_conf, h->trk_cap, cn_near_separate(R, P, K, h->max_conf, h->trk_cap) != 0, c.obs_layout);
     if (c.ped_contact && c.obs_layout != CN_LAYOUT_RISK)
         return fail(CN_ERR_CONFIG, "cn_create: ped_contact is built for the risk observation layout (obs_layout 0) only");
@@ -390,7 +413,8 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
     HIPCHK(hipMalloc(&h->d_state, (size_t)N * h->stride));
     HIPCHK(hipMalloc(&h->d_ped_init, pb));
     HIPCHK(hipMalloc(&h->d_ped_preset, pb));
-    HIPCHK(hipMalloc(&h->d_trk, (size_t)N * CN_TF_COUNT * h->trk_cap * 8));
+    // (a wide handle: + [N][trk_cap] doubles behind the tables, the entries' collision probabilities -- scratch inside one call)
+    HIPCHK(hipMalloc(&h->d_trk, (size_t)N * (CN_TF_COUNT + (h->wide ? 1 : 0)) * h->trk_cap * 8));
     HIPCHK(hipMalloc(&h->d_ped_aux, (size_t)N * (P > 0 ? P : 1) * 24));
     h->ped_init.resize((size_t)N * P * 2);
     for (int e = 0; e < N; ++e) default_ped_init(c, e, &h->ped_init[(size_t)e * P * 2]);
@@ -555,6 +579,7 @@ static KernelChoice choose_kernel(const cn_env_s* h, bool ext, bool same, bool o
     const cn_config& c = h->cfg;
     if (c.obs_layout == CN_LAYOUT_REALWORLD) return ext ? CN_KC(cn_env_kernel_rw_ext) : same ? CN_KC(cn_env_kernel_rw_same) : CN_KC(cn_env_kernel_rw);
     if (c.obs_layout == CN_LAYOUT_ORIGINAL) return ext ? CN_KC(cn_env_kernel_orig_ext) : same ? CN_KC(cn_env_kernel_orig_same) : CN_KC(cn_env_kernel_orig);
+    if (h->wide) return ext ? CN_KC(cn_env_kernel_wide_ext) : same ? CN_KC(cn_env_kernel_wide_same) : CN_KC(cn_env_kernel_wide);   // (cn_create: layout 0, tracker, plain simulator)
     if (ext) return c.risk_mode == CN_RISK_GT ? KernelChoice{nullptr, nullptr} : CN_KC(cn_env_kernel_ext);
     // simulated sensors: {lidar tracker, gt} x {plain, contact, social force, wheel ramp} x {one observation per launch, step + same-call reset}
     const bool gt = c.risk_mode == CN_RISK_GT, ct = c.ped_contact != 0, sf = c.ped_mode == 2, wa = c.wheel_accel > 0.0;
@@ -583,6 +608,7 @@ static KernelChoice choose_sequence_kernel(const cn_env_s* h)
     const cn_config& c = h->cfg;
     if (c.obs_layout == CN_LAYOUT_REALWORLD) return CN_KC(cn_env_kernel_seq_rw);
     if (c.obs_layout == CN_LAYOUT_ORIGINAL) return CN_KC(cn_env_kernel_seq_orig);
+    if (h->wide) return CN_KC(cn_env_kernel_seq_wide);
     const bool gt = c.risk_mode == CN_RISK_GT, ct = c.ped_contact != 0, sf = c.ped_mode == 2, wa = c.wheel_accel > 0.0;
     const bool sfd = sf && !h->kp.sf_pair_matrix && c.n_peds <= 128;
     if (wa) return gt ? CN_KC(cn_env_kernel_gt_seq_wa) : CN_KC(cn_env_kernel_seq_wa);          // (choose_kernel: the wheel ramp comes first)
@@ -597,6 +623,7 @@ static KernelChoice choose_policy_kernel(const cn_env_s* h)
     const cn_config& c = h->cfg;
     if (c.obs_layout == CN_LAYOUT_REALWORLD) return CN_KC(cn_policy_kernel_rw);
     if (c.obs_layout == CN_LAYOUT_ORIGINAL) return CN_KC(cn_policy_kernel_orig);
+    if (h->wide) return CN_KC(cn_policy_kernel_wide);
     const bool gt = c.risk_mode == CN_RISK_GT, ct = c.ped_contact != 0, sf = c.ped_mode == 2, wa = c.wheel_accel > 0.0;
     const bool sfd = sf && !h->kp.sf_pair_matrix && c.n_peds <= 128;
     if (wa) return gt ? CN_KC(cn_policy_kernel_gt_wa) : CN_KC(cn_policy_kernel_wa);
@@ -695,7 +722,7 @@ extern "C" int cn_set_group_envs(cn_handle h, int64_t total_envs)
 extern "C" int cn_get_arbitration(cn_handle h)
 {
     if (!h) return fail(CN_ERR_ARG, "cn_get_arbitration: null handle");
-    const bool has_variant = h->cfg.obs_layout == CN_LAYOUT_RISK && h->cfg.risk_mode != CN_RISK_GT && !h->cfg.ped_contact && h->cfg.ped_mode != 2 && !(h->cfg.wheel_accel > 0.0);
+    const bool has_variant = !h->wide && h->cfg.obs_layout == CN_LAYOUT_RISK && h->cfg.risk_mode != CN_RISK_GT && !h->cfg.ped_contact && h->cfg.ped_mode != 2 && !(h->cfg.wheel_accel > 0.0);
     return has_variant && fair_launch(h, false) ? CN_ARB_FAIR : CN_ARB_OLDEST_FIRST;
 }
 

@@ -100,11 +100,12 @@ struct Lds {
     double* ped;      // [2P] positions
     double* pedv;     // [2P] velocities
     double* trk;      // [CN_TF_COUNT][tcap]
-    int tcap;         // tracker slots (32 or 64)
+    int tcap;         // tracker slots (32 or 64; the wide kernels: 128 ... 1024, table in HBM)
     double* cfx; double* cfy; double* cfd; int* cft; int* checked;   // confirmed objects
     double* cpv;      // [CN_MAX_TRACKS] collision probability per track
     double* stage;    // [64] staging buffer of the bbox-size sum (reset only)
     double* gtrk;     // this env's tracker table in HBM
+    double* gcpv;     // wide kernels only: [tcap] collision probability per track, in HBM behind the N tracker tables
     int wstride;      // words per mask
     double* tail;     // [7 + 4K]
     int* kidx;        // [K]
@@ -1042,10 +1043,130 @@ __device__ __forceinline__ double bbox_size(KP p, double* stage, int lane, int n
 }
 
 // ---- ENV:656-743 tracker (the same block is RW:478-571), on the confirmed objects L.cfx / cfy / cfd / cft [nconf] ----------
-#define TRK(f, i) T[(f) * L.tcap + (i)]
+// WIDE (track_capacity 128 ... 1024): T is the env's table in HBM, used in place in its record layout [tcap][CN_TF_COUNT];
+// otherwise T is the LDS copy, field-major [CN_TF_COUNT][tcap]
+template <bool WIDE> __device__ __forceinline__ int trk_ix(int tcap, int f, int i) { if constexpr (WIDE) return i * CN_TF_COUNT + f; else return f * tcap + i; }
+#define TRK(f, i) T[trk_ix<WIDE>(L.tcap, (f), (i))]
+// The wide kernels hand track records from lane to lane through GLOBAL memory.  CN_SYNC orders the accesses for the compiler
+// (wavefront-scope fences: no instructions) and the LDS keeps a wave's DS operations in order; for global memory this adds an
+// explicit  s_waitcnt vmcnt(0)  (gfx9 counts stores on vmcnt too) so every store of the wave has COMPLETED before any load behind
+// the sync is issued.  A completed store is visible to every later load of the same CU: the vector L1 is shared by the CU's SIMDs
+// and write-through, and the LLVM AMDGPU memory model for gfx942 / gfx950 says "no special action is required for coherence
+// between the lanes of a single wavefront" (nor between waves of one work-group: same CU).  So lane B's load after
+// CN_WIDE_SYNC() sees lane A's store before it.
+#define CN_WIDE_SYNC() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); CN_SYNC(); } while (0)
+#define CN_TSYNC() do { if constexpr (WIDE) CN_WIDE_SYNC(); else CN_SYNC(); } while (0)
+
+// The wide tracker: the same ENV:656-743 steps as tracker_stage, over a table of up to 1024 tracks in HBM, 64 tracks per chunk
+// (lane = track - c0).  Chunk by chunk: popleft, the tiled IoU arg-max, the order-dependent walk of ENV:702-717 (`cur` carried
+// from chunk to chunk, one 64-bit alive mask per chunk), the matched tracks' update, and the in-order compaction (slot = the
+// survivors of the earlier chunks + the prefix popcount in this one).  A survivor moves to a slot <= its own index, and the
+// records of later chunks are not read before their own chunk, so the in-place compaction never overwrites a record still to be
+// read.  Then unmatched 'o' objects are appended at slot < tcap (CN_ST_TRACK_OVERFLOW past that), CN_ST_TRACK_WIDE once the list
+// has held more than CN_MAX_TRACKS (= where a 64-slot table, and the CPU oracle, would have overflowed).
+__device__ __forceinline__ void tracker_stage_wide(KP p, EnvRegs& e, const Lds& L, double* const T, int lane, int nconf, double now)
+{
+    constexpr bool WIDE = true;
+    constexpr bool CMP = false;
+    bool add_unchecked = false;
+    for (int j = lane; j < nconf; j += 64) chk_set<CMP>(L, j, 0);
+    if (e.ntracks == 0) {
+        add_unchecked = true;  // every 'o' object becomes a track
+    } else if (nconf == 0) {
+        e.ntracks = 0;  // ENV:683-686 nets out to clearing every track (the popleft of ENV:678-680 is then moot)
+    } else {
+        CN_SYNC();
+        const int nt0 = e.ntracks;
+        int cur = nt0, kept = 0;
+        for (int c0 = 0; c0 < nt0; c0 += 64) {
+            const int cn = min(nt0 - c0, 64);        // tracks in this chunk
+            const int it = c0 + lane;
+            if (lane < cn && TRK(CN_TF_DQLEN, it) > 1.0) {  // ENV:678-680 popleft
+                TRK(CN_TF_D0X, it) = TRK(CN_TF_D1X, it); TRK(CN_TF_D0Y, it) = TRK(CN_TF_D1Y, it);
+                TRK(CN_TF_DQLEN, it) = 1.0;
+            }
+            // ENV:688-700 arg-max, tiled 8 tracks x 8 objects per pass exactly as in tracker_stage
+            int mybj = 0; bool mymatch = false;
+            for (int t0 = 0; t0 < cn; t0 += 8) {
+                const int ti = t0 + (lane >> 3);
+                double best = -1.0; int bj = 0x7fffffff;
+                if (ti < cn) {
+                    const double tx = TRK(CN_TF_PX, c0 + ti), ty_ = TRK(CN_TF_PY, c0 + ti);
+                    for (int oj = lane & 7; oj < nconf; oj += 8) {
+                        const double u = cn_iou3(tx, ty_, cfx_at<CMP>(L, oj), cfy_at<CMP>(L, oj), 0.0505, PY2);
+                        if (u > best) { best = u; bj = oj; }
+                    }
+                }
+#define CN_AM_STEP(CTRL) { const double ob = cn_dpp_d<CTRL, 0xf>(best, best); const int ojx = cn_dpp_i<CTRL, 0xf>(bj, bj); \
+                           if (ob > best || (ob == best && ojx < bj)) { best = ob; bj = ojx; } }
+                CN_AM_STEP(0xF5)      /* quad_perm [1,1,3,3] */
+                CN_AM_STEP(0xEE)      /* quad_perm [2,3,2,3] */
+                CN_AM_STEP(0x104)     /* row_shl:4 */
+#undef CN_AM_STEP
+                const u64 posm = __ballot(best > 0.0);
+                const int wb = __shfl(bj, (lane & 7) * 8, 64);
+                if ((lane >> 3) == (t0 >> 3)) { mybj = wb; mymatch = ((posm >> (8 * (lane & 7))) & 1ull) != 0ull; }
+            }
+            const u64 matchm = __ballot(mymatch && lane < cn);
+            u64 alive = 0ull;
+            for (int b = 0; b < cn; ++b) {                          // ENV:702-717, the order-dependent part (scalar, global index c0 + b)
+                if ((matchm >> b) & 1ull) alive |= (1ull << b);
+                else if (cur > c0 + b) cur -= 1;
+                else alive |= (1ull << b);
+            }
+            if (lane < cn && ((matchm >> lane) & 1ull)) {           // ENV:702-712
+                double cxj = cfx_at<CMP>(L, mybj), cyj = cfy_at<CMP>(L, mybj);
+                TRK(CN_TF_PX, it) = cxj; TRK(CN_TF_PY, it) = cyj; TRK(CN_TF_DIST, it) = cfd_at<CMP>(L, mybj);
+                if (TRK(CN_TF_DQLEN, it) < 1.5) { TRK(CN_TF_D1X, it) = cxj; TRK(CN_TF_D1Y, it) = cyj; TRK(CN_TF_DQLEN, it) = 2.0; }
+                TRK(CN_TF_T, it) = now - TRK(CN_TF_T, it);
+                chk_set<CMP>(L, mybj, 1);
+            }
+            // compact this chunk's survivors behind the earlier chunks' (order preserved): read all, sync, write
+            double rec[CN_TF_COUNT];
+            const bool mine = (lane < cn) && ((alive >> lane) & 1ull);
+            if (mine) {
+#pragma unroll
+                for (int f = 0; f < CN_TF_COUNT; ++f) rec[f] = TRK(f, it);
+            }
+            CN_WIDE_SYNC();
+            if (mine) {
+                const int slot = kept + __popcll(alive & ((1ull << lane) - 1ull));
+#pragma unroll
+                for (int f = 0; f < CN_TF_COUNT; ++f) TRK(f, slot) = rec[f];
+            }
+            kept += __popcll(alive);
+            CN_WIDE_SYNC();
+        }
+        e.ntracks = kept;
+        add_unchecked = true;  // ENV:723-743
+    }
+    CN_WIDE_SYNC();
+    if (add_unchecked) {
+        for (int j0 = 0; j0 < nconf; j0 += 64) {
+            int j = j0 + lane;
+            bool want = (j < nconf) && !chk_at<CMP>(L, j) && (cft_at<CMP>(L, j) == TY_O);
+            unsigned long long m = __ballot(want);
+            int slot = e.ntracks + __popcll(m & ((1ull << lane) - 1ull));
+            if (want && slot < L.tcap) {
+                double cxj = cfx_at<CMP>(L, j), cyj = cfy_at<CMP>(L, j);
+                TRK(CN_TF_PX, slot) = cxj; TRK(CN_TF_PY, slot) = cyj; TRK(CN_TF_DIST, slot) = cfd_at<CMP>(L, j);
+                TRK(CN_TF_D0X, slot) = cxj; TRK(CN_TF_D0Y, slot) = cyj; TRK(CN_TF_D1X, slot) = 0.0; TRK(CN_TF_D1Y, slot) = 0.0;
+                TRK(CN_TF_T, slot) = now; TRK(CN_TF_SPEED, slot) = -1.0;
+                TRK(CN_TF_VX, slot) = 0.0; TRK(CN_TF_VY, slot) = 0.0; TRK(CN_TF_DQLEN, slot) = 1.0;
+            }
+            int total = e.ntracks + __popcll(m);
+            if (total > CN_MAX_TRACKS) e.status |= CN_ST_TRACK_WIDE;
+            if (total > L.tcap) { e.status |= CN_ST_TRACK_OVERFLOW; total = L.tcap; }
+            e.ntracks = total;
+        }
+    }
+    CN_WIDE_SYNC();
+}
+
 template <bool CMP = false>
 __device__ __forceinline__ void tracker_stage(KP p, EnvRegs& e, const Lds& L, double* const T, int lane, int nconf, double now)
 {
+    constexpr bool WIDE = false;
     // ---- ENV:656-743 tracker -----------------------------------------------------------------------
     // The tracker table shares LDS with the end-point arrays (dead from here on): bring it in now.
     if (lane < e.ntracks) {
@@ -1160,13 +1281,14 @@ __device__ __forceinline__ void tracker_stage(KP p, EnvRegs& e, const Lds& L, do
     CN_SYNC();
 }
 
-template <bool EXT, bool GT = false, bool FAIR = false, bool CMP = false, bool X2 = false, bool SF = false, bool HOIST = true>
+template <bool EXT, bool GT = false, bool FAIR = false, bool CMP = false, bool X2 = false, bool SF = false, bool HOIST = true, bool WIDE = false>
 __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const Lds& L, int env, int lane, int step_counter,
                         float* obs32, float* fin32, double* obs64, int* done_out, bool have_tg = false, Trig tg = Trig{0.0, 0.0, 0.0, 0.0},
                         const int wv = 0, XMail* const mb = nullptr)
 {
     constexpr bool SFENCE = SF || (CMP && !FAIR);
     static_assert(!X2 || (!EXT && !GT), "two wavefronts per environment: simulated sensors, lidar-tracker mode");
+    static_assert(!WIDE || (!GT && !CMP && !X2), "the wide tracker table: lidar-tracker mode, plain layout, one wavefront");
     const bool w0 = !X2 || wv == 0;             // wave 0 (or the only wave): everything that is not split
     const int R = p->R, n = R - 1, K = p->K, D = n + 7 + 4 * K;
     const double MAXR = p->max_scan_range;
@@ -1306,7 +1428,8 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
 
     CN_T(5);
     int ego_hit = 0;
-    double* const T = L.trk;      // track / entry table: [CN_TF_COUNT][tcap], shares LDS with the end points
+    double* const T = WIDE ? L.gtrk : L.trk;      // track / entry table: [CN_TF_COUNT][tcap], shares LDS with the end points (WIDE: in HBM)
+    double* const CPV = WIDE ? L.gcpv : L.cpv;    // collision probability per entry
     if constexpr (!GT) {
     const int W = (n + 63) >> 6;  // 64-ray words; ray i = bit (i & 63) of word (i >> 6)
 #define WORD(id, q) L.w64[__mul24((id), L.wstride) + (q)]   /* 24-bit multiply: full rate (v_mul_lo_u32 is quarter rate) */
@@ -1801,7 +1924,8 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
     if (n_obst > 0) e.obst_steps += 1;
 
     CN_T(13);
-    tracker_stage<CMP>(p, e, L, T, lane, nconf, now);
+    if constexpr (WIDE) tracker_stage_wide(p, e, L, T, lane, nconf, now);
+    else tracker_stage<CMP>(p, e, L, T, lane, nconf, now);
     } else {
         // ---- risk_mode gt (SURVEY 7 "two risk-feature modes", include/crowdnav.h): rows A21-A24 fed with the simulator's own
         // pedestrians instead of tracked lidar blobs -- the north star's "K-nearest perceived-risk feature extraction".
@@ -1877,11 +2001,19 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
     }
     CN_T(14);
     // ENV:745-760 speed of the tracks matched in this call
+    if constexpr (WIDE) {
+        for (int it = lane; it < e.ntracks; it += 64) {         // (64 tracks per pass)
+            if (TRK(CN_TF_DQLEN, it) > 1.5) {
+                double dc = cn_hypot(TRK(CN_TF_D0Y, it) - TRK(CN_TF_D1Y, it), TRK(CN_TF_D0X, it) - TRK(CN_TF_D1X, it));
+                TRK(CN_TF_SPEED, it) = cn_div_z(dc, TRK(CN_TF_T, it));
+            }
+        }
+    } else
     if (lane < e.ntracks && TRK(CN_TF_DQLEN, lane) > 1.5) {
         double dc = cn_hypot(TRK(CN_TF_D0Y, lane) - TRK(CN_TF_D1Y, lane), TRK(CN_TF_D0X, lane) - TRK(CN_TF_D1X, lane));
         TRK(CN_TF_SPEED, lane) = cn_div_z(dc, TRK(CN_TF_T, lane));
     }
-    CN_SYNC();
+    CN_TSYNC();
 
     // default K x [px, py, 0, 0] (ENV:273)
     for (int i = lane; i < 4 * K; i += 64) {
@@ -1902,6 +2034,14 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         double agent_vel = cn_sqrt(vx_ * vx_ + vy_ * vy_);
         double obstacle_vel = (nt == 0) ? 0.0 : TRK(CN_TF_SPEED, 0);  // ENV:787-793
         // ENV:800-815: per-track velocity; the relative-motion end point of the LAST track survives
+        if constexpr (WIDE) {
+            for (int it = lane; it < nt; it += 64)
+                if (TRK(CN_TF_DQLEN, it) > 1.5) {
+                    double chx = TRK(CN_TF_D0X, it) - TRK(CN_TF_D1X, it), chy = TRK(CN_TF_D0Y, it) - TRK(CN_TF_D1Y, it);
+                    TRK(CN_TF_VX, it) = cn_div_z(chx, ts); TRK(CN_TF_VY, it) = cn_div_z(chy, ts);
+                }
+            CN_WIDE_SYNC();         // (lane (nt - 1) & 63 wrote the last track's velocity; every lane reads it below)
+        } else
         if (!GT && lane < nt && TRK(CN_TF_DQLEN, lane) > 1.5) {
             double chx = TRK(CN_TF_D0X, lane) - TRK(CN_TF_D1X, lane), chy = TRK(CN_TF_D0Y, lane) - TRK(CN_TF_D1Y, lane);
             TRK(CN_TF_VX, lane) = cn_div_z(chx, ts); TRK(CN_TF_VY, lane) = cn_div_z(chy, ts);
@@ -2006,7 +2146,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
                             cpv = 0.5 * ego + 0.5 * gcp;
                         }
                     } else { ego = 0.0; cpv = 0.5 * 0.0 + 0.5 * gcp; }
-                    L.cpv[i] = cpv;
+                    CPV[i] = cpv;
                 }
                 if (__ballot(ttc0) != 0ull) e.status |= CN_ST_TTC_ZERO;
                 // ENV: `if i == 0 or ego > ego_max: ego_max = ego`, folded left to right (a NaN is only ever kept as the first value)
@@ -2019,13 +2159,36 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
             CN_SYNC();
         }
         e.nent = nt;
-        CN_SYNC();
+        CN_TSYNC();
         // (both fields are written once, after the branch: a store in each arm gets merged into one store through a pointer phi,
         // which keeps the whole EnvRegs field pair on the stack)
         double cprob_new = 0.0, ego_new = 0.0;         // ENV:862-876: no tracks
         if (nt != 0) {  // ENV:878-905: stable descending sort, keep the LAST K
             ego_new = ego_max;
             int first = nt > K ? nt - K : 0;
+            if constexpr (WIDE) {
+                // the same ranks as below (the order is total: larger CP first, then the lower index), 64 entries per pass
+                for (int c0 = 0; c0 < nt; c0 += 64) {
+                    const int it = c0 + lane;
+                    int rank = -1; double mycp = 0.0;
+                    if (it < nt) {
+                        mycp = CPV[it];
+                        rank = 0;
+                        for (int j = 0; j < nt; ++j) {
+                            const double c = CPV[j];
+                            rank += (c > mycp) || (c == mycp && j < it);
+                        }
+                        if (rank >= first) {
+                            const int kk = rank - first;
+                            L.tail[7 + 4 * kk + 0] = TRK(CN_TF_PX, it); L.tail[7 + 4 * kk + 1] = TRK(CN_TF_PY, it);
+                            L.tail[7 + 4 * kk + 2] = TRK(CN_TF_VX, it); L.tail[7 + 4 * kk + 3] = TRK(CN_TF_VY, it);
+                            L.kidx[kk] = it;
+                        }
+                    }
+                    const u64 mf = __ballot(rank == first);
+                    if (mf) cprob_new = bcast_d(mycp, __ffsll((long long)mf) - 1);
+                }
+            } else {
             int rank = -1; double mycp = 0.0;
             if (lane < nt) mycp = L.cpv[lane];
             if (nt <= 8) {
@@ -2053,10 +2216,13 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
             }
             unsigned long long mf = __ballot(rank == first);
             cprob_new = bcast_d(mycp, __ffsll((long long)mf) - 1);
+            }
         }
         e.cprob = cprob_new; e.ego = ego_new;
         // ENV:990-996
         e.dq0x = e.dq1x; e.dq0y = e.dq1y; e.dq_len = 1;
+        if constexpr (WIDE) { for (int it = lane; it < nt; it += 64) TRK(CN_TF_T, it) = now; }
+        else
         if (!GT && lane < nt) TRK(CN_TF_T, lane) = now;
     }
     CN_T(16);
@@ -2084,7 +2250,8 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         if (o64) o64[n + i] = so;
     }
     CN_T(17);
-    // tracker table back to HBM (its LDS space is reused by the next observation's end points)
+    // tracker table back to HBM (its LDS space is reused by the next observation's end points; WIDE: it never left)
+    if constexpr (!WIDE)
     if (lane < e.ntracks) {
 #pragma unroll
         for (int f = 0; f < CN_TF_COUNT; f += 2)
@@ -2355,6 +2522,7 @@ __device__ __forceinline__ void observe_realworld(KP p, const Poly& pg, EnvRegs&
     for (int j = lane; j < nconf; j += 64) if (L.cft[j] == TY_O && L.cfd[j] < 0.140) ego_hit = 1;     // RW:702-706
     ego_hit = __ballot(ego_hit != 0) != 0ull;
     // ---- RW:478-589 tracker and speeds: the same block as ENV:656-760 -------------------------------------------------------------
+    constexpr bool WIDE = false;          // (TRK: the LDS table)
     double* const T = L.trk;
     tracker_stage(p, e, L, T, lane, nconf, now);
     if (lane < e.ntracks && TRK(CN_TF_DQLEN, lane) > 1.5) {
@@ -2555,11 +2723,15 @@ __device__ __forceinline__ double compute_reward(KP p, const Poly& pg, EnvRegs& 
 // blockIdx.x / threadIdx.x / the block's dynamic LDS; the multi-step kernel (FUSED, cn_env_kernel_seq below) calls this once per
 // step, `t` steps into its launch, with the step's actions / outputs at slot t of the caller's buffers.  `act_here`: this
 // environment's (v, w) where the policy kernel's actor left it (LDS) instead of the caller's action array.
-template <bool EXT, bool TWO, int LAYOUT, bool GT = false, int SIM = 0, bool FUSED = false, bool FAIR = false, int SHAPE = 0, bool X2 = false>
+template <bool EXT, bool TWO, int LAYOUT, bool GT = false, int SIM = 0, bool FUSED = false, bool FAIR = false, int SHAPE = 0, bool X2 = false,
+          bool WIDE = false>
 __device__ __forceinline__ void env_kernel_body(const int env, const int lane, char* const smem, const long long t = 0,
                                                 const float* const act_here = nullptr, const int wv = 0)
 {
     static_assert(!X2 || (!EXT && !TWO && LAYOUT == 0 && !GT && SIM == 0 && !FUSED), "two wavefronts per environment: the plain step kernel");
+    // WIDE (cn_config.track_capacity 128 ... 1024): the tracker / entry table stays in HBM (observe, tracker_stage_wide) -- region A
+    // holds the end points only -- and the CP of the entries goes to HBM too (p->trk past the N tables: [N][tcap] doubles)
+    static_assert(!WIDE || (LAYOUT == 0 && !GT && SIM == 0 && SHAPE == 0 && !X2), "the wide tracker table: generic bodies, plain simulator");
     // (round 6: the oldest-first 360-ray step kernels as well -- 26 scalar spills without the fences, see tools/kernel_resources.sh)
     constexpr bool SFENCE = (SHAPE == 720 || SHAPE == 360) && !FAIR && !FUSED;
     KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
@@ -2608,7 +2780,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         // LDS map.  Region A: end points (integer thousandths) | tracker table.
         // Region B: gradients + alias sources | bbox staging | confirmed objects, CP, observation tail.
         const size_t szA_pts = (size_t)((CMP ? 6 : 10) * n + 7) & ~(size_t)7;
-        const size_t szA_trk = 8 * (size_t)(CN_TF_COUNT * p->trk_cap);
+        const size_t szA_trk = WIDE ? 0 : 8 * (size_t)(CN_TF_COUNT * p->trk_cap);
         L.tcap = p->trk_cap;
         const size_t szA = szA_pts > szA_trk ? szA_pts : szA_trk;
         const size_t mc = (size_t)p->max_conf;
@@ -2644,6 +2816,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         L.nearp = p->near_sep ? (double*)Cw : (double*)B;   // ray loop only: region B is dead until the gradients are written
         if (p->near_sep) Cw += 32 * (size_t)(P + 1);
         L.gtrk = p->trk + (size_t)env * CN_TF_COUNT * p->trk_cap;
+        if constexpr (WIDE) L.gcpv = p->trk + (size_t)p->N * CN_TF_COUNT * p->trk_cap + (size_t)env * p->trk_cap;
         if constexpr (LAYOUT == 2) {   // the real-world layout's own lists: 12 bytes per ray (cn_lds_bytes adds them)
             char* Rw = (char*)(((size_t)Cw + 15) & ~(size_t)15);
             RQ.g = (int*)Rw; Rw += 4 * (size_t)n;
@@ -2870,7 +3043,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         if (ph_obs) {
             if constexpr (LAYOUT == 1) observe_original<EXT>(p, e, L, env, lane, sc, io_obs(), fin, p->obs_f64, &done);
             else if constexpr (LAYOUT == 2) observe_realworld<EXT>(p, pg, e, L, RQ, env, lane, sc, io_obs(), fin, p->obs_f64, &done);
-            else observe<EXT, GT, FAIR, CMP, X2, SFENCE, !(FUSED && SHAPE == 720)>(p, pg, e, L, env, lane, sc, io_obs(), fin, p->obs_f64, &done, have_trig, trig, 0, mb);
+            else observe<EXT, GT, FAIR, CMP, X2, SFENCE, !(FUSED && SHAPE == 720), WIDE>(p, pg, e, L, env, lane, sc, io_obs(), fin, p->obs_f64, &done, have_trig, trig, 0, mb);
         } else if constexpr (EXT) {
             // Env.compute_reward(state, step_counter, done) on its own (ENV:1046): heading and distance are state[n], state[n+1]
             // (LAYOUT 1: state[-2], state[-1] are what ORIG:324-330 reads), `done` is the caller's
@@ -2980,7 +3153,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
             cold_settle();
             r = compute_reward_realworld(p, e, L, done);
         } else {
-            observe<EXT, GT, FAIR>(p, pg, e, L, env, lane, sc, p->obs, ext ? nullptr : p->final_obs, p->obs_f64, &done);
+            observe<EXT, GT, FAIR, false, false, false, true, WIDE>(p, pg, e, L, env, lane, sc, p->obs, ext ? nullptr : p->final_obs, p->obs_f64, &done);
             cold_settle();
             r = compute_reward(p, pg, e, L, lane, done);
         }
@@ -3031,7 +3204,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         e.prev_dist = dist3(e.rx, e.ry, e.wpx, e.wpy);        // ENV:1243 (unrounded)
         e.prev_head = heading_to_goal(p, e, e.rx, e.ry, e.ryaw);  // ENV:1244
         CN_SYNC();
-        observe<EXT, GT, FAIR>(p, pg, e, L, env, lane, 0, p->obs, nullptr, p->obs_f64, &d2);
+        observe<EXT, GT, FAIR, false, false, false, true, WIDE>(p, pg, e, L, env, lane, 0, p->obs, nullptr, p->obs_f64, &d2);
         }
         cold_settle();
         e.social_viol = 0; e.ego_viol = 0; e.obst_steps = 0;  // ENV:1260-1262
@@ -3111,6 +3284,11 @@ extern "C" __global__ void CN_S720_BOUNDS cn_env_kernel_s720(CnKParams p) { exte
 extern "C" __global__ void CN_S720_BOUNDS cn_env_kernel_fair_s720(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, true, 720>(blockIdx.x, threadIdx.x, cn_smem); }
 extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0>(blockIdx.x, threadIdx.x, cn_smem); }
 extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_ext(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<true, false, 0>(blockIdx.x, threadIdx.x, cn_smem); }
+// the wide tracker table (cn_config.track_capacity 128 ... 1024, in HBM): the generic bodies above with WIDE -- both auto-reset
+// conventions and the external-sensor flow
+extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_wide(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, false, 0, false, true>(blockIdx.x, threadIdx.x, cn_smem); }
+extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_wide_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, false, 0, false, false, 0, false, true>(blockIdx.x, threadIdx.x, cn_smem); }
+extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_wide_ext(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<true, false, 0, false, 0, false, false, 0, false, true>(blockIdx.x, threadIdx.x, cn_smem); }
 #endif
 #if !defined(CN_TU) || CN_TU == 2 || CN_TU == 3 || CN_TU == 5
 // cn_step_sequence: T control periods per launch with OPEN-LOOP actions (resident in HBM: [T][N][2], or one [N][2] held for T
@@ -3119,7 +3297,7 @@ extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_ext(CnKParams p) 
 // step -- and after a few steps the wavefronts of a SIMD are out of phase (they stop contending for the same unit at the same
 // time), which is what one launch per step can never be.  Each step is exactly cn_env_kernel's (next-step reset convention) and
 // writes its observation / reward / done / indices to slot t of the caller's buffers (stride 0: in place).
-template <bool GT, int SHAPE = 0, int SIM = 0, int LAYOUT = 0>
+template <bool GT, int SHAPE = 0, int SIM = 0, int LAYOUT = 0, bool WIDE = false>
 __device__ __forceinline__ void sequence_body()
 {
     extern __shared__ __attribute__((aligned(16))) char cn_smem[];
@@ -3131,7 +3309,7 @@ __device__ __forceinline__ void sequence_body()
         asm volatile("" : "+v"(lane_));          // per-step laundering (see env_kernel_body): nothing is hoisted out of the step loop
         lane_ &= 63;
         cn_setprio_uniform((int)(t + wslot) & 3);      // see "issue arbitration" at the top: every slot gets every level in turn
-        env_kernel_body<false, false, LAYOUT, GT, SIM, true, false, SHAPE>(blockIdx.x, lane_, cn_smem, t);
+        env_kernel_body<false, false, LAYOUT, GT, SIM, true, false, SHAPE, false, WIDE>(blockIdx.x, lane_, cn_smem, t);
     }
 }
 #endif
@@ -3140,6 +3318,7 @@ extern "C" __global__ void CN_HOT_BOUNDS cn_env_kernel_seq(CnKParams p) { sequen
 extern "C" __global__ void CN_HOT_BOUNDS cn_env_kernel_seq_s360(CnKParams p) { sequence_body<false, 360>(); }
 extern "C" __global__ void CN_S720_BOUNDS cn_env_kernel_seq_s720(CnKParams p) { sequence_body<false, 720>(); }
 extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_seq(CnKParams p) { sequence_body<true>(); }
+extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_seq_wide(CnKParams p) { sequence_body<false, 0, 0, 0, true>(); }   // the wide tracker table
 #endif
 #if !defined(CN_TU) || CN_TU == 3
 // round 5: the same persistent-wavefront form for the other simulators (SIM 2 / 4: social-force pedestrians, pair matrix / dense;
@@ -3525,7 +3704,7 @@ extern "C" __global__ void __launch_bounds__(ACT_THREADS) cn_actor_kernel(const 
 #ifndef POL_FAIR
 #define POL_FAIR 1            /* experiments: 0 = the sequence kernel's rotating levels instead of the falling ones */
 #endif
-template <int SHAPE, bool GT = false, int SIM = 0, int LAYOUT = 0>
+template <int SHAPE, bool GT = false, int SIM = 0, int LAYOUT = 0, bool WIDE = false>
 __device__ __forceinline__ void policy_sequence_body()
 {
     extern __shared__ __attribute__((aligned(16))) char cn_smem[];
@@ -3565,7 +3744,7 @@ __device__ __forceinline__ void policy_sequence_body()
 #if POL_FAIR == 0
             cn_setprio_uniform((t + (int)__builtin_amdgcn_s_getreg(4 | (1 << 11))) & 3);
 #endif
-            env_kernel_body<false, false, LAYOUT, GT, SIM, true, POL_FAIR != 0 && LAYOUT == 0, SHAPE>(env, lane_, cn_smem + (size_t)wave * ws, t, act_lds + 2 * wave);
+            env_kernel_body<false, false, LAYOUT, GT, SIM, true, POL_FAIR != 0 && LAYOUT == 0, SHAPE, false, WIDE>(env, lane_, cn_smem + (size_t)wave * ws, t, act_lds + 2 * wave);
         }
         POL_T(3);
         __syncthreads();
@@ -3577,6 +3756,7 @@ __device__ __forceinline__ void policy_sequence_body()
 extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel(CnKParams p) { policy_sequence_body<0>(); }
 extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_s360(CnKParams p) { policy_sequence_body<360>(); }
 extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_gt(CnKParams p) { policy_sequence_body<0, true>(); }   // risk_mode gt
+extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_wide(CnKParams p) { policy_sequence_body<0, false, 0, 0, true>(); }   // the wide tracker table
 #endif
 #if !defined(CN_TU) || CN_TU == 4
 extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_s720(CnKParams p) { policy_sequence_body<720>(); }      // BASELINE configs[4]: 8 per workgroup

@@ -27,7 +27,8 @@ extern "C" {
 #endif
 
 #define CN_ABI_VERSION 7
-#define CN_MAX_TRACKS 64      /* largest per-env capacity of the obstacle tracker (ENV:656-743): one lane per track */
+#define CN_MAX_TRACKS 64      /* largest per-env capacity of the LDS tracker table (ENV:656-743): one lane per track */
+#define CN_MAX_TRACKS_WIDE 1024   /* largest per-env capacity of the wide (HBM) tracker table: track_capacity 128 ... 1024 */
 #define CN_MAX_K 16
 
 enum {
@@ -39,8 +40,15 @@ enum {
     CN_ERR_SIZE = -5
 };
 
-/* per-env status bits (cn_get_counters column 6) */
-enum { CN_ST_TRACK_OVERFLOW = 1, CN_ST_TTC_ZERO = 2, CN_ST_DT_ZERO = 4, CN_ST_CONF_OVERFLOW = 8 };
+/* per-env status bits (cn_get_counters column 6), all sticky:
+ *   CN_ST_TRACK_OVERFLOW  the track list outgrew track_capacity; the tracks that did not fit were dropped (risk features from a
+ *                         truncated list from then on)
+ *   CN_ST_TTC_ZERO        a time-to-collision of exactly 0 was met
+ *   CN_ST_DT_ZERO         the agent's time step was exactly 0 (UTL:227-236 divide by it)
+ *   CN_ST_CONF_OVERFLOW   the confirmed-object table overflowed
+ *   CN_ST_TRACK_WIDE      informational: the track list has once held more than CN_MAX_TRACKS (64) tracks -- only a wide table
+ *                         (track_capacity >= 128) keeps them; past this point a 64-slot tracker would have overflowed */
+enum { CN_ST_TRACK_OVERFLOW = 1, CN_ST_TTC_ZERO = 2, CN_ST_DT_ZERO = 4, CN_ST_CONF_OVERFLOW = 8, CN_ST_TRACK_WIDE = 16 };
 
 /* Every field of Env.__init__'s rosparam reads (ENV:71-91), the robot/lidar constants of the
  * URDF/XACRO and world files, and the crowd node's constants.  SURVEY.md appendix B cites each. */
@@ -63,7 +71,11 @@ typedef struct cn_config {
     int32_t settle_ms;       /* trainer's time.sleep(0.1) after reset (TRAIN:114) -> 100 */
     int32_t ped_cycle_ms;    /* crowd node cycle: 0.1 s x number of obstacles (CROWD:128-144) */
     int32_t ped_stagger_ms;  /* 0.1 s between consecutive obstacles' updates (CROWD:144) -> 100 */
-    int32_t track_capacity;  /* tracker slots per env: 0 = auto (32 for <= 40 pedestrians -- <= 32 with risk_mode gt --, else 64), or 32 / 64 */
+    int32_t track_capacity;  /* tracker slots per env: 0 = auto (32 for <= 40 pedestrians -- <= 32 with risk_mode gt --, else 64), or 32 / 64
+                              * (the table lives in LDS), or 128 / 256 / 512 / 1024: a WIDE table, used in place in HBM, for long runs
+                              * whose track list (the reference's is unbounded and survives reset) outgrows 64 -- opt-in, slower, and
+                              * only for obs_layout 0 with risk_mode lidar_tracker and the plain simulator (ped_mode 0 / 1, no
+                              * ped_contact, no wheel_accel); cn_create refuses it elsewhere and names why */
     int32_t obs_layout;      /* CN_LAYOUT_RISK (0): environment_stage_1_nobonus.py, obs = R-1 + 7 + 4K (TD3 / DDPG trainers);
                               * CN_LAYOUT_ORIGINAL (1): environment_stage_1_original.py:278-402, obs = R-1 + 4 =
                               * rounded ranges + heading + distance + rounded (x, y) (SAC / DQN / Q-learning trainers);
@@ -409,7 +421,7 @@ int cn_get_returns(cn_handle h, float* last_return, float* running_return, void*
 
 /* Parity/debug view of one env (synchronises).  host buffers, any may be NULL:
  *   scalars[24] (layout: CN_SD_* below), robot_ped (5 + 4P doubles: x,y,yaw,v,w, ped xy, ped vxy),
- *   tracks [CN_MAX_TRACKS][12] one record per slot (CN_TF_*; the first track_capacity slots are used), ints[16] */
+ *   tracks [track_capacity][12] one record per slot (CN_TF_*; the first n_tracks slots are live), ints[16] */
 int cn_debug_env(cn_handle h, int env, double* scalars, double* robot_ped, double* tracks, int32_t* ints);
 
 /* Sizing diagnostics (no handle, no GPU): LDS bytes one env of obs_layout 0 needs for n_rays / n_peds / k with max_conf

@@ -59,6 +59,11 @@ def draw(rng):
         kw.update(n_peds=100 if dense else 20, n_rays=720 if dense else 360, k_obstacles=8, obs_layout=0, risk_mode=0, ped_mode=0, ped_contact=0,
                   wheel_accel=0.0, sf_tick_ms=0, track_capacity=0, room_half=float(rng.uniform(2.0, 3.2)) if dense else float(rng.uniform(1.0, 3.0)),
                   n_envs=int(rng.choice([1, 17, 64, 300, 1000, 2100, 4100] if not dense else [1, 17, 64, 300, 1000])))
+    if (kw["obs_layout"] == 0 and kw["risk_mode"] == 0 and kw["ped_mode"] != 2 and not kw["ped_contact"] and kw["wheel_accel"] == 0.0
+            and kw["n_peds"] > 0 and rng.random() < 0.3):
+        # the wide tracker table (track_capacity 128 ... 1024, in HBM): every env the ORACLE did not flag is compared, those past the
+        # 32 / 64 slots of the LDS table included
+        kw.update(track_capacity=int(rng.choice([128, 256, 512, 1024])))
     form = str(rng.choice(["step", "step", "sequence", "policy", "manual"]))
     mode = "next" if form != "step" else str(rng.choice(["next", "same"]))
     return kw, form, mode
@@ -72,6 +77,9 @@ def diff(tag, g, c):
     e = int(badm[0][0]); cols = np.nonzero(np.atleast_1d(g[e] != c[e]))[0]
     print("   %s: %d entries in %d env(s) differ; env %d cols %s\n      gpu %s\n      cpu %s"
           % (tag, len(badm), len(set(badm[:, 0])), e, cols[:16], np.atleast_1d(g[e])[cols[:8]], np.atleast_1d(c[e])[cols[:8]]))
+
+
+WIDE_STATS = dict(worlds=0, envs_past_lds=0)    # wide-table worlds run; their envs compared equal with more tracks than the LDS table holds
 
 
 def run_world(kw, form, mode, T, detail=False, as_steps=False):
@@ -92,6 +100,13 @@ def run_world(kw, form, mode, T, detail=False, as_steps=False):
     kn = env.kernel_name(what)
     env.reset(); torch.cuda.synchronize()
     bad, skipped, bad_envs = [], None, set()
+    wide = env.track_capacity > 64
+    lds_cap = 32 if (cfg.n_peds <= 40 and cfg.risk_mode == 0) else 64     # what the auto capacity would have been
+    peak = np.zeros(N, dtype=np.int64)
+
+    def track_peak():
+        if wide:
+            np.maximum(peak, env.counters().cpu().numpy()[:, 7], out=peak)
 
     def check(tag, g, c):
         if not np.array_equal(g, c):
@@ -114,6 +129,7 @@ def run_world(kw, form, mode, T, detail=False, as_steps=False):
             check("reward @%d" % t, env.reward.cpu().numpy(), rc.astype(np.float32))
             check("done @%d" % t, env.done.cpu().numpy(), dc)
             check("idx @%d" % t, env.topk_idx.cpu().numpy(), ic)
+            track_peak()
             if bad:
                 break
     elif form == "manual":
@@ -128,6 +144,7 @@ def run_world(kw, form, mode, T, detail=False, as_steps=False):
             check("reward @%d" % t, env.reward.cpu().numpy(), rc.astype(np.float32))
             check("done @%d" % t, env.done.cpu().numpy(), dc)
             check("idx @%d" % t, env.topk_idx.cpu().numpy(), ic)
+            track_peak()
             if bad:
                 break
             mask = (dc != 0) | (rng.random(N) < 0.02)
@@ -180,6 +197,7 @@ def run_world(kw, form, mode, T, detail=False, as_steps=False):
                 else:
                     env.bind_step_sequence(traj["action"], traj={k: traj[k] for k in ("obs", "reward", "done")})()
             torch.cuda.synchronize()
+            track_peak()
             A = traj["action"].cpu().numpy(); O = traj["obs"].cpu().numpy(); Rw = traj["reward"].cpu().numpy(); Dn = traj["done"].cpu().numpy()
             for t in range(Tc):
                 oc, rc, dc, ic = orc.step(A[t].astype(np.float64), auto_reset="next")
@@ -204,13 +222,19 @@ def run_world(kw, form, mode, T, detail=False, as_steps=False):
         # track_capacity (32 / 64) tracks and max_conf objects and RAISE A STATUS BIT when a world outgrows them (CN_ST_TRACK_OVERFLOW 1,
         # CN_ST_CONF_OVERFLOW 8, include/crowdnav.h).  A difference in an environment whose status carries one of the two is that
         # documented limit, not a disagreement about the arithmetic.
+        # A wide table (track_capacity 128 ... 1024) keeps the tracks past 64 the oracle (64 slots) drops: CN_ST_TRACK_WIDE (16) marks
+        # the envs where the ORACLE is no longer the reference.
         st = env.counters().cpu().numpy()[:, 6].astype(np.int64)
-        flagged = [e for e in sorted(bad_envs) if st[e] & 9]
+        flagged = [e for e in sorted(bad_envs) if st[e] & 25]
         if bad_envs and len(flagged) == len(bad_envs):
             skipped = "overflow"
         if detail:
             print("   differing envs %s; status words %s (1 = track table full, 8 = confirmed-object table full); tracks %s"
                   % (sorted(bad_envs)[:8], [int(st[e]) for e in sorted(bad_envs)[:8]], [int(x) for x in env.counters().cpu().numpy()[sorted(bad_envs)[:8], 7]]))
+    if wide and not skipped:
+        WIDE_STATS["worlds"] += 1
+        ost = np.array([orc.get_state(e)["si"][9] for e in range(N)])
+        WIDE_STATS["envs_past_lds"] += int(sum(1 for e in range(N) if peak[e] > lds_cap and not (ost[e] & 1) and e not in bad_envs))
     env.close()
     return bad, kn, skipped
 
@@ -275,6 +299,8 @@ def main():
             print("  bad world %d: %s %s %s %s | --form %s --mode %s --steps %d --repro \"%r\"" % (n_bad, form, mode, kn, bad[:3], form, mode, steps, kw))
     print("fuzz_parity: seed %d, %.0f s: %d worlds (%d more refused by cn_create), %d env-steps compared, %d world(s) with a difference; %d more outgrew the track / confirmed-object tables (status bit raised); cn_rollout_policy refused %d shape(s) for LDS"
           % (a.seed, a.seconds, n_trials, n_refused, env_steps, n_bad, n_overflow, n_form_refused))
+    print("  wide track tables: %d world(s); %d env(s) with more tracks than the LDS table holds compared equal past the LDS table"
+          % (WIDE_STATS["worlds"], WIDE_STATS["envs_past_lds"]))
     print("  launch forms:", dict(sorted(forms.items())))
     print("  kernels exercised (%d):" % len(kernels), dict(sorted(kernels.items(), key=lambda kv: -kv[1])))
     sys.exit(1 if n_bad else 0)
