@@ -72,6 +72,7 @@ typedef struct {
     int ntracks;
     double ego_score_cp;
     double collision_prob;
+    int cp_pow_sq;      /* the CP scalars above come from an agent speed where the C library's pow(v, 2) != v * v (see agent_speed) */
     double entry_cp[CNO_MAX_TRACKS];   /* debug: CP of every entry before the top-K cut (ENV:818-860) */
     double entry_ego[CNO_MAX_TRACKS];
     int ego_viol, social_viol, obst_steps;
@@ -809,6 +810,17 @@ int cno_topk(const double* cp, int n, int K, int32_t* idx_out)
  * Env.get_state (ENV:245-1044)
  * ---------------------------------------------------------------------------------------- */
 
+/* UTL:227-236 the agent's speed, sqrt(math.pow(vx, 2) + math.pow(vy, 2)).  The C library's pow is not correctly rounded: for a
+ * square within about 0.008 ulp of a rounding midpoint it can round the other way than v * v (vx = -0.44666666666666566 of the
+ * py2tie golden, 1.5000000000000007, ...).  The device squares with v * v, correctly rounded; *pow_sq records whether the two
+ * differ here, so a comparison can name the one place where the device's collision-probability scalars may differ from these. */
+static double agent_speed(double vx_, double vy_, int* pow_sq)
+{
+    double sx = pow(vx_, 2), sy = pow(vy_, 2);
+    *pow_sq = (sx != vx_ * vx_) || (sy != vy_ * vy_);
+    return sqrt(sx + sy);
+}
+
 static double heading_to_goal(const cno_config* c, const env_t* e, double px, double py, double yaw)
 {
     /* ENV:222-237: adds starting_point to the position (ENV:191-209 does not) */
@@ -1188,7 +1200,7 @@ static void env_get_state(const cno_sim* s, env_t* e, const double* ranges, doub
         /* UTL:227-236 */
         double vx_ = (e->agent_dq[1].x - e->agent_dq[0].x) / ts;
         double vy_ = (e->agent_dq[1].y - e->agent_dq[0].y) / ts;
-        double agent_vel = sqrt(pow(vx_, 2) + pow(vy_, 2));
+        double agent_vel = agent_speed(vx_, vy_, &e->cp_pow_sq);
         double obstacle_vel = (e->ntracks == 0) ? 0.0 : e->tracks[0].speed; /* ENV:787-793 */
         double vo_x = e->agent_dq[1].x, vo_y = e->agent_dq[1].y;
         for (int i = 0; i < e->ntracks; ++i) { /* ENV:800-815: the last track's value survives */
@@ -1558,7 +1570,7 @@ static void rw_get_state(const cno_sim* s, env_t* e, const double* ranges, doubl
         double ts = e->agent_vel_timestep;
         if (ts == 0.0) e->status |= ST_DT_ZERO;
         double vx_ = (e->agent_dq[1].x - e->agent_dq[0].x) / ts, vy_ = (e->agent_dq[1].y - e->agent_dq[0].y) / ts;
-        double agent_vel = sqrt(pow(vx_, 2) + pow(vy_, 2));
+        double agent_vel = agent_speed(vx_, vy_, &e->cp_pow_sq);
         double obstacle_vel = (e->ntracks == 0) ? 0.0 : e->tracks[0].speed;
         double vo_x = e->agent_dq[1].x, vo_y = e->agent_dq[1].y;
         for (int i = 0; i < e->ntracks; ++i) {
@@ -1665,6 +1677,7 @@ static void env_init(const cno_sim* s, env_t* e)
     e->agent_dq_len = 0; e->agent_vel_timestep = 0.0;
     e->bb = (c->obs_layout == 2) ? 0.0210 : 0.0;                  /* RW:103 */
     e->ntracks = 0;
+    e->cp_pow_sq = 0;
     e->ego_score_cp = 0.0; e->collision_prob = (c->obs_layout == 2) ? -INFINITY : 0.0;   /* RW:80 None: compares below any number in Python 2 */
     e->ego_viol = e->social_viol = e->obst_steps = 0;
     e->ep_success = e->ep_failure = 0;
@@ -1932,6 +1945,8 @@ int cno_get_sim_state(const cno_sim* s, int env, double* robot5, double* ped_p, 
     return 0;
 }
 
+int cno_get_cp_pow_sq(const cno_sim* s, int env) { return s->envs[env].cp_pow_sq; }
+
 int cno_get_debug(const cno_sim* s, int env, cno_debug* o)
 {
     const env_t* e = &s->envs[env];
@@ -2092,6 +2107,7 @@ int cno_set_state(cno_sim* s, int env, const double* sd, const int32_t* si, cons
         e->prev_dist = sd[SD_PREV_DIST]; e->prev_head = sd[SD_PREV_HEAD];
         e->agent_dq[0].x = sd[SD_DQ0X]; e->agent_dq[0].y = sd[SD_DQ0Y]; e->agent_dq[1].x = sd[SD_DQ1X]; e->agent_dq[1].y = sd[SD_DQ1Y];
         e->agent_vel_timestep = sd[SD_TS]; e->bb = sd[SD_BB]; e->ego_score_cp = sd[SD_EGO]; e->collision_prob = sd[SD_CPROB];
+        e->cp_pow_sq = 0;
         e->ep_return = sd[SD_EP_RETURN]; e->last_return = sd[SD_LAST_RETURN];
         e->last_ego_viol = (int)sd[SD_LAST_EGO_VIOL]; e->last_social_viol = (int)sd[SD_LAST_SOCIAL_VIOL];
         e->last_obst_steps = (int)sd[SD_LAST_OBST_STEPS]; e->last_ep_steps = (int)sd[SD_LAST_EP_STEPS];

@@ -113,6 +113,8 @@ int  cno_get_counters(const cno_sim* s, int32_t* out /* [N,6] ego,social,obst_st
 int  cno_get_returns(const cno_sim* s, double* out /* [N] return of the last finished episode */);
 int  cno_get_sim_state(const cno_sim* s, int env, double* robot5, double* ped_p, double* ped_v, double* ranges);
 int  cno_get_debug(const cno_sim* s, int env, cno_debug* out);
+/* 1 when the env's CP scalars come from an agent speed where the C library's pow(v, 2) differs from v * v (cn_oracle.c agent_speed) */
+int  cno_get_cp_pow_sq(const cno_sim* s, int env);
 int  cno_set_num_threads(int n);
 
 /* Externally driven path (golden replay): the caller supplies what Gazebo supplied. */

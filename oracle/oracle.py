@@ -100,6 +100,7 @@ def lib():
         dp = C.POINTER(C.c_double)
         L.cno_create.argtypes = [C.POINTER(CnoConfig), C.POINTER(C.c_void_p)]
         L.cno_destroy.argtypes = [C.c_void_p]
+        L.cno_get_cp_pow_sq.argtypes = [C.c_void_p, C.c_int]
         L.cno_obs_dim.argtypes = [C.c_void_p]
         L.cno_set_ped_init.argtypes = [C.c_void_p, dp]
         L.cno_get_ped_init.argtypes = [C.c_void_p, dp]
@@ -253,7 +254,8 @@ class Oracle:
         sd = np.zeros(24); si = np.zeros(16, dtype=np.int32); pp = np.zeros((self.P, 2)); pv = np.zeros((self.P, 2))
         trk = np.zeros((trk_cap, 12)); aux = np.zeros((self.P, 3))
         self.L.cno_get_state(self.h, int(env), _dp(sd), si.ctypes.data, _dp(pp), _dp(pv), _dp(trk), int(trk_cap), _dp(aux))
-        return dict(sd=sd, si=si, ped_p=pp, ped_v=pv, trk=trk, ped_aux=aux)
+        # cp_pow_sq: the CP scalars come from an agent speed where the C library's pow(v, 2) != v * v (cn_oracle.c agent_speed)
+        return dict(sd=sd, si=si, ped_p=pp, ped_v=pv, trk=trk, ped_aux=aux, cp_pow_sq=int(self.L.cno_get_cp_pow_sq(self.h, int(env))))
 
     # ---- harness-facing simulator access -------------------------------------------------
     def hsim_reset(self, env=0):

@@ -6,8 +6,8 @@
              (two processes sharing cuda:0, gloo) against one handle
   config 5   4096 envs x 100 pedestrians x 720 rays (dense crowd, the LDS-pressure case)
 
-Envs are independent, so the oracle needs < 1 s per config here (OpenMP over envs).  Bar: done flags and top-K
-indices bit-exact, observation / reward within 1e-5 (north_star); in practice everything is equal."""
+Envs are independent, so the oracle needs < 1 s per config here (OpenMP over envs).  Bar: equality -- done flags, top-K
+indices, observations, rewards, returns and counters equal the oracle's (float32 outputs: its float64 values cast to float32)."""
 import os
 import sys
 
@@ -17,7 +17,6 @@ import pytest
 from conftest import PKG, ROOT, load_seq
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
 
 
 @pytest.fixture(autouse=True)
@@ -46,9 +45,9 @@ def test_config2_full_size_4096_envs(oracle_mod):
         oc, rc, dc, ic, fc = orc.step(act.numpy().astype(np.float64), auto_reset=mode, want_final=True)
         assert np.array_equal(env.done.cpu().numpy(), dc), t                      # bit-exact
         assert np.array_equal(env.topk_idx.cpu().numpy(), ic), t                  # bit-exact
-        assert np.abs(env.reward.cpu().numpy() - rc).max() <= TOL, t
+        assert np.array_equal(env.reward.cpu().numpy(), rc.astype(np.float32)), t
         og = env.obs_f64.cpu().numpy()
-        assert np.abs(og - oc).max() <= TOL, t
+        assert np.array_equal(og, oc), t
         assert np.array_equal(env.obs.cpu().numpy(), oc.astype(np.float32)), t
         exact += int((og == oc).all(1).sum()); n_done += int(dc.sum())
     assert np.array_equal(env.counters().cpu().numpy()[:, :6], orc.counters())
@@ -77,9 +76,9 @@ def test_config5_full_size_dense_crowd_4096_envs(oracle_mod):
         oc, rc, dc, ic, fc = orc.step(act.numpy().astype(np.float64), auto_reset=mode, want_final=True)
         assert np.array_equal(env.done.cpu().numpy(), dc), t
         assert np.array_equal(env.topk_idx.cpu().numpy(), ic), t
-        assert np.abs(env.reward.cpu().numpy() - rc).max() <= TOL, t
+        assert np.array_equal(env.reward.cpu().numpy(), rc.astype(np.float32)), t
         og = env.obs_f64.cpu().numpy()
-        assert np.abs(og - oc).max() <= TOL, t
+        assert np.array_equal(og, oc), t
         exact += int((og == oc).all(1).sum()); n_done += int(dc.sum())
     assert np.array_equal(env.counters().cpu().numpy()[:, :6], orc.counters())
     assert (env.counters().cpu().numpy()[:, 6] == 0).all()          # status: no track / segment overflow in the dense crowd
@@ -118,8 +117,8 @@ def test_config3_actor_in_the_loop_4096_envs(oracle_mod, sigma):
         oc, rc, dc, ic = orc.step(act.astype(np.float64), auto_reset="next")
         assert np.array_equal(envs.done.cpu().numpy(), dc), t
         assert np.array_equal(envs.topk_idx.cpu().numpy(), ic), t
-        assert np.abs(envs.reward.cpu().numpy() - rc).max() <= TOL, t
-        assert np.abs(envs.obs.cpu().numpy().astype(np.float64) - oc).max() <= TOL, t
+        assert np.array_equal(envs.reward.cpu().numpy(), rc.astype(np.float32)), t
+        assert np.array_equal(envs.obs.cpu().numpy(), oc.astype(np.float32)), t
         n_done += int(dc.sum()); acts_seen.append(act[:64].copy())
     assert n_done > N
     a = np.stack(acts_seen)
@@ -545,7 +544,7 @@ def test_config4_full_workload_16384_envs_as_8_shards(oracle_mod):
         dg = torch.cat([e.done for e in shards]).cpu().numpy()
         assert np.array_equal(dg, dc), t                                                       # bit-exact
         assert np.array_equal(torch.cat([e.topk_idx for e in shards]).cpu().numpy(), ic), t    # bit-exact
-        assert np.abs(torch.cat([e.reward for e in shards]).cpu().numpy() - rc).max() <= TOL, t
+        assert np.array_equal(torch.cat([e.reward for e in shards]).cpu().numpy(), rc.astype(np.float32)), t
         og = torch.cat([e.obs for e in shards])
         assert np.array_equal(og.cpu().numpy(), oc.astype(np.float32)), t
         assert torch.equal(og, one.obs) and torch.equal(torch.cat([e.done for e in shards]), one.done), t
@@ -556,7 +555,7 @@ def test_config4_full_workload_16384_envs_as_8_shards(oracle_mod):
     torch.cuda.synchronize()
     ret = torch.cat(rets)
     assert torch.equal(ret, one.returns()[0])
-    assert np.abs(ret.cpu().numpy() - orc.returns()).max() <= 1e-3
+    assert np.array_equal(ret.cpu().numpy(), orc.returns().astype(np.float32))
     assert np.array_equal(torch.cat(cnts).cpu().numpy()[:, :6], orc.counters())
 
 
@@ -1079,7 +1078,6 @@ def test_env_wrapper_get_state_and_compute_reward_replay_the_reference_run():
 
     z, kw = load_seq("train20")
     env = Env(action_dim=2, max_step=int(kw.pop("max_steps")), **kw)
-    n_exact = 0
     for i in range(len(z["now"])):
         env.odom_callback(z["px"][i], z["py"][i], z["yaw"][i], z["v"][i], z["w"][i], now=z["now"][i])
         if z["is_reset"][i]:
@@ -1098,8 +1096,7 @@ def test_env_wrapper_get_state_and_compute_reward_replay_the_reference_run():
             assert isinstance(reward, float) and reward == z["reward"][i], (i, reward, z["reward"][i])
             assert done == bool(z["done"][i]), i
             state = np.asarray(state)
-        assert np.abs(state - z["obs"][i]).max() <= TOL, i
-        n_exact += int(np.array_equal(state, z["obs"][i]))
+        assert np.array_equal(state, z["obs"][i]), (i, np.nonzero(state != z["obs"][i])[0][:8])
         c = env._v.counters()[0].cpu().tolist()
         assert tuple(c[:3]) == tuple(int(x) for x in z["counters"][i]), i
-    assert n_exact >= 0.995 * len(z["now"])
+

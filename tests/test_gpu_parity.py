@@ -1,18 +1,43 @@
 """Parity tests proper: the HIP path (libcrowdnav.so through the C-ABI) against the CPU oracle on the
 same seeded inputs, and against the golden runs the REFERENCE's own Python produced.
 
-Bar (BASELINE.json north_star): obstacle indices and done flags bit-exact; float scan / reward within
-1e-5.  The simulator half (pedestrians, diff-drive, lidar) is bit-reproducible by construction
-(explicit fma, deterministic sincos), so in practice every observation value matches exactly."""
+Bar: equality.  Observations, rewards, done flags, top-K indices, returns and counters equal the oracle's (the float32
+outputs its float64 values cast to float32), and the whole state record of every env passes
+tools/bisect_divergence.py::first_state_difference (equality; its docstring names the two C-library exceptions) after every step.  The simulator
+half (pedestrians, diff-drive, lidar) is bit-reproducible by construction (explicit fma, deterministic sincos); the tracker
+and CP half uses device restatements of the same libm functions (cn_hypot)."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
-from conftest import load_seq
+from conftest import ROOT, load_seq
+
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from bisect_divergence import first_env_state_difference  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
+
+
+def _assert_states_equal(env, orc, risk_mode, where):
+    d = first_env_state_difference(env.snapshot(), orc, risk_mode=risk_mode)
+    assert d is None, "state differs %s: env %d %s gpu %r oracle %r" % ((where,) + d)
+
+
+def _assert_golden_cp(d, z, name, i):
+    """the two CP scalars of a golden call, exactly.  One recorded call is the exception, with its mechanism: py2tie call 77
+    (tests/test_state_comparator.py::test_py2tie_call_77_is_the_c_librarys_pow).  UTL:234 squares the agent's velocity with
+    math.pow, and the C library's pow is not correctly rounded: there vx = -0.44666666666666566, whose exact square lies 0.49991
+    ulp above vx * vx, and pow rounds it up where the kernel's correctly rounded vx * vx rounds down.  The ego score is
+    0.2860698797573434 on the device against the reference's 0.28606987975734355 (3 ulps), and the collision probability follows
+    it.  The oracle calls pow like the reference and equals it; equalling it on the device needs a restatement of glibc's
+    table-driven pow, whose source is not available (the same reason PREV_HEAD keeps its 1 ulp)."""
+    if (name, i) == ("py2tie", 77):
+        assert d["ego_score"] == 0.2860698797573434 and z["ego_score"][i] == 0.28606987975734355, (d["ego_score"], z["ego_score"][i])
+        assert d["collision_prob"] == 0.5190766065453384 and z["collision_prob"][i] == 0.5190766065453385, d["collision_prob"]
+        return
+    assert d["collision_prob"] == z["collision_prob"][i] and d["ego_score"] == z["ego_score"][i], (name, i)
 
 
 def _pair(oracle_mod, arbitration="auto", **kw):
@@ -32,8 +57,9 @@ def _compare_rollout(oracle_mod, steps, seed, reset_mode=True, **kw):
     env.reset(); torch.cuda.synchronize()
     oc = orc.reset()
     og = env.obs_f64.cpu().numpy()
-    assert np.abs(og - oc).max() <= TOL
+    assert np.array_equal(og, oc)
     assert np.array_equal(env.obs.cpu().numpy(), oc.astype(np.float32))
+    _assert_states_equal(env, orc, env.cfg.risk_mode, "after the reset")
     rng = np.random.default_rng(seed)
     n_done = 0
     exact_rows = 0
@@ -45,16 +71,18 @@ def _compare_rollout(oracle_mod, steps, seed, reset_mode=True, **kw):
         dg = env.done.cpu().numpy()
         assert np.array_equal(dg, dc), "done flags differ at step %d" % t                       # bit-exact
         assert np.array_equal(env.topk_idx.cpu().numpy(), ic), "top-K indices differ at step %d" % t  # bit-exact
-        assert np.abs(env.reward.cpu().numpy() - rc).max() <= TOL, "reward at step %d" % t
+        assert np.array_equal(env.reward.cpu().numpy(), rc.astype(np.float32)), "reward at step %d" % t
         og = env.obs_f64.cpu().numpy()
-        assert np.abs(og - oc).max() <= TOL, "obs at step %d: %g" % (t, np.abs(og - oc).max())
+        assert np.array_equal(og, oc), "obs at step %d: rows %s" % (t, np.nonzero((og != oc).any(1))[0][:8])
+        assert np.array_equal(env.obs.cpu().numpy(), oc.astype(np.float32)), "float32 obs at step %d" % t
         if reset_mode != "next":
-            assert np.abs(env.final_obs.cpu().numpy() - fc.astype(np.float32)).max() <= TOL
+            assert np.array_equal(env.final_obs.cpu().numpy(), fc.astype(np.float32)), "final obs at step %d" % t
+        _assert_states_equal(env, orc, env.cfg.risk_mode, "at step %d" % t)
         exact_rows += int((og == oc).all(1).sum())
         n_done += int(dc.sum())
     assert np.array_equal(env.counters().cpu().numpy()[:, :6], orc.counters())
     lr, rr = env.returns()
-    assert np.abs(lr.cpu().numpy() - orc.returns()).max() <= 1e-3
+    assert np.array_equal(lr.cpu().numpy(), orc.returns().astype(np.float32))
     # tracker tables of a few envs, bit for bit
     for e in range(0, N, max(1, N // 8)):
         g = env.debug_env(e); c = orc.debug(e)
@@ -69,7 +97,7 @@ def _compare_rollout(oracle_mod, steps, seed, reset_mode=True, **kw):
 def test_rollout_parity_train_config(oracle_mod):
     n_done, frac = _compare_rollout(oracle_mod, steps=150, seed=3, n_envs=64, n_peds=20, max_steps=60)
     assert n_done > 20          # auto-reset path exercised
-    assert frac > 0.999
+    assert frac == 1.0
 
 
 @pytest.mark.parametrize("arbitration", ["oldest_first", "fair"])
@@ -78,7 +106,7 @@ def test_rollout_parity_next_step_reset_mode(oracle_mod, arbitration):
     # of cn_set_arbitration (cn_env_kernel / cn_env_kernel_fair: s_setprio changes when instructions issue, not what they compute)
     n_done, frac = _compare_rollout(oracle_mod, steps=150, seed=4, reset_mode="next", n_envs=64, n_peds=20, max_steps=50,
                                     arbitration=arbitration)
-    assert n_done > 20 and frac > 0.999
+    assert n_done > 20 and frac == 1.0
 
 
 def test_arbitration_switch_rule_and_identical_results():
@@ -123,7 +151,7 @@ def test_rollout_parity_as_gazebo_delivers_it(oracle_mod, mode, risk):
     bit for bit, both reset conventions, both risk modes; the robot's pose AND twist equal the oracle's."""
     n_done, frac = _compare_rollout(oracle_mod, steps=120, seed=23 + risk, reset_mode=mode, n_envs=48, n_peds=20, max_steps=45,
                                     scan_f32=1, wheel_accel=1.0, waypoint_reward=0, risk_mode=risk)
-    assert n_done > 20 and frac > 0.999
+    assert n_done > 20 and frac == 1.0
 
 
 def test_each_round4_switch_changes_the_run_and_defaults_do_not():
@@ -158,7 +186,7 @@ def test_each_round4_switch_changes_the_run_and_defaults_do_not():
 def test_rollout_parity_dense_crowd(oracle_mod):
     # 100 pedestrians in the small room: > K tracks on most steps ("keep the K lowest", ENV:882-883)
     n_done, frac = _compare_rollout(oracle_mod, steps=60, seed=5, n_envs=32, n_peds=100, max_steps=40)
-    assert frac > 0.999
+    assert frac == 1.0
 
 
 def test_rollout_parity_eval_mode_and_k4(oracle_mod):
@@ -176,7 +204,7 @@ def test_rollout_parity_gt_risk_mode(oracle_mod, mode):
     """risk_mode = gt (row X1: the north star's "K-nearest perceived-risk feature extraction" on simulator pedestrians):
     cn_env_kernel_gt / _gt_same against the oracle's restatement -- observation, reward, done, pedestrian-id indices."""
     n_done, frac = _compare_rollout(oracle_mod, steps=150, seed=31, reset_mode=mode, n_envs=64, n_peds=20, max_steps=60, risk_mode=1)
-    assert n_done > 20 and frac > 0.999
+    assert n_done > 20 and frac == 1.0
 
 
 def test_gt_risk_mode_dense_and_semantics(oracle_mod):
@@ -184,7 +212,7 @@ def test_gt_risk_mode_dense_and_semantics(oracle_mod):
     reported index is a pedestrian that is within lidar reach of the robot, rows come with the negated true velocity."""
     import torch
     n_done, frac = _compare_rollout(oracle_mod, steps=60, seed=32, n_envs=32, n_peds=100, max_steps=40, risk_mode=1, k_obstacles=4)
-    assert frac > 0.999
+    assert frac == 1.0
     torch_, env, orc = _pair(oracle_mod, n_envs=16, n_peds=40, max_steps=200, seed=33, risk_mode=1)
     env.reset(); orc.reset()
     rng = np.random.default_rng(3)
@@ -222,7 +250,7 @@ def test_rollout_parity_contact_dynamics(oracle_mod, risk_mode):
     for mode in (True, "next"):
         n_done, frac = _compare_rollout(oracle_mod, steps=80, seed=51, reset_mode=mode, n_envs=32, n_peds=60, max_steps=40,
                                         ped_contact=1, risk_mode=risk_mode, min_scan_range=0.0)
-        assert frac > 0.999
+        assert frac == 1.0
     torch_, env, orc = _pair(oracle_mod, n_envs=8, n_peds=60, max_steps=300, seed=52, ped_contact=1, risk_mode=risk_mode, min_scan_range=0.0)
     env.reset(); orc.reset()
     rng = np.random.default_rng(4)
@@ -249,7 +277,7 @@ def test_rollout_parity_geos_untyped_empty(oracle_mod):
     """cn_config.geos_untyped_empty = 1 (shapely <= 1.7 / GEOS <= 3.8, the reference's Python-2.7 platform): a candidate
     segment that misses ends get_collision_point with None (UTL:279-289).  Dense room so that most tracks are affected."""
     n_done, frac = _compare_rollout(oracle_mod, steps=100, seed=23, n_envs=64, n_peds=60, max_steps=50, geos_untyped_empty=1)
-    assert frac > 0.999
+    assert frac == 1.0
     # and the switch is not a no-op: same seed, other setting, different collision probabilities somewhere
     import torch
     from crowdnav import Config
@@ -326,7 +354,9 @@ def test_rollout_parity_scripted_crowd(oracle_mod):
         torch.cuda.synchronize()
         oc, rc, dc, ic = orc.step(act.astype(np.float64), auto_reset=True)
         assert np.array_equal(env.done.cpu().numpy(), dc) and np.array_equal(env.topk_idx.cpu().numpy(), ic)
-        assert np.abs(env.obs_f64.cpu().numpy() - oc).max() <= TOL
+        assert np.array_equal(env.obs_f64.cpu().numpy(), oc), t
+        assert np.array_equal(env.reward.cpu().numpy(), rc.astype(np.float32)), t
+        _assert_states_equal(env, orc, 0, "at step %d" % t)
     g = env.debug_env(3); c = orc.sim_state(3)
     assert np.array_equal(g["ped_p"], c[1]) and np.array_equal(g["ped_v"], c[2])
 
@@ -352,7 +382,6 @@ def test_reproduces_reference_golden_run(name):
     env = VecEnv(Config(n_envs=1, **kw))
     env.enable_f64_obs()
     env.set_ped_init(z["ped_init"])
-    exact = 0
     for i in range(len(z["now"])):
         if z["is_reset"][i]:
             env.reset()
@@ -365,9 +394,7 @@ def test_reproduces_reference_golden_run(name):
         if not z["is_reset"][i]:
             assert bool(env.done[0].item()) == bool(z["done"][i]), (name, i)
             assert float(env.reward[0].item()) == z["reward"][i], (name, i)
-        assert np.abs(og - z["obs"][i]).max() <= TOL, (name, i, np.abs(og - z["obs"][i]).max())
-        exact += int(np.array_equal(og, z["obs"][i]))
-    assert exact >= 0.99 * len(z["now"])
+        assert np.array_equal(og, z["obs"][i]), (name, i, np.nonzero(og != z["obs"][i])[0][:8])
 
 
 def test_snapshot_restore_replays_bit_exact():
@@ -459,12 +486,12 @@ def test_rollout_parity_social_force_pedestrians(oracle_mod, risk_mode, tmp_path
     for mode in (True, "next"):
         n_done, frac = _compare_rollout(oracle_mod, steps=80, seed=61, reset_mode=mode, n_envs=32, n_peds=20, max_steps=40,
                                         ped_mode=2, risk_mode=risk_mode)
-        assert n_done > 10 and frac > 0.999
+        assert n_done > 10 and frac == 1.0
     # 50 ms ticks (160 ms = 3 x 50 + 10), with the pair matrix in LDS (20 pedestrians) and without (30: it no longer fits)
     for P in (20, 30):
         n_done, frac = _compare_rollout(oracle_mod, steps=60, seed=63 + P, reset_mode="next", n_envs=32, n_peds=P, max_steps=40,
                                         ped_mode=2, risk_mode=risk_mode, sf_tick_ms=50, sf_A=1.2)
-        assert frac > 0.999
+        assert frac == 1.0
     # a denser room with stronger forces, more than 64 pedestrians (two lane passes), goals reached all the time
     cfg = Config(n_envs=24, n_peds=80, n_rays=360, ped_mode=2, risk_mode=risk_mode, seed=62, max_steps=50, room_half=1.8,
                  sf_A=1.5, sf_B=0.15, sf_goal_eps=0.3, min_scan_range=0.0)
@@ -689,7 +716,7 @@ def test_reference_scenarios_presets(oracle_mod):
         act = np.stack([rng.uniform(0.1, 0.22, 8), rng.uniform(-0.5, 0.5, 8)], 1).astype(np.float32)
         env.step(torch.from_numpy(act).cuda(), auto_reset=True); torch.cuda.synchronize()
         oc, rc, dc, ic = orc.step(act.astype(np.float64), auto_reset=True)
-        assert np.array_equal(env.done.cpu().numpy(), dc) and np.abs(env.obs_f64.cpu().numpy() - oc).max() <= TOL
+        assert np.array_equal(env.done.cpu().numpy(), dc) and np.array_equal(env.obs_f64.cpu().numpy(), oc)
     cfg, init = presets.training(n_envs=8, max_steps=30, seed=4)
     assert cfg.n_peds == 14 and cfg.ped_cycle_ms == 1400
     env2 = VecEnv(cfg); env2.set_ped_init(init)
@@ -758,7 +785,6 @@ def test_golden_replay_through_the_kernel(name):
     z, kw = load_seq(name)
     env = VecEnv(Config(n_envs=1, **kw))
     env.enable_f64_obs()
-    n_exact = 0
     for i in range(len(z["now"])):
         odom = [z["px"][i], z["py"][i], z["yaw"][i], z["v"][i], z["w"][i], z["now"][i], z["deque_x"][i], z["deque_y"][i],
                 z["end_timestep"][i], 0.0]
@@ -766,8 +792,7 @@ def test_golden_replay_through_the_kernel(name):
         env.observe_external(z["ranges"][i][None, :], [odom], step_counter=[int(z["step_counter"][i])], is_reset=is_reset)
         torch.cuda.synchronize()
         og = env.obs_f64[0].cpu().numpy()
-        assert np.abs(og - z["obs"][i]).max() <= TOL, (name, i)
-        n_exact += int(np.array_equal(og, z["obs"][i]))
+        assert np.array_equal(og, z["obs"][i]), (name, i, np.nonzero(og != z["obs"][i])[0][:8])
         if not is_reset:
             assert float(env.reward[0].item()) == z["reward"][i] and bool(env.done[0].item()) == bool(z["done"][i]), (name, i)
         d = env.debug_env(0)
@@ -778,13 +803,9 @@ def test_golden_replay_through_the_kernel(name):
         # the last bit on 13 % of its arguments and these four lines carried a 1e-12 tolerance)
         assert np.array_equal(d["track_speed"], z["track_speed"][i][:n])
         assert np.array_equal(d["track_vel"], z["track_vel"][i][:n])
-        # (the two CP scalars keep the 1e-12 of the earlier rounds: ONE of the 1 462 recorded calls -- py2tie, call 77 -- differs in the
-        # last bit of the ego score, 0.2860698797573434 against ...4355, hence of collision_prob; the simulated path compares them
-        # exactly in test_scripted_collision_probability_corner_cases)
-        assert abs(d["collision_prob"] - z["collision_prob"][i]) <= 1e-12 and abs(d["ego_score"] - z["ego_score"][i]) <= 1e-12
+        _assert_golden_cp(d, z, name, i)
         assert np.array_equal(d["wp"], z["wp"][i]) and d["bb"] == z["bb"][i]
         assert tuple(env.counters()[0, :3].cpu().tolist()) == tuple(int(c) for c in z["counters"][i])
-    assert n_exact >= 0.995 * len(z["now"])
     if name == "py2tie":
         # the golden is the reference under Python-2.7 round() fed with sensor data on exact decimal ties: with the switch off
         # (Python-3 ties-to-even, numpy rounding of np.float64) the same inputs must give a visibly different run
@@ -816,7 +837,6 @@ def test_external_scans_with_nan_zero_inf_and_out_of_range_values(oracle_mod, la
     R = 360
     now = 10.0
     px, py, yaw = 1.0, -1.0, 3.14
-    worst = 0.0
     for i in range(80):
         is_reset = i % 27 == 0
         r = rng.uniform(0.05, 0.9, R)
@@ -849,8 +869,7 @@ def test_external_scans_with_nan_zero_inf_and_out_of_range_values(oracle_mod, la
         torch.cuda.synchronize()
         og = env.obs_f64[0].cpu().numpy()
         assert np.isfinite(og).all() and np.isfinite(oc).all(), i
-        worst = max(worst, float(np.abs(og - oc).max()))
-        assert np.abs(og - oc).max() <= TOL, (layout, i, kind)
+        assert np.array_equal(og, oc), (layout, i, kind, np.nonzero(og != oc)[0][:8])
         if not is_reset:
             assert float(env.reward[0].item()) == rc and bool(env.done[0].item()) == dc, (layout, i)
             if layout == 0:
@@ -860,7 +879,6 @@ def test_external_scans_with_nan_zero_inf_and_out_of_range_values(oracle_mod, la
         assert tuple(env.counters()[0, :3].cpu().tolist()) == tuple(orc.counters()[0][:3]), (layout, i)
         if layout != 1:
             assert env.debug_env(0)["status"] & 7 == orc.debug(0)["status"] & 7, (layout, i)
-    assert worst <= 1e-12
 
 
 # ---- obs_layout 1: environment_stage_1_original.py (363 inputs), SURVEY 8f N3 -----------------------------
@@ -912,7 +930,7 @@ def test_original_layout_golden_replay_and_run(name):
                       auto_reset=False)
             assert float(env2.reward[0].item()) == z["reward"][i] and bool(env2.done[0].item()) == bool(z["done"][i]), (name, i)
         torch.cuda.synchronize()
-        assert np.abs(env2.obs_f64[0].cpu().numpy() - z["obs"][i]).max() <= TOL, (name, i)
+        assert np.array_equal(env2.obs_f64[0].cpu().numpy(), z["obs"][i]), (name, i)
 
 
 def test_empty_room_and_masked_reset(oracle_mod):
@@ -986,7 +1004,7 @@ def test_randomised_configurations(oracle_mod):
             oc, rc, dc, ic = orc.step(act.astype(np.float64), auto_reset=mode)
             assert np.array_equal(env.done.cpu().numpy(), dc), (kw, t)
             assert np.array_equal(env.topk_idx.cpu().numpy(), ic), (kw, t)
-            assert np.abs(env.obs_f64.cpu().numpy() - oc).max() <= TOL, (kw, t)
+            assert np.array_equal(env.obs_f64.cpu().numpy(), oc), (kw, t)
             assert np.array_equal(env.reward.cpu().numpy(), rc.astype(np.float32)), (kw, t)
         env.close()
 
@@ -1035,31 +1053,39 @@ def test_worlds_the_fuzzer_found(oracle_mod, world):
         assert (not bad and not skipped) or late_overflow, (world, f, kernel, bad, skipped)
 
 
+SOAK_DRAWS = 60
+
+
 def test_randomised_soak_over_the_configuration_cross_product(oracle_mod):
-    """Twenty seconds of tools/fuzz_parity.py inside the gate (fixed seed: the same sequence of worlds every run, as many of them as
-    the box manages): worlds drawn from every switch cn_create accepts, each through one of the four launch forms, equal to the oracle
-    -- or flagged by the kernel itself as having outgrown a table."""
-    import sys
-    import time
+    """tools/fuzz_parity.py inside the gate: the first SOAK_DRAWS worlds of seed 2026 (refused ones included), the same worlds on
+    every machine.  They are drawn from every switch cn_create accepts, preset crowds (ped_mode 1) among them, and each goes through
+    one of the five launch forms, stream groups (VecEnvGroups) among them; each is equal to the oracle -- or flagged by the kernel
+    itself as having outgrown a table."""
     from conftest import ROOT
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import fuzz_parity
-    fuzz_parity.HEADLINE_FRAC = 0.25
-    rng = np.random.default_rng(2026)
-    t_end = time.time() + 20.0
     n = refused = 0
-    while time.time() < t_end:
-        kw, form, mode = fuzz_parity.draw(rng)
-        try:
-            bad, kernel, skipped = fuzz_parity.run_world(kw, form, mode, 40)
-        except Exception as ex:
-            assert "cn_create" in str(ex), (kw, ex)           # a combination cn_create refuses, with its reason
-            refused += 1
-            continue
-        n += 1
-        assert not bad or skipped == "overflow", (form, mode, kernel, bad, kw)
-    fuzz_parity.HEADLINE_FRAC = 0.0
-    assert n >= 50, (n, refused)
+    forms, ped_modes = set(), set()
+    saved = fuzz_parity.HEADLINE_FRAC
+    fuzz_parity.HEADLINE_FRAC = 0.25
+    try:
+        rng = np.random.default_rng(2026)
+        for _ in range(SOAK_DRAWS):
+            kw, form, mode = fuzz_parity.draw(rng)
+            try:
+                bad, kernel, skipped = fuzz_parity.run_world(kw, form, mode, 40)
+            except Exception as ex:
+                assert "cn_create" in str(ex), (kw, ex)           # a combination cn_create refuses, with its reason
+                refused += 1
+                continue
+            n += 1
+            forms.add(form); ped_modes.add(kw["ped_mode"])
+            assert not bad or skipped == "overflow", (form, mode, kernel, bad, kw)
+    finally:
+        fuzz_parity.HEADLINE_FRAC = saved
+    print("soak: %d draws, %d worlds ran, %d refused by cn_create; forms %s; ped_mode %s" % (SOAK_DRAWS, n, refused, sorted(forms), sorted(ped_modes)))
+    assert n + refused == SOAK_DRAWS and n >= 45, (n, refused)
+    assert "groups" in forms and 1 in ped_modes, (forms, ped_modes)
 
 
 def test_track_table_overflow_is_flagged_and_confined(oracle_mod):
@@ -1251,13 +1277,13 @@ def test_realworld_layout_rollout_parity(oracle_mod, mode):
     unrounded ranges, the one highest-CP obstacle, its own reward and 0.05 s / 0.15 s timestep quirk."""
     n_done, exact = _compare_rollout(oracle_mod, steps=150, seed=61, reset_mode=mode, n_envs=64, n_peds=20, max_steps=80,
                                      obs_layout=2, dt_ms=50)
-    assert (n_done > 20 or mode is False) and exact > 0.999
+    assert (n_done > 20 or mode is False) and exact == 1.0
 
 
 def test_realworld_layout_other_shapes(oracle_mod):
     n_done, exact = _compare_rollout(oracle_mod, steps=80, seed=62, n_envs=32, n_peds=100, max_steps=60, obs_layout=2, dt_ms=50,
                                      min_scan_range=0.0)
-    assert exact > 0.999
+    assert exact == 1.0
     _compare_rollout(oracle_mod, steps=60, seed=63, n_envs=16, n_peds=60, n_rays=181, max_steps=40, obs_layout=2, dt_ms=50)
     _compare_rollout(oracle_mod, steps=40, seed=64, n_envs=8, n_peds=100, n_rays=720, room_half=2.4, max_steps=30, obs_layout=2,
                      dt_ms=50, geos_untyped_empty=1)
@@ -1299,7 +1325,7 @@ def test_realworld_layout_golden_replay_and_run(name):
         env.observe_external(z["ranges"][i][None, :], [odom], step_counter=[int(z["step_counter"][i])], is_reset=is_reset)
         torch.cuda.synchronize()
         og = env.obs_f64[0].cpu().numpy()
-        assert np.abs(og - z["obs"][i]).max() <= TOL, (name, i, np.abs(og - z["obs"][i]).max())
+        assert np.array_equal(og, z["obs"][i]), (name, i, np.nonzero(og != z["obs"][i])[0][:8])
         if not is_reset:
             assert float(env.reward[0].item()) == z["reward"][i] and bool(env.done[0].item()) == bool(z["done"][i]), (name, i)
         d = env.debug_env(0)
@@ -1310,7 +1336,7 @@ def test_realworld_layout_golden_replay_and_run(name):
         if np.isinf(z["collision_prob"][i]):        # RW:80 None, kept as -inf (below every number, as in Python 2) until the first cone
             assert d["collision_prob"] == z["collision_prob"][i]
         else:
-            assert abs(d["collision_prob"] - z["collision_prob"][i]) <= 1e-12
+            assert d["collision_prob"] == z["collision_prob"][i], (name, i)
         assert d["bb"] == z["bb"][i]
         c = env.counters()[0].cpu().tolist()
         assert tuple(c[:2]) == tuple(int(x) for x in z["counters"][i]) and (bool(c[4]), bool(c[5])) == tuple(bool(x) for x in z["status"][i])
@@ -1325,7 +1351,7 @@ def test_realworld_layout_golden_replay_and_run(name):
                       auto_reset=False)
             assert float(env2.reward[0].item()) == z["reward"][i] and bool(env2.done[0].item()) == bool(z["done"][i]), (name, i)
         torch.cuda.synchronize()
-        assert np.abs(env2.obs_f64[0].cpu().numpy() - z["obs"][i]).max() <= TOL, (name, i)
+        assert np.array_equal(env2.obs_f64[0].cpu().numpy(), z["obs"][i]), (name, i)
 
 
 # ---- the hand-written device arithmetic (crowdnav_device.h) against libm, op by op --------------------------------------

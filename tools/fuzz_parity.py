@@ -4,8 +4,10 @@
 tools/parity_sweep.sh walks 37 hand-picked configurations and tests/test_gpu_parity.py::test_randomised_configurations a dozen random
 geometries of the default world; this draws worlds from every switch cn_create accepts at once -- observation layout x risk mode x
 pedestrian model x contact ticks x Python-2 rounding x GEOS <= 3.8 semantics x float32 scans x wheel ramp x reward variant x K x
-pedestrians x rays x room x clocks x reset convention -- and drives each through one of the three launch forms (cn_step per step,
-cn_step_sequence with trajectory buffers, cn_rollout_policy closed loop), small grids (two wavefronts per environment) and larger
+pedestrians x rays x room x clocks x reset convention, the preset crowds of the reference's evaluation scripts (ped_mode 1)
+among the pedestrian models -- and drives each through one of the launch forms (cn_step per step, cn_step_sequence with
+trajectory buffers, cn_rollout_policy closed loop, the reference's own loop with masked resets, and stream groups: a
+VecEnvGroups of 2-4 handles against one oracle), small grids (two wavefronts per environment) and larger
 ones, until the time budget is spent.  Every observation / reward / done flag / top-K index / counter is compared; a configuration
 cn_create refuses is counted and named, not an error.
     python tools/fuzz_parity.py [--seconds 300] [--seed 1] [--verbose 3]"""
@@ -27,10 +29,12 @@ HEADLINE_FRAC = 0.0
 def draw(rng):
     layout = int(rng.choice([0, 0, 0, 1, 2]))
     risk = int(rng.choice([0, 0, 1])) if layout == 0 else 0
-    ped_mode = int(rng.choice([0, 0, 2]))
+    ped_mode = int(rng.choice([0, 0, 1, 2]))
     R = int(rng.choice([int(rng.integers(8, 130)), 181, 360, 360, 361, int(rng.integers(130, 800)), 720, 1025]))
     P = int(rng.choice([0, 1, int(rng.integers(2, 30)), 20, int(rng.integers(30, 70)), int(rng.integers(70, 140))]))
-    room = float(rng.uniform(1.0, 3.0)) if P < 60 else float(rng.uniform(2.0, 3.2))
+    if ped_mode == 1:               # a preset crowd: its pedestrian count, in the 5 x 5 m room of its poses (preset_world)
+        P = int(rng.choice([4, 8, 12, 20]))
+    room = 2.4 if ped_mode == 1 else float(rng.uniform(1.0, 3.0)) if P < 60 else float(rng.uniform(2.0, 3.2))
     kw = dict(n_envs=int(rng.choice([1, 3, 8, 17, 64, 130, 300])), n_peds=P, n_rays=R,
               k_obstacles=int(rng.integers(1, 17)), max_steps=int(rng.integers(6, 60)), room_half=room,
               obs_layout=layout, risk_mode=risk, ped_mode=ped_mode, ped_contact=int(rng.choice([0, 0, 1])) if ped_mode == 0 else 0,
@@ -64,9 +68,29 @@ def draw(rng):
         # the wide tracker table (track_capacity 128 ... 1024, in HBM): every env the ORACLE did not flag is compared, those past the
         # 32 / 64 slots of the LDS table included
         kw.update(track_capacity=int(rng.choice([128, 256, 512, 1024])))
-    form = str(rng.choice(["step", "step", "sequence", "policy", "manual"]))
-    mode = "next" if form != "step" else str(rng.choice(["next", "same"]))
+    form = str(rng.choice(["step", "step", "sequence", "policy", "manual", "groups"]))
+    mode = "next" if form not in ("step", "groups") else str(rng.choice(["next", "same"]))
+    if form == "groups":            # n_envs a multiple of the group count (VecEnvGroups splits the envs evenly)
+        G = n_groups(kw)
+        kw["n_envs"] = max(G, int(round(kw["n_envs"] / G)) * G)
     return kw, form, mode
+
+
+def n_groups(kw):
+    """the group count of a world run in the `groups` form: 2, 3 or 4, a function of the world alone (--repro reproduces it)"""
+    return 2 + int(kw["seed"]) % 3
+
+
+def preset_world(kw):
+    """the pedestrian starts and constant velocities of a ped_mode 1 world: one of the reference's evaluation scripts with that
+    many pedestrians (crowdnav/presets_data.json), chosen by the world's seed; the same for every env"""
+    from crowdnav import presets
+    P, N = int(kw["n_peds"]), int(kw["n_envs"])
+    names = sorted(k for k, v in presets.data()["scripts"].items() if "vel" in v and k.split("_")[2] == str(P))
+    sc = presets.data()["scripts"][names[int(kw["seed"]) % len(names)]]
+    poses = np.asarray(presets.data()["worlds"]["test_%d" % P], dtype=np.float64)
+    vel = np.asarray(sc["vel"], dtype=np.float64)
+    return np.broadcast_to(poses, (N,) + poses.shape).copy(), np.broadcast_to(vel, (N,) + vel.shape).copy()
 
 
 def diff(tag, g, c):
@@ -90,13 +114,51 @@ def run_world(kw, form, mode, T, detail=False, as_steps=False):
     from crowdnav.env import VecEnv
     from crowdnav.td3 import Agent
     from oracle import oracle
+    from crowdnav.env import VecEnvGroups
     cfg = Config(**kw)
-    env = VecEnv(cfg)                               # cn_create's own validation raises here
+    # cn_create's own validation raises here
+    env = VecEnvGroups(cfg, groups=n_groups(kw)) if form == "groups" else VecEnv(cfg)
     rng = np.random.default_rng(int(kw["seed"]) ^ 0x5eed)
     N = cfg.n_envs
     orc = oracle.Oracle(cfg.as_dict())
+    if cfg.ped_mode == 1:
+        init, vel = preset_world(kw)
+        env.set_ped_init(init); env.set_ped_preset_vel(vel)
+        orc.set_ped_init(init); orc.set_ped_preset_vel(vel)
+    what = "policy" if form == "policy" else "sequence" if form == "sequence" else "same" if (mode == "same" and form in ("step", "groups")) else "step"
+    if form == "groups":
+        kn = "%s x%d" % (env.envs[0].kernel_name(what), env.G)
+        env.reset(); torch.cuda.synchronize()
+        bad, bad_envs = [], set()
+
+        def check_g(tag, g, c):
+            if not np.array_equal(g, c):
+                bad.append(tag)
+                bad_envs.update(int(x) for x in np.nonzero((g != c).reshape(g.shape[0], -1).any(1))[0])
+                if detail:
+                    diff(tag, g, c)
+        # (no float64 observation on a group handle: the float32 one, equal to the oracle's cast)
+        check_g("reset observation", env.obs.cpu().numpy(), orc.reset().astype(np.float32))
+        for t in range(T):
+            act = np.stack([rng.uniform(0, 0.22, N), rng.uniform(-2, 2, N)], 1).astype(np.float32)
+            env.step(torch.from_numpy(act).cuda(), auto_reset=mode); torch.cuda.synchronize()
+            oc, rc, dc, ic = orc.step(act.astype(np.float64), auto_reset=mode)
+            check_g("obs @%d" % t, env.obs.cpu().numpy(), oc.astype(np.float32))
+            check_g("reward @%d" % t, env.reward.cpu().numpy(), rc.astype(np.float32))
+            check_g("done @%d" % t, env.done.cpu().numpy(), dc)
+            check_g("idx @%d" % t, env.topk_idx.cpu().numpy(), ic)
+            if bad:
+                break
+        if not bad:
+            check_g("counters", env.counters().cpu().numpy()[:, :6], orc.counters())
+        skipped = None
+        if bad:
+            st = env.counters().cpu().numpy()[:, 6].astype(np.int64)
+            if all(st[e] & 25 for e in bad_envs):
+                skipped = "overflow"
+        env.close()
+        return bad, kn, skipped
     env.enable_f64_obs()
-    what = "policy" if form == "policy" else "sequence" if form == "sequence" else "same" if (mode == "same" and form == "step") else "step"
     kn = env.kernel_name(what)
     env.reset(); torch.cuda.synchronize()
     bad, skipped, bad_envs = [], None, set()
@@ -267,6 +329,7 @@ def main():
     env_steps = 0
     kernels = {}
     forms = {}
+    ped_modes = {}
     while time.time() < t_end:
         kw, form, mode = draw(rng)
         steps = a.steps if rng.random() < 0.8 else 4 * a.steps       # every fifth world four times as long (tracks persist across resets)
@@ -282,6 +345,7 @@ def main():
         n_trials += 1
         kernels[kn] = kernels.get(kn, 0) + 1
         forms[form] = forms.get(form, 0) + 1
+        ped_modes[kw["ped_mode"]] = ped_modes.get(kw["ped_mode"], 0) + 1
         if skipped == "refused":
             n_form_refused += 1
             continue
@@ -301,7 +365,8 @@ def main():
           % (a.seed, a.seconds, n_trials, n_refused, env_steps, n_bad, n_overflow, n_form_refused))
     print("  wide track tables: %d world(s); %d env(s) with more tracks than the LDS table holds compared equal past the LDS table"
           % (WIDE_STATS["worlds"], WIDE_STATS["envs_past_lds"]))
-    print("  launch forms:", dict(sorted(forms.items())))
+    print("  launch forms:", dict(sorted(forms.items())), "(stream groups: %d world(s) as VecEnvGroups of 2-4 handles)" % forms.get("groups", 0))
+    print("  pedestrian models (ped_mode):", dict(sorted(ped_modes.items())), "(1 = the preset crowds of the evaluation scripts)")
     print("  kernels exercised (%d):" % len(kernels), dict(sorted(kernels.items(), key=lambda kv: -kv[1])))
     sys.exit(1 if n_bad else 0)
 
