@@ -34,6 +34,7 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_policy_tail", "cn_actor_pack_weights", "cn_actor_forward", "cn_step_sequence", "cn_rollout_policy", "cn_get_counters",
            "cn_get_returns", "cn_debug_env", "cn_lds_bytes", "cn_near_separate", "cn_snapshot_size", "cn_snapshot", "cn_restore",
            "cn_td3_create", "cn_td3_destroy", "cn_td3_update", "cn_td3_loss_dev", "cn_td3_last_error",
+           "cn_ddpg_create", "cn_ddpg_destroy", "cn_ddpg_update", "cn_ddpg_loss_dev",
            "cn_replay_write", "cn_episode_log_add"]
 
 
@@ -115,6 +116,16 @@ class CnTd3Config(C.Structure):
                 ("beta2", C.c_float), ("eps", C.c_float), ("noise_std", C.c_float), ("noise_clip", C.c_float), ("max_v", C.c_float),
                 ("max_w", C.c_float), ("reserved", C.c_float),
                 ("actor", CnTd3Mlp), ("actor_t", CnTd3Mlp), ("q1", CnTd3Mlp), ("q1_t", CnTd3Mlp), ("q2", CnTd3Mlp), ("q2_t", CnTd3Mlp),
+                ("replay_s", C.c_void_p), ("replay_a", C.c_void_p), ("replay_r", C.c_void_p), ("replay_s2", C.c_void_p), ("replay_d", C.c_void_p),
+                ("replay_size_dev", C.c_void_p), ("seed", C.c_uint64)]
+
+
+class CnDdpgConfig(C.Structure):
+    """Mirror of `cn_ddpg_config` (include/crowdnav.h)."""
+    _fields_ = [("obs_dim", C.c_int32), ("hidden", C.c_int32), ("batch", C.c_int32), ("reserved0", C.c_int32),
+                ("gamma", C.c_float), ("tau", C.c_float), ("lr_actor", C.c_float), ("lr_critic", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("max_v", C.c_float), ("max_w", C.c_float), ("reserved1", C.c_float),
+                ("actor", CnTd3Mlp), ("actor_t", CnTd3Mlp), ("critic", CnTd3Mlp), ("critic_t", CnTd3Mlp),
                 ("replay_s", C.c_void_p), ("replay_a", C.c_void_p), ("replay_r", C.c_void_p), ("replay_s2", C.c_void_p), ("replay_d", C.c_void_p),
                 ("replay_size_dev", C.c_void_p), ("seed", C.c_uint64)]
 
@@ -247,6 +258,10 @@ def lib():
         L.cn_td3_update.argtypes = [vp, C.c_int, C.POINTER(CnTd3Batch), vp]
         L.cn_td3_loss_dev.argtypes = [vp]; L.cn_td3_loss_dev.restype = vp
         L.cn_td3_last_error.restype = C.c_char_p
+        L.cn_ddpg_create.argtypes = [C.POINTER(CnDdpgConfig), C.c_int, C.POINTER(vp)]
+        L.cn_ddpg_destroy.argtypes = [vp]; L.cn_ddpg_destroy.restype = None
+        L.cn_ddpg_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]
+        L.cn_ddpg_loss_dev.argtypes = [vp]; L.cn_ddpg_loss_dev.restype = vp
         L.cn_replay_write.argtypes = [C.POINTER(CnReplayRing), vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
         L.cn_episode_log_add.argtypes = [C.POINTER(CnEpisodeLog), vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, C.c_int, vp]
         _lib = L

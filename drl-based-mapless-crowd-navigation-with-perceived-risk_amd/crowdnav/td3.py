@@ -164,39 +164,12 @@ class DeviceReplay:
         return self._lb if self._lb == self._ub else self.sync_len()
 
 
-class Agent:
-    """TD3 agent (TD3:129-319) acting on batches of observations that stay on the device."""
+class FusedActorMixin:
+    """The actor-side interface the collection paths use (rollout, collect_policy, rollout_groups, evaluate,
+    VecEnv.rollout_policy): the packed-weight actor kernels of libcrowdnav and their exploration-noise bookkeeping.  Shared by
+    the TD3 and the DDPG agent; the host class provides `actor`, `device`, `max_v`, `max_w` and `explore_sigma`."""
 
-    def __init__(self, obs_dim=398, hidden=256, actor_lr=3e-4, critic_lr=3e-4, batch_size=128, memory_size=1_000_000,
-                 gamma=0.99, tau=0.005, max_v=0.22, max_w=2.0, noise_std=0.2, noise_clip=0.5, policy_delay=2,
-                 explore_sigma=1.0, device="cuda", seed=0, actor_final_init=None):
-        self.device = torch.device(device)
-        g = torch.Generator().manual_seed(seed)
-        torch.manual_seed(seed)
-        self.actor = Actor(obs_dim, 2, hidden, max_v, max_w).to(self.device)
-        self.actor_t = Actor(obs_dim, 2, hidden, max_v, max_w).to(self.device)
-        self.q1, self.q2 = Critic(obs_dim, 2, hidden).to(self.device), Critic(obs_dim, 2, hidden).to(self.device)
-        self.q1_t, self.q2_t = Critic(obs_dim, 2, hidden).to(self.device), Critic(obs_dim, 2, hidden).to(self.device)
-        if actor_final_init:
-            # NOT the reference (td3.py:81-95 keeps nn.Linear's default U(+-1/sqrt(256)) everywhere): the DDPG paper's small uniform
-            # initialisation of the actor's output layer, an opt-in for the seed sensitivity documented in profiles/r04/train/ (heads
-            # that start near the middle of the sigmoid / tanh instead of wherever the default range leaves them)
-            with torch.no_grad():
-                self.actor.linear3.weight.uniform_(-float(actor_final_init), float(actor_final_init))
-                self.actor.linear3.bias.uniform_(-float(actor_final_init), float(actor_final_init))
-        for t, s in ((self.actor_t, self.actor), (self.q1_t, self.q1), (self.q2_t, self.q2)):
-            t.load_state_dict(s.state_dict())
-        fused = self.device.type == "cuda"        # one kernel per optimizer step instead of ~10 per parameter tensor;
-        kw = dict(fused=True) if fused else {}
-        self.opt_a = torch.optim.Adam(self.actor.parameters(), lr=actor_lr, **kw)
-        self.opt_q1 = torch.optim.Adam(self.q1.parameters(), lr=critic_lr, **kw)
-        self.opt_q2 = torch.optim.Adam(self.q2.parameters(), lr=critic_lr, **kw)
-        self.memory = DeviceReplay(memory_size, obs_dim, self.device)
-        self.batch_size, self.gamma, self.tau = batch_size, gamma, tau
-        self.max_v, self.max_w = max_v, max_w
-        self.noise_std, self.noise_clip, self.policy_delay = noise_std, noise_clip, policy_delay
-        self.explore_sigma = explore_sigma
-        self.gen = torch.Generator(device=self.device).manual_seed(seed)
+    def _init_fused_actor(self, seed):
         # exploration-noise key of the fused actor paths (cn_policy_tail / cn_actor_forward): derived from the Agent seed so that
         # --seed changes the noise; the call counter is part of checkpoints' bookkeeping (noise_state) so a resumed run
         # does not replay the stream
@@ -204,17 +177,8 @@ class Agent:
         self._fused_calls = 0
         self._dev_index = self.device.index if self.device.type == "cuda" and self.device.index is not None else (
             torch.cuda.current_device() if self.device.type == "cuda" else -1)
-        self._lo = torch.tensor([0.0, -max_w], device=self.device)
-        self._hi = torch.tensor([max_v, max_w], device=self.device)
-        del g
-
-    @torch.no_grad()
-    def act(self, obs, add_noise=True):
-        """Agent.act (TD3:196-223) for a batch: actor, Gaussian noise sigma=1.0, clip."""
-        a = self.actor(obs)
-        if add_noise:
-            a = a + torch.randn(a.shape, generator=self.gen, device=self.device) * self.explore_sigma
-        return torch.max(torch.min(a, self._hi), self._lo).contiguous()
+        self._lo = torch.tensor([0.0, -self.max_w], device=self.device)
+        self._hi = torch.tensor([self.max_v, self.max_w], device=self.device)
 
     @torch.no_grad()
     def act_fused(self, obs, out=None, add_noise=True):
@@ -328,6 +292,51 @@ class Agent:
             if rc:
                 check(rc)
         return call
+
+
+class Agent(FusedActorMixin):
+    """TD3 agent (TD3:129-319) acting on batches of observations that stay on the device."""
+
+    def __init__(self, obs_dim=398, hidden=256, actor_lr=3e-4, critic_lr=3e-4, batch_size=128, memory_size=1_000_000,
+                 gamma=0.99, tau=0.005, max_v=0.22, max_w=2.0, noise_std=0.2, noise_clip=0.5, policy_delay=2,
+                 explore_sigma=1.0, device="cuda", seed=0, actor_final_init=None):
+        self.device = torch.device(device)
+        g = torch.Generator().manual_seed(seed)
+        torch.manual_seed(seed)
+        self.actor = Actor(obs_dim, 2, hidden, max_v, max_w).to(self.device)
+        self.actor_t = Actor(obs_dim, 2, hidden, max_v, max_w).to(self.device)
+        self.q1, self.q2 = Critic(obs_dim, 2, hidden).to(self.device), Critic(obs_dim, 2, hidden).to(self.device)
+        self.q1_t, self.q2_t = Critic(obs_dim, 2, hidden).to(self.device), Critic(obs_dim, 2, hidden).to(self.device)
+        if actor_final_init:
+            # NOT the reference (td3.py:81-95 keeps nn.Linear's default U(+-1/sqrt(256)) everywhere): the DDPG paper's small uniform
+            # initialisation of the actor's output layer, an opt-in for the seed sensitivity documented in profiles/r04/train/ (heads
+            # that start near the middle of the sigmoid / tanh instead of wherever the default range leaves them)
+            with torch.no_grad():
+                self.actor.linear3.weight.uniform_(-float(actor_final_init), float(actor_final_init))
+                self.actor.linear3.bias.uniform_(-float(actor_final_init), float(actor_final_init))
+        for t, s in ((self.actor_t, self.actor), (self.q1_t, self.q1), (self.q2_t, self.q2)):
+            t.load_state_dict(s.state_dict())
+        fused = self.device.type == "cuda"        # one kernel per optimizer step instead of ~10 per parameter tensor;
+        kw = dict(fused=True) if fused else {}
+        self.opt_a = torch.optim.Adam(self.actor.parameters(), lr=actor_lr, **kw)
+        self.opt_q1 = torch.optim.Adam(self.q1.parameters(), lr=critic_lr, **kw)
+        self.opt_q2 = torch.optim.Adam(self.q2.parameters(), lr=critic_lr, **kw)
+        self.memory = DeviceReplay(memory_size, obs_dim, self.device)
+        self.batch_size, self.gamma, self.tau = batch_size, gamma, tau
+        self.max_v, self.max_w = max_v, max_w
+        self.noise_std, self.noise_clip, self.policy_delay = noise_std, noise_clip, policy_delay
+        self.explore_sigma = explore_sigma
+        self.gen = torch.Generator(device=self.device).manual_seed(seed)
+        self._init_fused_actor(seed)
+        del g
+
+    @torch.no_grad()
+    def act(self, obs, add_noise=True):
+        """Agent.act (TD3:196-223) for a batch: actor, Gaussian noise sigma=1.0, clip."""
+        a = self.actor(obs)
+        if add_noise:
+            a = a + torch.randn(a.shape, generator=self.gen, device=self.device) * self.explore_sigma
+        return torch.max(torch.min(a, self._hi), self._lo).contiguous()
 
     def _update(self, s, a, r, s2, d, target_noise, do_actor):
         """The arithmetic of one TD3 update (TD3:225-285) on a given batch."""

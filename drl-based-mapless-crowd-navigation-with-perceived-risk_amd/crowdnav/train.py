@@ -7,6 +7,14 @@ Checkpoints are labelled with the episode count the weights really have behind t
 count at a log interval is rarely a round number); every save also rewrites `latest_checkpoint.txt` with that count, and
 `--load-episode latest` (the default) reads it -- resume / evaluate commands can be written before the run exists.
 
+`--algo ddpg` trains the reference's baseline learner instead (start_ddpg_training.py, ddpg.py; crowdnav.ddpg): batch 64, actor
+lr 1e-4, critic lr 1e-3, tau 0.001 unless --batch / --lr-actor / --lr-critic / --tau are given, no exploration noise
+(TRAIN_DDPG:100) unless --ou-noise, checkpoints ddpg_{actor,critic}_model_ep<N>.pt, CSV ddpg_training.csv; `--learner fused` is
+cn_ddpg_update.  `--obs-layout 1` is the 363-input observation of the shipped DDPG checkpoints:
+
+    python -m crowdnav.train --algo ddpg --scenario training_as_logged --waypoint-reward 0 --envs 16 --updates 16 --csv --learner fused
+    python -m crowdnav.train --algo ddpg --evaluate --load runs/ddpg --obs-layout 1 --scenario crossing_8
+
 What it keeps from the reference loop: Agent hyper-parameters (TRAIN:62-72), exploration noise sigma = 1.0 with the
 clip to v in [0, 0.22], w in [-2, 2], 1-based per-env step counters, `learn()` only once the replay holds more than a
 batch, target-network checkpoints named td3_{actor,critic1,critic2}_model_ep<N>.pt, one CSV row per finished episode
@@ -29,7 +37,7 @@ from . import presets
 from .config import Config
 from .env import VecEnv
 from .rollout import EpisodeStats, evaluate
-from .td3 import Agent
+from . import ddpg, td3
 
 
 def make_env(scenario, n_envs, max_steps, seed, device, ped_vmax=None, **switches):
@@ -132,22 +140,49 @@ def save_checkpoint(agent, outdir, episodes):
     os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
 
 
+CHECKPOINT_NETS = dict(td3=("actor", "critic1", "critic2"), ddpg=("actor", "critic"))
+
+
+def make_agent(a, obs_dim, device, **kw):
+    """The learner of --algo with its reference defaults; --batch / --lr-actor / --lr-critic / --tau override them when given."""
+    over = {k: v for k, v in (("batch_size", getattr(a, "batch", None)), ("actor_lr", getattr(a, "lr_actor", None)),
+                              ("critic_lr", getattr(a, "lr_critic", None)), ("tau", getattr(a, "tau", None))) if v is not None}
+    over.update(kw)
+    if getattr(a, "algo", "td3") == "ddpg":
+        return ddpg.Agent(obs_dim=obs_dim, device=device, seed=a.seed, n_envs=a.envs, **over)
+    return td3.Agent(obs_dim=obs_dim, device=device, seed=a.seed, **over)
+
+
+def load_checkpoint(agent, a):
+    algo = getattr(a, "algo", "td3")
+    a.load_episode = resolve_load_episode(a.load, a.load_episode)
+    agent.load_models(*[os.path.join(a.load, "%s_%s_model_ep%d.pt" % (algo, n, a.load_episode)) for n in CHECKPOINT_NETS[algo]])
+
+
+def env_switches(a):
+    return dict(waypoint_reward=a.waypoint_reward, scan_f32=a.scan_f32, wheel_accel=a.wheel_accel,
+                track_capacity=getattr(a, "track_capacity", None), obs_layout=getattr(a, "obs_layout", None))
+
+
 def train(a):
     dev = a.device
+    algo = getattr(a, "algo", "td3")
     torch.cuda.set_device(dev)        # policy kernels and torch ops of this process all target the env's GPU
-    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, waypoint_reward=a.waypoint_reward,
-                   scan_f32=a.scan_f32, wheel_accel=a.wheel_accel, track_capacity=getattr(a, "track_capacity", None))
-    agent = Agent(obs_dim=env.D, device="cuda:%d" % dev, seed=a.seed, batch_size=a.batch, memory_size=a.memory,
-                  actor_final_init=getattr(a, "actor_final_init", None))
+    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, **env_switches(a))
+    extra = dict(memory_size=a.memory)
+    if algo == "td3":
+        extra["actor_final_init"] = getattr(a, "actor_final_init", None)
+    agent = make_agent(a, env.D, "cuda:%d" % dev, **extra)
+    batch = agent.batch_size
+    ou = algo == "ddpg" and getattr(a, "ou_noise", False)      # OU noise: the act -> step loop (DDPG:170-196, add_noise=True)
     if a.load:
-        a.load_episode = resolve_load_episode(a.load, a.load_episode)
-        agent.load_models(*[os.path.join(a.load, "td3_%s_model_ep%d.pt" % (n, a.load_episode)) for n in ("actor", "critic1", "critic2")])
+        load_checkpoint(agent, a)
         ns = os.path.join(a.load, "noise_state_ep%d.txt" % a.load_episode)
         if os.path.exists(ns):           # continue the exploration-noise stream instead of replaying it
             agent.set_noise_state(*[int(x) for x in open(ns).read().split()])
     if a.learner == "fused":
-        agent.enable_fused_update()   # cn_td3_update: the update as 7 (+ 5) hand-written launches
-    elif a.graphs:
+        agent.enable_fused_update()   # cn_td3_update: the update as 7 (+ 5) hand-written launches; cn_ddpg_update: 8
+    elif a.graphs and algo == "td3":
         agent.enable_graphs()         # a TD3 update as one hipGraph launch (the eager update is launch-bound at batch 128)
     stats = EpisodeStats()
     os.makedirs(a.out, exist_ok=True)
@@ -172,7 +207,10 @@ def train(a):
     win = []                                                           # (successes, episodes) of the recent log windows
     warned_overflow = False
     for it in range(1, a.launches + 1):
-        act = agent.act_mfma(obs, add_noise=True)                      # TD3:196-223 as one kernel, sigma = 1.0, clipped
+        if ou:
+            act = agent.act(obs, add_noise=True, step=it - 1)
+        else:
+            act = agent.act_mfma(obs, add_noise=True)                  # TD3:196-223 as one kernel, sigma = 1.0 (DDPG: 0), clipped
         prev.copy_(obs)
         if same:
             obs, reward, done = env.step(act, auto_reset="same", want_final=True)
@@ -183,9 +221,11 @@ def train(a):
             keep = ~resetting
             agent.memory.add_masked(prev, act, reward, obs, done, keep)    # TRAIN:129-131; s' of a finished env = its terminal obs
             resetting = done.bool()
+        if ou:
+            agent.reset_noise(done)                                    # TRAIN_DDPG:161
         elog.add(done, env.counters(), env.returns()[0], it, keep)
         if not learning:                                               # TRAIN:132: only once the replay holds more than a batch
-            learning = agent.memory.ready(a.batch)                     # (a host read only while the bounds straddle it; none afterwards)
+            learning = agent.memory.ready(batch)                     # (a host read only while the bounds straddle it; none afterwards)
         if learning:
             for u in range(a.updates):
                 updates_done += 1
@@ -215,7 +255,7 @@ def train(a):
                             "track list equal to the reference's up to that many tracks" % (sc_["track_overflow"], sc_["conf_overflow"]))
                     print(line, flush=True); log.write(line + "\n"); log.flush()
             if a.csv:
-                stats.append_csv(a.out, "td3_training", resume=resumed)   # incremental: a killed run keeps its rows up to here
+                stats.append_csv(a.out, "%s_training" % algo, resume=resumed)   # incremental: a killed run keeps its rows up to here
             if episodes >= next_ckpt:                                    # TRAIN:150-154 (every 100 episodes there)
                 # labelled with the episode count the weights really have behind them (checked at log time, so it can be past
                 # the threshold that triggered it)
@@ -235,17 +275,15 @@ def train(a):
             updates_done, updates_done / max(1e-9, time.time() - t0), env_steps / max(1e-9, time.time() - t0))
         print(line, flush=True); log.write(line + "\n"); log.flush()
     if a.csv:
-        stats.append_csv(a.out, "td3_training", resume=resumed)
+        stats.append_csv(a.out, "%s_training" % algo, resume=resumed)
     return agent, episodes
 
 
 def run_evaluation(a):
     torch.cuda.set_device(a.device)
-    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, a.device, a.ped_vmax, waypoint_reward=a.waypoint_reward,
-                   scan_f32=a.scan_f32, wheel_accel=a.wheel_accel, track_capacity=getattr(a, "track_capacity", None))
-    agent = Agent(obs_dim=env.D, device="cuda:%d" % a.device, seed=a.seed, memory_size=16)
-    a.load_episode = resolve_load_episode(a.load, a.load_episode)
-    agent.load_models(*[os.path.join(a.load, "td3_%s_model_ep%d.pt" % (n, a.load_episode)) for n in ("actor", "critic1", "critic2")])
+    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, a.device, a.ped_vmax, **env_switches(a))
+    agent = make_agent(a, env.D, "cuda:%d" % a.device, memory_size=16)
+    load_checkpoint(agent, a)
     st = evaluate(env, agent, episodes_per_env=a.episodes_per_env)
     n = len(st.rows)
     print("%s: %d episodes, success %.3f, failure %.3f, mean return %.1f, mean steps %.1f, ego %.3f, social %.3f" % (
@@ -253,7 +291,7 @@ def run_evaluation(a):
         sum(r[5] for r in st.rows if r[5] == r[5]) / max(1, sum(1 for r in st.rows if r[5] == r[5])),
         sum(r[6] for r in st.rows if r[6] == r[6]) / max(1, sum(1 for r in st.rows if r[6] == r[6]))))
     if a.out:
-        print("wrote", st.write_csv(a.out, "td3_training_test_" + a.scenario))
+        print("wrote", st.write_csv(a.out, "%s_training_test_%s" % (getattr(a, "algo", "td3"), a.scenario)))
     return st
 
 
@@ -265,7 +303,15 @@ def main(argv=None):
     ap.add_argument("--time-limit", type=float, default=0.0, help="stop after this many seconds (checked at log time); 0 = run all launches")
     ap.add_argument("--max-steps", type=int, default=1000, help="nsteps (configs/td3.yaml)")
     ap.add_argument("--updates", type=int, default=4, help="TD3 updates per launch")
-    ap.add_argument("--batch", type=int, default=128, help="TRAIN:62")
+    ap.add_argument("--algo", default="td3", choices=["td3", "ddpg"], help="td3: start_td3_training.py; ddpg: start_ddpg_training.py (crowdnav.ddpg)")
+    ap.add_argument("--batch", type=int, default=None, help="TRAIN:62 -> 128 (td3); TRAIN_DDPG:55 -> 64 (ddpg)")
+    ap.add_argument("--lr-actor", type=float, default=None, help="default: the algorithm's (td3 3e-4, ddpg 1e-4)")
+    ap.add_argument("--lr-critic", type=float, default=None, help="default: the algorithm's (td3 3e-4, ddpg 1e-3)")
+    ap.add_argument("--tau", type=float, default=None, help="default: the algorithm's (td3 0.005, ddpg 0.001)")
+    ap.add_argument("--ou-noise", action="store_true", help="ddpg only: Agent.act(add_noise=True)'s Ornstein-Uhlenbeck noise (DDPG:44-64), "
+                    "host-side, one state per env; collection goes act -> step.  Off by default, as in TRAIN_DDPG:100")
+    ap.add_argument("--obs-layout", type=int, default=None, choices=[0, 1, 2], help="cn_config.obs_layout: 0 = 366 + 4K inputs (default); "
+                    "1 = environment_stage_1_original's 363 (the shipped DDPG checkpoints); 2 = 370")
     ap.add_argument("--memory", type=int, default=1_000_000, help="TRAIN:63")
     ap.add_argument("--checkpoint-every", type=int, default=100000, help="episodes between checkpoints (TRAIN:150: 100); checked at log time")
     ap.add_argument("--log-every", type=int, default=100)
@@ -277,12 +323,13 @@ def main(argv=None):
                     help="cn_config.track_capacity: 0 = auto (32 / 64, LDS); 128 ... 1024 = a wide table in HBM for long runs whose track "
                          "list outgrows 64 (slower; CN_ST_TRACK_OVERFLOW otherwise)")
     ap.add_argument("--reset-mode", default="next", choices=["next", "same"], help="next: the fast kernel, reset launches masked out of the replay; same: same-call reset + final_obs")
-    ap.add_argument("--graphs", type=int, default=1, help="1: capture the TD3 update into hipGraphs (Agent.enable_graphs)")
-    ap.add_argument("--learner", default="torch", choices=["torch", "fused"], help="torch: the PyTorch update (eager / hipGraph); fused: cn_td3_update (csrc/crowdnav_td3.hip)")
+    ap.add_argument("--graphs", type=int, default=1, help="1: capture the TD3 update into hipGraphs (Agent.enable_graphs; td3 only)")
+    ap.add_argument("--learner", default="torch", choices=["torch", "fused"], help="torch: the PyTorch update (td3: eager / hipGraph; ddpg: eager); "
+                    "fused: cn_td3_update / cn_ddpg_update (csrc/crowdnav_td3.hip)")
     ap.add_argument("--actor-final-init", type=float, default=None, help="NOT the reference: U(+-x) initialisation of the actor's output layer (e.g. 0.003)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
-    ap.add_argument("--out", default="runs/td3")
+    ap.add_argument("--out", default=None, help="default: runs/<algo>")
     ap.add_argument("--csv", action="store_true", help="one CSV row per finished episode in the reference's 8-column schema (recorded on the device, appended to the file at "
                     "every log interval); `timelapse` = the episode's own virtual duration, steps x (0.15 s + scan wait) -- TRAIN:141 "
                     "measures wall time since the episode's start, which the reference's time.sleep(0.15) makes the same quantity")
@@ -292,6 +339,10 @@ def main(argv=None):
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--episodes-per-env", type=int, default=1)
     a = ap.parse_args(argv)
+    if a.out is None:
+        a.out = "runs/%s" % a.algo
+    if a.ou_noise and a.algo != "ddpg":
+        ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     if a.evaluate:
         return run_evaluation(a)
     return train(a)

@@ -110,8 +110,10 @@ struct GemmJob {
     // whole row, so the reduction runs on hb_w3 (.) [h2 > 0] and the epilogue multiplies.  The first column tile also writes what
     // the weight-gradient launch needs: hb_dq [I] (linear3's gradient = dq^T h2: a job of that launch) and hb_dz2 [I][R] = A.
     // (Was td3_critic_head_bwd_kernel: a launch between the forward pass and this one.)
+    // hb_single != 0 (DDPG, ddpg.py:223-225): ONE target network, y = r + (1 - d) gamma q_t with q_t = network 2's partial sums;
+    // network 3's are not read.
     const float* hb_h2; const float* hb_w3; const float* hb_qpart; const float* hb_r; const float* hb_d;
-    float* hb_dq; float* hb_dz2; int hb_qnt, hb_net; float hb_gamma;
+    float* hb_dq; float* hb_dz2; int hb_qnt, hb_net; float hb_gamma; int hb_single;
     // G, optional, the ACTOR's counterpart (TD3:268-269, -mean Q1(s, pi(s)) arriving at the policy's second hidden layer):
     //   A[m][k] = (dl[m][0] ab_w3[k] + dl[m][1] ab_w3[R + k]) [ab_h2[m][k] > 0],   dl[m][o] = da[m][o] (max_v s (1 - s), max_w (1 - t^2)),
     // da from this kernel's own per-tile partial sums of the launch before (ab_dapart), s / t from the policy's logits.  The first
@@ -282,9 +284,11 @@ __global__ void __launch_bounds__(256) td3_dgrad_kernel(GemmArgs args)
     if (hb) arow = jb.hb_h2 + (size_t)min(i0 + li, I - 1) * jb.lda;
     if (hb && (blockIdx.x == 0 || (wave == 0 && lk == 0))) {      // (the first column tile needs dq in every lane: it stores dz2)
         const int m = min(i0 + li, I - 1);
-        float qs[3];                               // this critic, the two target critics
+        float qs[3] = {0.f, 0.f, 0.f};             // this critic, the two target critics (DDPG: one)
+        const int nq = jb.hb_single ? 2 : 3;
 #pragma unroll
         for (int n = 0; n < 3; ++n) {
+            if (n >= nq) break;
             const float* __restrict__ pp = jb.hb_qpart + ((size_t)(n == 0 ? jb.hb_net : 1 + n) * I + m) * jb.hb_qnt;
             float a_ = 0.f;
             int t = 0;
@@ -293,7 +297,7 @@ __global__ void __launch_bounds__(256) td3_dgrad_kernel(GemmArgs args)
             for (; t < jb.hb_qnt; ++t) a_ += pp[t];
             qs[n] = a_;
         }
-        const float y = jb.hb_r[m] + (1.f - jb.hb_d[m]) * jb.hb_gamma * fminf(qs[1], qs[2]);
+        const float y = jb.hb_r[m] + (1.f - jb.hb_d[m]) * jb.hb_gamma * (jb.hb_single ? qs[1] : fminf(qs[1], qs[2]));
         dq_li = 2.f * (qs[0] - y) / (float)I;
         if (wave == 0 && lk == 0) {
             dqs[li] = dq_li;
@@ -529,7 +533,7 @@ struct PrepArgs {
     const float *rs, *ra, *rr, *rs2, *rd;          // replay ring (rows `obs_dim` / 2 / 1 wide) or the explicit batch
     const float* noise_in;                         // explicit target-policy noise [B][2] (unit variance, before the clip) or null
     const int64_t* size_dev;                       // live replay size (device) or null = the rows ARE the batch
-    float *xs, *x2, *r, *d, *noise;                // outputs: [B][D + 2] x 2, [B], [B], [B][2]
+    float *xs, *x2, *r, *d, *noise;                // outputs: [B][D + 2] x 2, [B], [B], [B][2] (noise null: none drawn, DDPG)
     const unsigned long long* counter;             // update counter (keys the sampling; advanced by td3_tick)
     uint64_t seed;
     int B, D;
@@ -553,6 +557,8 @@ __global__ void __launch_bounds__(256) td3_prep_kernel(PrepArgs p)
     }
     if (tid < 2) {
         p.xs[(size_t)m * Dc + p.D + tid] = p.ra[row * 2 + tid];
+    }
+    if (tid < 2 && p.noise) {
         float z;
         if (p.noise_in) z = p.noise_in[(size_t)m * 2 + tid];
         else {   // Box-Muller on a counter-based pair, keyed by (seed, update counter, row)
@@ -901,6 +907,199 @@ extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* 
         launch_gemm<GEMM_H>(ga, 3, st);
         // (20, the soft updates of the three targets, ran in the Adam epilogues of 7, 9, 17 and 19)
     }
+    TD3CHK(hipGetLastError());
+    return CN_OK;
+}
+
+// ---- DDPG (ddpg.py:198-243 of the reference: Agent.learn) on the same three GEMM kernels -----------------------------------
+// One critic and its target, no policy delay, no target-policy noise.  The actor loss -mean Q(s, pi(s)) is back-propagated
+// BEFORE the critic's step (ddpg.py:226-238), so both gradients are taken at the pre-update weights and the two branches share
+// launches.  8 launches:  prep | actor_t L1 (+ actor L1) | L2 (+ L2) | critic_t L1 on (s2, pi_t(s2)), critic L1 on (s, a) and on
+// (s, pi(s)) | their L2 (+ q partials of critic_t and critic, dz on the pi(s) branch, tick) | G (critic: dq, dz2 evaluated;
+// pi(s) branch: da partials) | G (actor: dl, dz2a evaluated) | H (six jobs: critic and actor W1 / W2 / W3 + Adam + soft updates).
+struct cn_ddpg_s {
+    cn_ddpg_config cfg;
+    int device;
+    int B, D, Dc, H;
+    float* pool = nullptr;
+    float *xs, *x2, *r, *d, *logits;
+    float *t_h1, *t_h2, *a_h1, *a_h2;        // target actor on s2, actor on s
+    float *c_h1[3], *c_h2[3];                // critic on (s, a), critic on (s, pi(s)), critic_t on (s2, pi_t(s2))
+    float *qpart, *dapart; int qnt, dant;    // q partial sums [3][B][qnt] (slots 0: critic, 2: critic_t), action gradient [B][2][dant]
+    float *dq, *dl;
+    float *dz2c, *dz1c, *dz2p, *dz1p, *dz2a, *dz1a;   // critic step, pi(s) branch through the critic, actor
+    float* loss;
+    float* adam;                             // [4]: critic, actor
+    float* steps;                            // [2]
+    double* pw;                              // [4]
+    unsigned long long* counter;
+    float* mom[2][6][2];                     // Adam moments: actor, critic x {w1, b1, w2, b2, w3, b3} x {m, v}
+};
+
+namespace {
+size_t ddpg_param_count(const cn_ddpg_s* h, int net, int j)
+{
+    const size_t in1 = net == 0 ? (size_t)h->D : (size_t)h->Dc, out3 = net == 0 ? 2 : 1, H = (size_t)h->H;
+    switch (j) { case 0: return H * in1; case 1: return H; case 2: return H * H; case 3: return H; case 4: return out3 * H; default: return out3; }
+}
+}  // namespace
+
+extern "C" int cn_ddpg_create(const cn_ddpg_config* cfg, int device, cn_ddpg_handle* out)
+{
+    if (!cfg || !out) return td3_fail(CN_ERR_ARG, "cn_ddpg_create: null argument");
+    const cn_ddpg_config& c = *cfg;
+    if (c.obs_dim < 1 || c.hidden < 1 || c.batch < 1 || c.batch > 4096 || c.hidden > 4096)
+        return td3_fail(CN_ERR_CONFIG, "cn_ddpg_create: obs_dim / hidden / batch out of range");
+    const cn_td3_mlp* nets[4] = {&c.actor, &c.actor_t, &c.critic, &c.critic_t};
+    for (const cn_td3_mlp* n : nets)
+        if (!n->w1 || !n->b1 || !n->w2 || !n->b2 || !n->w3 || !n->b3) return td3_fail(CN_ERR_ARG, "cn_ddpg_create: null parameter pointer");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return td3_fail(CN_ERR_NO_DEVICE, "cn_ddpg_create: no HIP device (libcrowdnav has no CPU fallback)");
+    if (device < 0 || device >= ndev) return td3_fail(CN_ERR_ARG, "cn_ddpg_create: bad device ordinal");
+    DevScope scope(device);
+    cn_ddpg_s* h = new (std::nothrow) cn_ddpg_s();
+    if (!h) return td3_fail(CN_ERR_ARG, "cn_ddpg_create: out of memory");
+    h->cfg = c; h->device = device; h->B = c.batch; h->D = c.obs_dim; h->Dc = c.obs_dim + 2; h->H = c.hidden;
+    const size_t B = h->B, Dc = h->Dc, H = h->H;
+    h->qnt = (int)((H + 15) / 16); h->dant = (int)((H + 31) / 32);
+    const size_t words = 2 + 8                                         // counter, pw (8-byte aligned: first)
+                         + 2 * B * Dc + 2 * B + 2 * B                  // xs, x2, r, d, logits
+                         + 4 * B * H + 6 * B * H + 6 * B * H           // t_h, a_h, c_h, dz
+                         + 3 * B * h->qnt + 2 * B * h->dant + B + 2 * B // qpart, dapart, dq, dl
+                         + 1 + 4 + 2;                                  // loss, adam, steps
+    size_t mom_words = 0;
+    for (int net = 0; net < 2; ++net) for (int j = 0; j < 6; ++j) mom_words += 2 * ddpg_param_count(h, net, j);
+    hipError_t e = hipMalloc(&h->pool, (words + mom_words) * sizeof(float));
+    if (e != hipSuccess) { delete h; return td3_fail(CN_ERR_HIP, std::string("cn_ddpg_create: hipMalloc: ") + hipGetErrorString(e)); }
+    e = hipMemset(h->pool, 0, (words + mom_words) * sizeof(float));
+    if (e != hipSuccess) { (void)hipFree(h->pool); delete h; return td3_fail(CN_ERR_HIP, std::string("cn_ddpg_create: hipMemset: ") + hipGetErrorString(e)); }
+    float* q = h->pool;
+    auto take = [&](size_t n) { float* r_ = q; q += n; return r_; };
+    h->counter = (unsigned long long*)take(2);
+    h->pw = (double*)take(8);
+    { const double one[4] = {1.0, 1.0, 1.0, 1.0}; e = hipMemcpy(h->pw, one, sizeof(one), hipMemcpyHostToDevice); }
+    if (e != hipSuccess) { (void)hipFree(h->pool); delete h; return td3_fail(CN_ERR_HIP, std::string("cn_ddpg_create: hipMemcpy: ") + hipGetErrorString(e)); }
+    h->xs = take(B * Dc); h->x2 = take(B * Dc); h->r = take(B); h->d = take(B); h->logits = take(2 * B);
+    h->t_h1 = take(B * H); h->t_h2 = take(B * H); h->a_h1 = take(B * H); h->a_h2 = take(B * H);
+    for (int z = 0; z < 3; ++z) { h->c_h1[z] = take(B * H); h->c_h2[z] = take(B * H); }
+    h->dz2c = take(B * H); h->dz1c = take(B * H); h->dz2p = take(B * H); h->dz1p = take(B * H); h->dz2a = take(B * H); h->dz1a = take(B * H);
+    h->qpart = take(3 * B * h->qnt); h->dapart = take(2 * B * h->dant); h->dq = take(B); h->dl = take(2 * B);
+    h->loss = take(1); h->adam = take(4); h->steps = take(2);
+    for (int net = 0; net < 2; ++net) for (int j = 0; j < 6; ++j) for (int k = 0; k < 2; ++k) h->mom[net][j][k] = take(ddpg_param_count(h, net, j));
+    *out = h;
+    return CN_OK;
+}
+
+extern "C" void cn_ddpg_destroy(cn_ddpg_handle h)
+{
+    if (!h) return;
+    DevScope scope(h->device);
+    (void)hipFree(h->pool);
+    delete h;
+}
+
+extern "C" const float* cn_ddpg_loss_dev(cn_ddpg_handle h) { return h ? h->loss : nullptr; }
+
+extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream)
+{
+    if (!h) return td3_fail(CN_ERR_ARG, "cn_ddpg_update: null handle");
+    const cn_ddpg_config& c = h->cfg;
+    if (!batch && (!c.replay_s || !c.replay_a || !c.replay_r || !c.replay_s2 || !c.replay_d || !c.replay_size_dev))
+        return td3_fail(CN_ERR_ARG, "cn_ddpg_update: no explicit batch and no replay ring in the configuration");
+    if (batch && (!batch->s || !batch->a || !batch->r || !batch->s2 || !batch->d)) return td3_fail(CN_ERR_ARG, "cn_ddpg_update: null batch pointer");
+    if (batch && batch->target_noise) return td3_fail(CN_ERR_ARG, "cn_ddpg_update: DDPG has no target-policy noise (batch->target_noise must be NULL)");
+    DevScope scope(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int B = h->B, D = h->D, Dc = h->Dc, H = h->H;
+    // 1. sample / gather (ddpg.py:208-214); no noise is drawn
+    PrepArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    if (batch) { pa.rs = batch->s; pa.ra = batch->a; pa.rr = batch->r; pa.rs2 = batch->s2; pa.rd = batch->d; }
+    else { pa.rs = c.replay_s; pa.ra = c.replay_a; pa.rr = c.replay_r; pa.rs2 = c.replay_s2; pa.rd = c.replay_d; pa.size_dev = c.replay_size_dev; }
+    pa.xs = h->xs; pa.x2 = h->x2; pa.r = h->r; pa.d = h->d; pa.noise = nullptr; pa.counter = h->counter;
+    pa.seed = c.seed; pa.B = B; pa.D = D;
+    hipLaunchKernelGGL(td3_prep_kernel, dim3(B), dim3(256), 0, st, pa);
+
+    auto fwd_job = [&](GemmJob& j, const float* X, int ldx, int K, const float* W, const float* b, float* Y) {
+        memset(&j, 0, sizeof(j));
+        j.A = X; j.B = W; j.C = Y; j.bias = b; j.I = B; j.J = H; j.R = K; j.lda = ldx; j.ldb = K; j.ldc = H; j.relu = 1;
+    };
+    auto head_job = [&](GemmJob& j, const float* h2, const cn_td3_mlp& pol, float* logits) {     // action columns = pol's heads, no noise
+        j.R = D; j.hd_h2 = h2; j.hd_W3 = pol.w3; j.hd_b3 = pol.b3; j.hd_noise = nullptr; j.hd_logits = logits; j.hd_H = H;
+        j.hd_max_v = c.max_v; j.hd_max_w = c.max_w;
+    };
+    auto bwd_data_job = [&](GemmJob& j, const float* dY, const float* W, const float* mask, float* dX) {
+        memset(&j, 0, sizeof(j));
+        j.A = dY; j.B = W; j.C = dX; j.mask = mask; j.I = B; j.J = H; j.R = H; j.lda = H; j.ldb = H; j.ldc = H;
+    };
+    auto wgrad_job = [&](GemmJob& j, const float* dY, const float* X, int ldx, int K, float* W, float* bparam, int net, int wj,
+                         const float* adam, float* tgt, float* btgt) {
+        memset(&j, 0, sizeof(j));
+        j.A = dY; j.B = X; j.C = W; j.I = H; j.J = K; j.R = B; j.lda = H; j.ldb = ldx; j.ldc = K;
+        j.m = h->mom[net][wj][0]; j.v = h->mom[net][wj][1]; j.bparam = bparam; j.bm = h->mom[net][wj + 1][0]; j.bv = h->mom[net][wj + 1][1];
+        j.adam = adam; j.tgt = tgt; j.btgt = btgt;
+    };
+    GemmArgs ga;
+    ga.beta1 = c.beta1; ga.beta2 = c.beta2; ga.eps = c.eps; ga.tau = c.tau;
+    ga.tick.adam = h->adam; ga.tick.steps = h->steps; ga.tick.pw = h->pw; ga.tick.counter = h->counter; ga.tick.do_actor = 1;   // both optimizers step on every update
+    ga.tick.lr_critic = c.lr_critic; ga.tick.lr_actor = c.lr_actor; ga.tick.beta1 = c.beta1; ga.tick.beta2 = c.beta2;
+    ga.do_tick = 0;
+    // 2-3. actor_t's hidden layers on s2 (ddpg.py:219), actor's on s (:216)
+    fwd_job(ga.job[0], h->x2, Dc, D, c.actor_t.w1, c.actor_t.b1, h->t_h1);
+    fwd_job(ga.job[1], h->xs, Dc, D, c.actor.w1, c.actor.b1, h->a_h1);
+    launch_gemm<GEMM_F>(ga, 2, st);
+    fwd_job(ga.job[0], h->t_h1, H, H, c.actor_t.w2, c.actor_t.b2, h->t_h2);
+    fwd_job(ga.job[1], h->a_h1, H, H, c.actor.w2, c.actor.b2, h->a_h2);
+    launch_gemm<GEMM_F>(ga, 2, st);
+    // 4. the critics' first layers: critic on (s, a) (:229), critic on (s, pi(s)) (:216, the logits kept for the heads' backward),
+    // critic_t on (s2, pi_t(s2)) (:220) -- the policies' last layers and heads evaluated in place of the action columns
+    fwd_job(ga.job[0], h->xs, Dc, Dc, c.critic.w1, c.critic.b1, h->c_h1[0]);
+    fwd_job(ga.job[1], h->xs, Dc, Dc, c.critic.w1, c.critic.b1, h->c_h1[1]);
+    head_job(ga.job[1], h->a_h2, c.actor, h->logits);
+    fwd_job(ga.job[2], h->x2, Dc, Dc, c.critic_t.w1, c.critic_t.b1, h->c_h1[2]);
+    head_job(ga.job[2], h->t_h2, c.actor_t, nullptr);
+    launch_gemm<GEMM_F>(ga, 3, st);
+    // 5. their second layers; q = h2 . W3 + b3 as per-tile partial sums of critic (slot 0) and critic_t (slot 2); on the pi(s)
+    // branch the first link of -mean Q (:217): dz = -(1 / B) W3 [h2 > 0]; the tick
+    fwd_job(ga.job[0], h->c_h1[0], H, H, c.critic.w2, c.critic.b2, h->c_h2[0]);
+    ga.job[0].qp_w3 = c.critic.w3; ga.job[0].qp_b3 = c.critic.b3; ga.job[0].qp_out = h->qpart; ga.job[0].qp_nt = h->qnt;
+    fwd_job(ga.job[1], h->c_h1[1], H, H, c.critic.w2, c.critic.b2, h->c_h2[1]);
+    ga.job[1].dz_w3 = c.critic.w3; ga.job[1].dz_out = h->dz2p; ga.job[1].dz_rows = (float)B;
+    fwd_job(ga.job[2], h->c_h1[2], H, H, c.critic_t.w2, c.critic_t.b2, h->c_h2[2]);
+    ga.job[2].qp_w3 = c.critic_t.w3; ga.job[2].qp_b3 = c.critic_t.b3; ga.job[2].qp_out = h->qpart + (size_t)2 * B * h->qnt; ga.job[2].qp_nt = h->qnt;
+    ga.do_tick = 1;
+    launch_gemm<GEMM_F>(ga, 3, st);
+    ga.do_tick = 0;
+    // 6. both through the PRE-update critic: the TD target y = r + (1 - d) gamma q_t (:221-222, one target), the MSE gradient
+    // (:230) and dz1 = (dz2 W2) [h1 > 0]; the pi(s) branch on to the action (the two action columns of W1)
+    bwd_data_job(ga.job[0], h->c_h2[0], c.critic.w2, h->c_h1[0], h->dz1c);
+    {
+        GemmJob& j = ga.job[0];
+        j.hb_h2 = h->c_h2[0]; j.hb_w3 = c.critic.w3; j.hb_qpart = h->qpart; j.hb_qnt = h->qnt; j.hb_net = 0; j.hb_single = 1;
+        j.hb_r = h->r; j.hb_d = h->d; j.hb_gamma = c.gamma; j.hb_dq = h->dq; j.hb_dz2 = h->dz2c;
+    }
+    bwd_data_job(ga.job[1], h->dz2p, c.critic.w2, h->c_h1[1], h->dz1p);
+    ga.job[1].da_w = c.critic.w1 + D; ga.job[1].da_ld = Dc; ga.job[1].da_out = h->dapart; ga.job[1].da_nt = h->dant;
+    launch_gemm<GEMM_G>(ga, 2, st);
+    // 7. the actor: through the heads' derivatives and its second hidden layer
+    bwd_data_job(ga.job[0], h->a_h2, c.actor.w2, h->a_h1, h->dz1a);
+    {
+        GemmJob& j = ga.job[0];
+        j.ab_h2 = h->a_h2; j.ab_w3 = c.actor.w3; j.ab_dapart = h->dapart; j.ab_dant = h->dant; j.ab_logits = h->logits;
+        j.ab_max_v = c.max_v; j.ab_max_w = c.max_w; j.ab_dl = h->dl; j.ab_dz2 = h->dz2a;
+    }
+    launch_gemm<GEMM_G>(ga, 1, st);
+    // 8. weight gradients folded into both Adam steps (:233-238) and the soft updates of both targets (:241-242, from the
+    // stepped weights); linear3's gradients are the one- / two-row jobs; loss_out = the critic's MSE
+    wgrad_job(ga.job[0], h->dz2c, h->c_h1[0], H, H, c.critic.w2, c.critic.b2, 1, 2, h->adam, c.critic_t.w2, c.critic_t.b2);
+    wgrad_job(ga.job[1], h->dz1c, h->xs, Dc, Dc, c.critic.w1, c.critic.b1, 1, 0, h->adam, c.critic_t.w1, c.critic_t.b1);
+    wgrad_job(ga.job[2], h->dq, h->c_h2[0], H, H, c.critic.w3, c.critic.b3, 1, 4, h->adam, c.critic_t.w3, c.critic_t.b3);
+    ga.job[2].I = 1; ga.job[2].lda = 1; ga.job[2].loss_out = h->loss;
+    wgrad_job(ga.job[3], h->dz2a, h->a_h1, H, H, c.actor.w2, c.actor.b2, 0, 2, h->adam + 2, c.actor_t.w2, c.actor_t.b2);
+    wgrad_job(ga.job[4], h->dz1a, h->xs, Dc, D, c.actor.w1, c.actor.b1, 0, 0, h->adam + 2, c.actor_t.w1, c.actor_t.b1);
+    wgrad_job(ga.job[5], h->dl, h->a_h2, H, H, c.actor.w3, c.actor.b3, 0, 4, h->adam + 2, c.actor_t.w3, c.actor_t.b3);
+    ga.job[5].I = 2; ga.job[5].lda = 2;
+    launch_gemm<GEMM_H>(ga, 6, st);
     TD3CHK(hipGetLastError());
     return CN_OK;
 }

@@ -329,6 +329,38 @@ int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* batch, void
 const float* cn_td3_loss_dev(cn_td3_handle h);      /* device pointer: the first critic's MSE loss of the last update */
 const char* cn_td3_last_error(void);
 
+/* The DDPG update -- Agent.learn of the reference's ddpg.py:198-243, the baseline learner of start_ddpg_training.py -- on the
+ * same GEMM kernels as cn_td3_update (crowdnav_td3.hip), 8 launches per update.  One critic and one target critic, no policy
+ * delay, no target-policy noise: y = r + (1 - d) gamma Q_t(s2, pi_t(s2)) (ddpg.py:219-222), critic loss mean((Q(s, a) - y)^2)
+ * (:228-230), actor loss -mean Q(s, pi(s)) (:216-217) back-propagated through the critic's PRE-update weights (the actor step,
+ * :233-235, precedes the critic step, :237-239; the gradient the actor loss leaves on the critic is discarded by the critic's
+ * zero_grad), then both Adam steps and the soft updates of both targets (:241-242, soft_update :244-254).  Parameters, Adam
+ * state and arithmetic as cn_td3_*: the caller's nn.Linear storages stepped in place, moments zero at create, float32. */
+typedef struct cn_ddpg_config {
+    int32_t obs_dim;         /* actor input width; the critic takes obs_dim + 2 (ddpg.py:97) */
+    int32_t hidden;          /* TRAIN_DDPG:58 -> 256 */
+    int32_t batch;           /* TRAIN_DDPG:55 -> 64 */
+    int32_t reserved0;
+    float gamma, tau;        /* ddpg.yaml -> 0.99, 0.001 */
+    float lr_actor, lr_critic, beta1, beta2, eps;   /* ddpg.yaml 1e-4, 1e-3; torch.optim.Adam's 0.9, 0.999, 1e-8 (ddpg.py:138, 143) */
+    float max_v, max_w;                             /* TRAIN_DDPG:60-61 -> 0.22, 2.0 (the actor's heads, ddpg.py:87-88) */
+    float reserved1;
+    cn_td3_mlp actor, actor_t, critic, critic_t;
+    const float *replay_s, *replay_a, *replay_r, *replay_s2, *replay_d;   /* as cn_td3_config (ReplayBuffer, ddpg.py:21-39) */
+    const int64_t* replay_size_dev;
+    uint64_t seed;           /* keys the replay indices with the handle's update counter */
+} cn_ddpg_config;
+typedef struct cn_ddpg_s* cn_ddpg_handle;
+/* Shape limits as cn_td3_create's (obs_dim >= 1, 1 <= hidden, batch <= 4096); errors through cn_td3_last_error.
+ * Replaces the construction of ddpg.py:131-151 minus the networks themselves (the caller's, hard-copied to the targets). */
+int cn_ddpg_create(const cn_ddpg_config* cfg, int device, cn_ddpg_handle* out);
+void cn_ddpg_destroy(cn_ddpg_handle h);
+/* One update: ddpg.py:198-243 (learn), with soft_update (:244-254).  batch NULL = sample the replay (ReplayBuffer.sample,
+ * ddpg.py:33-36, uniform on the device); an explicit batch must have target_noise == NULL.  Enqueues only (capturable into a
+ * hipGraph on one stream), reads nothing from the host. */
+int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream);
+const float* cn_ddpg_loss_dev(cn_ddpg_handle h);    /* device pointer: the critic's MSE loss of the last update (ddpg.py:230) */
+
 /* The collection loop's bookkeeping between Env.step and Agent.learn (start_td3_training.py:129-149) for a batch of environments,
  * without a host read: ReplayBuffer.add (td3.py:24-31) into a ring on the device, and the per-episode record TRAIN:139-149 prints
  * and utils.record_data writes.  (crowdnav.td3.DeviceReplay and crowdnav.train.DeviceEpisodeLog do the same through ~35 PyTorch
