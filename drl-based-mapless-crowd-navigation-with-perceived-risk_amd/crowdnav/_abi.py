@@ -33,8 +33,8 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_observe_external",
            "cn_policy_tail", "cn_actor_pack_weights", "cn_actor_forward", "cn_step_sequence", "cn_rollout_policy", "cn_get_counters",
            "cn_get_returns", "cn_debug_env", "cn_lds_bytes", "cn_near_separate", "cn_snapshot_size", "cn_snapshot", "cn_restore",
-           "cn_td3_create", "cn_td3_destroy", "cn_td3_update", "cn_td3_loss_dev", "cn_td3_last_error",
-           "cn_ddpg_create", "cn_ddpg_destroy", "cn_ddpg_update", "cn_ddpg_loss_dev",
+           "cn_td3_create", "cn_td3_destroy", "cn_td3_update", "cn_td3_loss_dev", "cn_td3_batch_dev", "cn_td3_last_error",
+           "cn_ddpg_create", "cn_ddpg_destroy", "cn_ddpg_update", "cn_ddpg_loss_dev", "cn_ddpg_batch_dev",
            "cn_replay_write", "cn_episode_log_add"]
 
 
@@ -257,11 +257,13 @@ def lib():
         L.cn_td3_destroy.argtypes = [vp]; L.cn_td3_destroy.restype = None
         L.cn_td3_update.argtypes = [vp, C.c_int, C.POINTER(CnTd3Batch), vp]
         L.cn_td3_loss_dev.argtypes = [vp]; L.cn_td3_loss_dev.restype = vp
+        L.cn_td3_batch_dev.argtypes = [vp, C.c_int]; L.cn_td3_batch_dev.restype = vp
         L.cn_td3_last_error.restype = C.c_char_p
         L.cn_ddpg_create.argtypes = [C.POINTER(CnDdpgConfig), C.c_int, C.POINTER(vp)]
         L.cn_ddpg_destroy.argtypes = [vp]; L.cn_ddpg_destroy.restype = None
         L.cn_ddpg_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]
         L.cn_ddpg_loss_dev.argtypes = [vp]; L.cn_ddpg_loss_dev.restype = vp
+        L.cn_ddpg_batch_dev.argtypes = [vp, C.c_int]; L.cn_ddpg_batch_dev.restype = vp
         L.cn_replay_write.argtypes = [C.POINTER(CnReplayRing), vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
         L.cn_episode_log_add.argtypes = [C.POINTER(CnEpisodeLog), vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, C.c_int, vp]
         _lib = L

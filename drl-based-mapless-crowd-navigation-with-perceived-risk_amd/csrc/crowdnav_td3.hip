@@ -790,6 +790,13 @@ extern "C" void cn_td3_destroy(cn_td3_handle h)
 
 extern "C" const float* cn_td3_loss_dev(cn_td3_handle h) { return h ? h->loss : nullptr; }
 
+// the batch td3_prep_kernel gathered for the last update: written by that launch only, read (never written) by the GEMMs after it
+extern "C" const float* cn_td3_batch_dev(cn_td3_handle h, int what)
+{
+    if (!h) return nullptr;
+    switch (what) { case 0: return h->xs; case 1: return h->x2; case 2: return h->r; case 3: return h->d; case 4: return h->noise; default: return nullptr; }
+}
+
 extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* batch, void* stream)
 {
     if (!h) return td3_fail(CN_ERR_ARG, "cn_td3_update: null handle");
@@ -999,6 +1006,12 @@ extern "C" void cn_ddpg_destroy(cn_ddpg_handle h)
 }
 
 extern "C" const float* cn_ddpg_loss_dev(cn_ddpg_handle h) { return h ? h->loss : nullptr; }
+
+extern "C" const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what)     // as cn_td3_batch_dev; no target noise (what 4: NULL)
+{
+    if (!h) return nullptr;
+    switch (what) { case 0: return h->xs; case 1: return h->x2; case 2: return h->r; case 3: return h->d; default: return nullptr; }
+}
 
 extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream)
 {

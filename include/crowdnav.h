@@ -327,6 +327,14 @@ void cn_td3_destroy(cn_td3_handle h);
  * Enqueues only (capturable into a hipGraph). */
 int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* batch, void* stream);
 const float* cn_td3_loss_dev(cn_td3_handle h);      /* device pointer: the first critic's MSE loss of the last update */
+/* Device pointer, read only: the batch the last update gathered (its first launch, td3_prep_kernel, writes these buffers and the
+ * later launches only read them), valid until the next update is enqueued.  what = 0: [s | a] [batch][obs_dim + 2]; 1: s2 in the
+ * same layout, where only the columns < obs_dim are defined; 2: r [batch]; 3: d [batch]; 4: the target-policy noise after the
+ * scale and the clip [batch][2].  Other values of what, or a NULL handle: NULL.
+ * On the replay path row m of update number c (counting from 0 at cn_td3_create; every update counts, whether it passes an
+ * explicit batch or not, whether it steps the actor or not) is ring row mix64(mix64(seed ^ mix64(c)) ^ m) % max(*replay_size_dev, 1)
+ * (mix64: splitmix64's finaliser), and its noise is Box-Muller on the same hash with c ^ 0x5bd1e995 in place of c. */
+const float* cn_td3_batch_dev(cn_td3_handle h, int what);
 const char* cn_td3_last_error(void);
 
 /* The DDPG update -- Agent.learn of the reference's ddpg.py:198-243, the baseline learner of start_ddpg_training.py -- on the
@@ -360,6 +368,7 @@ void cn_ddpg_destroy(cn_ddpg_handle h);
  * hipGraph on one stream), reads nothing from the host. */
 int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream);
 const float* cn_ddpg_loss_dev(cn_ddpg_handle h);    /* device pointer: the critic's MSE loss of the last update (ddpg.py:230) */
+const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what);   /* as cn_td3_batch_dev, same indices; what = 4 (no noise): NULL */
 
 /* The collection loop's bookkeeping between Env.step and Agent.learn (start_td3_training.py:129-149) for a batch of environments,
  * without a host read: ReplayBuffer.add (td3.py:24-31) into a ring on the device, and the per-episode record TRAIN:139-149 prints
