@@ -35,6 +35,7 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_get_returns", "cn_debug_env", "cn_lds_bytes", "cn_near_separate", "cn_snapshot_size", "cn_snapshot", "cn_restore",
            "cn_td3_create", "cn_td3_destroy", "cn_td3_update", "cn_td3_loss_dev", "cn_td3_batch_dev", "cn_td3_last_error",
            "cn_ddpg_create", "cn_ddpg_destroy", "cn_ddpg_update", "cn_ddpg_loss_dev", "cn_ddpg_batch_dev",
+           "cn_dqn_create", "cn_dqn_destroy", "cn_dqn_update", "cn_dqn_loss_dev", "cn_dqn_batch_dev", "cn_dqn_act",
            "cn_replay_write", "cn_episode_log_add"]
 
 
@@ -128,6 +129,28 @@ class CnDdpgConfig(C.Structure):
                 ("actor", CnTd3Mlp), ("actor_t", CnTd3Mlp), ("critic", CnTd3Mlp), ("critic_t", CnTd3Mlp),
                 ("replay_s", C.c_void_p), ("replay_a", C.c_void_p), ("replay_r", C.c_void_p), ("replay_s2", C.c_void_p), ("replay_d", C.c_void_p),
                 ("replay_size_dev", C.c_void_p), ("seed", C.c_uint64)]
+
+
+class CnDqnConfig(C.Structure):
+    """Mirror of `cn_dqn_config` (include/crowdnav.h)."""
+    _fields_ = [("obs_dim", C.c_int32), ("obs_ld", C.c_int32), ("hidden", C.c_int32), ("batch", C.c_int32),
+                ("gamma", C.c_float), ("lr", C.c_float), ("rho", C.c_float), ("eps", C.c_float),
+                ("target_every", C.c_int32), ("learn_start", C.c_int32), ("q", CnTd3Mlp), ("q_t", CnTd3Mlp),
+                ("replay_s", C.c_void_p), ("replay_a", C.c_void_p), ("replay_r", C.c_void_p), ("replay_s2", C.c_void_p), ("replay_d", C.c_void_p),
+                ("replay_size_dev", C.c_void_p), ("seed", C.c_uint64)]
+
+
+class CnDqnBatch(C.Structure):
+    """Mirror of `cn_dqn_batch`: s, a (int32 indices), r, s2, d, perm (int32, or None)."""
+    _fields_ = [(n, C.c_void_p) for n in ("s", "a", "r", "s2", "d", "perm")]
+
+
+class CnDqnActIO(C.Structure):
+    """Mirror of `cn_dqn_act_io` (include/crowdnav.h)."""
+    _fields_ = [("obs", C.c_void_p), ("obs_ld", C.c_int64), ("n", C.c_int32), ("obs_dim", C.c_int32), ("hidden", C.c_int32),
+                ("reserved", C.c_int32), ("q", CnTd3Mlp), ("epsilon", C.c_double), ("epsilon_discount", C.c_double),
+                ("epsilon_min", C.c_double), ("episodes_dev", C.c_void_p), ("seed", C.c_uint64),
+                ("counter", C.c_uint64), ("action", C.c_void_p), ("twist", C.c_void_p), ("q_out", C.c_void_p)]
 
 
 class CnTd3Batch(C.Structure):
@@ -264,6 +287,12 @@ def lib():
         L.cn_ddpg_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]
         L.cn_ddpg_loss_dev.argtypes = [vp]; L.cn_ddpg_loss_dev.restype = vp
         L.cn_ddpg_batch_dev.argtypes = [vp, C.c_int]; L.cn_ddpg_batch_dev.restype = vp
+        L.cn_dqn_create.argtypes = [C.POINTER(CnDqnConfig), C.c_int, C.POINTER(vp)]
+        L.cn_dqn_destroy.argtypes = [vp]; L.cn_dqn_destroy.restype = None
+        L.cn_dqn_update.argtypes = [vp, C.POINTER(CnDqnBatch), vp]
+        L.cn_dqn_loss_dev.argtypes = [vp]; L.cn_dqn_loss_dev.restype = vp
+        L.cn_dqn_batch_dev.argtypes = [vp, C.c_int]; L.cn_dqn_batch_dev.restype = vp
+        L.cn_dqn_act.argtypes = [C.POINTER(CnDqnActIO), C.c_int, vp]
         L.cn_replay_write.argtypes = [C.POINTER(CnReplayRing), vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
         L.cn_episode_log_add.argtypes = [C.POINTER(CnEpisodeLog), vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, C.c_int, vp]
         _lib = L

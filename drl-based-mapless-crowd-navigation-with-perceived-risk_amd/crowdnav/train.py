@@ -10,7 +10,14 @@ count at a log interval is rarely a round number); every save also rewrites `lat
 `--algo ddpg` trains the reference's baseline learner instead (start_ddpg_training.py, ddpg.py; crowdnav.ddpg): batch 64, actor
 lr 1e-4, critic lr 1e-3, tau 0.001 unless --batch / --lr-actor / --lr-critic / --tau are given, no exploration noise
 (TRAIN_DDPG:100) unless --ou-noise, checkpoints ddpg_{actor,critic}_model_ep<N>.pt, CSV ddpg_training.csv; `--learner fused` is
-cn_ddpg_update.  `--obs-layout 1` is the 363-input observation of the shipped DDPG checkpoints:
+cn_ddpg_update.  `--obs-layout 1` is the 363-input observation of the shipped DDPG checkpoints.
+
+`--algo dqn` trains the reference's discrete learner (start_dqn_training.py, deepq.py; crowdnav.dqn) on obs_layout 1 with
+--max-steps 250 (dqn.yaml) unless given: the first --dqn-inputs (361) columns, the action index -> twist, epsilon from --epsilon
+(1.0, the logged run; dqn.yaml's 0.0 by flag) discounted by --epsilon-discount per finished episode on the device, checkpoints
+dqn_model_ep<N>.pt / .json, CSV dqn_training.csv; `--learner fused` is cn_dqn_update, `--evaluate` is greedy:
+
+    python -m crowdnav.train --algo dqn --scenario training_as_logged --waypoint-reward 0 --envs 16 --updates 16 --csv --learner fused
 
     python -m crowdnav.train --algo ddpg --scenario training_as_logged --waypoint-reward 0 --envs 16 --updates 16 --csv --learner fused
     python -m crowdnav.train --algo ddpg --evaluate --load runs/ddpg --obs-layout 1 --scenario crossing_8
@@ -37,7 +44,7 @@ from . import presets
 from .config import Config
 from .env import VecEnv
 from .rollout import EpisodeStats, evaluate
-from . import ddpg, td3
+from . import ddpg, dqn, td3
 
 
 def make_env(scenario, n_envs, max_steps, seed, device, ped_vmax=None, **switches):
@@ -141,6 +148,99 @@ def save_checkpoint(agent, outdir, episodes):
 
 
 CHECKPOINT_NETS = dict(td3=("actor", "critic1", "critic2"), ddpg=("actor", "critic"))
+
+
+def make_dqn_agent(a, obs_ld, device, memory_size):
+    """The DQN learner with the reference's defaults (TRAIN_DQN:45-57); --batch / --target-update / --epsilon override them."""
+    if a.dqn_inputs > obs_ld:
+        raise ValueError("--dqn-inputs %d > the observation width %d (use --obs-layout 1)" % (a.dqn_inputs, obs_ld))
+    return dqn.Agent(obs_dim=a.dqn_inputs, obs_ld=obs_ld, batch_size=a.batch or 64, memory_size=memory_size, epsilon=a.epsilon,
+                     epsilon_discount=a.epsilon_discount, target_update=a.target_update, device=device, seed=a.seed)
+
+
+def save_dqn_checkpoint(agent, a, outdir, episodes):
+    agent.save(outdir, episodes, nsteps=a.max_steps)
+    tmp = os.path.join(outdir, ".latest_checkpoint.txt.%d" % os.getpid())
+    open(tmp, "w").write("%d\n" % episodes)
+    os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
+
+
+def train_dqn(a):
+    """start_dqn_training.py:84-152 for N environments: cn_dqn_act (epsilon from the device's count of finished episodes) ->
+    env.step -> replay (the index in column 0) -> `--updates` learnOnMiniBatch calls per launch once the replay holds more than
+    learnStart rows.  Enqueue-only between log intervals, like train()."""
+    dev = a.device
+    torch.cuda.set_device(dev)
+    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, **env_switches(a))
+    agent = make_dqn_agent(a, env.D, "cuda:%d" % dev, a.memory)
+    eps0 = a.epsilon
+    if a.load:                                      # TRAIN_DQN:62-82: the weights, and epsilon from the parameter record
+        a.load_episode = resolve_load_episode(a.load, a.load_episode)
+        agent.load_models(os.path.join(a.load, "dqn_model_ep%d.pt" % a.load_episode),
+                          os.path.join(a.load, "dqn_model_ep%d.json" % a.load_episode))
+        eps0 = agent.epsilon0
+    if a.learner == "fused":
+        agent.enable_fused_update()
+    stats = EpisodeStats()
+    os.makedirs(a.out, exist_ok=True)
+    resumed = bool(a.load) and os.path.abspath(a.load) == os.path.abspath(a.out)
+    obs = env.reset()
+    t0 = time.time()
+    episodes, env_steps, updates_done = 0, 0, 0
+    log = open(os.path.join(a.out, "progress.txt"), "a")
+    N = env.N
+    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
+    prev = torch.empty_like(obs)
+    act2 = torch.zeros((N, 2), dtype=torch.float32, device=obs.device)
+    elog = DeviceEpisodeLog(obs.device, a.max_csv_rows)
+    learning = False
+    next_ckpt = a.checkpoint_every
+    step_s = (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0
+    for it in range(1, a.launches + 1):
+        idx, twist = agent.act_fused(obs, episodes_dev=elog.n)               # TRAIN_DQN:89-90, 103-104
+        act2[:, 0] = idx.float()
+        prev.copy_(obs)
+        obs, reward, done = env.step(twist, auto_reset="next")
+        keep = ~resetting
+        agent.memory.add_masked(prev, act2, reward, obs, done, keep)         # TRAIN_DQN:112
+        resetting = done.bool()
+        elog.add(done, env.counters(), env.returns()[0], it, keep)
+        if not learning:
+            learning = agent.memory.ready(agent.learn_start)                # TRAIN_DQN:114, deepq.py:221
+        if learning:
+            for u in range(a.updates):
+                updates_done += 1
+                agent.learn(updates_done)
+        if it % a.log_every == 0 or it == a.launches:
+            rows, tot = elog.flush()
+            ne = int(tot[0])
+            episodes += ne; env_steps += int(tot[4])
+            for r in rows.tolist():
+                seen = int(r[6])
+                stats.add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
+                          1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
+            agent.epsilon = dqn.epsilon_after(episodes + 1, eps0, a.epsilon_discount)   # what the device used (the json records it)
+            if ne:
+                line = "launch %6d  env-steps %10d  updates %9d  episodes %8d  success %.3f  mean return %8.1f  epsilon %.3f  %.0f s" % (
+                    it, env_steps, updates_done, episodes, tot[1] / ne, tot[2] / ne, agent.epsilon, time.time() - t0)
+                print(line, flush=True); log.write(line + "\n"); log.flush()
+            if a.csv:
+                stats.append_csv(a.out, "dqn_training", resume=resumed)
+            if episodes >= next_ckpt:                 # TRAIN_DQN:132-144 (every 100 episodes there), checked at log time
+                save_dqn_checkpoint(agent, a, a.out, episodes)
+                while next_ckpt <= episodes:
+                    next_ckpt += a.checkpoint_every
+            if a.time_limit and time.time() - t0 > a.time_limit:
+                break
+    agent.memory.sync_len()
+    save_dqn_checkpoint(agent, a, a.out, episodes)
+    last = stats.rows[-500:]
+    if last:
+        line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f | %d updates, %d env-steps, %.0f s" % (
+            len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
+            updates_done, env_steps, time.time() - t0)
+        print(line, flush=True); log.write(line + "\n"); log.flush()
+    return agent, episodes
 
 
 def make_agent(a, obs_dim, device, **kw):
@@ -282,8 +382,13 @@ def train(a):
 def run_evaluation(a):
     torch.cuda.set_device(a.device)
     env = make_env(a.scenario, a.envs, a.max_steps, a.seed, a.device, a.ped_vmax, **env_switches(a))
-    agent = make_agent(a, env.D, "cuda:%d" % a.device, memory_size=16)
-    load_checkpoint(agent, a)
+    if getattr(a, "algo", "td3") == "dqn":           # greedy: Agent.act(add_noise=False) takes epsilon = 0
+        agent = make_dqn_agent(a, env.D, "cuda:%d" % a.device, 16)
+        a.load_episode = resolve_load_episode(a.load, a.load_episode)
+        agent.load_models(os.path.join(a.load, "dqn_model_ep%d.pt" % a.load_episode))
+    else:
+        agent = make_agent(a, env.D, "cuda:%d" % a.device, memory_size=16)
+        load_checkpoint(agent, a)
     st = evaluate(env, agent, episodes_per_env=a.episodes_per_env)
     n = len(st.rows)
     print("%s: %d episodes, success %.3f, failure %.3f, mean return %.1f, mean steps %.1f, ego %.3f, social %.3f" % (
@@ -295,15 +400,22 @@ def run_evaluation(a):
     return st
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The command line with the algorithm's defaults resolved (max_steps, obs_layout, out)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenario", default="training", help="training | training_as_logged | bench | {crossing,towards,ahead,random}_{4,8,12,20}")
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--launches", type=int, default=3000)
     ap.add_argument("--time-limit", type=float, default=0.0, help="stop after this many seconds (checked at log time); 0 = run all launches")
-    ap.add_argument("--max-steps", type=int, default=1000, help="nsteps (configs/td3.yaml)")
+    ap.add_argument("--max-steps", type=int, default=None, help="nsteps: configs/td3.yaml 1000; configs/dqn.yaml 250 (--algo dqn)")
     ap.add_argument("--updates", type=int, default=4, help="TD3 updates per launch")
-    ap.add_argument("--algo", default="td3", choices=["td3", "ddpg"], help="td3: start_td3_training.py; ddpg: start_ddpg_training.py (crowdnav.ddpg)")
+    ap.add_argument("--algo", default="td3", choices=["td3", "ddpg", "dqn"],
+                    help="td3: start_td3_training.py; ddpg: start_ddpg_training.py (crowdnav.ddpg); dqn: start_dqn_training.py (crowdnav.dqn)")
+    ap.add_argument("--epsilon", type=float, default=1.0, help="dqn: the initial exploration rate (the logged run: 1.0; dqn.yaml: 0.0)")
+    ap.add_argument("--epsilon-discount", type=float, default=0.995, help="dqn: dqn.yaml epsilon_discount, applied per episode while > 0.05")
+    ap.add_argument("--target-update", type=int, default=10000, help="dqn: updates between hard target copies (TRAIN_DQN:51)")
+    ap.add_argument("--dqn-inputs", type=int, default=361, choices=[361, 363], help="dqn: network inputs (TRAIN_DQN:55: 361 = the first "
+                    "361 columns of the obs_layout-1 observation)")
     ap.add_argument("--batch", type=int, default=None, help="TRAIN:62 -> 128 (td3); TRAIN_DDPG:55 -> 64 (ddpg)")
     ap.add_argument("--lr-actor", type=float, default=None, help="default: the algorithm's (td3 3e-4, ddpg 1e-4)")
     ap.add_argument("--lr-critic", type=float, default=None, help="default: the algorithm's (td3 3e-4, ddpg 1e-3)")
@@ -341,10 +453,23 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.out is None:
         a.out = "runs/%s" % a.algo
+    if a.max_steps is None:
+        a.max_steps = 250 if a.algo == "dqn" else 1000
+    if a.algo == "dqn" and a.obs_layout is None:
+        a.obs_layout = 1
+    if a.algo == "dqn" and a.reset_mode != "next":
+        ap.error("--algo dqn collects with the next-step reset only (--reset-mode next)")
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     if a.evaluate:
         return run_evaluation(a)
+    if a.algo == "dqn":
+        return train_dqn(a)
     return train(a)
 
 

@@ -124,7 +124,13 @@ struct GemmJob {
     // H, optional: A is one column (I = 1) of per-row loss gradients dq; loss_out[0] = mean squared TD error = (R / 4) sum dq^2
     float* loss_out;
 };
-struct GemmArgs { GemmJob job[6]; float beta1, beta2, eps, tau; TickArgs tick; int do_tick; };
+// (rms_*: the RMSprop instantiation of the weight-gradient kernel, td3_wgrad_kernel<true>, alone reads them -- appended after the
+// fields the Adam kernels read, so those keep their kernel-argument offsets)
+struct GemmArgs {
+    GemmJob job[6]; float beta1, beta2, eps, tau; TickArgs tick; int do_tick;
+    const int* rms_gate;                           // RMSprop: the launch steps nothing while *rms_gate == 0 (device)
+    float rms_lr, rms_rho, rms_eps;
+};
 static_assert(sizeof(GemmArgs) <= 4096, "GemmArgs travels in the kernarg segment (4 KB)");
 // target <- target (1 - tau) + local tau (TD3:297-299)
 __device__ __forceinline__ float td3_soft(float target, float local, float tau) { return target * (1.f - tau) + local * tau; }
@@ -156,8 +162,11 @@ __device__ __forceinline__ f32x2_t td3_ld2(const float* __restrict__ p, int c, i
 // X[i0 + li][16 t + 4 lk ..+3] and W[j0 + li][the same]: component e of the two vectors is the pair the lane feeds to MFMA e of
 // the block (k = 16 t + 4 lk + e on both sides).
 #define TD3_FKB 8          /* blocks a wavefront has in flight (16 dwordx4 loads) */
+// GATE = true (DQN's second chunk): the launch does nothing while *args.rms_gate == 0
+template <bool GATE>
 __global__ void __launch_bounds__(256) td3_fwd_kernel(GemmArgs args)
 {
+    if constexpr (GATE) { if (*args.rms_gate == 0) return; }
     const GemmJob& jb = args.job[blockIdx.z];
     const int I = jb.I, J = jb.J, R = jb.R;
     const int i0 = blockIdx.y * 16, j0 = blockIdx.x * 16;
@@ -254,8 +263,10 @@ __global__ void __launch_bounds__(256) td3_fwd_kernel(GemmArgs args)
 // G: a 16 x 32 tile per workgroup.  dY's rows are contiguous along the reduction (as in F), W's along the OUTPUT: lane (li, lk)
 // loads W[16 t + 4 lk + e][j0 + 2 li, + 1] for e = 0..3 -- two accumulators, columns j0 + 2 c and j0 + 2 c + 1.
 #define TD3_GKB 4
+template <bool GATE>
 __global__ void __launch_bounds__(256) td3_dgrad_kernel(GemmArgs args)
 {
+    if constexpr (GATE) { if (*args.rms_gate == 0) return; }
     const GemmJob& jb = args.job[blockIdx.z];
     const int I = jb.I, J = jb.J, R = jb.R;
     const int i0 = blockIdx.y * 16, j0 = blockIdx.x * 32;
@@ -414,13 +425,17 @@ __global__ void __launch_bounds__(256) td3_dgrad_kernel(GemmArgs args)
 // H: a 32 x 32 tile per workgroup, the batch rows split over the four wavefronts in steps of 4 (step s = wavefront s mod 4).
 // Both operands are contiguous along their output index: lane (li, lk) loads dY[4 s + lk][i0 + 2 li, + 1] and
 // X[4 s + lk][j0 + 2 li, + 1] -- 2 x 2 accumulators, acc[a][b] = the (rows i0 + 2 r + a) x (columns j0 + 2 c + b) sub-lattice.
+// RMS = false: Adam (TD3, DDPG); RMS = true: RMSprop without momentum (DQN, Keras 2's RMSprop.get_updates:
+// a = rho a + (1 - rho) g^2, p -= lr g / (sqrt(a) + eps), the accumulator in jb.m / jb.bm; no target copy, no loss).
 #define TD3_HKS 8          /* steps a wavefront has in flight (16 dwordx2 loads, 32 MFMAs) */
+template <bool RMS>
 __global__ void __launch_bounds__(256) td3_wgrad_kernel(GemmArgs args)
 {
     const GemmJob& jb = args.job[blockIdx.z];
     const int I = jb.I, J = jb.J, R = jb.R;
     const int i0 = blockIdx.y * 32, j0 = blockIdx.x * 32;
     if (i0 >= I || j0 >= J) return;
+    if constexpr (RMS) { if (*args.rms_gate == 0) return; }
     __shared__ float red[4][16][64];
     __shared__ float bred[4][4][32];
     __shared__ float lred[4][4];
@@ -434,7 +449,7 @@ __global__ void __launch_bounds__(256) td3_wgrad_kernel(GemmArgs args)
     const int amode = ic + 1 < I ? 2 : ic < I ? 1 : 0, bmode = jc + 1 < J ? 2 : jc < J ? 1 : 0;
     const bool vec = __all(bmode != 1) && J >= 2;       // (an odd last ROW of the tile -- or I = 1, the linear3 jobs -- loads one element)
     const int jcv = bmode == 2 ? jc : 0;
-    const float adam0 = jb.adam[0], adam1 = jb.adam[1];
+    const float adam0 = RMS ? 0.f : jb.adam[0], adam1 = RMS ? 0.f : jb.adam[1];
     f32x4_t acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -449,7 +464,8 @@ __global__ void __launch_bounds__(256) td3_wgrad_kernel(GemmArgs args)
         const int i = i0 + (tid >> 5) + 8 * z, j = j0 + (tid & 31);
         const bool in = i < I && j < J;
         const size_t o = in ? (size_t)i * jb.ldc + j : 0;
-        pm[z] = in ? jb.m[o] : 0.f; pv[z] = in ? jb.v[o] : 0.f; pw[z] = in ? jb.C[o] : 0.f; pt[z] = (in && jb.tgt) ? jb.tgt[o] : 0.f;
+        pm[z] = in ? jb.m[o] : 0.f; pv[z] = (!RMS && in) ? jb.v[o] : 0.f; pw[z] = in ? jb.C[o] : 0.f;
+        pt[z] = (!RMS && in && jb.tgt) ? jb.tgt[o] : 0.f;
     }
     for (int s0 = wave; s0 < ns; s0 += 4 * TD3_HKS) {
         f32x2_t av[TD3_HKS], bv[TD3_HKS];
@@ -486,7 +502,7 @@ __global__ void __launch_bounds__(256) td3_wgrad_kernel(GemmArgs args)
     bred[wave][lk][2 * li] = bs0; bred[wave][lk][2 * li + 1] = bs1;
     if (li == 0) lred[wave][lk] = ls0;
     __syncthreads();
-    if (jb.loss_out && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
+    if (!RMS && jb.loss_out && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
         float l_ = 0.f;
 #pragma unroll
         for (int w = 0; w < 4; ++w)
@@ -504,6 +520,12 @@ __global__ void __launch_bounds__(256) td3_wgrad_kernel(GemmArgs args)
         if (i >= I || j >= J) continue;
         const float gsum = ((red[0][slot][l] + red[1][slot][l]) + red[2][slot][l]) + red[3][slot][l];
         const size_t o = (size_t)i * jb.ldc + j;
+        if constexpr (RMS) {
+            const float a = args.rms_rho * pm[z] + (1.f - args.rms_rho) * (gsum * gsum);
+            jb.m[o] = a;
+            jb.C[o] = pw[z] - args.rms_lr * gsum / (sqrtf(a) + args.rms_eps);
+            continue;
+        }
         const float m = args.beta1 * pm[z] + (1.f - args.beta1) * gsum;
         const float v = args.beta2 * pv[z] + (1.f - args.beta2) * gsum * gsum;
         jb.m[o] = m; jb.v[o] = v;
@@ -518,6 +540,12 @@ __global__ void __launch_bounds__(256) td3_wgrad_kernel(GemmArgs args)
         for (int w = 0; w < 4; ++w)
 #pragma unroll
             for (int k = 0; k < 4; ++k) gsum += bred[w][k][tid];
+        if constexpr (RMS) {
+            const float a = args.rms_rho * jb.bm[i] + (1.f - args.rms_rho) * (gsum * gsum);
+            jb.bm[i] = a;
+            jb.bparam[i] = jb.bparam[i] - args.rms_lr * gsum / (sqrtf(a) + args.rms_eps);
+            return;
+        }
         const float m = args.beta1 * jb.bm[i] + (1.f - args.beta1) * gsum;
         const float v = args.beta2 * jb.bv[i] + (1.f - args.beta2) * gsum * gsum;
         jb.bm[i] = m; jb.bv[i] = v;
@@ -721,15 +749,15 @@ size_t param_count(const cn_td3_s* h, int net, int j)
     const size_t in1 = net == 0 ? (size_t)h->D : (size_t)h->Dc, out3 = net == 0 ? 2 : 1, H = (size_t)h->H;
     switch (j) { case 0: return H * in1; case 1: return H; case 2: return H * H; case 3: return H; case 4: return out3 * H; default: return out3; }
 }
-template <int MODE>
+template <int MODE, bool GATE = false>
 void launch_gemm(const GemmArgs& ga, int njobs, hipStream_t st)
 {
     constexpr int TI = MODE == GEMM_H ? 32 : 16, TJ = MODE == GEMM_F ? 16 : 32;      // the kernel's tile of C
     int gx = 0, gy = 0;
     for (int z = 0; z < njobs; ++z) { const int x_ = (ga.job[z].J + TJ - 1) / TJ, y_ = (ga.job[z].I + TI - 1) / TI; gx = x_ > gx ? x_ : gx; gy = y_ > gy ? y_ : gy; }
-    if (MODE == GEMM_F) hipLaunchKernelGGL(td3_fwd_kernel, dim3(gx, gy, njobs), dim3(256), 0, st, ga);
-    else if (MODE == GEMM_G) hipLaunchKernelGGL(td3_dgrad_kernel, dim3(gx, gy, njobs), dim3(256), 0, st, ga);
-    else hipLaunchKernelGGL(td3_wgrad_kernel, dim3(gx, gy, njobs), dim3(256), 0, st, ga);
+    if (MODE == GEMM_F) hipLaunchKernelGGL(td3_fwd_kernel<GATE>, dim3(gx, gy, njobs), dim3(256), 0, st, ga);
+    else if (MODE == GEMM_G) hipLaunchKernelGGL(td3_dgrad_kernel<GATE>, dim3(gx, gy, njobs), dim3(256), 0, st, ga);
+    else hipLaunchKernelGGL(td3_wgrad_kernel<GATE>, dim3(gx, gy, njobs), dim3(256), 0, st, ga);
 }
 }  // namespace
 
@@ -1113,6 +1141,442 @@ extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void*
     wgrad_job(ga.job[5], h->dl, h->a_h2, H, H, c.actor.w3, c.actor.b3, 0, 4, h->adam + 2, c.actor_t.w3, c.actor_t.b3);
     ga.job[5].I = 2; ga.job[5].lda = 2;
     launch_gemm<GEMM_H>(ga, 6, st);
+    TD3CHK(hipGetLastError());
+    return CN_OK;
+}
+
+// ---- DQN (deepq.py of the reference: learnOnMiniBatch, selectAction) -----------------------------------------------------------
+// The update (deepq.py:219-266 with memory.py:22-28 and Keras's fit(batch_size = 64, epochs = 1, shuffle)), 16 launches:
+//   prep   sample B rows (with replacement, td3_prep_kernel's hash), gather [s; s2] as 2B stacked rows; one extra workgroup lays
+//          out X_batch (sample m's s, then its s2 when final: 64 + F rows), draws the shuffle, marks chunk 1 (the first B shuffled
+//          rows) and chunk 2 (the F after them), and publishes the gates
+//   F x 3  online net L1 / L2 / L3 on the 2B rows, target net on the B s2 rows (its result is read only after the first copy)
+//   T      Y and dq of chunk 1 (rows outside the chunk: dq = 0); the loss
+//   G x 2, H   backward, weight gradients folded into RMSprop (td3_wgrad_kernel<true>; gate: the update is live)
+//   F x 3, T, G x 2, H   chunk 2 on the stepped weights against the same Y: all seven return at once on the device when F = 0
+//   (every GEMM here is a GATE = true instantiation; the TD3 / DDPG launches use GATE = false, the parent's instructions)
+//   copy   the hard target copy when this update is the target_every-th, and the update counter
+namespace {
+struct DqnPrepArgs {
+    const float *rs, *rr, *rs2, *rd;               // replay ring / explicit batch: s, s2 rows `ld` floats apart
+    const float* ra;                               // replay: actions [.][2], the index in column 0 (or null)
+    const int32_t* a_in;                           // explicit batch: action indices [B] (or null)
+    const int32_t* perm_in;                        // explicit shuffle of the B + F X_batch rows, or null = drawn here
+    const int64_t* size_dev;                       // live replay size, or null = the rows ARE the batch
+    float *x, *r, *d; int32_t* a;                  // [2B][ld], [B], [B], [B]
+    int32_t *chunk, *flags;                        // [2B], [8]
+    const unsigned long long* counter; unsigned long long* kcur;
+    uint64_t seed;
+    int B, ld, D, learn_start, target_every;
+};
+__device__ __forceinline__ size_t dqn_row(const DqnPrepArgs& p, int m, unsigned long long cnt)
+{
+    if (!p.size_dev) return (size_t)m;
+    const unsigned long long size = (unsigned long long)(*p.size_dev > 0 ? *p.size_dev : 1);
+    return (size_t)(cn_mix64(cn_mix64(p.seed ^ cn_mix64(cnt)) ^ (uint64_t)(uint32_t)m) % size);
+}
+__global__ void __launch_bounds__(256) dqn_prep_kernel(DqnPrepArgs p)
+{
+    const int B = p.B, tid = threadIdx.x;
+    const unsigned long long cnt = *p.counter;
+    if ((int)blockIdx.x < 2 * B) {                 // gather one stacked row
+        const int g = blockIdx.x, m = g < B ? g : g - B;
+        const size_t row = dqn_row(p, m, cnt);
+        const float* src = (g < B ? p.rs : p.rs2) + row * (size_t)p.ld;
+        float* dst = p.x + (size_t)g * p.ld;
+        for (int c = tid; c < p.D; c += blockDim.x) dst[c] = src[c];
+        if (g < B && tid == 0) {
+            p.r[m] = p.rr[row]; p.d[m] = p.rd[row];
+            p.a[m] = p.a_in ? p.a_in[m] : (int32_t)p.ra[row * 2];
+        }
+        return;
+    }
+    // the plan (the last workgroup), in LDS: perm, order and the shuffle's draws as int16 [2B] each, the final flags [B]
+    extern __shared__ __align__(8) unsigned char dqn_plan_lds[];
+    int16_t* perm = (int16_t*)dqn_plan_lds;
+    int16_t* order = perm + 2 * B;
+    int16_t* jr = order + 2 * B;
+    uint8_t* fin = (uint8_t*)(jr + 2 * B);
+    __shared__ int n_rows;
+    const bool live = !p.size_dev || *p.size_dev > (int64_t)p.learn_start;
+    for (int m = tid; m < B; m += blockDim.x) fin[m] = p.rd[dqn_row(p, m, cnt)] != 0.f ? 1 : 0;
+    for (int g = tid; g < 2 * B; g += blockDim.x) p.chunk[g] = 0;
+    __syncthreads();
+    if (tid == 0) {                                // X_batch order (deepq.py:248-262): s_m, then s2_m when final
+        int n = 0;
+        for (int m = 0; m < B; ++m) { order[n++] = (int16_t)m; if (fin[m]) order[n++] = (int16_t)(B + m); }
+        n_rows = n;
+    }
+    __syncthreads();
+    const int n = n_rows, F = n - B;
+    if (p.perm_in) { for (int i = tid; i < n; i += blockDim.x) perm[i] = (int16_t)p.perm_in[i]; }
+    else {                                         // Fisher-Yates keyed by (seed, update counter): draws in parallel, swaps in order
+        for (int i = tid; i < n; i += blockDim.x) {
+            const uint64_t h = cn_mix64(cn_mix64(p.seed ^ cn_mix64(cnt ^ 0x3c6ef372fe94f82bull)) ^ (uint64_t)(uint32_t)i);
+            perm[i] = (int16_t)i;
+            jr[i] = (int16_t)(h % (uint64_t)(i + 1));
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int i = n - 1; i > 0; --i) { const int j = jr[i]; const int16_t t = perm[i]; perm[i] = perm[j]; perm[j] = t; }
+    }
+    __syncthreads();
+    if (live)
+        for (int i = tid; i < n; i += blockDim.x) {
+            const int xr = perm[i];
+            if (xr >= 0 && xr < n) p.chunk[order[xr]] = i < B ? 1 : 2;
+        }
+    if (tid != 0) return;
+    *p.kcur = cnt;
+    p.flags[0] = live ? 1 : 0;
+    p.flags[1] = (live && F > 0) ? 1 : 0;
+    p.flags[2] = F;
+    p.flags[3] = cnt >= (unsigned long long)p.target_every ? 1 : 0;            // Q' = the target net after the first copy
+    p.flags[4] = (live && (cnt + 1ull) % (unsigned long long)p.target_every == 0ull) ? 1 : 0;
+}
+// Y (deepq.py:240-262, once, before either step) and dq = 2 (q - Y) / (3 n_chunk) of the rows of chunk `which` (Keras mse: the mean
+// over the 3 outputs, then over the chunk's rows); one workgroup.  which == 1 also writes Y and the chunk's loss.
+struct DqnTargetArgs {
+    const float *q, *tq, *r, *d; const int32_t *a, *chunk, *flags;   // q: this chunk's forward (chunk 1: the pre-step Q)
+    float *Y, *dq, *loss;
+    float gamma; int B, which;
+};
+__global__ void __launch_bounds__(256) dqn_target_kernel(DqnTargetArgs p)
+{
+    __shared__ float red[256];
+    if (p.flags[p.which - 1] == 0) {               // nothing to step: not live yet (chunk 1), or F = 0 (chunk 2)
+        if (p.which == 2 && threadIdx.x == 0) p.loss[1] = 0.f;
+        return;
+    }
+    const int B = p.B, F = p.flags[2];
+    const float n = p.which == 1 ? (float)B : (float)(F > 0 ? F : 1);
+    float ls = 0.f;
+    for (int g = threadIdx.x; g < 2 * B; g += blockDim.x) {
+        const float* q = p.q + (size_t)g * 3;
+        float y[3];
+        if (p.which == 1) {
+            const int m = g < B ? g : g - B;
+            if (g < B) {
+                const float* qn = p.flags[3] ? p.tq + (size_t)m * 3 : p.q + (size_t)(B + m) * 3;
+                const float mx = fmaxf(fmaxf(qn[0], qn[1]), qn[2]);
+                const float t = p.d[m] != 0.f ? p.r[m] : p.r[m] + p.gamma * mx;
+                y[0] = q[0]; y[1] = q[1]; y[2] = q[2];
+                const int a = p.a[m];
+                if (a >= 0 && a < 3) y[a] = t;
+            } else {
+                y[0] = y[1] = y[2] = p.r[m];           // a final sample's extra row: [r, r, r]
+            }
+#pragma unroll
+            for (int o = 0; o < 3; ++o) p.Y[(size_t)g * 3 + o] = y[o];
+        } else {
+#pragma unroll
+            for (int o = 0; o < 3; ++o) y[o] = p.Y[(size_t)g * 3 + o];
+        }
+        const bool in = p.chunk[g] == p.which;
+#pragma unroll
+        for (int o = 0; o < 3; ++o) {
+            const float e = q[o] - y[o];
+            p.dq[(size_t)g * 3 + o] = in ? 2.f * e / (3.f * n) : 0.f;
+            if (in) ls = fmaf(e, e, ls);
+        }
+    }
+    red[threadIdx.x] = ls;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s]; __syncthreads(); }
+    if (threadIdx.x == 0) p.loss[p.which - 1] = red[0] / (3.f * n);
+}
+// the hard copy online -> target (deepq.py:136-148) when flags[4] is set; the update counter
+struct DqnCopyArgs { const float* src[6]; float* dst[6]; long long n[6]; const int32_t* flags; unsigned long long* counter; const unsigned long long* kcur; };
+__global__ void __launch_bounds__(256) dqn_copy_kernel(DqnCopyArgs p)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0 && p.flags[0]) *p.counter = *p.kcur + 1ull;
+    if (!p.flags[4]) return;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (int t = 0; t < 6; ++t)
+        for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < p.n[t]; i += stride) p.dst[t][i] = p.src[t][i];
+}
+
+// Action selection (start_dqn_training.py:103-104: getQValues, selectAction) for 16 rows per workgroup: both hidden layers on the
+// f32 matrix cores with the activations in LDS (hidden padded to a multiple of 32 with zero units), the 3-way head, argmax with
+// ties to the lowest index (np.argmax), and the epsilon draw keyed by (seed, counter, row).
+struct DqnActArgs {
+    const float* obs; int64_t ld; int n, D, H, Hp;
+    const float *w1, *b1, *w2, *b2, *w3, *b3;
+    double eps0, disc, eps_min; const int64_t* episodes_dev;
+    uint64_t seed, counter;
+    int32_t* action; float* twist; float* q;
+};
+// out[r][n] = relu(sum_k A[r][k] W[n][k] + b[n]) for the workgroup's 16 rows, units n < Hp (zero from H on); lane (li, lk) feeds
+// A[li][16 t + 4 lk + e] and W[n0 + li][the same k] to MFMA e of block t, as td3_fwd_kernel does
+__device__ __forceinline__ void dqn_act_layer(const float* arow, int K, const float* __restrict__ W, const float* __restrict__ b, int H,
+                                              float* out, int Hp, int wave, int li, int lk)
+{
+    const int nb = (K + 15) >> 4;
+    for (int nt = wave; nt < (Hp >> 4); nt += 4) {
+        const int n0 = nt * 16;
+        const float* __restrict__ wrow = W + (size_t)min(n0 + li, H - 1) * K;
+        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+        const int nfull = K >> 4;
+        // full blocks of 16 inputs, 8 in flight (the loads of a block do not wait for the MFMAs of the one before), then the ragged one
+        for (int t0 = 0; t0 < nfull; t0 += 8) {
+            f32x4_t av[8], bv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int k = 16 * min(t0 + u, nfull - 1) + 4 * lk;          // (past the end: loaded, not used)
+                av[u] = *(const f32x4u_t*)(arow + k); bv[u] = *(const f32x4u_t*)(wrow + k);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (t0 + u < nfull) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc = TD3_MFMA(av[u][e], bv[u][e], acc);
+                }
+        }
+        if (nfull < nb) {
+            const int k = 16 * nfull + 4 * lk;
+            const f32x4_t av = td3_ld4(arow, k, K), bv = td3_ld4(wrow, k, K);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = TD3_MFMA(av[e], bv[e], acc);
+        }
+        const int nn = n0 + li;
+        const float bias = nn < H ? b[nn] : 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) out[(4 * lk + q) * Hp + nn] = nn < H ? fmaxf(acc[q] + bias, 0.f) : 0.f;
+    }
+}
+__global__ void __launch_bounds__(256) dqn_act_kernel(DqnActArgs p)
+{
+    extern __shared__ float dqn_lds[];
+    float* h1 = dqn_lds;
+    float* h2 = dqn_lds + 16 * p.Hp;
+    __shared__ float qs[16][3];
+    __shared__ double eps_s;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
+    const int i0 = blockIdx.x * 16;
+    if (tid == 0) {       // the epsilon of the episode under way: start_dqn_training.py:89-90 applied once per episode begun
+        double e = p.eps0;
+        if (p.episodes_dev && p.disc < 1.0) {
+            const long long E = *p.episodes_dev;
+            // (bounded: eps_min > 0 and disc < 1 end the loop after log(eps_min / eps0) / log(disc) steps; the cap only guards
+            // against a discount so close to 1 that the schedule would take longer than any run has episodes)
+            for (long long k = 0; k <= E && k < (1ll << 22) && e > p.eps_min; ++k) e *= p.disc;
+        }
+        eps_s = e;
+    }
+    dqn_act_layer(p.obs + (size_t)min(i0 + li, p.n - 1) * p.ld, p.D, p.w1, p.b1, p.H, h1, p.Hp, wave, li, lk);
+    __syncthreads();
+    dqn_act_layer(h1 + li * p.Hp, p.H, p.w2, p.b2, p.H, h2, p.Hp, wave, li, lk);      // (h1's row in LDS; the reduction over its H units)
+    __syncthreads();
+    if (tid < 192) {      // q[r][o] = h2[r] . W3[o] + b3[o]: 4 lanes per (row, output), units n = part mod 4
+        const int r = tid / 12, o = (tid % 12) >> 2, part = tid & 3;
+        const float* __restrict__ w = p.w3 + (size_t)o * p.H;
+        float s = 0.f;
+        for (int nn = part; nn < p.H; nn += 4) s = fmaf(h2[r * p.Hp + nn], w[nn], s);
+        s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64);
+        if (part == 0) qs[r][o] = s + p.b3[o];
+    }
+    __syncthreads();
+    if (tid < 16 && i0 + tid < p.n) {
+        const int i = i0 + tid;
+        const float q0 = qs[tid][0], q1 = qs[tid][1], q2 = qs[tid][2];
+        int best = 0; float bq = q0;
+        if (q1 > bq) { best = 1; bq = q1; }
+        if (q2 > bq) { best = 2; }
+        const uint64_t h = cn_mix64(cn_mix64(p.seed ^ cn_mix64(p.counter ^ 0x2545f4914f6cdd1dull)) ^ (uint64_t)(uint32_t)i);
+        const double u = (double)(h >> 11) * (1.0 / 9007199254740992.0);             // random.random(): 53 bits in [0, 1)
+        const uint64_t h2_ = cn_mix64(h ^ 0x9e3779b97f4a7c15ull);
+        const int pick = (int)(((h2_ >> 32) * 3ull) >> 32);                           // np.random.randint(0, 3)
+        const int act = u < eps_s ? pick : best;
+        p.action[i] = act;
+        // environment_stage_1_original.py:412-425: (0.22, 0), (0.22, 2.0), (0.22, -2.0)
+        p.twist[2 * i] = 0.22f; p.twist[2 * i + 1] = act == 0 ? 0.f : act == 1 ? 2.0f : -2.0f;
+        if (p.q) { p.q[3 * i] = q0; p.q[3 * i + 1] = q1; p.q[3 * i + 2] = q2; }
+    }
+}
+}  // namespace
+
+struct cn_dqn_s {
+    cn_dqn_config cfg;
+    int device;
+    int B, D, ld, H;
+    float* pool = nullptr;
+    float *x, *r, *d, *h1, *h2, *th1, *th2, *q, *q2, *tq, *Y, *dq, *dz2, *dz1, *loss;   // q: pre-step Q, q2: chunk 2's
+    int32_t *a, *chunk, *flags;
+    unsigned long long *counter, *kcur;
+    float* acc[6];                                 // RMSprop accumulators of w1, b1, w2, b2, w3, b3
+};
+
+namespace {
+size_t dqn_param_count(const cn_dqn_s* h, int j)
+{
+    const size_t H = (size_t)h->H, D = (size_t)h->D;
+    switch (j) { case 0: return H * D; case 1: return H; case 2: return H * H; case 3: return H; case 4: return 3 * H; default: return 3; }
+}
+bool dqn_mlp_ok(const cn_td3_mlp& n) { return n.w1 && n.b1 && n.w2 && n.b2 && n.w3 && n.b3; }
+}  // namespace
+
+extern "C" int cn_dqn_create(const cn_dqn_config* cfg, int device, cn_dqn_handle* out)
+{
+    if (!cfg || !out) return td3_fail(CN_ERR_ARG, "cn_dqn_create: null argument");
+    const cn_dqn_config& c = *cfg;
+    if (c.obs_dim < 1 || c.obs_ld < c.obs_dim || c.hidden < 1 || c.hidden > 4096 || c.batch < 1 || c.batch > 4096 || c.target_every < 1 || c.learn_start < 0)
+        return td3_fail(CN_ERR_CONFIG, "cn_dqn_create: obs_dim / obs_ld / hidden / batch / target_every / learn_start out of range");
+    if (!dqn_mlp_ok(c.q) || !dqn_mlp_ok(c.q_t)) return td3_fail(CN_ERR_ARG, "cn_dqn_create: null parameter pointer");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return td3_fail(CN_ERR_NO_DEVICE, "cn_dqn_create: no HIP device (libcrowdnav has no CPU fallback)");
+    if (device < 0 || device >= ndev) return td3_fail(CN_ERR_ARG, "cn_dqn_create: bad device ordinal");
+    DevScope scope(device);
+    cn_dqn_s* h = new (std::nothrow) cn_dqn_s();
+    if (!h) return td3_fail(CN_ERR_ARG, "cn_dqn_create: out of memory");
+    h->cfg = c; h->device = device; h->B = c.batch; h->D = c.obs_dim; h->ld = c.obs_ld; h->H = c.hidden;
+    const size_t B = h->B, ld = h->ld, H = h->H;
+    const size_t words = 4 + 2 * B * ld + 2 * B                  // counter, kcur (8-byte aligned: first); x, r, d
+                         + 2 * 2 * B * H + 2 * B * H             // h1, h2, th1, th2
+                         + 4 * 2 * B * 3 + B * 3                 // q, Y, dq, q2, tq
+                         + 2 * 2 * B * H + 2                     // dz2, dz1, loss
+                         + B + 2 * B + 8;                        // a, chunk, flags
+    size_t acc_words = 0;
+    for (int j = 0; j < 6; ++j) acc_words += dqn_param_count(h, j);
+    hipError_t e = hipMalloc(&h->pool, (words + acc_words) * sizeof(float));
+    if (e != hipSuccess) { delete h; return td3_fail(CN_ERR_HIP, std::string("cn_dqn_create: hipMalloc: ") + hipGetErrorString(e)); }
+    e = hipMemset(h->pool, 0, (words + acc_words) * sizeof(float));
+    if (e != hipSuccess) { (void)hipFree(h->pool); delete h; return td3_fail(CN_ERR_HIP, std::string("cn_dqn_create: hipMemset: ") + hipGetErrorString(e)); }
+    float* q = h->pool;
+    auto take = [&](size_t n) { float* r_ = q; q += n; return r_; };
+    h->counter = (unsigned long long*)take(2); h->kcur = (unsigned long long*)take(2);
+    h->x = take(2 * B * ld); h->r = take(B); h->d = take(B);
+    h->h1 = take(2 * B * H); h->h2 = take(2 * B * H); h->th1 = take(B * H); h->th2 = take(B * H);
+    h->q = take(2 * B * 3); h->Y = take(2 * B * 3); h->dq = take(2 * B * 3); h->q2 = take(2 * B * 3); h->tq = take(B * 3);
+    h->dz2 = take(2 * B * H); h->dz1 = take(2 * B * H); h->loss = take(2);
+    h->a = (int32_t*)take(B); h->chunk = (int32_t*)take(2 * B);
+    h->flags = (int32_t*)take(8);
+    for (int j = 0; j < 6; ++j) h->acc[j] = take(dqn_param_count(h, j));
+    *out = h;
+    return CN_OK;
+}
+
+extern "C" void cn_dqn_destroy(cn_dqn_handle h)
+{
+    if (!h) return;
+    DevScope scope(h->device);
+    (void)hipFree(h->pool);
+    delete h;
+}
+
+extern "C" const float* cn_dqn_loss_dev(cn_dqn_handle h) { return h ? h->loss : nullptr; }
+
+extern "C" const void* cn_dqn_batch_dev(cn_dqn_handle h, int what)
+{
+    if (!h) return nullptr;
+    switch (what) {
+        case 0: return h->x; case 1: return h->r; case 2: return h->d; case 3: return h->a; case 4: return h->chunk;
+        case 5: return h->flags; case 6: return h->Y; case 7: return h->q; case 8: return h->counter; default: return nullptr;
+    }
+}
+
+extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* stream)
+{
+    if (!h) return td3_fail(CN_ERR_ARG, "cn_dqn_update: null handle");
+    const cn_dqn_config& c = h->cfg;
+    if (!batch && (!c.replay_s || !c.replay_a || !c.replay_r || !c.replay_s2 || !c.replay_d || !c.replay_size_dev))
+        return td3_fail(CN_ERR_ARG, "cn_dqn_update: no explicit batch and no replay ring in the configuration");
+    if (batch && (!batch->s || !batch->a || !batch->r || !batch->s2 || !batch->d)) return td3_fail(CN_ERR_ARG, "cn_dqn_update: null batch pointer");
+    DevScope scope(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int B = h->B, D = h->D, ld = h->ld, H = h->H;
+    DqnPrepArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    if (batch) { pa.rs = batch->s; pa.rs2 = batch->s2; pa.rr = batch->r; pa.rd = batch->d; pa.a_in = batch->a; pa.perm_in = batch->perm; }
+    else { pa.rs = c.replay_s; pa.rs2 = c.replay_s2; pa.rr = c.replay_r; pa.rd = c.replay_d; pa.ra = c.replay_a; pa.size_dev = c.replay_size_dev; }
+    pa.x = h->x; pa.r = h->r; pa.d = h->d; pa.a = h->a; pa.chunk = h->chunk; pa.flags = h->flags;
+    pa.counter = h->counter; pa.kcur = h->kcur; pa.seed = c.seed; pa.B = B; pa.ld = ld; pa.D = D;
+    pa.learn_start = c.learn_start; pa.target_every = c.target_every;
+    hipLaunchKernelGGL(dqn_prep_kernel, dim3(2 * B + 1), dim3(256), (size_t)(13 * B + 8) / 8 * 8, st, pa);
+
+    GemmArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.rms_lr = c.lr; ga.rms_rho = c.rho; ga.rms_eps = c.eps;
+    auto fwd = [&](GemmJob& j, const float* X, int I, int ldx, int K, const float* W, const float* b, float* Y, int J, int relu) {
+        memset(&j, 0, sizeof(j));
+        j.A = X; j.B = W; j.C = Y; j.bias = b; j.I = I; j.J = J; j.R = K; j.lda = ldx; j.ldb = K; j.ldc = J; j.relu = relu;
+    };
+    // every GEMM of a chunk is gated on the device (the launches of chunk 2 return at once when F = 0; all of them while the replay
+    // path waits for learn_start)
+    auto forward = [&](int chunk) {               // online net on the 2B stacked rows (+ chunk 1: the target net on the B s2 rows)
+        const int nj = chunk == 1 ? 2 : 1;
+        float* q = chunk == 1 ? h->q : h->q2;
+        ga.rms_gate = h->flags + (chunk - 1);
+        fwd(ga.job[0], h->x, 2 * B, ld, D, c.q.w1, c.q.b1, h->h1, H, 1);
+        fwd(ga.job[1], h->x + (size_t)B * ld, B, ld, D, c.q_t.w1, c.q_t.b1, h->th1, H, 1);
+        launch_gemm<GEMM_F, true>(ga, nj, st);
+        fwd(ga.job[0], h->h1, 2 * B, H, H, c.q.w2, c.q.b2, h->h2, H, 1);
+        fwd(ga.job[1], h->th1, B, H, H, c.q_t.w2, c.q_t.b2, h->th2, H, 1);
+        launch_gemm<GEMM_F, true>(ga, nj, st);
+        fwd(ga.job[0], h->h2, 2 * B, H, H, c.q.w3, c.q.b3, q, 3, 0);
+        fwd(ga.job[1], h->th2, B, H, H, c.q_t.w3, c.q_t.b3, h->tq, 3, 0);
+        launch_gemm<GEMM_F, true>(ga, nj, st);
+    };
+    auto target = [&](int which) {
+        DqnTargetArgs ta;
+        ta.q = which == 1 ? h->q : h->q2; ta.tq = h->tq; ta.r = h->r; ta.d = h->d; ta.a = h->a; ta.chunk = h->chunk; ta.flags = h->flags;
+        ta.Y = h->Y; ta.dq = h->dq; ta.loss = h->loss; ta.gamma = c.gamma; ta.B = B; ta.which = which;
+        hipLaunchKernelGGL(dqn_target_kernel, dim3(1), dim3(256), 0, st, ta);
+    };
+    auto backward = [&](const int* gate) {        // dz2 = (dq W3) [h2 > 0], dz1 = (dz2 W2) [h1 > 0], then RMSprop of all six tensors
+        ga.rms_gate = gate;
+        GemmJob& j = ga.job[0];
+        memset(&j, 0, sizeof(j));
+        j.A = h->dq; j.B = c.q.w3; j.C = h->dz2; j.mask = h->h2; j.I = 2 * B; j.J = H; j.R = 3; j.lda = 3; j.ldb = H; j.ldc = H;
+        launch_gemm<GEMM_G, true>(ga, 1, st);
+        memset(&j, 0, sizeof(j));
+        j.A = h->dz2; j.B = c.q.w2; j.C = h->dz1; j.mask = h->h1; j.I = 2 * B; j.J = H; j.R = H; j.lda = H; j.ldb = H; j.ldc = H;
+        launch_gemm<GEMM_G, true>(ga, 1, st);
+        auto wj = [&](GemmJob& k, const float* dY, int I, int lda, const float* X, int ldx, int J, float* W, float* bp, int slot) {
+            memset(&k, 0, sizeof(k));
+            k.A = dY; k.B = X; k.C = W; k.I = I; k.J = J; k.R = 2 * B; k.lda = lda; k.ldb = ldx; k.ldc = J;
+            k.m = h->acc[slot]; k.bparam = bp; k.bm = h->acc[slot + 1];
+        };
+        wj(ga.job[0], h->dz2, H, H, h->h1, H, H, c.q.w2, c.q.b2, 2);
+        wj(ga.job[1], h->dz1, H, H, h->x, ld, D, c.q.w1, c.q.b1, 0);
+        wj(ga.job[2], h->dq, 3, 3, h->h2, H, H, c.q.w3, c.q.b3, 4);
+        ga.rms_gate = gate;
+        int gx = 0, gy = 0;
+        for (int z = 0; z < 3; ++z) { const int x_ = (ga.job[z].J + 31) / 32, y_ = (ga.job[z].I + 31) / 32; gx = x_ > gx ? x_ : gx; gy = y_ > gy ? y_ : gy; }
+        hipLaunchKernelGGL(td3_wgrad_kernel<true>, dim3(gx, gy, 3), dim3(256), 0, st, ga);
+    };
+    // chunk 1 (its Y from the pre-step nets), then chunk 2 on the stepped weights (gated off on the device when F = 0)
+    forward(1);
+    target(1);
+    backward(h->flags + 0);
+    forward(2);
+    target(2);
+    backward(h->flags + 1);
+    DqnCopyArgs ca;
+    const float* src[6] = {c.q.w1, c.q.b1, c.q.w2, c.q.b2, c.q.w3, c.q.b3};
+    float* dst[6] = {c.q_t.w1, c.q_t.b1, c.q_t.w2, c.q_t.b2, c.q_t.w3, c.q_t.b3};
+    for (int j = 0; j < 6; ++j) { ca.src[j] = src[j]; ca.dst[j] = dst[j]; ca.n[j] = (long long)dqn_param_count(h, j); }
+    ca.flags = h->flags; ca.counter = h->counter; ca.kcur = h->kcur;
+    hipLaunchKernelGGL(dqn_copy_kernel, dim3(128), dim3(256), 0, st, ca);
+    TD3CHK(hipGetLastError());
+    return CN_OK;
+}
+
+extern "C" int cn_dqn_act(const cn_dqn_act_io* io, int device, void* stream)
+{
+    if (!io || !io->obs || !io->action || !io->twist) return td3_fail(CN_ERR_ARG, "cn_dqn_act: null argument");
+    if (!dqn_mlp_ok(io->q)) return td3_fail(CN_ERR_ARG, "cn_dqn_act: null parameter pointer");
+    if (io->n < 1 || io->obs_dim < 1 || io->obs_ld < io->obs_dim || io->hidden < 1 || io->hidden > 480)
+        return td3_fail(CN_ERR_CONFIG, "cn_dqn_act: n / obs_dim / obs_ld / hidden out of range (hidden <= 480: two 16-row activations in 64 KB of LDS)");
+    if (!(io->epsilon_discount >= 0.0 && io->epsilon_discount <= 1.0) || !(io->epsilon_min > 0.0))
+        return td3_fail(CN_ERR_CONFIG, "cn_dqn_act: epsilon_discount outside [0, 1] or epsilon_min <= 0");
+    DevScope scope(device);
+    DqnActArgs p;
+    p.obs = io->obs; p.ld = io->obs_ld; p.n = io->n; p.D = io->obs_dim; p.H = io->hidden; p.Hp = (io->hidden + 31) / 32 * 32;
+    p.w1 = io->q.w1; p.b1 = io->q.b1; p.w2 = io->q.w2; p.b2 = io->q.b2; p.w3 = io->q.w3; p.b3 = io->q.b3;
+    p.eps0 = io->epsilon; p.disc = io->epsilon_discount; p.eps_min = io->epsilon_min; p.episodes_dev = io->episodes_dev;
+    p.seed = io->seed; p.counter = io->counter; p.action = io->action; p.twist = io->twist; p.q = io->q_out;
+    const size_t lds = (size_t)2 * 16 * p.Hp * sizeof(float);
+    hipLaunchKernelGGL(dqn_act_kernel, dim3((io->n + 15) / 16), dim3(256), lds, (hipStream_t)stream, p);
     TD3CHK(hipGetLastError());
     return CN_OK;
 }

@@ -370,6 +370,63 @@ int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream);
 const float* cn_ddpg_loss_dev(cn_ddpg_handle h);    /* device pointer: the critic's MSE loss of the last update (ddpg.py:230) */
 const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what);   /* as cn_td3_batch_dev, same indices; what = 4 (no noise): NULL */
 
+/* DQN -- the reference's discrete learner (deepq.py, start_dqn_training.py) -- on the same GEMM kernels (crowdnav_td3.hip).
+ * Network (deepq.py:102-127, TRAIN_DQN:55-57): Linear(obs_dim, H) - ReLU - Linear(H, H) - ReLU - Linear(H, 3), H = 300.
+ * One update = learnOnMiniBatch (deepq.py:219-266) with Memory.getMiniBatch (memory.py:22-28):
+ *   - B rows sampled on the device with replacement (td3_prep_kernel's hash; the reference samples without replacement);
+ *   - Y = Q(s), Y[a] = r if final else r + gamma max Q'(s2) (deepq.py:240-256), Q' = the online net until the first target copy,
+ *     the target net after it; every final sample appends the row (s2, [r, r, r]) right after its own (:257-262): B + F rows;
+ *   - model.fit(batch_size = B, epochs = 1) shuffles them and takes two steps when F > 0: the first B shuffled rows, then the
+ *     other F on the stepped weights, both against the Y computed before either; loss per chunk = Keras mse (mean over the 3
+ *     outputs and the chunk's rows); RMSprop a = rho a + (1 - rho) g^2, p -= lr g / (sqrt(a) + eps), accumulators zero at create.
+ *     No second step at all when F = 0;
+ *   - the hard copy online -> target after every target_every-th update (TRAIN_DQN:123-124, counted in updates here: the
+ *     reference counts its non-terminal env-steps, stepCounter).
+ * The replay path is a no-op (counter included) while the ring holds no more than learn_start rows (TRAIN_DQN:114, deepq.py:221).
+ * Enqueue-only, no host read, capturable into a hipGraph; 16 launches, those of chunk 2 returning at once on the device when F = 0.  Errors through cn_td3_last_error. */
+typedef struct cn_dqn_config {
+    int32_t obs_dim;         /* network inputs: TRAIN_DQN:55 -> 361 (the first 361 columns of the obs_layout-1 row) */
+    int32_t obs_ld;          /* row stride of s / s2 in the replay ring and in an explicit batch (>= obs_dim; the env's 363) */
+    int32_t hidden;          /* TRAIN_DQN:57 -> 300 */
+    int32_t batch;           /* TRAIN_DQN:52 -> 64 (also Keras's fit batch size) */
+    float gamma, lr, rho, eps;   /* dqn.yaml 0.99, 2.5e-4; RMSprop(rho = 0.9, epsilon = 1e-6) (deepq.py:124) */
+    int32_t target_every;    /* TRAIN_DQN:51 -> 10000 */
+    int32_t learn_start;     /* TRAIN_DQN:53 -> 64 */
+    cn_td3_mlp q, q_t;       /* the online and target networks (nn.Linear storages; linear3 has 3 outputs) */
+    const float *replay_s, *replay_a, *replay_r, *replay_s2, *replay_d;   /* as cn_td3_config; rows of s / s2 obs_ld wide, the action
+                                                                           * index in column 0 of replay_a [.][2] */
+    const int64_t* replay_size_dev;
+    uint64_t seed;           /* keys the replay indices and the shuffle with the handle's update counter */
+} cn_dqn_config;
+typedef struct cn_dqn_batch {   /* an explicit batch (tests): s, s2 [B][obs_ld], a [B] action indices, r [B], d [B] */
+    const float* s; const int32_t* a; const float* r; const float* s2; const float* d;
+    const int32_t* perm;         /* the shuffle: X_batch row at each of the B + F positions, or NULL = drawn on the device */
+} cn_dqn_batch;
+typedef struct cn_dqn_s* cn_dqn_handle;
+int cn_dqn_create(const cn_dqn_config* cfg, int device, cn_dqn_handle* out);
+void cn_dqn_destroy(cn_dqn_handle h);
+int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* stream);
+const float* cn_dqn_loss_dev(cn_dqn_handle h);      /* device pointer: [2] the losses of chunk 1 and chunk 2 (0 when F = 0) */
+/* Device pointers, read only, into what the last update computed: 0 = the stacked rows [2B][obs_ld] (s, then s2), 1 = r [B],
+ * 2 = d [B], 3 = a [B] (int32), 4 = the chunk of each stacked row [2B] (int32: 0 none, 1, 2), 5 = flags [8] (int32: live, second
+ * step, F, Q' is the target net, target copied), 6 = Y [2B][3], 7 = the pre-step Q [2B][3] (chunk 1's forward; chunk 2's is kept apart), 8 = the update counter (uint64). */
+const void* cn_dqn_batch_dev(cn_dqn_handle h, int what);
+/* Action selection (TRAIN_DQN:103-104, deepq.py:151-184) for n rows as ONE launch: Q on the f32 matrix cores, argmax with ties to
+ * the lowest index, and with probability epsilon a uniform index instead, drawn from (seed, counter, row).  epsilon: episodes_dev
+ * NULL = `epsilon` itself; else the schedule TRAIN_DQN:89-90 (if eps > epsilon_min: eps *= epsilon_discount, once per episode
+ * begun, before its first step) applied *episodes_dev + 1 times to `epsilon` (at most 2^22 times), in float64 on the doubles given.  Writes the index [n] and the twist of
+ * environment_stage_1_original.py:412-425 [n][2]: (0.22, 0), (0.22, 2.0), (0.22, -2.0); q_out [n][3] optional. */
+typedef struct cn_dqn_act_io {
+    const float* obs; int64_t obs_ld;
+    int32_t n, obs_dim, hidden, reserved;     /* hidden <= 480 */
+    cn_td3_mlp q;
+    double epsilon, epsilon_discount, epsilon_min;   /* epsilon_min > 0 */
+    const int64_t* episodes_dev;
+    uint64_t seed, counter;
+    int32_t* action; float* twist; float* q_out;
+} cn_dqn_act_io;
+int cn_dqn_act(const cn_dqn_act_io* io, int device, void* stream);
+
 /* The collection loop's bookkeeping between Env.step and Agent.learn (start_td3_training.py:129-149) for a batch of environments,
  * without a host read: ReplayBuffer.add (td3.py:24-31) into a ring on the device, and the per-episode record TRAIN:139-149 prints
  * and utils.record_data writes.  (crowdnav.td3.DeviceReplay and crowdnav.train.DeviceEpisodeLog do the same through ~35 PyTorch
