@@ -1,0 +1,70 @@
+"""What the TD3, DDPG and DQN agents share on the way to libcrowdnav's fused learners (csrc/crowdnav_td3.hip): the network
+pointers, views of the library's device memory, and the owner of a learner handle."""
+import ctypes as C
+
+import torch
+
+from . import _abi
+
+
+def mlp_of(m):
+    """The `cn_td3_mlp` of a module with linear1 / linear2 / linear3: device pointers to its nn.Linear storages."""
+    ps = [m.linear1.weight, m.linear1.bias, m.linear2.weight, m.linear2.bias, m.linear3.weight, m.linear3.bias]
+    assert all(p.is_contiguous() and p.dtype == torch.float32 and p.is_cuda for p in ps)
+    return _abi.CnTd3Mlp(*[p.data_ptr() for p in ps])
+
+
+def _device_view(ptr, shape, dtype, device):
+    """A tensor aliasing device memory owned by libcrowdnav (alive as long as its handle)."""
+    ts = {torch.float32: "<f4", torch.int32: "<i4", torch.int64: "<i8"}[dtype]
+    n = 1
+    for x in shape:
+        n *= int(x)
+
+    class _Arr:
+        __cuda_array_interface__ = {"shape": (n,), "typestr": ts, "data": (int(ptr), False), "version": 2}
+    return torch.as_tensor(_Arr(), device=device).reshape(tuple(shape))
+
+
+class FusedLearner:
+    """Owns one learner handle of libcrowdnav: family = "td3", "ddpg" or "dqn" names cn_<family>_create / _update / _destroy /
+    _loss_dev / _batch_dev.  An error raises CrowdNavError("<function>: <cn_td3_last_error>")."""
+
+    def __init__(self, family, cfg, device, dev_index, loss_shape=()):
+        self._L = L = _abi.lib()
+        self.family, self.cfg, self.device = family, cfg, device
+        self.h = C.c_void_p()
+        self._check("create", self._fn("create")(C.byref(cfg), dev_index, C.byref(self.h)))
+        self._loss = _device_view(self._fn("loss_dev")(self.h), loss_shape, torch.float32, device)
+        self._keep, self._update = None, self._fn("update")
+
+    def _fn(self, what):
+        return getattr(self._L, "cn_%s_%s" % (self.family, what))
+
+    def _check(self, what, rc):
+        if rc != 0:
+            raise _abi.CrowdNavError("cn_%s_%s: %s" % (self.family, what, self._L.cn_td3_last_error().decode()))
+
+    def update(self, *args, batch=None, keep=None):
+        """cn_<family>_update(handle, *args, batch, torch's current stream): enqueue-only.  batch: the ctypes batch struct or None
+        (= sample the replay); keep: the tensors it points into, held until the next explicit batch because the launches are
+        asynchronous.  Returns the loss where the kernels left it as a fresh tensor per call, the same contract as the PyTorch
+        learners (no host synchronisation: one small device-to-device copy on the update's stream).  The view of the handle's own
+        loss is overwritten by the next update and dies with the handle, so it is not handed out."""
+        if batch is not None:
+            self._keep = (batch, keep)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._check("update", self._update(self.h, *args, C.byref(batch) if batch is not None else None, st))
+        return self._loss.clone()
+
+    def batch_dev(self, what, shape, dtype=torch.float32):
+        """A view of what the last update gathered or computed (cn_<family>_batch_dev), valid until the next update."""
+        return _device_view(self._fn("batch_dev")(self.h, int(what)), shape, dtype, self.device)
+
+    def __del__(self):
+        try:
+            if self.h:
+                self._fn("destroy")(self.h)
+                self.h = None
+        except Exception:
+            pass

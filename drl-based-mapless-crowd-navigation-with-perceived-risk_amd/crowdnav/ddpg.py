@@ -19,7 +19,8 @@ import os
 import torch
 import torch.nn.functional as F
 
-from .td3 import Actor, Critic, DeviceReplay, FusedActorMixin, _device_scalar_view
+from ._fused import FusedLearner, mlp_of
+from .td3 import Actor, Critic, DeviceReplay, FusedActorMixin
 
 INIT_W = 3e-3      # DDPG:68, 96: init_w of linear3
 
@@ -119,64 +120,30 @@ class Agent(FusedActorMixin):
         """Hand the update to cn_ddpg_update: the forward / backward GEMMs of the four networks on the f32 matrix cores, weight
         gradients and soft updates folded into the Adam steps, 8 launches per update.  The networks stay these nn.Modules (stepped
         in place); Adam's moments restart from zero inside the library, so call this before training."""
-        import ctypes as C
         from . import _abi
         if self.device.type != "cuda":
             raise RuntimeError("enable_fused_update needs a HIP device")
-        if getattr(self, "_ddpg_h", None):
+        if getattr(self, "_fused", None):
             return
-        L = _abi.lib()
-
-        def mlp(m):
-            ps = [m.linear1.weight, m.linear1.bias, m.linear2.weight, m.linear2.bias, m.linear3.weight, m.linear3.bias]
-            assert all(p.is_contiguous() and p.dtype == torch.float32 and p.is_cuda for p in ps)
-            return _abi.CnTd3Mlp(*[p.data_ptr() for p in ps])
-        mem = self.memory
         og = self.opt_a.param_groups[0]
         cfg = _abi.CnDdpgConfig(obs_dim=self.actor.linear1.in_features, hidden=self.actor.linear1.out_features, batch=self.batch_size,
                                 gamma=self.gamma, tau=self.tau, lr_actor=og["lr"], lr_critic=self.opt_c.param_groups[0]["lr"],
                                 beta1=og["betas"][0], beta2=og["betas"][1], eps=og["eps"], max_v=self.max_v, max_w=self.max_w,
-                                actor=mlp(self.actor), actor_t=mlp(self.actor_t), critic=mlp(self.critic), critic_t=mlp(self.critic_t),
-                                replay_s=mem.s.data_ptr(), replay_a=mem.a.data_ptr(), replay_r=mem.r.data_ptr(),
-                                replay_s2=mem.s2.data_ptr(), replay_d=mem.d.data_ptr(), replay_size_dev=mem.size_dev.data_ptr(),
-                                seed=self._noise_seed)
-        h = C.c_void_p()
-        rc = L.cn_ddpg_create(C.byref(cfg), self._dev_index, C.byref(h))
-        if rc != 0:
-            raise _abi.CrowdNavError("cn_ddpg_create: %s" % L.cn_td3_last_error().decode())
-        self._ddpg_h, self._ddpg_cfg = h, cfg
-        self._ddpg_loss = None
+                                actor=mlp_of(self.actor), actor_t=mlp_of(self.actor_t), critic=mlp_of(self.critic),
+                                critic_t=mlp_of(self.critic_t), seed=self._noise_seed, **self.memory.ring_fields())
+        self._fused = FusedLearner("ddpg", cfg, self.device, self._dev_index)
 
     def _fused_learn(self, batch=None):
-        import ctypes as C
         from . import _abi
-        L = _abi.lib()
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        bp = None
+        bs = keep = None
         if batch is not None:
-            s, a, r, s2, d = [t.contiguous().float() for t in batch]
+            keep = s, a, r, s2, d = [t.contiguous().float() for t in batch]
             B, D = self.batch_size, self.actor.linear1.in_features
             if s.shape != (B, D) or s2.shape != (B, D) or a.shape != (B, 2) or r.numel() != B or d.numel() != B:
                 raise ValueError("cn_ddpg_update was created for batches of %d x %d; got s %s a %s r %s s2 %s d %s" % (
                     B, D, tuple(s.shape), tuple(a.shape), tuple(r.shape), tuple(s2.shape), tuple(d.shape)))
-            self._ddpg_keep = (s, a, r, s2, d)            # alive until the next call: the launches are asynchronous
-            bp = C.byref(_abi.CnTd3Batch(s.data_ptr(), a.data_ptr(), r.data_ptr(), s2.data_ptr(), d.data_ptr(), None))
-        rc = L.cn_ddpg_update(self._ddpg_h, bp, st)
-        if rc != 0:
-            raise _abi.CrowdNavError("cn_ddpg_update: %s" % L.cn_td3_last_error().decode())
-        if self._ddpg_loss is None:
-            ptr = L.cn_ddpg_loss_dev(self._ddpg_h)
-            self._ddpg_loss = _device_scalar_view(ptr, self.device) if ptr else False
-        return self._ddpg_loss.clone() if self._ddpg_loss is not False else None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_ddpg_h", None):
-                from . import _abi
-                _abi.lib().cn_ddpg_destroy(self._ddpg_h)
-                self._ddpg_h = None
-        except Exception:
-            pass
+            bs = _abi.CnTd3Batch(s.data_ptr(), a.data_ptr(), r.data_ptr(), s2.data_ptr(), d.data_ptr(), None)
+        return self._fused.update(batch=bs, keep=keep)
 
     def learn(self, step=None, batch=None):
         """One DDPG update (DDPG:198-243).  `batch` = (s, a, r[B,1], s2, d[B,1]) overrides the replay sample (parity tests).
@@ -184,7 +151,7 @@ class Agent(FusedActorMixin):
         tensor (no host synchronisation), or None while the replay holds no more than a batch (TRAIN_DDPG:111)."""
         if batch is None and not self.memory.ready(self.batch_size):
             return None
-        if getattr(self, "_ddpg_h", None):
+        if getattr(self, "_fused", None):
             return self._fused_learn(batch)
         if batch is None:
             batch = self.memory.sample(self.batch_size)

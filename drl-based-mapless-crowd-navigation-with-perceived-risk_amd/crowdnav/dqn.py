@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._fused import FusedLearner, mlp_of
 from .td3 import DeviceReplay
 
 TWISTS = ((0.22, 0.0), (0.22, 2.0), (0.22, -2.0))     # environment_stage_1_original.py:412-425
@@ -136,7 +137,7 @@ class Agent:
         if out_twist is None:
             out_twist = torch.empty((n, 2), dtype=torch.float32, device=self.device)
         io = _abi.CnDqnActIO(obs=obs.data_ptr(), obs_ld=obs.stride(0), n=n, obs_dim=self.obs_dim, hidden=self.hidden[0], reserved=0,
-                             q=self._mlp(self.q),
+                             q=mlp_of(self.q),
                              epsilon=self.epsilon0 if episodes_dev is not None else (self.epsilon if epsilon is None else float(epsilon)),
                              epsilon_discount=self.epsilon_discount, epsilon_min=self.epsilon_min,
                              episodes_dev=episodes_dev.data_ptr() if episodes_dev is not None else None,
@@ -188,43 +189,23 @@ class Agent:
             self.q_t.load_state_dict(self.q.state_dict())
         return losses[0]
 
-    @staticmethod
-    def _mlp(m):
-        from . import _abi
-        ps = [m.linear1.weight, m.linear1.bias, m.linear2.weight, m.linear2.bias, m.linear3.weight, m.linear3.bias]
-        assert all(p.is_contiguous() and p.dtype == torch.float32 and p.is_cuda for p in ps)
-        return _abi.CnTd3Mlp(*[p.data_ptr() for p in ps])
-
     def enable_fused_update(self):
         """Hand the update to cn_dqn_update (16 launches, enqueue-only).  RMSprop's accumulators restart from zero inside the
         library and the update counter from 0: call this before training."""
-        import ctypes as C
         from . import _abi
         if self.device.type != "cuda":
             raise RuntimeError("enable_fused_update needs a HIP device")
-        if getattr(self, "_dqn_h", None):
+        if getattr(self, "_fused", None):
             return
-        L = _abi.lib()
-        mem = self.memory
         cfg = _abi.CnDqnConfig(obs_dim=self.obs_dim, obs_ld=self.obs_ld, hidden=self.hidden[0], batch=self.batch_size,
                                gamma=self.gamma, lr=self.lr, rho=self.rho, eps=self.eps, target_every=self.target_update,
-                               learn_start=self.learn_start, q=self._mlp(self.q), q_t=self._mlp(self.q_t),
-                               replay_s=mem.s.data_ptr(), replay_a=mem.a.data_ptr(), replay_r=mem.r.data_ptr(),
-                               replay_s2=mem.s2.data_ptr(), replay_d=mem.d.data_ptr(), replay_size_dev=mem.size_dev.data_ptr(),
-                               seed=self._replay_seed)
-        h = C.c_void_p()
-        rc = L.cn_dqn_create(C.byref(cfg), self._dev_index, C.byref(h))
-        if rc != 0:
-            raise _abi.CrowdNavError("cn_dqn_create: %s" % L.cn_td3_last_error().decode())
-        self._dqn_h, self._dqn_cfg = h, cfg
-        self._dqn_loss = None
+                               learn_start=self.learn_start, q=mlp_of(self.q), q_t=mlp_of(self.q_t), seed=self._replay_seed,
+                               **self.memory.ring_fields())
+        self._fused = FusedLearner("dqn", cfg, self.device, self._dev_index, loss_shape=(2,))
 
     def _fused_learn(self, batch=None, perm=None):
-        import ctypes as C
         from . import _abi
-        L = _abi.lib()
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        bp = None
+        bs = keep = None
         if batch is not None:
             s, a, r, s2, d = batch
             B = self.batch_size
@@ -238,29 +219,14 @@ class Agent:
                 if p.numel() != B + int((d != 0).sum()):
                     raise ValueError("perm has %d entries; the batch has %d rows after its final samples' extra rows" % (
                         p.numel(), B + int((d != 0).sum())))
-            self._dqn_keep = (s, a, r, s2, d, p)                     # alive until the next call: the launches are asynchronous
-            bp = C.byref(_abi.CnDqnBatch(s.data_ptr(), a.data_ptr(), r.data_ptr(), s2.data_ptr(), d.data_ptr(),
-                                         p.data_ptr() if p is not None else None))
-        rc = L.cn_dqn_update(self._dqn_h, bp, st)
-        if rc != 0:
-            raise _abi.CrowdNavError("cn_dqn_update: %s" % L.cn_td3_last_error().decode())
-        if self._dqn_loss is None:
-            self._dqn_loss = _device_view(L.cn_dqn_loss_dev(self._dqn_h), (2,), torch.float32, self.device)
-        return self._dqn_loss.clone()
+            keep = (s, a, r, s2, d, p)
+            bs = _abi.CnDqnBatch(s.data_ptr(), a.data_ptr(), r.data_ptr(), s2.data_ptr(), d.data_ptr(),
+                                 p.data_ptr() if p is not None else None)
+        return self._fused.update(batch=bs, keep=keep)
 
     def fused_batch(self, what, shape, dtype=torch.float32):
         """A host copy of what the last fused update computed (cn_dqn_batch_dev; synchronises)."""
-        from . import _abi
-        return _device_view(_abi.lib().cn_dqn_batch_dev(self._dqn_h, int(what)), shape, dtype, self.device).cpu()
-
-    def __del__(self):
-        try:
-            if getattr(self, "_dqn_h", None):
-                from . import _abi
-                _abi.lib().cn_dqn_destroy(self._dqn_h)
-                self._dqn_h = None
-        except Exception:
-            pass
+        return self._fused.batch_dev(what, shape, dtype).cpu()
 
     def learn(self, step=None, batch=None, perm=None):
         """One learnOnMiniBatch (deepq.py:219-266).  batch = (s [B, obs_ld], a [B] indices, r, s2, d) overrides the replay sample;
@@ -268,7 +234,7 @@ class Agent:
         losses [2]), or None while the replay holds no more than learn_start rows (TRAIN_DQN:114, deepq.py:221)."""
         if batch is None and not self.memory.ready(self.learn_start):
             return None
-        if getattr(self, "_dqn_h", None):
+        if getattr(self, "_fused", None):
             return self._fused_learn(batch, perm)
         if batch is None:
             s, a2, r, s2, d = self.memory.sample(self.batch_size)
@@ -298,14 +264,3 @@ class Agent:
                 self.epsilon = float(json.load(f).get("explorationRate", self.epsilon))
             self.epsilon0 = self.epsilon
 
-
-def _device_view(ptr, shape, dtype, device):
-    """A tensor aliasing device memory owned by libcrowdnav (alive as long as its handle)."""
-    ts = {torch.float32: "<f4", torch.int32: "<i4", torch.int64: "<i8"}[dtype]
-    n = 1
-    for x in shape:
-        n *= int(x)
-
-    class _Arr:
-        __cuda_array_interface__ = {"shape": (n,), "typestr": ts, "data": (int(ptr), False), "version": 2}
-    return torch.as_tensor(_Arr(), device=device).reshape(tuple(shape))

@@ -9,6 +9,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._fused import FusedLearner, _device_view, mlp_of
+
 
 class Actor(nn.Module):
     def __init__(self, num_inputs=398, num_actions=2, hidden_size=256, max_lin_vel=0.22, max_ang_vel=2.0):
@@ -44,9 +46,7 @@ class Critic(nn.Module):
 
 def _device_scalar_view(ptr, device):
     """A 0-d float32 tensor aliasing one device float owned by libcrowdnav (alive as long as its handle)."""
-    class _Arr:
-        __cuda_array_interface__ = {"shape": (1,), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
-    return torch.as_tensor(_Arr(), device=device).reshape(())
+    return _device_view(ptr, (), torch.float32, device)
 
 
 class DeviceReplay:
@@ -131,6 +131,11 @@ class DeviceReplay:
         tot = c[-1]
         self.pos_dev.copy_((self.pos_dev + tot) % self.cap)
         self.size_dev.copy_(torch.clamp(self.size_dev + tot, max=self.cap))
+
+    def ring_fields(self):
+        """The six replay_* fields of a learner's configuration (cn_td3_config, cn_ddpg_config, cn_dqn_config)."""
+        return dict(replay_s=self.s.data_ptr(), replay_a=self.a.data_ptr(), replay_r=self.r.data_ptr(), replay_s2=self.s2.data_ptr(),
+                    replay_d=self.d.data_ptr(), replay_size_dev=self.size_dev.data_ptr())
 
     def sync_len(self):
         """The exact fill level (one host read); collapses the host-side bounds onto it."""
@@ -301,7 +306,6 @@ class Agent(FusedActorMixin):
                  gamma=0.99, tau=0.005, max_v=0.22, max_w=2.0, noise_std=0.2, noise_clip=0.5, policy_delay=2,
                  explore_sigma=1.0, device="cuda", seed=0, actor_final_init=None):
         self.device = torch.device(device)
-        g = torch.Generator().manual_seed(seed)
         torch.manual_seed(seed)
         self.actor = Actor(obs_dim, 2, hidden, max_v, max_w).to(self.device)
         self.actor_t = Actor(obs_dim, 2, hidden, max_v, max_w).to(self.device)
@@ -328,7 +332,6 @@ class Agent(FusedActorMixin):
         self.explore_sigma = explore_sigma
         self.gen = torch.Generator(device=self.device).manual_seed(seed)
         self._init_fused_actor(seed)
-        del g
 
     @torch.no_grad()
     def act(self, obs, add_noise=True):
@@ -425,42 +428,23 @@ class Agent(FusedActorMixin):
         drawn on the device -- 7 launches for the critic step, 5 more with the actor and the targets, against ~150 through PyTorch.  The
         networks stay these nn.Modules (the kernels step their parameter storages in place); Adam's moments restart from zero
         inside the library (torch.optim state is not carried over), so call this before training, not in the middle of it."""
-        import ctypes as C
         from . import _abi
         if self.device.type != "cuda":
             raise RuntimeError("enable_fused_update needs a HIP device")
-        if getattr(self, "_td3_h", None):
+        if getattr(self, "_fused", None):
             return
-        L = _abi.lib()
-
-        def mlp(m):
-            ps = [m.linear1.weight, m.linear1.bias, m.linear2.weight, m.linear2.bias, m.linear3.weight, m.linear3.bias]
-            assert all(p.is_contiguous() and p.dtype == torch.float32 and p.is_cuda for p in ps)
-            return _abi.CnTd3Mlp(*[p.data_ptr() for p in ps])
-        mem = self.memory
         og = self.opt_a.param_groups[0]
         cfg = _abi.CnTd3Config(obs_dim=self.actor.linear1.in_features, hidden=self.actor.linear1.out_features, batch=self.batch_size,
                                policy_delay=self.policy_delay, gamma=self.gamma, tau=self.tau, lr_actor=og["lr"],
                                lr_critic=self.opt_q1.param_groups[0]["lr"], beta1=og["betas"][0], beta2=og["betas"][1], eps=og["eps"],
                                noise_std=self.noise_std, noise_clip=self.noise_clip, max_v=self.max_v, max_w=self.max_w, reserved=0.0,
-                               actor=mlp(self.actor), actor_t=mlp(self.actor_t), q1=mlp(self.q1), q1_t=mlp(self.q1_t), q2=mlp(self.q2),
-                               q2_t=mlp(self.q2_t), replay_s=mem.s.data_ptr(), replay_a=mem.a.data_ptr(), replay_r=mem.r.data_ptr(),
-                               replay_s2=mem.s2.data_ptr(), replay_d=mem.d.data_ptr(), replay_size_dev=mem.size_dev.data_ptr(),
-                               seed=self._noise_seed)
-        h = C.c_void_p()
-        rc = L.cn_td3_create(C.byref(cfg), self._dev_index, C.byref(h))
-        if rc != 0:
-            raise _abi.CrowdNavError("cn_td3_create: %s" % L.cn_td3_last_error().decode())
-        self._td3_h, self._td3_cfg = h, cfg
-        import numpy as np  # noqa: F401
-        self._td3_loss = None
+                               actor=mlp_of(self.actor), actor_t=mlp_of(self.actor_t), q1=mlp_of(self.q1), q1_t=mlp_of(self.q1_t),
+                               q2=mlp_of(self.q2), q2_t=mlp_of(self.q2_t), seed=self._noise_seed, **self.memory.ring_fields())
+        self._fused = FusedLearner("td3", cfg, self.device, self._dev_index)
 
     def _fused_learn(self, step, batch=None, target_noise=None):
-        import ctypes as C
         from . import _abi
-        L = _abi.lib()
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        bp = None
+        bs = keep = None
         if batch is not None:
             s, a, r, s2, d = [t.contiguous().float() for t in batch]
             tn = target_noise.contiguous().float() if target_noise is not None else None
@@ -471,28 +455,10 @@ class Agent(FusedActorMixin):
                 raise ValueError("cn_td3_update was created for batches of %d x %d; got s %s a %s r %s s2 %s d %s noise %s" % (
                     B, D, tuple(s.shape), tuple(a.shape), tuple(r.shape), tuple(s2.shape), tuple(d.shape),
                     None if tn is None else tuple(tn.shape)))
-            self._td3_keep = (s, a, r, s2, d, tn)            # alive until the next call: the launches are asynchronous
-            bp = C.byref(_abi.CnTd3Batch(s.data_ptr(), a.data_ptr(), r.data_ptr(), s2.data_ptr(), d.data_ptr(),
-                                         tn.data_ptr() if tn is not None else None))
-        rc = L.cn_td3_update(self._td3_h, int(step % self.policy_delay == 0), bp, st)
-        if rc != 0:
-            raise _abi.CrowdNavError("cn_td3_update: %s" % L.cn_td3_last_error().decode())
-        # the first critic's loss of this update, where the kernels left it: a fresh 0-d tensor per call, the same contract as the
-        # PyTorch learner (no host synchronisation: one 4-byte device-to-device copy on the update's stream).  The view of the
-        # handle's device scalar itself is overwritten by the next update and dies with cn_td3_destroy, so it is not handed out.
-        if self._td3_loss is None:
-            ptr = L.cn_td3_loss_dev(self._td3_h)
-            self._td3_loss = _device_scalar_view(ptr, self.device) if ptr else False
-        return self._td3_loss.clone() if self._td3_loss is not False else None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_td3_h", None):
-                from . import _abi
-                _abi.lib().cn_td3_destroy(self._td3_h)
-                self._td3_h = None
-        except Exception:
-            pass
+            keep = (s, a, r, s2, d, tn)
+            bs = _abi.CnTd3Batch(s.data_ptr(), a.data_ptr(), r.data_ptr(), s2.data_ptr(), d.data_ptr(),
+                                 tn.data_ptr() if tn is not None else None)
+        return self._fused.update(int(step % self.policy_delay == 0), batch=bs, keep=keep)      # the first critic's loss
 
     def learn(self, step, batch=None, target_noise=None):
         """One TD3 update (TD3:225-285): clipped target-policy noise added to the target actor's action (the
@@ -501,7 +467,7 @@ class Agent(FusedActorMixin):
         the three soft updates.  `batch` = (s, a, r[B,1], s2, d[B,1]) and `target_noise` [B,2] (before the clip)
         override the replay sample / the generator -- used by the parity test against the reference's update.
         Returns the first critic's loss as a 0-d tensor (no host synchronisation)."""
-        if getattr(self, "_td3_h", None):
+        if getattr(self, "_fused", None):
             if batch is None and not self.memory.ready(self.batch_size):
                 return None
             return self._fused_learn(step, batch, target_noise)

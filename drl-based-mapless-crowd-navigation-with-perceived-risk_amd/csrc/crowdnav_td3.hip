@@ -20,6 +20,8 @@
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+#include <initializer_list>
+#include <memory>
 #include <new>
 #include <string>
 
@@ -714,40 +716,178 @@ __global__ void __launch_bounds__(1024) cn_episode_log_kernel(EpisodeLogArgs p)
 }  // namespace
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-struct cn_td3_s {
-    cn_td3_config cfg;
-    int device;
-    int B, D, Dc, H;
-    float* pool = nullptr;         // one allocation for the whole workspace
-    // batch
-    float *xs, *x2, *r, *d, *noise, *logits;
-    float *t_h1, *t_h2;            // target actor
-    float *c_h1[4], *c_h2[4];               // q1, q2, q1_t, q2_t
-    float *dq[2];                           // the critics' loss gradients per row (td3_dgrad_kernel's head-backward mode)
-    float *dl;                              // the actor's: dlogit [B][2]
-    float *qpart, *dapart; int qnt, dant;   // partial sums of the critics' outputs [4][B][qnt] and of the action gradient [B][2][dant]
-    float *a_h1, *a_h2;            // actor
-    float *dz2[2], *dz1[2];
-    float* loss;
-    float* adam;                   // [4]
-    float* steps;                  // [2]
-    double* pw;                    // [4] running products beta^t
-    unsigned long long* counter;
-    // Adam moments: actor, q1, q2 x {w1, b1, w2, b2, w3, b3} x {m, v}
-    float* mom[3][6][2];
-};
-
 namespace {
 struct DevScope {
     int prev = -1, want;
     explicit DevScope(int dev) : want(dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != want) (void)hipSetDevice(want); }
     ~DevScope() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
 };
-const cn_td3_mlp& net_of(const cn_td3_config& c, int k) { return k == 0 ? c.actor : k == 1 ? c.q1 : c.q2; }
-size_t param_count(const cn_td3_s* h, int net, int j)
+
+// A learner's workspace is ONE device allocation that the handle's layout(Pool&) describes once, as a take(field, n) per buffer.
+// learner_create runs it twice: with base == nullptr it only sums (the size hipMalloc gets), then it assigns the fields -- so the
+// size cannot disagree with the carve-up.  Every field is aligned for its own type, wherever it stands.
+struct Pool {
+    char* base;
+    size_t size = 0;
+    template <class T> void take(T*& field, size_t n)
+    {
+        size = (size + alignof(T) - 1) / alignof(T) * alignof(T);
+        if (base) field = (T*)(base + size);
+        size += n * sizeof(T);
+    }
+};
+// elements of tensor j of {w1, b1, w2, b2, w3, b3} of Linear(in1, H) - Linear(H, H) - Linear(H, out3)
+size_t param_count(int in1, int out3, int H, int j)
 {
-    const size_t in1 = net == 0 ? (size_t)h->D : (size_t)h->Dc, out3 = net == 0 ? 2 : 1, H = (size_t)h->H;
-    switch (j) { case 0: return H * in1; case 1: return H; case 2: return H * H; case 3: return H; case 4: return out3 * H; default: return out3; }
+    const size_t h = (size_t)H;
+    switch (j) { case 0: return h * in1; case 1: return h; case 2: return h * h; case 3: return h; case 4: return out3 * h; default: return out3; }
+}
+bool mlp_ok(const cn_td3_mlp& n) { return n.w1 && n.b1 && n.w2 && n.b2 && n.w3 && n.b3; }
+int check_mlps(const char* fn, std::initializer_list<const cn_td3_mlp*> nets)
+{
+    for (const cn_td3_mlp* n : nets) if (!mlp_ok(*n)) return td3_fail(CN_ERR_ARG, std::string(fn) + ": null parameter pointer");
+    return CN_OK;
+}
+
+// What the three handles share.  It owns the pool: deleting the handle frees it, on every path.
+struct Learner {
+    int device = 0, B = 0, D = 0, H = 0;
+    void* pool = nullptr;          // one allocation for the whole workspace
+    float* loss = nullptr;
+    unsigned long long* counter = nullptr;         // update counter (keys the sampling)
+    Learner() = default;
+    Learner(const Learner&) = delete;
+    ~Learner() { if (pool) { DevScope scope(device); (void)hipFree(pool); } }
+    int start(const char*) { return CN_OK; }       // what create still has to write into the zeroed pool: nothing by default
+};
+// cn_*_create after the checks of the configuration: Hd = the handle (cfg, layout(Pool&), start(fn)), fn = the name in the error texts
+template <class Hd, class Cfg>
+int learner_create(const char* fn, const Cfg& c, int device, Hd** out)
+{
+    const std::string f(fn);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return td3_fail(CN_ERR_NO_DEVICE, f + ": no HIP device (libcrowdnav has no CPU fallback)");
+    if (device < 0 || device >= ndev) return td3_fail(CN_ERR_ARG, f + ": bad device ordinal");
+    DevScope scope(device);
+    std::unique_ptr<Hd> h(new (std::nothrow) Hd());
+    if (!h) return td3_fail(CN_ERR_ARG, f + ": out of memory");
+    h->cfg = c; h->device = device; h->B = c.batch; h->D = c.obs_dim; h->H = c.hidden;
+    Pool count{nullptr};
+    h->layout(count);
+    hipError_t e = hipMalloc(&h->pool, count.size);
+    if (e != hipSuccess) return td3_fail(CN_ERR_HIP, f + ": hipMalloc: " + hipGetErrorString(e));
+    e = hipMemset(h->pool, 0, count.size);
+    if (e != hipSuccess) return td3_fail(CN_ERR_HIP, f + ": hipMemset: " + hipGetErrorString(e));
+    Pool assign{(char*)h->pool};
+    h->layout(assign);
+    if (const int rc = h->start(fn)) return rc;
+    *out = h.release();
+    return CN_OK;
+}
+// cn_*_update's argument checks: a handle, and either an explicit batch with its five arrays or a replay ring in the configuration
+template <class Hd, class Batch>
+int check_update(const char* fn, const Hd* h, const Batch* batch)
+{
+    if (!h) return td3_fail(CN_ERR_ARG, std::string(fn) + ": null handle");
+    const auto& c = h->cfg;
+    if (!batch && (!c.replay_s || !c.replay_a || !c.replay_r || !c.replay_s2 || !c.replay_d || !c.replay_size_dev))
+        return td3_fail(CN_ERR_ARG, std::string(fn) + ": no explicit batch and no replay ring in the configuration");
+    if (batch && (!batch->s || !batch->a || !batch->r || !batch->s2 || !batch->d)) return td3_fail(CN_ERR_ARG, std::string(fn) + ": null batch pointer");
+    return CN_OK;
+}
+
+// What the TD3 and the DDPG handle share: the gathered batch, the two policies' activations, the actor-loss chain and Adam's state.
+struct ActorCritic : Learner {
+    float *xs, *x2, *r, *d, *noise, *logits;       // batch (noise: TD3 alone, null in a DDPG handle)
+    float *t_h1, *t_h2, *a_h1, *a_h2;              // target actor on s2, actor on s
+    float *qpart, *dapart;                         // partial sums of the critics' outputs [.][B][qnt] and of the action gradient [B][2][dant]
+    float* dl;                                     // the actor's loss gradient: dlogit [B][2]
+    float* adam;                                   // [2 optimizers: critic(s), actor][2]
+    float* steps;                                  // [2]
+    double* pw;                                    // [4] running products beta^t
+    float* mom[3][6][2];                           // Adam moments: actor, critic (, second critic) x {w1, b1, w2, b2, w3, b3} x {m, v}
+    int qnt() const { return (H + 15) / 16; }
+    int dant() const { return (H + 31) / 32; }
+    void take_moments(Pool& p, int nets)
+    {
+        for (int net = 0; net < nets; ++net) for (int j = 0; j < 6; ++j) for (int k = 0; k < 2; ++k)
+            p.take(mom[net][j][k], param_count(net == 0 ? D : D + 2, net == 0 ? 2 : 1, H, j));
+    }
+    int start(const char* fn)
+    {
+        const double one[4] = {1.0, 1.0, 1.0, 1.0};
+        const hipError_t e = hipMemcpy(pw, one, sizeof(one), hipMemcpyHostToDevice);
+        return e == hipSuccess ? CN_OK : td3_fail(CN_ERR_HIP, std::string(fn) + ": hipMemcpy: " + hipGetErrorString(e));
+    }
+};
+// the batch td3_prep_kernel gathered for the last update: written by that launch only, read (never written) by the GEMMs after it
+const float* batch_dev(const ActorCritic* h, int what)
+{
+    if (!h) return nullptr;
+    switch (what) { case 0: return h->xs; case 1: return h->x2; case 2: return h->r; case 3: return h->d; case 4: return h->noise; default: return nullptr; }
+}
+// td3_prep_kernel's arguments: the rows of the explicit batch, or a sample of the configuration's replay ring
+template <class Cfg>
+PrepArgs prep_args(const ActorCritic& h, const Cfg& c, const cn_td3_batch* batch)
+{
+    PrepArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    if (batch) { pa.rs = batch->s; pa.ra = batch->a; pa.rr = batch->r; pa.rs2 = batch->s2; pa.rd = batch->d; pa.noise_in = batch->target_noise; }
+    else { pa.rs = c.replay_s; pa.ra = c.replay_a; pa.rr = c.replay_r; pa.rs2 = c.replay_s2; pa.rd = c.replay_d; pa.size_dev = c.replay_size_dev; }
+    pa.xs = h.xs; pa.x2 = h.x2; pa.r = h.r; pa.d = h.d; pa.noise = h.noise; pa.counter = h.counter;
+    pa.seed = c.seed; pa.B = h.B; pa.D = h.D;
+    return pa;
+}
+// the part of GemmArgs (zeroed by the caller) that no launch of an update changes: Adam's constants and the tick's arguments
+template <class Cfg>
+void adam_args(GemmArgs& ga, const ActorCritic& h, const Cfg& c, int do_actor)
+{
+    ga.beta1 = c.beta1; ga.beta2 = c.beta2; ga.eps = c.eps; ga.tau = c.tau;
+    ga.tick.adam = h.adam; ga.tick.steps = h.steps; ga.tick.pw = h.pw; ga.tick.counter = h.counter; ga.tick.do_actor = do_actor;
+    ga.tick.lr_critic = c.lr_critic; ga.tick.lr_actor = c.lr_actor; ga.tick.beta1 = c.beta1; ga.tick.beta2 = c.beta2;
+}
+
+// ---- the GemmJob builders of the three updates: every field they do not name is zero -------------------------------------------
+// F: Y [I][J] = act(X [I][K] W^T + b)
+void fwd_job(GemmJob& j, const float* X, int I, int ldx, int K, const float* W, const float* b, float* Y, int J, int relu)
+{
+    memset(&j, 0, sizeof(j));
+    j.A = X; j.B = W; j.C = Y; j.bias = b; j.I = I; j.J = J; j.R = K; j.lda = ldx; j.ldb = K; j.ldc = J; j.relu = relu;
+}
+// F, on top of fwd_job: the last two columns of X are policy `pol`'s action on the row, evaluated from its second hidden activation h2
+void head_job(GemmJob& j, int D, int H, const float* h2, const cn_td3_mlp& pol, const float* noise, float* logits, float max_v, float max_w)
+{
+    j.R = D; j.hd_h2 = h2; j.hd_W3 = pol.w3; j.hd_b3 = pol.b3; j.hd_noise = noise; j.hd_logits = logits; j.hd_H = H; j.hd_max_v = max_v; j.hd_max_w = max_w;
+}
+// G: dX [I][J] = (dY [I][R] W) (.) [mask > 0]
+void dgrad_job(GemmJob& j, const float* dY, int I, int R, const float* W, const float* mask, float* dX, int J)
+{
+    memset(&j, 0, sizeof(j));
+    j.A = dY; j.B = W; j.C = dX; j.mask = mask; j.I = I; j.J = J; j.R = R; j.lda = R; j.ldb = J; j.ldc = J;
+}
+// G through a critic's second layer with dY evaluated (hb_*): the TD target from q partial-sum slot `net` and the target slots
+void critic_bwd_job(GemmJob& j, const ActorCritic& h, const cn_td3_mlp& crit, const float* h1, const float* h2, int net, int single, float gamma,
+                    float* dq, float* dz2, float* dz1)
+{
+    dgrad_job(j, h2, h.B, h.H, crit.w2, h1, dz1, h.H);
+    j.hb_h2 = h2; j.hb_w3 = crit.w3; j.hb_qpart = h.qpart; j.hb_qnt = h.qnt(); j.hb_net = net; j.hb_single = single; j.hb_r = h.r; j.hb_d = h.d;
+    j.hb_gamma = gamma; j.hb_dq = dq; j.hb_dz2 = dz2;
+}
+// G through the actor's second layer with dY evaluated (ab_*): the heads' derivatives on the action gradient's partial sums
+void actor_bwd_job(GemmJob& j, const ActorCritic& h, const cn_td3_mlp& actor, float max_v, float max_w, float* dz2, float* dz1)
+{
+    dgrad_job(j, h.a_h2, h.B, h.H, actor.w2, h.a_h1, dz1, h.H);
+    j.ab_h2 = h.a_h2; j.ab_w3 = actor.w3; j.ab_dapart = h.dapart; j.ab_dant = h.dant(); j.ab_logits = h.logits;
+    j.ab_max_v = max_v; j.ab_max_w = max_w; j.ab_dl = h.dl; j.ab_dz2 = dz2;
+}
+// H: W [I][J] stepped by dY^T [I][R] X [R][J], its bias by the row sums of dY^T; st = the optimizer's state of W, then of the bias,
+// {m, v} each (RMSprop: the accumulator and null); adam = the optimizer's bias corrections; tgt / btgt = the target's copies, or null
+void wgrad_job(GemmJob& j, const float* dY, int I, const float* X, int ldx, int J, int R, float* W, float* bparam, float* const (*st)[2],
+               const float* adam = nullptr, float* tgt = nullptr, float* btgt = nullptr)
+{
+    memset(&j, 0, sizeof(j));
+    j.A = dY; j.B = X; j.C = W; j.I = I; j.J = J; j.R = R; j.lda = I; j.ldb = ldx; j.ldc = J;
+    j.m = st[0][0]; j.v = st[0][1]; j.bparam = bparam; j.bm = st[1][0]; j.bv = st[1][1]; j.adam = adam; j.tgt = tgt; j.btgt = btgt;
 }
 template <int MODE, bool GATE = false>
 void launch_gemm(const GemmArgs& ga, int njobs, hipStream_t st)
@@ -763,182 +903,111 @@ void launch_gemm(const GemmArgs& ga, int njobs, hipStream_t st)
 
 extern "C" const char* cn_td3_last_error(void) { return g_td3_err.c_str(); }
 
+// ---- TD3 --------------------------------------------------------------------------------------------------------------------
+struct cn_td3_s : ActorCritic {
+    cn_td3_config cfg;
+    float *c_h1[4], *c_h2[4];               // q1, q2, q1_t, q2_t
+    float *dq[2];                           // the critics' loss gradients per row (td3_dgrad_kernel's head-backward mode)
+    float *dz2[2], *dz1[2];
+    void layout(Pool& p)
+    {
+        const size_t b = B, Dc = D + 2, h = H;
+        p.take(counter, 1); p.take(pw, 4);
+        p.take(xs, b * Dc); p.take(x2, b * Dc); p.take(r, b); p.take(d, b); p.take(noise, 2 * b); p.take(logits, 2 * b);
+        p.take(t_h1, b * h); p.take(t_h2, b * h);
+        for (int z = 0; z < 4; ++z) { p.take(c_h1[z], b * h); p.take(c_h2[z], b * h); }
+        p.take(qpart, 4 * b * qnt()); p.take(dapart, 2 * b * dant()); p.take(dq[0], b); p.take(dq[1], b); p.take(dl, 2 * b);
+        p.take(a_h1, b * h); p.take(a_h2, b * h);
+        for (int z = 0; z < 2; ++z) { p.take(dz2[z], b * h); p.take(dz1[z], b * h); }
+        p.take(loss, 1); p.take(adam, 4); p.take(steps, 2);
+        take_moments(p, 3);
+    }
+};
+
 extern "C" int cn_td3_create(const cn_td3_config* cfg, int device, cn_td3_handle* out)
 {
     if (!cfg || !out) return td3_fail(CN_ERR_ARG, "cn_td3_create: null argument");
     const cn_td3_config& c = *cfg;
     if (c.obs_dim < 1 || c.hidden < 1 || c.batch < 1 || c.batch > 4096 || c.hidden > 4096 || c.policy_delay < 1)
         return td3_fail(CN_ERR_CONFIG, "cn_td3_create: obs_dim / hidden / batch / policy_delay out of range");
-    const cn_td3_mlp* nets[6] = {&c.actor, &c.actor_t, &c.q1, &c.q1_t, &c.q2, &c.q2_t};
-    for (const cn_td3_mlp* n : nets)
-        if (!n->w1 || !n->b1 || !n->w2 || !n->b2 || !n->w3 || !n->b3) return td3_fail(CN_ERR_ARG, "cn_td3_create: null parameter pointer");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return td3_fail(CN_ERR_NO_DEVICE, "cn_td3_create: no HIP device (libcrowdnav has no CPU fallback)");
-    if (device < 0 || device >= ndev) return td3_fail(CN_ERR_ARG, "cn_td3_create: bad device ordinal");
-    DevScope scope(device);
-    cn_td3_s* h = new (std::nothrow) cn_td3_s();
-    if (!h) return td3_fail(CN_ERR_ARG, "cn_td3_create: out of memory");
-    h->cfg = c; h->device = device; h->B = c.batch; h->D = c.obs_dim; h->Dc = c.obs_dim + 2; h->H = c.hidden;
-    const size_t B = h->B, Dc = h->Dc, H = h->H;
-    size_t words = 2 * B * Dc + 2 * B + 2 * B + 2 * B          // xs, x2, r, d, noise, logits
-                   + 2 * B * H + 4 * (2 * B * H) + 2 * B * H + 4 * B * H + 1 + 4 + 2 + 2 + 8  // t_h, c_h, a_h, dz, loss, adam, steps, counter, pw
-                   + 4 * B * ((H + 15) / 16) + 2 * B * ((H + 31) / 32) + 2 * B + 2 * B;                        // qpart, dapart
-    size_t mom_words = 0;
-    for (int net = 0; net < 3; ++net) for (int j = 0; j < 6; ++j) mom_words += 2 * param_count(h, net, j);
-    hipError_t e = hipMalloc(&h->pool, (words + mom_words) * sizeof(float));
-    if (e != hipSuccess) { delete h; return td3_fail(CN_ERR_HIP, std::string("cn_td3_create: hipMalloc: ") + hipGetErrorString(e)); }
-    e = hipMemset(h->pool, 0, (words + mom_words) * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(h->pool); delete h; return td3_fail(CN_ERR_HIP, std::string("cn_td3_create: hipMemset: ") + hipGetErrorString(e)); }
-    float* q = h->pool;
-    auto take = [&](size_t n) { float* r_ = q; q += n; return r_; };
-    h->counter = (unsigned long long*)take(2);       // first: 8-byte aligned
-    h->pw = (double*)take(8);
-    { const double one[4] = {1.0, 1.0, 1.0, 1.0}; e = hipMemcpy(h->pw, one, sizeof(one), hipMemcpyHostToDevice); }
-    if (e != hipSuccess) { (void)hipFree(h->pool); delete h; return td3_fail(CN_ERR_HIP, std::string("cn_td3_create: hipMemcpy: ") + hipGetErrorString(e)); }
-    h->xs = take(B * Dc); h->x2 = take(B * Dc); h->r = take(B); h->d = take(B); h->noise = take(2 * B); h->logits = take(2 * B);
-    h->t_h1 = take(B * H); h->t_h2 = take(B * H);
-    for (int z = 0; z < 4; ++z) { h->c_h1[z] = take(B * H); h->c_h2[z] = take(B * H); }
-    h->qnt = (int)((H + 15) / 16); h->dant = (int)((H + 31) / 32);
-    h->qpart = take(4 * B * h->qnt); h->dapart = take(2 * B * h->dant); h->dq[0] = take(B); h->dq[1] = take(B); h->dl = take(2 * B);
-    h->a_h1 = take(B * H); h->a_h2 = take(B * H);
-    for (int z = 0; z < 2; ++z) { h->dz2[z] = take(B * H); h->dz1[z] = take(B * H); }
-    h->loss = take(1); h->adam = take(4); h->steps = take(2);
-    for (int net = 0; net < 3; ++net) for (int j = 0; j < 6; ++j) for (int k = 0; k < 2; ++k) h->mom[net][j][k] = take(param_count(h, net, j));
-    *out = h;
-    return CN_OK;
+    if (const int rc = check_mlps("cn_td3_create", {&c.actor, &c.actor_t, &c.q1, &c.q1_t, &c.q2, &c.q2_t})) return rc;
+    return learner_create("cn_td3_create", c, device, out);
 }
-
-extern "C" void cn_td3_destroy(cn_td3_handle h)
-{
-    if (!h) return;
-    DevScope scope(h->device);
-    (void)hipFree(h->pool);
-    delete h;
-}
-
+extern "C" void cn_td3_destroy(cn_td3_handle h) { delete h; }
 extern "C" const float* cn_td3_loss_dev(cn_td3_handle h) { return h ? h->loss : nullptr; }
-
-// the batch td3_prep_kernel gathered for the last update: written by that launch only, read (never written) by the GEMMs after it
-extern "C" const float* cn_td3_batch_dev(cn_td3_handle h, int what)
-{
-    if (!h) return nullptr;
-    switch (what) { case 0: return h->xs; case 1: return h->x2; case 2: return h->r; case 3: return h->d; case 4: return h->noise; default: return nullptr; }
-}
+extern "C" const float* cn_td3_batch_dev(cn_td3_handle h, int what) { return batch_dev(h, what); }
 
 extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* batch, void* stream)
 {
-    if (!h) return td3_fail(CN_ERR_ARG, "cn_td3_update: null handle");
+    if (const int rc = check_update("cn_td3_update", h, batch)) return rc;
     const cn_td3_config& c = h->cfg;
-    if (!batch && (!c.replay_s || !c.replay_a || !c.replay_r || !c.replay_s2 || !c.replay_d || !c.replay_size_dev))
-        return td3_fail(CN_ERR_ARG, "cn_td3_update: no explicit batch and no replay ring in the configuration");
-    if (batch && (!batch->s || !batch->a || !batch->r || !batch->s2 || !batch->d)) return td3_fail(CN_ERR_ARG, "cn_td3_update: null batch pointer");
     DevScope scope(h->device);
     hipStream_t st = (hipStream_t)stream;
-    const int B = h->B, D = h->D, Dc = h->Dc, H = h->H;
+    const int B = h->B, D = h->D, Dc = D + 2, H = h->H, qnt = h->qnt();
     // 0. sample / gather, noise, Adam constants
-    PrepArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    if (batch) { pa.rs = batch->s; pa.ra = batch->a; pa.rr = batch->r; pa.rs2 = batch->s2; pa.rd = batch->d; pa.noise_in = batch->target_noise; pa.size_dev = nullptr; }
-    else { pa.rs = c.replay_s; pa.ra = c.replay_a; pa.rr = c.replay_r; pa.rs2 = c.replay_s2; pa.rd = c.replay_d; pa.noise_in = nullptr; pa.size_dev = c.replay_size_dev; }
-    pa.xs = h->xs; pa.x2 = h->x2; pa.r = h->r; pa.d = h->d; pa.noise = h->noise; pa.counter = h->counter;
-    pa.seed = c.seed; pa.B = B; pa.D = D; pa.noise_std = c.noise_std; pa.noise_clip = c.noise_clip;
+    PrepArgs pa = prep_args(*h, c, batch);
+    pa.noise_std = c.noise_std; pa.noise_clip = c.noise_clip;
     hipLaunchKernelGGL(td3_prep_kernel, dim3(B), dim3(256), 0, st, pa);
-
-    auto fwd_job = [&](GemmJob& j, const float* X, int ldx, int K, const float* W, const float* b, float* Y) {
-        memset(&j, 0, sizeof(j));
-        j.A = X; j.B = W; j.C = Y; j.bias = b; j.I = B; j.J = H; j.R = K; j.lda = ldx; j.ldb = K; j.ldc = H; j.relu = 1;
-    };
-    auto bwd_data_job = [&](GemmJob& j, const float* dY, const float* W, const float* mask, float* dX) {   // through a hidden layer (H x H)
-        memset(&j, 0, sizeof(j));
-        j.A = dY; j.B = W; j.C = dX; j.mask = mask; j.I = B; j.J = H; j.R = H; j.lda = H; j.ldb = H; j.ldc = H;
-    };
-    auto wgrad_job = [&](GemmJob& j, const float* dY, const float* X, int ldx, int K, float* W, float* bparam, int net, int wj, const float* adam) {
-        memset(&j, 0, sizeof(j));
-        j.A = dY; j.B = X; j.C = W; j.I = H; j.J = K; j.R = B; j.lda = H; j.ldb = ldx; j.ldc = K;
-        j.m = h->mom[net][wj][0]; j.v = h->mom[net][wj][1]; j.bparam = bparam; j.bm = h->mom[net][wj + 1][0]; j.bv = h->mom[net][wj + 1][1]; j.adam = adam;
-    };
     GemmArgs ga;
-    ga.beta1 = c.beta1; ga.beta2 = c.beta2; ga.eps = c.eps; ga.tau = c.tau;
-    ga.tick.adam = h->adam; ga.tick.steps = h->steps; ga.tick.pw = h->pw; ga.tick.counter = h->counter; ga.tick.do_actor = do_actor ? 1 : 0;
-    ga.tick.lr_critic = c.lr_critic; ga.tick.lr_actor = c.lr_actor; ga.tick.beta1 = c.beta1; ga.tick.beta2 = c.beta2;
-    ga.do_tick = 0;
+    memset(&ga, 0, sizeof(ga));
+    adam_args(ga, *h, c, do_actor ? 1 : 0);
     // 1-2. the target actor's hidden layers on s2 (TD3:238).  On actor updates the policy's own hidden layers on s (TD3:268; they
     // read the actor, which the critic step does not touch) ride in the same two launches as a second job.
     const int na = do_actor ? 2 : 1;
-    fwd_job(ga.job[0], h->x2, Dc, D, c.actor_t.w1, c.actor_t.b1, h->t_h1);
-    fwd_job(ga.job[1], h->xs, Dc, D, c.actor.w1, c.actor.b1, h->a_h1);
+    fwd_job(ga.job[0], h->x2, B, Dc, D, c.actor_t.w1, c.actor_t.b1, h->t_h1, H, 1);
+    fwd_job(ga.job[1], h->xs, B, Dc, D, c.actor.w1, c.actor.b1, h->a_h1, H, 1);
     launch_gemm<GEMM_F>(ga, na, st);
-    fwd_job(ga.job[0], h->t_h1, H, H, c.actor_t.w2, c.actor_t.b2, h->t_h2);
-    fwd_job(ga.job[1], h->a_h1, H, H, c.actor.w2, c.actor.b2, h->a_h2);
+    fwd_job(ga.job[0], h->t_h1, B, H, H, c.actor_t.w2, c.actor_t.b2, h->t_h2, H, 1);
+    fwd_job(ga.job[1], h->a_h1, B, H, H, c.actor.w2, c.actor.b2, h->a_h2, H, 1);
     launch_gemm<GEMM_F>(ga, na, st);
     // (3, the policies' last layer and heads, runs inside the launches that consume the actions: 4 and 13)
-    auto head_job = [&](GemmJob& j, const float* h2, const cn_td3_mlp& pol, const float* noise, float* logits) {
-        j.R = D; j.hd_h2 = h2; j.hd_W3 = pol.w3; j.hd_b3 = pol.b3; j.hd_noise = noise; j.hd_logits = logits; j.hd_H = H; j.hd_max_v = c.max_v; j.hd_max_w = c.max_w;
-    };
     // 4-6. the four critics forward: q1, q2 on (s, a); q1_t, q2_t on (s2, a2)
     const cn_td3_mlp* crit[4] = {&c.q1, &c.q2, &c.q1_t, &c.q2_t};
-    for (int z = 0; z < 4; ++z) fwd_job(ga.job[z], z < 2 ? h->xs : h->x2, Dc, Dc, crit[z]->w1, crit[z]->b1, h->c_h1[z]);
-    for (int z = 2; z < 4; ++z) head_job(ga.job[z], h->t_h2, c.actor_t, h->noise, nullptr);      // a2 = pi_t(s2) + clipped noise
+    for (int z = 0; z < 4; ++z) fwd_job(ga.job[z], z < 2 ? h->xs : h->x2, B, Dc, Dc, crit[z]->w1, crit[z]->b1, h->c_h1[z], H, 1);
+    for (int z = 2; z < 4; ++z) head_job(ga.job[z], D, H, h->t_h2, c.actor_t, h->noise, nullptr, c.max_v, c.max_w);      // a2 = pi_t(s2) + clipped noise
     launch_gemm<GEMM_F>(ga, 4, st);
     // 5-6. ... their second layers, and the last (q = h2 . W3 + b3) as per-tile partial sums in the same epilogue; the tick too
     for (int z = 0; z < 4; ++z) {
-        fwd_job(ga.job[z], h->c_h1[z], H, H, crit[z]->w2, crit[z]->b2, h->c_h2[z]);
-        ga.job[z].qp_w3 = crit[z]->w3; ga.job[z].qp_b3 = crit[z]->b3; ga.job[z].qp_out = h->qpart + (size_t)z * B * h->qnt; ga.job[z].qp_nt = h->qnt;
+        fwd_job(ga.job[z], h->c_h1[z], B, H, H, crit[z]->w2, crit[z]->b2, h->c_h2[z], H, 1);
+        ga.job[z].qp_w3 = crit[z]->w3; ga.job[z].qp_b3 = crit[z]->b3; ga.job[z].qp_out = h->qpart + (size_t)z * B * qnt; ga.job[z].qp_nt = qnt;
     }
     ga.do_tick = 1;
     launch_gemm<GEMM_F>(ga, 4, st);
     ga.do_tick = 0;
     // 7-8. TD target, MSE gradient (per row, evaluated where it is consumed) and through the second hidden layer:
     // dz1 = (dz2 W2) (.) [h1 > 0], dz2 = dq W3 (.) [h2 > 0]   (W2, W3 are read here, stepped in 9)
-    for (int z = 0; z < 2; ++z) {
-        bwd_data_job(ga.job[z], h->c_h2[z], crit[z]->w2, h->c_h1[z], h->dz1[z]);
-        GemmJob& j = ga.job[z];
-        j.hb_h2 = h->c_h2[z]; j.hb_w3 = crit[z]->w3; j.hb_qpart = h->qpart; j.hb_qnt = h->qnt; j.hb_net = z; j.hb_r = h->r; j.hb_d = h->d;
-        j.hb_gamma = c.gamma; j.hb_dq = h->dq[z]; j.hb_dz2 = h->dz2[z];
-    }
+    for (int z = 0; z < 2; ++z) critic_bwd_job(ga.job[z], *h, *crit[z], h->c_h1[z], h->c_h2[z], z, 0, c.gamma, h->dq[z], h->dz2[z], h->dz1[z]);
     launch_gemm<GEMM_G>(ga, 2, st);
-    // 9. weight gradients folded into Adam: W2, b2, W1, b1 of both critics, and linear3 (dW3 = dq^T h2, db3 = sum dq: one-row jobs)
+    // 9. weight gradients folded into Adam: W2, b2, W1, b1 of both critics, and linear3 (dW3 = dq^T h2, db3 = sum dq: one-row jobs);
+    // on actor updates the target critics follow in the same epilogue (nothing reads them again in this update)
     for (int z = 0; z < 2; ++z) {
-        wgrad_job(ga.job[z], h->dz2[z], h->c_h1[z], H, H, crit[z]->w2, crit[z]->b2, 1 + z, 2, h->adam);
-        wgrad_job(ga.job[2 + z], h->dz1[z], h->xs, Dc, Dc, crit[z]->w1, crit[z]->b1, 1 + z, 0, h->adam);
-        wgrad_job(ga.job[4 + z], h->dq[z], h->c_h2[z], H, H, crit[z]->w3, crit[z]->b3, 1 + z, 4, h->adam);
-        ga.job[4 + z].I = 1; ga.job[4 + z].lda = 1;
-        if (z == 0) ga.job[4].loss_out = h->loss;             // the first critic's MSE: what Agent.learn returns
-        if (do_actor) {      // the target critics follow in the same epilogue (nothing reads them again in this update)
-            ga.job[z].tgt = crit[2 + z]->w2; ga.job[z].btgt = crit[2 + z]->b2;
-            ga.job[2 + z].tgt = crit[2 + z]->w1; ga.job[2 + z].btgt = crit[2 + z]->b1;
-            ga.job[4 + z].tgt = crit[2 + z]->w3; ga.job[4 + z].btgt = crit[2 + z]->b3;
-        }
+        const cn_td3_mlp none = {}, &t = do_actor ? *crit[2 + z] : none;
+        wgrad_job(ga.job[z], h->dz2[z], H, h->c_h1[z], H, H, B, crit[z]->w2, crit[z]->b2, &h->mom[1 + z][2], h->adam, t.w2, t.b2);
+        wgrad_job(ga.job[2 + z], h->dz1[z], H, h->xs, Dc, Dc, B, crit[z]->w1, crit[z]->b1, &h->mom[1 + z][0], h->adam, t.w1, t.b1);
+        wgrad_job(ga.job[4 + z], h->dq[z], 1, h->c_h2[z], H, H, B, crit[z]->w3, crit[z]->b3, &h->mom[1 + z][4], h->adam, t.w3, t.b3);
     }
+    ga.job[4].loss_out = h->loss;                                 // the first critic's MSE: what Agent.learn returns
     launch_gemm<GEMM_H>(ga, 6, st);
     if (do_actor) {
         // (10-11, the policy's hidden layers on s, ran inside launches 1-2; 12, its head, runs inside 13)
         // 13-14. the UPDATED first critic on (s, pi(s)) (TD3:268)
-        fwd_job(ga.job[0], h->xs, Dc, Dc, c.q1.w1, c.q1.b1, h->c_h1[0]);    // (xs's own action columns are not read: head_job)
-        head_job(ga.job[0], h->a_h2, c.actor, nullptr, h->logits);                                  // pi(s)
+        fwd_job(ga.job[0], h->xs, B, Dc, Dc, c.q1.w1, c.q1.b1, h->c_h1[0], H, 1);    // (xs's own action columns are not read: head_job)
+        head_job(ga.job[0], D, H, h->a_h2, c.actor, nullptr, h->logits, c.max_v, c.max_w);        // pi(s)
         launch_gemm<GEMM_F>(ga, 1, st);
-        fwd_job(ga.job[0], h->c_h1[0], H, H, c.q1.w2, c.q1.b2, h->c_h2[0]);
+        fwd_job(ga.job[0], h->c_h1[0], B, H, H, c.q1.w2, c.q1.b2, h->c_h2[0], H, 1);
         ga.job[0].dz_w3 = c.q1.w3; ga.job[0].dz_out = h->dz2[0]; ga.job[0].dz_rows = (float)B;      // 15. -mean Q's gradient at h2, in the epilogue
         launch_gemm<GEMM_F>(ga, 1, st);
         // 16-17. ... back to the action, through the heads, linear3 of the actor + Adam
-        bwd_data_job(ga.job[0], h->dz2[0], c.q1.w2, h->c_h1[0], h->dz1[0]);
-        ga.job[0].da_w = c.q1.w1 + D; ga.job[0].da_ld = Dc; ga.job[0].da_out = h->dapart; ga.job[0].da_nt = h->dant;     // the action columns of W1
+        dgrad_job(ga.job[0], h->dz2[0], B, H, c.q1.w2, h->c_h1[0], h->dz1[0], H);
+        ga.job[0].da_w = c.q1.w1 + D; ga.job[0].da_ld = Dc; ga.job[0].da_out = h->dapart; ga.job[0].da_nt = h->dant();     // the action columns of W1
         launch_gemm<GEMM_G>(ga, 1, st);
         // 17-19. through the heads' derivatives and the actor's hidden layers (the heads' part evaluated inside the backward GEMM,
         // linear3's gradient dl^T h2 as a two-row job of the weight-gradient launch)
-        bwd_data_job(ga.job[0], h->a_h2, c.actor.w2, h->a_h1, h->dz1[1]);
-        {
-            GemmJob& j = ga.job[0];
-            j.ab_h2 = h->a_h2; j.ab_w3 = c.actor.w3; j.ab_dapart = h->dapart; j.ab_dant = h->dant; j.ab_logits = h->logits;
-            j.ab_max_v = c.max_v; j.ab_max_w = c.max_w; j.ab_dl = h->dl; j.ab_dz2 = h->dz2[1];
-        }
+        actor_bwd_job(ga.job[0], *h, c.actor, c.max_v, c.max_w, h->dz2[1], h->dz1[1]);
         launch_gemm<GEMM_G>(ga, 1, st);
-        wgrad_job(ga.job[0], h->dz2[1], h->a_h1, H, H, c.actor.w2, c.actor.b2, 0, 2, h->adam + 2);
-        wgrad_job(ga.job[1], h->dz1[1], h->xs, Dc, D, c.actor.w1, c.actor.b1, 0, 0, h->adam + 2);
-        wgrad_job(ga.job[2], h->dl, h->a_h2, H, H, c.actor.w3, c.actor.b3, 0, 4, h->adam + 2);
-        ga.job[2].I = 2; ga.job[2].lda = 2;
-        ga.job[0].tgt = c.actor_t.w2; ga.job[0].btgt = c.actor_t.b2; ga.job[1].tgt = c.actor_t.w1; ga.job[1].btgt = c.actor_t.b1;
-        ga.job[2].tgt = c.actor_t.w3; ga.job[2].btgt = c.actor_t.b3;
+        wgrad_job(ga.job[0], h->dz2[1], H, h->a_h1, H, H, B, c.actor.w2, c.actor.b2, &h->mom[0][2], h->adam + 2, c.actor_t.w2, c.actor_t.b2);
+        wgrad_job(ga.job[1], h->dz1[1], H, h->xs, Dc, D, B, c.actor.w1, c.actor.b1, &h->mom[0][0], h->adam + 2, c.actor_t.w1, c.actor_t.b1);
+        wgrad_job(ga.job[2], h->dl, 2, h->a_h2, H, H, B, c.actor.w3, c.actor.b3, &h->mom[0][4], h->adam + 2, c.actor_t.w3, c.actor_t.b3);
         launch_gemm<GEMM_H>(ga, 3, st);
         // (20, the soft updates of the three targets, ran in the Adam epilogues of 7, 9, 17 and 19)
     }
@@ -952,32 +1021,24 @@ extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* 
 // launches.  8 launches:  prep | actor_t L1 (+ actor L1) | L2 (+ L2) | critic_t L1 on (s2, pi_t(s2)), critic L1 on (s, a) and on
 // (s, pi(s)) | their L2 (+ q partials of critic_t and critic, dz on the pi(s) branch, tick) | G (critic: dq, dz2 evaluated;
 // pi(s) branch: da partials) | G (actor: dl, dz2a evaluated) | H (six jobs: critic and actor W1 / W2 / W3 + Adam + soft updates).
-struct cn_ddpg_s {
+struct cn_ddpg_s : ActorCritic {
     cn_ddpg_config cfg;
-    int device;
-    int B, D, Dc, H;
-    float* pool = nullptr;
-    float *xs, *x2, *r, *d, *logits;
-    float *t_h1, *t_h2, *a_h1, *a_h2;        // target actor on s2, actor on s
-    float *c_h1[3], *c_h2[3];                // critic on (s, a), critic on (s, pi(s)), critic_t on (s2, pi_t(s2))
-    float *qpart, *dapart; int qnt, dant;    // q partial sums [3][B][qnt] (slots 0: critic, 2: critic_t), action gradient [B][2][dant]
-    float *dq, *dl;
+    float *c_h1[3], *c_h2[3];                // critic on (s, a), critic on (s, pi(s)), critic_t on (s2, pi_t(s2)); q partials: slots 0 and 2
+    float* dq;
     float *dz2c, *dz1c, *dz2p, *dz1p, *dz2a, *dz1a;   // critic step, pi(s) branch through the critic, actor
-    float* loss;
-    float* adam;                             // [4]: critic, actor
-    float* steps;                            // [2]
-    double* pw;                              // [4]
-    unsigned long long* counter;
-    float* mom[2][6][2];                     // Adam moments: actor, critic x {w1, b1, w2, b2, w3, b3} x {m, v}
+    void layout(Pool& p)
+    {
+        const size_t b = B, Dc = D + 2, h = H;
+        p.take(counter, 1); p.take(pw, 4);
+        p.take(xs, b * Dc); p.take(x2, b * Dc); p.take(r, b); p.take(d, b); p.take(logits, 2 * b);
+        p.take(t_h1, b * h); p.take(t_h2, b * h); p.take(a_h1, b * h); p.take(a_h2, b * h);
+        for (int z = 0; z < 3; ++z) { p.take(c_h1[z], b * h); p.take(c_h2[z], b * h); }
+        for (float** f : {&dz2c, &dz1c, &dz2p, &dz1p, &dz2a, &dz1a}) p.take(*f, b * h);
+        p.take(qpart, 3 * b * qnt()); p.take(dapart, 2 * b * dant()); p.take(dq, b); p.take(dl, 2 * b);
+        p.take(loss, 1); p.take(adam, 4); p.take(steps, 2);
+        take_moments(p, 2);
+    }
 };
-
-namespace {
-size_t ddpg_param_count(const cn_ddpg_s* h, int net, int j)
-{
-    const size_t in1 = net == 0 ? (size_t)h->D : (size_t)h->Dc, out3 = net == 0 ? 2 : 1, H = (size_t)h->H;
-    switch (j) { case 0: return H * in1; case 1: return H; case 2: return H * H; case 3: return H; case 4: return out3 * H; default: return out3; }
-}
-}  // namespace
 
 extern "C" int cn_ddpg_create(const cn_ddpg_config* cfg, int device, cn_ddpg_handle* out)
 {
@@ -985,161 +1046,71 @@ extern "C" int cn_ddpg_create(const cn_ddpg_config* cfg, int device, cn_ddpg_han
     const cn_ddpg_config& c = *cfg;
     if (c.obs_dim < 1 || c.hidden < 1 || c.batch < 1 || c.batch > 4096 || c.hidden > 4096)
         return td3_fail(CN_ERR_CONFIG, "cn_ddpg_create: obs_dim / hidden / batch out of range");
-    const cn_td3_mlp* nets[4] = {&c.actor, &c.actor_t, &c.critic, &c.critic_t};
-    for (const cn_td3_mlp* n : nets)
-        if (!n->w1 || !n->b1 || !n->w2 || !n->b2 || !n->w3 || !n->b3) return td3_fail(CN_ERR_ARG, "cn_ddpg_create: null parameter pointer");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return td3_fail(CN_ERR_NO_DEVICE, "cn_ddpg_create: no HIP device (libcrowdnav has no CPU fallback)");
-    if (device < 0 || device >= ndev) return td3_fail(CN_ERR_ARG, "cn_ddpg_create: bad device ordinal");
-    DevScope scope(device);
-    cn_ddpg_s* h = new (std::nothrow) cn_ddpg_s();
-    if (!h) return td3_fail(CN_ERR_ARG, "cn_ddpg_create: out of memory");
-    h->cfg = c; h->device = device; h->B = c.batch; h->D = c.obs_dim; h->Dc = c.obs_dim + 2; h->H = c.hidden;
-    const size_t B = h->B, Dc = h->Dc, H = h->H;
-    h->qnt = (int)((H + 15) / 16); h->dant = (int)((H + 31) / 32);
-    const size_t words = 2 + 8                                         // counter, pw (8-byte aligned: first)
-                         + 2 * B * Dc + 2 * B + 2 * B                  // xs, x2, r, d, logits
-                         + 4 * B * H + 6 * B * H + 6 * B * H           // t_h, a_h, c_h, dz
-                         + 3 * B * h->qnt + 2 * B * h->dant + B + 2 * B // qpart, dapart, dq, dl
-                         + 1 + 4 + 2;                                  // loss, adam, steps
-    size_t mom_words = 0;
-    for (int net = 0; net < 2; ++net) for (int j = 0; j < 6; ++j) mom_words += 2 * ddpg_param_count(h, net, j);
-    hipError_t e = hipMalloc(&h->pool, (words + mom_words) * sizeof(float));
-    if (e != hipSuccess) { delete h; return td3_fail(CN_ERR_HIP, std::string("cn_ddpg_create: hipMalloc: ") + hipGetErrorString(e)); }
-    e = hipMemset(h->pool, 0, (words + mom_words) * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(h->pool); delete h; return td3_fail(CN_ERR_HIP, std::string("cn_ddpg_create: hipMemset: ") + hipGetErrorString(e)); }
-    float* q = h->pool;
-    auto take = [&](size_t n) { float* r_ = q; q += n; return r_; };
-    h->counter = (unsigned long long*)take(2);
-    h->pw = (double*)take(8);
-    { const double one[4] = {1.0, 1.0, 1.0, 1.0}; e = hipMemcpy(h->pw, one, sizeof(one), hipMemcpyHostToDevice); }
-    if (e != hipSuccess) { (void)hipFree(h->pool); delete h; return td3_fail(CN_ERR_HIP, std::string("cn_ddpg_create: hipMemcpy: ") + hipGetErrorString(e)); }
-    h->xs = take(B * Dc); h->x2 = take(B * Dc); h->r = take(B); h->d = take(B); h->logits = take(2 * B);
-    h->t_h1 = take(B * H); h->t_h2 = take(B * H); h->a_h1 = take(B * H); h->a_h2 = take(B * H);
-    for (int z = 0; z < 3; ++z) { h->c_h1[z] = take(B * H); h->c_h2[z] = take(B * H); }
-    h->dz2c = take(B * H); h->dz1c = take(B * H); h->dz2p = take(B * H); h->dz1p = take(B * H); h->dz2a = take(B * H); h->dz1a = take(B * H);
-    h->qpart = take(3 * B * h->qnt); h->dapart = take(2 * B * h->dant); h->dq = take(B); h->dl = take(2 * B);
-    h->loss = take(1); h->adam = take(4); h->steps = take(2);
-    for (int net = 0; net < 2; ++net) for (int j = 0; j < 6; ++j) for (int k = 0; k < 2; ++k) h->mom[net][j][k] = take(ddpg_param_count(h, net, j));
-    *out = h;
-    return CN_OK;
+    if (const int rc = check_mlps("cn_ddpg_create", {&c.actor, &c.actor_t, &c.critic, &c.critic_t})) return rc;
+    return learner_create("cn_ddpg_create", c, device, out);
 }
-
-extern "C" void cn_ddpg_destroy(cn_ddpg_handle h)
-{
-    if (!h) return;
-    DevScope scope(h->device);
-    (void)hipFree(h->pool);
-    delete h;
-}
-
+extern "C" void cn_ddpg_destroy(cn_ddpg_handle h) { delete h; }
 extern "C" const float* cn_ddpg_loss_dev(cn_ddpg_handle h) { return h ? h->loss : nullptr; }
-
-extern "C" const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what)     // as cn_td3_batch_dev; no target noise (what 4: NULL)
-{
-    if (!h) return nullptr;
-    switch (what) { case 0: return h->xs; case 1: return h->x2; case 2: return h->r; case 3: return h->d; default: return nullptr; }
-}
+extern "C" const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what) { return batch_dev(h, what); }     // no target noise (what 4: NULL)
 
 extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream)
 {
-    if (!h) return td3_fail(CN_ERR_ARG, "cn_ddpg_update: null handle");
-    const cn_ddpg_config& c = h->cfg;
-    if (!batch && (!c.replay_s || !c.replay_a || !c.replay_r || !c.replay_s2 || !c.replay_d || !c.replay_size_dev))
-        return td3_fail(CN_ERR_ARG, "cn_ddpg_update: no explicit batch and no replay ring in the configuration");
-    if (batch && (!batch->s || !batch->a || !batch->r || !batch->s2 || !batch->d)) return td3_fail(CN_ERR_ARG, "cn_ddpg_update: null batch pointer");
+    if (const int rc = check_update("cn_ddpg_update", h, batch)) return rc;
     if (batch && batch->target_noise) return td3_fail(CN_ERR_ARG, "cn_ddpg_update: DDPG has no target-policy noise (batch->target_noise must be NULL)");
+    const cn_ddpg_config& c = h->cfg;
     DevScope scope(h->device);
     hipStream_t st = (hipStream_t)stream;
-    const int B = h->B, D = h->D, Dc = h->Dc, H = h->H;
+    const int B = h->B, D = h->D, Dc = D + 2, H = h->H, qnt = h->qnt();
     // 1. sample / gather (ddpg.py:208-214); no noise is drawn
-    PrepArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    if (batch) { pa.rs = batch->s; pa.ra = batch->a; pa.rr = batch->r; pa.rs2 = batch->s2; pa.rd = batch->d; }
-    else { pa.rs = c.replay_s; pa.ra = c.replay_a; pa.rr = c.replay_r; pa.rs2 = c.replay_s2; pa.rd = c.replay_d; pa.size_dev = c.replay_size_dev; }
-    pa.xs = h->xs; pa.x2 = h->x2; pa.r = h->r; pa.d = h->d; pa.noise = nullptr; pa.counter = h->counter;
-    pa.seed = c.seed; pa.B = B; pa.D = D;
+    const PrepArgs pa = prep_args(*h, c, batch);
     hipLaunchKernelGGL(td3_prep_kernel, dim3(B), dim3(256), 0, st, pa);
-
-    auto fwd_job = [&](GemmJob& j, const float* X, int ldx, int K, const float* W, const float* b, float* Y) {
-        memset(&j, 0, sizeof(j));
-        j.A = X; j.B = W; j.C = Y; j.bias = b; j.I = B; j.J = H; j.R = K; j.lda = ldx; j.ldb = K; j.ldc = H; j.relu = 1;
-    };
-    auto head_job = [&](GemmJob& j, const float* h2, const cn_td3_mlp& pol, float* logits) {     // action columns = pol's heads, no noise
-        j.R = D; j.hd_h2 = h2; j.hd_W3 = pol.w3; j.hd_b3 = pol.b3; j.hd_noise = nullptr; j.hd_logits = logits; j.hd_H = H;
-        j.hd_max_v = c.max_v; j.hd_max_w = c.max_w;
-    };
-    auto bwd_data_job = [&](GemmJob& j, const float* dY, const float* W, const float* mask, float* dX) {
-        memset(&j, 0, sizeof(j));
-        j.A = dY; j.B = W; j.C = dX; j.mask = mask; j.I = B; j.J = H; j.R = H; j.lda = H; j.ldb = H; j.ldc = H;
-    };
-    auto wgrad_job = [&](GemmJob& j, const float* dY, const float* X, int ldx, int K, float* W, float* bparam, int net, int wj,
-                         const float* adam, float* tgt, float* btgt) {
-        memset(&j, 0, sizeof(j));
-        j.A = dY; j.B = X; j.C = W; j.I = H; j.J = K; j.R = B; j.lda = H; j.ldb = ldx; j.ldc = K;
-        j.m = h->mom[net][wj][0]; j.v = h->mom[net][wj][1]; j.bparam = bparam; j.bm = h->mom[net][wj + 1][0]; j.bv = h->mom[net][wj + 1][1];
-        j.adam = adam; j.tgt = tgt; j.btgt = btgt;
-    };
     GemmArgs ga;
-    ga.beta1 = c.beta1; ga.beta2 = c.beta2; ga.eps = c.eps; ga.tau = c.tau;
-    ga.tick.adam = h->adam; ga.tick.steps = h->steps; ga.tick.pw = h->pw; ga.tick.counter = h->counter; ga.tick.do_actor = 1;   // both optimizers step on every update
-    ga.tick.lr_critic = c.lr_critic; ga.tick.lr_actor = c.lr_actor; ga.tick.beta1 = c.beta1; ga.tick.beta2 = c.beta2;
-    ga.do_tick = 0;
+    memset(&ga, 0, sizeof(ga));
+    adam_args(ga, *h, c, 1);                        // both optimizers step on every update
     // 2-3. actor_t's hidden layers on s2 (ddpg.py:219), actor's on s (:216)
-    fwd_job(ga.job[0], h->x2, Dc, D, c.actor_t.w1, c.actor_t.b1, h->t_h1);
-    fwd_job(ga.job[1], h->xs, Dc, D, c.actor.w1, c.actor.b1, h->a_h1);
+    fwd_job(ga.job[0], h->x2, B, Dc, D, c.actor_t.w1, c.actor_t.b1, h->t_h1, H, 1);
+    fwd_job(ga.job[1], h->xs, B, Dc, D, c.actor.w1, c.actor.b1, h->a_h1, H, 1);
     launch_gemm<GEMM_F>(ga, 2, st);
-    fwd_job(ga.job[0], h->t_h1, H, H, c.actor_t.w2, c.actor_t.b2, h->t_h2);
-    fwd_job(ga.job[1], h->a_h1, H, H, c.actor.w2, c.actor.b2, h->a_h2);
+    fwd_job(ga.job[0], h->t_h1, B, H, H, c.actor_t.w2, c.actor_t.b2, h->t_h2, H, 1);
+    fwd_job(ga.job[1], h->a_h1, B, H, H, c.actor.w2, c.actor.b2, h->a_h2, H, 1);
     launch_gemm<GEMM_F>(ga, 2, st);
     // 4. the critics' first layers: critic on (s, a) (:229), critic on (s, pi(s)) (:216, the logits kept for the heads' backward),
-    // critic_t on (s2, pi_t(s2)) (:220) -- the policies' last layers and heads evaluated in place of the action columns
-    fwd_job(ga.job[0], h->xs, Dc, Dc, c.critic.w1, c.critic.b1, h->c_h1[0]);
-    fwd_job(ga.job[1], h->xs, Dc, Dc, c.critic.w1, c.critic.b1, h->c_h1[1]);
-    head_job(ga.job[1], h->a_h2, c.actor, h->logits);
-    fwd_job(ga.job[2], h->x2, Dc, Dc, c.critic_t.w1, c.critic_t.b1, h->c_h1[2]);
-    head_job(ga.job[2], h->t_h2, c.actor_t, nullptr);
+    // critic_t on (s2, pi_t(s2)) (:220) -- the policies' last layers and heads evaluated in place of the action columns, no noise
+    fwd_job(ga.job[0], h->xs, B, Dc, Dc, c.critic.w1, c.critic.b1, h->c_h1[0], H, 1);
+    fwd_job(ga.job[1], h->xs, B, Dc, Dc, c.critic.w1, c.critic.b1, h->c_h1[1], H, 1);
+    head_job(ga.job[1], D, H, h->a_h2, c.actor, nullptr, h->logits, c.max_v, c.max_w);
+    fwd_job(ga.job[2], h->x2, B, Dc, Dc, c.critic_t.w1, c.critic_t.b1, h->c_h1[2], H, 1);
+    head_job(ga.job[2], D, H, h->t_h2, c.actor_t, nullptr, nullptr, c.max_v, c.max_w);
     launch_gemm<GEMM_F>(ga, 3, st);
     // 5. their second layers; q = h2 . W3 + b3 as per-tile partial sums of critic (slot 0) and critic_t (slot 2); on the pi(s)
     // branch the first link of -mean Q (:217): dz = -(1 / B) W3 [h2 > 0]; the tick
-    fwd_job(ga.job[0], h->c_h1[0], H, H, c.critic.w2, c.critic.b2, h->c_h2[0]);
-    ga.job[0].qp_w3 = c.critic.w3; ga.job[0].qp_b3 = c.critic.b3; ga.job[0].qp_out = h->qpart; ga.job[0].qp_nt = h->qnt;
-    fwd_job(ga.job[1], h->c_h1[1], H, H, c.critic.w2, c.critic.b2, h->c_h2[1]);
+    fwd_job(ga.job[0], h->c_h1[0], B, H, H, c.critic.w2, c.critic.b2, h->c_h2[0], H, 1);
+    ga.job[0].qp_w3 = c.critic.w3; ga.job[0].qp_b3 = c.critic.b3; ga.job[0].qp_out = h->qpart; ga.job[0].qp_nt = qnt;
+    fwd_job(ga.job[1], h->c_h1[1], B, H, H, c.critic.w2, c.critic.b2, h->c_h2[1], H, 1);
     ga.job[1].dz_w3 = c.critic.w3; ga.job[1].dz_out = h->dz2p; ga.job[1].dz_rows = (float)B;
-    fwd_job(ga.job[2], h->c_h1[2], H, H, c.critic_t.w2, c.critic_t.b2, h->c_h2[2]);
-    ga.job[2].qp_w3 = c.critic_t.w3; ga.job[2].qp_b3 = c.critic_t.b3; ga.job[2].qp_out = h->qpart + (size_t)2 * B * h->qnt; ga.job[2].qp_nt = h->qnt;
+    fwd_job(ga.job[2], h->c_h1[2], B, H, H, c.critic_t.w2, c.critic_t.b2, h->c_h2[2], H, 1);
+    ga.job[2].qp_w3 = c.critic_t.w3; ga.job[2].qp_b3 = c.critic_t.b3; ga.job[2].qp_out = h->qpart + (size_t)2 * B * qnt; ga.job[2].qp_nt = qnt;
     ga.do_tick = 1;
     launch_gemm<GEMM_F>(ga, 3, st);
     ga.do_tick = 0;
     // 6. both through the PRE-update critic: the TD target y = r + (1 - d) gamma q_t (:221-222, one target), the MSE gradient
     // (:230) and dz1 = (dz2 W2) [h1 > 0]; the pi(s) branch on to the action (the two action columns of W1)
-    bwd_data_job(ga.job[0], h->c_h2[0], c.critic.w2, h->c_h1[0], h->dz1c);
-    {
-        GemmJob& j = ga.job[0];
-        j.hb_h2 = h->c_h2[0]; j.hb_w3 = c.critic.w3; j.hb_qpart = h->qpart; j.hb_qnt = h->qnt; j.hb_net = 0; j.hb_single = 1;
-        j.hb_r = h->r; j.hb_d = h->d; j.hb_gamma = c.gamma; j.hb_dq = h->dq; j.hb_dz2 = h->dz2c;
-    }
-    bwd_data_job(ga.job[1], h->dz2p, c.critic.w2, h->c_h1[1], h->dz1p);
-    ga.job[1].da_w = c.critic.w1 + D; ga.job[1].da_ld = Dc; ga.job[1].da_out = h->dapart; ga.job[1].da_nt = h->dant;
+    critic_bwd_job(ga.job[0], *h, c.critic, h->c_h1[0], h->c_h2[0], 0, 1, c.gamma, h->dq, h->dz2c, h->dz1c);
+    dgrad_job(ga.job[1], h->dz2p, B, H, c.critic.w2, h->c_h1[1], h->dz1p, H);
+    ga.job[1].da_w = c.critic.w1 + D; ga.job[1].da_ld = Dc; ga.job[1].da_out = h->dapart; ga.job[1].da_nt = h->dant();
     launch_gemm<GEMM_G>(ga, 2, st);
     // 7. the actor: through the heads' derivatives and its second hidden layer
-    bwd_data_job(ga.job[0], h->a_h2, c.actor.w2, h->a_h1, h->dz1a);
-    {
-        GemmJob& j = ga.job[0];
-        j.ab_h2 = h->a_h2; j.ab_w3 = c.actor.w3; j.ab_dapart = h->dapart; j.ab_dant = h->dant; j.ab_logits = h->logits;
-        j.ab_max_v = c.max_v; j.ab_max_w = c.max_w; j.ab_dl = h->dl; j.ab_dz2 = h->dz2a;
-    }
+    actor_bwd_job(ga.job[0], *h, c.actor, c.max_v, c.max_w, h->dz2a, h->dz1a);
     launch_gemm<GEMM_G>(ga, 1, st);
     // 8. weight gradients folded into both Adam steps (:233-238) and the soft updates of both targets (:241-242, from the
     // stepped weights); linear3's gradients are the one- / two-row jobs; loss_out = the critic's MSE
-    wgrad_job(ga.job[0], h->dz2c, h->c_h1[0], H, H, c.critic.w2, c.critic.b2, 1, 2, h->adam, c.critic_t.w2, c.critic_t.b2);
-    wgrad_job(ga.job[1], h->dz1c, h->xs, Dc, Dc, c.critic.w1, c.critic.b1, 1, 0, h->adam, c.critic_t.w1, c.critic_t.b1);
-    wgrad_job(ga.job[2], h->dq, h->c_h2[0], H, H, c.critic.w3, c.critic.b3, 1, 4, h->adam, c.critic_t.w3, c.critic_t.b3);
-    ga.job[2].I = 1; ga.job[2].lda = 1; ga.job[2].loss_out = h->loss;
-    wgrad_job(ga.job[3], h->dz2a, h->a_h1, H, H, c.actor.w2, c.actor.b2, 0, 2, h->adam + 2, c.actor_t.w2, c.actor_t.b2);
-    wgrad_job(ga.job[4], h->dz1a, h->xs, Dc, D, c.actor.w1, c.actor.b1, 0, 0, h->adam + 2, c.actor_t.w1, c.actor_t.b1);
-    wgrad_job(ga.job[5], h->dl, h->a_h2, H, H, c.actor.w3, c.actor.b3, 0, 4, h->adam + 2, c.actor_t.w3, c.actor_t.b3);
-    ga.job[5].I = 2; ga.job[5].lda = 2;
+    wgrad_job(ga.job[0], h->dz2c, H, h->c_h1[0], H, H, B, c.critic.w2, c.critic.b2, &h->mom[1][2], h->adam, c.critic_t.w2, c.critic_t.b2);
+    wgrad_job(ga.job[1], h->dz1c, H, h->xs, Dc, Dc, B, c.critic.w1, c.critic.b1, &h->mom[1][0], h->adam, c.critic_t.w1, c.critic_t.b1);
+    wgrad_job(ga.job[2], h->dq, 1, h->c_h2[0], H, H, B, c.critic.w3, c.critic.b3, &h->mom[1][4], h->adam, c.critic_t.w3, c.critic_t.b3);
+    ga.job[2].loss_out = h->loss;
+    wgrad_job(ga.job[3], h->dz2a, H, h->a_h1, H, H, B, c.actor.w2, c.actor.b2, &h->mom[0][2], h->adam + 2, c.actor_t.w2, c.actor_t.b2);
+    wgrad_job(ga.job[4], h->dz1a, H, h->xs, Dc, D, B, c.actor.w1, c.actor.b1, &h->mom[0][0], h->adam + 2, c.actor_t.w1, c.actor_t.b1);
+    wgrad_job(ga.job[5], h->dl, 2, h->a_h2, H, H, B, c.actor.w3, c.actor.b3, &h->mom[0][4], h->adam + 2, c.actor_t.w3, c.actor_t.b3);
     launch_gemm<GEMM_H>(ga, 6, st);
     TD3CHK(hipGetLastError());
     return CN_OK;
@@ -1395,25 +1366,25 @@ __global__ void __launch_bounds__(256) dqn_act_kernel(DqnActArgs p)
 }
 }  // namespace
 
-struct cn_dqn_s {
+struct cn_dqn_s : Learner {
     cn_dqn_config cfg;
-    int device;
-    int B, D, ld, H;
-    float* pool = nullptr;
-    float *x, *r, *d, *h1, *h2, *th1, *th2, *q, *q2, *tq, *Y, *dq, *dz2, *dz1, *loss;   // q: pre-step Q, q2: chunk 2's
+    float *x, *r, *d, *h1, *h2, *th1, *th2, *q, *q2, *tq, *Y, *dq, *dz2, *dz1;   // q: pre-step Q, q2: chunk 2's
     int32_t *a, *chunk, *flags;
-    unsigned long long *counter, *kcur;
-    float* acc[6];                                 // RMSprop accumulators of w1, b1, w2, b2, w3, b3
+    unsigned long long* kcur;
+    float* acc[6][2];                              // RMSprop accumulators of w1, b1, w2, b2, w3, b3 ([.][1]: null, Adam's second moment)
+    size_t params(int j) const { return param_count(D, 3, H, j); }
+    void layout(Pool& p)
+    {
+        const size_t b = B, ld = cfg.obs_ld, h = H;
+        p.take(counter, 1); p.take(kcur, 1);
+        p.take(x, 2 * b * ld); p.take(r, b); p.take(d, b);
+        p.take(h1, 2 * b * h); p.take(h2, 2 * b * h); p.take(th1, b * h); p.take(th2, b * h);
+        p.take(q, 2 * b * 3); p.take(Y, 2 * b * 3); p.take(dq, 2 * b * 3); p.take(q2, 2 * b * 3); p.take(tq, b * 3);
+        p.take(dz2, 2 * b * h); p.take(dz1, 2 * b * h); p.take(loss, 2);
+        p.take(a, b); p.take(chunk, 2 * b); p.take(flags, 8);
+        for (int j = 0; j < 6; ++j) p.take(acc[j][0], params(j));
+    }
 };
-
-namespace {
-size_t dqn_param_count(const cn_dqn_s* h, int j)
-{
-    const size_t H = (size_t)h->H, D = (size_t)h->D;
-    switch (j) { case 0: return H * D; case 1: return H; case 2: return H * H; case 3: return H; case 4: return 3 * H; default: return 3; }
-}
-bool dqn_mlp_ok(const cn_td3_mlp& n) { return n.w1 && n.b1 && n.w2 && n.b2 && n.w3 && n.b3; }
-}  // namespace
 
 extern "C" int cn_dqn_create(const cn_dqn_config* cfg, int device, cn_dqn_handle* out)
 {
@@ -1421,48 +1392,10 @@ extern "C" int cn_dqn_create(const cn_dqn_config* cfg, int device, cn_dqn_handle
     const cn_dqn_config& c = *cfg;
     if (c.obs_dim < 1 || c.obs_ld < c.obs_dim || c.hidden < 1 || c.hidden > 4096 || c.batch < 1 || c.batch > 4096 || c.target_every < 1 || c.learn_start < 0)
         return td3_fail(CN_ERR_CONFIG, "cn_dqn_create: obs_dim / obs_ld / hidden / batch / target_every / learn_start out of range");
-    if (!dqn_mlp_ok(c.q) || !dqn_mlp_ok(c.q_t)) return td3_fail(CN_ERR_ARG, "cn_dqn_create: null parameter pointer");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return td3_fail(CN_ERR_NO_DEVICE, "cn_dqn_create: no HIP device (libcrowdnav has no CPU fallback)");
-    if (device < 0 || device >= ndev) return td3_fail(CN_ERR_ARG, "cn_dqn_create: bad device ordinal");
-    DevScope scope(device);
-    cn_dqn_s* h = new (std::nothrow) cn_dqn_s();
-    if (!h) return td3_fail(CN_ERR_ARG, "cn_dqn_create: out of memory");
-    h->cfg = c; h->device = device; h->B = c.batch; h->D = c.obs_dim; h->ld = c.obs_ld; h->H = c.hidden;
-    const size_t B = h->B, ld = h->ld, H = h->H;
-    const size_t words = 4 + 2 * B * ld + 2 * B                  // counter, kcur (8-byte aligned: first); x, r, d
-                         + 2 * 2 * B * H + 2 * B * H             // h1, h2, th1, th2
-                         + 4 * 2 * B * 3 + B * 3                 // q, Y, dq, q2, tq
-                         + 2 * 2 * B * H + 2                     // dz2, dz1, loss
-                         + B + 2 * B + 8;                        // a, chunk, flags
-    size_t acc_words = 0;
-    for (int j = 0; j < 6; ++j) acc_words += dqn_param_count(h, j);
-    hipError_t e = hipMalloc(&h->pool, (words + acc_words) * sizeof(float));
-    if (e != hipSuccess) { delete h; return td3_fail(CN_ERR_HIP, std::string("cn_dqn_create: hipMalloc: ") + hipGetErrorString(e)); }
-    e = hipMemset(h->pool, 0, (words + acc_words) * sizeof(float));
-    if (e != hipSuccess) { (void)hipFree(h->pool); delete h; return td3_fail(CN_ERR_HIP, std::string("cn_dqn_create: hipMemset: ") + hipGetErrorString(e)); }
-    float* q = h->pool;
-    auto take = [&](size_t n) { float* r_ = q; q += n; return r_; };
-    h->counter = (unsigned long long*)take(2); h->kcur = (unsigned long long*)take(2);
-    h->x = take(2 * B * ld); h->r = take(B); h->d = take(B);
-    h->h1 = take(2 * B * H); h->h2 = take(2 * B * H); h->th1 = take(B * H); h->th2 = take(B * H);
-    h->q = take(2 * B * 3); h->Y = take(2 * B * 3); h->dq = take(2 * B * 3); h->q2 = take(2 * B * 3); h->tq = take(B * 3);
-    h->dz2 = take(2 * B * H); h->dz1 = take(2 * B * H); h->loss = take(2);
-    h->a = (int32_t*)take(B); h->chunk = (int32_t*)take(2 * B);
-    h->flags = (int32_t*)take(8);
-    for (int j = 0; j < 6; ++j) h->acc[j] = take(dqn_param_count(h, j));
-    *out = h;
-    return CN_OK;
+    if (const int rc = check_mlps("cn_dqn_create", {&c.q, &c.q_t})) return rc;
+    return learner_create("cn_dqn_create", c, device, out);
 }
-
-extern "C" void cn_dqn_destroy(cn_dqn_handle h)
-{
-    if (!h) return;
-    DevScope scope(h->device);
-    (void)hipFree(h->pool);
-    delete h;
-}
-
+extern "C" void cn_dqn_destroy(cn_dqn_handle h) { delete h; }
 extern "C" const float* cn_dqn_loss_dev(cn_dqn_handle h) { return h ? h->loss : nullptr; }
 
 extern "C" const void* cn_dqn_batch_dev(cn_dqn_handle h, int what)
@@ -1476,14 +1409,11 @@ extern "C" const void* cn_dqn_batch_dev(cn_dqn_handle h, int what)
 
 extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* stream)
 {
-    if (!h) return td3_fail(CN_ERR_ARG, "cn_dqn_update: null handle");
+    if (const int rc = check_update("cn_dqn_update", h, batch)) return rc;
     const cn_dqn_config& c = h->cfg;
-    if (!batch && (!c.replay_s || !c.replay_a || !c.replay_r || !c.replay_s2 || !c.replay_d || !c.replay_size_dev))
-        return td3_fail(CN_ERR_ARG, "cn_dqn_update: no explicit batch and no replay ring in the configuration");
-    if (batch && (!batch->s || !batch->a || !batch->r || !batch->s2 || !batch->d)) return td3_fail(CN_ERR_ARG, "cn_dqn_update: null batch pointer");
     DevScope scope(h->device);
     hipStream_t st = (hipStream_t)stream;
-    const int B = h->B, D = h->D, ld = h->ld, H = h->H;
+    const int B = h->B, D = h->D, ld = c.obs_ld, H = h->H;
     DqnPrepArgs pa;
     memset(&pa, 0, sizeof(pa));
     if (batch) { pa.rs = batch->s; pa.rs2 = batch->s2; pa.rr = batch->r; pa.rd = batch->d; pa.a_in = batch->a; pa.perm_in = batch->perm; }
@@ -1496,24 +1426,20 @@ extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* s
     GemmArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.rms_lr = c.lr; ga.rms_rho = c.rho; ga.rms_eps = c.eps;
-    auto fwd = [&](GemmJob& j, const float* X, int I, int ldx, int K, const float* W, const float* b, float* Y, int J, int relu) {
-        memset(&j, 0, sizeof(j));
-        j.A = X; j.B = W; j.C = Y; j.bias = b; j.I = I; j.J = J; j.R = K; j.lda = ldx; j.ldb = K; j.ldc = J; j.relu = relu;
-    };
     // every GEMM of a chunk is gated on the device (the launches of chunk 2 return at once when F = 0; all of them while the replay
     // path waits for learn_start)
     auto forward = [&](int chunk) {               // online net on the 2B stacked rows (+ chunk 1: the target net on the B s2 rows)
         const int nj = chunk == 1 ? 2 : 1;
         float* q = chunk == 1 ? h->q : h->q2;
         ga.rms_gate = h->flags + (chunk - 1);
-        fwd(ga.job[0], h->x, 2 * B, ld, D, c.q.w1, c.q.b1, h->h1, H, 1);
-        fwd(ga.job[1], h->x + (size_t)B * ld, B, ld, D, c.q_t.w1, c.q_t.b1, h->th1, H, 1);
+        fwd_job(ga.job[0], h->x, 2 * B, ld, D, c.q.w1, c.q.b1, h->h1, H, 1);
+        fwd_job(ga.job[1], h->x + (size_t)B * ld, B, ld, D, c.q_t.w1, c.q_t.b1, h->th1, H, 1);
         launch_gemm<GEMM_F, true>(ga, nj, st);
-        fwd(ga.job[0], h->h1, 2 * B, H, H, c.q.w2, c.q.b2, h->h2, H, 1);
-        fwd(ga.job[1], h->th1, B, H, H, c.q_t.w2, c.q_t.b2, h->th2, H, 1);
+        fwd_job(ga.job[0], h->h1, 2 * B, H, H, c.q.w2, c.q.b2, h->h2, H, 1);
+        fwd_job(ga.job[1], h->th1, B, H, H, c.q_t.w2, c.q_t.b2, h->th2, H, 1);
         launch_gemm<GEMM_F, true>(ga, nj, st);
-        fwd(ga.job[0], h->h2, 2 * B, H, H, c.q.w3, c.q.b3, q, 3, 0);
-        fwd(ga.job[1], h->th2, B, H, H, c.q_t.w3, c.q_t.b3, h->tq, 3, 0);
+        fwd_job(ga.job[0], h->h2, 2 * B, H, H, c.q.w3, c.q.b3, q, 3, 0);
+        fwd_job(ga.job[1], h->th2, B, H, H, c.q_t.w3, c.q_t.b3, h->tq, 3, 0);
         launch_gemm<GEMM_F, true>(ga, nj, st);
     };
     auto target = [&](int which) {
@@ -1524,25 +1450,14 @@ extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* s
     };
     auto backward = [&](const int* gate) {        // dz2 = (dq W3) [h2 > 0], dz1 = (dz2 W2) [h1 > 0], then RMSprop of all six tensors
         ga.rms_gate = gate;
-        GemmJob& j = ga.job[0];
-        memset(&j, 0, sizeof(j));
-        j.A = h->dq; j.B = c.q.w3; j.C = h->dz2; j.mask = h->h2; j.I = 2 * B; j.J = H; j.R = 3; j.lda = 3; j.ldb = H; j.ldc = H;
+        dgrad_job(ga.job[0], h->dq, 2 * B, 3, c.q.w3, h->h2, h->dz2, H);
         launch_gemm<GEMM_G, true>(ga, 1, st);
-        memset(&j, 0, sizeof(j));
-        j.A = h->dz2; j.B = c.q.w2; j.C = h->dz1; j.mask = h->h1; j.I = 2 * B; j.J = H; j.R = H; j.lda = H; j.ldb = H; j.ldc = H;
+        dgrad_job(ga.job[0], h->dz2, 2 * B, H, c.q.w2, h->h1, h->dz1, H);
         launch_gemm<GEMM_G, true>(ga, 1, st);
-        auto wj = [&](GemmJob& k, const float* dY, int I, int lda, const float* X, int ldx, int J, float* W, float* bp, int slot) {
-            memset(&k, 0, sizeof(k));
-            k.A = dY; k.B = X; k.C = W; k.I = I; k.J = J; k.R = 2 * B; k.lda = lda; k.ldb = ldx; k.ldc = J;
-            k.m = h->acc[slot]; k.bparam = bp; k.bm = h->acc[slot + 1];
-        };
-        wj(ga.job[0], h->dz2, H, H, h->h1, H, H, c.q.w2, c.q.b2, 2);
-        wj(ga.job[1], h->dz1, H, H, h->x, ld, D, c.q.w1, c.q.b1, 0);
-        wj(ga.job[2], h->dq, 3, 3, h->h2, H, H, c.q.w3, c.q.b3, 4);
-        ga.rms_gate = gate;
-        int gx = 0, gy = 0;
-        for (int z = 0; z < 3; ++z) { const int x_ = (ga.job[z].J + 31) / 32, y_ = (ga.job[z].I + 31) / 32; gx = x_ > gx ? x_ : gx; gy = y_ > gy ? y_ : gy; }
-        hipLaunchKernelGGL(td3_wgrad_kernel<true>, dim3(gx, gy, 3), dim3(256), 0, st, ga);
+        wgrad_job(ga.job[0], h->dz2, H, h->h1, H, H, 2 * B, c.q.w2, c.q.b2, &h->acc[2]);
+        wgrad_job(ga.job[1], h->dz1, H, h->x, ld, D, 2 * B, c.q.w1, c.q.b1, &h->acc[0]);
+        wgrad_job(ga.job[2], h->dq, 3, h->h2, H, H, 2 * B, c.q.w3, c.q.b3, &h->acc[4]);
+        launch_gemm<GEMM_H, true>(ga, 3, st);
     };
     // chunk 1 (its Y from the pre-step nets), then chunk 2 on the stepped weights (gated off on the device when F = 0)
     forward(1);
@@ -1554,7 +1469,7 @@ extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* s
     DqnCopyArgs ca;
     const float* src[6] = {c.q.w1, c.q.b1, c.q.w2, c.q.b2, c.q.w3, c.q.b3};
     float* dst[6] = {c.q_t.w1, c.q_t.b1, c.q_t.w2, c.q_t.b2, c.q_t.w3, c.q_t.b3};
-    for (int j = 0; j < 6; ++j) { ca.src[j] = src[j]; ca.dst[j] = dst[j]; ca.n[j] = (long long)dqn_param_count(h, j); }
+    for (int j = 0; j < 6; ++j) { ca.src[j] = src[j]; ca.dst[j] = dst[j]; ca.n[j] = (long long)h->params(j); }
     ca.flags = h->flags; ca.counter = h->counter; ca.kcur = h->kcur;
     hipLaunchKernelGGL(dqn_copy_kernel, dim3(128), dim3(256), 0, st, ca);
     TD3CHK(hipGetLastError());
@@ -1564,7 +1479,7 @@ extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* s
 extern "C" int cn_dqn_act(const cn_dqn_act_io* io, int device, void* stream)
 {
     if (!io || !io->obs || !io->action || !io->twist) return td3_fail(CN_ERR_ARG, "cn_dqn_act: null argument");
-    if (!dqn_mlp_ok(io->q)) return td3_fail(CN_ERR_ARG, "cn_dqn_act: null parameter pointer");
+    if (!mlp_ok(io->q)) return td3_fail(CN_ERR_ARG, "cn_dqn_act: null parameter pointer");
     if (io->n < 1 || io->obs_dim < 1 || io->obs_ld < io->obs_dim || io->hidden < 1 || io->hidden > 480)
         return td3_fail(CN_ERR_CONFIG, "cn_dqn_act: n / obs_dim / obs_ld / hidden out of range (hidden <= 480: two 16-row activations in 64 KB of LDS)");
     if (!(io->epsilon_discount >= 0.0 && io->epsilon_discount <= 1.0) || !(io->epsilon_min > 0.0))

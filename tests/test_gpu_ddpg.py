@@ -395,7 +395,7 @@ def test_trainer_runs_ddpg_end_to_end_and_evaluates_its_checkpoint(tmp_path, var
     assert agent.actor.linear1.in_features == (363 if variant != "fused" else 398)
     assert episodes > 64
     if variant == "fused":
-        assert getattr(agent, "_ddpg_h", None)
+        assert getattr(agent, "_fused", None) and agent._fused.h
     else:
         assert float(agent.noise.state.abs().max()) > 0          # OU states moved (and were reset per finished episode)
     latest = int(open(os.path.join(out, "latest_checkpoint.txt")).read().split()[0])

@@ -361,7 +361,7 @@ def test_agent_replay_indices_follow_the_statement(algo):
     B, cap = 16, 50
     agent = Agent(obs_dim=OBS, hidden=HID, batch_size=B, memory_size=cap, device="cuda", seed=5)
     agent.enable_fused_update()
-    hnd = agent._td3_h if algo == "td3" else agent._ddpg_h
+    hnd = agent._fused.h
     view = L.cn_td3_batch_dev if algo == "td3" else L.cn_ddpg_batch_dev
     rng = np.random.default_rng(3)
     slot_t = np.full(cap, -1, dtype=np.int64)
