@@ -221,7 +221,7 @@ class _Pass:
         lin = lambda h, w, b: self.mm(torch.cat([h, ones], 1), torch.cat([w, b[:, None]], 1).T)   # (the bias: one more term)
         z1 = lin(x, p["w1"], p["b1"]); h1 = z1 * self.mask(key + ".1", z1)
         z2 = lin(h1, p["w2"], p["b2"]); h2 = z2 * self.mask(key + ".2", z2)
-        return dict(h1=h1, h2=h2, out=lin(h2, p["w3"], p["b3"]), m1=self.masks[key + ".1"], m2=self.masks[key + ".2"])
+        return dict(z1=z1, z2=z2, h1=h1, h2=h2, out=lin(h2, p["w3"], p["b3"]), m1=self.masks[key + ".1"], m2=self.masks[key + ".2"])
 
     def heads(self, lg, cfg):
         """actions and head derivatives.  The derivatives are max_v s (1 - s) and max_w (1 - t^2): near saturation 1 - s and
@@ -377,14 +377,14 @@ def zero_tile(g, i0=0, j0=0, size=16):
 
 
 # ---- ReLU margins -------------------------------------------------------------------------------------------------------------
-def plant_dead_units(P, hidden):
-    """Unit 1 of the first and unit hidden - 2 of the second hidden layer of each local network get a zero weight row and a zero
-    bias: their pre-activation is exactly 0 in any summation order, so nothing flows through them (hidden >= 4).  Returns
+def plant_dead_units(P, hidden, nets=LOCAL):
+    """Unit 1 of the first and unit hidden - 2 of the second hidden layer of each local network (`nets`) get a zero weight row and
+    a zero bias: their pre-activation is exactly 0 in any summation order, so nothing flows through them (hidden >= 4).  Returns
     {net: (unit of layer 1, unit of layer 2)}."""
     if hidden < 4:
         return {}
     dead = {}
-    for n in LOCAL:
+    for n in nets:
         u1, u2 = 1, hidden - 2
         P[n]["w1"][u1].zero_(); P[n]["b1"][u1] = 0
         P[n]["w2"][u2].zero_(); P[n]["b2"][u2] = 0
