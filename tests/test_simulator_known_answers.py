@@ -182,6 +182,32 @@ def test_rounding_restatements_match_python_and_numpy(oracle_mod):
             assert L.cno_py_round(x, nd) == round(x, nd), (x, nd)
             assert L.cno_np_around(x, nd) == float(np.around(np.float64(x), nd)), (x, nd)
             assert L.cno_np_around(x, nd) == float(round(np.float64(x), nd)), (x, nd)
+    # ... and on the adversarial sets of tests/device_math_ref.py (every decimal near-tie stepped by ulps, every exact binary tie,
+    # negatives that round to zero, the 2^31 guard, products up to 2^52; the IoU set with its sweep through the 0.0005 tie), for
+    # BOTH Python versions' rule, values and the sign of a zero compared separately: the kernel is held to the same references on
+    # the same sets by tests/test_gpu_device_math.py, so a misreading of Python that oracle and kernel share shows here
+    import device_math_ref as R
+    try:
+        for nd in (2, 3):
+            xs = R.round_guarded(nd)
+            for py2 in (0, 1):
+                L.cno_set_py2_round(py2)
+                got = np.array([L.cno_py_round(float(x), nd) for x in xs])
+                ref = R.py_round(xs, nd, py2)
+                assert np.array_equal(got, ref), (nd, py2, xs[got != ref][:5])
+                assert np.array_equal(np.signbit(got), np.signbit(ref)), (nd, py2, xs[np.signbit(got) != np.signbit(ref)][:5])
+            got = np.array([L.cno_np_around(float(x), nd) for x in xs])
+            ref = R.np_around(xs, nd)
+            assert np.array_equal(got, ref) and np.array_equal(np.signbit(got), np.signbit(ref)), nd
+        q = R.iou_set()
+        for py2 in (0, 1):
+            L.cno_set_py2_round(py2)
+            got = np.array([L.cno_iou(*(float(v) for v in t)) for t in zip(*q)])
+            ref = R.iou3(*q, py2)
+            assert np.array_equal(got, ref), (py2, np.nonzero(got != ref)[0][:5])
+            assert np.array_equal(np.signbit(got), np.signbit(ref)), py2
+    finally:
+        L.cno_set_py2_round(0)
 
 
 # ---- cn_config.ped_contact = 1 (row A2): frictionless rigid contact, WORLD:86-145 -------------------------------------
