@@ -10,4 +10,7 @@ def __getattr__(name):
     if name in ("VecEnv", "VecEnvGroups", "Env"):
         from . import env
         return getattr(env, name)
+    if name == "sac":          # the SAC learner (crowdnav.sac.Agent), imported on first use like the env classes
+        import importlib
+        return importlib.import_module(".sac", __name__)
     raise AttributeError(name)

@@ -36,6 +36,7 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_td3_create", "cn_td3_destroy", "cn_td3_update", "cn_td3_loss_dev", "cn_td3_batch_dev", "cn_td3_last_error",
            "cn_ddpg_create", "cn_ddpg_destroy", "cn_ddpg_update", "cn_ddpg_loss_dev", "cn_ddpg_batch_dev",
            "cn_dqn_create", "cn_dqn_destroy", "cn_dqn_update", "cn_dqn_loss_dev", "cn_dqn_batch_dev", "cn_dqn_act",
+           "cn_sac_create", "cn_sac_destroy", "cn_sac_update", "cn_sac_loss_dev", "cn_sac_batch_dev", "cn_sac_act",
            "cn_replay_write", "cn_episode_log_add"]
 
 
@@ -151,6 +152,33 @@ class CnDqnActIO(C.Structure):
                 ("reserved", C.c_int32), ("q", CnTd3Mlp), ("epsilon", C.c_double), ("epsilon_discount", C.c_double),
                 ("epsilon_min", C.c_double), ("episodes_dev", C.c_void_p), ("seed", C.c_uint64),
                 ("counter", C.c_uint64), ("action", C.c_void_p), ("twist", C.c_void_p), ("q_out", C.c_void_p)]
+
+
+class CnSacActor(C.Structure):
+    """Mirror of `cn_sac_actor`: the trunk's two layers, then the two heads."""
+    _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "mean_w", "mean_b", "log_std_w", "log_std_b")]
+
+
+class CnSacConfig(C.Structure):
+    """Mirror of `cn_sac_config` (include/crowdnav.h)."""
+    _fields_ = [("obs_dim", C.c_int32), ("hidden", C.c_int32), ("hidden_v", C.c_int32), ("batch", C.c_int32),
+                ("gamma", C.c_float), ("tau", C.c_float), ("lr_actor", C.c_float), ("lr_v", C.c_float), ("lr_q", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("max_v", C.c_float), ("max_w", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
+                ("mean_lambda", C.c_float), ("std_lambda", C.c_float), ("z_lambda", C.c_float), ("logp_eps", C.c_float),
+                ("soft_update", C.c_int32), ("reserved", C.c_int32),
+                ("actor", CnSacActor), ("q", CnTd3Mlp), ("v", CnTd3Mlp), ("v_t", CnTd3Mlp),
+                ("replay_s", C.c_void_p), ("replay_a", C.c_void_p), ("replay_r", C.c_void_p), ("replay_s2", C.c_void_p), ("replay_d", C.c_void_p),
+                ("replay_size_dev", C.c_void_p), ("seed", C.c_uint64)]
+
+
+class CnSacActIO(C.Structure):
+    """Mirror of `cn_sac_act_io` (include/crowdnav.h)."""
+    _fields_ = [("obs", C.c_void_p), ("obs_ld", C.c_int64), ("n", C.c_int32), ("obs_dim", C.c_int32), ("hidden", C.c_int32),
+                ("deterministic", C.c_int32), ("actor", CnSacActor),
+                ("max_v", C.c_float), ("max_w", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
+                ("eps", C.c_void_p), ("seed", C.c_uint64), ("counter", C.c_uint64),
+                ("twist", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p), ("z", C.c_void_p)]
 
 
 class CnTd3Batch(C.Structure):
@@ -293,6 +321,12 @@ def lib():
         L.cn_dqn_loss_dev.argtypes = [vp]; L.cn_dqn_loss_dev.restype = vp
         L.cn_dqn_batch_dev.argtypes = [vp, C.c_int]; L.cn_dqn_batch_dev.restype = vp
         L.cn_dqn_act.argtypes = [C.POINTER(CnDqnActIO), C.c_int, vp]
+        L.cn_sac_create.argtypes = [C.POINTER(CnSacConfig), C.c_int, C.POINTER(vp)]
+        L.cn_sac_destroy.argtypes = [vp]; L.cn_sac_destroy.restype = None
+        L.cn_sac_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]
+        L.cn_sac_loss_dev.argtypes = [vp]; L.cn_sac_loss_dev.restype = vp
+        L.cn_sac_batch_dev.argtypes = [vp, C.c_int]; L.cn_sac_batch_dev.restype = vp
+        L.cn_sac_act.argtypes = [C.POINTER(CnSacActIO), C.c_int, vp]
         L.cn_replay_write.argtypes = [C.POINTER(CnReplayRing), vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
         L.cn_episode_log_add.argtypes = [C.POINTER(CnEpisodeLog), vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, C.c_int, vp]
         _lib = L

@@ -22,6 +22,13 @@ dqn_model_ep<N>.pt / .json, CSV dqn_training.csv; `--learner fused` is cn_dqn_up
     python -m crowdnav.train --algo ddpg --scenario training_as_logged --waypoint-reward 0 --envs 16 --updates 16 --csv --learner fused
     python -m crowdnav.train --algo ddpg --evaluate --load runs/ddpg --obs-layout 1 --scenario crossing_8
 
+`--algo sac` trains the reference's SAC (sac.py; start_sac_training.py's values taken at their names; crowdnav.sac) on obs_layout 1
+with --max-steps 1000 (sac.yaml): cn_sac_act -> env.step -> replay -> learn, batch 64, lr 3e-4, tau 5e-3; --sac-value-net /
+--sac-soft-update choose between sac.py as committed (default) and what its calls intend; checkpoints
+sac_{actor,critic_v,critic_soft_q}_model_ep<N>.pt, CSV sac_training.csv; `--learner fused` is cn_sac_update:
+
+    python -m crowdnav.train --algo sac --scenario training_as_logged --waypoint-reward 0 --envs 16 --updates 16 --csv --learner fused
+
 What it keeps from the reference loop: Agent hyper-parameters (TRAIN:62-72), exploration noise sigma = 1.0 with the
 clip to v in [0, 0.22], w in [-2, 2], 1-based per-env step counters, `learn()` only once the replay holds more than a
 batch, target-network checkpoints named td3_{actor,critic1,critic2}_model_ep<N>.pt, one CSV row per finished episode
@@ -44,7 +51,7 @@ from . import presets
 from .config import Config
 from .env import VecEnv
 from .rollout import EpisodeStats, evaluate
-from . import ddpg, dqn, td3
+from . import ddpg, dqn, sac, td3
 
 
 def make_env(scenario, n_envs, max_steps, seed, device, ped_vmax=None, **switches):
@@ -147,7 +154,7 @@ def save_checkpoint(agent, outdir, episodes):
     os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
 
 
-CHECKPOINT_NETS = dict(td3=("actor", "critic1", "critic2"), ddpg=("actor", "critic"))
+CHECKPOINT_NETS = dict(td3=("actor", "critic1", "critic2"), ddpg=("actor", "critic"), sac=("actor", "critic_v", "critic_soft_q"))
 
 
 def make_dqn_agent(a, obs_ld, device, memory_size):
@@ -243,11 +250,91 @@ def train_dqn(a):
     return agent, episodes
 
 
+def train_sac(a):
+    """start_sac_training.py's loop for N environments, on train_dqn's pattern: cn_sac_act -> env.step -> replay -> `--updates`
+    learn() calls per launch once the replay holds more than a batch (TRAIN_SAC:127).  Enqueue-only between log intervals."""
+    dev = a.device
+    torch.cuda.set_device(dev)
+    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, **env_switches(a))
+    agent = make_agent(a, env.D, "cuda:%d" % dev, memory_size=a.memory)
+    if a.load:
+        load_checkpoint(agent, a)
+        ns = os.path.join(a.load, "noise_state_ep%d.txt" % a.load_episode)
+        if os.path.exists(ns):
+            agent.set_noise_state(*[int(x) for x in open(ns).read().split()])
+    if a.learner == "fused":
+        agent.enable_fused_update()
+    stats = EpisodeStats()
+    os.makedirs(a.out, exist_ok=True)
+    resumed = bool(a.load) and os.path.abspath(a.load) == os.path.abspath(a.out)
+    obs = env.reset()
+    t0 = time.time()
+    episodes, env_steps, updates_done = 0, 0, 0
+    log = open(os.path.join(a.out, "progress.txt"), "a")
+    N = env.N
+    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
+    prev = torch.empty_like(obs)
+    elog = DeviceEpisodeLog(obs.device, a.max_csv_rows)
+    learning = False
+    next_ckpt = a.checkpoint_every
+    step_s = (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0
+    for it in range(1, a.launches + 1):
+        act = agent.act_fused(obs)                                           # Agent.act: samples, squashes twice, clips
+        prev.copy_(obs)
+        obs, reward, done = env.step(act, auto_reset="next")
+        keep = ~resetting
+        agent.memory.add_masked(prev, act, reward, obs, done, keep)
+        resetting = done.bool()
+        elog.add(done, env.counters(), env.returns()[0], it, keep)
+        if not learning:
+            learning = agent.memory.ready(agent.batch_size)
+        if learning:
+            for u in range(a.updates):
+                updates_done += 1
+                agent.learn(updates_done)
+        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
+        if it % a.log_every == 0 or last_launch:
+            rows, tot = elog.flush()
+            ne = int(tot[0])
+            episodes += ne; env_steps += int(tot[4])
+            for r in rows.tolist():
+                seen = int(r[6])
+                stats.add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
+                          1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
+            if ne:
+                line = "launch %6d  env-steps %10d  updates %9d  episodes %8d  success %.3f  mean return %8.1f  mean steps %6.1f  %.0f s" % (
+                    it, env_steps, updates_done, episodes, tot[1] / ne, tot[2] / ne, tot[3] / ne, time.time() - t0)
+                print(line, flush=True); log.write(line + "\n"); log.flush()
+            if a.csv:
+                stats.append_csv(a.out, "sac_training", resume=resumed)
+            if episodes >= next_ckpt:
+                save_checkpoint(agent, a.out, episodes)
+                while next_ckpt <= episodes:
+                    next_ckpt += a.checkpoint_every
+            if last_launch:
+                break
+    agent.memory.sync_len()
+    save_checkpoint(agent, a.out, episodes)
+    last = stats.rows[-500:]
+    if last:
+        line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f | %d updates, %.0f updates/s, %d env-steps, %.0f s" % (
+            len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
+            updates_done, updates_done / max(1e-9, time.time() - t0), env_steps, time.time() - t0)
+        print(line, flush=True); log.write(line + "\n"); log.flush()
+    return agent, episodes
+
+
 def make_agent(a, obs_dim, device, **kw):
     """The learner of --algo with its reference defaults; --batch / --lr-actor / --lr-critic / --tau override them when given."""
     over = {k: v for k, v in (("batch_size", getattr(a, "batch", None)), ("actor_lr", getattr(a, "lr_actor", None)),
                               ("critic_lr", getattr(a, "lr_critic", None)), ("tau", getattr(a, "tau", None))) if v is not None}
     over.update(kw)
+    if getattr(a, "algo", "td3") == "sac":
+        over = {dict(critic_lr="q_lr").get(k, k): v for k, v in over.items()}
+        if "q_lr" in over:
+            over["v_lr"] = over["q_lr"]
+        return sac.Agent(obs_dim=obs_dim, device=device, seed=a.seed, n_envs=a.envs, value_net=a.sac_value_net.replace("-", "_"),
+                         soft_update=a.sac_soft_update.replace("-", "_"), deterministic=getattr(a, "sac_deterministic", False), **over)
     if getattr(a, "algo", "td3") == "ddpg":
         return ddpg.Agent(obs_dim=obs_dim, device=device, seed=a.seed, n_envs=a.envs, **over)
     return td3.Agent(obs_dim=obs_dim, device=device, seed=a.seed, **over)
@@ -409,8 +496,14 @@ def parse_args(argv=None):
     ap.add_argument("--time-limit", type=float, default=0.0, help="stop after this many seconds (checked at log time); 0 = run all launches")
     ap.add_argument("--max-steps", type=int, default=None, help="nsteps: configs/td3.yaml 1000; configs/dqn.yaml 250 (--algo dqn)")
     ap.add_argument("--updates", type=int, default=4, help="TD3 updates per launch")
-    ap.add_argument("--algo", default="td3", choices=["td3", "ddpg", "dqn"],
-                    help="td3: start_td3_training.py; ddpg: start_ddpg_training.py (crowdnav.ddpg); dqn: start_dqn_training.py (crowdnav.dqn)")
+    ap.add_argument("--algo", default="td3", choices=["td3", "ddpg", "dqn", "sac"],
+                    help="td3: start_td3_training.py; ddpg: start_ddpg_training.py (crowdnav.ddpg); dqn: start_dqn_training.py (crowdnav.dqn); "
+                         "sac: sac.py with start_sac_training.py's values at their names (crowdnav.sac)")
+    ap.add_argument("--sac-value-net", default="as-written", choices=["as-written", "intended"], help="sac: the value nets as sac.py:175-176 "
+                    "constructs them (hidden width 2, linear3 ~ U(+-hidden)) or as intended (hidden width --hidden, 3e-3)")
+    ap.add_argument("--sac-soft-update", default="as-written", choices=["as-written", "intended"], help="sac: sac.py:290 as written (V is pulled "
+                    "towards its frozen copy) or as intended (the target follows V)")
+    ap.add_argument("--sac-deterministic", action="store_true", help="sac: act with z = mean (the reference's act() always samples)")
     ap.add_argument("--epsilon", type=float, default=1.0, help="dqn: the initial exploration rate (the logged run: 1.0; dqn.yaml: 0.0)")
     ap.add_argument("--epsilon-discount", type=float, default=0.995, help="dqn: dqn.yaml epsilon_discount, applied per episode while > 0.05")
     ap.add_argument("--target-update", type=int, default=10000, help="dqn: updates between hard target copies (TRAIN_DQN:51)")
@@ -455,10 +548,10 @@ def parse_args(argv=None):
         a.out = "runs/%s" % a.algo
     if a.max_steps is None:
         a.max_steps = 250 if a.algo == "dqn" else 1000
-    if a.algo == "dqn" and a.obs_layout is None:
+    if a.algo in ("dqn", "sac") and a.obs_layout is None:
         a.obs_layout = 1
-    if a.algo == "dqn" and a.reset_mode != "next":
-        ap.error("--algo dqn collects with the next-step reset only (--reset-mode next)")
+    if a.algo in ("dqn", "sac") and a.reset_mode != "next":
+        ap.error("--algo %s collects with the next-step reset only (--reset-mode next)" % a.algo)
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     return a
@@ -470,6 +563,8 @@ def main(argv=None):
         return run_evaluation(a)
     if a.algo == "dqn":
         return train_dqn(a)
+    if a.algo == "sac":
+        return train_sac(a)
     return train(a)
 
 

@@ -427,6 +427,72 @@ typedef struct cn_dqn_act_io {
 } cn_dqn_act_io;
 int cn_dqn_act(const cn_dqn_act_io* io, int device, void* stream);
 
+/* SAC -- the reference's fourth neural learner (sac.py; start_sac_training.py cannot run: its arguments are shifted by one, so
+ * every value is taken AT ITS NAME) -- on the same GEMM kernels (crowdnav_td3.hip), float32.
+ * Networks: actor Linear(D, H) - ReLU - Linear(H, H) - ReLU - {mean_linear (H, 2), log_std_linear (H, 2)} (SAC:43-76);
+ * Q Linear(D + 2, H) - ReLU - Linear(H, H) - ReLU - Linear(H, 1) (:109-125); V and its copy V_t Linear(D, Hv) - ReLU -
+ * Linear(Hv, Hv) - ReLU - Linear(Hv, 1) with Hv = hidden_v (as the reference constructs them, :175-176, Hv = 2).
+ * One update = Agent.learn (SAC:231-290), every forward pass on the pre-update weights:
+ *   log_std clamped to [log_std_min, log_std_max]; z = eps exp(log_std) + mean with eps a unit normal -- a VALUE (Normal.sample,
+ *   not rsample: no gradient through z); t = tanh z; log_prob = sum_k [Normal.log_prob(z) - log(1 - t^2 + logp_eps)];
+ *   a_new = (sigmoid(t0) max_v, tanh(t1) max_w) (the action is squashed twice, :84-91);
+ *   q_loss = MSE(Q(s, a), r + (1 - d) gamma V_t(s2));  value_loss = MSE(V(s), Q(s, a_new) - log_prob);
+ *   policy_loss = mean(log_prob (log_prob - (Q(s, a_new) - V(s)))_detached) + mean_lambda mean(mean^2)
+ *                 + std_lambda mean(log_std^2) [clamped value] + z_lambda mean(sum z^2) [no gradient];
+ *   three Adam steps (Q, V, actor; torch.optim.Adam's formulas, moments zero at create), then the soft update:
+ *     soft_update = 0 (the reference as committed): sac.py:290 calls soft_update(V_t, V) against the signature
+ *       soft_update(local, target), so it is V that moves, V <- (1 - tau) V + tau V_t, and V_t keeps its initial value;
+ *     soft_update = 1 (what the call intends): V_t <- (1 - tau) V_t + tau V from the stepped V, folded into V's Adam step.
+ * 10 launches (11 with soft_update = 0): prep | F (actor, Q, V, V_t first layers) | F (second layers, Q / V / V_t outputs) |
+ * heads | F, F (Q on (s, a_new)) | losses and row gradients | G (three jobs) | H (Q, V) | H (actor) [| pull].  Q(s, a_new) needs the
+ * action and the action needs the actor's trunk, every loss needs Q(s, a_new), and backward is G then H: those are the data
+ * dependencies; the heads and the losses are kernels of their own rather than new branches in the GEMM kernels, which the TD3
+ * and DDPG updates share.  Enqueue-only, no host read, capturable into a hipGraph on one stream. */
+typedef struct cn_sac_actor { float *w1, *b1, *w2, *b2, *mean_w, *mean_b, *log_std_w, *log_std_b; } cn_sac_actor;
+typedef struct cn_sac_config {
+    int32_t obs_dim;         /* actor and V input width (the env's: 363 with obs_layout 1, 398 with 0); Q takes obs_dim + 2 */
+    int32_t hidden;          /* start_sac_training.py:58-67 -> 256 (actor, Q) */
+    int32_t hidden_v;        /* V / V_t hidden width: 2 as written (SAC:175-176), `hidden` as intended */
+    int32_t batch;           /* -> 64 */
+    float gamma, tau;        /* sac.yaml -> 0.99, 5e-3 */
+    float lr_actor, lr_v, lr_q, beta1, beta2, eps;   /* 3e-4 x 3; torch.optim.Adam's 0.9, 0.999, 1e-8 */
+    float max_v, max_w, log_std_min, log_std_max;    /* 0.22, 2.0, -20, 2 */
+    float mean_lambda, std_lambda, z_lambda, logp_eps;   /* 1e-3, 1e-3, 0, 1e-6 (SAC:78) */
+    int32_t soft_update;     /* 0 = as written, 1 = intended (above) */
+    int32_t reserved;
+    cn_sac_actor actor;
+    cn_td3_mlp q, v, v_t;
+    const float *replay_s, *replay_a, *replay_r, *replay_s2, *replay_d;   /* as cn_td3_config */
+    const int64_t* replay_size_dev;
+    uint64_t seed;           /* keys the replay indices and eps with the handle's update counter */
+} cn_sac_config;
+typedef struct cn_sac_s* cn_sac_handle;
+/* Limits as cn_td3_create's: obs_dim >= 1, 1 <= hidden, hidden_v, batch <= 4096.  Errors through cn_td3_last_error. */
+int cn_sac_create(const cn_sac_config* cfg, int device, cn_sac_handle* out);
+void cn_sac_destroy(cn_sac_handle h);
+/* batch NULL = sample the replay.  batch->target_noise = the unit eps [B][2] of the sample learn() USES (the second Normal.sample
+ * of the call: forward() draws one first and drops it), or NULL = drawn on the device: Box-Muller on
+ * mix64(mix64(seed ^ mix64(c ^ 0x5bd1e995)) ^ m), c = the update counter, m = the row -- cn_td3_update's draw, unscaled. */
+int cn_sac_update(cn_sac_handle h, const cn_td3_batch* batch, void* stream);
+const float* cn_sac_loss_dev(cn_sac_handle h);      /* device pointer: [3] q_loss, value_loss, policy_loss of the last update */
+/* what = 0 .. 3 as cn_td3_batch_dev; 4: eps [batch][2]; 5: a record per row [batch][12] = mean[2], clamped log_std[2], raw
+ * log_std[2], z[2], log_prob, Q(s, a_new), a_new[2]; 6: d policy_loss / d (mean[2], log_std[2]) [batch][4]; 7: d q_loss / d Q [batch];
+ * 8: d value_loss / d V [batch]. */
+const float* cn_sac_batch_dev(cn_sac_handle h, int what);
+/* Agent.act (SAC:206-229) for n rows as ONE launch: trunk on the f32 matrix cores, both heads, the clamp, z = eps std + mean
+ * (deterministic != 0: z = mean), the double squash, the clip to v in [0, max_v], w in [-max_w, max_w].  eps [n][2] or NULL = drawn
+ * from (seed, counter, row) as above with c = counter, m = row.  Writes twist [n][2]; mean, log_std (clamped), z [n][2] optional. */
+typedef struct cn_sac_act_io {
+    const float* obs; int64_t obs_ld;
+    int32_t n, obs_dim, hidden, deterministic;     /* hidden <= 480 */
+    cn_sac_actor actor;
+    float max_v, max_w, log_std_min, log_std_max;
+    const float* eps;
+    uint64_t seed, counter;
+    float *twist, *mean, *log_std, *z;
+} cn_sac_act_io;
+int cn_sac_act(const cn_sac_act_io* io, int device, void* stream);
+
 /* The collection loop's bookkeeping between Env.step and Agent.learn (start_td3_training.py:129-149) for a batch of environments,
  * without a host read: ReplayBuffer.add (td3.py:24-31) into a ring on the device, and the per-episode record TRAIN:139-149 prints
  * and utils.record_data writes.  (crowdnav.td3.DeviceReplay and crowdnav.train.DeviceEpisodeLog do the same through ~35 PyTorch
