@@ -121,7 +121,7 @@ class Agent:
     def act(self, obs, add_noise=True, eps=None, deterministic=None):
         """Agent.act (SAC:206-229) for a batch: z = eps std + mean (eps: unit normal [N, 2], default drawn), the double squash, the
         clip.  It samples whatever add_noise says, as the reference does; deterministic (default: the agent's) takes z = mean."""
-        mean, log_std, _ = self.actor(obs[:, :self.obs_dim].float())
+        mean, log_std, _ = self.actor(obs[:, :self.obs_dim].to(self.actor.linear1.weight.dtype))      # (float32 unless the actor was cast)
         if self.deterministic if deterministic is None else deterministic:
             z = mean
         else:
@@ -141,7 +141,9 @@ class Agent:
 
     def act_fused(self, obs, eps=None, deterministic=None, out=None, mean=None, log_std=None, z=None):
         """cn_sac_act: the whole of act() as one launch.  eps None = drawn on the device from (seed, call counter, row).
-        mean / log_std / z: optional [N, 2] outputs.  -> twist [N, 2]."""
+        mean / log_std / z: optional [N, 2] outputs.  -> twist [N, 2].
+        The call counter travels as a kernel argument: a captured graph of this call would replay ONE draw.  Nothing captures
+        it today; a capture must supply eps (or read the counter from device memory first)."""
         import ctypes as C
         from . import _abi
         L = _abi.lib()

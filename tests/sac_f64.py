@@ -4,10 +4,15 @@ the gradients BY FORMULA (rows()), and the whole update -- those and every weigh
 td3_f64._Pass evaluation (run()) whose perturbed runs give the error bounds (reference()).  tests/test_sac_f64_helpers.py holds
 both to torch.autograd on the reference's loss expressions.
 
+cn_sac_act's statement (act_pass / act_reference) shares run()'s head, clamp, sample and squash statements (_heads, _squash);
+act_case builds its inputs with margins on every row from make_case's own pieces; box_muller_draw states the on-device draw.
+
 Parameters are dicts {net: {name: tensor}} like tests/td3_f64.py's: actor = w1, b1, w2, b2, mean_w, mean_b, ls_w, ls_b;
 q, v, v_t = td3_f64.NAMES.  `variant` restates the update WRONGLY in one named way (the discrimination tests)."""
+import functools
 import math
 
+import numpy as np
 import torch
 
 import td3_f64 as R
@@ -104,6 +109,47 @@ def _lin(ps, h, w, b):
     return ps.mm(torch.cat([h, ones], 1), torch.cat([w, b[:, None]], 1).T)
 
 
+def _heads(ps, pa, h2, eps, cfg=CFG, deterministic=False, variant=None):
+    """Both heads, the clamp, std and the sample from the trunk's output h2, statement by statement as sac_squash computes them
+    (cn_sac_update's head kernel and cn_sac_act share it) -> mean, raw, ls, sd, inside, z, t.  The clamp classes are those of the
+    exact run.  deterministic: z = mean, no rounding.  variant: one of ACT_VARIANTS' wrong heads (the squash's are _squash's)."""
+    c = cfg
+    mw, lw, mb, lb = pa["mean_w"], pa["ls_w"], pa["mean_b"], pa["ls_b"]
+    if variant == "heads_swapped":
+        mw, lw = lw, mw
+    if variant == "no_head_bias":
+        mb, lb = torch.zeros_like(mb), torch.zeros_like(lb)
+    if variant == "second_row_of_head_is_first":
+        mw, lw = mw[[0, 0]], lw[[0, 0]]
+    mean, raw = _lin(ps, h2, mw, mb), _lin(ps, h2, lw, lb)
+    if ps.gen is None:
+        ps.masks["lo"], ps.masks["hi"] = (raw < c["ls_min"]).to(raw.dtype), (raw > c["ls_max"]).to(raw.dtype)
+        if variant == "unclamped_log_std":
+            ps.masks["lo"], ps.masks["hi"] = torch.zeros_like(raw), torch.zeros_like(raw)
+    lo, hi = ps.masks["lo"], ps.masks["hi"]
+    inside = 1 - lo - hi
+    ls = raw * inside + lo * c["ls_min"] + hi * c["ls_max"]
+    sd = ls if variant == "std_is_log_std" else ps.ew(ls.exp(), 4.0)
+    if deterministic:
+        z = mean
+    else:
+        e = eps.flip(1) if variant == "eps_swapped" else eps
+        step = ps.ew(e * sd)
+        z = ps._noise(step + mean, R.U * (step + mean).abs() * (step != 0))          # eps = 0: z = mean exactly
+    t = ps.ew(torch.tanh(z), 4.0).clamp(-1.0, 1.0)                            # tanhf never leaves [-1, 1]
+    return mean, raw, ls, sd, inside, z, t
+
+
+def _squash(ps, t, cfg=CFG, variant=None):
+    """The second squash (SAC:90-91) of t = tanh z."""
+    c = cfg
+    if variant == "single_squash":
+        return ps.ew(torch.stack([t[:, 0] * c["max_v"], t[:, 1] * c["max_w"]], 1))
+    if variant == "squashes_swapped":
+        return ps.ew(torch.stack([torch.tanh(t[:, 0]) * c["max_v"], torch.sigmoid(t[:, 1]) * c["max_w"]], 1), 4.0)
+    return ps.ew(torch.stack([torch.sigmoid(t[:, 0]) * c["max_v"], torch.tanh(t[:, 1]) * c["max_w"]], 1), 4.0)
+
+
 def run(ps, P, batch, eps, cfg=CFG, variant=None, eps_first=None):
     """One update as a td3_f64._Pass evaluation, operation by operation as sac_head_kernel / sac_loss_kernel and the GEMM jobs
     compute it (exact with _Pass(), or with every rounding perturbed: td3_f64.propagated_bounds).  -> the per-row quantities
@@ -113,26 +159,14 @@ def run(ps, P, batch, eps, cfg=CFG, variant=None, eps_first=None):
     B, c, pa = s.shape[0], cfg, P["actor"]
     z1 = _lin(ps, s, pa["w1"], pa["b1"]); m1 = ps.mask("actor.1", z1); h1 = z1 * m1
     z2 = _lin(ps, h1, pa["w2"], pa["b2"]); m2 = ps.mask("actor.2", z2); h2 = z2 * m2
-    mean, raw = _lin(ps, h2, pa["mean_w"], pa["mean_b"]), _lin(ps, h2, pa["ls_w"], pa["ls_b"])
-    if ps.gen is None:
-        ps.masks["lo"], ps.masks["hi"] = (raw < c["ls_min"]).to(raw.dtype), (raw > c["ls_max"]).to(raw.dtype)
-    lo, hi = ps.masks["lo"], ps.masks["hi"]
-    inside = 1 - lo - hi
-    ls = raw * inside + lo * c["ls_min"] + hi * c["ls_max"]
-    sd = ps.ew(ls.exp(), 4.0)
     e = eps_first if variant == "first_sample" else eps
-    step = ps.ew(e * sd)
-    z = ps._noise(step + mean, R.U * (step + mean).abs() * (step != 0))          # eps = 0: z = mean exactly
-    t = ps.ew(torch.tanh(z), 4.0).clamp(-1.0, 1.0)                            # tanhf never leaves [-1, 1]
+    mean, raw, ls, sd, inside, z, t = _heads(ps, pa, h2, e, c)
     dz, var = ps.ew(z - mean), ps.ew(sd * sd)
     om = ps.ew(ps.ew(1 - ps.ew(t * t)) + c["logp_eps"])                       # 1 - t^2 cancels: t^2's rounding lands on it absolutely
     terms = torch.stack([-ps.ew(ps.ew(dz * dz) / (2 * var), 2.0), -ps.ew(sd.log(), 4.0), torch.full_like(z, -0.5 * math.log(2 * math.pi)),
                          -ps.ew(om.log(), 4.0)], 2)
     logp = ps._noise(terms.sum((1, 2)), 8 * R.U * terms.abs().sum((1, 2)))
-    if variant == "single_squash":
-        a_new = ps.ew(torch.stack([t[:, 0] * c["max_v"], t[:, 1] * c["max_w"]], 1))
-    else:
-        a_new = ps.ew(torch.stack([torch.sigmoid(t[:, 0]) * c["max_v"], torch.tanh(t[:, 1]) * c["max_w"]], 1), 4.0)
+    a_new = _squash(ps, t, c, "single_squash" if variant == "single_squash" else None)
     xq, xn = torch.cat([s, a], 1), torch.cat([s, a_new], 1)
     fq, fv = ps.mlp(P["q"], xq, "q"), ps.mlp(P["v"], s, "v")
     q, v = fq["out"][:, 0], fv["out"][:, 0]
@@ -199,31 +233,33 @@ def clamp_margin(P, batch, chain):
     return torch.minimum((raw - CFG["ls_min"]).abs(), (raw - CFG["ls_max"]).abs()) / (chain * EPS32 * ra)
 
 
+def relu_margins_ok(p, x, chain):
+    """Both hidden layers of p on the rows x: every pre-activation farther from zero than chain EPS32 x its magnitude."""
+    u = chain * EPS32
+    z1 = x @ p["w1"].T + p["b1"]; a1 = x.abs() @ p["w1"].abs().T + p["b1"].abs()
+    h1 = torch.relu(z1)
+    z2 = h1 @ p["w2"].T + p["b2"]; a2 = a1 @ p["w2"].abs().T + p["b2"].abs()
+    return bool((z1.abs() > u * a1).all()) and bool((z2.abs() > u * a2).all())
+
+
+def actor_margins_ok(pa, s, chain, clamp_chain):
+    """margins_ok's actor part: the trunk's ReLU masks and every clamp decision of every row of s."""
+    return relu_margins_ok(pa, s, chain) and bool((clamp_margin({"actor": pa}, (s,), clamp_chain) > 1).all())
+
+
 def margins_ok(P, batch, eps, chain, clamp_chain=None):
     """No ReLU mask and no clamp decision may differ between float32 and float64: every pre-activation and every raw log_std keeps
     a distance from its threshold above the forward-error bound of its own dot product."""
     s, a, r, s2, d = batch
-    u = chain * EPS32
-    ok = True
-
-    def check(p, x):
-        nonlocal ok
-        z1 = x @ p["w1"].T + p["b1"]; a1 = x.abs() @ p["w1"].abs().T + p["b1"].abs()
-        ok = ok and bool((z1.abs() > u * a1).all())
-        h1 = torch.relu(z1)
-        z2 = h1 @ p["w2"].T + p["b2"]; a2 = a1 @ p["w2"].abs().T + p["b2"].abs()
-        ok = ok and bool((z2.abs() > u * a2).all())
-    check(P["actor"], s)
-    ok = ok and bool((clamp_margin(P, batch, clamp_chain or chain) > 1).all())
     R_ = rows(P, batch, eps)
-    check(P["q"], torch.cat([s, a], 1)); check(P["q"], torch.cat([s, R_["a_new"]], 1)); check(P["v"], s); check(P["v_t"], s2)
-    return ok
+    return actor_margins_ok(P["actor"], s, chain, clamp_chain or chain) and all(relu_margins_ok(p, x, chain) for p, x in (
+        (P["q"], torch.cat([s, a], 1)), (P["q"], torch.cat([s, R_["a_new"]], 1)), (P["v"], s), (P["v_t"], s2)))
 
 
 def establish_margins(P, batch, eps, N, which="all"):
     """Shift every hidden unit's bias (td3_f64._layer_margins), network by network in the order the rows depend on each other:
     the actor on s, Q on (s, a) and (s, a_new), V on s, V_t on s2.  Modifies P's float32 tensors in place."""
-    s, a, r, s2, d = [x.double() for x in batch]
+    s = batch[0].double()
 
     def net(name, xs, xms):
         p = P[name]
@@ -235,11 +271,60 @@ def establish_margins(P, batch, eps, N, which="all"):
         net("actor", [s], [s.abs()])
     if which == "actor":
         return
+    s, a, r, s2, d = [x.double() for x in batch]
     R_ = rows(to64(P), (s, a, r, s2, d), eps.double())
     m_act = torch.full_like(R_["a_new"], 4.0)                  # |a_new| <= 2 and its error's magnitude, generously
     net("q", [torch.cat([s, a], 1), torch.cat([s, R_["a_new"]], 1)], [torch.cat([s, a], 1).abs(), torch.cat([s.abs(), m_act], 1)])
     net("v", [s], [s.abs()])
     net("v_t", [s2], [s2.abs()])
+
+
+def plant_clamp_head(pa, s, cc):
+    """make_case's log_std head, in place on the float32 actor pa and the rows s: per output one large weight on the second-layer
+    unit with the largest spread over the rows, the bias where the two clamp edges are clearest, rows still within the bound of
+    an edge replaced by copies of rows that are not.  False (pa's head may have changed) where it cannot be built: fewer than two
+    rows, no unit with spread, or every row near an edge."""
+    B = s.shape[0]
+    p64 = {k_: v.double() for k_, v in pa.items()}
+    s64 = s.double()
+    h2 = trunk(p64, s64)[3]
+    a2 = (s64.abs() @ p64["w1"].abs().T + p64["b1"].abs()) @ p64["w2"].abs().T + p64["b2"].abs()
+    spread = h2.max(0).values - h2.min(0).values
+    units = torch.argsort(spread / a2.max(0).values, descending=True)[:2].tolist()
+    if B < 2 or float(spread[units[0]]) <= 0:
+        return False
+    for o in range(2):
+        j = units[o % len(units)]
+        if float(spread[j]) > 0:
+            pa["ls_w"][o, j] = (44.0 if o == 0 else -44.0) / float(spread[j])
+    p64 = {k_: v.double() for k_, v in pa.items()}
+    raw0 = h2 @ p64["ls_w"].T
+    ra = a2 @ p64["ls_w"].abs().T + 22.0
+    ts = torch.linspace(-12.0, -6.0, 241).double()
+    for o in range(2):           # the first of the 241 centres at which the (B // 16)-th smallest clearance is largest
+        x = (raw0[:, o] - raw0[:, o].mean())[:, None] + ts[None, :]
+        clear = torch.minimum((x - CFG["ls_min"]).abs(), (x - CFG["ls_max"]).abs()) / ra[:, o, None]
+        best_t = float(ts[clear.kthvalue(max(1, B // 16), 0).values.argmax()])
+        pa["ls_b"][o] = float(best_t - raw0[:, o].mean())
+    return replace_rows_near_an_edge(pa, s, cc)
+
+
+def replace_rows_near_an_edge(pa, s, cc):
+    """Rows of s (in place) with a raw log_std within its bound of a clamp edge become copies of rows without; False if all are."""
+    bad = ~(clamp_margin({"actor": {k_: v.double() for k_, v in pa.items()}}, (s.double(),), cc) > 1).all(1)
+    if bool(bad.all()):
+        return False
+    good = torch.nonzero(~bad).reshape(-1)
+    for n_, m in enumerate(torch.nonzero(bad).reshape(-1).tolist()):
+        s[m] = s[good[n_ % len(good)]]
+    return True
+
+
+def tame_eps(pa, s, eps):
+    """make_case's eps treatment, in place: zero where the raw log_std is below EPS0_BELOW, scaled so that |eps| std <= Z_STEP_MAX."""
+    raw = trunk({k_: v.double() for k_, v in pa.items()}, s.double())[1]
+    eps[raw < EPS0_BELOW] = 0.0
+    eps.mul_((Z_STEP_MAX / 3.0 / raw.clamp(CFG["ls_min"], CFG["ls_max"]).exp()).clamp(max=1.0).float())
 
 
 def make_case(obs_dim, hidden, hidden_v, B, seed=0):
@@ -270,40 +355,9 @@ def make_case(obs_dim, hidden, hidden_v, B, seed=0):
         eps = torch.randn((B, 2), generator=g).clamp(-3, 3)
         eps1 = torch.randn((B, 2), generator=g)
         establish_margins(P, (s, a, r, s2, d), eps, chain, which="actor")
-        pa = {k_: v.double() for k_, v in P["actor"].items()}
-        s64 = s.double()
-        h2 = trunk(pa, s64)[3]
-        a2 = (s64.abs() @ pa["w1"].abs().T + pa["b1"].abs()) @ pa["w2"].abs().T + pa["b2"].abs()
-        spread = h2.max(0).values - h2.min(0).values
-        units = torch.argsort(spread / a2.max(0).values, descending=True)[:2].tolist()
-        if B < 2 or float(spread[units[0]]) <= 0:
+        if not plant_clamp_head(P["actor"], s, cc):
             continue
-        for o in range(2):
-            j = units[o % len(units)]
-            if float(spread[j]) > 0:
-                P["actor"]["ls_w"][o, j] = (44.0 if o == 0 else -44.0) / float(spread[j])
-        pa = {k_: v.double() for k_, v in P["actor"].items()}
-        raw0 = h2 @ pa["ls_w"].T
-        ra = a2 @ pa["ls_w"].abs().T + 22.0
-        for o in range(2):
-            best, best_t = -1.0, 0.0
-            for t_ in torch.linspace(-12.0, -6.0, 241).tolist():
-                x = raw0[:, o] - raw0[:, o].mean() + t_
-                clear = torch.minimum((x - CFG["ls_min"]).abs(), (x - CFG["ls_max"]).abs()) / ra[:, o]
-                score = float(clear.kthvalue(max(1, B // 16)).values)
-                if score > best:
-                    best, best_t = score, t_
-            P["actor"]["ls_b"][o] = float(best_t - raw0[:, o].mean())
-        b64 = (s64, a.double(), r.double(), s2.double(), d.double())
-        bad = ~(clamp_margin(to64(P), b64, cc) > 1).all(1)
-        if bool(bad.all()):
-            continue
-        good = torch.nonzero(~bad).reshape(-1)
-        for n_, m in enumerate(torch.nonzero(bad).reshape(-1).tolist()):
-            s[m] = s[good[n_ % len(good)]]
-        raw = trunk(to64(P)["actor"], s.double())[1]
-        eps[raw < EPS0_BELOW] = 0.0
-        eps.mul_((Z_STEP_MAX / 3.0 / raw.clamp(CFG["ls_min"], CFG["ls_max"]).exp()).clamp(max=1.0).float())
+        tame_eps(P["actor"], s, eps)
         batch = (s, a, r, s2, d)
         establish_margins(P, batch, eps, chain, which="rest")
         P64, b64 = to64(P), tuple(x.double() for x in batch)
@@ -315,3 +369,127 @@ def make_case(obs_dim, hidden, hidden_v, B, seed=0):
             continue
         return P, batch, eps, eps1, chain
     raise RuntimeError("no case with margins for %r" % ((obs_dim, hidden, hidden_v, B),))
+
+
+# ---- cn_sac_act ---------------------------------------------------------------------------------------------------------------
+ACT_KEYS = ("mean", "log_std", "z", "twist")
+ACT_VARIANTS = ("single_squash", "squashes_swapped", "unclamped_log_std", "std_is_log_std", "eps_swapped", "heads_swapped", "no_head_bias",
+                "second_row_of_head_is_first")
+# the 16-unit tile, the 32-unit padding of hidden, the head's four lanes (units part mod 4), the LDS limit
+ACT_HIDDEN = (1, 15, 16, 17, 31, 32, 33, 300, 479, 480)
+ACT_D = (1, 3, 15, 16, 17, 127, 128, 129, 363)        # the ragged block of 16 inputs, eight blocks in flight
+ACT_N = (1, 15, 16, 17, 33)                           # rows against the 16-row workgroup
+ACT_LARGE = (32, 17, 65541)                           # (hidden, D, n): more than 4096 workgroups, a ragged last one
+ACT_DISCRIMINATE = ((32, 46, 16), (33, 45, 40), (256, 363, 64))       # (hidden, D, n)
+
+
+def act_pass(ps, actor, obs, eps, deterministic, cfg=CFG, variant=None):
+    """What sac_act_kernel computes per row (Agent.act, SAC:206-229) as a td3_f64._Pass evaluation: the trunk, _heads (both heads,
+    the clamp, exp, z = eps std + mean or z = mean, tanh), _squash, the clip to [0, max_v] x [-max_w, max_w] -- run()'s own
+    statements and roundings.  actor, obs [n, obs_dim], eps [n, 2]: float64.  -> mean, log_std (clamped), z, twist."""
+    c = cfg
+    z1 = _lin(ps, obs, actor["w1"], actor["b1"]); h1 = z1 * ps.mask("actor.1", z1)
+    z2 = _lin(ps, h1, actor["w2"], actor["b2"]); h2 = z2 * ps.mask("actor.2", z2)
+    mean, raw, ls, sd, inside, z, t = _heads(ps, actor, h2, eps, c, deterministic, variant)
+    a = _squash(ps, t, c, variant)
+    lo = torch.tensor([0.0, -c["max_w"]], dtype=a.dtype, device=a.device)
+    hi = torch.tensor([c["max_v"], c["max_w"]], dtype=a.dtype, device=a.device)
+    return dict(mean=mean, log_std=ls, z=z, twist=torch.maximum(torch.minimum(a, hi), lo))
+
+
+def act_reference(actor, obs, eps, deterministic, cfg=CFG, variant=None):
+    """(float64 values, bounds) of act_pass: td3_f64.propagated_bounds.  A clamped log_std has bound zero."""
+    return R.propagated_bounds(lambda ps: act_pass(ps, actor, obs, eps, deterministic, cfg, variant))
+
+
+def act_classes(actor, obs):
+    """(below, inside, above): which raw log_std elements the float64 actor clamps at log_std_min, leaves, clamps at log_std_max."""
+    raw = trunk({k: v.double() for k, v in actor.items()}, obs.double())[1]
+    return raw < CFG["ls_min"], (raw >= CFG["ls_min"]) & (raw <= CFG["ls_max"]), raw > CFG["ls_max"]
+
+
+def act_promises_classes(hidden, n):
+    return hidden >= 15 and n >= 15
+
+
+@functools.lru_cache(maxsize=None)
+def _act_case(hidden, obs_dim, n, seed):
+    cc = clamp_chain(obs_dim, hidden)          # >= the roundings on the way to any pre-activation of the trunk as well
+    need = act_promises_classes(hidden, n)
+    for k in range(60):
+        g = torch.Generator().manual_seed(1000 * seed + k + 31 * hidden + 977 * obs_dim + 7919 * n)
+        pa = new_params(obs_dim, hidden, 1, g)["actor"]
+        s = torch.randn((n, obs_dim), generator=g) * 0.5
+        eps = torch.randn((n, 2), generator=g).clamp(-3, 3)
+        establish_margins({"actor": pa}, (s,), None, cc, which="actor")
+        plain = {k_: pa[k_].clone() for k_ in ("ls_w", "ls_b")}
+        if not plant_clamp_head(pa, s, cc):
+            # one row, or a trunk whose output is the same on every row: the nn.Linear-like head as drawn, far inside the clamp
+            pa.update(plain)
+            if need or not replace_rows_near_an_edge(pa, s, cc):
+                continue
+        if (hidden + obs_dim + n) % 2:       # plant_clamp_head's output 0 reaches the upper edge alone, output 1 the lower: every
+            pa["ls_w"], pa["ls_b"] = pa["ls_w"][[1, 0]].contiguous(), pa["ls_b"][[1, 0]].contiguous()      # other case the other way
+        tame_eps(pa, s, eps)
+        below, inside, above = act_classes(pa, s)
+        if need and not (bool(below.any()) and bool(inside.any()) and bool(above.any())):
+            continue
+        if not actor_margins_ok({k_: v.double() for k_, v in pa.items()}, s.double(), cc, cc):
+            continue
+        return pa, s, eps
+    raise RuntimeError("no act case with margins for %r" % ((hidden, obs_dim, n),))
+
+
+def act_case(hidden, obs_dim, ld, n, seed=0):
+    """cn_sac_act's inputs: actor parameters (float32 values), obs [n, ld] with NaN in columns obs_dim .. ld - 1 (the same values
+    whatever ld) and eps [n, 2], such that actor_margins_ok holds at clamp_chain(obs_dim, hidden) for EVERY row: no ReLU mask
+    and no clamp decision differs between float32 and float64.  Built as make_case builds its actor: establish_margins on the
+    trunk, plant_clamp_head, tame_eps.  hidden >= 15 and n >= 15: elements clamped at -20, clamped at 2 and inside all occur.
+    Smaller: the same head where it can be built, else (one row, or no second-layer unit that differs between the rows) the
+    nn.Linear-like head as drawn, which stays inside the clamp; margins in either case."""
+    pa, s, eps = _act_case(hidden, obs_dim, n, seed)
+    obs = torch.full((n, ld), float("nan"))
+    obs[:, :obs_dim] = s
+    return {k: v.clone() for k, v in pa.items()}, obs, eps.clone()
+
+
+# ---- the draw -----------------------------------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x):
+    """cn_mix64 (csrc/crowdnav_device.h): splitmix64's increment, then its finaliser.  A Python int -> a Python int; anything else
+    as a numpy uint64 array, wrapping as the device's 64-bit integers do."""
+    scalar = isinstance(x, int)
+    z = np.asarray([x & _M64] if scalar else x, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
+    z = z ^ (z >> np.uint64(31))
+    return int(z[0]) if scalar else z
+
+
+def draw_hash(seed, counter, rows):
+    """h = mix64(mix64(seed ^ mix64(counter ^ 0x5bd1e995)) ^ (uint32) row): the key of td3_prep_kernel's and sac_act_kernel's eps."""
+    base = _mix64((int(seed) & _M64) ^ _mix64((int(counter) & _M64) ^ 0x5bd1e995))
+    return _mix64(np.uint64(base) ^ (np.asarray(rows, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)))
+
+
+def uniforms(h):
+    """(u1, u2) of a hash, the float32 values the kernels compute: u1 = (k + 1) 2^-24 over k = h >> 40, in (0, 1] (the literal
+    1.0f / 16777217.0f is 2^-24: 16777217.0f rounds to 16777216; u1 = 1 at k = 2^24 - 1 alone, where eps = 0),
+    u2 = k' 2^-24 over k' = (h >> 8) & 0xffffff, in [0, 1)."""
+    h = np.asarray(h, dtype=np.uint64)
+    u1 = ((h >> np.uint64(40)).astype(np.float32) + np.float32(1)) * (np.float32(1) / np.float32(16777217.0))
+    u2 = ((h >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(np.float32) * (np.float32(1) / np.float32(16777216.0))
+    return u1, u2
+
+
+def box_muller_draw(seed, counter, rows):
+    """The documented draw of row `rows` of call `counter`: eps = (r cos a, r sin a), r = sqrt(-2 ln u1), a = fl32(6.28318530718f u2)
+    -- the angle as the kernel rounds it, everything else in float64.  -> float64 [len(rows), 2]."""
+    u1, u2 = uniforms(draw_hash(seed, counter, rows))
+    r = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
+    a = (np.float32(6.28318530718) * u2).astype(np.float64)
+    return np.stack([r * np.cos(a), r * np.sin(a)], 1)

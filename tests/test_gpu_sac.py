@@ -332,12 +332,7 @@ def test_two_handles_on_identical_parameters_end_bit_identical():
         a.close(); b.close()
 
 
-def _mix64(x):
-    M = (1 << 64) - 1
-    x = (x + 0x9E3779B97F4A7C15) & M          # cn_mix64 (csrc/crowdnav_device.h): splitmix64's increment, then its finaliser
-    x ^= x >> 30; x = (x * 0xbf58476d1ce4e5b9) & M
-    x ^= x >> 27; x = (x * 0x94d049bb133111eb) & M
-    return x ^ (x >> 31)
+_mix64 = S._mix64          # cn_mix64: stated once, in tests/sac_f64.py
 
 
 def test_replay_path_samples_only_live_rows_and_its_eps_is_the_documented_draw():
@@ -416,7 +411,8 @@ def test_graph_capture_of_the_update_replays_bit_for_bit():
 
 @pytest.mark.parametrize("n", [1, 16, 4096])
 def test_cn_sac_act_matches_float64(n):
-    """Supplied eps and deterministic, a row stride larger than obs_dim; drawn eps: mean and variance of 2n unit normals within
+    """Supplied eps and deterministic, a row stride larger than obs_dim (mean, log_std, z and the twist; the tile edges, the clamp
+    and the documented draw: tests/test_gpu_sac_act_f64.py); drawn eps: mean and variance of 2n unit normals within
     5 standard errors (|mean| <= 5 / sqrt(2n), |var - 1| <= 5 sqrt(2 / (2n)))."""
     from crowdnav.sac import Agent
     ag = Agent(obs_dim=363, hidden=256, device="cuda:0", seed=5, memory_size=16)
@@ -446,6 +442,10 @@ def test_cn_sac_act_matches_float64(n):
         e_z = e_mean + (0 if det else eps.double().cpu().abs() * ls.exp() * (e_raw + 8 * S.EPS32)) + 8 * S.EPS32 * (z.abs() + 1)
         assert bool(((m_.cpu().double() - mean).abs() <= e_mean).all())
         assert bool(((z_.cpu().double() - z).abs() <= e_z).all())
+        # the clamp is 1-Lipschitz: every element within e_raw; exactly the edge where float64 is past it by more than e_raw
+        ld = l_.cpu().double()
+        assert bool(((ld - ls).abs() <= e_raw).all())
+        assert bool((ld[raw < -20 - e_raw] == -20.0).all()) and bool((ld[raw > 2 + e_raw] == 2.0).all())
         assert bool(((got.cpu().double() - want).abs() <= 2.0 * e_z + 8 * S.EPS32).all())
         np.testing.assert_allclose(got.cpu().numpy(), ag.act(obs, eps=eps, deterministic=det).cpu().numpy(), rtol=0, atol=float(2 * e_z.max() + 1e-6))
     if n == 4096:

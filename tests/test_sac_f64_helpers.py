@@ -1,6 +1,8 @@
-"""tests/sac_f64.py against torch.autograd in float64 on the reference's loss expressions (sac.py:253-272).  CPU only."""
+"""tests/sac_f64.py against torch.autograd in float64 on the reference's loss expressions (sac.py:253-272), its statement of
+cn_sac_act against crowdnav.sac.Agent.act in float64, and the promises of act_case and box_muller_draw.  CPU only."""
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -113,3 +115,120 @@ def test_every_wrong_variant_differs_by_more_than_the_bounds():
         assert worst > 1.0, (var, worst)
     assert all(bool(torch.isfinite(v).all()) for v in Bd.values())
     assert math.isfinite(float(want["loss"].sum()))
+
+
+# ---- cn_sac_act's statement ---------------------------------------------------------------------------------------------------
+def _agent64(pa, obs_dim, hidden):
+    """crowdnav.sac.Agent on the CPU with its actor in float64 holding pa."""
+    from crowdnav.sac import Agent
+    ag = Agent(obs_dim=obs_dim, hidden=hidden, device="cpu", memory_size=4)
+    ag.actor.double()
+    a = ag.actor
+    with torch.no_grad():
+        for k, t in zip(S.ACTOR_NAMES, (a.linear1.weight, a.linear1.bias, a.linear2.weight, a.linear2.bias, a.mean_linear.weight,
+                                        a.mean_linear.bias, a.log_std_linear.weight, a.log_std_linear.bias)):
+            t.copy_(pa[k].double())
+    return ag
+
+
+@pytest.mark.parametrize("shape", [(17, 20, 24), (33, 13, 40), (1, 3, 5)], ids=lambda s: "x".join(map(str, s)))
+def test_act_pass_equals_agent_act_in_float64(shape):
+    """act_pass with the exact _Pass() against Agent.act (actor.double()), sampled with supplied eps and deterministic: the twist
+    to 1e-12, and mean / log_std / z against the actor's own forward."""
+    H, D, n = shape
+    pa, obs, eps = S.act_case(H, D, D + 3, n)
+    ag = _agent64(pa, D, H)
+    p64 = {k: v.double() for k, v in pa.items()}
+    x, e = obs[:, :D].double(), eps.double()
+    mean, ls, _ = ag.actor(x)
+    for det in (False, True):
+        got = S.act_pass(R._Pass(), p64, x, e, det)
+        want = ag.act(obs.double(), eps=e, deterministic=det)
+        assert want.dtype == torch.float64
+        torch.testing.assert_close(got["twist"], want, rtol=0, atol=1e-12)
+        torch.testing.assert_close(got["mean"], mean.detach(), rtol=0, atol=1e-12)
+        torch.testing.assert_close(got["log_std"], ls.detach(), rtol=0, atol=1e-12)
+        torch.testing.assert_close(got["z"], (mean if det else e * ls.exp() + mean).detach(), rtol=0, atol=1e-12)
+        assert torch.equal(got["z"], got["mean"]) == det
+
+
+def _check_case(H, D, n):
+    pa, obs, eps = S.act_case(H, D, D + 3, n)
+    assert obs.shape == (n, D + 3) and eps.shape == (n, 2) and bool(torch.isnan(obs[:, D:]).all()) and bool(torch.isfinite(obs[:, :D]).all())
+    assert all(v.dtype == torch.float32 for v in pa.values()) and obs.dtype == torch.float32 and eps.dtype == torch.float32
+    p64, x = {k: v.double() for k, v in pa.items()}, obs[:, :D].double()
+    cc = S.clamp_chain(D, H)
+    assert S.actor_margins_ok(p64, x, cc, cc), (H, D, n)                                   # every row: ReLU masks and clamp decisions
+    assert float(S.clamp_margin({"actor": p64}, (x,), cc).min()) > 1.0, (H, D, n)
+    below, inside, above = S.act_classes(pa, x)
+    if S.act_promises_classes(H, n):
+        assert bool(below.any()) and bool(inside.any()) and bool(above.any()), (H, D, n)
+    raw = S.trunk(p64, x)[1]
+    assert bool((eps[raw < S.EPS0_BELOW] == 0).all())
+    assert bool(((eps.double() * raw.clamp(-20, 2).exp()).abs() <= S.Z_STEP_MAX * (1 + 1e-6)).all())
+    again = S.act_case(H, D, D, n)
+    assert torch.equal(again[1], obs[:, :D]) and torch.equal(again[2], eps) and all(torch.equal(again[0][k], pa[k]) for k in pa)
+    return bool(below.any()), bool(above.any())
+
+
+@pytest.mark.parametrize("H", S.ACT_HIDDEN)
+def test_act_case_keeps_its_promises_at_every_shape_the_gpu_tests_use(H):
+    """Margins on every row of every (hidden, D, n); the three clamp classes where hidden >= 15 and n >= 15; the same values
+    whatever ld; eps zero below EPS0_BELOW and |eps| std <= Z_STEP_MAX."""
+    for D in S.ACT_D:
+        for n in S.ACT_N:
+            _check_case(H, D, n)
+
+
+def test_act_case_at_the_large_and_the_discrimination_shapes():
+    for H, D, n in (S.ACT_LARGE,) + S.ACT_DISCRIMINATE:
+        assert _check_case(H, D, n) == (True, True), (H, D, n)
+
+
+@pytest.mark.parametrize("shape", S.ACT_DISCRIMINATE, ids=lambda s: "x".join(map(str, s)))
+def test_every_wrong_act_variant_differs_by_more_than_twice_the_bound(shape):
+    """Each ACT_VARIANTS entry, on the sampled path, moves some element of twist, z or log_std by more than twice the exact
+    statement's propagated bound (the device may sit a bound away from float64 and must still be told apart), and the bounds hold
+    the same pass evaluated in float32 on the CPU."""
+    H, D, n = shape
+    pa, obs, eps = S.act_case(H, D, D, n)
+    p64, x, e = {k: v.double() for k, v in pa.items()}, obs.double(), eps.double()
+    want, Bd = S.act_reference(p64, x, e, False)
+    assert all(bool(torch.isfinite(v).all()) for v in Bd.values())
+    for det in (False, True):
+        w_, b_ = (want, Bd) if not det else S.act_reference(p64, x, e, True)
+        f32 = S.act_pass(R._Pass(), pa, obs, eps, det)
+        for k in S.ACT_KEYS:
+            assert R.worst_ratio(f32[k], w_[k], b_[k]) <= 1.0, (k, det)
+    for var in S.ACT_VARIANTS:
+        wrong = S.act_pass(R._Pass(), p64, x, e, False, variant=var)
+        worst = max(R.worst_ratio(wrong[k], want[k], 2 * Bd[k]) for k in ("twist", "z", "log_std"))
+        assert worst > 1.0, (var, worst)
+
+
+def test_mix64_is_splitmix64_and_the_same_on_ints_and_arrays():
+    """splitmix64's first outputs from state 0 (Vigna's reference implementation) are mix64(0), mix64(0x9E3779B97F4A7C15), ..."""
+    assert S._mix64(0) == 0xE220A8397B1DCDAF and S._mix64(0x9E3779B97F4A7C15) == 0x6E789E6AA1B965F4
+    xs = [0, 1, 7, (1 << 63) + 5, (1 << 64) - 1]
+    assert S._mix64(np.array(xs, dtype=np.uint64)).tolist() == [S._mix64(x) for x in xs]
+
+
+def test_box_muller_draw_keeps_what_the_device_draw_promises():
+    """Over 2^20 rows: every u1 in (0, 1), u2 in [0, 1), every value finite, mean and variance those of unit normals within 5
+    standard errors; rows and counters give different values.  The edges of the 24-bit integers: u1's smallest value is 2^-24
+    (r = 5.77), its largest -- at k = 2^24 - 1 alone, one hash in 2^24 -- is exactly 1, where r = 0 and eps = (0, 0): finite."""
+    rows = np.arange(1 << 20)
+    u1, u2 = S.uniforms(S.draw_hash(7, 3, rows))
+    assert u1.dtype == np.float32 and bool((u1 > 0).all()) and bool((u1 < 1).all()) and bool((u2 >= 0).all()) and bool((u2 < 1).all())
+    e = S.box_muller_draw(7, 3, rows)
+    assert e.shape == (1 << 20, 2) and bool(np.isfinite(e).all())
+    k = e.size
+    assert abs(float(e.mean())) <= 5 / math.sqrt(k) and abs(float(e.var()) - 1) <= 5 * math.sqrt(2.0 / k)
+    assert len(np.unique(e.view(np.int64)[:, 0])) == 1 << 20
+    assert not np.array_equal(e[:64], S.box_muller_draw(7, 4, rows[:64])) and not np.array_equal(e[:64], S.box_muller_draw(8, 3, rows[:64]))
+    assert np.array_equal(S.box_muller_draw(7 + (1 << 64), 3, rows[:64]), e[:64])          # seed and counter are 64-bit
+    edge = np.array([0, (1 << 64) - 1, ((1 << 24) - 1) << 40], dtype=np.uint64)
+    eu1, eu2 = S.uniforms(edge)
+    assert eu1.tolist() == [2.0 ** -24, 1.0, 1.0] and eu2.tolist() == [0.0, 1 - 2.0 ** -24, 0.0]
+    h = S.draw_hash(0xD1B54A32D192ED03, (1 << 63) + 5, [0, 1, 4098])
+    assert h.tolist() == [S._mix64(S._mix64(0xD1B54A32D192ED03 ^ S._mix64(((1 << 63) + 5) ^ 0x5bd1e995)) ^ m) for m in (0, 1, 4098)]
