@@ -8,7 +8,12 @@ cn_sac_act's statement (act_pass / act_reference) shares run()'s head, clamp, sa
 act_case builds its inputs with margins on every row from make_case's own pieces; box_muller_draw states the on-device draw.
 
 Parameters are dicts {net: {name: tensor}} like tests/td3_f64.py's: actor = w1, b1, w2, b2, mean_w, mean_b, ls_w, ls_b;
-q, v, v_t = td3_f64.NAMES.  `variant` restates the update WRONGLY in one named way (the discrimination tests)."""
+q, v, v_t = td3_f64.NAMES.  `variant` restates the update WRONGLY in one named way (the discrimination tests).
+
+The series (series_step, series_run): four updates with Adam's moments, the shared step count and V's soft update carried in
+float64 beside a learner -- the device handle, or EmulatedLearner's float32 formula on the CPU -- whose weights are read back
+before and after every update; SERIES_VARIANTS restate the series wrongly, one way at a time."""
+import copy
 import functools
 import math
 
@@ -234,12 +239,14 @@ def clamp_margin(P, batch, chain):
 
 
 def relu_margins_ok(p, x, chain):
-    """Both hidden layers of p on the rows x: every pre-activation farther from zero than chain EPS32 x its magnitude."""
+    """Both hidden layers of p on the rows x: every pre-activation farther from zero than chain EPS32 x its magnitude -- but for a
+    planted dead unit (zero weight row, zero bias: td3_f64.plant_dead_units), whose pre-activation is exactly 0 in any order."""
     u = chain * EPS32
     z1 = x @ p["w1"].T + p["b1"]; a1 = x.abs() @ p["w1"].abs().T + p["b1"].abs()
     h1 = torch.relu(z1)
     z2 = h1 @ p["w2"].T + p["b2"]; a2 = a1 @ p["w2"].abs().T + p["b2"].abs()
-    return bool((z1.abs() > u * a1).all()) and bool((z2.abs() > u * a2).all())
+    d1, d2 = R._is_dead(p["w1"], p["b1"]), R._is_dead(p["w2"], p["b2"])
+    return bool(((z1.abs() > u * a1) | d1).all()) and bool(((z2.abs() > u * a2) | d2).all())
 
 
 def actor_margins_ok(pa, s, chain, clamp_chain):
@@ -493,3 +500,268 @@ def box_muller_draw(seed, counter, rows):
     r = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
     a = (np.float32(6.28318530718) * u2).astype(np.float64)
     return np.stack([r * np.cos(a), r * np.sin(a)], 1)
+
+
+# ---- Adam across updates ------------------------------------------------------------------------------------------------------
+SERIES_VARIANTS = ("frozen_bias_correction", "moments_not_carried", "betas_exchanged", "head_moments_exchanged", "one_lr",
+                   "target_from_pre_step_v", "pull_before_adam", "pull_not_seen_by_moments")
+# variant -> (the soft_update modes it exists in, the first update (from 0) at which it can differ, the networks it concerns: it
+# must be rejected on at least one tensor of EACH)
+SERIES_RULES = dict(frozen_bias_correction=((0, 1), 1, ("q", "v", "actor")), moments_not_carried=((0, 1), 1, ("q", "v", "actor")),
+                    betas_exchanged=((0, 1), 1, ("q", "v", "actor")), head_moments_exchanged=((0, 1), 1, ("heads",)),
+                    one_lr=((0, 1), 0, ("v", "actor")), target_from_pre_step_v=((1,), 0, ("v_t",)), pull_before_adam=((0,), 0, ("v",)),
+                    pull_not_seen_by_moments=((0,), 1, ("v",)))
+HEADS = ("mean_w", "mean_b", "ls_w", "ls_b")
+SERIES_SHAPES = ((46, 32, 2, 16), (45, 33, 3, 40), (45, 24, 17, 40))       # (obs_dim, hidden, hidden_v, batch); both soft_update modes
+SERIES_PRODUCT = (363, 256, 2, 64)                                         # once
+F32 = lambda x: float(np.float32(x))
+# carried moments weigh most at 0.5 / 0.75; the product's 0.9 / 0.999 AS THE CONFIG'S FLOAT32 FIELDS HOLD THEM (the kernel's
+# 1 - beta and its tick's beta^t both start from that float32 value): the bias corrections are x10 and x1000 at t = 1
+SERIES_BETAS = ((0.5, 0.75), (F32(0.9), F32(0.999)))
+SERIES_TAU = 2.0 ** -4
+SERIES_LR = 2.0 ** -7            # the largest step of an element of any network, about: each lr is this x eps / (2 top |g| of its net)
+SERIES_UPDATES = 4
+NET_NAMES = (("q", NAMES), ("v", NAMES), ("actor", ACTOR_NAMES))
+# (shape, betas, soft_update, clamp_all): what the GPU series tests run and the CPU power test runs first.  The product shape once,
+# as the product is configured (soft_update 0); one case with log_std output 1 clamped on every row (its head rows' exact zeros)
+SERIES_CASES = tuple((s_, b_, m_, False) for s_ in SERIES_SHAPES for b_ in SERIES_BETAS for m_ in (0, 1)) + (
+    (SERIES_PRODUCT, SERIES_BETAS[1], 0, False), (SERIES_SHAPES[1], SERIES_BETAS[1], 1, True))
+
+
+def series_id(case):
+    shape, betas, mode, clamp_all = case
+    return "%s-b%g-soft%d%s" % ("x".join(map(str, shape)), round(betas[0], 3), mode, "-clamped" if clamp_all else "")
+
+
+def _pow2_at_least(x):
+    return 2.0 ** math.ceil(math.log2(max(x, 2.0 ** -60)))
+
+
+def series_hp(want, betas, soft_update, tau=SERIES_TAU):
+    """The hyper-parameters of a series from the first update's float64 gradients `want`: eps = a power of two >= twice the
+    largest gradient element; each optimiser's lr = SERIES_LR x (the largest network's top |g|) / (its own), powers of two,
+    a later one doubled until the three differ (one_lr must show on V and on the actor)."""
+    top = {n: _pow2_at_least(max(float(want[k].abs().max()) for k in GRADS if k[0] == n)) for n in ("q", "v", "actor")}
+    e_ = max(top.values())
+    lr, seen = {}, set()
+    for n in ("q", "v", "actor"):
+        x = SERIES_LR * e_ / top[n]
+        while x in seen:
+            x *= 2.0
+        seen.add(x)
+        lr[n] = x
+    return dict(lr_q=lr["q"], lr_v=lr["v"], lr_actor=lr["actor"], beta1=betas[0], beta2=betas[1], eps=2.0 * e_, tau=tau, soft_update=soft_update)
+
+
+def series_state(hp):
+    """What a series carries from update to update: the shared step count, three td3_f64.Adam64 (Q, V, actor: each its own lr and
+    moments), the running element-wise maximum of the gradient bounds, and (pull_not_seen_by_moments) V's last un-pulled step."""
+    mk = lambda lr: R.Adam64(lr, hp["beta1"], hp["beta2"], hp["eps"])
+    return dict(t=0, opt=dict(q=mk(hp["lr_q"]), v=mk(hp["lr_v"]), actor=mk(hp["lr_actor"])), gerr={}, unpulled=None)
+
+
+def series_step(state, P_pre, batch, eps, cfg, hp, variant=None, ref=None):
+    """One update of the series.  P_pre: the pre-update weights in float64 (as read back from the learner); ref: reference()'s
+    (gradients, bounds) at P_pre (computed here if None).  Advances `state` and returns (predicted post-update tensors, bounds),
+    both {net: {name: tensor}} over q, v, v_t and actor.
+
+    Q and the actor: Adam64's step at td3_f64.adam_step_bound, gerr the running maximum of the gradient bounds so far.
+    soft_update 1: V the same, V_t = soft_update(V_t, V', tau) at soft_bound + tau x V's step bound.
+    soft_update 0: V = soft_update(V', V_t, tau) at (1 - tau) x V's step bound + soft_bound; V_t keeps every bit (bound 0).
+    variant: one of SERIES_VARIANTS."""
+    if ref is None:
+        ref = reference(P_pre, batch, eps, cfg)
+    want, Bd = ref
+    tau, mode = hp["tau"], hp["soft_update"]
+    if variant == "pull_not_seen_by_moments" and state["unpulled"] is not None:       # the gradients at V as it was before the last pull
+        alt = dict(P_pre, v={k: P_pre["v"][k] + state["unpulled"][k] for k in NAMES})
+        want = run(R._Pass(), alt, batch, eps, cfg)
+    state["t"] += 1
+    pred, bound = {}, {}
+    for net, names in NET_NAMES:
+        o = state["opt"][net]
+        o.t = state["t"]
+        o.lr = hp["lr_q"] if variant == "one_lr" else hp["lr_" + net]
+        o.b1, o.b2 = (hp["beta2"], hp["beta1"]) if variant == "betas_exchanged" else (hp["beta1"], hp["beta2"])
+        if variant == "moments_not_carried":
+            o.m.clear(); o.v.clear()
+        if variant == "head_moments_exchanged" and net == "actor":
+            for a_, b_ in (("mean_w", "ls_w"), ("mean_b", "ls_b")):
+                for mom in (o.m, o.v):
+                    if a_ in mom:
+                        mom[a_], mom[b_] = mom[b_], mom[a_]
+        pred[net], bound[net] = {}, {}
+        for k in names:
+            ge = state["gerr"][(net, k)] = torch.maximum(state["gerr"].get((net, k), torch.zeros_like(Bd[(net, k)])), Bd[(net, k)])
+            w0 = P_pre[net][k]
+            if net == "v" and variant == "pull_before_adam":
+                w0 = R.soft_update(w0, P_pre["v_t"][k], tau)
+            w1, ratio = o.step(k, w0, want[(net, k)], t=1 if variant == "frozen_bias_correction" else None)
+            pred[net][k], bound[net][k] = w1, R.adam_step_bound(w1, ratio, o.lr, hp["eps"], ge)
+    pred["v_t"], bound["v_t"] = {}, {}
+    unpulled = {}
+    for k in NAMES:
+        v1, sb, t0 = pred["v"][k], bound["v"][k], P_pre["v_t"][k]
+        if mode == 1:
+            src = P_pre["v"][k] if variant == "target_from_pre_step_v" else v1
+            pred["v_t"][k], bound["v_t"][k] = R.soft_update(t0, src, tau), R.soft_bound(t0, src, tau) + tau * sb
+        else:
+            pred["v_t"][k], bound["v_t"][k] = t0, torch.zeros_like(t0)
+            if variant != "pull_before_adam":
+                pred["v"][k], bound["v"][k] = R.soft_update(v1, t0, tau), (1 - tau) * sb + R.soft_bound(v1, t0, tau)
+            unpulled[k] = v1 - pred["v"][k]
+    state["unpulled"] = unpulled if mode == 0 else None
+    return pred, bound
+
+
+def series_ratios(got, pred, bound):
+    """{(net, name): worst |got - pred| / bound}"""
+    return {(n, k): R.worst_ratio(got[n][k], pred[n][k], bound[n][k]) for n in pred for k in pred[n]}
+
+
+def _net_worst(ratios, net):
+    if net == "heads":
+        return max(ratios[("actor", k)] for k in HEADS)
+    return max(v for (n, _), v in ratios.items() if n == net)
+
+
+class EmulatedLearner:
+    """The stand-in for the device handle in the CPU checks: float64 gradients rounded to float32 into td3_f64.adam_f32_emulation
+    (the kernel's formula in float32) with carried moments and one step count, V's soft update in float32."""
+
+    def __init__(self, P, shape, hp):
+        self.P = {n: {k: v.detach().clone().float() for k, v in p.items()} for n, p in P.items()}
+        self.hp, self.t, self.mom = hp, 0, {}
+
+    def read(self):
+        return {n: {k: v.clone() for k, v in p.items()} for n, p in self.P.items()}
+
+    def write(self, P):
+        for n in P:
+            for k in P[n]:
+                self.P[n][k].copy_(P[n][k])
+
+    def update(self, batch, eps):
+        hp, f = self.hp, np.float32
+        g = run(R._Pass(), to64(self.P), tuple(x.double() for x in batch), eps.double())
+        self.t += 1
+        for net, names in NET_NAMES:
+            for k in names:
+                m0, v0 = self.mom.get((net, k), (None, None))
+                w1, m, v = R.adam_f32_emulation(self.P[net][k].numpy(), g[(net, k)].float().numpy(), hp["lr_" + net], hp["eps"], hp["beta1"], hp["beta2"],
+                                                m0, v0, self.t)
+                self.mom[(net, k)] = (m, v)
+                self.P[net][k] = torch.from_numpy(w1)
+        tau = f(hp["tau"])
+        moved, toward = ("v_t", "v") if hp["soft_update"] == 1 else ("v", "v_t")
+        for k in NAMES:
+            self.P[moved][k] = torch.from_numpy((self.P[moved][k].numpy() * (f(1) - tau) + self.P[toward][k].numpy() * tau).astype(f))
+
+    def close(self):
+        pass
+
+
+def series_case(shape, clamp_all=False):
+    """make_case plus a planted dead unit in each hidden layer of Q (td3_f64.plant_dead_units) and, with clamp_all, log_std output 1
+    pushed 60 below on every row: clamped at log_std_min everywhere.  -> P, batch (a list: its s is edited in place between
+    updates), eps, chain, clamp chain, the dead units."""
+    P, batch, eps, _, chain = make_case(*shape)
+    cc = clamp_chain(shape[0], shape[1])
+    dead = R.plant_dead_units(P, shape[1], nets=("q",))
+    if clamp_all:
+        P["actor"]["ls_b"][1] -= 60.0
+        assert replace_rows_near_an_edge(P["actor"], batch[0], cc)
+        tame_eps(P["actor"], batch[0], eps)
+    establish_margins(P, batch, eps, chain, which="rest")
+    return P, list(batch), eps, chain, cc, dead
+
+
+def _replant(P, batch, eps, chain, cc):
+    """Before every update after the first, on the weights as they now stand (float32, in place): the actor's ReLU margins, rows
+    near a clamp edge replaced, eps tamed, then the margins of Q, V and V_t on the rows that follow from those."""
+    establish_margins(P, batch, eps, chain, which="actor")
+    assert replace_rows_near_an_edge(P["actor"], batch[0], cc), "every row near a clamp edge"
+    tame_eps(P["actor"], batch[0], eps)
+    establish_margins(P, batch, eps, chain, which="rest")
+
+
+def _dead_slices(p, dead):
+    u1, u2 = dead
+    return [p["w1"][u1], p["b1"][u1], p["w2"][:, u1], p["w2"][u2], p["b2"][u2], p["w3"][:, u2]]
+
+
+def series_run(make_learner, shape, betas, soft_update, reference_fn=None, clamp_all=False, log=print):
+    """SERIES_UPDATES updates of `make_learner(P, shape, hp)` (read() / write(P) float32 CPU dicts, update(batch, eps), close())
+    beside the float64 series, a fresh eps per update, margins re-planted before every update after the first; then a NEW learner
+    on the stepped parameters for one more update (fresh state at create).  Asserts, per update: margins_ok; eps >= every gradient
+    element; every tensor of Q, V, V_t and the actor within the series' bound; every wrong variant of SERIES_RULES rejected on each
+    network it concerns from the update at which it can differ; the planted zeros bit for bit.  -> dict(worst={net: ratio},
+    rejected={variant: smallest rejecting ratio})."""
+    ref_fn = reference_fn or (lambda P_, b_, e_: reference(to64(P_), tuple(x.double() for x in b_), e_.double()))
+    tag = "%s betas %.3g/%.4g soft_update %d%s" % ("x".join(map(str, shape)), betas[0], betas[1], soft_update, " clamp_all" if clamp_all else "")
+    P, batch, eps, chain, cc, dead = series_case(shape, clamp_all)
+    ref = ref_fn(P, batch, eps)
+    hp = series_hp(ref[0], betas, soft_update)
+    assert len({hp["lr_q"], hp["lr_v"], hp["lr_actor"]}) == 3
+    log("%s: lr q %g v %g actor %g, eps %g" % (tag, hp["lr_q"], hp["lr_v"], hp["lr_actor"], hp["eps"]))
+    variants = [v for v in SERIES_VARIANTS if soft_update in SERIES_RULES[v][0]]
+    right, wrong = series_state(hp), {v: series_state(hp) for v in variants}
+    worst, rejected = {}, {}
+    gen = torch.Generator().manual_seed(4242 + shape[1] + shape[3])
+    vt0 = {k: v.clone() for k, v in P["v_t"].items()}
+    zeros0 = None
+    be = make_learner(P, shape, hp)
+    try:
+        for u in range(SERIES_UPDATES + 1):
+            if u == SERIES_UPDATES:                            # fresh state at create: a new learner on the stepped parameters
+                stepped = be.read()
+                be.close()
+                be = make_learner(stepped, shape, hp)
+            cur = be.read()
+            if u:
+                eps = torch.randn(eps.shape, generator=gen).clamp(-3, 3)
+                _replant(cur, batch, eps, chain, cc)
+                be.write(cur)
+                ref = ref_fn(cur, batch, eps)
+            P64, b64, e64 = to64(cur), tuple(x.double() for x in batch), eps.double()
+            assert margins_ok(P64, b64, e64, chain, cc), (tag, u, "margins")
+            top = max(float(ref[0][k].abs().max()) for k in GRADS)
+            assert top <= hp["eps"], (tag, u, "eps %g below the largest gradient element %g" % (hp["eps"], top))
+            if clamp_all:
+                assert bool((ref[0]["raw"][:, 1] < CFG["ls_min"]).all()) and bool((ref[0]["dl"][:, 3] == 0).all())
+            z_ = _dead_slices(cur["q"], dead["q"]) + ([cur["actor"]["ls_w"][1], cur["actor"]["ls_b"][1]] if clamp_all else [])
+            zeros0 = [x.clone() for x in z_] if zeros0 is None else zeros0
+            be.update(tuple(batch), eps)
+            post = be.read()
+            got = to64(post)
+            z_ = _dead_slices(post["q"], dead["q"]) + ([post["actor"]["ls_w"][1], post["actor"]["ls_b"][1]] if clamp_all else [])
+            assert all(torch.equal(a_, b_) for a_, b_ in zip(z_, zeros0)), (tag, u, "a weight with zero gradient and zero moments moved")
+            if u == SERIES_UPDATES:
+                fresh = series_ratios(got, *series_step(series_state(hp), P64, b64, e64, CFG, hp, ref=ref))
+                carried = series_ratios(got, *series_step(right, P64, b64, e64, CFG, hp, ref=ref))
+                log("%s: new handle: fresh Adam %.3g, the carried one %s" % (tag, max(fresh.values()), {n: "%.3g" % _net_worst(carried, n) for n in ("q", "v", "actor")}))
+                assert max(fresh.values()) <= 1.0, (tag, "fresh state at create", fresh)
+                for n in ("q", "v", "actor"):
+                    assert _net_worst(carried, n) > 1.0, (tag, "carried state accepted after create", n)
+                    rejected["carried_after_create"] = min(rejected.get("carried_after_create", math.inf), _net_worst(carried, n))
+                break
+            ratios = series_ratios(got, *series_step(right, P64, b64, e64, CFG, hp, ref=ref))
+            for n in ("q", "v", "v_t", "actor"):
+                worst[n] = max(worst.get(n, 0.0), _net_worst(ratios, n))
+            log("%s: update %d worst/bound %s" % (tag, u, {n: "%.3g" % _net_worst(ratios, n) for n in ("q", "v", "v_t", "actor")}))
+            assert max(ratios.values()) <= 1.0, (tag, u, {k: v for k, v in ratios.items() if v > 1.0})
+            for var in variants:
+                rv = series_ratios(got, *series_step(wrong[var], P64, b64, e64, CFG, hp, variant=var, ref=ref))
+                _, first, nets = SERIES_RULES[var]
+                if u < first:
+                    continue
+                per = {n: _net_worst(rv, n) for n in nets}
+                log("%s: update %d %s %s" % (tag, u, var, {n: "%.3g" % v for n, v in per.items()}))
+                for n, v in per.items():
+                    assert v > 1.0, (tag, u, var, n, v)
+                    rejected[var] = min(rejected.get(var, math.inf), v)
+            if soft_update == 0:
+                assert all(torch.equal(post["v_t"][k], vt0[k]) for k in NAMES), (tag, u, "V_t moved")
+    finally:
+        be.close()
+    return dict(worst=worst, rejected=rejected, hp=hp)

@@ -1,6 +1,6 @@
 """cn_ddpg_update (csrc/crowdnav_td3.hip) on the device: the reference's learn() goldens (tests/golden/ddpg.npz), a float64
 statement of the same update with the gradients observed (tests/ddpg_f64.py), determinism, the replay path, argument checks,
-a hipGraph capture, the DDPG agent in the fused collection loop, and the trainer end to end.
+Adam across four updates against a float64 series (ddpg_f64.series_run), a hipGraph capture, the DDPG agent in the fused collection loop, and the trainer end to end.
 
 Adam with beta1 = beta2 = 0 steps w' = w - lr g / (|g| + eps); the tests invert that per element.  Both DDPG gradients are taken
 at the pre-update weights (ddpg.py:216-239), so ONE call with large learning rates for both optimizers yields the critic's and
@@ -226,6 +226,28 @@ def _gradients(shape, report):
         for net, ref, g, x in (("critic", refc, gc, xc), ("actor", refa, ga, xa)):
             scaled = {kk: v * (1 + SCALE_ERR) for kk, v in ref["g"].items()}
             assert not _accept(R.compare_grads(g, scaled, ref["bound"], x)), "%s x (1 + %g) accepted" % (net, SCALE_ERR)
+
+
+class _SeriesHandle(Fused):
+    """ddpg_f64.series_run's learner: one cn_ddpg handle on its own tensors (.P), stepped and re-margined in place."""
+
+    def __init__(self, P, shape, hp):
+        super().__init__(P, shape, hp["lr_critic"], hp["lr_actor"], hp["eps"], beta1=hp["beta1"], beta2=hp["beta2"], tau=hp["tau"])
+
+
+@pytest.mark.parametrize("case", D.SERIES_CASES, ids=D.series_id)
+def test_fused_ddpg_adam_across_four_updates_matches_float64(case):
+    """Four updates (both optimisers step on every one: adam_args(.., 1)) beside ddpg_f64's float64 series: every tensor of the
+    four networks within its bound after every update, each wrong variant (a bias correction frozen at t = 1, moments not
+    carried, betas exchanged, one lr for both, targets from the pre-step weights) rejected on each network it concerns, dead
+    units bit for bit, and a new handle on the stepped parameters stepping as a fresh Adam.  Betas 0.5 / 0.75 and the product's;
+    eps a power of two >= twice the first update's largest gradient element, re-asserted before every update; two different
+    power-of-two learning rates; tau = 2^-4.  Moments are observed only through the weights, and the margins are re-established
+    between updates: not a free-running trajectory.  tests/test_ddpg_f64_helpers.py runs the same cases on the CPU."""
+    shape, betas = case
+    res = D.series_run(_SeriesHandle, shape, betas, device="cuda", cfg=dict(CFG))
+    print("worst/bound %s; smallest rejecting ratio %s" % ({n: "%.3g" % v for n, v in res["worst"].items()}, {k: "%.3g" % v for k, v in res["rejected"].items()}))
+    assert max(res["worst"].values()) <= 1.0
 
 
 def test_cn_ddpg_create_and_update_reject_bad_arguments():

@@ -1,5 +1,7 @@
 """tests/sac_f64.py against torch.autograd in float64 on the reference's loss expressions (sac.py:253-272), its statement of
-cn_sac_act against crowdnav.sac.Agent.act in float64, and the promises of act_case and box_muller_draw.  CPU only."""
+cn_sac_act against crowdnav.sac.Agent.act in float64, the promises of act_case and box_muller_draw, and the series of four
+updates: against crowdnav.sac.Agent.learn in float64 (torch.optim.Adam), and its acceptance rule's power on every case the GPU
+tests run.  CPU only."""
 import math
 
 import numpy as np
@@ -232,3 +234,73 @@ def test_box_muller_draw_keeps_what_the_device_draw_promises():
     assert eu1.tolist() == [2.0 ** -24, 1.0, 1.0] and eu2.tolist() == [0.0, 1 - 2.0 ** -24, 0.0]
     h = S.draw_hash(0xD1B54A32D192ED03, (1 << 63) + 5, [0, 1, 4098])
     assert h.tolist() == [S._mix64(S._mix64(0xD1B54A32D192ED03 ^ S._mix64(((1 << 63) + 5) ^ 0x5bd1e995)) ^ m) for m in (0, 1, 4098)]
+
+
+# ---- the series of four updates -----------------------------------------------------------------------------------------------
+def _agent64_for_series(P, shape, hp):
+    """crowdnav.sac.Agent on the CPU in float64 holding P, torch.optim.Adam at hp's betas / eps / lrs (value_net as written: width 2)."""
+    from crowdnav.sac import Agent
+    assert shape[2] == 2
+    ag = Agent(obs_dim=shape[0], hidden=shape[1], actor_lr=hp["lr_actor"], v_lr=hp["lr_v"], q_lr=hp["lr_q"], batch_size=shape[3], memory_size=4,
+               tau=hp["tau"], soft_update="intended" if hp["soft_update"] else "as_written", device="cpu")
+    a = ag.actor
+    mods = dict(actor=(a.linear1.weight, a.linear1.bias, a.linear2.weight, a.linear2.bias, a.mean_linear.weight, a.mean_linear.bias,
+                       a.log_std_linear.weight, a.log_std_linear.bias))
+    for n, m in (("q", ag.q), ("v", ag.v), ("v_t", ag.v_t)):
+        mods[n] = (m.linear1.weight, m.linear1.bias, m.linear2.weight, m.linear2.bias, m.linear3.weight, m.linear3.bias)
+    for m in (ag.actor, ag.q, ag.v, ag.v_t):
+        m.double()
+    with torch.no_grad():
+        for n, ts in mods.items():
+            for k, t in zip(S.ACTOR_NAMES if n == "actor" else S.NAMES, ts):
+                t.copy_(P[n][k].double().reshape(t.shape))
+    for o in (ag.opt_a, ag.opt_v, ag.opt_q):
+        o.param_groups[0]["betas"], o.param_groups[0]["eps"] = (hp["beta1"], hp["beta2"]), hp["eps"]
+    read = lambda: {n: {k: t.detach().clone().reshape(P[n][k].shape) for k, t in zip(S.ACTOR_NAMES if n == "actor" else S.NAMES, ts)} for n, ts in mods.items()}
+    return ag, read
+
+
+@pytest.mark.parametrize("soft_update", [0, 1])
+def test_series_step_equals_agent_learn_in_float64(soft_update):
+    """Four updates of sac.Agent.learn(batch=..., noise=...) cast to float64 (torch.optim.Adam; the product's betas) against
+    series_step from the agent's own pre-update weights, a fresh eps each: every tensor within N 2^-53 (|w| + lr) -- the two
+    differ by float64 rounding alone: N = chain_length roundings on the longest chain to a gradient element, each 2^-53 of its
+    magnitude, and an element's step moves by lr x (its gradient's error) / eps <= lr x that, eps >= max |g|."""
+    shape = (20, 16, 2, 24)
+    P, batch, eps, _, chain = S.make_case(*shape)
+    b64 = tuple(x.double() for x in batch)
+    hp = S.series_hp(S.reference(S.to64(P), b64, eps.double())[0], S.SERIES_BETAS[1], soft_update)
+    ag, read = _agent64_for_series(P, shape, hp)
+    st = S.series_state(hp)
+    gen = torch.Generator().manual_seed(9)
+    worst = 0.0
+    for u in range(4):
+        e = eps.double() if u == 0 else torch.randn((shape[3], 2), generator=gen).double().clamp(-2, 2) * 0.1
+        pre = read()
+        ag.learn(batch=(b64[0], b64[1], b64[2][:, None], b64[3], b64[4][:, None]), noise=e)
+        got = read()
+        pred, _ = S.series_step(st, pre, b64, e, S.CFG, hp, ref=(S.run(R._Pass(), pre, b64, e), {k: torch.zeros(()) for k in S.GRADS}))
+        for n in pred:
+            lr = hp["lr_" + ("v" if n == "v_t" else n)]
+            for k in pred[n]:
+                tol = chain * 2.0 ** -53 * (pred[n][k].abs() + lr)
+                worst = max(worst, float(((got[n][k] - pred[n][k]).abs() / tol).max()))
+                assert bool(((got[n][k] - pred[n][k]).abs() <= tol).all()), (u, n, k)
+                if u == 3 and not (n == "v_t" and soft_update == 0):
+                    assert not torch.equal(got[n][k], P[n][k].double()), (n, k)
+    print("soft_update %d: worst |agent - series| / (N 2^-53 (|w| + lr)) = %.3g" % (soft_update, worst))
+    assert st["t"] == 4
+
+
+@pytest.mark.parametrize("case", S.SERIES_CASES, ids=S.series_id)
+def test_the_series_rule_accepts_a_float32_emulation_and_rejects_each_wrong_variant(case):
+    """Every case of the GPU series test with the kernel's Adam formula emulated in float32 (td3_f64.adam_f32_emulation on
+    float32-rounded float64 gradients, carried moments, one step count) in the handle's place: the inputs leave the emulation
+    inside the series' bound at every update and every wrong variant outside it on each network it concerns, before anything
+    runs on a GPU."""
+    shape, betas, mode, clamp_all = case
+    res = S.series_run(S.EmulatedLearner, shape, betas, mode, clamp_all=clamp_all, log=lambda s: None)
+    print(S.series_id(case), {n: "%.3g" % v for n, v in res["worst"].items()}, {k: "%.3g" % v for k, v in res["rejected"].items()})
+    assert max(res["worst"].values()) <= 1.0
+    want = {v for v in S.SERIES_VARIANTS if mode in S.SERIES_RULES[v][0]} | {"carried_after_create"}
+    assert set(res["rejected"]) == want and min(res["rejected"].values()) > 1.0
