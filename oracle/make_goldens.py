@@ -9,6 +9,17 @@ outputs the reference produced for them.  Re-run with:  python oracle/make_golde
                    clock, step counter, deque pose, timestep) and what the reference returned
                    (obs[366+4K], reward, done, safety counters, track table, CP scalars, waypoint)
   func.npz         function level: utils.py helpers and Env helpers on seeded random inputs
+
+Two action sources, chosen per configuration by the last member of its tuple:
+  (v_lo, v_hi, w_lo, w_hi)   uniform random actions.  Such a run never arrives anywhere: all its episodes end in a collision.
+  dict(driver="seek", ...)   SeekDriver, a scripted controller that reads only what Env.reset / Env.step returned -- heading
+                             and distance to the current way-point, observation slots R-1 and R -- turns towards it and
+                             drives, with seeded jitter.  It records what random actions cannot: success after a full
+                             way-point chain (goal8), the step counter ending an episode (timeout, timeout0), and both in
+                             the 363- and 370-input layouts (orig_goal, rw_goal).  k1 / k16 put the top-K rule (ENV:882-883)
+                             and the padding of a short list at the two ends of the K the kernels take.
+What each of those files has to contain is written down in oracle/golden_census.py (REQUIRED); a run that misses a condition,
+or a file above MAX_BYTES, is not written.  Every action is float32-representable.
 """
 import os
 import sys
@@ -18,13 +29,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import oracle  # noqa: E402
+from oracle import golden_census  # noqa: E402
 from oracle.harness.refenv import Harness, HarnessOriginal, HarnessRealworld  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
-MAXT = 24
+MAXT = golden_census.MAXT
+MAX_BYTES = 1 << 20     # no new sequence file above this (the largest one committed, seq_rw20, has 1.49 MB)
 
 SEQ_CONFIGS = {
-    # name: (config overrides, episodes, action ranges)
+    # name: (config overrides, episodes, action source: ranges of random actions or a SeekDriver spec)
     "train20": (dict(n_peds=20, max_steps=200, seed=11), 5, (0.0, 0.22, -2.0, 2.0)),
     "dense100": (dict(n_peds=100, max_steps=120, seed=12), 4, (0.02, 0.12, -1.0, 1.0)),
     "eval60": (dict(n_peds=60, max_steps=80, seed=13, min_scan_range=0.0, goal_x=-1.0, goal_y=1.0), 2,
@@ -36,7 +49,93 @@ SEQ_CONFIGS = {
     # the reference fed by the simulator's "as Gazebo delivers it" switches: float32 LaserScan.ranges (cn_config.scan_f32) and the
     # diff-drive plugin's wheel-speed ramp (cn_config.wheel_accel; /odom then reports the wheels' twist, not the command)
     "gazebo20": (dict(n_peds=20, max_steps=150, seed=17, scan_f32=1, wheel_accel=1.0), 4, (0.0, 0.22, -2.0, 2.0)),
+    # the branches random actions never reach (oracle/golden_census.py REQUIRED names what each file must contain)
+    # goal8: four slow pedestrians, the driver at full speed: success after a whole way-point chain, the snap onto the goal
+    "goal8": (dict(n_peds=4, max_steps=200, seed=46, ped_vmax=0.05), 4, dict(driver="seek", v=0.2, hold_beyond=0.6)),
+    # timeout: the driver creeps, so the step counter ends every episode (ENV:1021-1023) with tracks alive and nothing near
+    "timeout": (dict(n_peds=6, max_steps=40, seed=44, ped_vmax=0.05), 3, dict(driver="seek", v=0.06, hold_beyond=0.6)),
+    # timeout0: the same in an empty room (n_peds is one value per file): the track list stays empty, the K slots are padding
+    "timeout0": (dict(n_peds=0, max_steps=30, seed=43), 2, dict(driver="seek", v=0.06, hold_beyond=0.6)),
+    # k1 / k16: the two ends of the K the kernels take, crowds under which n_tracks is both above K and a short list
+    "k1": (dict(n_peds=20, max_steps=100, seed=46, k_obstacles=1), 3, (0.0, 0.22, -2.0, 2.0)),
+    "k16": (dict(n_peds=140, max_steps=100, seed=45, k_obstacles=16), 3, (0.0, 0.22, -2.0, 2.0)),
 }
+
+
+class RandomActions(object):
+    """Uniform random actions from (v_lo, v_hi, w_lo, w_hi)."""
+
+    def __init__(self, arange, seed):
+        self.arange, self.rng = arange, np.random.default_rng(seed)
+
+    def reset(self):
+        pass
+
+    def __call__(self, obs):
+        ar = self.arange
+        # float32-representable: the product's ABI takes float32 actions (the TD3 actor's dtype)
+        return (float(np.float32(self.rng.uniform(ar[0], ar[1]))), float(np.float32(self.rng.uniform(ar[2], ar[3]))))
+
+
+class SeekDriver(object):
+    """A goal-seeking controller on the two numbers every layout reports about the current way-point: heading (slot R-1, goal
+    angle minus yaw, positive = to the left) and distance (slot R).  Angular speed proportional to the heading, linear speed `v`
+    scaled down while the heading is off, seeded uniform jitter on both.  `v` may be a list, one speed per episode in turn: an
+    episode too slow to arrive within max_steps ends at the step counter.
+
+    hold_beyond (layout 0): once the robot is within waypoint_radius of the goal, get_local_goal_waypoints finds no intersection
+    and hands back the goal mirrored in x (UTL:310-312), a point on the far side of the room, until compute_reward snaps the
+    way-point onto the goal.  The driver sees that as a reported distance that leaps from below 0.3 to beyond `hold_beyond`, and
+    then holds its course instead of turning round: the last stretch into the goal box is straight ahead."""
+
+    def __init__(self, spec, seed, R):
+        self.R, self.rng = R, np.random.default_rng(seed)
+        self.speeds = list(np.atleast_1d(spec.get("v", 0.2)))
+        self.episode, self.v = -1, self.speeds[0]
+        self.gain, self.wmax = spec.get("gain", 1.5), spec.get("wmax", 1.5)
+        self.slow = spec.get("slow", 1.0)                      # heading (rad) at which the linear speed reaches zero
+        self.jv, self.jw = spec.get("jv", 0.02), spec.get("jw", 0.2)
+        self.hold_beyond = spec.get("hold_beyond")
+        self.near = False
+
+    def reset(self):
+        self.near = False
+        self.episode += 1
+        self.v = float(self.speeds[self.episode % len(self.speeds)])
+
+    def __call__(self, obs):
+        heading, dist = float(obs[self.R - 1]), float(obs[self.R])
+        if self.hold_beyond is not None and self.near and dist > self.hold_beyond:
+            v, w = self.v, 0.0
+        else:
+            self.near = self.near or (self.hold_beyond is not None and dist <= self.hold_beyond)
+            w = min(self.wmax, max(-self.wmax, self.gain * heading))
+            v = self.v * max(0.0, 1.0 - abs(heading) / self.slow)
+        v = min(0.22, max(0.0, v + self.rng.uniform(-self.jv, self.jv)))
+        w = w + self.rng.uniform(-self.jw, self.jw)
+        return float(np.float32(v)), float(np.float32(w))
+
+
+def action_source(spec, seed, R=360):
+    return SeekDriver(spec, seed, R) if isinstance(spec, dict) else RandomActions(spec, seed)
+
+
+def write_seq(name, arrs, kw):
+    """Writes tests/golden/seq_<name>.npz unless the run misses what golden_census.REQUIRED asks of it or the file is too large."""
+    bad = golden_census.unmet(name, arrs, kw)
+    assert not bad, "seq_%s not written: %s" % (name, "; ".join(bad))
+    path = os.path.join(OUT, "seq_%s.npz" % name)
+    tmp = os.path.join(OUT, ".seq_%s.tmp.npz" % name)
+    np.savez_compressed(tmp, **arrs)
+    size = os.path.getsize(tmp)
+    if name in golden_census.REQUIRED and size > MAX_BYTES:
+        os.remove(tmp)
+        raise AssertionError("seq_%s not written: %d bytes > %d (record fewer episodes)" % (name, size, MAX_BYTES))
+    os.replace(tmp, path)
+    c = golden_census.census(arrs, kw)
+    print("%-10s endings: %d success %d collision %d time-out; %d way-point bonuses (%d snaps), before each success %r" % (
+        name, c["success"], c["collision"], c["timeout"], c["bonuses"], c["snaps"], c["bonuses_before_success"]))
+    return path
 # the reference under Python-2.7 round() (cn_config.py2_round; harness refenv.py2_round), fed by TieSim: sensor data on exact ties
 TIE_CONFIGS = {
     "py2tie": (dict(n_peds=40, max_steps=60, seed=16, py2_round=1), 3, (0.0, 0.22, -2.0, 2.0)),
@@ -96,7 +195,7 @@ def gen_seq(name, kw, episodes, arange, tie_sim=False):
     if tie_sim:
         sim = TieSim(sim, kw["seed"])
     h = Harness(sim)
-    rng = np.random.default_rng(kw["seed"])
+    act = action_source(arange, kw["seed"], kw.get("n_rays", 360))
     rows = []
     cols = {k: [] for k in ("ranges", "px", "py", "yaw", "v", "w", "now", "step_counter", "is_reset", "deque_x",
                             "deque_y", "end_timestep", "action", "obs", "reward", "done", "counters", "n_tracks",
@@ -129,10 +228,10 @@ def gen_seq(name, kw, episodes, arange, tie_sim=False):
     max_steps = kw["max_steps"]
     for ep in range(episodes):
         obs = h.reset()
+        act.reset()
         push(h.trace[-1], (0.0, 0.0), obs, 0.0, False)
         for st in range(max_steps):
-            # float32-representable: the product's ABI takes float32 actions (the TD3 actor's dtype)
-            a = (float(np.float32(rng.uniform(arange[0], arange[1]))), float(np.float32(rng.uniform(arange[2], arange[3]))))
+            a = act(obs)
             obs, r, d = h.step(a, st + 1)
             push(h.trace[-1], a, obs, r, d)
             if d:
@@ -141,8 +240,7 @@ def gen_seq(name, kw, episodes, arange, tie_sim=False):
     arrs["ped_init"] = sim.get_ped_init()
     arrs["config_keys"] = np.array(sorted(kw.keys()))
     arrs["config_vals"] = np.array([float(kw[k]) for k in sorted(kw.keys())])
-    path = os.path.join(OUT, "seq_%s.npz" % name)
-    np.savez_compressed(path, **arrs)
+    path = write_seq(name, arrs, kw)
     nt = arrs["n_tracks"]
     print("%-10s calls=%4d  tracks mean %.2f max %d  (>K on %d calls)  done=%d  %.0f KB" % (
         name, len(nt), nt.mean(), nt.max(), int((nt > kw.get("k_obstacles", 8)).sum()), int(arrs["done"].sum()),
@@ -153,6 +251,9 @@ ORIG_CONFIGS = {
     # environment_stage_1_original.py (obs_layout 1, 363 inputs): name -> (config overrides, episodes, action ranges)
     "orig20": (dict(n_peds=20, max_steps=150, seed=21, obs_layout=1), 6, (0.0, 0.22, -2.0, 2.0)),
     "orig60": (dict(n_peds=60, max_steps=80, seed=22, obs_layout=1, room_half=1.8), 4, (0.05, 0.22, -1.0, 1.0)),
+    # success endings, and the third episode too slow to arrive: ORIG:311 ends it
+    "orig_goal": (dict(n_peds=4, max_steps=150, seed=50, obs_layout=1, ped_vmax=0.05), 5,
+                  dict(driver="seek", v=[0.2, 0.2, 0.03, 0.2, 0.2])),
 }
 
 
@@ -161,7 +262,7 @@ def gen_seq_original(name, kw, episodes, arange):
     returned (obs[363], reward, done, success/failure flags, previous_distance / previous_heading)."""
     sim = oracle.Oracle(n_envs=1, **kw)
     h = HarnessOriginal(sim)
-    rng = np.random.default_rng(kw["seed"])
+    act = action_source(arange, kw["seed"], kw.get("n_rays", 360))
     cols = {k: [] for k in ("ranges", "px", "py", "yaw", "v", "w", "now", "step_counter", "is_reset", "action", "obs",
                             "reward", "done", "status", "prev")}
 
@@ -174,9 +275,10 @@ def gen_seq_original(name, kw, episodes, arange):
 
     for ep in range(episodes):
         obs = h.reset()
+        act.reset()
         push(h.trace[-1], (0.0, 0.0), obs, 0.0, False)
         for st in range(kw["max_steps"]):
-            a = (float(np.float32(rng.uniform(arange[0], arange[1]))), float(np.float32(rng.uniform(arange[2], arange[3]))))
+            a = act(obs)
             obs, r, d = h.step(a, st + 1)
             push(h.trace[-1], a, obs, r, d)
             if d:
@@ -185,8 +287,7 @@ def gen_seq_original(name, kw, episodes, arange):
     arrs["ped_init"] = sim.get_ped_init()
     arrs["config_keys"] = np.array(sorted(kw.keys()))
     arrs["config_vals"] = np.array([float(kw[k]) for k in sorted(kw.keys())])
-    path = os.path.join(OUT, "seq_%s.npz" % name)
-    np.savez_compressed(path, **arrs)
+    path = write_seq(name, arrs, kw)
     print("%-10s calls=%4d  done=%d (success %d)  %.0f KB" % (name, len(arrs["done"]), int(arrs["done"].sum()),
                                                               int(sum(1 for i in range(len(arrs["done"])) if arrs["done"][i] and arrs["status"][i][0])),
                                                               os.path.getsize(path) / 1024))
@@ -197,6 +298,9 @@ RW_CONFIGS = {
     "rw20": (dict(n_peds=20, max_steps=250, seed=31, obs_layout=2, dt_ms=50), 5, (0.0, 0.22, -2.0, 2.0)),
     "rw60": (dict(n_peds=60, max_steps=200, seed=32, obs_layout=2, dt_ms=50, min_scan_range=0.0, room_half=1.8), 3,
              (0.05, 0.22, -1.0, 1.0)),
+    # a step is 0.06 s here, so the goal is put 0.99 m from the spawn pose: three arrivals and one episode ended by RW:732
+    "rw_goal": (dict(n_peds=8, max_steps=150, seed=52, obs_layout=2, dt_ms=50, ped_vmax=0.05, goal_x=0.3, goal_y=-0.3), 4,
+                dict(driver="seek", v=[0.2, 0.2, 0.03, 0.2])),
 }
 
 
@@ -205,7 +309,7 @@ def gen_seq_realworld(name, kw, episodes, arange):
     (obs[370], reward, done, counters, track table, collision probability, bbox size, previous distance / heading)."""
     sim = oracle.Oracle(n_envs=1, **kw)
     h = HarnessRealworld(sim)
-    rng = np.random.default_rng(kw["seed"])
+    act = action_source(arange, kw["seed"], kw.get("n_rays", 360))
     cols = {k: [] for k in ("ranges", "px", "py", "yaw", "v", "w", "now", "step_counter", "is_reset", "deque_x", "deque_y",
                             "end_timestep", "action", "obs", "reward", "done", "counters", "n_tracks", "track_pose",
                             "track_dist", "track_speed", "track_vel", "collision_prob", "bb", "status", "prev")}
@@ -229,9 +333,10 @@ def gen_seq_realworld(name, kw, episodes, arange):
 
     for ep in range(episodes):
         obs = h.reset()
+        act.reset()
         push(h.trace[-1], (0.0, 0.0), obs, 0.0, False)
         for st in range(kw["max_steps"]):
-            a = (float(np.float32(rng.uniform(arange[0], arange[1]))), float(np.float32(rng.uniform(arange[2], arange[3]))))
+            a = act(obs)
             obs, r, d = h.step(a, st + 1)
             push(h.trace[-1], a, obs, r, d)
             if d:
@@ -240,8 +345,7 @@ def gen_seq_realworld(name, kw, episodes, arange):
     arrs["ped_init"] = sim.get_ped_init()
     arrs["config_keys"] = np.array(sorted(kw.keys()))
     arrs["config_vals"] = np.array([float(kw[k]) for k in sorted(kw.keys())])
-    path = os.path.join(OUT, "seq_%s.npz" % name)
-    np.savez_compressed(path, **arrs)
+    path = write_seq(name, arrs, kw)
     nt = arrs["n_tracks"]
     print("%-10s calls=%4d  tracks mean %.2f max %d  done=%d (success %d)  %.0f KB" % (
         name, len(nt), nt.mean(), nt.max(), int(arrs["done"].sum()),

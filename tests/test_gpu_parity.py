@@ -371,7 +371,11 @@ def test_rollout_parity_720_rays(oracle_mod):
     _compare_rollout(oracle_mod, steps=30, seed=11, n_envs=8, n_peds=100, n_rays=720, room_half=2.4, max_steps=25)
 
 
-@pytest.mark.parametrize("name", ["train20", "dense100", "eval60", "k4", "geos38", "gazebo20"])
+# goal8 ... k16: the endings and K edges recorded under oracle/make_goldens.py's goal-seeking driver (oracle/golden_census.py)
+GOAL_SEQS = ["goal8", "timeout", "timeout0", "k1", "k16"]
+
+
+@pytest.mark.parametrize("name", ["train20", "dense100", "eval60", "k4", "geos38", "gazebo20"] + GOAL_SEQS)
 def test_reproduces_reference_golden_run(name):
     """N=1, driven only by the recorded actions: the HIP path reproduces what the REFERENCE's Python
     returned in the golden run (observations, rewards, done flags)."""
@@ -773,7 +777,7 @@ def test_every_scripted_evaluation_scenario_equals_the_oracle(oracle_mod):
     assert seen == 29
 
 
-@pytest.mark.parametrize("name", ["train20", "dense100", "eval60", "k4", "geos38", "py2tie", "gazebo20"])
+@pytest.mark.parametrize("name", ["train20", "dense100", "eval60", "k4", "geos38", "py2tie", "gazebo20"] + GOAL_SEQS)
 def test_golden_replay_through_the_kernel(name):
     """The kernel fed with EXACTLY what Gazebo/ROS handed the reference in the golden runs (lidar ranges, odom,
     clock, step counter; cn_observe_external) returns what the REFERENCE's own Python returned: observations,
@@ -898,7 +902,7 @@ def test_original_layout_other_shapes(oracle_mod):
     assert n_done >= 32 and exact == 1.0
 
 
-@pytest.mark.parametrize("name", ["orig20", "orig60"])
+@pytest.mark.parametrize("name", ["orig20", "orig60", "orig_goal"])
 def test_original_layout_golden_replay_and_run(name):
     """Layout 1 against the REFERENCE's own Python: (a) the kernel fed with the recorded /scan + /odom
     (cn_observe_external), (b) the full simulated path driven by the recorded actions."""
@@ -1307,7 +1311,7 @@ def test_realworld_layout_env_wrapper_surface():
     assert 0.0 <= env.get_social_safety_violation_status(step + 1) <= 1.0 and 0.0 <= env.get_ego_safety_violation_status(step + 1) <= 1.0
 
 
-@pytest.mark.parametrize("name", ["rw20", "rw60"])
+@pytest.mark.parametrize("name", ["rw20", "rw60", "rw_goal"])
 def test_realworld_layout_golden_replay_and_run(name):
     """Layout 2 against the REFERENCE's own Python: (a) the kernel fed with the recorded /scan + /odom (cn_observe_external,
     the way a physical robot would drive it), (b) the full simulated path driven by the recorded actions."""

@@ -7,7 +7,10 @@ import pytest
 from conftest import load_seq
 
 SEQS = ["train20", "dense100", "eval60", "k4", "geos38",  # geos38: the reference under GEOS <= 3.8 empty-result semantics
-        "gazebo20"]   # float32 LaserScan.ranges + the diff-drive plugin's wheel-speed ramp (cn_config.scan_f32, wheel_accel)
+        "gazebo20",   # float32 LaserScan.ranges + the diff-drive plugin's wheel-speed ramp (cn_config.scan_f32, wheel_accel)
+        # recorded under oracle/make_goldens.py's goal-seeking driver, for the endings random actions never reach
+        # (oracle/golden_census.py): success after a way-point chain, the step counter, an empty room; and K = 1 / 16
+        "goal8", "timeout", "timeout0", "k1", "k16"]
 # py2tie: the reference under Python-2.7 round() (cn_config.py2_round), its sensor data placed on exact decimal ties by
 # oracle/make_goldens.py's TieSim -- replay only (the poses it was fed are not the simulator's)
 REPLAY_SEQS = SEQS + ["py2tie"]
@@ -42,7 +45,7 @@ def test_sequence_replay_bit_exact(oracle_mod, name):
         assert dbg["bb"] == z["bb"][i]
         assert tuple(o.counters()[0][:3]) == tuple(z["counters"][i])
         over_k += n > o.K
-    if name in ("dense100", "eval60", "k4", "geos38"):
+    if name in ("dense100", "eval60", "k4", "geos38", "k1", "k16"):
         assert over_k > 0  # the "keep the K lowest" branch of ENV:882-883 is exercised
 
 
@@ -214,7 +217,7 @@ def test_function_level_goldens_collision_probability_topk_heading_box_reward(or
 
 
 # ---- obs_layout 1: environment_stage_1_original.py (363 inputs), SURVEY 8f N3 -----------------------------
-ORIG_SEQS = ["orig20", "orig60"]
+ORIG_SEQS = ["orig20", "orig60", "orig_goal"]
 
 
 @pytest.mark.parametrize("name", ORIG_SEQS)
@@ -254,7 +257,7 @@ def test_original_layout_full_simulation_reproduces_reference_run(oracle_mod, na
 
 
 # ---- obs_layout 2: environment_stage_1_nobonus_realworld.py (370 inputs), SURVEY 8f N3 ------------------------
-RW_SEQS = ["rw20", "rw60"]
+RW_SEQS = ["rw20", "rw60", "rw_goal"]
 
 
 @pytest.mark.parametrize("name", RW_SEQS)
@@ -298,6 +301,99 @@ def test_realworld_layout_full_simulation_reproduces_reference_run(oracle_mod, n
             obs = obs[0]
             assert r[0] == z["reward"][i] and bool(d[0]) == bool(z["done"][i]), (name, i)
         assert np.abs(obs - z["obs"][i]).max() <= 1e-9, (name, i, np.abs(obs - z["obs"][i]).max())
+
+
+# ---- what the goldens were recorded for: a census of their branches, and proof that they bite on them ----------------------
+def test_census_of_the_goldens_recorded_for_success_timeout_and_k_edges():
+    """oracle/golden_census.py on the committed files: each of them still holds the branch it was recorded for (the conditions
+    oracle/make_goldens.py refuses to write a file without), recomputed here from the recorded columns alone."""
+    from oracle import golden_census as gc
+    cen = {}
+    for name in sorted(gc.REQUIRED):
+        z, kw = load_seq(name)
+        assert gc.unmet(name, z, kw) == [], name
+        cen[name] = gc.census(z, kw)
+    # layouts 0 / 1 / 2: at least three arrivals each, status [True, False]
+    assert all(cen[n]["success"] >= 3 for n in ("goal8", "orig_goal", "rw_goal"))
+    assert (cen["goal8"]["layout"], cen["orig_goal"]["layout"], cen["rw_goal"]["layout"]) == (0, 1, 2)
+    # goal8: a success after a chain of at least three way-point bonuses, and a way-point snapped onto the goal (ENV:1121-1123)
+    assert max(cen["goal8"]["bonuses_before_success"]) >= 3 and cen["goal8"]["snaps"] >= 1
+    # step_counter == max_steps with nothing below min_scan_range, scored as a failure (ENV:1021-1023, 1155-1159; ORIG:311; RW:732)
+    assert cen["timeout"]["timeout"] >= 2 and cen["orig_goal"]["timeout"] >= 1 and cen["rw_goal"]["timeout"] >= 1
+    # the empty room: no track on any call of an episode that runs to its time limit
+    assert cen["timeout0"]["timeout"] >= 1 and cen["timeout0"]["no_tracks"] == cen["timeout0"]["calls"]
+    # K = 1 and K = 16: the top-K cut and a short, padded list both occur
+    for name, K in (("k1", 1), ("k16", 16)):
+        assert cen[name]["K"] == K and cen[name]["over_k"] > 0 and cen[name]["under_k"] > 0, (name, cen[name])
+        assert cen[name]["max_tracks"] <= gc.MAXT
+    import os
+    from conftest import GOLDEN
+    for name in gc.REQUIRED:
+        assert os.path.getsize(os.path.join(GOLDEN, "seq_%s.npz" % name)) <= 1 << 20, name
+
+
+def _replay(oracle_mod, z, kw):
+    """(obs, reward, done, status) of every call of a layout-0 golden replayed from its recorded sensor inputs under `kw`."""
+    o = oracle_mod.Oracle(n_envs=1, **kw)
+    out = []
+    for i in range(len(z["now"])):
+        inp = {k: (int(z[k][i]) if k in ("step_counter", "is_reset") else float(z[k][i])) for k in IN_KEYS}
+        obs, r, d, idx = o.ext_call(0, z["ranges"][i], **inp)
+        if inp["is_reset"]:
+            o.ext_set_done(0, False)
+        c = o.counters()[0]
+        out.append((obs, r, d, (bool(c[4]), bool(c[5]))))
+    return out
+
+
+def _same(got, z, i):
+    obs, r, d, st = got[i]
+    return (np.array_equal(obs, z["obs"][i]) and (bool(z["is_reset"][i]) or (r == z["reward"][i] and d == bool(z["done"][i])))
+            and st == tuple(bool(x) for x in z["status"][i]))
+
+
+def test_timeout_golden_bites_on_max_steps(oracle_mod):
+    """`timeout` replayed with max_steps + 1: identical up to the first ending, where done, reward and status all differ -- the
+    only thing that ended that episode is ENV:1021-1023, and ENV:1155-1159 scored it -200 and episode_failure."""
+    from oracle import golden_census as gc
+    z, kw = load_seq("timeout")
+    end = gc.census(z, kw)["timeout_calls"][0]
+    got = _replay(oracle_mod, z, dict(kw, max_steps=kw["max_steps"] + 1))
+    assert all(_same(got, z, i) for i in range(end))
+    obs, r, d, st = got[end]
+    assert bool(z["done"][end]) and not d
+    assert r == z["reward"][end] + 200.0
+    assert tuple(bool(x) for x in z["status"][end]) == (False, True) and st != (False, True)
+
+
+def test_goal8_golden_bites_on_the_goal_box(oracle_mod):
+    """`goal8` replayed with the goal one box width (2 * goal_eps) further along x: the first recorded success is none there."""
+    from oracle import golden_census as gc
+    z, kw = load_seq("goal8")
+    first = gc.census(z, kw)["first_success"]
+    # ENV:1153: goal_reward + non_terminating_reward, the latter at least the step penalty
+    assert first > 0 and tuple(bool(x) for x in z["status"][first]) == (True, False) and z["reward"][first] >= 198.0
+    got = _replay(oracle_mod, z, dict(kw, goal_x=kw.get("goal_x", -1.0) - 0.4))
+    obs, r, d, st = got[first]
+    assert not d and st != (True, False) and r != z["reward"][first]
+    assert not _same(got, z, first)
+
+
+def test_k1_golden_bites_on_k(oracle_mod):
+    """`k1` replayed with K = 2: everything before the obstacle slots stays what the reference returned, and the tail differs.
+    ENV:882-883 keeps `sorted(..., reverse=True)[-K:]`, so with two entries the first slot now holds the second lowest CP
+    instead of the lowest, and the second slot a real obstacle instead of nothing."""
+    z, kw = load_seq("k1")
+    assert kw["k_obstacles"] == 1
+    got = _replay(oracle_mod, z, dict(kw, k_obstacles=2))
+    first_differs = second_real = 0
+    for i in range(len(got)):
+        obs, want = got[i][0], z["obs"][i]
+        assert len(want) == 370 and len(obs) == 374
+        assert np.array_equal(obs[:366], want[:366]), i
+        first_differs += int(not np.array_equal(obs[366:370], want[366:370]))
+        second_real += int(not np.array_equal(obs[370:374], [obs[361], obs[362], 0.0, 0.0]))     # ENV:273's padding
+    assert first_differs > 0 and second_real > 0, (first_differs, second_real)
 
 
 def test_state_exchange_round_trip_and_first_difference(oracle_mod):
