@@ -37,6 +37,7 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_ddpg_create", "cn_ddpg_destroy", "cn_ddpg_update", "cn_ddpg_loss_dev", "cn_ddpg_batch_dev",
            "cn_dqn_create", "cn_dqn_destroy", "cn_dqn_update", "cn_dqn_loss_dev", "cn_dqn_batch_dev", "cn_dqn_act",
            "cn_sac_create", "cn_sac_destroy", "cn_sac_update", "cn_sac_loss_dev", "cn_sac_batch_dev", "cn_sac_act",
+           "cn_tab_create", "cn_tab_destroy", "cn_tab_set", "cn_tab_get", "cn_tab_tables", "cn_tab_learn_act", "cn_tab_last_error",
            "cn_replay_write", "cn_episode_log_add"]
 
 
@@ -179,6 +180,24 @@ class CnSacActIO(C.Structure):
                 ("max_v", C.c_float), ("max_w", C.c_float), ("log_std_min", C.c_float), ("log_std_max", C.c_float),
                 ("eps", C.c_void_p), ("seed", C.c_uint64), ("counter", C.c_uint64),
                 ("twist", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p), ("z", C.c_void_p)]
+
+
+CN_TAB_STATES, CN_TAB_ACTIONS = 977, 3
+CN_TAB_QLEARN, CN_TAB_SARSA = 0, 1
+
+
+class CnTabConfig(C.Structure):
+    """Mirror of `cn_tab_config` (include/crowdnav.h)."""
+    _fields_ = [("algo", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_double), ("gamma", C.c_double), ("seed", C.c_uint64)]
+
+
+class CnTabIO(C.Structure):
+    """Mirror of `cn_tab_io` (include/crowdnav.h)."""
+    _fields_ = [("obs_prev", C.c_void_p), ("obs", C.c_void_p), ("obs_ld", C.c_int64), ("n", C.c_int32), ("col", C.c_int32),
+                ("learn", C.c_int32), ("act", C.c_int32), ("action_prev", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p),
+                ("keep", C.c_void_p), ("epsilon", C.c_double), ("epsilon_discount", C.c_double), ("epsilon_min", C.c_double),
+                ("episodes_dev", C.c_void_p), ("u_learn", C.c_void_p), ("u_act", C.c_void_p), ("counter", C.c_uint64),
+                ("action", C.c_void_p), ("twist", C.c_void_p), ("state", C.c_void_p), ("state_prev", C.c_void_p), ("q_row", C.c_void_p)]
 
 
 class CnTd3Batch(C.Structure):
@@ -327,6 +346,13 @@ def lib():
         L.cn_sac_loss_dev.argtypes = [vp]; L.cn_sac_loss_dev.restype = vp
         L.cn_sac_batch_dev.argtypes = [vp, C.c_int]; L.cn_sac_batch_dev.restype = vp
         L.cn_sac_act.argtypes = [C.POINTER(CnSacActIO), C.c_int, vp]
+        L.cn_tab_create.argtypes = [C.POINTER(CnTabConfig), C.c_int, C.POINTER(vp)]
+        L.cn_tab_destroy.argtypes = [vp]; L.cn_tab_destroy.restype = None
+        L.cn_tab_set.argtypes = [vp, vp, vp, vp]
+        L.cn_tab_get.argtypes = [vp, vp, vp, vp]
+        L.cn_tab_tables.argtypes = [vp, vp, vp, vp]
+        L.cn_tab_learn_act.argtypes = [vp, C.POINTER(CnTabIO), vp]
+        L.cn_tab_last_error.restype = C.c_char_p
         L.cn_replay_write.argtypes = [C.POINTER(CnReplayRing), vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
         L.cn_episode_log_add.argtypes = [C.POINTER(CnEpisodeLog), vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, C.c_int, vp]
         _lib = L

@@ -29,6 +29,16 @@ sac_{actor,critic_v,critic_soft_q}_model_ep<N>.pt, CSV sac_training.csv; `--lear
 
     python -m crowdnav.train --algo sac --scenario training_as_logged --waypoint-reward 0 --envs 16 --updates 16 --csv --learner fused
 
+`--algo qlearn` / `--algo sarsa` train the reference's tabular learners (start_qlearn_training.py, start_sarsa_training.py; qlearn.py,
+sarsa.py; crowdnav.tabular) on obs_layout 1 with --max-steps 200 (qlearn.yaml, sarsa.yaml): ONE Q-table shared by all envs, one
+cn_tab_learn_act per launch (learn from the transitions of the launch with keep = ~resetting, then chooseAction on the table after
+the writes); --alpha 0.2, --gamma 0.9, --epsilon 0.9 (the yamls' commented value) discounted by --epsilon-discount 0.9986 per
+finished episode; checkpoints <algo>_qtable_ep<N>.txt (the reference's pickled dict), CSV <algo>_training.csv; --load-qtable
+reads such a file (the published discrete tables included); `--evaluate` acts only (the committed start_qlearn_training.py: the
+loaded table, epsilon as given, no learning).  --updates, --memory, --batch and --graphs do not apply and are rejected:
+
+    python -m crowdnav.train --algo sarsa --scenario training_as_logged --waypoint-reward 0 --envs 16 --csv --learner fused
+
 What it keeps from the reference loop: Agent hyper-parameters (TRAIN:62-72), exploration noise sigma = 1.0 with the
 clip to v in [0, 0.22], w in [-2, 2], 1-based per-env step counters, `learn()` only once the replay holds more than a
 batch, target-network checkpoints named td3_{actor,critic1,critic2}_model_ep<N>.pt, one CSV row per finished episode
@@ -51,7 +61,9 @@ from . import presets
 from .config import Config
 from .env import VecEnv
 from .rollout import EpisodeStats, evaluate
-from . import ddpg, dqn, sac, td3
+from . import ddpg, dqn, sac, tabular, td3
+
+TABULAR = dict(qlearn=tabular.QLearn, sarsa=tabular.Sarsa)
 
 
 def make_env(scenario, n_envs, max_steps, seed, device, ped_vmax=None, **switches):
@@ -324,6 +336,86 @@ def train_sac(a):
     return agent, episodes
 
 
+def save_tabular_checkpoint(agent, outdir, episodes):
+    agent.save(outdir, episodes)
+    tmp = os.path.join(outdir, ".latest_checkpoint.txt.%d" % os.getpid())
+    open(tmp, "w").write("%d\n" % episodes)
+    os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
+
+
+def train_tabular(a):
+    """start_sarsa_training.py:48-116 / start_qlearn_training.py for N environments that share one Q-table, on train_dqn's pattern:
+    chooseAction for every env after the reset, then per launch env.step -> ONE learn_act (learn the launch's transitions except
+    the reset launches, then chooseAction on the table after the writes; epsilon from the device's count of finished episodes).
+    --evaluate: the same loop without the learn phase (and no checkpoint: the table does not change)."""
+    dev = a.device
+    torch.cuda.set_device(dev)
+    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, **env_switches(a))
+    if env.D < 2:
+        raise ValueError("the tabular learners read the last two columns of the observation")
+    agent = TABULAR[a.algo](epsilon=a.epsilon, alpha=a.alpha, gamma=a.gamma, epsilon_discount=a.epsilon_discount, seed=a.seed,
+                            device="cuda:%d" % dev)
+    if a.load_qtable:
+        agent.load_q(a.load_qtable)                 # utils.load_q (qlearn.py:23)
+    if a.learner == "fused":
+        agent.enable_fused()
+    learn = not a.evaluate
+    stats = EpisodeStats()
+    os.makedirs(a.out, exist_ok=True)
+    obs = env.reset()
+    t0 = time.time()
+    episodes, env_steps = 0, 0
+    log = open(os.path.join(a.out, "progress.txt"), "a")
+    N = env.N
+    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
+    prev = torch.empty_like(obs)
+    elog = DeviceEpisodeLog(obs.device, a.max_csv_rows)
+    next_ckpt = a.checkpoint_every
+    step_s = (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0
+    name = "%s_training%s" % (a.algo, "_test" if a.evaluate else "")
+    out = agent.learn_act(None, None, None, obs, learn=False, act=True, episodes_dev=elog.n)      # the first step of every first episode
+    for it in range(1, a.launches + 1):
+        action = out["action"]
+        prev.copy_(obs)
+        obs, reward, done = env.step(out["twist"], auto_reset="next")
+        keep = ~resetting
+        resetting = done.bool()
+        elog.add(done, env.counters(), env.returns()[0], it, keep)
+        out = agent.learn_act(prev, action, reward, obs, keep=keep, learn=learn, act=True, episodes_dev=elog.n)
+        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
+        if it % a.log_every == 0 or last_launch:
+            rows, tot = elog.flush()
+            ne = int(tot[0])
+            episodes += ne; env_steps += int(tot[4])
+            for r in rows.tolist():
+                seen = int(r[6])
+                stats.add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
+                          1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
+            agent.epsilon = dqn.epsilon_after(episodes + 1, a.epsilon, a.epsilon_discount)      # what the device used
+            if ne:
+                line = "launch %6d  env-steps %10d  episodes %8d  success %.3f  mean return %8.1f  mean steps %6.1f  epsilon %.3f  %.0f s" % (
+                    it, env_steps, episodes, tot[1] / ne, tot[2] / ne, tot[3] / ne, agent.epsilon, time.time() - t0)
+                print(line, flush=True); log.write(line + "\n"); log.flush()
+            if a.csv:
+                stats.append_csv(a.out, name)
+            if learn and episodes >= next_ckpt:            # start_sarsa_training.py:105-108 (every 100 episodes there)
+                save_tabular_checkpoint(agent, a.out, episodes)
+                while next_ckpt <= episodes:
+                    next_ckpt += a.checkpoint_every
+            if last_launch:
+                break
+    if learn:
+        save_tabular_checkpoint(agent, a.out, episodes)
+    last = stats.rows[-500:]
+    if last:
+        _, present, counts = agent.table()
+        line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f | %d table entries, %d first writes, %d blends, %d env-steps, %.0f s" % (
+            len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
+            int(present.sum()), counts[0], counts[1], env_steps, time.time() - t0)
+        print(line, flush=True); log.write(line + "\n"); log.flush()
+    return agent, episodes
+
+
 def make_agent(a, obs_dim, device, **kw):
     """The learner of --algo with its reference defaults; --batch / --lr-actor / --lr-critic / --tau override them when given."""
     over = {k: v for k, v in (("batch_size", getattr(a, "batch", None)), ("actor_lr", getattr(a, "lr_actor", None)),
@@ -495,21 +587,28 @@ def parse_args(argv=None):
     ap.add_argument("--launches", type=int, default=3000)
     ap.add_argument("--time-limit", type=float, default=0.0, help="stop after this many seconds (checked at log time); 0 = run all launches")
     ap.add_argument("--max-steps", type=int, default=None, help="nsteps: configs/td3.yaml 1000; configs/dqn.yaml 250 (--algo dqn)")
-    ap.add_argument("--updates", type=int, default=4, help="TD3 updates per launch")
-    ap.add_argument("--algo", default="td3", choices=["td3", "ddpg", "dqn", "sac"],
+    ap.add_argument("--updates", type=int, default=4, help="TD3 updates per launch (not qlearn / sarsa: one table update per transition)")
+    ap.add_argument("--algo", default="td3", choices=["td3", "ddpg", "dqn", "sac", "qlearn", "sarsa"],
                     help="td3: start_td3_training.py; ddpg: start_ddpg_training.py (crowdnav.ddpg); dqn: start_dqn_training.py (crowdnav.dqn); "
-                         "sac: sac.py with start_sac_training.py's values at their names (crowdnav.sac)")
+                         "sac: sac.py with start_sac_training.py's values at their names (crowdnav.sac); qlearn / sarsa: the tabular learners "
+                         "of start_qlearn_training.py / start_sarsa_training.py (crowdnav.tabular) -- --updates, --memory, --batch and "
+                         "--graphs do not apply to them and are rejected")
+    ap.add_argument("--alpha", type=float, default=0.2, help="qlearn / sarsa: the learning rate (qlearn.yaml, sarsa.yaml)")
+    ap.add_argument("--gamma", type=float, default=0.9, help="qlearn / sarsa: the discount (qlearn.yaml, sarsa.yaml)")
+    ap.add_argument("--load-qtable", default=None, help="qlearn / sarsa: a <algo>_qtable_ep<N>.txt to start from (the reference's pickled dict)")
     ap.add_argument("--sac-value-net", default="as-written", choices=["as-written", "intended"], help="sac: the value nets as sac.py:175-176 "
                     "constructs them (hidden width 2, linear3 ~ U(+-hidden)) or as intended (hidden width --hidden, 3e-3)")
     ap.add_argument("--sac-soft-update", default="as-written", choices=["as-written", "intended"], help="sac: sac.py:290 as written (V is pulled "
                     "towards its frozen copy) or as intended (the target follows V)")
     ap.add_argument("--sac-deterministic", action="store_true", help="sac: act with z = mean (the reference's act() always samples)")
-    ap.add_argument("--epsilon", type=float, default=1.0, help="dqn: the initial exploration rate (the logged run: 1.0; dqn.yaml: 0.0)")
-    ap.add_argument("--epsilon-discount", type=float, default=0.995, help="dqn: dqn.yaml epsilon_discount, applied per episode while > 0.05")
+    ap.add_argument("--epsilon", type=float, default=None, help="dqn: the initial exploration rate (default 1.0, the logged run; dqn.yaml: 0.0); "
+                    "qlearn / sarsa: default 0.9 (sarsa.yaml; qlearn.yaml's commented value)")
+    ap.add_argument("--epsilon-discount", type=float, default=None, help="epsilon_discount, applied per episode while > 0.05: dqn.yaml 0.995; "
+                    "qlearn.yaml / sarsa.yaml 0.9986")
     ap.add_argument("--target-update", type=int, default=10000, help="dqn: updates between hard target copies (TRAIN_DQN:51)")
     ap.add_argument("--dqn-inputs", type=int, default=361, choices=[361, 363], help="dqn: network inputs (TRAIN_DQN:55: 361 = the first "
                     "361 columns of the obs_layout-1 observation)")
-    ap.add_argument("--batch", type=int, default=None, help="TRAIN:62 -> 128 (td3); TRAIN_DDPG:55 -> 64 (ddpg)")
+    ap.add_argument("--batch", type=int, default=None, help="TRAIN:62 -> 128 (td3); TRAIN_DDPG:55 -> 64 (ddpg) (not qlearn / sarsa)")
     ap.add_argument("--lr-actor", type=float, default=None, help="default: the algorithm's (td3 3e-4, ddpg 1e-4)")
     ap.add_argument("--lr-critic", type=float, default=None, help="default: the algorithm's (td3 3e-4, ddpg 1e-3)")
     ap.add_argument("--tau", type=float, default=None, help="default: the algorithm's (td3 0.005, ddpg 0.001)")
@@ -517,7 +616,7 @@ def parse_args(argv=None):
                     "host-side, one state per env; collection goes act -> step.  Off by default, as in TRAIN_DDPG:100")
     ap.add_argument("--obs-layout", type=int, default=None, choices=[0, 1, 2], help="cn_config.obs_layout: 0 = 366 + 4K inputs (default); "
                     "1 = environment_stage_1_original's 363 (the shipped DDPG checkpoints); 2 = 370")
-    ap.add_argument("--memory", type=int, default=1_000_000, help="TRAIN:63")
+    ap.add_argument("--memory", type=int, default=1_000_000, help="TRAIN:63 (not qlearn / sarsa: no replay)")
     ap.add_argument("--checkpoint-every", type=int, default=100000, help="episodes between checkpoints (TRAIN:150: 100); checked at log time")
     ap.add_argument("--log-every", type=int, default=100)
     ap.add_argument("--ped-vmax", type=float, default=None, help="training world only: walker speed bound (CROWD:101 -> 0.2)")
@@ -528,7 +627,7 @@ def parse_args(argv=None):
                     help="cn_config.track_capacity: 0 = auto (32 / 64, LDS); 128 ... 1024 = a wide table in HBM for long runs whose track "
                          "list outgrows 64 (slower; CN_ST_TRACK_OVERFLOW otherwise)")
     ap.add_argument("--reset-mode", default="next", choices=["next", "same"], help="next: the fast kernel, reset launches masked out of the replay; same: same-call reset + final_obs")
-    ap.add_argument("--graphs", type=int, default=1, help="1: capture the TD3 update into hipGraphs (Agent.enable_graphs; td3 only)")
+    ap.add_argument("--graphs", type=int, default=1, help="1: capture the TD3 update into hipGraphs (Agent.enable_graphs; td3 only; rejected for qlearn / sarsa)")
     ap.add_argument("--learner", default="torch", choices=["torch", "fused"], help="torch: the PyTorch update (td3: eager / hipGraph; ddpg: eager); "
                     "fused: cn_td3_update / cn_ddpg_update (csrc/crowdnav_td3.hip)")
     ap.add_argument("--actor-final-init", type=float, default=None, help="NOT the reference: U(+-x) initialisation of the actor's output layer (e.g. 0.003)")
@@ -544,13 +643,25 @@ def parse_args(argv=None):
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--episodes-per-env", type=int, default=1)
     a = ap.parse_args(argv)
+    tab = a.algo in TABULAR
+    if tab:           # flags of the replay learners: rejected when given, whatever their value
+        probe = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+        for flag in ("--updates", "--memory", "--batch", "--graphs"):
+            probe.add_argument(flag, default=None)
+        given = [k for k, v in vars(probe.parse_known_args(argv)[0]).items() if v is not None]
+        if given:
+            ap.error("--algo %s has no replay, batch or update count: %s do(es) not apply" % (a.algo, ", ".join("--" + g for g in given)))
+    if a.epsilon is None:
+        a.epsilon = 0.9 if tab else 1.0
+    if a.epsilon_discount is None:
+        a.epsilon_discount = 0.9986 if tab else 0.995
     if a.out is None:
         a.out = "runs/%s" % a.algo
     if a.max_steps is None:
-        a.max_steps = 250 if a.algo == "dqn" else 1000
-    if a.algo in ("dqn", "sac") and a.obs_layout is None:
+        a.max_steps = 250 if a.algo == "dqn" else 200 if tab else 1000
+    if (a.algo in ("dqn", "sac") or tab) and a.obs_layout is None:
         a.obs_layout = 1
-    if a.algo in ("dqn", "sac") and a.reset_mode != "next":
+    if (a.algo in ("dqn", "sac") or tab) and a.reset_mode != "next":
         ap.error("--algo %s collects with the next-step reset only (--reset-mode next)" % a.algo)
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
@@ -559,6 +670,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
+    if a.algo in TABULAR:
+        return train_tabular(a)
     if a.evaluate:
         return run_evaluation(a)
     if a.algo == "dqn":

@@ -29,11 +29,12 @@ build_lib() {   # $1 = output name, $2.. = extra flags
   "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -DCN_TU=5 -mllvm -disable-machine-licm -c -o "$T/k5.o" "$HERE/crowdnav_kernel.hip" & pids+=($!)
   "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/abi.o" "$HERE/crowdnav_abi.hip" & pids+=($!)
   "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/td3.o" "$HERE/crowdnav_td3.hip" & pids+=($!)
+  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/tab.o" "$HERE/crowdnav_tab.hip" & pids+=($!)
   local failed=0 pid
   for pid in "${pids[@]}"; do wait "$pid" || failed=1; done     # a bare `wait` returns 0 whatever the jobs returned
   if [ "$failed" != 0 ]; then echo "build.sh: a compile of $name failed" >&2; return 1; fi
   # link next to the target and rename: a process that already mapped the old file keeps it, nobody maps a partial one
-  "$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/.$name.$$" "$T/k1.o" "$T/k2.o" "$T/k3.o" "$T/k4.o" "$T/k5.o" "$T/abi.o" "$T/td3.o"
+  "$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/.$name.$$" "$T/k1.o" "$T/k2.o" "$T/k3.o" "$T/k4.o" "$T/k5.o" "$T/abi.o" "$T/td3.o" "$T/tab.o"
   mv -f "$OUT/.$name.$$" "$OUT/$name"
 }
 if [ "$WHAT" = "product" ] || [ "$WHAT" = "all" ]; then

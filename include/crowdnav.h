@@ -493,6 +493,77 @@ typedef struct cn_sac_act_io {
 } cn_sac_act_io;
 int cn_sac_act(const cn_sac_act_io* io, int device, void* stream);
 
+/* Q-learning and SARSA -- the reference's tabular learners (qlearn.py, sarsa.py; start_qlearn_training.py,
+ * start_sarsa_training.py) -- with ONE table shared by the n rows of a launch (crowdnav_tab.hip).
+ * State: the last two columns of the obs_layout-1 row (observation[-2], [-1]: round(x, 3), round(y, 3) of the robot,
+ * environment_stage_1_original.py:315-320) digitised as np.digitize does -- d = the number of distance edges <= column `col`
+ * (30 edges round(0.1 k, 2), d in 0..30), h = the number of radian edges <= column `col + 1` (32 edges
+ * round(-3.14 + 0.19625 k, 2), h in 0..32) -- and keyed by the STRING str(d) + str(h): 977 distinct keys, 46 of them shared by two
+ * pairs ((1, 10) and (11, 0) are both '110').  The handle numbers the keys 0..976 in order of first appearance for d ascending,
+ * then h ascending (state_of[31][33]).  The rows are float32 and are compared against the edges narrowed to float32: the two
+ * columns are multiples of 0.001 below 16 narrowed to float32, narrowing is monotone and keeps such multiples distinct, so the
+ * count equals np.digitize on the double.
+ * Table: q[977][3] float64 and present[977][3] bytes (the dict {(key, action): float}; an absent entry reads 0.0, an entry that
+ * holds 0.0 is present), count_same / count_diff (int64).  All on the device; cn_tab_set / cn_tab_get move the whole table.
+ * One launch, cn_tab_learn_act, for n rows:
+ *   1. learn (io.learn != 0), the bootstrap reads: every row reads the table AS IT STOOD WHEN THE LAUNCH BEGAN.
+ *        Q-learning: value = reward + gamma max_a Q(s2, a);   SARSA: a2 = chooseAction(s2) from u_learn, value = reward + gamma Q(s2, a2)
+ *      with s = state(obs_prev row), s2 = state(obs row), reward widened to double;
+ *   2. the writes, for the rows with keep[i] != 0 (keep NULL = all) and 0 <= action_prev[i] <= 2, PER CELL (s, action_prev) IN
+ *      ASCENDING ROW ORDER, by learnQ's rule: a cell absent at that moment becomes (double)reward, present, count_same += 1;
+ *      otherwise q = q + alpha (value - q), count_diff += 1.  Rows of different cells do not interact;
+ *   3. act (io.act != 0): chooseAction(state(obs row)) from u_act on the table AFTER all writes -> action, twist.
+ * For n = 1 this is the reference's loop statement for statement.  Arithmetic: float64, every product, sum and difference
+ * rounded on its own (no FMA).  max / min keep the first of equal values, as Python's.
+ * chooseAction, draws u[0..4] of the row (a slot always means the same draw, consumed or not):
+ *   SARSA (sarsa.py:39-55): u[0] < epsilon -> action int(u[1] * 3); else the argmax, several maxima -> best[int(u[4] * count)];
+ *   Q-learning (qlearn.py:47-72): u[0] < epsilon -> mag = max(|min q|, |max q|), q[i] = (q[i] + u[1 + i] * mag) - .5 * mag, the
+ *   maximum again; then the argmax with the same tie break.  (random.choice(seq) = seq[int(random() * len(seq))], Python 2.)
+ * u_learn / u_act [n][5] float64, or NULL = drawn on the device: u[j] = (x >> 11) * 2^-53 with
+ *   x = mix64(mix64(mix64(seed ^ mix64(counter ^ C)) ^ row) ^ j), mix64 = splitmix64's finaliser,
+ *   C = 0x6a09e667f3bcc909 for u_learn, 0xbb67ae8584caa73b for u_act.
+ * epsilon / epsilon_discount / epsilon_min / episodes_dev: as cn_dqn_act_io (the schedule of start_sarsa_training.py:51-52).
+ * Outputs: action [n] and twist [n][2] (act; the twists of cn_dqn_act), optional state [n], state_prev [n] (0..976), q_row [n][3]
+ * (the row chooseAction ended with, Q-learning's noise included; SARSA's random branch: the plain row).  `done` is not read by the
+ * arithmetic (the reference learns from a terminal transition like any other).
+ * One workgroup; enqueue-only, no host read, capturable into a hipGraph on one stream.  Errors through cn_tab_last_error. */
+#define CN_TAB_STATES 977
+#define CN_TAB_ACTIONS 3
+enum { CN_TAB_QLEARN = 0, CN_TAB_SARSA = 1 };
+typedef struct cn_tab_config {
+    int32_t algo;            /* CN_TAB_QLEARN | CN_TAB_SARSA */
+    int32_t reserved;
+    double alpha, gamma;     /* qlearn.yaml / sarsa.yaml -> 0.2, 0.9 */
+    uint64_t seed;           /* keys the device draws with io.counter */
+} cn_tab_config;
+typedef struct cn_tab_s* cn_tab_handle;
+int cn_tab_create(const cn_tab_config* cfg, int device, cn_tab_handle* out);      /* an empty table, counters 0 */
+void cn_tab_destroy(cn_tab_handle h);
+/* Host arrays q [977][3] float64, present [977][3] bytes, counts [2] int64 = {count_same, count_diff} (NULL: set zeroes them, get
+ * skips them).  Both wait for the device's queued work; a q value whose present byte is 0 is stored as 0.0. */
+int cn_tab_set(cn_tab_handle h, const double* q_host, const uint8_t* present_host, const int64_t* counts_host);
+int cn_tab_get(cn_tab_handle h, double* q_host, uint8_t* present_host, int64_t* counts_host);
+/* Host copies [31][33] int32, [30] and [32] float64 of the handle's key table and edges (any may be NULL). */
+int cn_tab_tables(cn_tab_handle h, int32_t* state_of_host, double* distance_bins_host, double* radian_bins_host);
+typedef struct cn_tab_io {
+    const float* obs_prev;   /* [n] rows, row stride obs_ld; read when learn != 0 */
+    const float* obs;        /* [n] rows: s2 of the learn phase, the state of the act phase */
+    int64_t obs_ld;
+    int32_t n, col;          /* columns col, col + 1 are read (the env's 363-wide row: col = 361) */
+    int32_t learn, act;
+    const int32_t* action_prev; const float* reward;   /* [n]; read when learn != 0 */
+    const uint8_t* done;     /* [n] or NULL; not read */
+    const uint8_t* keep;     /* [n] or NULL = all rows */
+    double epsilon, epsilon_discount, epsilon_min;     /* epsilon_min > 0 */
+    const int64_t* episodes_dev;
+    const double *u_learn, *u_act;                     /* [n][5] or NULL */
+    uint64_t counter;
+    int32_t* action; float* twist;                     /* [n], [n][2]; written when act != 0 */
+    int32_t *state, *state_prev; double* q_row;        /* optional: [n], [n] (learn != 0), [n][3] (act != 0) */
+} cn_tab_io;
+int cn_tab_learn_act(cn_tab_handle h, const cn_tab_io* io, void* stream);
+const char* cn_tab_last_error(void);
+
 /* The collection loop's bookkeeping between Env.step and Agent.learn (start_td3_training.py:129-149) for a batch of environments,
  * without a host read: ReplayBuffer.add (td3.py:24-31) into a ring on the device, and the per-episode record TRAIN:139-149 prints
  * and utils.record_data writes.  (crowdnav.td3.DeviceReplay and crowdnav.train.DeviceEpisodeLog do the same through ~35 PyTorch
