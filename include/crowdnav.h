@@ -502,7 +502,8 @@ int cn_sac_act(const cn_sac_act_io* io, int device, void* stream);
  * pairs ((1, 10) and (11, 0) are both '110').  The handle numbers the keys 0..976 in order of first appearance for d ascending,
  * then h ascending (state_of[31][33]).  The rows are float32 and are compared against the edges narrowed to float32: the two
  * columns are multiples of 0.001 below 16 narrowed to float32, narrowing is monotone and keeps such multiples distinct, so the
- * count equals np.digitize on the double.
+ * count equals np.digitize on the double.  That is the whole domain: an observation that is NaN, or of magnitude 16 and above, is
+ * outside it, and what it is digitised to is not specified (the state index stays within 0..976 all the same: a count of edges).
  * Table: q[977][3] float64 and present[977][3] bytes (the dict {(key, action): float}; an absent entry reads 0.0, an entry that
  * holds 0.0 is present), count_same / count_diff (int64).  All on the device; cn_tab_set / cn_tab_get move the whole table.
  * One launch, cn_tab_learn_act, for n rows:
@@ -524,7 +525,8 @@ int cn_sac_act(const cn_sac_act_io* io, int device, void* stream);
  *   C = 0x6a09e667f3bcc909 for u_learn, 0xbb67ae8584caa73b for u_act.
  * epsilon / epsilon_discount / epsilon_min / episodes_dev: as cn_dqn_act_io (the schedule of start_sarsa_training.py:51-52).
  * Outputs: action [n] and twist [n][2] (act; the twists of cn_dqn_act), optional state [n], state_prev [n] (0..976), q_row [n][3]
- * (the row chooseAction ended with, Q-learning's noise included; SARSA's random branch: the plain row).  `done` is not read by the
+ * (the row chooseAction ended with, Q-learning's noise included; SARSA's random branch: the plain row).  state_prev is written for
+ * every row of a learning launch, also one that keep or an action_prev outside 0..2 leaves unwritten.  `done` is not read by the
  * arithmetic (the reference learns from a terminal transition like any other).
  * One workgroup; enqueue-only, no host read, capturable into a hipGraph on one stream.  Errors through cn_tab_last_error. */
 #define CN_TAB_STATES 977

@@ -1,7 +1,8 @@
 """cn_tab_learn_act (csrc/crowdnav_tab.hip) on the GPU: the reference's sequences at n = 1, the order of reads and writes at one
 wavefront, a chunk edge and two chunks plus a tail, chooseAction's branches, the documented device draw, the fused agent against its
-PyTorch path on a VecEnv, the trainer, and a hipGraph.  The expectation is `Ref` below: a Python loop written from the rules in
-include/crowdnav.h, on a dict as the reference's, that does not call crowdnav.tabular.  Every comparison is equality."""
+PyTorch path on a VecEnv, the trainer, and a hipGraph.  The expectation is `Ref` of tests/tabular_ref.py: a Python loop written from
+the rules in include/crowdnav.h, on a dict as the reference's, that does not call crowdnav.tabular.  Every comparison is equality.
+(The tile seam, single-wavefront cells, the action range, all 1023 pairs, the epsilon memo and the refusals: test_gpu_tabular_edges.py.)"""
 import os
 
 import numpy as np
@@ -12,8 +13,6 @@ from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-ALPHA, GAMMA = 0.2, 0.9
-M64 = 0xFFFFFFFFFFFFFFFF
 
 
 @pytest.fixture(scope="module")
@@ -21,81 +20,8 @@ def G():
     return np.load(os.path.join(GOLDEN, "tabular.npz"))
 
 
-# ---- the restatement ---------------------------------------------------------------------------------------------------------
-DIST = [round(i, 2) for i in np.arange(0, 3, 0.1)]
-RAD = [round(i, 2) for i in np.arange(-3.14, 3.14, 0.19625)]
-
-
-def _state_table():
-    seen, tab = {}, {}
-    for d in range(31):
-        for h in range(33):
-            tab[(d, h)] = seen.setdefault(str(d) + str(h), len(seen))
-    return tab
-
-
-STATE = _state_table()
-
-
-def states_of(obs64):
-    """State indices of double observations [n, 2]: np.digitize on the doubles, the string key, its number."""
-    return [STATE[(int(np.digitize([x], DIST)[0]), int(np.digitize([y], RAD)[0]))] for x, y in obs64]
-
-
-def obs_at(d, h):
-    """A multiple of 0.001 inside bin (d, h)."""
-    x = round(0.1 * d - 0.05, 3)
-    y = -3.2 if h == 0 else 3.0 if h == 32 else round((RAD[h - 1] + RAD[h]) / 2, 3)
-    assert int(np.digitize([x], DIST)[0]) == d and int(np.digitize([y], RAD)[0]) == h
-    return (x, y)
-
-
-class Ref:
-    def __init__(self, sarsa, alpha=ALPHA, gamma=GAMMA, live_reads=False):
-        self.sarsa, self.alpha, self.gamma, self.live = sarsa, alpha, gamma, live_reads
-        self.q, self.same, self.diff = {}, 0, 0
-
-    def choose(self, q, s, u, eps):
-        row = [q.get((s, a), 0.0) for a in range(3)]
-        u = [float(x) for x in u]
-        if self.sarsa:
-            if u[0] < eps:
-                return int(u[1] * 3), row
-        elif u[0] < eps:
-            mag = max(abs(min(row)), abs(max(row)))
-            row = [row[i] + u[1 + i] * mag - .5 * mag for i in range(3)]
-        mx = max(row)
-        if row.count(mx) > 1:
-            best = [i for i in range(3) if row[i] == mx]
-            return best[int(u[4] * len(best))], row
-        return row.index(mx), row
-
-    def launch(self, s1, a1, r, s2, keep=None, u_learn=None, u_act=None, eps=0.0, learn=True, act=True):
-        n = len(s2)
-        if learn:
-            old = self.q if self.live else dict(self.q)           # 1. bootstrap reads: the table as the launch began
-            for i in range(n):                                     # 2. writes, ascending rows (live_reads interleaves: the WRONG order)
-                if self.sarsa:
-                    a2, _ = self.choose(old, s2[i], u_learn[i], eps)
-                    boot = old.get((s2[i], a2), 0.0)
-                else:
-                    boot = max(old.get((s2[i], a), 0.0) for a in range(3))
-                value = float(r[i]) + self.gamma * boot
-                if keep is not None and not keep[i]:
-                    continue
-                k = (s1[i], int(a1[i]))
-                if k not in self.q:
-                    self.q[k] = float(r[i]); self.same += 1
-                else:
-                    self.q[k] = self.q[k] + self.alpha * (value - self.q[k]); self.diff += 1
-        out = [self.choose(self.q, s2[i], u_act[i], eps) for i in range(n)] if act else []       # 3. act: after all writes
-        return [o[0] for o in out], [o[1] for o in out]
-
-    def arrays(self):
-        q, p = np.zeros((977, 3)), np.zeros((977, 3), dtype=bool)
-        for (s, a), v in self.q.items():
-            q[s, a] = v; p[s, a] = True
-        return q, p
+# ---- the restatement: tests/tabular_ref.py ---------------------------------------------------------------------------------------
+from tabular_ref import ALPHA, GAMMA, Ref, _draws, _mix, _state_table, obs_at, states_of  # noqa: E402,F401
 
 
 def _agent(sarsa, **kw):
@@ -316,18 +242,6 @@ def test_epsilon_schedule_on_the_device(sarsa):
 
 
 # ---- the device draw ---------------------------------------------------------------------------------------------------------
-def _mix(z):
-    z = (z + 0x9E3779B97F4A7C15) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    return z ^ (z >> 31)
-
-
-def _draws(seed, counter, n, const):
-    base = _mix(seed ^ _mix(counter ^ const))
-    return np.array([[(_mix(_mix(base ^ i) ^ j) >> 11) * 2.0 ** -53 for j in range(5)] for i in range(n)])
-
-
 @pytest.mark.parametrize("sarsa", [False, True])
 def test_device_draw_is_the_documented_hash(sarsa):
     n, rng = 130, np.random.default_rng(9)
