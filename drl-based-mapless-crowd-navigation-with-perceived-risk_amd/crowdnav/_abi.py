@@ -38,7 +38,18 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_dqn_create", "cn_dqn_destroy", "cn_dqn_update", "cn_dqn_loss_dev", "cn_dqn_batch_dev", "cn_dqn_act",
            "cn_sac_create", "cn_sac_destroy", "cn_sac_update", "cn_sac_loss_dev", "cn_sac_batch_dev", "cn_sac_act",
            "cn_tab_create", "cn_tab_destroy", "cn_tab_set", "cn_tab_get", "cn_tab_tables", "cn_tab_learn_act", "cn_tab_last_error",
-           "cn_replay_write", "cn_episode_log_add"]
+           "cn_td3_set_replay_sample", "cn_ddpg_set_replay_sample", "cn_dqn_set_replay_sample", "cn_sac_set_replay_sample",
+           "cn_replay_sample_indices", "cn_replay_write", "cn_episode_log_add"]
+CN_SAMPLE_WITH_REPLACEMENT, CN_SAMPLE_DISTINCT = 0, 1      # include/crowdnav.h: cn_*_set_replay_sample
+REPLAY_SAMPLE = {"with": CN_SAMPLE_WITH_REPLACEMENT, "without": CN_SAMPLE_DISTINCT}
+
+
+def replay_sample_mode(name):
+    """"with" | "without" -> CN_SAMPLE_*; anything else is a ValueError."""
+    try:
+        return REPLAY_SAMPLE[name]
+    except (KeyError, TypeError):
+        raise ValueError("replay_sample must be 'with' or 'without', not %r" % (name,))
 
 
 class CnStepIO(C.Structure):
@@ -353,6 +364,9 @@ def lib():
         L.cn_tab_tables.argtypes = [vp, vp, vp, vp]
         L.cn_tab_learn_act.argtypes = [vp, C.POINTER(CnTabIO), vp]
         L.cn_tab_last_error.restype = C.c_char_p
+        for fam in ("td3", "ddpg", "dqn", "sac"):
+            getattr(L, "cn_%s_set_replay_sample" % fam).argtypes = [vp, C.c_int]
+        L.cn_replay_sample_indices.argtypes = [C.c_uint64, C.c_uint64, C.c_int, vp, C.c_int, vp, C.c_int, vp]
         L.cn_replay_write.argtypes = [C.POINTER(CnReplayRing), vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp]
         L.cn_episode_log_add.argtypes = [C.POINTER(CnEpisodeLog), vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, C.c_int, vp]
         _lib = L

@@ -1,4 +1,4 @@
-"""What the TD3, DDPG and DQN agents share on the way to libcrowdnav's fused learners (csrc/crowdnav_td3.hip): the network
+"""What the TD3, DDPG, DQN and SAC agents share on the way to libcrowdnav's fused learners (csrc/crowdnav_td3.hip): the network
 pointers, views of the library's device memory, and the owner of a learner handle."""
 import ctypes as C
 
@@ -30,13 +30,17 @@ class FusedLearner:
     """Owns one learner handle of libcrowdnav: family = "td3", "ddpg" or "dqn" names cn_<family>_create / _update / _destroy /
     _loss_dev / _batch_dev.  An error raises CrowdNavError("<function>: <cn_td3_last_error>")."""
 
-    def __init__(self, family, cfg, device, dev_index, loss_shape=()):
+    def __init__(self, family, cfg, device, dev_index, loss_shape=(), replay_sample="with"):
+        mode = _abi.replay_sample_mode(replay_sample)
         self._L = L = _abi.lib()
         self.family, self.cfg, self.device = family, cfg, device
         self.h = C.c_void_p()
         self._check("create", self._fn("create")(C.byref(cfg), dev_index, C.byref(self.h)))
         self._loss = _device_view(self._fn("loss_dev")(self.h), loss_shape, torch.float32, device)
         self._keep, self._update = None, self._fn("update")
+        self.replay_sample = "with"               # a fresh handle's mode
+        if mode != _abi.CN_SAMPLE_WITH_REPLACEMENT:
+            self.set_replay_sample(replay_sample)
 
     def _fn(self, what):
         return getattr(self._L, "cn_%s_%s" % (self.family, what))
@@ -56,6 +60,12 @@ class FusedLearner:
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         self._check("update", self._update(self.h, *args, C.byref(batch) if batch is not None else None, st))
         return self._loss.clone()
+
+    def set_replay_sample(self, replay_sample):
+        """cn_<family>_set_replay_sample: "with" (replacement, the default) or "without" (distinct rows, as the reference's
+        random.sample) for the updates enqueued from now on; a captured update keeps the mode it was captured with."""
+        self._check("set_replay_sample", self._fn("set_replay_sample")(self.h, _abi.replay_sample_mode(replay_sample)))
+        self.replay_sample = replay_sample
 
     def batch_dev(self, what, shape, dtype=torch.float32):
         """A view of what the last update gathered or computed (cn_<family>_batch_dev), valid until the next update."""

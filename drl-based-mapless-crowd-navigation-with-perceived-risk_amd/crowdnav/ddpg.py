@@ -58,7 +58,11 @@ class Agent(FusedActorMixin):
     """DDPG agent (DDPG:112-272) acting on batches of observations that stay on the device."""
 
     def __init__(self, obs_dim=363, hidden=256, actor_lr=1e-4, critic_lr=1e-3, batch_size=64, memory_size=1_000_000,
-                 gamma=0.99, tau=0.001, max_v=0.22, max_w=2.0, explore_sigma=0.0, n_envs=1, device="cuda", seed=0):
+                 gamma=0.99, tau=0.001, max_v=0.22, max_w=2.0, explore_sigma=0.0, n_envs=1, device="cuda", seed=0,
+                 replay_sample="with"):
+        from . import _abi
+        _abi.replay_sample_mode(replay_sample)      # "with" (replacement) | "without" (distinct rows, ddpg.py:33-34's random.sample)
+        self.replay_sample = replay_sample
         self.device = torch.device(device)
         torch.manual_seed(seed)
 
@@ -131,7 +135,7 @@ class Agent(FusedActorMixin):
                                 beta1=og["betas"][0], beta2=og["betas"][1], eps=og["eps"], max_v=self.max_v, max_w=self.max_w,
                                 actor=mlp_of(self.actor), actor_t=mlp_of(self.actor_t), critic=mlp_of(self.critic),
                                 critic_t=mlp_of(self.critic_t), seed=self._noise_seed, **self.memory.ring_fields())
-        self._fused = FusedLearner("ddpg", cfg, self.device, self._dev_index)
+        self._fused = FusedLearner("ddpg", cfg, self.device, self._dev_index, replay_sample=self.replay_sample)
 
     def _fused_learn(self, batch=None):
         from . import _abi
@@ -154,7 +158,7 @@ class Agent(FusedActorMixin):
         if getattr(self, "_fused", None):
             return self._fused_learn(batch)
         if batch is None:
-            batch = self.memory.sample(self.batch_size)
+            batch = self.memory.sample(self.batch_size, replace=self.replay_sample == "with")
         s, a, r, s2, d = batch
         return self._update(s, a, r.reshape(-1, 1), s2, d.reshape(-1, 1))
 

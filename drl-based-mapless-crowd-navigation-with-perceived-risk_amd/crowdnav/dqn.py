@@ -13,8 +13,8 @@ What it keeps from the reference:
   shuffles the 64 + F rows and takes one RMSprop step on the first 64 and, when F > 0, a second on the other F, against the same Y;
 - selectAction (deepq.py:178-184): with probability epsilon a uniform index, else argmax with ties to the lowest index; the index
   maps to the twists of environment_stage_1_original.py:412-425; epsilon *= 0.995 at the start of every episode while > 0.05.
-Replay: td3.DeviceReplay with the action index in column 0 of its action rows; sampling with replacement (the reference samples
-without replacement, memory.py:23)."""
+Replay: td3.DeviceReplay with the action index in column 0 of its action rows; sampling with replacement by default,
+replay_sample="without" draws distinct rows as the reference's random.sample does (memory.py:23)."""
 import json
 import math
 import os
@@ -63,7 +63,10 @@ class Agent:
 
     def __init__(self, obs_dim=361, obs_ld=None, hidden=(300, 300), n_actions=3, batch_size=64, learn_start=64, gamma=0.99,
                  lr=2.5e-4, rho=0.9, eps=1e-6, target_update=10000, memory_size=1_000_000, epsilon=1.0, epsilon_discount=0.995,
-                 epsilon_min=0.05, device="cuda", seed=0):
+                 epsilon_min=0.05, device="cuda", seed=0, replay_sample="with"):
+        from . import _abi
+        _abi.replay_sample_mode(replay_sample)      # "with" (replacement) | "without" (distinct rows, memory.py:23's random.sample)
+        self.replay_sample = replay_sample
         self.device = torch.device(device)
         torch.manual_seed(seed)
         self.obs_dim = int(obs_dim)
@@ -201,7 +204,7 @@ class Agent:
                                gamma=self.gamma, lr=self.lr, rho=self.rho, eps=self.eps, target_every=self.target_update,
                                learn_start=self.learn_start, q=mlp_of(self.q), q_t=mlp_of(self.q_t), seed=self._replay_seed,
                                **self.memory.ring_fields())
-        self._fused = FusedLearner("dqn", cfg, self.device, self._dev_index, loss_shape=(2,))
+        self._fused = FusedLearner("dqn", cfg, self.device, self._dev_index, loss_shape=(2,), replay_sample=self.replay_sample)
 
     def _fused_learn(self, batch=None, perm=None):
         from . import _abi
@@ -237,7 +240,7 @@ class Agent:
         if getattr(self, "_fused", None):
             return self._fused_learn(batch, perm)
         if batch is None:
-            s, a2, r, s2, d = self.memory.sample(self.batch_size)
+            s, a2, r, s2, d = self.memory.sample(self.batch_size, replace=self.replay_sample == "with")
             batch = (s, a2[:, 0].round().long(), r, s2, d)
         return self._update(*batch, perm=perm)
 

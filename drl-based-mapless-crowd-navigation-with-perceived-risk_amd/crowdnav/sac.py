@@ -87,7 +87,11 @@ class Agent:
 
     def __init__(self, obs_dim=363, hidden=256, actor_lr=3e-4, v_lr=3e-4, q_lr=3e-4, batch_size=64, memory_size=1_000_000,
                  gamma=0.99, tau=5e-3, max_v=0.22, max_w=2.0, mean_lambda=1e-3, std_lambda=1e-3, z_lambda=0.0,
-                 value_net="as_written", soft_update="as_written", deterministic=False, n_envs=1, device="cuda", seed=0):
+                 value_net="as_written", soft_update="as_written", deterministic=False, n_envs=1, device="cuda", seed=0,
+                 replay_sample="with"):
+        from . import _abi
+        _abi.replay_sample_mode(replay_sample)      # "with" (replacement) | "without" (distinct rows, sac.py:34-35's random.sample)
+        self.replay_sample = replay_sample
         if value_net not in ("as_written", "intended") or soft_update not in ("as_written", "intended"):
             raise ValueError("value_net / soft_update: 'as_written' or 'intended'")
         self.device = torch.device(device)
@@ -210,7 +214,7 @@ class Agent:
                                soft_update=0 if self.soft_update == "as_written" else 1, reserved=0,
                                actor=self.actor_struct(), q=mlp_of(self.q), v=mlp_of(self.v), v_t=mlp_of(self.v_t),
                                seed=self._act_seed ^ 0x5851F42D4C957F2D, **self.memory.ring_fields())
-        self._fused = FusedLearner("sac", cfg, self.device, self._dev_index, loss_shape=(3,))
+        self._fused = FusedLearner("sac", cfg, self.device, self._dev_index, loss_shape=(3,), replay_sample=self.replay_sample)
 
     def _fused_learn(self, batch=None, noise=None):
         from . import _abi
@@ -245,7 +249,7 @@ class Agent:
         if getattr(self, "_fused", None):
             return self._fused_learn(batch, noise)
         if batch is None:
-            batch = self.memory.sample(self.batch_size)
+            batch = self.memory.sample(self.batch_size, replace=self.replay_sample == "with")
         s, a, r, s2, d = batch
         if noise is None:
             torch.randn((s.shape[0], 2), device=s.device)                    # forward()'s sample, thrown away (SAC:74, 79)

@@ -75,6 +75,9 @@ class DeviceReplay:
         self.size_dev = torch.zeros((), dtype=torch.int64, device=device)
         self._lb, self._ub = 0, 0
         self._ar = None
+        # sample(replace=False): the key of cn_replay_sample_indices and the number of such samples drawn so far
+        self.sample_seed = (0xD6E8FEB86659FD93 * (self.cap + 1) ^ 0x2545F4914F6CDD1D) & 0xFFFFFFFFFFFFFFFF
+        self.sample_calls = 0
 
     def add(self, s, a, r, s2, d):
         """ReplayBuffer.add for a batch of transitions (all rows kept).  Same device-side path as add_masked()."""
@@ -158,8 +161,35 @@ class DeviceReplay:
     def pos(self):
         return int(self.pos_dev.item())
 
-    def sample(self, batch):
-        """Uniform sample of the filled part; the indices are drawn on the device from the device-side fill level."""
+    def sample_indices(self, batch, seed=None, counter=None, mode=1):
+        """cn_replay_sample_indices: the ring rows [batch] (int64, on the device) that a fused update keyed (seed, counter) draws
+        in `mode` (1 = distinct rows) from the fill level as it stands on the device when the launch runs.  seed / counter None =
+        this buffer's own (`sample_seed`, and `sample_calls`, which then advances).  One launch, no host read."""
+        import ctypes as C
+        from . import _abi
+        dev = self.s.device
+        if dev.type != "cuda":
+            raise RuntimeError("sampling without replacement is libcrowdnav's cn_replay_sample_indices: it needs a HIP device")
+        if counter is None:
+            counter, self.sample_calls = self.sample_calls, self.sample_calls + 1
+        L = _abi.lib()
+        idx = torch.empty(int(batch), dtype=torch.int64, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = L.cn_replay_sample_indices(self.sample_seed if seed is None else int(seed), int(counter), int(batch),
+                                        C.c_void_p(self.size_dev.data_ptr()), int(mode), C.c_void_p(idx.data_ptr()),
+                                        dev.index if dev.index is not None else torch.cuda.current_device(), st)
+        if rc != 0:
+            raise _abi.CrowdNavError("cn_replay_sample_indices: %s" % L.cn_td3_last_error().decode())
+        return idx
+
+    def sample(self, batch, replace=True):
+        """Uniform sample of the filled part; the indices are drawn on the device from the device-side fill level.  replace=False:
+        `batch` distinct rows, as the reference's random.sample (td3.py:31-32) -- a keyed bijection of the filled part evaluated at
+        0 .. batch-1 (include/crowdnav.h, cn_td3_batch_dev), O(batch) work and no host read; with batch > len() every row comes
+        up floor or ceil(batch / len()) times instead of the reference's ValueError (callers gate on ready(batch))."""
+        if not replace:
+            idx = self.sample_indices(batch)
+            return self.s[idx], self.a[idx], self.r[idx], self.s2[idx], self.d[idx]
         u = torch.rand(batch, device=self.s.device)
         idx = (u * self.size_dev.clamp(min=1).to(torch.float32)).long().clamp_(max=self.cap - 1)
         idx = torch.minimum(idx, (self.size_dev - 1).clamp(min=0))
@@ -304,7 +334,10 @@ class Agent(FusedActorMixin):
 
     def __init__(self, obs_dim=398, hidden=256, actor_lr=3e-4, critic_lr=3e-4, batch_size=128, memory_size=1_000_000,
                  gamma=0.99, tau=0.005, max_v=0.22, max_w=2.0, noise_std=0.2, noise_clip=0.5, policy_delay=2,
-                 explore_sigma=1.0, device="cuda", seed=0, actor_final_init=None):
+                 explore_sigma=1.0, device="cuda", seed=0, actor_final_init=None, replay_sample="with"):
+        from . import _abi
+        _abi.replay_sample_mode(replay_sample)      # "with" (replacement) | "without" (distinct rows, the reference's random.sample)
+        self.replay_sample = replay_sample
         self.device = torch.device(device)
         torch.manual_seed(seed)
         self.actor = Actor(obs_dim, 2, hidden, max_v, max_w).to(self.device)
@@ -375,6 +408,9 @@ class Agent(FusedActorMixin):
             raise RuntimeError("enable_graphs needs a HIP device")
         if getattr(self, "_graphs", None):
             return
+        if self.replay_sample != "with":
+            raise RuntimeError("the captured PyTorch update draws its own indices with replacement; replay_sample='without' runs "
+                               "eagerly or through enable_fused_update()")
         B, dev = self.batch_size, self.device
         nets = (self.actor, self.actor_t, self.q1, self.q1_t, self.q2, self.q2_t)
         saved = [[p.detach().clone() for p in m.parameters()] for m in nets]
@@ -440,7 +476,7 @@ class Agent(FusedActorMixin):
                                noise_std=self.noise_std, noise_clip=self.noise_clip, max_v=self.max_v, max_w=self.max_w, reserved=0.0,
                                actor=mlp_of(self.actor), actor_t=mlp_of(self.actor_t), q1=mlp_of(self.q1), q1_t=mlp_of(self.q1_t),
                                q2=mlp_of(self.q2), q2_t=mlp_of(self.q2_t), seed=self._noise_seed, **self.memory.ring_fields())
-        self._fused = FusedLearner("td3", cfg, self.device, self._dev_index)
+        self._fused = FusedLearner("td3", cfg, self.device, self._dev_index, replay_sample=self.replay_sample)
 
     def _fused_learn(self, step, batch=None, target_noise=None):
         from . import _abi
@@ -478,7 +514,7 @@ class Agent(FusedActorMixin):
                 do_actor = step % self.policy_delay == 0
                 self._graphs[do_actor].replay()
                 return self._g_loss[do_actor]
-            batch = self.memory.sample(self.batch_size)
+            batch = self.memory.sample(self.batch_size, replace=self.replay_sample == "with")
         s, a, r, s2, d = batch
         if target_noise is None:
             target_noise = torch.randn(a.shape, generator=self.gen, device=self.device)

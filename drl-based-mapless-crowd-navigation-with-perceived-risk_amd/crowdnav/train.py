@@ -174,7 +174,8 @@ def make_dqn_agent(a, obs_ld, device, memory_size):
     if a.dqn_inputs > obs_ld:
         raise ValueError("--dqn-inputs %d > the observation width %d (use --obs-layout 1)" % (a.dqn_inputs, obs_ld))
     return dqn.Agent(obs_dim=a.dqn_inputs, obs_ld=obs_ld, batch_size=a.batch or 64, memory_size=memory_size, epsilon=a.epsilon,
-                     epsilon_discount=a.epsilon_discount, target_update=a.target_update, device=device, seed=a.seed)
+                     epsilon_discount=a.epsilon_discount, target_update=a.target_update, device=device, seed=a.seed,
+                     replay_sample=getattr(a, "replay_sample", "with"))
 
 
 def save_dqn_checkpoint(agent, a, outdir, episodes):
@@ -421,6 +422,7 @@ def make_agent(a, obs_dim, device, **kw):
     over = {k: v for k, v in (("batch_size", getattr(a, "batch", None)), ("actor_lr", getattr(a, "lr_actor", None)),
                               ("critic_lr", getattr(a, "lr_critic", None)), ("tau", getattr(a, "tau", None))) if v is not None}
     over.update(kw)
+    over["replay_sample"] = getattr(a, "replay_sample", "with")
     if getattr(a, "algo", "td3") == "sac":
         over = {dict(critic_lr="q_lr").get(k, k): v for k, v in over.items()}
         if "q_lr" in over:
@@ -617,6 +619,9 @@ def parse_args(argv=None):
     ap.add_argument("--obs-layout", type=int, default=None, choices=[0, 1, 2], help="cn_config.obs_layout: 0 = 366 + 4K inputs (default); "
                     "1 = environment_stage_1_original's 363 (the shipped DDPG checkpoints); 2 = 370")
     ap.add_argument("--memory", type=int, default=1_000_000, help="TRAIN:63 (not qlearn / sarsa: no replay)")
+    ap.add_argument("--replay-sample", default="with", choices=["with", "without"], help="how an update draws its mini-batch from the replay: "
+                    "with replacement (default), or without -- distinct rows, as the reference's random.sample (td3.py:31-32, ddpg.py:33-34, "
+                    "sac.py:34-35, memory.py:23); not qlearn / sarsa (no replay), and with --algo td3 --learner torch it needs --graphs 0")
     ap.add_argument("--checkpoint-every", type=int, default=100000, help="episodes between checkpoints (TRAIN:150: 100); checked at log time")
     ap.add_argument("--log-every", type=int, default=100)
     ap.add_argument("--ped-vmax", type=float, default=None, help="training world only: walker speed bound (CROWD:101 -> 0.2)")
@@ -646,11 +651,11 @@ def parse_args(argv=None):
     tab = a.algo in TABULAR
     if tab:           # flags of the replay learners: rejected when given, whatever their value
         probe = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
-        for flag in ("--updates", "--memory", "--batch", "--graphs"):
+        for flag in ("--updates", "--memory", "--batch", "--graphs", "--replay-sample"):
             probe.add_argument(flag, default=None)
         given = [k for k, v in vars(probe.parse_known_args(argv)[0]).items() if v is not None]
         if given:
-            ap.error("--algo %s has no replay, batch or update count: %s do(es) not apply" % (a.algo, ", ".join("--" + g for g in given)))
+            ap.error("--algo %s has no replay, batch or update count: %s do(es) not apply" % (a.algo, ", ".join("--" + g.replace("_", "-") for g in given)))
     if a.epsilon is None:
         a.epsilon = 0.9 if tab else 1.0
     if a.epsilon_discount is None:
@@ -663,6 +668,8 @@ def parse_args(argv=None):
         a.obs_layout = 1
     if (a.algo in ("dqn", "sac") or tab) and a.reset_mode != "next":
         ap.error("--algo %s collects with the next-step reset only (--reset-mode next)" % a.algo)
+    if a.replay_sample == "without" and a.algo == "td3" and a.learner == "torch" and a.graphs and not a.evaluate:
+        ap.error("--replay-sample without: the captured PyTorch TD3 update draws its own indices with replacement; use --learner fused or --graphs 0")
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     return a

@@ -559,6 +559,44 @@ __global__ void __launch_bounds__(256) td3_wgrad_kernel(GemmArgs args)
 
 
 // ---- small kernels ------------------------------------------------------------------------------------------------------
+// Replay sampling WITHOUT replacement (CN_SAMPLE_DISTINCT; the statement is in include/crowdnav.h next to cn_td3_batch_dev): row m of
+// update `cnt` is a keyed bijection of [0, n) evaluated at m mod n -- a four-round Feistel network on Z_a x Z_b (a = ceil(sqrt n),
+// b = ceil(n / a)), walked along its cycle until it lands below n.  Nothing here depends on another row, and with a workgroup-uniform
+// m every value is uniform.  Sums are exact: (L + h) mod a is taken as (L + h mod a) mod a, never wrapped at 2^64 first (a wrapped
+// sum would not be a rotation of Z_a).  n >= 1; a <= 3037000500, so t * t, a * b and L * b + R stay below 2^64.
+__device__ __forceinline__ uint64_t cn_replay_row_distinct(uint64_t seed, uint64_t cnt, uint64_t m, uint64_t n)
+{
+    uint64_t r = 0;                                // floor(sqrt(n - 1)), bit by bit: a = r + 1 is the least integer with a * a >= n
+    for (uint64_t bit = 1ull << 31; bit; bit >>= 1) { const uint64_t t = r | bit; if (t * t <= n - 1) r = t; }
+    const uint64_t a = r + 1, b = (n + a - 1) / a;
+    const uint64_t K = cn_mix64(seed ^ cn_mix64(cnt ^ 0x9E3779B97F4A7C15ull));
+    const uint64_t k0 = cn_mix64(K ^ 1ull), k1 = cn_mix64(K ^ 2ull), k2 = cn_mix64(K ^ 3ull), k3 = cn_mix64(K ^ 4ull);
+    uint64_t x = m % n;
+    for (int pass = 0; pass < 64; ++pass) {
+        uint64_t L = x / b, R = x % b;
+        L += cn_mix64(k0 ^ R) % a; if (L >= a) L -= a;
+        R += cn_mix64(k1 ^ L) % b; if (R >= b) R -= b;
+        L += cn_mix64(k2 ^ R) % a; if (L >= a) L -= a;
+        R += cn_mix64(k3 ^ L) % b; if (R >= b) R -= b;
+        x = L * b + R;
+        if (x < n) return x;
+    }
+    return x % n;                                  // (never expected: a pass lands at or above n with probability <= 1/4)
+}
+// ring row of batch row m of update `cnt`: the draw with replacement, or the bijection above (mode: the handle's, CN_SAMPLE_*)
+__device__ __forceinline__ size_t cn_replay_row(uint64_t seed, unsigned long long cnt, int m, const int64_t* size_dev, int mode)
+{
+    const unsigned long long size = (unsigned long long)(*size_dev > 0 ? *size_dev : 1);
+    if (mode == CN_SAMPLE_DISTINCT) return (size_t)cn_replay_row_distinct(seed, cnt, (uint64_t)(uint32_t)m, size);
+    return (size_t)(cn_mix64(cn_mix64(seed ^ cn_mix64(cnt)) ^ (uint64_t)(uint32_t)m) % size);
+}
+// the rows an update with (seed, counter, mode) gathers, without the update: cn_replay_sample_indices
+__global__ void __launch_bounds__(256) cn_replay_indices_kernel(uint64_t seed, unsigned long long cnt, int B, const int64_t* size_dev, int mode,
+                                                                int64_t* __restrict__ rows)
+{
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m < B) rows[m] = (int64_t)cn_replay_row(seed, cnt, m, size_dev, mode);
+}
 struct PrepArgs {
     const float *rs, *ra, *rr, *rs2, *rd;          // replay ring (rows `obs_dim` / 2 / 1 wide) or the explicit batch
     const float* noise_in;                         // explicit target-policy noise [B][2] (unit variance, before the clip) or null
@@ -568,17 +606,14 @@ struct PrepArgs {
     uint64_t seed;
     int B, D;
     float noise_std, noise_clip;
+    int mode;                                      // CN_SAMPLE_*: how the replay rows are drawn
 };
 __global__ void __launch_bounds__(256) td3_prep_kernel(PrepArgs p)
 {
     const int m = blockIdx.x, tid = threadIdx.x, Dc = p.D + 2;
     const unsigned long long cnt = *p.counter;       // (advanced by td3_tick inside a later launch on the stream)
     size_t row = (size_t)m;
-    if (p.size_dev) {
-        const unsigned long long size = (unsigned long long)(*p.size_dev > 0 ? *p.size_dev : 1);
-        const uint64_t h = cn_mix64(cn_mix64(p.seed ^ cn_mix64(cnt)) ^ (uint64_t)(uint32_t)m);
-        row = (size_t)(h % size);
-    }
+    if (p.size_dev) row = cn_replay_row(p.seed, cnt, m, p.size_dev, p.mode);
     const float* s = p.rs + row * (size_t)p.D;
     const float* s2 = p.rs2 + row * (size_t)p.D;
     for (int c = tid; c < p.D; c += blockDim.x) {
@@ -755,6 +790,7 @@ struct Learner {
     void* pool = nullptr;          // one allocation for the whole workspace
     float* loss = nullptr;
     unsigned long long* counter = nullptr;         // update counter (keys the sampling)
+    int sample_mode = CN_SAMPLE_WITH_REPLACEMENT;  // cn_*_set_replay_sample: read on the host when an update is enqueued
     Learner() = default;
     Learner(const Learner&) = delete;
     ~Learner() { if (pool) { DevScope scope(device); (void)hipFree(pool); } }
@@ -793,6 +829,16 @@ int check_update(const char* fn, const Hd* h, const Batch* batch)
     if (!batch && (!c.replay_s || !c.replay_a || !c.replay_r || !c.replay_s2 || !c.replay_d || !c.replay_size_dev))
         return td3_fail(CN_ERR_ARG, std::string(fn) + ": no explicit batch and no replay ring in the configuration");
     if (batch && (!batch->s || !batch->a || !batch->r || !batch->s2 || !batch->d)) return td3_fail(CN_ERR_ARG, std::string(fn) + ": null batch pointer");
+    return CN_OK;
+}
+
+// cn_*_set_replay_sample: the mode of the updates enqueued from now on (a captured update keeps the kernel arguments it was captured with)
+int set_replay_sample(const char* fn, Learner* h, int mode)
+{
+    if (!h) return td3_fail(CN_ERR_ARG, std::string(fn) + ": null handle");
+    if (mode != CN_SAMPLE_WITH_REPLACEMENT && mode != CN_SAMPLE_DISTINCT)
+        return td3_fail(CN_ERR_ARG, std::string(fn) + ": mode must be CN_SAMPLE_WITH_REPLACEMENT (0) or CN_SAMPLE_DISTINCT (1); the handle keeps its mode");
+    h->sample_mode = mode;
     return CN_OK;
 }
 
@@ -835,7 +881,7 @@ PrepArgs prep_args(const ActorCritic& h, const Cfg& c, const cn_td3_batch* batch
     if (batch) { pa.rs = batch->s; pa.ra = batch->a; pa.rr = batch->r; pa.rs2 = batch->s2; pa.rd = batch->d; pa.noise_in = batch->target_noise; }
     else { pa.rs = c.replay_s; pa.ra = c.replay_a; pa.rr = c.replay_r; pa.rs2 = c.replay_s2; pa.rd = c.replay_d; pa.size_dev = c.replay_size_dev; }
     pa.xs = h.xs; pa.x2 = h.x2; pa.r = h.r; pa.d = h.d; pa.noise = h.noise; pa.counter = h.counter;
-    pa.seed = c.seed; pa.B = h.B; pa.D = h.D;
+    pa.seed = c.seed; pa.B = h.B; pa.D = h.D; pa.mode = h.sample_mode;
     return pa;
 }
 // the part of GemmArgs (zeroed by the caller) that no launch of an update changes: Adam's constants and the tick's arguments
@@ -936,6 +982,7 @@ extern "C" int cn_td3_create(const cn_td3_config* cfg, int device, cn_td3_handle
 extern "C" void cn_td3_destroy(cn_td3_handle h) { delete h; }
 extern "C" const float* cn_td3_loss_dev(cn_td3_handle h) { return h ? h->loss : nullptr; }
 extern "C" const float* cn_td3_batch_dev(cn_td3_handle h, int what) { return batch_dev(h, what); }
+extern "C" int cn_td3_set_replay_sample(cn_td3_handle h, int mode) { return set_replay_sample("cn_td3_set_replay_sample", h, mode); }
 
 extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* batch, void* stream)
 {
@@ -1052,6 +1099,7 @@ extern "C" int cn_ddpg_create(const cn_ddpg_config* cfg, int device, cn_ddpg_han
 extern "C" void cn_ddpg_destroy(cn_ddpg_handle h) { delete h; }
 extern "C" const float* cn_ddpg_loss_dev(cn_ddpg_handle h) { return h ? h->loss : nullptr; }
 extern "C" const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what) { return batch_dev(h, what); }     // no target noise (what 4: NULL)
+extern "C" int cn_ddpg_set_replay_sample(cn_ddpg_handle h, int mode) { return set_replay_sample("cn_ddpg_set_replay_sample", h, mode); }
 
 extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream)
 {
@@ -1139,12 +1187,12 @@ struct DqnPrepArgs {
     const unsigned long long* counter; unsigned long long* kcur;
     uint64_t seed;
     int B, ld, D, learn_start, target_every;
+    int mode;                                      // CN_SAMPLE_*
 };
 __device__ __forceinline__ size_t dqn_row(const DqnPrepArgs& p, int m, unsigned long long cnt)
 {
     if (!p.size_dev) return (size_t)m;
-    const unsigned long long size = (unsigned long long)(*p.size_dev > 0 ? *p.size_dev : 1);
-    return (size_t)(cn_mix64(cn_mix64(p.seed ^ cn_mix64(cnt)) ^ (uint64_t)(uint32_t)m) % size);
+    return cn_replay_row(p.seed, cnt, m, p.size_dev, p.mode);
 }
 __global__ void __launch_bounds__(256) dqn_prep_kernel(DqnPrepArgs p)
 {
@@ -1397,6 +1445,7 @@ extern "C" int cn_dqn_create(const cn_dqn_config* cfg, int device, cn_dqn_handle
 }
 extern "C" void cn_dqn_destroy(cn_dqn_handle h) { delete h; }
 extern "C" const float* cn_dqn_loss_dev(cn_dqn_handle h) { return h ? h->loss : nullptr; }
+extern "C" int cn_dqn_set_replay_sample(cn_dqn_handle h, int mode) { return set_replay_sample("cn_dqn_set_replay_sample", h, mode); }
 
 extern "C" const void* cn_dqn_batch_dev(cn_dqn_handle h, int what)
 {
@@ -1420,7 +1469,7 @@ extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* s
     else { pa.rs = c.replay_s; pa.rs2 = c.replay_s2; pa.rr = c.replay_r; pa.rd = c.replay_d; pa.ra = c.replay_a; pa.size_dev = c.replay_size_dev; }
     pa.x = h->x; pa.r = h->r; pa.d = h->d; pa.a = h->a; pa.chunk = h->chunk; pa.flags = h->flags;
     pa.counter = h->counter; pa.kcur = h->kcur; pa.seed = c.seed; pa.B = B; pa.ld = ld; pa.D = D;
-    pa.learn_start = c.learn_start; pa.target_every = c.target_every;
+    pa.learn_start = c.learn_start; pa.target_every = c.target_every; pa.mode = h->sample_mode;
     hipLaunchKernelGGL(dqn_prep_kernel, dim3(2 * B + 1), dim3(256), (size_t)(13 * B + 8) / 8 * 8, st, pa);
 
     GemmArgs ga;
@@ -1783,6 +1832,7 @@ extern "C" int cn_sac_create(const cn_sac_config* cfg, int device, cn_sac_handle
 }
 extern "C" void cn_sac_destroy(cn_sac_handle h) { delete h; }
 extern "C" const float* cn_sac_loss_dev(cn_sac_handle h) { return h ? h->loss : nullptr; }
+extern "C" int cn_sac_set_replay_sample(cn_sac_handle h, int mode) { return set_replay_sample("cn_sac_set_replay_sample", h, mode); }
 extern "C" const float* cn_sac_batch_dev(cn_sac_handle h, int what)
 {
     if (!h) return nullptr;
@@ -1807,6 +1857,7 @@ extern "C" int cn_sac_update(cn_sac_handle h, const cn_td3_batch* batch, void* s
     else { pa.rs = c.replay_s; pa.ra = c.replay_a; pa.rr = c.replay_r; pa.rs2 = c.replay_s2; pa.rd = c.replay_d; pa.size_dev = c.replay_size_dev; }
     pa.xs = h->xs; pa.x2 = h->x2; pa.r = h->r; pa.d = h->d; pa.noise = h->eps; pa.counter = h->counter;
     pa.seed = c.seed; pa.B = B; pa.D = D; pa.noise_std = 1.f; pa.noise_clip = 3.4e38f;       // (eps x 1, clipped at a bound no draw reaches)
+    pa.mode = h->sample_mode;
     hipLaunchKernelGGL(td3_prep_kernel, dim3(B), dim3(256), 0, st, pa);
     GemmArgs ga;
     memset(&ga, 0, sizeof(ga));
@@ -1902,6 +1953,20 @@ extern "C" int cn_sac_act(const cn_sac_act_io* io, int device, void* stream)
     p.twist = io->twist; p.mean = io->mean; p.log_std = io->log_std; p.z = io->z;
     const size_t lds = (size_t)2 * 16 * p.Hp * sizeof(float);
     hipLaunchKernelGGL(sac_act_kernel, dim3((io->n + 15) / 16), dim3(256), lds, (hipStream_t)stream, p);
+    TD3CHK(hipGetLastError());
+    return CN_OK;
+}
+
+extern "C" int cn_replay_sample_indices(uint64_t seed, uint64_t counter, int B, const int64_t* size_dev, int mode, int64_t* rows_dev,
+                                        int device, void* stream)
+{
+    if (!size_dev || !rows_dev) return td3_fail(CN_ERR_ARG, "cn_replay_sample_indices: null argument");
+    if (B < 1) return td3_fail(CN_ERR_ARG, "cn_replay_sample_indices: B < 1");
+    if (mode != CN_SAMPLE_WITH_REPLACEMENT && mode != CN_SAMPLE_DISTINCT)
+        return td3_fail(CN_ERR_ARG, "cn_replay_sample_indices: mode must be CN_SAMPLE_WITH_REPLACEMENT (0) or CN_SAMPLE_DISTINCT (1)");
+    DevScope scope(device);
+    hipLaunchKernelGGL(cn_replay_indices_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, (unsigned long long)counter, B,
+                       size_dev, mode, rows_dev);
     TD3CHK(hipGetLastError());
     return CN_OK;
 }

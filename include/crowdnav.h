@@ -333,8 +333,39 @@ const float* cn_td3_loss_dev(cn_td3_handle h);      /* device pointer: the first
  * scale and the clip [batch][2].  Other values of what, or a NULL handle: NULL.
  * On the replay path row m of update number c (counting from 0 at cn_td3_create; every update counts, whether it passes an
  * explicit batch or not, whether it steps the actor or not) is ring row mix64(mix64(seed ^ mix64(c)) ^ m) % max(*replay_size_dev, 1)
- * (mix64: splitmix64's finaliser), and its noise is Box-Muller on the same hash with c ^ 0x5bd1e995 in place of c. */
+ * (mix64: splitmix64's finaliser), and its noise is Box-Muller on the same hash with c ^ 0x5bd1e995 in place of c.  That draw is
+ * WITH replacement (CN_SAMPLE_WITH_REPLACEMENT, the mode of a fresh handle).
+ * With cn_td3_set_replay_sample(h, CN_SAMPLE_DISTINCT) the rows of an update are DISTINCT, as the reference's random.sample gives
+ * them (td3.py:31-32, ddpg.py:33-34, sac.py:34-35, memory.py:23): row m is a keyed bijection of [0, n) evaluated at m, still a pure
+ * function of (seed, c, m, live size) -- no communication between rows, no host read, the same single prep launch.  All integers
+ * are unsigned 64-bit; sums are exact (never wrapped at 2^64: (L + h) % a is evaluated as (L + h % a) % a):
+ *   n = max(*replay_size_dev, 1)                       (read when the update runs)
+ *   a = the least integer with a*a >= n;  b = ceil(n / a)          (a*b >= n, and (a*b - n) / (a*b) <= 1/4)
+ *   K = mix64(seed ^ mix64(c ^ 0x9E3779B97F4A7C15))
+ *   x = m mod n
+ *   repeat (at most 64 times):
+ *       L = x / b;  R = x % b
+ *       for i = 0..3:   i even: L = (L + mix64(mix64(K ^ (i+1)) ^ R)) % a
+ *                       i odd : R = (R + mix64(mix64(K ^ (i+1)) ^ L)) % b
+ *       x = L*b + R
+ *   until x < n
+ *   row = x        (if the 64th pass still left x >= n: x mod n -- never expected: probability <= 4^-64)
+ * Each round is invertible on Z_a x Z_b, so the four are a bijection there, and walking its cycle until x < n makes it a bijection
+ * of [0, n).  Rows m = 0 .. batch-1 with batch <= n are therefore distinct, and at batch == n a permutation of the whole ring.
+ * batch > n is outside the reference's domain (random.sample raises; the Python callers gate on ready(batch)); it is not refused,
+ * because the size lives on the device: x = m mod n makes every ring row appear floor(batch / n) or ceil(batch / n) times.
+ * The target-policy noise does not depend on the mode. */
 const float* cn_td3_batch_dev(cn_td3_handle h, int what);
+/* How the replay path draws its rows.  The setters store the mode in the handle on the host: the next update enqueued uses it, an
+ * update already captured into a hipGraph keeps the mode it was captured with.  A fresh handle is CN_SAMPLE_WITH_REPLACEMENT.  Any
+ * other value: CN_ERR_ARG (text in cn_td3_last_error) and the handle keeps its mode.  An explicit batch is not sampled at all. */
+enum { CN_SAMPLE_WITH_REPLACEMENT = 0, CN_SAMPLE_DISTINCT = 1 };
+int cn_td3_set_replay_sample(cn_td3_handle h, int mode);
+/* The B ring rows that an update of a handle with this seed, at update counter `counter`, in this mode would gather: int64 [B] on
+ * the device, *size_dev read on the device when the launch runs (the updates call the same device function).  B >= 1.  One launch,
+ * enqueue-only.  crowdnav.td3.DeviceReplay.sample(batch, replace=False) draws through it. */
+int cn_replay_sample_indices(uint64_t seed, uint64_t counter, int B, const int64_t* size_dev, int mode, int64_t* rows_dev,
+                             int device, void* stream);
 const char* cn_td3_last_error(void);
 
 /* The DDPG update -- Agent.learn of the reference's ddpg.py:198-243, the baseline learner of start_ddpg_training.py -- on the
@@ -369,11 +400,15 @@ void cn_ddpg_destroy(cn_ddpg_handle h);
 int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream);
 const float* cn_ddpg_loss_dev(cn_ddpg_handle h);    /* device pointer: the critic's MSE loss of the last update (ddpg.py:230) */
 const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what);   /* as cn_td3_batch_dev, same indices; what = 4 (no noise): NULL */
+int cn_ddpg_set_replay_sample(cn_ddpg_handle h, int mode);    /* as cn_td3_set_replay_sample */
 
 /* DQN -- the reference's discrete learner (deepq.py, start_dqn_training.py) -- on the same GEMM kernels (crowdnav_td3.hip).
  * Network (deepq.py:102-127, TRAIN_DQN:55-57): Linear(obs_dim, H) - ReLU - Linear(H, H) - ReLU - Linear(H, 3), H = 300.
  * One update = learnOnMiniBatch (deepq.py:219-266) with Memory.getMiniBatch (memory.py:22-28):
- *   - B rows sampled on the device with replacement (td3_prep_kernel's hash; the reference samples without replacement);
+ *   - B rows sampled on the device: with replacement by default (td3_prep_kernel's hash), or distinct as memory.py:23's
+ *     random.sample after cn_dqn_set_replay_sample(h, CN_SAMPLE_DISTINCT) (the bijection stated at cn_td3_batch_dev; s, s2, r, d,
+ *     the action and the final flags of row m all come from the same ring row).  The reference's min(size, len) does not arise:
+ *     the replay path is live only above learn_start rows, and the callers keep learn_start >= batch;
  *   - Y = Q(s), Y[a] = r if final else r + gamma max Q'(s2) (deepq.py:240-256), Q' = the online net until the first target copy,
  *     the target net after it; every final sample appends the row (s2, [r, r, r]) right after its own (:257-262): B + F rows;
  *   - model.fit(batch_size = B, epochs = 1) shuffles them and takes two steps when F > 0: the first B shuffled rows, then the
@@ -411,6 +446,7 @@ const float* cn_dqn_loss_dev(cn_dqn_handle h);      /* device pointer: [2] the l
  * 2 = d [B], 3 = a [B] (int32), 4 = the chunk of each stacked row [2B] (int32: 0 none, 1, 2), 5 = flags [8] (int32: live, second
  * step, F, Q' is the target net, target copied), 6 = Y [2B][3], 7 = the pre-step Q [2B][3] (chunk 1's forward; chunk 2's is kept apart), 8 = the update counter (uint64). */
 const void* cn_dqn_batch_dev(cn_dqn_handle h, int what);
+int cn_dqn_set_replay_sample(cn_dqn_handle h, int mode);      /* as cn_td3_set_replay_sample */
 /* Action selection (TRAIN_DQN:103-104, deepq.py:151-184) for n rows as ONE launch: Q on the f32 matrix cores, argmax with ties to
  * the lowest index, and with probability epsilon a uniform index instead, drawn from (seed, counter, row).  epsilon: episodes_dev
  * NULL = `epsilon` itself; else the schedule TRAIN_DQN:89-90 (if eps > epsilon_min: eps *= epsilon_discount, once per episode
@@ -479,6 +515,7 @@ const float* cn_sac_loss_dev(cn_sac_handle h);      /* device pointer: [3] q_los
  * log_std[2], z[2], log_prob, Q(s, a_new), a_new[2]; 6: d policy_loss / d (mean[2], log_std[2]) [batch][4]; 7: d q_loss / d Q [batch];
  * 8: d value_loss / d V [batch]. */
 const float* cn_sac_batch_dev(cn_sac_handle h, int what);
+int cn_sac_set_replay_sample(cn_sac_handle h, int mode);      /* as cn_td3_set_replay_sample */
 /* Agent.act (SAC:206-229) for n rows as ONE launch: trunk on the f32 matrix cores, both heads, the clamp, z = eps std + mean
  * (deterministic != 0: z = mean), the double squash, the clip to v in [0, max_v], w in [-max_w, max_w].  eps [n][2] or NULL = drawn
  * from (seed, counter, row) as above with c = counter, m = row.  Writes twist [n][2]; mean, log_std (clamped), z [n][2] optional. */

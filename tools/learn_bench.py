@@ -1,11 +1,21 @@
 #!/usr/bin/env python
 """TD3 updates per second: the eager torch path, Agent.enable_graphs (one hipGraph launch per update) and cn_td3_update
-(Agent.enable_fused_update: 7 + 5 hand-written launches, csrc/crowdnav_td3.hip; also captured into hipGraphs here)."""
-import os, sys, time
+(Agent.enable_fused_update: 7 + 5 hand-written launches, csrc/crowdnav_td3.hip; also captured into hipGraphs here).
+--replay-sample {with,without}: how the updates draw their mini-batch (cn_*_set_replay_sample; `without` times the fused and the
+eager update only: the captured PyTorch update draws with replacement).  --samples N (with CN_LEARN_MODES=fused): the median, min and
+max of N samples of 400 updates instead of one mean.  --algo dqn: cn_dqn_update at (361 of 363, 300, batch) in the same way (fused only)."""
+import argparse, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "drl-based-mapless-crowd-navigation-with-perceived-risk_amd"))
 import torch
 from crowdnav.td3 import Agent
+
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--replay-sample", default="with", choices=["with", "without"])
+ap.add_argument("--algo", default="td3", choices=["td3", "dqn"])
+ap.add_argument("--samples", type=int, default=0)
+args = ap.parse_args()
+RS = args.replay_sample
 
 
 def fill(ag, n=100000):
@@ -21,13 +31,38 @@ def timed(fn, K=400, warm=50):
     return (time.perf_counter() - t0) / K * 1e3
 
 
+def report(B, name, fn):
+    if args.samples > 0:
+        ms = [timed(fn, warm=50 if j == 0 else 0) for j in range(args.samples)]
+        print("batch %5d: %s, replay sample %s: median %.4f ms per update (min %.4f, max %.4f, %d samples of 400)" % (
+            B, name, RS, statistics.median(ms), min(ms), max(ms), len(ms)), flush=True)
+    else:
+        print("batch %5d: %s %.3f ms per update (replay sample %s)" % (B, name, timed(fn), RS), flush=True)
+
+
 ONLY_FUSED = os.environ.get("CN_LEARN_MODES", "") == "fused"      # (tools/learn_profile.sh: the fused chain alone under rocprofv3)
-for B in [int(x) for x in os.environ.get("CN_BATCHES", "128,1024").split(",")]:
+for B in [int(x) for x in os.environ.get("CN_BATCHES", "128,1024" if args.algo == "td3" else "64").split(",")]:
     row = []
+    if args.algo == "dqn":
+        from crowdnav import dqn
+        ag = dqn.Agent(obs_dim=361, obs_ld=363, device="cuda", seed=0, batch_size=B, memory_size=200000, replay_sample=RS)
+        n = 100000
+        ag.memory.add(torch.randn((n, 363), device="cuda"), torch.randint(0, 3, (n, 2), device="cuda").float(), torch.randn(n, device="cuda"),
+                      torch.randn((n, 363), device="cuda"), torch.rand(n, device="cuda") < 0.05)
+        ag.enable_fused_update()
+        report(B, "dqn fused", ag.learn)
+        continue
     if ONLY_FUSED:
-        ag = Agent(obs_dim=398, device="cuda", seed=0, batch_size=B, memory_size=200000)
+        ag = Agent(obs_dim=398, device="cuda", seed=0, batch_size=B, memory_size=200000, replay_sample=RS)
         fill(ag); ag.enable_fused_update()
-        print("batch %5d: fused %.3f ms per update" % (B, timed(ag.learn)), flush=True)
+        report(B, "fused", ag.learn)
+        continue
+    if RS == "without":
+        for mode in ("eager", "fused"):
+            ag = Agent(obs_dim=398, device="cuda", seed=0, batch_size=B, memory_size=200000, replay_sample=RS)
+            fill(ag)
+            if mode == "fused": ag.enable_fused_update()
+            report(B, mode, ag.learn)
         continue
     for mode in ("eager", "graphs", "fused"):
         ag = Agent(obs_dim=398, device="cuda", seed=0, batch_size=B, memory_size=200000)

@@ -1,13 +1,18 @@
 #!/usr/bin/env python
 """SAC updates per second at (363, 256, 64): cn_sac_update (Agent.enable_fused_update) beside the PyTorch eager update of the
 same Agent and the fused DDPG update, on the same device; cn_sac_act beside Agent.act.  Warm-up, then the median of `SAMPLES`
-samples of `K` updates each (one synchronisation per sample).  Prints one line per measurement."""
-import os, statistics, sys, time
+samples of `K` updates each (one synchronisation per sample).  Prints one line per measurement.
+--replay-sample {with,without}: how the updates draw their mini-batch (cn_*_set_replay_sample / DeviceReplay.sample(replace=...))."""
+import argparse, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "drl-based-mapless-crowd-navigation-with-perceived-risk_amd"))
 import torch
 from crowdnav import ddpg, sac
 
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--replay-sample", default="with", choices=["with", "without"])
+RS = ap.parse_args().replay_sample
+print("replay sample: %s replacement" % RS, flush=True)
 D, K, SAMPLES = 363, int(os.environ.get("CN_K", "300")), int(os.environ.get("CN_SAMPLES", "7"))
 
 
@@ -30,11 +35,11 @@ def timed(fn, warm=50):
 for vn in ("as_written", "intended"):
     for su in ("as_written", "intended"):
         for mode in ("eager", "fused"):
-            ag = sac.Agent(obs_dim=D, device="cuda", seed=0, memory_size=200000, value_net=vn, soft_update=su)
+            ag = sac.Agent(obs_dim=D, device="cuda", seed=0, memory_size=200000, value_net=vn, soft_update=su, replay_sample=RS)
             fill(ag)
             if mode == "fused": ag.enable_fused_update()
             print("sac value_net %-10s soft_update %-10s %-5s: %.4f ms per update (min %.4f, max %.4f)" % ((vn, su, mode) + timed(ag.learn)), flush=True)
-ag = ddpg.Agent(obs_dim=D, device="cuda", seed=0, memory_size=200000)
+ag = ddpg.Agent(obs_dim=D, device="cuda", seed=0, memory_size=200000, replay_sample=RS)
 fill(ag); ag.enable_fused_update()
 print("ddpg fused: %.4f ms per update (min %.4f, max %.4f)" % timed(ag.learn), flush=True)
 ag = sac.Agent(obs_dim=D, device="cuda", seed=0, memory_size=16)
