@@ -39,7 +39,10 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_sac_create", "cn_sac_destroy", "cn_sac_update", "cn_sac_loss_dev", "cn_sac_batch_dev", "cn_sac_act",
            "cn_tab_create", "cn_tab_destroy", "cn_tab_set", "cn_tab_get", "cn_tab_tables", "cn_tab_learn_act", "cn_tab_last_error",
            "cn_td3_set_replay_sample", "cn_ddpg_set_replay_sample", "cn_dqn_set_replay_sample", "cn_sac_set_replay_sample",
-           "cn_replay_sample_indices", "cn_replay_write", "cn_episode_log_add"]
+           "cn_replay_sample_indices", "cn_replay_write", "cn_episode_log_add",
+           "cn_td3_pop_create", "cn_td3_pop_destroy", "cn_td3_pop_update", "cn_td3_pop_members", "cn_td3_pop_loss_dev",
+           "cn_td3_pop_batch_dev", "cn_td3_pop_set_replay_sample"]
+CN_TD3_POP_MAX = 64         # include/crowdnav.h: cn_td3_pop_create's n_members is 1 ... 64
 CN_SAMPLE_WITH_REPLACEMENT, CN_SAMPLE_DISTINCT = 0, 1      # include/crowdnav.h: cn_*_set_replay_sample
 REPLAY_SAMPLE = {"with": CN_SAMPLE_WITH_REPLACEMENT, "without": CN_SAMPLE_DISTINCT}
 
@@ -340,6 +343,13 @@ def lib():
         L.cn_td3_loss_dev.argtypes = [vp]; L.cn_td3_loss_dev.restype = vp
         L.cn_td3_batch_dev.argtypes = [vp, C.c_int]; L.cn_td3_batch_dev.restype = vp
         L.cn_td3_last_error.restype = C.c_char_p
+        L.cn_td3_pop_create.argtypes = [C.POINTER(CnTd3Config), C.c_int, C.c_int, C.POINTER(vp)]      # an array of n_members configs
+        L.cn_td3_pop_destroy.argtypes = [vp]; L.cn_td3_pop_destroy.restype = None
+        L.cn_td3_pop_update.argtypes = [vp, C.c_int, vp]
+        L.cn_td3_pop_members.argtypes = [vp]
+        L.cn_td3_pop_loss_dev.argtypes = [vp]; L.cn_td3_pop_loss_dev.restype = vp
+        L.cn_td3_pop_batch_dev.argtypes = [vp, C.c_int, C.c_int]; L.cn_td3_pop_batch_dev.restype = vp
+        L.cn_td3_pop_set_replay_sample.argtypes = [vp, C.c_int]
         L.cn_ddpg_create.argtypes = [C.POINTER(CnDdpgConfig), C.c_int, C.POINTER(vp)]
         L.cn_ddpg_destroy.argtypes = [vp]; L.cn_ddpg_destroy.restype = None
         L.cn_ddpg_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]

@@ -78,3 +78,51 @@ class FusedLearner:
                 self.h = None
         except Exception:
             pass
+
+
+class FusedPopulation:
+    """Owns one cn_td3_pop handle: P TD3 learners updated by the launches of one (include/crowdnav.h, cn_td3_pop_create).  cfgs: the
+    members' CnTd3Config, in member order.  The sibling of FusedLearner for the population calls; errors raise the same way."""
+
+    def __init__(self, cfgs, device, dev_index, replay_sample="with"):
+        mode = _abi.replay_sample_mode(replay_sample)
+        self._L = L = _abi.lib()
+        self.device, self.P = device, len(cfgs)
+        self.cfgs = (_abi.CnTd3Config * self.P)(*cfgs)
+        self.h = C.c_void_p()
+        self._check("create", L.cn_td3_pop_create(self.cfgs, self.P, dev_index, C.byref(self.h)))
+        self._loss = _device_view(L.cn_td3_pop_loss_dev(self.h), (self.P,), torch.float32, device)
+        self.replay_sample = "with"
+        if mode != _abi.CN_SAMPLE_WITH_REPLACEMENT:
+            self.set_replay_sample(replay_sample)
+
+    def _check(self, what, rc):
+        if rc != 0:
+            raise _abi.CrowdNavError("cn_td3_pop_%s: %s" % (what, self._L.cn_td3_last_error().decode()))
+
+    def update(self, do_actor):
+        """cn_td3_pop_update on torch's current stream: enqueue-only.  Returns the P losses as a fresh tensor (one small
+        device-to-device copy on that stream; the handle's own buffer is overwritten by the next update)."""
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._check("update", self._L.cn_td3_pop_update(self.h, int(do_actor), st))
+        return self._loss.clone()
+
+    def set_replay_sample(self, replay_sample):
+        """cn_td3_pop_set_replay_sample: "with" | "without", for all members, for the updates enqueued from now on."""
+        self._check("set_replay_sample", self._L.cn_td3_pop_set_replay_sample(self.h, _abi.replay_sample_mode(replay_sample)))
+        self.replay_sample = replay_sample
+
+    def batch_dev(self, member, what, shape, dtype=torch.float32):
+        """A view of what the last update gathered for `member` (cn_td3_pop_batch_dev), valid until the next update."""
+        ptr = self._L.cn_td3_pop_batch_dev(self.h, int(member), int(what))
+        if not ptr:
+            raise _abi.CrowdNavError("cn_td3_pop_batch_dev: member %r / what %r out of range" % (member, what))
+        return _device_view(ptr, shape, dtype, self.device)
+
+    def __del__(self):
+        try:
+            if self.h:
+                self._L.cn_td3_pop_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass

@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ._fused import FusedLearner, _device_view, mlp_of
+from ._fused import FusedLearner, FusedPopulation, _device_view, mlp_of
 
 
 class Actor(nn.Module):
@@ -464,19 +464,22 @@ class Agent(FusedActorMixin):
         drawn on the device -- 7 launches for the critic step, 5 more with the actor and the targets, against ~150 through PyTorch.  The
         networks stay these nn.Modules (the kernels step their parameter storages in place); Adam's moments restart from zero
         inside the library (torch.optim state is not carried over), so call this before training, not in the middle of it."""
-        from . import _abi
         if self.device.type != "cuda":
             raise RuntimeError("enable_fused_update needs a HIP device")
         if getattr(self, "_fused", None):
             return
+        self._fused = FusedLearner("td3", self.fused_config(), self.device, self._dev_index, replay_sample=self.replay_sample)
+
+    def fused_config(self):
+        """The cn_td3_config of this agent: its hyper-parameters, its six networks' storages, its replay ring and its seed."""
+        from . import _abi
         og = self.opt_a.param_groups[0]
-        cfg = _abi.CnTd3Config(obs_dim=self.actor.linear1.in_features, hidden=self.actor.linear1.out_features, batch=self.batch_size,
-                               policy_delay=self.policy_delay, gamma=self.gamma, tau=self.tau, lr_actor=og["lr"],
-                               lr_critic=self.opt_q1.param_groups[0]["lr"], beta1=og["betas"][0], beta2=og["betas"][1], eps=og["eps"],
-                               noise_std=self.noise_std, noise_clip=self.noise_clip, max_v=self.max_v, max_w=self.max_w, reserved=0.0,
-                               actor=mlp_of(self.actor), actor_t=mlp_of(self.actor_t), q1=mlp_of(self.q1), q1_t=mlp_of(self.q1_t),
-                               q2=mlp_of(self.q2), q2_t=mlp_of(self.q2_t), seed=self._noise_seed, **self.memory.ring_fields())
-        self._fused = FusedLearner("td3", cfg, self.device, self._dev_index, replay_sample=self.replay_sample)
+        return _abi.CnTd3Config(obs_dim=self.actor.linear1.in_features, hidden=self.actor.linear1.out_features, batch=self.batch_size,
+                                policy_delay=self.policy_delay, gamma=self.gamma, tau=self.tau, lr_actor=og["lr"],
+                                lr_critic=self.opt_q1.param_groups[0]["lr"], beta1=og["betas"][0], beta2=og["betas"][1], eps=og["eps"],
+                                noise_std=self.noise_std, noise_clip=self.noise_clip, max_v=self.max_v, max_w=self.max_w, reserved=0.0,
+                                actor=mlp_of(self.actor), actor_t=mlp_of(self.actor_t), q1=mlp_of(self.q1), q1_t=mlp_of(self.q1_t),
+                                q2=mlp_of(self.q2), q2_t=mlp_of(self.q2_t), seed=self._noise_seed, **self.memory.ring_fields())
 
     def _fused_learn(self, step, batch=None, target_noise=None):
         from . import _abi
@@ -538,3 +541,42 @@ class Agent(FusedActorMixin):
         torch.save(self.actor_t.state_dict(), os.path.join(outdir, "td3_actor_model_ep%d.pt" % ep))
         torch.save(self.q1_t.state_dict(), os.path.join(outdir, "td3_critic1_model_ep%d.pt" % ep))
         torch.save(self.q2_t.state_dict(), os.path.join(outdir, "td3_critic2_model_ep%d.pt" % ep))
+
+
+class Population:
+    """P TD3 agents on one device whose updates run as ONE chain of 7 (+ 5) launches (cn_td3_pop_update): member p's update is, bit
+    for bit, the update agents[p].enable_fused_update() would run alone.  The agents keep their networks, replay rings, seeds,
+    learning rates, gamma and target-noise parameters; they must agree in obs_dim, hidden, batch_size, policy_delay, tau, max_v,
+    max_w and Adam's betas / eps (the library names the field and the member otherwise).  Acting stays per member (act_mfma)."""
+
+    def __init__(self, agents, replay_sample=None):
+        agents = list(agents)
+        if not agents:
+            raise ValueError("a population needs at least one agent")
+        a0 = agents[0]
+        if any(a.device != a0.device for a in agents) or a0.device.type != "cuda":
+            raise ValueError("the agents of a population live on one HIP device")
+        if any(getattr(a, "_fused", None) or getattr(a, "_graphs", None) for a in agents):
+            raise ValueError("an agent of a population is not updated on its own (enable_fused_update / enable_graphs were called)")
+        self.agents, self.device, self.policy_delay, self.batch_size = agents, a0.device, a0.policy_delay, a0.batch_size
+        self._fused = FusedPopulation([a.fused_config() for a in agents], self.device, a0._dev_index,
+                                      replay_sample=a0.replay_sample if replay_sample is None else replay_sample)
+
+    def __len__(self):
+        return len(self.agents)
+
+    def ready(self):
+        """Every member's ring holds more than a batch (a host read only while a member's bounds straddle it)."""
+        return all(a.memory.ready(self.batch_size) for a in self.agents)
+
+    def learn(self, step):
+        """One update of every member; the actor and the targets move when step % policy_delay == 0, as in Agent.learn.  Enqueue-only.
+        Returns the members' first-critic losses [P] as a fresh tensor.  The caller gates on ready(): the kernels read each ring's
+        live size on the device and do not refuse a ring shorter than the batch."""
+        return self._fused.update(int(step % self.policy_delay == 0))
+
+    def set_replay_sample(self, replay_sample):
+        self._fused.set_replay_sample(replay_sample)
+
+    def batch_dev(self, member, what, shape):
+        return self._fused.batch_dev(member, what, shape)

@@ -59,15 +59,16 @@ import torch
 
 from . import presets
 from .config import Config
-from .env import VecEnv
+from .env import VecEnv, VecEnvGroups
 from .rollout import EpisodeStats, evaluate
 from . import ddpg, dqn, sac, tabular, td3
 
 TABULAR = dict(qlearn=tabular.QLearn, sarsa=tabular.Sarsa)
 
 
-def make_env(scenario, n_envs, max_steps, seed, device, ped_vmax=None, **switches):
-    """switches: cn_config fields applied on top of the scenario (waypoint_reward, scan_f32, wheel_accel, ...)."""
+def scenario_config(scenario, n_envs, max_steps, seed, ped_vmax=None, **switches):
+    """-> (Config, ped_init or None, ped_preset_vel or None) of a scenario.  switches: cn_config fields applied on top of it
+    (waypoint_reward, scan_f32, wheel_accel, ...)."""
     sw = {k: v for k, v in switches.items() if v is not None}
     if scenario in ("training", "training_as_logged"):
         # training_as_logged: without obstacles 7-14, which the world file creates at one point (presets.training's docstring)
@@ -80,6 +81,11 @@ def make_env(scenario, n_envs, max_steps, seed, device, ped_vmax=None, **switche
     else:
         kind, n = scenario.rsplit("_", 1)
         cfg, init, vel = presets.evaluation(kind, int(n), n_envs=n_envs, max_steps=max_steps, seed=seed, **sw)
+    return cfg, init, vel
+
+
+def make_env(scenario, n_envs, max_steps, seed, device, ped_vmax=None, **switches):
+    cfg, init, vel = scenario_config(scenario, n_envs, max_steps, seed, ped_vmax, **switches)
     env = VecEnv(cfg, device=device)
     if init is not None:
         env.set_ped_init(init)
@@ -560,6 +566,127 @@ def train(a):
     return agent, episodes
 
 
+class MemberEnvs(VecEnvGroups):
+    """The environments of a population: group p is member p's own environment handle -- its own seed, the same env indices as a solo
+    run's -- instead of a slice of one configuration, so cn_step_multi steps all members with one call and member p sees the
+    trajectory of VecEnv(cfgs[p])."""
+
+    def __init__(self, cfgs, device):
+        import dataclasses
+        self._cfgs = list(cfgs)
+        super().__init__(dataclasses.replace(self._cfgs[0], n_envs=self._cfgs[0].n_envs * len(self._cfgs)), groups=len(self._cfgs), device=device)
+
+    def _group_cfg(self, g):
+        return self._cfgs[g]
+
+
+def train_population(a):
+    """--population P: P independent TD3 runs, seeds a.seed ... a.seed + P - 1, whose updates are ONE cn_td3_pop_update per update
+    (crowdnav.td3.Population) instead of P processes.  Member p has what `train()` with --seed <seed + p> has -- its environment
+    handle of --envs environments, its Agent, replay, episode log, statistics -- and writes what that run writes into
+    <out>/member<p>/.  Per launch: P act launches, one grouped environment step (cn_step_multi), P replay writes and P log adds; once
+    EVERY member's replay holds more than a batch, --updates population updates and the P actor re-packs.
+    Member p's run IS the solo run --seed <seed + p> --learner fused (same parameters, same CSV rows) as long as the members' rings pass
+    the batch size on the same launch: a member whose ring is not ready yet (it lost rows to reset launches) holds the others back, so
+    that the update counters -- which key the sampling and drive policy_delay -- stay aligned; from then on that member's solo run
+    would have started its updates earlier."""
+    dev = a.device
+    P = a.population
+    torch.cuda.set_device(dev)
+    members = []
+    for p in range(P):
+        m = argparse.Namespace(**vars(a))
+        m.seed, m.out = a.seed + p, os.path.join(a.out, "member%d" % p)
+        members.append(m)
+    specs = [scenario_config(a.scenario, a.envs, a.max_steps, m.seed, a.ped_vmax, **env_switches(a)) for m in members]
+    envs = MemberEnvs([sp[0] for sp in specs], dev)
+    for e, (_, init, vel) in zip(envs.envs, specs):
+        if init is not None:
+            e.set_ped_init(init)
+        if vel is not None:
+            e.set_ped_preset_vel(vel)
+    agents = [make_agent(m, envs.D, "cuda:%d" % dev, memory_size=a.memory, actor_final_init=getattr(a, "actor_final_init", None)) for m in members]
+    pop = td3.Population(agents)
+    batch = agents[0].batch_size
+    stats = [EpisodeStats() for _ in range(P)]
+    logs = []
+    for m in members:
+        os.makedirs(m.out, exist_ok=True)
+        logs.append(open(os.path.join(m.out, "progress.txt"), "a"))
+    obs = envs.reset()
+    t0 = time.time()
+    episodes, env_steps, next_ckpt = [0] * P, [0] * P, [a.checkpoint_every] * P
+    N, rows = envs.N, [envs.rows(p) for p in range(P)]
+    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
+    prev = torch.empty_like(obs)
+    act = torch.zeros((N, 2), dtype=torch.float32, device=obs.device)
+    step_all = envs.bind_step_all(act, auto_reset="next")
+    elogs = [DeviceEpisodeLog(obs.device, a.max_csv_rows) for _ in range(P)]
+    learning = False
+    updates_done = 0
+    for ag in agents:
+        ag.sync_fused_weights()
+    step_s = (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0
+    reward, done = envs.reward, envs.done
+    for it in range(1, a.launches + 1):
+        for ag, r in zip(agents, rows):
+            ag.act_mfma(obs[r], out=act[r], add_noise=True)
+        prev.copy_(obs)
+        envs.fork()                                                    # the members' steps wait for the actions ...
+        step_all()
+        cnt = [e.counters() for e in envs.envs]
+        ret = [e.returns()[0] for e in envs.envs]
+        envs.join()                                                    # ... and everything below for the steps
+        keep = ~resetting
+        for p, (ag, r) in enumerate(zip(agents, rows)):
+            ag.memory.add_masked(prev[r], act[r], reward[r], obs[r], done[r], keep[r])
+            elogs[p].add(done[r], cnt[p], ret[p], it, keep[r])
+        resetting = done.bool()
+        if not learning:
+            learning = pop.ready()                                     # every member: the update counters stay aligned
+        if learning:
+            for u in range(a.updates):
+                updates_done += 1
+                pop.learn(updates_done)
+            for ag in agents:
+                ag.sync_fused_weights()
+        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
+        if it % a.log_every == 0 or last_launch:
+            for p, m in enumerate(members):
+                new, tot = elogs[p].flush()
+                ne = int(tot[0])
+                episodes[p] += ne; env_steps[p] += int(tot[4])
+                for r in new.tolist():
+                    seen = int(r[6])
+                    stats[p].add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
+                                 1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
+                if ne:
+                    line = "launch %6d  env-steps %10d  updates %9d  episodes %8d  success %.3f  mean return %8.1f  mean steps %6.1f  %.0f s" % (
+                        it, env_steps[p], updates_done, episodes[p], tot[1] / ne, tot[2] / ne, tot[3] / ne, time.time() - t0)
+                    print("member %2d  %s" % (p, line), flush=True); logs[p].write(line + "\n"); logs[p].flush()
+                if a.csv:
+                    stats[p].append_csv(m.out, "td3_training")
+                if episodes[p] >= next_ckpt[p]:
+                    save_checkpoint(agents[p], m.out, episodes[p])
+                    while next_ckpt[p] <= episodes[p]:
+                        next_ckpt[p] += a.checkpoint_every
+            if last_launch:
+                break
+    for p, m in enumerate(members):
+        agents[p].memory.sync_len()
+        save_checkpoint(agents[p], m.out, episodes[p])
+        last = stats[p].rows[-500:]
+        if last:
+            line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f  | %d updates, %.0f updates/s (x %d members)" % (
+                len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
+                updates_done, updates_done / max(1e-9, time.time() - t0), P)
+            print("member %2d  %s" % (p, line), flush=True); logs[p].write(line + "\n"); logs[p].flush()
+        if a.csv:
+            stats[p].append_csv(m.out, "td3_training")
+        logs[p].close()
+    return agents, episodes
+
+
 def run_evaluation(a):
     torch.cuda.set_device(a.device)
     env = make_env(a.scenario, a.envs, a.max_steps, a.seed, a.device, a.ped_vmax, **env_switches(a))
@@ -637,6 +764,9 @@ def parse_args(argv=None):
                     "fused: cn_td3_update / cn_ddpg_update (csrc/crowdnav_td3.hip)")
     ap.add_argument("--actor-final-init", type=float, default=None, help="NOT the reference: U(+-x) initialisation of the actor's output layer (e.g. 0.003)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--population", type=int, default=0, help="P > 0: train P independent TD3 agents, seeds --seed ... --seed + P - 1, their updates "
+                    "as one cn_td3_pop_update (1 ... 64; --algo td3 --learner fused only, not with --evaluate or --load); member p has its own "
+                    "--envs environments and writes into <out>/member<p>/ what the solo run --seed <seed + p> writes into <out>")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="default: runs/<algo>")
     ap.add_argument("--csv", action="store_true", help="one CSV row per finished episode in the reference's 8-column schema (recorded on the device, appended to the file at "
@@ -670,6 +800,19 @@ def parse_args(argv=None):
         ap.error("--algo %s collects with the next-step reset only (--reset-mode next)" % a.algo)
     if a.replay_sample == "without" and a.algo == "td3" and a.learner == "torch" and a.graphs and not a.evaluate:
         ap.error("--replay-sample without: the captured PyTorch TD3 update draws its own indices with replacement; use --learner fused or --graphs 0")
+    if a.population:
+        if not 1 <= a.population <= 64:
+            ap.error("--population must be 1 ... 64")
+        if a.algo != "td3":
+            ap.error("--population trains TD3 agents (--algo td3), not --algo %s" % a.algo)
+        if a.learner != "fused":
+            ap.error("--population is cn_td3_pop_update: it needs --learner fused")
+        if a.evaluate:
+            ap.error("--population does not apply to --evaluate (evaluate a member's checkpoints from <out>/member<p>)")
+        if a.load:
+            ap.error("--population starts its members fresh: --load is not supported")
+        if a.reset_mode != "next":
+            ap.error("--population collects with the next-step reset only (--reset-mode next)")
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     return a
@@ -681,6 +824,8 @@ def main(argv=None):
         return train_tabular(a)
     if a.evaluate:
         return run_evaluation(a)
+    if a.population:
+        return train_population(a)
     if a.algo == "dqn":
         return train_dqn(a)
     if a.algo == "sac":

@@ -23,7 +23,9 @@
 #include <initializer_list>
 #include <memory>
 #include <new>
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../../include/crowdnav.h"
 #include "crowdnav_device.h"
@@ -134,6 +136,13 @@ struct GemmArgs {
     float rms_lr, rms_rho, rms_eps;
 };
 static_assert(sizeof(GemmArgs) <= 4096, "GemmArgs travels in the kernarg segment (4 KB)");
+// The population form (cn_td3_pop_update): P members' jobs do not fit the kernarg segment, so they lie in device memory, built once
+// when the handle is created: job[member * njobs + z] is job z of the launch for that member (blockIdx.z walks it), tick[member] its
+// tick's arguments.  What differs between members travels in the job (its pointers, the Adam constants' pointer, hb_gamma) or in the
+// tick's arguments; the four scalars here are the ones the members must agree in.
+struct PopGemmArgs { const GemmJob* job; const TickArgs* tick; int njobs; float beta1, beta2, eps, tau; int do_tick; };
+template <bool POP> struct td3_args { typedef GemmArgs type; };
+template <> struct td3_args<true> { typedef PopGemmArgs type; };
 // target <- target (1 - tau) + local tau (TD3:297-299)
 __device__ __forceinline__ float td3_soft(float target, float local, float tau) { return target * (1.f - tau) + local * tau; }
 
@@ -165,14 +174,21 @@ __device__ __forceinline__ f32x2_t td3_ld2(const float* __restrict__ p, int c, i
 // the block (k = 16 t + 4 lk + e on both sides).
 #define TD3_FKB 8          /* blocks a wavefront has in flight (16 dwordx4 loads) */
 // GATE = true (DQN's second chunk): the launch does nothing while *args.rms_gate == 0
-template <bool GATE>
-__global__ void __launch_bounds__(256) td3_fwd_kernel(GemmArgs args)
+// POP = true (a population; td3_dgrad_kernel and td3_wgrad_kernel have the same parameter): args is a PopGemmArgs -- the job comes
+// from the table in device memory, and every member ticks once, in the first workgroup of its first job.  One body for both, so a
+// member's tile is the same arithmetic in the same order as a solo handle's.
+template <bool GATE, bool POP = false>
+__global__ void __launch_bounds__(256) td3_fwd_kernel(typename td3_args<POP>::type args)
 {
     if constexpr (GATE) { if (*args.rms_gate == 0) return; }
     const GemmJob& jb = args.job[blockIdx.z];
     const int I = jb.I, J = jb.J, R = jb.R;
     const int i0 = blockIdx.y * 16, j0 = blockIdx.x * 16;
-    if (args.do_tick && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) td3_tick(args.tick);
+    if constexpr (POP) {
+        if (args.do_tick && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z % args.njobs == 0 && threadIdx.x == 0) td3_tick(args.tick[blockIdx.z / args.njobs]);
+    } else {
+        if (args.do_tick && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) td3_tick(args.tick);
+    }
     if (i0 >= I || j0 >= J) return;
     __shared__ float red[4][4][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lk = lane >> 4;
@@ -265,8 +281,8 @@ __global__ void __launch_bounds__(256) td3_fwd_kernel(GemmArgs args)
 // G: a 16 x 32 tile per workgroup.  dY's rows are contiguous along the reduction (as in F), W's along the OUTPUT: lane (li, lk)
 // loads W[16 t + 4 lk + e][j0 + 2 li, + 1] for e = 0..3 -- two accumulators, columns j0 + 2 c and j0 + 2 c + 1.
 #define TD3_GKB 4
-template <bool GATE>
-__global__ void __launch_bounds__(256) td3_dgrad_kernel(GemmArgs args)
+template <bool GATE, bool POP = false>
+__global__ void __launch_bounds__(256) td3_dgrad_kernel(typename td3_args<POP>::type args)
 {
     if constexpr (GATE) { if (*args.rms_gate == 0) return; }
     const GemmJob& jb = args.job[blockIdx.z];
@@ -430,8 +446,8 @@ __global__ void __launch_bounds__(256) td3_dgrad_kernel(GemmArgs args)
 // RMS = false: Adam (TD3, DDPG); RMS = true: RMSprop without momentum (DQN, Keras 2's RMSprop.get_updates:
 // a = rho a + (1 - rho) g^2, p -= lr g / (sqrt(a) + eps), the accumulator in jb.m / jb.bm; no target copy, no loss).
 #define TD3_HKS 8          /* steps a wavefront has in flight (16 dwordx2 loads, 32 MFMAs) */
-template <bool RMS>
-__global__ void __launch_bounds__(256) td3_wgrad_kernel(GemmArgs args)
+template <bool RMS, bool POP = false>
+__global__ void __launch_bounds__(256) td3_wgrad_kernel(typename td3_args<POP>::type args)
 {
     const GemmJob& jb = args.job[blockIdx.z];
     const int I = jb.I, J = jb.J, R = jb.R;
@@ -608,8 +624,15 @@ struct PrepArgs {
     float noise_std, noise_clip;
     int mode;                                      // CN_SAMPLE_*: how the replay rows are drawn
 };
-__global__ void __launch_bounds__(256) td3_prep_kernel(PrepArgs p)
+// POP = true (a population): grid (B, P), member blockIdx.y's arguments from a table in device memory (one table per sampling mode)
+template <bool POP> struct td3_prep_in { typedef PrepArgs type; typedef const PrepArgs view; };
+template <> struct td3_prep_in<true> { typedef const PrepArgs* type; typedef const PrepArgs& view; };
+__device__ __forceinline__ const PrepArgs& td3_prep_of(const PrepArgs& p) { return p; }
+__device__ __forceinline__ const PrepArgs& td3_prep_of(const PrepArgs* table) { return table[blockIdx.y]; }
+template <bool POP = false>
+__global__ void __launch_bounds__(256) td3_prep_kernel(typename td3_prep_in<POP>::type in)
 {
+    typename td3_prep_in<POP>::view p = td3_prep_of(in);
     const int m = blockIdx.x, tid = threadIdx.x, Dc = p.D + 2;
     const unsigned long long cnt = *p.counter;       // (advanced by td3_tick inside a later launch on the stream)
     size_t row = (size_t)m;
@@ -984,17 +1007,17 @@ extern "C" const float* cn_td3_loss_dev(cn_td3_handle h) { return h ? h->loss : 
 extern "C" const float* cn_td3_batch_dev(cn_td3_handle h, int what) { return batch_dev(h, what); }
 extern "C" int cn_td3_set_replay_sample(cn_td3_handle h, int mode) { return set_replay_sample("cn_td3_set_replay_sample", h, mode); }
 
-extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* batch, void* stream)
+// The launches of one update, in order, handed to `em`: em.prep(PrepArgs), then em.gemm<MODE>(GemmArgs, njobs) per GEMM launch.
+// cn_td3_update's emitter launches them as they come; a population's records them once, when the handle is created.
+template <class Emit>
+void td3_chain(const cn_td3_s* h, int do_actor, const cn_td3_batch* batch, Emit& em)
 {
-    if (const int rc = check_update("cn_td3_update", h, batch)) return rc;
     const cn_td3_config& c = h->cfg;
-    DevScope scope(h->device);
-    hipStream_t st = (hipStream_t)stream;
     const int B = h->B, D = h->D, Dc = D + 2, H = h->H, qnt = h->qnt();
     // 0. sample / gather, noise, Adam constants
     PrepArgs pa = prep_args(*h, c, batch);
     pa.noise_std = c.noise_std; pa.noise_clip = c.noise_clip;
-    hipLaunchKernelGGL(td3_prep_kernel, dim3(B), dim3(256), 0, st, pa);
+    em.prep(pa);
     GemmArgs ga;
     memset(&ga, 0, sizeof(ga));
     adam_args(ga, *h, c, do_actor ? 1 : 0);
@@ -1003,28 +1026,28 @@ extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* 
     const int na = do_actor ? 2 : 1;
     fwd_job(ga.job[0], h->x2, B, Dc, D, c.actor_t.w1, c.actor_t.b1, h->t_h1, H, 1);
     fwd_job(ga.job[1], h->xs, B, Dc, D, c.actor.w1, c.actor.b1, h->a_h1, H, 1);
-    launch_gemm<GEMM_F>(ga, na, st);
+    em.template gemm<GEMM_F>(ga, na);
     fwd_job(ga.job[0], h->t_h1, B, H, H, c.actor_t.w2, c.actor_t.b2, h->t_h2, H, 1);
     fwd_job(ga.job[1], h->a_h1, B, H, H, c.actor.w2, c.actor.b2, h->a_h2, H, 1);
-    launch_gemm<GEMM_F>(ga, na, st);
+    em.template gemm<GEMM_F>(ga, na);
     // (3, the policies' last layer and heads, runs inside the launches that consume the actions: 4 and 13)
     // 4-6. the four critics forward: q1, q2 on (s, a); q1_t, q2_t on (s2, a2)
     const cn_td3_mlp* crit[4] = {&c.q1, &c.q2, &c.q1_t, &c.q2_t};
     for (int z = 0; z < 4; ++z) fwd_job(ga.job[z], z < 2 ? h->xs : h->x2, B, Dc, Dc, crit[z]->w1, crit[z]->b1, h->c_h1[z], H, 1);
     for (int z = 2; z < 4; ++z) head_job(ga.job[z], D, H, h->t_h2, c.actor_t, h->noise, nullptr, c.max_v, c.max_w);      // a2 = pi_t(s2) + clipped noise
-    launch_gemm<GEMM_F>(ga, 4, st);
+    em.template gemm<GEMM_F>(ga, 4);
     // 5-6. ... their second layers, and the last (q = h2 . W3 + b3) as per-tile partial sums in the same epilogue; the tick too
     for (int z = 0; z < 4; ++z) {
         fwd_job(ga.job[z], h->c_h1[z], B, H, H, crit[z]->w2, crit[z]->b2, h->c_h2[z], H, 1);
         ga.job[z].qp_w3 = crit[z]->w3; ga.job[z].qp_b3 = crit[z]->b3; ga.job[z].qp_out = h->qpart + (size_t)z * B * qnt; ga.job[z].qp_nt = qnt;
     }
     ga.do_tick = 1;
-    launch_gemm<GEMM_F>(ga, 4, st);
+    em.template gemm<GEMM_F>(ga, 4);
     ga.do_tick = 0;
     // 7-8. TD target, MSE gradient (per row, evaluated where it is consumed) and through the second hidden layer:
     // dz1 = (dz2 W2) (.) [h1 > 0], dz2 = dq W3 (.) [h2 > 0]   (W2, W3 are read here, stepped in 9)
     for (int z = 0; z < 2; ++z) critic_bwd_job(ga.job[z], *h, *crit[z], h->c_h1[z], h->c_h2[z], z, 0, c.gamma, h->dq[z], h->dz2[z], h->dz1[z]);
-    launch_gemm<GEMM_G>(ga, 2, st);
+    em.template gemm<GEMM_G>(ga, 2);
     // 9. weight gradients folded into Adam: W2, b2, W1, b1 of both critics, and linear3 (dW3 = dq^T h2, db3 = sum dq: one-row jobs);
     // on actor updates the target critics follow in the same epilogue (nothing reads them again in this update)
     for (int z = 0; z < 2; ++z) {
@@ -1034,29 +1057,229 @@ extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* 
         wgrad_job(ga.job[4 + z], h->dq[z], 1, h->c_h2[z], H, H, B, crit[z]->w3, crit[z]->b3, &h->mom[1 + z][4], h->adam, t.w3, t.b3);
     }
     ga.job[4].loss_out = h->loss;                                 // the first critic's MSE: what Agent.learn returns
-    launch_gemm<GEMM_H>(ga, 6, st);
+    em.template gemm<GEMM_H>(ga, 6);
     if (do_actor) {
         // (10-11, the policy's hidden layers on s, ran inside launches 1-2; 12, its head, runs inside 13)
         // 13-14. the UPDATED first critic on (s, pi(s)) (TD3:268)
         fwd_job(ga.job[0], h->xs, B, Dc, Dc, c.q1.w1, c.q1.b1, h->c_h1[0], H, 1);    // (xs's own action columns are not read: head_job)
         head_job(ga.job[0], D, H, h->a_h2, c.actor, nullptr, h->logits, c.max_v, c.max_w);        // pi(s)
-        launch_gemm<GEMM_F>(ga, 1, st);
+        em.template gemm<GEMM_F>(ga, 1);
         fwd_job(ga.job[0], h->c_h1[0], B, H, H, c.q1.w2, c.q1.b2, h->c_h2[0], H, 1);
         ga.job[0].dz_w3 = c.q1.w3; ga.job[0].dz_out = h->dz2[0]; ga.job[0].dz_rows = (float)B;      // 15. -mean Q's gradient at h2, in the epilogue
-        launch_gemm<GEMM_F>(ga, 1, st);
+        em.template gemm<GEMM_F>(ga, 1);
         // 16-17. ... back to the action, through the heads, linear3 of the actor + Adam
         dgrad_job(ga.job[0], h->dz2[0], B, H, c.q1.w2, h->c_h1[0], h->dz1[0], H);
         ga.job[0].da_w = c.q1.w1 + D; ga.job[0].da_ld = Dc; ga.job[0].da_out = h->dapart; ga.job[0].da_nt = h->dant();     // the action columns of W1
-        launch_gemm<GEMM_G>(ga, 1, st);
+        em.template gemm<GEMM_G>(ga, 1);
         // 17-19. through the heads' derivatives and the actor's hidden layers (the heads' part evaluated inside the backward GEMM,
         // linear3's gradient dl^T h2 as a two-row job of the weight-gradient launch)
         actor_bwd_job(ga.job[0], *h, c.actor, c.max_v, c.max_w, h->dz2[1], h->dz1[1]);
-        launch_gemm<GEMM_G>(ga, 1, st);
+        em.template gemm<GEMM_G>(ga, 1);
         wgrad_job(ga.job[0], h->dz2[1], H, h->a_h1, H, H, B, c.actor.w2, c.actor.b2, &h->mom[0][2], h->adam + 2, c.actor_t.w2, c.actor_t.b2);
         wgrad_job(ga.job[1], h->dz1[1], H, h->xs, Dc, D, B, c.actor.w1, c.actor.b1, &h->mom[0][0], h->adam + 2, c.actor_t.w1, c.actor_t.b1);
         wgrad_job(ga.job[2], h->dl, 2, h->a_h2, H, H, B, c.actor.w3, c.actor.b3, &h->mom[0][4], h->adam + 2, c.actor_t.w3, c.actor_t.b3);
-        launch_gemm<GEMM_H>(ga, 3, st);
+        em.template gemm<GEMM_H>(ga, 3);
         // (20, the soft updates of the three targets, ran in the Adam epilogues of 7, 9, 17 and 19)
+    }
+}
+namespace {
+struct Td3LaunchNow {                              // cn_td3_update: every launch goes to the stream as the chain names it
+    hipStream_t st;
+    void prep(const PrepArgs& pa) { hipLaunchKernelGGL(td3_prep_kernel<false>, dim3(pa.B), dim3(256), 0, st, pa); }
+    template <int MODE> void gemm(const GemmArgs& ga, int njobs) { launch_gemm<MODE>(ga, njobs, st); }
+};
+}  // namespace
+
+extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* batch, void* stream)
+{
+    if (const int rc = check_update("cn_td3_update", h, batch)) return rc;
+    DevScope scope(h->device);
+    Td3LaunchNow em{(hipStream_t)stream};
+    td3_chain(h, do_actor, batch, em);
+    TD3CHK(hipGetLastError());
+    return CN_OK;
+}
+
+// ---- a population of TD3 learners: P members' updates in the 7 (+ 5) launches of one --------------------------------------------
+// Member p's jobs are what td3_chain gives for a solo handle of cfgs[p]; they ride in the grid's z dimension (z = p * njobs + job)
+// of the kernels' POP = true instantiations, which read them from tables in device memory.  A handle's pointers never change, so the
+// tables of both chains (do_actor 0 / 1) and of both sampling modes are built and uploaded once, in cn_td3_pop_create;
+// cn_td3_pop_update only enqueues.
+namespace {
+struct PopStep { int mode, njobs, do_tick, gx, gy; size_t first; };      // one GEMM launch: its jobs are table[first + p * njobs + z]
+struct Td3Record {                                 // td3_chain's emitter at create time: keeps what a solo update would have launched
+    struct Step { int mode, njobs, do_tick; GemmJob job[6]; };
+    PrepArgs pa;
+    TickArgs tick;
+    Step step[12];
+    int n = 0;
+    void prep(const PrepArgs& p) { pa = p; }
+    template <int MODE> void gemm(const GemmArgs& ga, int njobs)
+    {
+        if (n >= 12 || njobs > 6) return;             // (an update is at most 11 GEMM launches of at most 6 jobs)
+        Step& s = step[n++];
+        s.mode = MODE; s.njobs = njobs; s.do_tick = ga.do_tick; tick = ga.tick;
+        for (int z = 0; z < njobs; ++z) s.job[z] = ga.job[z];
+    }
+};
+}  // namespace
+struct cn_td3_pop_s {
+    int device = 0, P = 0, B = 0;
+    int sample_mode = CN_SAMPLE_WITH_REPLACEMENT;
+    float beta1 = 0.f, beta2 = 0.f, eps = 0.f, tau = 0.f;
+    std::vector<std::unique_ptr<cn_td3_s>> mem;    // the members' workspaces and Adam state: solo handles that are never updated alone
+    void* tables = nullptr;                        // one allocation: losses [P], prep tables [2 modes][P], tick tables [2 chains][P], jobs
+    float* loss = nullptr;
+    const PrepArgs* prep[2] = {nullptr, nullptr};
+    const TickArgs* tick[2] = {nullptr, nullptr};
+    const GemmJob* jobs = nullptr;
+    std::vector<PopStep> chain[2];
+    cn_td3_pop_s() = default;
+    cn_td3_pop_s(const cn_td3_pop_s&) = delete;
+    ~cn_td3_pop_s() { if (tables) { DevScope scope(device); (void)hipFree(tables); } }
+};
+
+extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int device, cn_td3_pop_handle* out)
+{
+    const std::string f("cn_td3_pop_create");
+    if (!cfgs || !out) return td3_fail(CN_ERR_ARG, f + ": null argument");
+    if (n_members < 1 || n_members > 64) return td3_fail(CN_ERR_ARG, f + ": n_members must be 1 ... 64");
+    const int P = n_members;
+    const cn_td3_config& c0 = cfgs[0];
+    struct Named { const float* p; int member; const char* what; };
+    std::vector<Named> named;
+    for (int p = 0; p < P; ++p) {
+        const cn_td3_config& c = cfgs[p];
+        const std::string who = "member " + std::to_string(p);
+        if (c.obs_dim < 1 || c.hidden < 1 || c.batch < 1 || c.batch > 4096 || c.hidden > 4096 || c.policy_delay < 1)
+            return td3_fail(CN_ERR_CONFIG, f + ": " + who + ": obs_dim / hidden / batch / policy_delay out of range");
+        // the grid and the launch-level scalars are one for all members
+        const char* differs = c.obs_dim != c0.obs_dim ? "obs_dim" : c.hidden != c0.hidden ? "hidden" : c.batch != c0.batch ? "batch"
+            : c.policy_delay != c0.policy_delay ? "policy_delay" : c.beta1 != c0.beta1 ? "beta1" : c.beta2 != c0.beta2 ? "beta2"
+            : c.eps != c0.eps ? "eps" : c.tau != c0.tau ? "tau" : c.max_v != c0.max_v ? "max_v" : c.max_w != c0.max_w ? "max_w" : nullptr;
+        if (differs) return td3_fail(CN_ERR_CONFIG, f + ": " + who + " differs from member 0 in " + differs + " (the members share it)");
+        if (!mlp_ok(c.actor) || !mlp_ok(c.actor_t) || !mlp_ok(c.q1) || !mlp_ok(c.q1_t) || !mlp_ok(c.q2) || !mlp_ok(c.q2_t))
+            return td3_fail(CN_ERR_ARG, f + ": " + who + ": null parameter pointer");
+        if (!c.replay_s || !c.replay_a || !c.replay_r || !c.replay_s2 || !c.replay_d || !c.replay_size_dev)
+            return td3_fail(CN_ERR_ARG, f + ": " + who + ": no replay ring in the configuration (a population has no explicit-batch form)");
+        const cn_td3_mlp* nets[6] = {&c.actor, &c.actor_t, &c.q1, &c.q1_t, &c.q2, &c.q2_t};
+        static const char* const netn[6] = {"actor", "actor_t", "q1", "q1_t", "q2", "q2_t"};
+        for (int n = 0; n < 6; ++n)
+            for (const float* t : {nets[n]->w1, nets[n]->b1, nets[n]->w2, nets[n]->b2, nets[n]->w3, nets[n]->b3}) named.push_back({t, p, netn[n]});
+    }
+    // two members stepping one tensor would race inside a launch: every parameter tensor belongs to one member
+    std::sort(named.begin(), named.end(), [](const Named& a, const Named& b) { return a.p != b.p ? a.p < b.p : a.member < b.member; });
+    for (size_t i = 1; i < named.size(); ++i)
+        if (named[i].p == named[i - 1].p && named[i].member != named[i - 1].member)
+            return td3_fail(CN_ERR_CONFIG, f + ": members " + std::to_string(named[i - 1].member) + " (" + named[i - 1].what + ") and " +
+                            std::to_string(named[i].member) + " (" + named[i].what + ") name the same parameter tensor");
+    std::unique_ptr<cn_td3_pop_s> h(new (std::nothrow) cn_td3_pop_s());
+    if (!h) return td3_fail(CN_ERR_ARG, f + ": out of memory");
+    h->device = device; h->P = P; h->B = c0.batch;
+    h->beta1 = c0.beta1; h->beta2 = c0.beta2; h->eps = c0.eps; h->tau = c0.tau;
+    for (int p = 0; p < P; ++p) {
+        cn_td3_s* m = nullptr;
+        if (const int rc = learner_create(f.c_str(), cfgs[p], device, &m)) return rc;
+        h->mem.emplace_back(m);
+    }
+    DevScope scope(device);
+    // record what a solo update of every member would launch, for both chains (GEMMs, tick); the job tables' size follows from it
+    std::vector<Td3Record> rec[2];
+    size_t njobs_all = 0;
+    for (int a = 0; a < 2; ++a) {
+        rec[a].resize(P);
+        for (int p = 0; p < P; ++p) td3_chain(h->mem[p].get(), a, nullptr, rec[a][p]);
+        for (int k = 0; k < rec[a][0].n; ++k) njobs_all += (size_t)P * rec[a][0].step[k].njobs;
+    }
+    Pool count{nullptr};
+    float* loss = nullptr; PrepArgs* prep[2] = {nullptr, nullptr}; TickArgs* tick[2] = {nullptr, nullptr}; GemmJob* jobs = nullptr;
+    auto layout = [&](Pool& pl) {
+        pl.take(loss, (size_t)P);
+        for (int q = 0; q < 2; ++q) pl.take(prep[q], (size_t)P);
+        for (int q = 0; q < 2; ++q) pl.take(tick[q], (size_t)P);
+        pl.take(jobs, njobs_all);
+    };
+    layout(count);
+    hipError_t e = hipMalloc(&h->tables, count.size);
+    if (e != hipSuccess) return td3_fail(CN_ERR_HIP, f + ": hipMalloc: " + hipGetErrorString(e));
+    e = hipMemset(h->tables, 0, count.size);
+    if (e != hipSuccess) return td3_fail(CN_ERR_HIP, f + ": hipMemset: " + hipGetErrorString(e));
+    Pool assign{(char*)h->tables};
+    layout(assign);
+    // the losses lie side by side: a member writes pop loss [p], not its own handle's (recorded again below, with that pointer)
+    std::vector<PrepArgs> hprep((size_t)2 * P);
+    std::vector<TickArgs> htick((size_t)2 * P);
+    std::vector<GemmJob> hjobs(njobs_all);
+    size_t first = 0;
+    for (int a = 0; a < 2; ++a) {
+        for (int p = 0; p < P; ++p) {
+            cn_td3_s* m = h->mem[p].get();
+            m->loss = loss + p;
+            for (int mode : {CN_SAMPLE_DISTINCT, CN_SAMPLE_WITH_REPLACEMENT}) {      // (ends on the mode a fresh handle has)
+                m->sample_mode = mode;
+                rec[a][p].n = 0;
+                td3_chain(m, a, nullptr, rec[a][p]);
+                hprep[(size_t)mode * P + p] = rec[a][p].pa;
+            }
+            htick[(size_t)a * P + p] = rec[a][p].tick;
+        }
+        for (int k = 0; k < rec[a][0].n; ++k) {
+            const Td3Record::Step& s0 = rec[a][0].step[k];
+            constexpr int TI[3] = {16, 16, 32}, TJ[3] = {16, 32, 32};      // the kernels' tiles of C (launch_gemm)
+            PopStep ps{s0.mode, s0.njobs, s0.do_tick, 0, 0, first};
+            for (int z = 0; z < s0.njobs; ++z) {
+                const int x_ = (s0.job[z].J + TJ[s0.mode] - 1) / TJ[s0.mode], y_ = (s0.job[z].I + TI[s0.mode] - 1) / TI[s0.mode];
+                ps.gx = x_ > ps.gx ? x_ : ps.gx; ps.gy = y_ > ps.gy ? y_ : ps.gy;
+            }
+            if (first + (size_t)P * s0.njobs > hjobs.size()) return td3_fail(CN_ERR_ARG, f + ": job table size");      // (never: counted above)
+            for (int p = 0; p < P; ++p)
+                for (int z = 0; z < s0.njobs; ++z) hjobs[first + (size_t)p * s0.njobs + z] = rec[a][p].step[k].job[z];
+            first += (size_t)P * s0.njobs;
+            h->chain[a].push_back(ps);
+        }
+    }
+    static_assert(CN_SAMPLE_WITH_REPLACEMENT == 0 && CN_SAMPLE_DISTINCT == 1, "the prep tables are indexed by the mode");
+    for (int q = 0; q < 2; ++q) {
+        e = hipMemcpy(prep[q], hprep.data() + (size_t)q * P, sizeof(PrepArgs) * P, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(tick[q], htick.data() + (size_t)q * P, sizeof(TickArgs) * P, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return td3_fail(CN_ERR_HIP, f + ": hipMemcpy: " + hipGetErrorString(e));
+        h->prep[q] = prep[q]; h->tick[q] = tick[q];
+    }
+    e = hipMemcpy(jobs, hjobs.data(), sizeof(GemmJob) * hjobs.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return td3_fail(CN_ERR_HIP, f + ": hipMemcpy: " + hipGetErrorString(e));
+    h->loss = loss; h->jobs = jobs;
+    *out = h.release();
+    return CN_OK;
+}
+extern "C" void cn_td3_pop_destroy(cn_td3_pop_handle h) { delete h; }
+extern "C" int cn_td3_pop_members(cn_td3_pop_handle h) { return h ? h->P : 0; }
+extern "C" const float* cn_td3_pop_loss_dev(cn_td3_pop_handle h) { return h ? h->loss : nullptr; }
+extern "C" const float* cn_td3_pop_batch_dev(cn_td3_pop_handle h, int member, int what)
+{
+    return (h && member >= 0 && member < h->P) ? batch_dev(h->mem[member].get(), what) : nullptr;
+}
+extern "C" int cn_td3_pop_set_replay_sample(cn_td3_pop_handle h, int mode)
+{
+    if (!h) return td3_fail(CN_ERR_ARG, "cn_td3_pop_set_replay_sample: null handle");
+    if (mode != CN_SAMPLE_WITH_REPLACEMENT && mode != CN_SAMPLE_DISTINCT)
+        return td3_fail(CN_ERR_ARG, "cn_td3_pop_set_replay_sample: mode must be CN_SAMPLE_WITH_REPLACEMENT (0) or CN_SAMPLE_DISTINCT (1); the handle keeps its mode");
+    h->sample_mode = mode;
+    return CN_OK;
+}
+
+extern "C" int cn_td3_pop_update(cn_td3_pop_handle h, int do_actor, void* stream)
+{
+    if (!h) return td3_fail(CN_ERR_ARG, "cn_td3_pop_update: null handle");
+    DevScope scope(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int a = do_actor ? 1 : 0;
+    hipLaunchKernelGGL(td3_prep_kernel<true>, dim3(h->B, h->P), dim3(256), 0, st, h->prep[h->sample_mode]);
+    for (const PopStep& s : h->chain[a]) {
+        const PopGemmArgs ga{h->jobs + s.first, h->tick[a], s.njobs, h->beta1, h->beta2, h->eps, h->tau, s.do_tick};
+        const dim3 grid(s.gx, s.gy, h->P * s.njobs);
+        if (s.mode == GEMM_F) hipLaunchKernelGGL((td3_fwd_kernel<false, true>), grid, dim3(256), 0, st, ga);
+        else if (s.mode == GEMM_G) hipLaunchKernelGGL((td3_dgrad_kernel<false, true>), grid, dim3(256), 0, st, ga);
+        else hipLaunchKernelGGL((td3_wgrad_kernel<false, true>), grid, dim3(256), 0, st, ga);
     }
     TD3CHK(hipGetLastError());
     return CN_OK;
@@ -1111,7 +1334,7 @@ extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void*
     const int B = h->B, D = h->D, Dc = D + 2, H = h->H, qnt = h->qnt();
     // 1. sample / gather (ddpg.py:208-214); no noise is drawn
     const PrepArgs pa = prep_args(*h, c, batch);
-    hipLaunchKernelGGL(td3_prep_kernel, dim3(B), dim3(256), 0, st, pa);
+    hipLaunchKernelGGL(td3_prep_kernel<false>, dim3(B), dim3(256), 0, st, pa);
     GemmArgs ga;
     memset(&ga, 0, sizeof(ga));
     adam_args(ga, *h, c, 1);                        // both optimizers step on every update
@@ -1858,7 +2081,7 @@ extern "C" int cn_sac_update(cn_sac_handle h, const cn_td3_batch* batch, void* s
     pa.xs = h->xs; pa.x2 = h->x2; pa.r = h->r; pa.d = h->d; pa.noise = h->eps; pa.counter = h->counter;
     pa.seed = c.seed; pa.B = B; pa.D = D; pa.noise_std = 1.f; pa.noise_clip = 3.4e38f;       // (eps x 1, clipped at a bound no draw reaches)
     pa.mode = h->sample_mode;
-    hipLaunchKernelGGL(td3_prep_kernel, dim3(B), dim3(256), 0, st, pa);
+    hipLaunchKernelGGL(td3_prep_kernel<false>, dim3(B), dim3(256), 0, st, pa);
     GemmArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.beta1 = c.beta1; ga.beta2 = c.beta2; ga.eps = c.eps; ga.tau = c.tau;

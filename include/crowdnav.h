@@ -368,6 +368,34 @@ int cn_replay_sample_indices(uint64_t seed, uint64_t counter, int B, const int64
                              int device, void* stream);
 const char* cn_td3_last_error(void);
 
+/* A population: n_members independent TD3 learners updated by the 7 (+ 5) launches of ONE cn_td3_update -- seed studies and
+ * hyper-parameter sweeps on one card, where a single update is a chain of small dependent launches that leave most of it idle.
+ * Member p's work rides in the grid's z dimension of the same kernels (their *_pop_kernel instantiations, which read their jobs from
+ * tables in device memory that cn_td3_pop_create builds and uploads once; cn_td3_pop_update only enqueues, does no host read and no
+ * copy, and is capturable on one stream like cn_td3_update).
+ * Statement: after any sequence of cn_td3_pop_update calls, member p equals a solo handle made by cn_td3_create from cfgs[p] (on its
+ * own copies of the parameters and the ring) and given cn_td3_update(h, do_actor, NULL, stream) with the same sequence of do_actor
+ * values, in the same sampling mode: the six networks, Adam's state, the loss and the gathered batch (cn_td3_pop_batch_dev), BIT FOR
+ * BIT.  It depends neither on n_members nor on p: a member's tile is computed by the same instructions in the same order as a solo
+ * handle's, from the member's own update counter, seed and *replay_size_dev (all read on the device).
+ * Per member (cfgs[p]): seed, lr_actor, lr_critic, gamma, noise_std, noise_clip, the six networks, the replay ring and its size.
+ * Shared -- the grid and the launch-level scalars are one, so cfgs[p] must equal cfgs[0] in: obs_dim, hidden, batch, policy_delay,
+ * beta1, beta2, eps, tau, max_v, max_w; otherwise CN_ERR_CONFIG naming the field and the member.
+ * Also refused: n_members outside 1 ... 64, a NULL parameter pointer, a member without a replay ring (there is no explicit-batch form)
+ * -- CN_ERR_ARG; two members naming the same parameter tensor (pointer equality over all members' cn_td3_mlp fields: they would race
+ * inside a launch) -- CN_ERR_CONFIG.  Texts in cn_td3_last_error.
+ * cn_td3_pop_loss_dev: [n_members], member p's first-critic MSE of the last update.  cn_td3_pop_batch_dev(h, p, what): as
+ * cn_td3_batch_dev for member p; a member or what out of range: NULL.  cn_td3_pop_set_replay_sample: as cn_td3_set_replay_sample, one
+ * mode for all members (an unknown mode: CN_ERR_ARG and the handle keeps its mode). */
+typedef struct cn_td3_pop_s* cn_td3_pop_handle;
+int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int device, cn_td3_pop_handle* out);
+void cn_td3_pop_destroy(cn_td3_pop_handle h);
+int cn_td3_pop_update(cn_td3_pop_handle h, int do_actor, void* stream);      /* replay path only */
+int cn_td3_pop_members(cn_td3_pop_handle h);
+const float* cn_td3_pop_loss_dev(cn_td3_pop_handle h);                        /* [n_members] */
+const float* cn_td3_pop_batch_dev(cn_td3_pop_handle h, int member, int what); /* as cn_td3_batch_dev */
+int cn_td3_pop_set_replay_sample(cn_td3_pop_handle h, int mode);
+
 /* The DDPG update -- Agent.learn of the reference's ddpg.py:198-243, the baseline learner of start_ddpg_training.py -- on the
  * same GEMM kernels as cn_td3_update (crowdnav_td3.hip), 8 launches per update.  One critic and one target critic, no policy
  * delay, no target-policy noise: y = r + (1 - d) gamma Q_t(s2, pi_t(s2)) (ddpg.py:219-222), critic loss mean((Q(s, a) - y)^2)

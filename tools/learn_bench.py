@@ -3,7 +3,10 @@
 (Agent.enable_fused_update: 7 + 5 hand-written launches, csrc/crowdnav_td3.hip; also captured into hipGraphs here).
 --replay-sample {with,without}: how the updates draw their mini-batch (cn_*_set_replay_sample; `without` times the fused and the
 eager update only: the captured PyTorch update draws with replacement).  --samples N (with CN_LEARN_MODES=fused): the median, min and
-max of N samples of 400 updates instead of one mean.  --algo dqn: cn_dqn_update at (361 of 363, 300, batch) in the same way (fused only)."""
+max of N samples of 400 updates instead of one mean.  --algo dqn: cn_dqn_update at (361 of 363, 300, batch) in the same way (fused only).
+--population P: P solo cn_td3_update handles updated one after another on one stream against ONE cn_td3_pop_update of P members
+(crowdnav.td3.Population) on the same build -- the medians of 7 samples of 400 updates, their spread and the ratio; the solo line
+(one handle) is the figure to hold against the parent commit."""
 import argparse, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "drl-based-mapless-crowd-navigation-with-perceived-risk_amd"))
@@ -14,6 +17,7 @@ ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDe
 ap.add_argument("--replay-sample", default="with", choices=["with", "without"])
 ap.add_argument("--algo", default="td3", choices=["td3", "dqn"])
 ap.add_argument("--samples", type=int, default=0)
+ap.add_argument("--population", type=int, default=0)
 args = ap.parse_args()
 RS = args.replay_sample
 
@@ -40,9 +44,39 @@ def report(B, name, fn):
         print("batch %5d: %s %.3f ms per update (replay sample %s)" % (B, name, timed(fn), RS), flush=True)
 
 
+def samples_of(fn, n=7):
+    ms = [timed(fn, warm=50 if j == 0 else 0) for j in range(n)]
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def population_bench(B, P):
+    from crowdnav.td3 import Population
+    line = lambda name, m: "%s median %.4f ms per update (min %.4f, max %.4f, 7 samples of 400)" % ((name,) + m)
+
+    def agents():
+        out = [Agent(obs_dim=398, device="cuda", seed=p, batch_size=B, memory_size=20000, replay_sample=RS) for p in range(P)]
+        for a in out: fill(a, 10000)
+        return out
+    solo = agents()
+    for a in solo: a.enable_fused_update()
+    one = samples_of(solo[0].learn)
+    print("batch %5d: %s" % (B, line("solo (one handle)", one)), flush=True)
+    seq = samples_of(lambda i: [a.learn(i) for a in solo])
+    print("batch %5d: %s" % (B, line("%d solo handles in sequence" % P, seq)), flush=True)
+    del solo
+    pop = Population(agents())
+    tog = samples_of(pop.learn)
+    print("batch %5d: %s" % (B, line("population of %d" % P, tog)), flush=True)
+    print("batch %5d: population %d: %.4f ms against %.4f ms in sequence: ratio %.3f (%.4f ms per member and update)" % (
+        B, P, tog[0], seq[0], tog[0] / seq[0], tog[0] / P), flush=True)
+
+
 ONLY_FUSED = os.environ.get("CN_LEARN_MODES", "") == "fused"      # (tools/learn_profile.sh: the fused chain alone under rocprofv3)
 for B in [int(x) for x in os.environ.get("CN_BATCHES", "128,1024" if args.algo == "td3" else "64").split(",")]:
     row = []
+    if args.population > 0:
+        population_bench(B, args.population)
+        continue
     if args.algo == "dqn":
         from crowdnav import dqn
         ag = dqn.Agent(obs_dim=361, obs_ld=363, device="cuda", seed=0, batch_size=B, memory_size=200000, replay_sample=RS)
