@@ -41,8 +41,11 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_td3_set_replay_sample", "cn_ddpg_set_replay_sample", "cn_dqn_set_replay_sample", "cn_sac_set_replay_sample",
            "cn_replay_sample_indices", "cn_replay_write", "cn_episode_log_add",
            "cn_td3_pop_create", "cn_td3_pop_destroy", "cn_td3_pop_update", "cn_td3_pop_members", "cn_td3_pop_loss_dev",
-           "cn_td3_pop_batch_dev", "cn_td3_pop_set_replay_sample"]
+           "cn_td3_pop_batch_dev", "cn_td3_pop_set_replay_sample",
+           "cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", "cn_actor_pop_pack", "cn_actor_pop_forward",
+           "cn_actor_pop_weights"]
 CN_TD3_POP_MAX = 64         # include/crowdnav.h: cn_td3_pop_create's n_members is 1 ... 64
+CN_ACTOR_POP_MAX = 64       # include/crowdnav.h: cn_actor_pop_create's n_members is 1 ... 64
 CN_SAMPLE_WITH_REPLACEMENT, CN_SAMPLE_DISTINCT = 0, 1      # include/crowdnav.h: cn_*_set_replay_sample
 REPLAY_SAMPLE = {"with": CN_SAMPLE_WITH_REPLACEMENT, "without": CN_SAMPLE_DISTINCT}
 
@@ -124,6 +127,12 @@ class CnActorWeights(C.Structure):
 class CnTd3Mlp(C.Structure):
     """Mirror of `cn_td3_mlp`: device pointers to one network's nn.Linear storages."""
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3")]
+
+
+class CnActorPopMember(C.Structure):
+    """Mirror of `cn_actor_pop_member` (include/crowdnav.h): one member of cn_actor_pop_create."""
+    _fields_ = [("actor", CnTd3Mlp), ("obs", C.c_void_p), ("action", C.c_void_p), ("n", C.c_int32), ("reserved", C.c_int32),
+                ("max_v", C.c_float), ("max_w", C.c_float), ("sigma", C.c_float), ("reserved_f", C.c_float), ("seed", C.c_uint64)]
 
 
 class CnTd3Config(C.Structure):
@@ -350,6 +359,12 @@ def lib():
         L.cn_td3_pop_loss_dev.argtypes = [vp]; L.cn_td3_pop_loss_dev.restype = vp
         L.cn_td3_pop_batch_dev.argtypes = [vp, C.c_int, C.c_int]; L.cn_td3_pop_batch_dev.restype = vp
         L.cn_td3_pop_set_replay_sample.argtypes = [vp, C.c_int]
+        L.cn_actor_pop_create.argtypes = [C.POINTER(CnActorPopMember), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]      # an array of members
+        L.cn_actor_pop_destroy.argtypes = [vp]; L.cn_actor_pop_destroy.restype = None
+        L.cn_actor_pop_members.argtypes = [vp]
+        L.cn_actor_pop_pack.argtypes = [vp, vp]
+        L.cn_actor_pop_forward.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int, vp]      # counters: a host array [n_members]
+        L.cn_actor_pop_weights.argtypes = [vp, C.c_int, C.POINTER(CnActorWeights)]
         L.cn_ddpg_create.argtypes = [C.POINTER(CnDdpgConfig), C.c_int, C.POINTER(vp)]
         L.cn_ddpg_destroy.argtypes = [vp]; L.cn_ddpg_destroy.restype = None
         L.cn_ddpg_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]

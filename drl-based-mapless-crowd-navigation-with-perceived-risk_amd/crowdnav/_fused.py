@@ -1,5 +1,5 @@
 """What the TD3, DDPG, DQN and SAC agents share on the way to libcrowdnav's fused learners (csrc/crowdnav_td3.hip): the network
-pointers, views of the library's device memory, and the owner of a learner handle."""
+pointers, views of the library's device memory, and the owners of a learner handle and of a population's handles."""
 import ctypes as C
 
 import torch
@@ -123,6 +123,58 @@ class FusedPopulation:
         try:
             if self.h:
                 self._L.cn_td3_pop_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+class FusedPopulationActor:
+    """Owns one cn_actor_pop handle: P actors run by one launch and re-packed by one launch (include/crowdnav.h,
+    cn_actor_pop_create).  members: the CnActorPopMember of every member, in member order; keep: whatever their pointers point into
+    (the handle holds them for its lifetime).  Errors raise CrowdNavError("<function>: <cn_last_error>")."""
+
+    def __init__(self, members, obs_dim, device, dev_index, keep=None):
+        self._L = L = _abi.lib()
+        self.device, self.P, self.obs_dim, self._keep = device, len(members), int(obs_dim), keep
+        self.members = (_abi.CnActorPopMember * self.P)(*members)
+        self._counters = (C.c_uint64 * self.P)()
+        self.h = C.c_void_p()
+        self._check("create", L.cn_actor_pop_create(self.members, self.P, self.obs_dim, dev_index, C.byref(self.h)))
+
+    def _check(self, what, rc):
+        if rc != 0:
+            raise _abi.CrowdNavError("cn_actor_pop_%s: %s" % (what, self._L.cn_last_error().decode()))
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def pack(self):
+        """cn_actor_pop_pack on torch's current stream: every member's packed weights from its nn.Linear storages, one launch."""
+        self._check("pack", self._L.cn_actor_pop_pack(self.h, self._stream()))
+
+    def forward(self, counters, add_noise=True):
+        """cn_actor_pop_forward on torch's current stream: one launch; counters[p] keys member p's exploration noise."""
+        c = self._counters
+        for p, v in enumerate(counters):
+            c[p] = v
+        self._check("forward", self._L.cn_actor_pop_forward(self.h, c, int(bool(add_noise)), self._stream()))
+
+    def weights(self, member):
+        """The CnActorWeights of `member` (cn_actor_pop_weights): the handle's packed buffers, the member's biases and w3."""
+        w = _abi.CnActorWeights()
+        self._check("weights", self._L.cn_actor_pop_weights(self.h, int(member), C.byref(w)))
+        return w
+
+    def packed(self, member):
+        """Views (w1p [Dp, 256], w2p [256, 256]) of the handle's packed buffers of `member`, alive as long as the handle."""
+        w = self.weights(member)
+        return (_device_view(w.w1p, (w.obs_dim_padded, 256), torch.float32, self.device),
+                _device_view(w.w2p, (256, 256), torch.float32, self.device))
+
+    def __del__(self):
+        try:
+            if self.h:
+                self._L.cn_actor_pop_destroy(self.h)
                 self.h = None
         except Exception:
             pass

@@ -547,7 +547,10 @@ class Population:
     """P TD3 agents on one device whose updates run as ONE chain of 7 (+ 5) launches (cn_td3_pop_update): member p's update is, bit
     for bit, the update agents[p].enable_fused_update() would run alone.  The agents keep their networks, replay rings, seeds,
     learning rates, gamma and target-noise parameters; they must agree in obs_dim, hidden, batch_size, policy_delay, tau, max_v,
-    max_w and Adam's betas / eps (the library names the field and the member otherwise).  Acting stays per member (act_mfma)."""
+    max_w and Adam's betas / eps (the library names the field and the member otherwise).
+    Acting: bind_act(obs_list, out_list) once, then act() is ONE launch for all members (cn_actor_pop_forward) and sync_actors() ONE
+    re-pack of all their actors (cn_actor_pop_pack); member p's actions are, bit for bit, agents[p].act_mfma's, and both advance the
+    same per-agent noise counter, so the two may be mixed."""
 
     def __init__(self, agents, replay_sample=None):
         agents = list(agents)
@@ -561,6 +564,7 @@ class Population:
         self.agents, self.device, self.policy_delay, self.batch_size = agents, a0.device, a0.policy_delay, a0.batch_size
         self._fused = FusedPopulation([a.fused_config() for a in agents], self.device, a0._dev_index,
                                       replay_sample=a0.replay_sample if replay_sample is None else replay_sample)
+        self._actors = self._act_io = self._act_key = None
 
     def __len__(self):
         return len(self.agents)
@@ -574,6 +578,62 @@ class Population:
         Returns the members' first-critic losses [P] as a fresh tensor.  The caller gates on ready(): the kernels read each ring's
         live size on the device and do not refuse a ring shorter than the batch."""
         return self._fused.update(int(step % self.policy_delay == 0))
+
+    def _noise_key(self):
+        """What cn_actor_pop_create froze into the members' jobs besides the pointers."""
+        return [(a._noise_seed, float(a.explore_sigma), float(a.max_v), float(a.max_w)) for a in self.agents]
+
+    def bind_act(self, obs_list, out_list):
+        """Create the cn_actor_pop handle for fixed buffers: obs_list[p] [n_p, obs_dim] and out_list[p] [n_p, 2] are member p's
+        observations and actions (contiguous float32 on the population's device; n_p may differ and may be 0), read and written in
+        place by every act().  Packs the actors once, on torch's current stream."""
+        from . import _abi
+        from ._fused import FusedPopulationActor, mlp_of
+        obs_list, out_list = list(obs_list), list(out_list)
+        if len(obs_list) != len(self.agents) or len(out_list) != len(self.agents):
+            raise ValueError("bind_act takes one observation and one action buffer per member")
+        D, dev = self.agents[0].actor.linear1.in_features, self.agents[0]._dev_index
+        members = []
+        for p, (a, o, u) in enumerate(zip(self.agents, obs_list, out_list)):
+            ok = (o.dim() == 2 and o.shape[1] == D and tuple(u.shape) == (o.shape[0], 2) and o.is_contiguous() and u.is_contiguous()
+                  and o.dtype == torch.float32 and u.dtype == torch.float32 and o.is_cuda and u.is_cuda and o.get_device() == dev == u.get_device())
+            if not ok or a.actor.linear1.in_features != D or a.actor.linear1.out_features != 256:
+                raise ValueError("member %d: obs must be [n, %d] and out [n, 2], contiguous float32 on %s, for an actor of hidden width 256"
+                                 % (p, D, self.device))
+            members.append(_abi.CnActorPopMember(actor=mlp_of(a.actor), obs=o.data_ptr(), action=u.data_ptr(), n=o.shape[0], reserved=0,
+                                                 max_v=a.max_v, max_w=a.max_w, sigma=a.explore_sigma, reserved_f=0.0, seed=a._noise_seed))
+        self._actors = FusedPopulationActor(members, D, self.device, self.agents[0]._dev_index, keep=(obs_list, out_list))
+        self._act_io, self._act_key = (obs_list, out_list), self._noise_key()
+        self._actors.pack()
+        return self
+
+    def _bound(self):
+        if self._actors is None:
+            raise RuntimeError("Population.bind_act(obs_list, out_list) first: the one-launch actor works on fixed buffers")
+        if self._act_key != self._noise_key():       # set_noise_state / explore_sigma changed a member's key: the jobs are rebuilt
+            self.bind_act(*self._act_io)
+        return self._actors
+
+    @torch.no_grad()
+    def act(self, add_noise=True):
+        """Every member's Agent.act on its bound observations as ONE launch (cn_actor_pop_forward) on torch's current stream; the
+        actions land in the bound buffers, which are returned.  Each agent's call counter advances as in act_mfma (it keys the
+        noise whether or not noise is added), so noise_state() / set_noise_state() cover both paths."""
+        actors = self._bound()
+        for a in self.agents:
+            a._fused_calls += 1
+        actors.forward([a._fused_calls for a in self.agents], add_noise)
+        return self._act_io[1]
+
+    def sync_actors(self):
+        """Re-pack every member's actor from its nn.Linear storages (cn_actor_pop_pack: one launch on torch's current stream, no
+        transposed staging copy); call after the weights change, as sync_fused_weights for one agent."""
+        self._bound().pack()
+
+    def actor_weights(self, p):
+        """The CnActorWeights of member p (cn_actor_pop_weights): usable with cn_actor_forward / cn_rollout_policy while this
+        population's binding lives."""
+        return self._bound().weights(p)
 
     def set_replay_sample(self, replay_sample):
         self._fused.set_replay_sample(replay_sample)

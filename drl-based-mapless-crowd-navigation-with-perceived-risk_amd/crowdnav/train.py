@@ -584,8 +584,10 @@ def train_population(a):
     """--population P: P independent TD3 runs, seeds a.seed ... a.seed + P - 1, whose updates are ONE cn_td3_pop_update per update
     (crowdnav.td3.Population) instead of P processes.  Member p has what `train()` with --seed <seed + p> has -- its environment
     handle of --envs environments, its Agent, replay, episode log, statistics -- and writes what that run writes into
-    <out>/member<p>/.  Per launch: P act launches, one grouped environment step (cn_step_multi), P replay writes and P log adds; once
-    EVERY member's replay holds more than a batch, --updates population updates and the P actor re-packs.
+    <out>/member<p>/.  Per launch: ONE act launch for all members (--population-act one-launch, Population.act; per-member: P
+    act_mfma calls), one grouped environment step (cn_step_multi), P replay writes and P log adds; once EVERY member's replay holds more
+    than a batch, --updates population updates and ONE re-pack of the P actors (per-member: P sync_fused_weights, 4 launches each).
+    The two --population-act values give the same run, bit for bit.
     Member p's run IS the solo run --seed <seed + p> --learner fused (same parameters, same CSV rows) as long as the members' rings pass
     the batch size on the same launch: a member whose ring is not ready yet (it lost rows to reset launches) holds the others back, so
     that the update counters -- which key the sampling and drive policy_delay -- stay aligned; from then on that member's solo run
@@ -624,13 +626,20 @@ def train_population(a):
     elogs = [DeviceEpisodeLog(obs.device, a.max_csv_rows) for _ in range(P)]
     learning = False
     updates_done = 0
-    for ag in agents:
-        ag.sync_fused_weights()
+    one_launch = getattr(a, "population_act", "one-launch") == "one-launch"
+    if one_launch:
+        pop.bind_act([obs[r] for r in rows], [act[r] for r in rows])      # (packs the actors)
+    else:
+        for ag in agents:
+            ag.sync_fused_weights()
     step_s = (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0
     reward, done = envs.reward, envs.done
     for it in range(1, a.launches + 1):
-        for ag, r in zip(agents, rows):
-            ag.act_mfma(obs[r], out=act[r], add_noise=True)
+        if one_launch:
+            pop.act(add_noise=True)
+        else:
+            for ag, r in zip(agents, rows):
+                ag.act_mfma(obs[r], out=act[r], add_noise=True)
         prev.copy_(obs)
         envs.fork()                                                    # the members' steps wait for the actions ...
         step_all()
@@ -648,8 +657,11 @@ def train_population(a):
             for u in range(a.updates):
                 updates_done += 1
                 pop.learn(updates_done)
-            for ag in agents:
-                ag.sync_fused_weights()
+            if one_launch:
+                pop.sync_actors()
+            else:
+                for ag in agents:
+                    ag.sync_fused_weights()
         last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
         if it % a.log_every == 0 or last_launch:
             for p, m in enumerate(members):
@@ -767,6 +779,9 @@ def parse_args(argv=None):
     ap.add_argument("--population", type=int, default=0, help="P > 0: train P independent TD3 agents, seeds --seed ... --seed + P - 1, their updates "
                     "as one cn_td3_pop_update (1 ... 64; --algo td3 --learner fused only, not with --evaluate or --load); member p has its own "
                     "--envs environments and writes into <out>/member<p>/ what the solo run --seed <seed + p> writes into <out>")
+    ap.add_argument("--population-act", default=None, choices=["one-launch", "per-member"], help="--population only: one-launch (default) = all "
+                    "members act in one cn_actor_pop_forward and re-pack in one cn_actor_pop_pack per training launch; per-member = one "
+                    "cn_actor_forward and one 4-launch re-pack per member.  Same results, bit for bit")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="default: runs/<algo>")
     ap.add_argument("--csv", action="store_true", help="one CSV row per finished episode in the reference's 8-column schema (recorded on the device, appended to the file at "
@@ -813,6 +828,10 @@ def parse_args(argv=None):
             ap.error("--population starts its members fresh: --load is not supported")
         if a.reset_mode != "next":
             ap.error("--population collects with the next-step reset only (--reset-mode next)")
+    if a.population_act is not None and not a.population:
+        ap.error("--population-act selects how a --population acts: it needs --population")
+    if a.population_act is None:
+        a.population_act = "one-launch"
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     return a

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -815,6 +816,123 @@ extern "C" int cn_actor_forward(const cn_actor_weights* w, const float* obs, flo
     hipLaunchKernelGGL(cn_actor_kernel, dim3((n + 15) / 16), dim3(512), lds, (hipStream_t)stream, obs, n, w->obs_dim, Dp,
                        w->w1p, w->b1, w->w2p, w->b2, w->w3, w->b3, action, max_v, max_w, sigma, seed, counter);
     HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+// ---- a population's actors: one forward launch and one pack launch for all members (kernels: crowdnav_kernel.hip, unit 6) ----------
+extern "C" __global__ void cn_actor_pop_kernel(const CnActorPopJob* table, int D, int Dp, int add_noise, CnActorPopCounters ctr);
+extern "C" __global__ void cn_actor_pop_pack_kernel(const CnActorPopPackJob* table, int D, int Dp);
+
+struct cn_actor_pop_s {
+    int device = 0, P = 0, D = 0, Dp = 0, tiles = 0;      // tiles: the widest member's, the grid's x (0: nothing to launch)
+    size_t lds = 0;
+    void* mem = nullptr;                                   // one allocation: the two tables, then every member's w1p and w2p
+    const CnActorPopJob* jobs = nullptr;
+    const CnActorPopPackJob* pack = nullptr;
+    std::vector<cn_actor_weights> weights;
+    cn_actor_pop_s() = default;
+    cn_actor_pop_s(const cn_actor_pop_s&) = delete;
+    ~cn_actor_pop_s() { if (mem) { DeviceScope scope(device); (void)hipFree(mem); } }
+};
+
+extern "C" int cn_actor_pop_create(const cn_actor_pop_member* members, int n_members, int obs_dim, int device, cn_actor_pop_handle* out)
+{
+    const std::string f("cn_actor_pop_create");
+    if (!members) return fail(CN_ERR_ARG, f + ": members is null");
+    if (!out) return fail(CN_ERR_ARG, f + ": out is null");
+    if (n_members < 1 || n_members > CN_ACTOR_POP_MAX) return fail(CN_ERR_ARG, f + ": n_members must be 1 ... 64");
+    if (obs_dim < 1) return fail(CN_ERR_CONFIG, f + ": obs_dim must be at least 1");
+    const int64_t Dp64 = ((int64_t)obs_dim + 31) / 32 * 32;
+    const size_t lds = sizeof(float) * (16 * ((size_t)Dp64 + 1) + 16 * 257);       // cn_actor_forward's tile: X (layer 2 reuses it), H
+    const int P = n_members, D = obs_dim, Dp = (int)Dp64;
+    if (lds > 160 * 1024) return fail(CN_ERR_CONFIG, f + ": obs_dim: observation too wide for one LDS tile");
+    int tiles = 0;
+    for (int p = 0; p < P; ++p) {
+        const cn_actor_pop_member& m = members[p];
+        const std::string who = ": member " + std::to_string(p) + ": ";
+        const float* const ps[6] = {m.actor.w1, m.actor.b1, m.actor.w2, m.actor.b2, m.actor.w3, m.actor.b3};
+        static const char* const pn[6] = {"actor.w1", "actor.b1", "actor.w2", "actor.b2", "actor.w3", "actor.b3"};
+        for (int i = 0; i < 6; ++i)
+            if (!ps[i]) return fail(CN_ERR_ARG, f + who + pn[i] + " is null");
+        if (m.n < 0) return fail(CN_ERR_ARG, f + who + "n is negative");
+        if (m.n > 0 && !m.obs) return fail(CN_ERR_ARG, f + who + "obs is null");
+        if (m.n > 0 && !m.action) return fail(CN_ERR_ARG, f + who + "action is null");
+        tiles = std::max(tiles, (int)(((int64_t)m.n + 15) / 16));
+    }
+    std::unique_ptr<cn_actor_pop_s> h(new (std::nothrow) cn_actor_pop_s());
+    if (!h) return fail(CN_ERR_ARG, f + ": out of memory");
+    int dev = device;
+    if (dev < 0) HIPCHK(hipGetDevice(&dev));
+    h->device = dev; h->P = P; h->D = D; h->Dp = Dp; h->tiles = tiles; h->lds = lds;
+    DeviceScope scope(dev);
+    // [jobs P][pack jobs P] rounded up to 256 bytes, then per member w1p [Dp][256] and w2p [256][256] (16-byte loads: both sizes are
+    // multiples of 1 KB)
+    const size_t n1 = (size_t)Dp * 256, n2 = (size_t)256 * 256;
+    const size_t tab = (sizeof(CnActorPopJob) * P + sizeof(CnActorPopPackJob) * P + 255) & ~(size_t)255;
+    HIPCHK(hipMalloc(&h->mem, tab + sizeof(float) * (n1 + n2) * P));
+    CnActorPopJob* jobs = (CnActorPopJob*)h->mem;
+    CnActorPopPackJob* pack = (CnActorPopPackJob*)(jobs + P);
+    float* wbuf = (float*)((char*)h->mem + tab);
+    std::vector<CnActorPopJob> hj(P);
+    std::vector<CnActorPopPackJob> hp(P);
+    h->weights.resize(P);
+    for (int p = 0; p < P; ++p) {
+        const cn_actor_pop_member& m = members[p];
+        float* w1p = wbuf + (size_t)p * (n1 + n2);
+        float* w2p = w1p + n1;
+        hj[p] = CnActorPopJob{m.obs, w1p, m.actor.b1, w2p, m.actor.b2, m.actor.w3, m.actor.b3, m.action, m.n, m.max_v, m.max_w, m.sigma, m.seed};
+        hp[p] = CnActorPopPackJob{m.actor.w1, m.actor.w2, w1p, w2p};
+        h->weights[p] = cn_actor_weights{w1p, m.actor.b1, w2p, m.actor.b2, m.actor.w3, m.actor.b3, D, Dp, 256, 0};
+    }
+    HIPCHK(hipMemcpy(jobs, hj.data(), sizeof(CnActorPopJob) * P, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(pack, hp.data(), sizeof(CnActorPopPackJob) * P, hipMemcpyHostToDevice));
+    h->jobs = jobs; h->pack = pack;
+    if (lds > 64 * 1024) {   // hipFuncSetAttribute is per device: once per ordinal, under a lock (as cn_actor_forward does for its kernel)
+        static std::mutex mu;
+        static bool attr_set[64] = {false};
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 64 || !attr_set[dev]) {
+            HIPCHK(hipFuncSetAttribute((const void*)cn_actor_pop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            if (dev < 64) attr_set[dev] = true;
+        }
+    }
+    *out = h.release();
+    return CN_OK;
+}
+extern "C" void cn_actor_pop_destroy(cn_actor_pop_handle h) { delete h; }
+extern "C" int cn_actor_pop_members(cn_actor_pop_handle h) { return h ? h->P : 0; }
+
+extern "C" int cn_actor_pop_pack(cn_actor_pop_handle h, void* stream)
+{
+    if (!h) return fail(CN_ERR_ARG, "cn_actor_pop_pack: null handle");
+    DeviceScope scope(h->device);
+    // x covers the larger layer: Dp blocks of 256 elements for layer 1, 256 for layer 2
+    hipLaunchKernelGGL(cn_actor_pop_pack_kernel, dim3(std::max(h->Dp, 256), 2, h->P), dim3(256), 0, (hipStream_t)stream, h->pack, h->D, h->Dp);
+    HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+extern "C" int cn_actor_pop_forward(cn_actor_pop_handle h, const uint64_t* counters, int add_noise, void* stream)
+{
+    if (!h) return fail(CN_ERR_ARG, "cn_actor_pop_forward: null handle");
+    if (!counters) return fail(CN_ERR_ARG, "cn_actor_pop_forward: counters is null");
+    if (h->tiles == 0) return CN_OK;
+    CnActorPopCounters ctr;
+    memset(&ctr, 0, sizeof(ctr));
+    memcpy(ctr.c, counters, sizeof(uint64_t) * h->P);
+    DeviceScope scope(h->device);
+    hipLaunchKernelGGL(cn_actor_pop_kernel, dim3(h->tiles, 1, h->P), dim3(512), h->lds, (hipStream_t)stream, h->jobs, h->D, h->Dp,
+                       add_noise ? 1 : 0, ctr);
+    HIPCHK(hipGetLastError());
+    return CN_OK;
+}
+
+extern "C" int cn_actor_pop_weights(cn_actor_pop_handle h, int member, cn_actor_weights* out)
+{
+    if (!h) return fail(CN_ERR_ARG, "cn_actor_pop_weights: null handle");
+    if (!out) return fail(CN_ERR_ARG, "cn_actor_pop_weights: out is null");
+    if (member < 0 || member >= h->P) return fail(CN_ERR_ARG, "cn_actor_pop_weights: member " + std::to_string(member) + " out of range (the handle has " + std::to_string(h->P) + ")");
+    *out = h->weights[member];
     return CN_OK;
 }
 

@@ -82,6 +82,17 @@ struct CnKParams {
     long long* timing;      // profiling build only: [N, 32] s_memtime stamps
 };
 
+// cn_actor_pop_kernel / cn_actor_pop_pack_kernel: one row per member in device memory, written once by cn_actor_pop_create
+struct CnActorPopJob {
+    const float *obs, *w1p, *b1, *w2p, *b2, *w3, *b3;
+    float* action;
+    int32_t n;
+    float max_v, max_w, sigma;
+    uint64_t seed;
+};
+struct CnActorPopPackJob { const float *w1, *w2; float *w1p, *w2p; };     // linear1.weight [256][D], linear2.weight [256][256]
+struct CnActorPopCounters { uint64_t c[CN_ACTOR_POP_MAX]; };              // by value in the kernel-argument segment
+
 #define CN_ST_OFF_SD 0
 #define CN_ST_OFF_SI (CN_SD_COUNT * 8)
 #define CN_ST_OFF_PED_P (CN_SD_COUNT * 8 + CN_SI_COUNT * 4)

@@ -3683,6 +3683,48 @@ extern "C" __global__ void __launch_bounds__(ACT_THREADS) cn_actor_kernel(const 
 }
 #endif
 
+#if !defined(CN_TU) || CN_TU == 6
+// ---- a population's actors: P members' cn_actor_forward in ONE launch, their re-pack in one more (cn_actor_pop_*) --------------
+// (a unit of its own, so that unit 1's kernels -- cn_actor_kernel among them -- stay the instruction streams they were)
+// Member = blockIdx.z, its job a row of a table in device memory that cn_actor_pop_create uploads once (workgroup-uniform: scalar
+// loads); the members' call counters change with every call and travel BY VALUE in the kernel-argument segment (64 x 8 bytes), so a
+// call copies nothing to the device.  The grid's x is the widest member's tile count: a workgroup beyond its own member's rows
+// leaves before the first barrier (the test is workgroup-uniform).  Everything else is actor_tile with the row WITHIN the member --
+// the tile, the noise key (seed_p, counter_p, row) and therefore every bit of the output are cn_actor_kernel's for that member.
+// One tile is 42 KB of LDS at 398 inputs: tiles of different members share a CU, which P launches in series on one stream never do.
+extern "C" __global__ void __launch_bounds__(ACT_THREADS) cn_actor_pop_kernel(const CnActorPopJob* __restrict__ table, int D, int Dp,
+                                                                              int add_noise, CnActorPopCounters ctr)
+{
+    extern __shared__ __attribute__((aligned(16))) float act_sm[];
+    const CnActorPopJob& jb = table[blockIdx.z];
+    const int n = jb.n, row0 = blockIdx.x * ACT_M;
+    if (row0 >= n) return;
+    actor_tile<ACT_THREADS / 64>(jb.obs + (size_t)row0 * D, min(ACT_M, n - row0), row0, D, Dp, jb.w1p, jb.b1, jb.w2p, jb.b2, jb.w3, jb.b3,
+                                 jb.action + 2 * (size_t)row0, nullptr, jb.max_v, jb.max_w, add_noise ? jb.sigma : 0.0f, jb.seed,
+                                 ctr.c[blockIdx.z], act_sm);
+}
+
+// cn_actor_pack_kernel's layout for every member and both layers in one launch, read straight from the nn.Linear storages
+// W[c][k] ([256][K_in] row-major: the transpose that cn_actor_pack_weights' caller stages first never exists).  One thread per packed
+// element; grid (Dp, 2 layers, P) x 256 threads; layer 1 pads k >= D with zeros, so every element of both buffers is written.
+// Pure data movement, once per weight update: neighbouring threads read W 4 K_in bytes apart (about 0.4 MB per member, uncoalesced,
+// out of L2 after the update that wrote it) and write coalesced.  A tile transposed through LDS would mend the read; it is not worth
+// the machinery for a launch whose cost is its latency.
+extern "C" __global__ void __launch_bounds__(256) cn_actor_pop_pack_kernel(const CnActorPopPackJob* __restrict__ table, int D, int Dp)
+{
+    const CnActorPopPackJob& jb = table[blockIdx.z];
+    const int layer = blockIdx.y;
+    const int K = layer ? ACT_H : Dp, K_in = layer ? ACT_H : D;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;        // index into the packed buffer
+    if (idx >= K * ACT_H) return;
+    const float* __restrict__ W = layer ? jb.w2 : jb.w1;
+    float* __restrict__ packed = layer ? jb.w2p : jb.w1p;
+    const int j = idx & 3, lane = (idx >> 2) & 63, q = (idx >> 8) & 3, w = (idx >> 10) & 7, b = idx >> 13;
+    const int k = 32 * b + 4 * (2 * q + (j >> 1)) + (lane >> 4), c = 32 * w + 2 * (lane & 15) + (j & 1);
+    packed[idx] = k < K_in ? W[(size_t)c * K_in + k] : 0.0f;
+}
+#endif
+
 #if !defined(CN_TU) || CN_TU == 2 || CN_TU == 4 || CN_TU == 5
 // ---- cn_rollout_policy: T control periods per launch with the POLICY IN THE LOOP --------------------------------------------
 // A workgroup = 16 environments = 16 wavefronts (one CU's worth at 4 per SIMD).  Per control period: the first eight waves run

@@ -287,6 +287,45 @@ int cn_actor_pack_weights(const float* wt_dev, int k_rows, float* packed_dev, in
 int cn_actor_forward(const cn_actor_weights* w, const float* obs, float* action, int n, float max_v, float max_w,
                      float sigma, uint64_t seed, uint64_t counter, int device, void* stream);
 
+/* A population's actors: n_members independent actors (the members of cn_td3_pop_create, or any actors of one observation width)
+ * run by ONE cn_actor_forward-like launch and re-packed by ONE launch, instead of one launch per member and four per re-pack (two
+ * transposing copies + two cn_actor_pack_weights).  The launches are small and latency-bound; side by side in one grid, tiles of
+ * different members share the card's CUs.
+ * The handle owns, per member, the packed w1p [Dp x 256] and w2p [256 x 256] buffers (Dp = obs_dim rounded up to a multiple of 32)
+ * and one job per member in a device table.  A member's pointers never change after create; the table is uploaded once.  Members
+ * agree in obs_dim (and the hidden width, 256), which fix the LDS tile; n, max_v, max_w, sigma and seed are per member.  actor: the
+ * member's nn.Linear storages as in cn_td3_config.actor.  obs / action may be NULL for a member with n == 0.  device: HIP ordinal,
+ * -1 = current.
+ * cn_actor_pop_pack (one launch): after it member p's w1p / w2p equal BYTE FOR BYTE what cn_actor_pack_weights gives for
+ * linear1.weight^T zero-padded to Dp rows / linear2.weight^T.  It reads the [out][in] storages directly and writes every element of
+ * the packed buffers, the zero rows included.  Call it after create and after every weight update, before the next forward.
+ * cn_actor_pop_forward (one launch): action_p equals BIT FOR BIT what cn_actor_forward(weights_p, obs_p, action_p, n_p, max_v_p,
+ * max_w_p, add_noise ? sigma_p : 0, seed_p, counters[p], ...) writes, whatever n_members and p are; rows at and beyond n_p are not
+ * touched.  counters: HOST array [n_members], passed by value with the launch: no host-to-device copy, nothing read back, capturable
+ * on one stream (a captured call keeps the counters it was captured with).  If every n_p is 0, no launch is made.
+ * cn_actor_pop_weights: the cn_actor_weights of a member -- the handle's packed buffers, the member's own biases and w3 -- valid while
+ * the handle lives; the member can then also be driven by cn_actor_forward / cn_rollout_policy.
+ * Refused before any device work, text in cn_last_error naming the field and the member: a NULL handle / members / out / counters,
+ * n_members outside 1 ... CN_ACTOR_POP_MAX, a NULL pointer inside a member, n < 0, member out of range -- CN_ERR_ARG; obs_dim < 1 or
+ * an obs_dim whose tile exceeds 160 KiB of LDS (from 2273, as cn_actor_forward) -- CN_ERR_CONFIG. */
+#define CN_ACTOR_POP_MAX 64
+typedef struct cn_td3_mlp { float *w1, *b1, *w2, *b2, *w3, *b3; } cn_td3_mlp;   /* Linear(in, H) - ReLU - Linear(H, H) - ReLU - Linear(H, out) */
+typedef struct cn_actor_pop_member {
+    cn_td3_mlp actor;        /* the member's nn.Linear storages, as cn_td3_config.actor: weight [out][in] row-major, bias [out] */
+    const float* obs;        /* dev [n, obs_dim] */
+    float* action;           /* dev [n, 2] */
+    int32_t n, reserved;     /* n >= 0; members may differ */
+    float max_v, max_w, sigma, reserved_f;
+    uint64_t seed;           /* exploration-noise key, as cn_actor_forward's */
+} cn_actor_pop_member;
+typedef struct cn_actor_pop_s* cn_actor_pop_handle;
+int cn_actor_pop_create(const cn_actor_pop_member* members, int n_members, int obs_dim, int device, cn_actor_pop_handle* out);
+void cn_actor_pop_destroy(cn_actor_pop_handle h);
+int cn_actor_pop_members(cn_actor_pop_handle h);
+int cn_actor_pop_pack(cn_actor_pop_handle h, void* stream);                       /* ONE launch */
+int cn_actor_pop_forward(cn_actor_pop_handle h, const uint64_t* counters, int add_noise, void* stream);   /* ONE launch */
+int cn_actor_pop_weights(cn_actor_pop_handle h, int member, cn_actor_weights* out);
+
 /* The TD3 update -- Agent.learn (td3.py:225-285) with the hyper-parameters of start_td3_training.py:62-72 -- as a short chain
  * of launches on the caller's stream (crowdnav_td3.hip): the forward and backward GEMMs of the six 3-layer networks on the f32
  * matrix cores, weight gradients folded into the Adam step (a gradient never exists in memory), the TD target / MSE gradient /
@@ -296,8 +335,8 @@ int cn_actor_forward(const cn_actor_weights* w, const float* obs, float* action,
  * The parameters stay the caller's: device pointers to the nn.Linear storages (weight [out][in] row-major float32, bias
  * [out]) of actor / critics and their targets, stepped in place.  Adam's moments and step counters are the handle's (zero at
  * cn_td3_create, like a fresh torch.optim.Adam).  Arithmetic: float32 throughout like the reference; same formulas as
- * torch.optim.Adam (no weight decay, no amsgrad) and F.mse_loss; results agree with the PyTorch update up to summation order. */
-typedef struct cn_td3_mlp { float *w1, *b1, *w2, *b2, *w3, *b3; } cn_td3_mlp;   /* Linear(in, H) - ReLU - Linear(H, H) - ReLU - Linear(H, out) */
+ * torch.optim.Adam (no weight decay, no amsgrad) and F.mse_loss; results agree with the PyTorch update up to summation order.
+ * (cn_td3_mlp, one network's storages, is declared above with cn_actor_pop_member.) */
 typedef struct cn_td3_config {
     int32_t obs_dim;         /* actor input width (TRAIN:88 -> 398); the critics take obs_dim + 2 (TD3:114) */
     int32_t hidden;          /* TRAIN:65 -> 256 */
