@@ -42,16 +42,17 @@ class EpisodeStats:
         self.rows.append([len(self.rows) + 1, bool(success), bool(failure), float(reward), int(steps), float(ego),
                           float(social), float(timelapse)])
 
-    def add_from_counters(self, c, episode_return, timelapse=None, step_seconds=0.16):
+    def add_from_counters(self, c, episode_return, timelapse=None, step_seconds=0.16, cols=(4, 5, 10, 11, 12, 13)):
         """One row from an env's cn_get_counters record taken after the launch in which it finished.  timelapse: TRAIN:141's
         `time.time() - start_time`; by default the episode's own (virtual) duration, steps x (time.sleep(0.15) + the /scan
-        wait) -- what the reference measures when it is not slowed down by its host."""
+        wait) -- what the reference measures when it is not slowed down by its host.  cols: where c holds success, failure, ego /
+        social violations, obstacle-present steps and steps (the default: cn_get_counters; a row of train.DeviceEpisodeLog: its COLS)."""
+        success, failure, ego, soc, seen, steps = (int(c[k]) for k in cols)
         if timelapse is None:
-            timelapse = int(c[13]) * step_seconds
-        seen = int(c[12])
-        ego = 1.0 - int(c[10]) * 1.0 / seen if seen else float("nan")      # ENV:1277-1283 (ZeroDivisionError there)
-        soc = 1.0 - int(c[11]) * 1.0 / seen if seen else float("nan")      # ENV:1269-1275
-        self.add(int(c[4]), int(c[5]), episode_return, int(c[13]), ego, soc, timelapse)
+            timelapse = steps * step_seconds
+        ego = 1.0 - ego * 1.0 / seen if seen else float("nan")             # ENV:1277-1283 (ZeroDivisionError there)
+        soc = 1.0 - soc * 1.0 / seen if seen else float("nan")             # ENV:1269-1275
+        self.add(success, failure, episode_return, steps, ego, soc, timelapse)
 
     def write_csv(self, outdir, filename):
         os.makedirs(outdir, exist_ok=True)

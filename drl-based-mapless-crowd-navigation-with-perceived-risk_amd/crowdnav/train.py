@@ -99,6 +99,7 @@ class DeviceEpisodeLog:
     (success, failure, return, steps, ego / social violations, obstacle-present steps, launch index) -- appended with a
     cumulative-sum scatter, rows of envs that did not finish go to a spare row.  One host read per flush().  On a HIP device add()
     is libcrowdnav's cn_episode_log_add (one launch instead of ~20 PyTorch kernels); `fused=False` keeps the PyTorch formulation."""
+    COLS = (0, 1, 4, 5, 6, 3)         # a row's success, failure, ego / social violations, obstacle-present steps, steps (EpisodeStats.add_from_counters)
 
     def __init__(self, device, max_rows, fused=True):
         self.max_rows = int(max_rows)
@@ -163,13 +164,18 @@ def resolve_load_episode(load_dir, episode):
     return int(episode)
 
 
+def write_latest(outdir, episodes):
+    """The `latest` pointer, replaced atomically: a reader never sees a half-written count."""
+    tmp = os.path.join(outdir, ".latest_checkpoint.txt.%d" % os.getpid())
+    open(tmp, "w").write("%d\n" % episodes)
+    os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
+
+
 def save_checkpoint(agent, outdir, episodes):
     """TRAIN:150-154's checkpoint + the exploration-noise stream's position + the `latest` pointer."""
     agent.save(outdir, episodes)
     open(os.path.join(outdir, "noise_state_ep%d.txt" % episodes), "w").write("%d %d\n" % agent.noise_state())
-    tmp = os.path.join(outdir, ".latest_checkpoint.txt.%d" % os.getpid())
-    open(tmp, "w").write("%d\n" % episodes)
-    os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
+    write_latest(outdir, episodes)
 
 
 CHECKPOINT_NETS = dict(td3=("actor", "critic1", "critic2"), ddpg=("actor", "critic"), sac=("actor", "critic_v", "critic_soft_q"))
@@ -181,389 +187,362 @@ def make_dqn_agent(a, obs_ld, device, memory_size):
         raise ValueError("--dqn-inputs %d > the observation width %d (use --obs-layout 1)" % (a.dqn_inputs, obs_ld))
     return dqn.Agent(obs_dim=a.dqn_inputs, obs_ld=obs_ld, batch_size=a.batch or 64, memory_size=memory_size, epsilon=a.epsilon,
                      epsilon_discount=a.epsilon_discount, target_update=a.target_update, device=device, seed=a.seed,
-                     replay_sample=getattr(a, "replay_sample", "with"))
-
-
-def save_dqn_checkpoint(agent, a, outdir, episodes):
-    agent.save(outdir, episodes, nsteps=a.max_steps)
-    tmp = os.path.join(outdir, ".latest_checkpoint.txt.%d" % os.getpid())
-    open(tmp, "w").write("%d\n" % episodes)
-    os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
-
-
-def train_dqn(a):
-    """start_dqn_training.py:84-152 for N environments: cn_dqn_act (epsilon from the device's count of finished episodes) ->
-    env.step -> replay (the index in column 0) -> `--updates` learnOnMiniBatch calls per launch once the replay holds more than
-    learnStart rows.  Enqueue-only between log intervals, like train()."""
-    dev = a.device
-    torch.cuda.set_device(dev)
-    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, **env_switches(a))
-    agent = make_dqn_agent(a, env.D, "cuda:%d" % dev, a.memory)
-    eps0 = a.epsilon
-    if a.load:                                      # TRAIN_DQN:62-82: the weights, and epsilon from the parameter record
-        a.load_episode = resolve_load_episode(a.load, a.load_episode)
-        agent.load_models(os.path.join(a.load, "dqn_model_ep%d.pt" % a.load_episode),
-                          os.path.join(a.load, "dqn_model_ep%d.json" % a.load_episode))
-        eps0 = agent.epsilon0
-    if a.learner == "fused":
-        agent.enable_fused_update()
-    stats = EpisodeStats()
-    os.makedirs(a.out, exist_ok=True)
-    resumed = bool(a.load) and os.path.abspath(a.load) == os.path.abspath(a.out)
-    obs = env.reset()
-    t0 = time.time()
-    episodes, env_steps, updates_done = 0, 0, 0
-    log = open(os.path.join(a.out, "progress.txt"), "a")
-    N = env.N
-    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
-    prev = torch.empty_like(obs)
-    act2 = torch.zeros((N, 2), dtype=torch.float32, device=obs.device)
-    elog = DeviceEpisodeLog(obs.device, a.max_csv_rows)
-    learning = False
-    next_ckpt = a.checkpoint_every
-    step_s = (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0
-    for it in range(1, a.launches + 1):
-        idx, twist = agent.act_fused(obs, episodes_dev=elog.n)               # TRAIN_DQN:89-90, 103-104
-        act2[:, 0] = idx.float()
-        prev.copy_(obs)
-        obs, reward, done = env.step(twist, auto_reset="next")
-        keep = ~resetting
-        agent.memory.add_masked(prev, act2, reward, obs, done, keep)         # TRAIN_DQN:112
-        resetting = done.bool()
-        elog.add(done, env.counters(), env.returns()[0], it, keep)
-        if not learning:
-            learning = agent.memory.ready(agent.learn_start)                # TRAIN_DQN:114, deepq.py:221
-        if learning:
-            for u in range(a.updates):
-                updates_done += 1
-                agent.learn(updates_done)
-        if it % a.log_every == 0 or it == a.launches:
-            rows, tot = elog.flush()
-            ne = int(tot[0])
-            episodes += ne; env_steps += int(tot[4])
-            for r in rows.tolist():
-                seen = int(r[6])
-                stats.add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
-                          1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
-            agent.epsilon = dqn.epsilon_after(episodes + 1, eps0, a.epsilon_discount)   # what the device used (the json records it)
-            if ne:
-                line = "launch %6d  env-steps %10d  updates %9d  episodes %8d  success %.3f  mean return %8.1f  epsilon %.3f  %.0f s" % (
-                    it, env_steps, updates_done, episodes, tot[1] / ne, tot[2] / ne, agent.epsilon, time.time() - t0)
-                print(line, flush=True); log.write(line + "\n"); log.flush()
-            if a.csv:
-                stats.append_csv(a.out, "dqn_training", resume=resumed)
-            if episodes >= next_ckpt:                 # TRAIN_DQN:132-144 (every 100 episodes there), checked at log time
-                save_dqn_checkpoint(agent, a, a.out, episodes)
-                while next_ckpt <= episodes:
-                    next_ckpt += a.checkpoint_every
-            if a.time_limit and time.time() - t0 > a.time_limit:
-                break
-    agent.memory.sync_len()
-    save_dqn_checkpoint(agent, a, a.out, episodes)
-    last = stats.rows[-500:]
-    if last:
-        line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f | %d updates, %d env-steps, %.0f s" % (
-            len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
-            updates_done, env_steps, time.time() - t0)
-        print(line, flush=True); log.write(line + "\n"); log.flush()
-    return agent, episodes
-
-
-def train_sac(a):
-    """start_sac_training.py's loop for N environments, on train_dqn's pattern: cn_sac_act -> env.step -> replay -> `--updates`
-    learn() calls per launch once the replay holds more than a batch (TRAIN_SAC:127).  Enqueue-only between log intervals."""
-    dev = a.device
-    torch.cuda.set_device(dev)
-    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, **env_switches(a))
-    agent = make_agent(a, env.D, "cuda:%d" % dev, memory_size=a.memory)
-    if a.load:
-        load_checkpoint(agent, a)
-        ns = os.path.join(a.load, "noise_state_ep%d.txt" % a.load_episode)
-        if os.path.exists(ns):
-            agent.set_noise_state(*[int(x) for x in open(ns).read().split()])
-    if a.learner == "fused":
-        agent.enable_fused_update()
-    stats = EpisodeStats()
-    os.makedirs(a.out, exist_ok=True)
-    resumed = bool(a.load) and os.path.abspath(a.load) == os.path.abspath(a.out)
-    obs = env.reset()
-    t0 = time.time()
-    episodes, env_steps, updates_done = 0, 0, 0
-    log = open(os.path.join(a.out, "progress.txt"), "a")
-    N = env.N
-    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
-    prev = torch.empty_like(obs)
-    elog = DeviceEpisodeLog(obs.device, a.max_csv_rows)
-    learning = False
-    next_ckpt = a.checkpoint_every
-    step_s = (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0
-    for it in range(1, a.launches + 1):
-        act = agent.act_fused(obs)                                           # Agent.act: samples, squashes twice, clips
-        prev.copy_(obs)
-        obs, reward, done = env.step(act, auto_reset="next")
-        keep = ~resetting
-        agent.memory.add_masked(prev, act, reward, obs, done, keep)
-        resetting = done.bool()
-        elog.add(done, env.counters(), env.returns()[0], it, keep)
-        if not learning:
-            learning = agent.memory.ready(agent.batch_size)
-        if learning:
-            for u in range(a.updates):
-                updates_done += 1
-                agent.learn(updates_done)
-        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
-        if it % a.log_every == 0 or last_launch:
-            rows, tot = elog.flush()
-            ne = int(tot[0])
-            episodes += ne; env_steps += int(tot[4])
-            for r in rows.tolist():
-                seen = int(r[6])
-                stats.add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
-                          1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
-            if ne:
-                line = "launch %6d  env-steps %10d  updates %9d  episodes %8d  success %.3f  mean return %8.1f  mean steps %6.1f  %.0f s" % (
-                    it, env_steps, updates_done, episodes, tot[1] / ne, tot[2] / ne, tot[3] / ne, time.time() - t0)
-                print(line, flush=True); log.write(line + "\n"); log.flush()
-            if a.csv:
-                stats.append_csv(a.out, "sac_training", resume=resumed)
-            if episodes >= next_ckpt:
-                save_checkpoint(agent, a.out, episodes)
-                while next_ckpt <= episodes:
-                    next_ckpt += a.checkpoint_every
-            if last_launch:
-                break
-    agent.memory.sync_len()
-    save_checkpoint(agent, a.out, episodes)
-    last = stats.rows[-500:]
-    if last:
-        line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f | %d updates, %.0f updates/s, %d env-steps, %.0f s" % (
-            len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
-            updates_done, updates_done / max(1e-9, time.time() - t0), env_steps, time.time() - t0)
-        print(line, flush=True); log.write(line + "\n"); log.flush()
-    return agent, episodes
-
-
-def save_tabular_checkpoint(agent, outdir, episodes):
-    agent.save(outdir, episodes)
-    tmp = os.path.join(outdir, ".latest_checkpoint.txt.%d" % os.getpid())
-    open(tmp, "w").write("%d\n" % episodes)
-    os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
-
-
-def train_tabular(a):
-    """start_sarsa_training.py:48-116 / start_qlearn_training.py for N environments that share one Q-table, on train_dqn's pattern:
-    chooseAction for every env after the reset, then per launch env.step -> ONE learn_act (learn the launch's transitions except
-    the reset launches, then chooseAction on the table after the writes; epsilon from the device's count of finished episodes).
-    --evaluate: the same loop without the learn phase (and no checkpoint: the table does not change)."""
-    dev = a.device
-    torch.cuda.set_device(dev)
-    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, **env_switches(a))
-    if env.D < 2:
-        raise ValueError("the tabular learners read the last two columns of the observation")
-    agent = TABULAR[a.algo](epsilon=a.epsilon, alpha=a.alpha, gamma=a.gamma, epsilon_discount=a.epsilon_discount, seed=a.seed,
-                            device="cuda:%d" % dev)
-    if a.load_qtable:
-        agent.load_q(a.load_qtable)                 # utils.load_q (qlearn.py:23)
-    if a.learner == "fused":
-        agent.enable_fused()
-    learn = not a.evaluate
-    stats = EpisodeStats()
-    os.makedirs(a.out, exist_ok=True)
-    obs = env.reset()
-    t0 = time.time()
-    episodes, env_steps = 0, 0
-    log = open(os.path.join(a.out, "progress.txt"), "a")
-    N = env.N
-    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
-    prev = torch.empty_like(obs)
-    elog = DeviceEpisodeLog(obs.device, a.max_csv_rows)
-    next_ckpt = a.checkpoint_every
-    step_s = (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0
-    name = "%s_training%s" % (a.algo, "_test" if a.evaluate else "")
-    out = agent.learn_act(None, None, None, obs, learn=False, act=True, episodes_dev=elog.n)      # the first step of every first episode
-    for it in range(1, a.launches + 1):
-        action = out["action"]
-        prev.copy_(obs)
-        obs, reward, done = env.step(out["twist"], auto_reset="next")
-        keep = ~resetting
-        resetting = done.bool()
-        elog.add(done, env.counters(), env.returns()[0], it, keep)
-        out = agent.learn_act(prev, action, reward, obs, keep=keep, learn=learn, act=True, episodes_dev=elog.n)
-        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
-        if it % a.log_every == 0 or last_launch:
-            rows, tot = elog.flush()
-            ne = int(tot[0])
-            episodes += ne; env_steps += int(tot[4])
-            for r in rows.tolist():
-                seen = int(r[6])
-                stats.add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
-                          1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
-            agent.epsilon = dqn.epsilon_after(episodes + 1, a.epsilon, a.epsilon_discount)      # what the device used
-            if ne:
-                line = "launch %6d  env-steps %10d  episodes %8d  success %.3f  mean return %8.1f  mean steps %6.1f  epsilon %.3f  %.0f s" % (
-                    it, env_steps, episodes, tot[1] / ne, tot[2] / ne, tot[3] / ne, agent.epsilon, time.time() - t0)
-                print(line, flush=True); log.write(line + "\n"); log.flush()
-            if a.csv:
-                stats.append_csv(a.out, name)
-            if learn and episodes >= next_ckpt:            # start_sarsa_training.py:105-108 (every 100 episodes there)
-                save_tabular_checkpoint(agent, a.out, episodes)
-                while next_ckpt <= episodes:
-                    next_ckpt += a.checkpoint_every
-            if last_launch:
-                break
-    if learn:
-        save_tabular_checkpoint(agent, a.out, episodes)
-    last = stats.rows[-500:]
-    if last:
-        _, present, counts = agent.table()
-        line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f | %d table entries, %d first writes, %d blends, %d env-steps, %.0f s" % (
-            len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
-            int(present.sum()), counts[0], counts[1], env_steps, time.time() - t0)
-        print(line, flush=True); log.write(line + "\n"); log.flush()
-    return agent, episodes
+                     replay_sample=a.replay_sample)
 
 
 def make_agent(a, obs_dim, device, **kw):
     """The learner of --algo with its reference defaults; --batch / --lr-actor / --lr-critic / --tau override them when given."""
-    over = {k: v for k, v in (("batch_size", getattr(a, "batch", None)), ("actor_lr", getattr(a, "lr_actor", None)),
-                              ("critic_lr", getattr(a, "lr_critic", None)), ("tau", getattr(a, "tau", None))) if v is not None}
+    over = {k: v for k, v in (("batch_size", a.batch), ("actor_lr", a.lr_actor), ("critic_lr", a.lr_critic), ("tau", a.tau)) if v is not None}
     over.update(kw)
-    over["replay_sample"] = getattr(a, "replay_sample", "with")
-    if getattr(a, "algo", "td3") == "sac":
+    over["replay_sample"] = a.replay_sample
+    if a.algo == "sac":
         over = {dict(critic_lr="q_lr").get(k, k): v for k, v in over.items()}
         if "q_lr" in over:
             over["v_lr"] = over["q_lr"]
         return sac.Agent(obs_dim=obs_dim, device=device, seed=a.seed, n_envs=a.envs, value_net=a.sac_value_net.replace("-", "_"),
-                         soft_update=a.sac_soft_update.replace("-", "_"), deterministic=getattr(a, "sac_deterministic", False), **over)
-    if getattr(a, "algo", "td3") == "ddpg":
+                         soft_update=a.sac_soft_update.replace("-", "_"), deterministic=a.sac_deterministic, **over)
+    if a.algo == "ddpg":
         return ddpg.Agent(obs_dim=obs_dim, device=device, seed=a.seed, n_envs=a.envs, **over)
     return td3.Agent(obs_dim=obs_dim, device=device, seed=a.seed, **over)
 
 
 def load_checkpoint(agent, a):
-    algo = getattr(a, "algo", "td3")
     a.load_episode = resolve_load_episode(a.load, a.load_episode)
-    agent.load_models(*[os.path.join(a.load, "%s_%s_model_ep%d.pt" % (algo, n, a.load_episode)) for n in CHECKPOINT_NETS[algo]])
+    agent.load_models(*[os.path.join(a.load, "%s_%s_model_ep%d.pt" % (a.algo, n, a.load_episode)) for n in CHECKPOINT_NETS[a.algo]])
 
 
 def env_switches(a):
     return dict(waypoint_reward=a.waypoint_reward, scan_f32=a.scan_f32, wheel_accel=a.wheel_accel,
-                track_capacity=getattr(a, "track_capacity", None), obs_layout=getattr(a, "obs_layout", None))
+                track_capacity=a.track_capacity, obs_layout=a.obs_layout)
 
 
-def train(a):
-    dev = a.device
-    algo = getattr(a, "algo", "td3")
-    torch.cuda.set_device(dev)        # policy kernels and torch ops of this process all target the env's GPU
-    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, dev, a.ped_vmax, **env_switches(a))
-    extra = dict(memory_size=a.memory)
-    if algo == "td3":
-        extra["actor_final_init"] = getattr(a, "actor_final_init", None)
-    agent = make_agent(a, env.D, "cuda:%d" % dev, **extra)
-    batch = agent.batch_size
-    ou = algo == "ddpg" and getattr(a, "ou_noise", False)      # OU noise: the act -> step loop (DDPG:170-196, add_noise=True)
-    if a.load:
-        load_checkpoint(agent, a)
-        ns = os.path.join(a.load, "noise_state_ep%d.txt" % a.load_episode)
-        if os.path.exists(ns):           # continue the exploration-noise stream instead of replaying it
-            agent.set_noise_state(*[int(x) for x in open(ns).read().split()])
-    if a.learner == "fused":
-        agent.enable_fused_update()   # cn_td3_update: the update as 7 (+ 5) hand-written launches; cn_ddpg_update: 8
-    elif a.graphs and algo == "td3":
-        agent.enable_graphs()         # a TD3 update as one hipGraph launch (the eager update is launch-bound at batch 128)
-    stats = EpisodeStats()
-    os.makedirs(a.out, exist_ok=True)
-    # a run continued into the directory it was loaded from appends to that run's CSV (as progress.txt always did)
-    resumed = bool(a.load) and os.path.abspath(a.load) == os.path.abspath(a.out)
+class Learner:
+    """What the collection loop asks of a learner, with the answers TD3, DDPG, SAC and a population's member share: the replay
+    write, `learn()` once the replay holds more than a batch (TRAIN:132), save_checkpoint, the progress line with mean steps."""
+    consume_after_log = False         # the transition is consumed before the episode log's add
+    checkpoints = True
+    line_updates = True               # the progress line shows the update count ...
+    line_steps = True                 # ... and the mean episode length
+
+    def __init__(self, a, agent):
+        self.a, self.agent = a, agent
+        self.learn = agent.learn      # TRAIN:133-136; bound here: the loop calls it --updates times per launch
+        self.csv_name = "%s_training" % a.algo
+        # a run continued into the directory it was loaded from appends to that run's CSV (as progress.txt always did)
+        self.resume = bool(a.load) and os.path.abspath(a.load) == os.path.abspath(a.out)
+
+    def load(self):
+        """--load: the networks, and the exploration-noise stream continued instead of replayed."""
+        if self.a.load:
+            load_checkpoint(self.agent, self.a)
+            ns = os.path.join(self.a.load, "noise_state_ep%d.txt" % self.a.load_episode)
+            if os.path.exists(ns):
+                self.agent.set_noise_state(*[int(x) for x in open(ns).read().split()])
+
+    def start(self, obs, elog):
+        """Before launch 1."""
+
+    def consume(self, prev, act, reward, obs, done, keep):
+        self.agent.memory.add_masked(prev, act, reward, obs, done, keep)    # TRAIN:129-131; s' of a finished env = its terminal obs
+
+    def ready(self):
+        return self.agent.memory.ready(self.agent.batch_size)   # (a host read only while the bounds straddle it; none afterwards)
+
+    def after_updates(self):
+        """After the launch's --updates updates."""
+
+    def epsilon_at(self, episodes):
+        """At log time, before the progress line: the exploration rate the line shows, None = none."""
+
+    def warn(self, run):
+        """At log time, after the progress line."""
+
+    def checkpoint(self, outdir, episodes):
+        save_checkpoint(self.agent, outdir, episodes)
+
+    def close(self):
+        self.agent.memory.sync_len()
+
+    def summary(self, run, last, updates, t):
+        return " | %d updates, %.0f updates/s, %d env-steps, %.0f s" % (updates, updates / max(1e-9, t), run.env_steps, t)
+
+
+class Td3(Learner):
+    """--algo td3 / ddpg: the whole actor as ONE kernel on the weights packed after the launch's updates."""
+
+    def __init__(self, a, env):
+        extra = dict(actor_final_init=a.actor_final_init) if a.algo == "td3" else {}
+        super().__init__(a, make_agent(a, env.D, "cuda:%d" % a.device, memory_size=a.memory, **extra))
+        self.env = env
+        self.load()
+        if a.learner == "fused":
+            self.agent.enable_fused_update()   # cn_td3_update: the update as 7 (+ 5) hand-written launches; cn_ddpg_update: 8
+        elif a.graphs and a.algo == "td3":
+            self.agent.enable_graphs()         # a TD3 update as one hipGraph launch (the eager update is launch-bound at batch 128)
+        self.warned_overflow = False
+        if a.algo == "ddpg" and a.ou_noise:    # OU noise: the act -> step loop (DDPG:170-196, add_noise=True)
+            self.act, self.consume = self.act_ou, self.consume_ou
+
+    def start(self, obs, elog):
+        self.agent.sync_fused_weights()
+
+    def act(self, obs, it):
+        return self.agent.act_mfma(obs, add_noise=True)      # TD3:196-223 as one kernel, sigma = 1.0 (DDPG: 0), clipped
+
+    def act_ou(self, obs, it):
+        return self.agent.act(obs, add_noise=True, step=it - 1)
+
+    def consume_ou(self, prev, act, reward, obs, done, keep):
+        self.agent.memory.add_masked(prev, act, reward, obs, done, keep)
+        self.agent.reset_noise(done)                         # TRAIN_DDPG:161
+
+    def after_updates(self):
+        self.agent.sync_fused_weights()                      # the actor the next launch acts with
+
+    def warn(self, run):
+        if self.warned_overflow:
+            return
+        sc_ = self.env.status_counts()
+        if sc_["track_overflow"] or sc_["conf_overflow"]:
+            self.warned_overflow = True
+            run.say("WARNING: %d env(s) outgrew the track table and %d the confirmed-object table (status bits CN_ST_TRACK_OVERFLOW / "
+                    "CN_ST_CONF_OVERFLOW): their risk features use the tracks that fit and differ from the reference's unbounded "
+                    "lists from there on; --track-capacity 256 (or 128 / 512 / 1024: a wide table in HBM, slower) keeps the "
+                    "track list equal to the reference's up to that many tracks" % (sc_["track_overflow"], sc_["conf_overflow"]))
+
+    def summary(self, run, last, updates, t):
+        return "  ego %.3f  social %.3f  | %d updates, %.0f updates/s, %.0f env-steps/s overall" % (
+            sum(r[5] for r in last if r[5] == r[5]) / max(1, sum(1 for r in last if r[5] == r[5])),
+            sum(r[6] for r in last if r[6] == r[6]) / max(1, sum(1 for r in last if r[6] == r[6])),
+            updates, updates / max(1e-9, t), run.env_steps / max(1e-9, t))
+
+
+class Dqn(Learner):
+    """--algo dqn, start_dqn_training.py:84-152: cn_dqn_act (epsilon from the device's count of finished episodes) -> env.step ->
+    replay (the index in column 0) -> learnOnMiniBatch once the replay holds more than learnStart rows."""
+    line_steps = False
+
+    def __init__(self, a, env):
+        super().__init__(a, make_dqn_agent(a, env.D, "cuda:%d" % a.device, a.memory))
+        self.eps0 = a.epsilon
+        if a.load:                                      # TRAIN_DQN:62-82: the weights, and epsilon from the parameter record
+            a.load_episode = resolve_load_episode(a.load, a.load_episode)
+            self.agent.load_models(os.path.join(a.load, "dqn_model_ep%d.pt" % a.load_episode),
+                                   os.path.join(a.load, "dqn_model_ep%d.json" % a.load_episode))
+            self.eps0 = self.agent.epsilon0
+        if a.learner == "fused":
+            self.agent.enable_fused_update()
+
+    def start(self, obs, elog):
+        self.episodes_dev = elog.n
+        self.act2 = torch.zeros((obs.shape[0], 2), dtype=torch.float32, device=obs.device)
+
+    def act(self, obs, it):
+        idx, twist = self.agent.act_fused(obs, episodes_dev=self.episodes_dev)     # TRAIN_DQN:89-90, 103-104
+        self.act2[:, 0] = idx.float()
+        return twist
+
+    def consume(self, prev, act, reward, obs, done, keep):
+        self.agent.memory.add_masked(prev, self.act2, reward, obs, done, keep)     # TRAIN_DQN:112
+
+    def ready(self):
+        return self.agent.memory.ready(self.agent.learn_start)                    # TRAIN_DQN:114, deepq.py:221
+
+    def epsilon_at(self, episodes):
+        self.agent.epsilon = dqn.epsilon_after(episodes + 1, self.eps0, self.a.epsilon_discount)   # what the device used (the json records it)
+        return self.agent.epsilon
+
+    def checkpoint(self, outdir, episodes):
+        self.agent.save(outdir, episodes, nsteps=self.a.max_steps)
+        write_latest(outdir, episodes)
+
+    def summary(self, run, last, updates, t):
+        return " | %d updates, %d env-steps, %.0f s" % (updates, run.env_steps, t)
+
+
+class Sac(Learner):
+    """--algo sac, start_sac_training.py's loop: cn_sac_act -> env.step -> replay -> learn() (TRAIN_SAC:127)."""
+
+    def __init__(self, a, env):
+        super().__init__(a, make_agent(a, env.D, "cuda:%d" % a.device, memory_size=a.memory))
+        self.load()
+        if a.learner == "fused":
+            self.agent.enable_fused_update()
+
+    def act(self, obs, it):
+        return self.agent.act_fused(obs)                     # Agent.act: samples, squashes twice, clips
+
+
+class Tabular(Learner):
+    """--algo qlearn / sarsa, start_sarsa_training.py:48-116 / start_qlearn_training.py for N environments that share one Q-table:
+    chooseAction for every env after the reset, then per launch env.step -> ONE learn_act (learn the launch's transitions except
+    the reset launches, then chooseAction on the table after the writes; epsilon from the device's count of finished episodes).
+    --evaluate: the same loop without the learn phase (and no checkpoint: the table does not change)."""
+    consume_after_log = True          # learn_act's epsilon reads the episode count the log's add has just advanced
+    line_updates = False
+
+    def __init__(self, a, env):
+        if env.D < 2:
+            raise ValueError("the tabular learners read the last two columns of the observation")
+        self.a = a
+        self.agent = TABULAR[a.algo](epsilon=a.epsilon, alpha=a.alpha, gamma=a.gamma, epsilon_discount=a.epsilon_discount, seed=a.seed,
+                                     device="cuda:%d" % a.device)
+        if a.load_qtable:
+            self.agent.load_q(a.load_qtable)            # utils.load_q (qlearn.py:23)
+        if a.learner == "fused":
+            self.agent.enable_fused()
+        self.learning = self.checkpoints = not a.evaluate
+        self.csv_name = "%s_training%s" % (a.algo, "_test" if a.evaluate else "")
+        self.resume = False
+
+    def start(self, obs, elog):
+        self.episodes_dev = elog.n
+        self.out = self.agent.learn_act(None, None, None, obs, learn=False, act=True, episodes_dev=elog.n)   # the first step of every first episode
+
+    def act(self, obs, it):
+        self.action = self.out["action"]
+        return self.out["twist"]
+
+    def consume(self, prev, act, reward, obs, done, keep):
+        self.out = self.agent.learn_act(prev, self.action, reward, obs, keep=keep, learn=self.learning, act=True, episodes_dev=self.episodes_dev)
+
+    def ready(self):
+        return False                  # no replay, no --updates loop
+
+    def epsilon_at(self, episodes):
+        self.agent.epsilon = dqn.epsilon_after(episodes + 1, self.a.epsilon, self.a.epsilon_discount)      # what the device used
+        return self.agent.epsilon
+
+    def checkpoint(self, outdir, episodes):            # start_sarsa_training.py:105-108 (every 100 episodes there)
+        self.agent.save(outdir, episodes)
+        write_latest(outdir, episodes)
+
+    def close(self):
+        pass
+
+    def summary(self, run, last, updates, t):
+        _, present, counts = self.agent.table()
+        return " | %d table entries, %d first writes, %d blends, %d env-steps, %.0f s" % (int(present.sum()), counts[0], counts[1], run.env_steps, t)
+
+
+class Member(Learner):
+    """Member p of a --population: train_population acts, stores and learns for all members at once; this is its log-time side."""
+
+    def summary(self, run, last, updates, t):
+        return "  | %d updates, %.0f updates/s (x %d members)" % (updates, updates / max(1e-9, t), self.a.population)
+
+
+SOLO = dict(td3=Td3, ddpg=Td3, dqn=Dqn, sac=Sac, qlearn=Tabular, sarsa=Tabular)
+
+
+class RunLog:
+    """One run's bookkeeping: the device's episode log, the EpisodeStats rows it becomes, progress.txt, the episode and env-step
+    counts, the checkpoint cadence.  log() is the whole log-interval block, finish() the tail; `learner` answers what differs
+    between the algorithms (a Learner).  prefix goes in front of the lines on stdout only."""
+
+    def __init__(self, a, out, elog, step_s, learner, prefix=""):
+        self.a, self.out, self.elog, self.step_s, self.learner, self.prefix = a, out, elog, step_s, learner, prefix
+        self.stats = EpisodeStats()
+        os.makedirs(out, exist_ok=True)
+        self.file = open(os.path.join(out, "progress.txt"), "a")
+        self.episodes, self.env_steps, self.next_ckpt = 0, 0, a.checkpoint_every
+        self.t0 = time.time()
+
+    def say(self, line):
+        print(self.prefix + line, flush=True); self.file.write(line + "\n"); self.file.flush()
+
+    def log(self, it, updates):
+        """One host read of the device's log, then: rows -> stats, the progress line, the CSV's new rows (a killed run keeps its
+        rows up to here), a checkpoint once the episode count has reached the next multiple of --checkpoint-every."""
+        L = self.learner
+        rows, tot = self.elog.flush()
+        ne = int(tot[0])
+        self.episodes += ne; self.env_steps += int(tot[4])
+        for r in rows.tolist():
+            self.stats.add_from_counters(r, r[2], step_seconds=self.step_s, cols=DeviceEpisodeLog.COLS)
+        eps = L.epsilon_at(self.episodes)
+        if ne:
+            self.say("launch %6d  env-steps %10d%s  episodes %8d  success %.3f  mean return %8.1f%s%s  %.0f s" % (
+                it, self.env_steps, "  updates %9d" % updates if L.line_updates else "", self.episodes, tot[1] / ne, tot[2] / ne,
+                "  mean steps %6.1f" % (tot[3] / ne) if L.line_steps else "", "" if eps is None else "  epsilon %.3f" % eps,
+                time.time() - self.t0))
+        L.warn(self)
+        if self.a.csv:
+            self.stats.append_csv(self.out, L.csv_name, resume=L.resume)
+        if L.checkpoints and self.episodes >= self.next_ckpt:       # TRAIN:150-154 (every 100 episodes there)
+            # labelled with the episode count the weights really have behind them (checked at log time, so it can be past
+            # the threshold that triggered it)
+            L.checkpoint(self.out, self.episodes)
+            while self.next_ckpt <= self.episodes:
+                self.next_ckpt += self.a.checkpoint_every
+
+    def finish(self, updates):
+        """The final checkpoint and the summary of the last 500 episodes."""
+        L = self.learner
+        L.close()
+        if L.checkpoints:
+            L.checkpoint(self.out, self.episodes)
+        last = self.stats.rows[-500:]
+        if last:
+            self.say("last %d episodes: success %.3f  mean return %.1f  mean steps %.1f%s" % (
+                len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
+                L.summary(self, last, updates, time.time() - self.t0)))
+        self.file.close()
+
+
+def collect(a, env, learner, elog=None):
+    """The collection loop of every solo run (TRAIN:104-168 for N environments): per launch act -> env.step -> the learner consumes
+    the transition -> episode log -> `--updates` updates once the learner is ready; every --log-every launches RunLog.log().
+    Enqueue-only between log intervals.  elog: the episode log (default: DeviceEpisodeLog on the observation's device)."""
     obs = env.reset()
-    t0 = time.time()
-    episodes = 0
-    env_steps = 0
-    next_ckpt = a.checkpoint_every
-    log = open(os.path.join(a.out, "progress.txt"), "a")
-    N = env.N
+    run = RunLog(a, a.out, elog or DeviceEpisodeLog(obs.device, a.max_csv_rows), (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0, learner)
+    elog = run.elog
     same = a.reset_mode == "same"
-    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)   # envs whose NEXT launch is their Env.reset
-    all_rows = torch.ones(N, dtype=torch.bool, device=obs.device)
+    resetting = torch.zeros(env.N, dtype=torch.bool, device=obs.device)   # envs whose NEXT launch is their Env.reset
+    all_rows = torch.ones(env.N, dtype=torch.bool, device=obs.device)
     prev = torch.empty_like(obs)
-    elog = DeviceEpisodeLog(obs.device, a.max_csv_rows)
     learning = False
     updates_done = 0
-    agent.sync_fused_weights()
-    step_s = (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0
-    win = []                                                           # (successes, episodes) of the recent log windows
-    warned_overflow = False
+    late = learner.consume_after_log
+    learner.start(obs, elog)
     for it in range(1, a.launches + 1):
-        if ou:
-            act = agent.act(obs, add_noise=True, step=it - 1)
-        else:
-            act = agent.act_mfma(obs, add_noise=True)                  # TD3:196-223 as one kernel, sigma = 1.0 (DDPG: 0), clipped
+        act = learner.act(obs, it)
         prev.copy_(obs)
         if same:
             obs, reward, done = env.step(act, auto_reset="same", want_final=True)
-            agent.memory.add_masked(prev, act, reward, env.final_obs, done, all_rows)
-            keep = all_rows
+            keep, nxt = all_rows, env.final_obs
         else:
             obs, reward, done = env.step(act, auto_reset="next")
-            keep = ~resetting
-            agent.memory.add_masked(prev, act, reward, obs, done, keep)    # TRAIN:129-131; s' of a finished env = its terminal obs
+            keep, nxt = ~resetting, obs
+        if not late:
+            learner.consume(prev, act, reward, nxt, done, keep)
+        if not same:
             resetting = done.bool()
-        if ou:
-            agent.reset_noise(done)                                    # TRAIN_DDPG:161
         elog.add(done, env.counters(), env.returns()[0], it, keep)
-        if not learning:                                               # TRAIN:132: only once the replay holds more than a batch
-            learning = agent.memory.ready(batch)                     # (a host read only while the bounds straddle it; none afterwards)
+        if late:
+            learner.consume(prev, act, reward, nxt, done, keep)
+        if not learning:
+            learning = learner.ready()
         if learning:
             for u in range(a.updates):
                 updates_done += 1
-                agent.learn(updates_done)                              # TRAIN:133-136
-            agent.sync_fused_weights()                                 # the actor the next launch acts with
-        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
+                learner.learn(updates_done)
+            learner.after_updates()
+        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - run.t0 > a.time_limit)
         if it % a.log_every == 0 or last_launch:
-            rows, tot = elog.flush()
-            ne = int(tot[0])
-            episodes += ne; env_steps += int(tot[4])
-            for r in rows.tolist():
-                seen = int(r[6])
-                stats.add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
-                          1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
-            if ne:
-                win.append((tot[1], ne))
-                line = "launch %6d  env-steps %10d  updates %9d  episodes %8d  success %.3f  mean return %8.1f  mean steps %6.1f  %.0f s" % (
-                    it, env_steps, updates_done, episodes, tot[1] / ne, tot[2] / ne, tot[3] / ne, time.time() - t0)
-                print(line, flush=True); log.write(line + "\n"); log.flush()
-            if not warned_overflow:
-                sc_ = env.status_counts()
-                if sc_["track_overflow"] or sc_["conf_overflow"]:
-                    warned_overflow = True
-                    line = ("WARNING: %d env(s) outgrew the track table and %d the confirmed-object table (status bits CN_ST_TRACK_OVERFLOW / "
-                            "CN_ST_CONF_OVERFLOW): their risk features use the tracks that fit and differ from the reference's unbounded "
-                            "lists from there on; --track-capacity 256 (or 128 / 512 / 1024: a wide table in HBM, slower) keeps the "
-                            "track list equal to the reference's up to that many tracks" % (sc_["track_overflow"], sc_["conf_overflow"]))
-                    print(line, flush=True); log.write(line + "\n"); log.flush()
-            if a.csv:
-                stats.append_csv(a.out, "%s_training" % algo, resume=resumed)   # incremental: a killed run keeps its rows up to here
-            if episodes >= next_ckpt:                                    # TRAIN:150-154 (every 100 episodes there)
-                # labelled with the episode count the weights really have behind them (checked at log time, so it can be past
-                # the threshold that triggered it)
-                save_checkpoint(agent, a.out, episodes)
-                while next_ckpt <= episodes:
-                    next_ckpt += a.checkpoint_every
+            run.log(it, updates_done)
             if last_launch:
                 break
-    agent.memory.sync_len()
-    save_checkpoint(agent, a.out, episodes)
-    last = stats.rows[-500:]
-    if last:
-        line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f  ego %.3f  social %.3f  | %d updates, %.0f updates/s, %.0f env-steps/s overall" % (
-            len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
-            sum(r[5] for r in last if r[5] == r[5]) / max(1, sum(1 for r in last if r[5] == r[5])),
-            sum(r[6] for r in last if r[6] == r[6]) / max(1, sum(1 for r in last if r[6] == r[6])),
-            updates_done, updates_done / max(1e-9, time.time() - t0), env_steps / max(1e-9, time.time() - t0))
-        print(line, flush=True); log.write(line + "\n"); log.flush()
-    if a.csv:
-        stats.append_csv(a.out, "%s_training" % algo, resume=resumed)
-    return agent, episodes
+    run.finish(updates_done)
+    return learner.agent, run.episodes
+
+
+def train(a):
+    """One solo run of --algo on N environments of one GPU -> (agent, finished episodes)."""
+    fill_defaults(a)
+    torch.cuda.set_device(a.device)        # policy kernels and torch ops of this process all target the env's GPU
+    env = make_env(a.scenario, a.envs, a.max_steps, a.seed, a.device, a.ped_vmax, **env_switches(a))
+    return collect(a, env, SOLO[a.algo](a, env))
 
 
 class MemberEnvs(VecEnvGroups):
@@ -583,7 +562,7 @@ class MemberEnvs(VecEnvGroups):
 def train_population(a):
     """--population P: P independent TD3 runs, seeds a.seed ... a.seed + P - 1, whose updates are ONE cn_td3_pop_update per update
     (crowdnav.td3.Population) instead of P processes.  Member p has what `train()` with --seed <seed + p> has -- its environment
-    handle of --envs environments, its Agent, replay, episode log, statistics -- and writes what that run writes into
+    handle of --envs environments, its Agent, replay, RunLog -- and writes what that run writes into
     <out>/member<p>/.  Per launch: ONE act launch for all members (--population-act one-launch, Population.act; per-member: P
     act_mfma calls), one grouped environment step (cn_step_multi), P replay writes and P log adds; once EVERY member's replay holds more
     than a batch, --updates population updates and ONE re-pack of the P actors (per-member: P sync_fused_weights, 4 launches each).
@@ -592,6 +571,7 @@ def train_population(a):
     the batch size on the same launch: a member whose ring is not ready yet (it lost rows to reset launches) holds the others back, so
     that the update counters -- which key the sampling and drive policy_delay -- stay aligned; from then on that member's solo run
     would have started its updates earlier."""
+    fill_defaults(a)
     dev = a.device
     P = a.population
     torch.cuda.set_device(dev)
@@ -607,32 +587,27 @@ def train_population(a):
             e.set_ped_init(init)
         if vel is not None:
             e.set_ped_preset_vel(vel)
-    agents = [make_agent(m, envs.D, "cuda:%d" % dev, memory_size=a.memory, actor_final_init=getattr(a, "actor_final_init", None)) for m in members]
+    agents = [make_agent(m, envs.D, "cuda:%d" % dev, memory_size=a.memory, actor_final_init=a.actor_final_init) for m in members]
     pop = td3.Population(agents)
-    batch = agents[0].batch_size
-    stats = [EpisodeStats() for _ in range(P)]
-    logs = []
-    for m in members:
-        os.makedirs(m.out, exist_ok=True)
-        logs.append(open(os.path.join(m.out, "progress.txt"), "a"))
     obs = envs.reset()
-    t0 = time.time()
-    episodes, env_steps, next_ckpt = [0] * P, [0] * P, [a.checkpoint_every] * P
+    step_s = (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0
+    runs = [RunLog(m, m.out, DeviceEpisodeLog(obs.device, a.max_csv_rows), step_s, Member(m, ag), prefix="member %2d  " % p)
+            for p, (m, ag) in enumerate(zip(members, agents))]
+    t0 = runs[0].t0
     N, rows = envs.N, [envs.rows(p) for p in range(P)]
     resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
     prev = torch.empty_like(obs)
     act = torch.zeros((N, 2), dtype=torch.float32, device=obs.device)
     step_all = envs.bind_step_all(act, auto_reset="next")
-    elogs = [DeviceEpisodeLog(obs.device, a.max_csv_rows) for _ in range(P)]
+    elogs = [r.elog for r in runs]
     learning = False
     updates_done = 0
-    one_launch = getattr(a, "population_act", "one-launch") == "one-launch"
+    one_launch = a.population_act == "one-launch"
     if one_launch:
         pop.bind_act([obs[r] for r in rows], [act[r] for r in rows])      # (packs the actors)
     else:
         for ag in agents:
             ag.sync_fused_weights()
-    step_s = (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0
     reward, done = envs.reward, envs.done
     for it in range(1, a.launches + 1):
         if one_launch:
@@ -664,45 +639,20 @@ def train_population(a):
                     ag.sync_fused_weights()
         last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
         if it % a.log_every == 0 or last_launch:
-            for p, m in enumerate(members):
-                new, tot = elogs[p].flush()
-                ne = int(tot[0])
-                episodes[p] += ne; env_steps[p] += int(tot[4])
-                for r in new.tolist():
-                    seen = int(r[6])
-                    stats[p].add(int(r[0]), int(r[1]), r[2], int(r[3]), 1.0 - r[4] / seen if seen else float("nan"),
-                                 1.0 - r[5] / seen if seen else float("nan"), int(r[3]) * step_s)
-                if ne:
-                    line = "launch %6d  env-steps %10d  updates %9d  episodes %8d  success %.3f  mean return %8.1f  mean steps %6.1f  %.0f s" % (
-                        it, env_steps[p], updates_done, episodes[p], tot[1] / ne, tot[2] / ne, tot[3] / ne, time.time() - t0)
-                    print("member %2d  %s" % (p, line), flush=True); logs[p].write(line + "\n"); logs[p].flush()
-                if a.csv:
-                    stats[p].append_csv(m.out, "td3_training")
-                if episodes[p] >= next_ckpt[p]:
-                    save_checkpoint(agents[p], m.out, episodes[p])
-                    while next_ckpt[p] <= episodes[p]:
-                        next_ckpt[p] += a.checkpoint_every
+            for run in runs:
+                run.log(it, updates_done)
             if last_launch:
                 break
-    for p, m in enumerate(members):
-        agents[p].memory.sync_len()
-        save_checkpoint(agents[p], m.out, episodes[p])
-        last = stats[p].rows[-500:]
-        if last:
-            line = "last %d episodes: success %.3f  mean return %.1f  mean steps %.1f  | %d updates, %.0f updates/s (x %d members)" % (
-                len(last), sum(r[1] for r in last) / len(last), sum(r[3] for r in last) / len(last), sum(r[4] for r in last) / len(last),
-                updates_done, updates_done / max(1e-9, time.time() - t0), P)
-            print("member %2d  %s" % (p, line), flush=True); logs[p].write(line + "\n"); logs[p].flush()
-        if a.csv:
-            stats[p].append_csv(m.out, "td3_training")
-        logs[p].close()
-    return agents, episodes
+    for run in runs:
+        run.finish(updates_done)
+    return agents, [run.episodes for run in runs]
 
 
 def run_evaluation(a):
+    fill_defaults(a)
     torch.cuda.set_device(a.device)
     env = make_env(a.scenario, a.envs, a.max_steps, a.seed, a.device, a.ped_vmax, **env_switches(a))
-    if getattr(a, "algo", "td3") == "dqn":           # greedy: Agent.act(add_noise=False) takes epsilon = 0
+    if a.algo == "dqn":           # greedy: Agent.act(add_noise=False) takes epsilon = 0
         agent = make_dqn_agent(a, env.D, "cuda:%d" % a.device, 16)
         a.load_episode = resolve_load_episode(a.load, a.load_episode)
         agent.load_models(os.path.join(a.load, "dqn_model_ep%d.pt" % a.load_episode))
@@ -716,12 +666,12 @@ def run_evaluation(a):
         sum(r[5] for r in st.rows if r[5] == r[5]) / max(1, sum(1 for r in st.rows if r[5] == r[5])),
         sum(r[6] for r in st.rows if r[6] == r[6]) / max(1, sum(1 for r in st.rows if r[6] == r[6]))))
     if a.out:
-        print("wrote", st.write_csv(a.out, "%s_training_test_%s" % (getattr(a, "algo", "td3"), a.scenario)))
+        print("wrote", st.write_csv(a.out, "%s_training_test_%s" % (a.algo, a.scenario)))
     return st
 
 
-def parse_args(argv=None):
-    """The command line with the algorithm's defaults resolved (max_steps, obs_layout, out)."""
+def build_parser():
+    """The command line's parser: every flag and its default."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--scenario", default="training", help="training | training_as_logged | bench | {crossing,towards,ahead,random}_{4,8,12,20}")
     ap.add_argument("--envs", type=int, default=1024)
@@ -792,6 +742,12 @@ def parse_args(argv=None):
     ap.add_argument("--load-episode", default="latest", help="the <N> of td3_*_model_ep<N>.pt, or `latest` = the count in <load>/latest_checkpoint.txt")
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--episodes-per-env", type=int, default=1)
+    return ap
+
+
+def parse_args(argv=None):
+    """The command line with the algorithm's defaults resolved (max_steps, obs_layout, out)."""
+    ap = build_parser()
     a = ap.parse_args(argv)
     tab = a.algo in TABULAR
     if tab:           # flags of the replay learners: rejected when given, whatever their value
@@ -837,18 +793,21 @@ def parse_args(argv=None):
     return a
 
 
+def fill_defaults(a):
+    """Give a Namespace that a caller built by hand every option it lacks, at the value the command line without that flag gives
+    (the algorithm's own defaults resolved for a.algo); what it sets stays untouched."""
+    for k, v in vars(parse_args(["--algo", vars(a).get("algo", build_parser().get_default("algo"))])).items():
+        if not hasattr(a, k):
+            setattr(a, k, v)
+    return a
+
+
 def main(argv=None):
     a = parse_args(argv)
-    if a.algo in TABULAR:
-        return train_tabular(a)
-    if a.evaluate:
+    if a.evaluate and a.algo not in TABULAR:
         return run_evaluation(a)
     if a.population:
         return train_population(a)
-    if a.algo == "dqn":
-        return train_dqn(a)
-    if a.algo == "sac":
-        return train_sac(a)
     return train(a)
 
 
