@@ -43,9 +43,11 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_td3_pop_create", "cn_td3_pop_destroy", "cn_td3_pop_update", "cn_td3_pop_members", "cn_td3_pop_loss_dev",
            "cn_td3_pop_batch_dev", "cn_td3_pop_set_replay_sample",
            "cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", "cn_actor_pop_pack", "cn_actor_pop_forward",
-           "cn_actor_pop_weights"]
+           "cn_actor_pop_weights",
+           "cn_pop_record_create", "cn_pop_record_destroy", "cn_pop_record_members", "cn_pop_record_resetting", "cn_pop_record"]
 CN_TD3_POP_MAX = 64         # include/crowdnav.h: cn_td3_pop_create's n_members is 1 ... 64
 CN_ACTOR_POP_MAX = 64       # include/crowdnav.h: cn_actor_pop_create's n_members is 1 ... 64
+CN_POP_RECORD_MAX = 64      # include/crowdnav.h: cn_pop_record_create's n_members is 1 ... 64
 CN_SAMPLE_WITH_REPLACEMENT, CN_SAMPLE_DISTINCT = 0, 1      # include/crowdnav.h: cn_*_set_replay_sample
 REPLAY_SAMPLE = {"with": CN_SAMPLE_WITH_REPLACEMENT, "without": CN_SAMPLE_DISTINCT}
 
@@ -238,6 +240,13 @@ class CnEpisodeLog(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("max_rows", C.c_int64), ("n_dev", C.c_void_p), ("tot_dev", C.c_void_p)]
 
 
+class CnPopRecordMember(C.Structure):
+    """Mirror of `cn_pop_record_member` (include/crowdnav.h): one member of cn_pop_record_create."""
+    _fields_ = [("env", C.c_void_p), ("counters", C.c_void_p), ("last_return", C.c_void_p), ("prev", C.c_void_p), ("obs", C.c_void_p),
+                ("action", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p), ("ring", CnReplayRing), ("log", CnEpisodeLog),
+                ("n", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CnSequenceIO(C.Structure):
     """Mirror of `cn_sequence_io` (include/crowdnav.h)."""
     _fields_ = [("action", C.c_void_p), ("obs", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p), ("topk_idx", C.c_void_p),
@@ -365,6 +374,11 @@ def lib():
         L.cn_actor_pop_pack.argtypes = [vp, vp]
         L.cn_actor_pop_forward.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int, vp]      # counters: a host array [n_members]
         L.cn_actor_pop_weights.argtypes = [vp, C.c_int, C.POINTER(CnActorWeights)]
+        L.cn_pop_record_create.argtypes = [C.POINTER(CnPopRecordMember), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]      # an array of members
+        L.cn_pop_record_destroy.argtypes = [vp]; L.cn_pop_record_destroy.restype = None
+        L.cn_pop_record_members.argtypes = [vp]
+        L.cn_pop_record_resetting.argtypes = [vp, C.c_int]; L.cn_pop_record_resetting.restype = vp
+        L.cn_pop_record.argtypes = [vp, C.c_float, vp]
         L.cn_ddpg_create.argtypes = [C.POINTER(CnDdpgConfig), C.c_int, C.POINTER(vp)]
         L.cn_ddpg_destroy.argtypes = [vp]; L.cn_ddpg_destroy.restype = None
         L.cn_ddpg_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]

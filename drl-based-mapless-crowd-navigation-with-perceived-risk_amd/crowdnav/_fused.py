@@ -178,3 +178,46 @@ class FusedPopulationActor:
                 self.h = None
         except Exception:
             pass
+
+
+class FusedPopulationRecorder:
+    """Owns one cn_pop_record handle: every member's replay write and episode log as two launches (include/crowdnav.h,
+    cn_pop_record_create).  members: the CnPopRecordMember of every member, in member order; keep: whatever their pointers point into
+    (the handle holds them for its lifetime).  Errors raise CrowdNavError("<function>: <cn_last_error>")."""
+
+    def __init__(self, members, obs_dim, device, dev_index, keep=None):
+        self._L = L = _abi.lib()
+        self.device, self.P, self.obs_dim, self._keep = device, len(members), int(obs_dim), keep
+        self.members = (_abi.CnPopRecordMember * self.P)(*members)
+        self.h = C.c_void_p()
+        self._check("_create", L.cn_pop_record_create(self.members, self.P, self.obs_dim, dev_index, C.byref(self.h)))
+
+    def _check(self, what, rc):
+        if rc != 0:
+            raise _abi.CrowdNavError("cn_pop_record%s: %s" % (what, self._L.cn_last_error().decode()))
+
+    def record(self, launch):
+        """cn_pop_record on torch's current stream: at most two launches; `launch` is the index the finished episodes' rows carry."""
+        self._check("", self._L.cn_pop_record(self.h, float(launch), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def resetting(self, member):
+        """A uint8 view [n_member] of the handle's flags of `member` (cn_pop_record_resetting), alive as long as the handle: row i's
+        next record is its environment's reset launch, not a transition."""
+        ptr = self._L.cn_pop_record_resetting(self.h, int(member))
+        if not ptr:
+            raise _abi.CrowdNavError("cn_pop_record_resetting: %s" % self._L.cn_last_error().decode())
+        n = int(self.members[int(member)].n)
+        if n == 0:
+            return torch.zeros(0, dtype=torch.uint8, device=self.device)
+
+        class _Arr:
+            __cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+        return torch.as_tensor(_Arr(), device=self.device)
+
+    def __del__(self):
+        try:
+            if self.h:
+                self._L.cn_pop_record_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass

@@ -99,9 +99,7 @@ class DeviceReplay:
         n = s.shape[0]
         dev = self.s.device
         if self._ring is None:
-            self._ring = _abi.CnReplayRing(s=self.s.data_ptr(), a=self.a.data_ptr(), r=self.r.data_ptr(), s2=self.s2.data_ptr(), d=self.d.data_ptr(),
-                                           capacity=self.cap, pos_dev=self.pos_dev.data_ptr(), size_dev=self.size_dev.data_ptr(),
-                                           obs_dim=self.obs_dim, reserved=0)
+            self._ring = self.ring_struct()
             self._slot = torch.zeros(0, dtype=torch.int32, device=dev)
         if self._slot.numel() < n:
             self._slot = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -134,6 +132,13 @@ class DeviceReplay:
         tot = c[-1]
         self.pos_dev.copy_((self.pos_dev + tot) % self.cap)
         self.size_dev.copy_(torch.clamp(self.size_dev + tot, max=self.cap))
+
+    def ring_struct(self):
+        """The `cn_replay_ring` of this buffer (cn_replay_write, cn_pop_record_create): its five arrays, capacity, position and size."""
+        from . import _abi
+        return _abi.CnReplayRing(s=self.s.data_ptr(), a=self.a.data_ptr(), r=self.r.data_ptr(), s2=self.s2.data_ptr(), d=self.d.data_ptr(),
+                                 capacity=self.cap, pos_dev=self.pos_dev.data_ptr(), size_dev=self.size_dev.data_ptr(),
+                                 obs_dim=self.obs_dim, reserved=0)
 
     def ring_fields(self):
         """The six replay_* fields of a learner's configuration (cn_td3_config, cn_ddpg_config, cn_dqn_config)."""
@@ -550,7 +555,10 @@ class Population:
     max_w and Adam's betas / eps (the library names the field and the member otherwise).
     Acting: bind_act(obs_list, out_list) once, then act() is ONE launch for all members (cn_actor_pop_forward) and sync_actors() ONE
     re-pack of all their actors (cn_actor_pop_pack); member p's actions are, bit for bit, agents[p].act_mfma's, and both advance the
-    same per-agent noise counter, so the two may be mixed."""
+    same per-agent noise counter, so the two may be mixed.
+    Recording: bind_record(...) once, then record(launch) is ONE call of two launches for all members (cn_pop_record) in place of P x
+    (DeviceReplay.add_masked, VecEnv.counters, VecEnv.returns, DeviceEpisodeLog.add) and the copies around them; rings and logs are,
+    bit for bit, what those leave."""
 
     def __init__(self, agents, replay_sample=None):
         agents = list(agents)
@@ -565,6 +573,7 @@ class Population:
         self._fused = FusedPopulation([a.fused_config() for a in agents], self.device, a0._dev_index,
                                       replay_sample=a0.replay_sample if replay_sample is None else replay_sample)
         self._actors = self._act_io = self._act_key = None
+        self._recorder = None
 
     def __len__(self):
         return len(self.agents)
@@ -634,6 +643,54 @@ class Population:
         """The CnActorWeights of member p (cn_actor_pop_weights): usable with cn_actor_forward / cn_rollout_policy while this
         population's binding lives."""
         return self._bound().weights(p)
+
+    def bind_record(self, envs, prev, obs, act, reward, done, elogs):
+        """Create the cn_pop_record handle for fixed buffers.  Per member p: envs[p] its VecEnv (the finished episodes' counters and
+        returns are read straight from its state records), prev[p] / obs[p] [n_p, obs_dim], act[p] [n_p, 2], reward[p] [n_p]
+        (contiguous float32), done[p] [n_p] (uint8), all on the population's device, and elogs[p] its episode log (rows [>= max_rows,
+        8] float32, n int64, tot [5] float64, max_rows: crowdnav.train.DeviceEpisodeLog).  The transitions go to agents[p].memory.
+        prev[p] must hold the observation the first record()'s actions are computed from; every record() leaves obs[p] in it."""
+        from . import _abi
+        from ._fused import FusedPopulationRecorder
+        lists = [list(x) for x in (envs, prev, obs, act, reward, done, elogs)]
+        if any(len(x) != len(self.agents) for x in lists):
+            raise ValueError("bind_record takes one environment, one buffer of each kind and one episode log per member")
+        D, dev = self.agents[0].actor.linear1.in_features, self.agents[0]._dev_index
+        members = []
+        for p, (ag, e, pv, o, u, r, d, lg) in enumerate(zip(self.agents, *lists)):
+            n = o.shape[0]
+            f32 = [(pv, (n, D)), (o, (n, D)), (u, (n, 2)), (r, (n,))]
+            ok = (all(tuple(t.shape) == sh and t.dtype == torch.float32 for t, sh in f32) and tuple(d.shape) == (n,) and d.dtype == torch.uint8
+                  and all(t.is_contiguous() and t.is_cuda and t.get_device() == dev for t in (pv, o, u, r, d))
+                  and lg.rows.dtype == torch.float32 and lg.rows.is_contiguous() and lg.rows.shape[0] >= lg.max_rows and lg.rows.shape[1] == 8
+                  and lg.n.dtype == torch.int64 and lg.tot.dtype == torch.float64 and lg.tot.numel() == 5
+                  and ag.memory.obs_dim == D and e.N == n)
+            if not ok:
+                raise ValueError("member %d: prev / obs must be [n, %d], act [n, 2], reward [n] (contiguous float32), done [n] (uint8) on %s "
+                                 "for an environment of n rows, and the log a DeviceEpisodeLog's tensors" % (p, D, self.device))
+            log = _abi.CnEpisodeLog(rows=lg.rows.data_ptr(), max_rows=lg.max_rows, n_dev=lg.n.data_ptr(), tot_dev=lg.tot.data_ptr())
+            members.append(_abi.CnPopRecordMember(env=e.h.value, counters=None, last_return=None, prev=pv.data_ptr(), obs=o.data_ptr(),
+                                                  action=u.data_ptr(), reward=r.data_ptr(), done=d.data_ptr(), ring=ag.memory.ring_struct(),
+                                                  log=log, n=n, reserved=0))
+        self._recorder = FusedPopulationRecorder(members, D, self.device, dev, keep=lists)
+        self._record_n = [m.n for m in members]
+        return self
+
+    def record(self, launch):
+        """Every member's transition and finished episodes of this launch as ONE call of two launches (cn_pop_record) on torch's
+        current stream: the replay write of the rows that are not reset launches, the episode log, prev <- obs.  Moves each member's
+        host-side bound on its ring's fill level as DeviceReplay.add_masked does, so ready() / len() stay right."""
+        if self._recorder is None:
+            raise RuntimeError("Population.bind_record(envs, prev, obs, act, reward, done, elogs) first: the recorder works on fixed buffers")
+        self._recorder.record(launch)
+        for a, n in zip(self.agents, self._record_n):
+            a.memory._ub = min(a.memory.cap, a.memory._ub + n)
+
+    def resetting(self, p):
+        """The recorder's flags of member p (uint8 [n_p], a view): set where the member's next record is a reset launch."""
+        if self._recorder is None:
+            raise RuntimeError("Population.bind_record first")
+        return self._recorder.resetting(p)
 
     def set_replay_sample(self, replay_sample):
         self._fused.set_replay_sample(replay_sample)

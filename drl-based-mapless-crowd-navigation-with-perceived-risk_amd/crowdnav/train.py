@@ -564,9 +564,11 @@ def train_population(a):
     (crowdnav.td3.Population) instead of P processes.  Member p has what `train()` with --seed <seed + p> has -- its environment
     handle of --envs environments, its Agent, replay, RunLog -- and writes what that run writes into
     <out>/member<p>/.  Per launch: ONE act launch for all members (--population-act one-launch, Population.act; per-member: P
-    act_mfma calls), one grouped environment step (cn_step_multi), P replay writes and P log adds; once EVERY member's replay holds more
-    than a batch, --updates population updates and ONE re-pack of the P actors (per-member: P sync_fused_weights, 4 launches each).
-    The two --population-act values give the same run, bit for bit.
+    act_mfma calls), one grouped environment step (cn_step_multi), ONE record call of two launches for all members' replay writes and
+    episode logs (--population-record one-call, Population.record; per-member: P x (add_masked, counters, returns, log add) and the
+    copies around them); once EVERY member's replay holds more than a batch, --updates population updates and ONE re-pack of the P
+    actors (per-member: P sync_fused_weights, 4 launches each).
+    The two --population-act values give the same run, bit for bit, and so do the two --population-record values.
     Member p's run IS the solo run --seed <seed + p> --learner fused (same parameters, same CSV rows) as long as the members' rings pass
     the batch size on the same launch: a member whose ring is not ready yet (it lost rows to reset launches) holds the others back, so
     that the update counters -- which key the sampling and drive policy_delay -- stay aligned; from then on that member's solo run
@@ -609,23 +611,33 @@ def train_population(a):
         for ag in agents:
             ag.sync_fused_weights()
     reward, done = envs.reward, envs.done
+    one_call = a.population_record == "one-call"
+    if one_call:
+        prev.copy_(obs)                                                # once: every record() leaves the new observation in prev
+        pop.bind_record(envs.envs, *[[x[r] for r in rows] for x in (prev, obs, act, reward, done)], elogs)
     for it in range(1, a.launches + 1):
         if one_launch:
             pop.act(add_noise=True)
         else:
             for ag, r in zip(agents, rows):
                 ag.act_mfma(obs[r], out=act[r], add_noise=True)
-        prev.copy_(obs)
-        envs.fork()                                                    # the members' steps wait for the actions ...
-        step_all()
-        cnt = [e.counters() for e in envs.envs]
-        ret = [e.returns()[0] for e in envs.envs]
-        envs.join()                                                    # ... and everything below for the steps
-        keep = ~resetting
-        for p, (ag, r) in enumerate(zip(agents, rows)):
-            ag.memory.add_masked(prev[r], act[r], reward[r], obs[r], done[r], keep[r])
-            elogs[p].add(done[r], cnt[p], ret[p], it, keep[r])
-        resetting = done.bool()
+        if one_call:
+            envs.fork()                                                # the members' steps wait for the actions ...
+            step_all()
+            envs.join()                                                # ... and everything below for the steps
+            pop.record(it)
+        else:
+            prev.copy_(obs)
+            envs.fork()
+            step_all()
+            cnt = [e.counters() for e in envs.envs]
+            ret = [e.returns()[0] for e in envs.envs]
+            envs.join()
+            keep = ~resetting
+            for p, (ag, r) in enumerate(zip(agents, rows)):
+                ag.memory.add_masked(prev[r], act[r], reward[r], obs[r], done[r], keep[r])
+                elogs[p].add(done[r], cnt[p], ret[p], it, keep[r])
+            resetting = done.bool()
         if not learning:
             learning = pop.ready()                                     # every member: the update counters stay aligned
         if learning:
@@ -732,6 +744,9 @@ def build_parser():
     ap.add_argument("--population-act", default=None, choices=["one-launch", "per-member"], help="--population only: one-launch (default) = all "
                     "members act in one cn_actor_pop_forward and re-pack in one cn_actor_pop_pack per training launch; per-member = one "
                     "cn_actor_forward and one 4-launch re-pack per member.  Same results, bit for bit")
+    ap.add_argument("--population-record", default=None, choices=["one-call", "per-member"], help="--population only: one-call (default) = all "
+                    "members' replay writes and episode logs in one cn_pop_record (two launches) per training launch; per-member = one "
+                    "cn_replay_write, cn_get_counters, cn_get_returns and cn_episode_log_add per member.  Same results, bit for bit")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="default: runs/<algo>")
     ap.add_argument("--csv", action="store_true", help="one CSV row per finished episode in the reference's 8-column schema (recorded on the device, appended to the file at "
@@ -788,6 +803,10 @@ def parse_args(argv=None):
         ap.error("--population-act selects how a --population acts: it needs --population")
     if a.population_act is None:
         a.population_act = "one-launch"
+    if a.population_record is not None and not a.population:
+        ap.error("--population-record selects how a --population records its transitions: it needs --population")
+    if a.population_record is None:
+        a.population_record = "one-call"
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     return a

@@ -11,6 +11,8 @@
 # 720-ray one), CN_TU=5 (round 6: the sequence / policy kernels of the contact ticks and of the two older observation layouts)
 # -- units 2-5 with -mllvm -disable-machine-licm: see the note above the kernel definitions -- and CN_TU=6 (the population's actor
 # kernels, cn_actor_pop_*: apart, so that unit 1's kernels keep their instruction streams).
+# crowdnav_pop_record.hip holds the population recorder's two kernels (cn_pop_record); their bodies, crowdnav_record.h, are the ones
+# crowdnav_td3.hip's cn_replay_write / cn_episode_log_add kernels are made of.
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="$HERE/../lib"
@@ -32,11 +34,12 @@ build_lib() {   # $1 = output name, $2.. = extra flags
   "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/abi.o" "$HERE/crowdnav_abi.hip" & pids+=($!)
   "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/td3.o" "$HERE/crowdnav_td3.hip" & pids+=($!)
   "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/tab.o" "$HERE/crowdnav_tab.hip" & pids+=($!)
+  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/rec.o" "$HERE/crowdnav_pop_record.hip" & pids+=($!)
   local failed=0 pid
   for pid in "${pids[@]}"; do wait "$pid" || failed=1; done     # a bare `wait` returns 0 whatever the jobs returned
   if [ "$failed" != 0 ]; then echo "build.sh: a compile of $name failed" >&2; return 1; fi
   # link next to the target and rename: a process that already mapped the old file keeps it, nobody maps a partial one
-  "$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/.$name.$$" "$T/k1.o" "$T/k2.o" "$T/k3.o" "$T/k4.o" "$T/k5.o" "$T/k6.o" "$T/abi.o" "$T/td3.o" "$T/tab.o"
+  "$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/.$name.$$" "$T/k1.o" "$T/k2.o" "$T/k3.o" "$T/k4.o" "$T/k5.o" "$T/k6.o" "$T/abi.o" "$T/td3.o" "$T/tab.o" "$T/rec.o"
   mv -f "$OUT/.$name.$$" "$OUT/$name"
 }
 if [ "$WHAT" = "product" ] || [ "$WHAT" = "all" ]; then

@@ -29,6 +29,7 @@
 
 #include "../../include/crowdnav.h"
 #include "crowdnav_device.h"
+#include "crowdnav_record.h"
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
@@ -673,55 +674,17 @@ __device__ __forceinline__ float td3_wave_sum(float v)
 // the next launch; dW3a = dl^T h2a = a two-row job of td3_wgrad_kernel.  (Rounds 3-4: td3_dlogit_kernel, one wavefront per row,
 // 4.8 us, and td3_actor_head_bwd_kernel, 9 us; the critics had td3_q_head_kernel and td3_critic_head_bwd_kernel.)
 // ---- the collection loop's bookkeeping (cn_replay_write, cn_episode_log_add) --------------------------------------------------
-// inclusive scan of one int per thread over a 1024-thread workgroup (wave scans + a scan of the 16 wave totals)
-__device__ __forceinline__ int cn_block_scan_1024(int v, int* __restrict__ wsum, int& total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(v, d, 64); if (lane >= d) v += u; }
-    if (lane == 63) wsum[wave] = v;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) { const int x = wsum[w]; if (w < wave) before += x; tot += x; }
-    __syncthreads();
-    total = tot;
-    return v + before;
-}
-// slots of the kept rows, in row order; the ring's position and fill level move at the end (one workgroup: they are read first)
+// (bodies: crowdnav_record.h, shared with cn_pop_record's kernels -- crowdnav_pop_record.hip -- so that both are the same text)
 __global__ void __launch_bounds__(1024) cn_replay_slot_kernel(const uint8_t* __restrict__ keep, int n, int64_t cap, int64_t* pos_dev,
                                                               int64_t* size_dev, int32_t* __restrict__ slot)
 {
     __shared__ int wsum[16];
-    const int64_t pos = *pos_dev, size = *size_dev;
-    int64_t carry = 0;
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int k = i < n ? (keep ? (keep[i] != 0) : 1) : 0;
-        int tot;
-        const int c = cn_block_scan_1024(k, wsum, tot);
-        if (i < n) slot[i] = k ? (int32_t)((pos + carry + c - 1) % cap) : -1;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) {
-        *pos_dev = (pos + carry) % cap;
-        *size_dev = size + carry < cap ? size + carry : cap;
-    }
+    cn_replay_slot_body(CnKeepBytes{keep}, n, cap, pos_dev, size_dev, slot, wsum);
 }
 struct ReplayCopyArgs { cn_replay_ring ring; const float *s, *a, *r, *s2; const uint8_t* done; const int32_t* slot; };
 __global__ void __launch_bounds__(256) cn_replay_copy_kernel(ReplayCopyArgs p)
 {
-    const int i = blockIdx.x, D = p.ring.obs_dim;
-    const int32_t sl = p.slot[i];
-    if (sl < 0) return;
-    const float* __restrict__ s = p.s + (size_t)i * D;
-    const float* __restrict__ s2 = p.s2 + (size_t)i * D;
-    float* __restrict__ ds = p.ring.s + (size_t)sl * D;
-    float* __restrict__ ds2 = p.ring.s2 + (size_t)sl * D;
-    for (int c = threadIdx.x; c < D; c += blockDim.x) { ds[c] = s[c]; ds2[c] = s2[c]; }
-    if (threadIdx.x < 2) p.ring.a[(size_t)sl * 2 + threadIdx.x] = p.a[(size_t)i * 2 + threadIdx.x];
-    if (threadIdx.x == 2) p.ring.r[sl] = p.r[i];
-    if (threadIdx.x == 3) p.ring.d[sl] = p.done[i] ? 1.f : 0.f;
+    cn_replay_copy_body(p.ring, p.s, p.a, p.r, p.s2, p.done, p.slot, blockIdx.x);
 }
 // the finished episodes' rows and the running totals, one workgroup
 struct EpisodeLogArgs { cn_episode_log log; const uint8_t* done; const int32_t* counters; int cols; const float* ret; const uint8_t* trans; float launch; int n; };
@@ -729,46 +692,7 @@ __global__ void __launch_bounds__(1024) cn_episode_log_kernel(EpisodeLogArgs p)
 {
     __shared__ int wsum[16];
     __shared__ double red[5][16];
-    const int64_t n0 = *p.log.n_dev;
-    int64_t carry = 0;
-    double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int base = 0; base < p.n; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int k = i < p.n ? (p.done[i] != 0) : 0;
-        int tot;
-        const int c = cn_block_scan_1024(k, wsum, tot);
-        if (i < p.n) {
-            const int32_t* __restrict__ cr = p.counters + (size_t)i * p.cols;
-            if (k) {
-                const int64_t at = n0 + carry + c - 1;
-                if (at < p.log.max_rows) {
-                    float* __restrict__ row = p.log.rows + (size_t)at * 8;
-                    row[0] = (float)cr[4]; row[1] = (float)cr[5]; row[2] = p.ret[i]; row[3] = (float)cr[13];
-                    row[4] = (float)cr[10]; row[5] = (float)cr[11]; row[6] = (float)cr[12]; row[7] = p.launch;
-                }
-                t[0] += 1.0; t[1] += (double)(float)cr[4]; t[2] += (double)p.ret[i]; t[3] += (double)(float)cr[13];
-            }
-            if (p.trans[i]) t[4] += 1.0;
-        }
-        carry += tot;
-    }
-    // totals: lanes, then wavefronts, in a fixed order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        double v = t[q];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        if (lane == 0) red[q][wave] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        double v = 0.0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) v += red[threadIdx.x][w];
-        p.log.tot_dev[threadIdx.x] += v;
-    }
-    if (threadIdx.x == 0) *p.log.n_dev = n0 + carry;
+    cn_episode_log_body(p.log, p.done, CnEpisodeFromArrays{p.counters, p.cols, p.ret}, CnKeepBytes{p.trans}, p.launch, p.n, wsum, red);
 }
 
 }  // namespace

@@ -701,6 +701,57 @@ typedef struct cn_episode_log {
 int cn_episode_log_add(const cn_episode_log* log, const uint8_t* done, const int32_t* counters, int counter_cols,
                        const float* last_return, const uint8_t* transitions, float launch, int n, int device, void* stream);
 
+/* A population's recorder: the bookkeeping above for n_members members -- every member's cn_replay_write, its cn_get_counters /
+ * cn_get_returns, its cn_episode_log_add, and the `prev <- obs`, `keep = !resetting`, `resetting <- done` around them -- as TWO
+ * launches whatever n_members is, instead of about five small dependent launches per member.  Member p rides in the grid's z
+ * dimension; its job is a row of a device table that cn_pop_record_create builds and uploads once (a member's pointers never change).
+ * Per member: its replay ring and episode log; prev [n][obs_dim] (the observation the actions were computed from), obs [n][obs_dim],
+ * action [n][2], reward [n], done [n] bytes; and where the counters and the last return come from: env != NULL -- read straight from
+ * that environment's state records (CN_SI_SUCCESS, CN_SI_FAILURE, CN_SD_LAST_EGO_VIOL, CN_SD_LAST_SOCIAL_VIOL, CN_SD_LAST_OBST_STEPS,
+ * CN_SD_LAST_EP_STEPS, CN_SD_LAST_RETURN, with cn_get_counters' / cn_get_returns' conversions; n must equal its n_envs) -- or
+ * env == NULL and explicit counters [n][CN_COUNTER_COLS] and last_return [n], as cn_episode_log_add takes them.  n may differ between
+ * members; n == 0 is allowed with NULL row pointers.  obs_dim is one for all members and must equal every ring's obs_dim.
+ * The handle owns, per member, n int32 of slot scratch and the byte array resetting [n], zero at create (cn_pop_record_resetting: its
+ * device pointer, so that a caller may set it, e.g. when resuming; member out of range or a NULL handle: NULL).
+ * Statement: after cn_pop_record(h, launch, stream), for every member p, whatever n_members and p are:
+ *   - ring_p (the five arrays below capacity, *pos_dev, *size_dev) is BYTE FOR BYTE what cn_replay_write(&ring_p, prev_p, action_p,
+ *     reward_p, obs_p, done_p, keep, n_p, ...) leaves, with keep[i] = !resetting_p[i] as it stood before the call;
+ *   - log_p (rows below max_rows, *n_dev, tot_dev[5]) is BIT FOR BIT what cn_episode_log_add(&log_p, done_p, counters, 14,
+ *     last_return, keep, launch, n_p, ...) leaves, counters / last_return being what cn_get_counters / cn_get_returns of env_p return at
+ *     that point, or the explicit arrays (the float64 totals are summed in cn_episode_log_add's order: the kernels share its code);
+ *   - afterwards resetting_p[i] = (done_p[i] != 0) and prev_p equals obs_p over all n_p rows, kept or not: the next call's previous
+ *     observation costs no launch of its own;
+ *   - rows at and beyond n_p of any buffer, and ring rows that receive nothing, are not touched.  If every n_p is 0, no launch is made.
+ * Launch A, grid (1, 1, P) x 1024: the keep scan and the slots, the ring's position and fill level, the episode log, resetting <- done.
+ * Launch B, grid (max n_p, 1, P) x 256: a row's copy into its slot, then prev <- obs for the row.  (Not one launch: every copying
+ * workgroup would have to read *pos_dev before one of them advances it.)  Enqueue-only: no host read, no copy, `launch` by value;
+ * capturable on one stream.
+ * Refused before any device work, text in cn_last_error naming the field and the member.  CN_ERR_ARG: a NULL handle / members / out;
+ * n_members outside 1 ... CN_POP_RECORD_MAX; n < 0; a NULL row pointer in a member with n > 0; neither env nor both explicit arrays; n
+ * different from the env's n_envs; an incomplete ring or log; n > ring.capacity; log.max_rows < 0; a member index out of range.
+ * CN_ERR_CONFIG: obs_dim < 1; ring.obs_dim != obs_dim; two members naming the same ring array, pos_dev, size_dev, log rows / n_dev /
+ * tot_dev, or prev (they would race inside a launch). */
+#define CN_POP_RECORD_MAX 64
+typedef struct cn_pop_record_member {
+    cn_handle env;               /* or NULL: then counters and last_return below */
+    const int32_t* counters;     /* dev [n][CN_COUNTER_COLS]; read when env == NULL */
+    const float* last_return;    /* dev [n]; read when env == NULL */
+    float* prev;                 /* dev [n][obs_dim]: read (the transition's s), then overwritten with obs */
+    const float* obs;            /* dev [n][obs_dim] (the transition's s2) */
+    const float* action;         /* dev [n][2] */
+    const float* reward;         /* dev [n] */
+    const uint8_t* done;         /* dev [n] */
+    cn_replay_ring ring;
+    cn_episode_log log;
+    int32_t n, reserved;         /* n >= 0; members may differ */
+} cn_pop_record_member;
+typedef struct cn_pop_record_s* cn_pop_record_handle;
+int cn_pop_record_create(const cn_pop_record_member* members, int n_members, int obs_dim, int device, cn_pop_record_handle* out);
+void cn_pop_record_destroy(cn_pop_record_handle h);
+int cn_pop_record_members(cn_pop_record_handle h);
+uint8_t* cn_pop_record_resetting(cn_pop_record_handle h, int member);        /* dev [n_member] bytes, owned by the handle */
+int cn_pop_record(cn_pop_record_handle h, float launch, void* stream);        /* at most TWO launches */
+
 /* n_steps calls of cn_step (auto_reset = 2, the next-step reset convention) with OPEN-LOOP actions -- scripted or recorded
  * actions, action repeat, the uniform-random warm-up phase of an off-policy learner -- as ONE launch: a wavefront keeps its
  * environment for the whole launch and walks its steps at its own pace (no launch boundary and no device-wide join between
