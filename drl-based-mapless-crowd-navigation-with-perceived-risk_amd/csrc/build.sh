@@ -6,11 +6,11 @@
 #   build.sh all        both
 #   -ffp-contract=off : no implicit FMA contraction; every fma() in the sources is explicit, which is
 #                       what makes the simulator bit-reproducible against the CPU oracle
-# crowdnav_kernel.hip is compiled as four units: CN_TU=1 (every one-step kernel), CN_TU=2 (the sequence / policy kernels of the
-# plain simulator), CN_TU=3 (the sequence kernels of the social-force / wheel-ramp simulators), CN_TU=4 (their policy kernels + the
-# 720-ray one), CN_TU=5 (round 6: the sequence / policy kernels of the contact ticks and of the two older observation layouts)
-# -- units 2-5 with -mllvm -disable-machine-licm: see the note above the kernel definitions -- and CN_TU=6 (the population's actor
-# kernels, cn_actor_pop_*: apart, so that unit 1's kernels keep their instruction streams).
+# crowdnav_kernel.hip is compiled as six units (-DCN_TU=n).  Which kernel is defined in which unit is a column of the kernel table,
+# crowdnav_variants.h: unit 1 holds every one-step kernel, units 2-5 the sequence and policy kernels (their rows name the unit) --
+# compiled with -mllvm -disable-machine-licm: see the note above the kernel definitions -- and unit 6 the population's actor
+# kernels (cn_actor_pop_*: apart, so that unit 1's kernels keep their instruction streams).  The units only spread the compile
+# over processes and flags; the file also compiles as one unit with CN_TU unset.
 # crowdnav_pop_record.hip holds the population recorder's two kernels (cn_pop_record); their bodies, crowdnav_record.h, are the ones
 # crowdnav_td3.hip's cn_replay_write / cn_episode_log_add kernels are made of.
 set -euo pipefail

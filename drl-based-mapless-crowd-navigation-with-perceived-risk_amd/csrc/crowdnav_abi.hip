@@ -15,98 +15,20 @@
 #include "crowdnav_device.h"
 #include "crowdnav_kernel.h"
 #include "crowdnav_record.h"
+#include "crowdnav_variants.h"
 
-extern "C" __global__ void cn_env_kernel(CnKParams p);
-extern "C" __global__ void cn_env_kernel_fair(CnKParams p);
-extern "C" __global__ void cn_env_kernel_ext(CnKParams p);
-extern "C" __global__ void cn_env_kernel_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_ct(CnKParams p);
-extern "C" __global__ void cn_env_kernel_ct_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_ct(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_ct_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_sf(CnKParams p);
-extern "C" __global__ void cn_env_kernel_sf_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_sf(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_sf_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_rw(CnKParams p);
-extern "C" __global__ void cn_env_kernel_rw_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_rw_ext(CnKParams p);
-extern "C" __global__ void cn_env_kernel_orig(CnKParams p);
-extern "C" __global__ void cn_env_kernel_orig_ext(CnKParams p);
-extern "C" __global__ void cn_env_kernel_orig_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_sfd(CnKParams p);
-extern "C" __global__ void cn_env_kernel_sfd_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_sfd(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_sfd_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_wa(CnKParams p);
-extern "C" __global__ void cn_env_kernel_wa_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_wa(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_wa_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq(CnKParams p);
-extern "C" __global__ void cn_env_kernel_s360(CnKParams p);
-extern "C" __global__ void cn_env_kernel_fair_s360(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq_s360(CnKParams p);
-extern "C" __global__ void cn_env_kernel_s360_w4(CnKParams p);
-extern "C" __global__ void cn_env_kernel_fair_s360_w4(CnKParams p);
-extern "C" __global__ void cn_env_kernel_s360_x2(CnKParams p);
-
-extern "C" __global__ void cn_env_kernel_seq_s720(CnKParams p);
-extern "C" __global__ void cn_policy_kernel(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_s360(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_gt(CnKParams p);
-extern "C" __global__ void cn_env_kernel_s720(CnKParams p);
-extern "C" __global__ void cn_env_kernel_fair_s720(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_seq(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq_sf(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq_sfd(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq_wa(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_seq_sf(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_seq_sfd(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_seq_wa(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_s720(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_sf(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_sfd(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_wa(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_gt_sf(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_gt_sfd(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_gt_wa(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq_ct(CnKParams p);
-extern "C" __global__ void cn_env_kernel_gt_seq_ct(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq_orig(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq_rw(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_ct(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_gt_ct(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_orig(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_rw(CnKParams p);
-extern "C" __global__ void cn_env_kernel_wide(CnKParams p);
-extern "C" __global__ void cn_env_kernel_wide_same(CnKParams p);
-extern "C" __global__ void cn_env_kernel_wide_ext(CnKParams p);
-extern "C" __global__ void cn_env_kernel_seq_wide(CnKParams p);
-extern "C" __global__ void cn_policy_kernel_wide(CnKParams p);
-// every kernel launched with cn_create's dynamic LDS size (hipFuncAttributeMaxDynamicSharedMemorySize above 64 KiB)
-static const void* const kDynamicLdsKernels[] = {
-    (const void*)cn_env_kernel, (const void*)cn_env_kernel_fair, (const void*)cn_env_kernel_ext, (const void*)cn_env_kernel_same,
-    (const void*)cn_env_kernel_gt, (const void*)cn_env_kernel_gt_same, (const void*)cn_env_kernel_ct, (const void*)cn_env_kernel_ct_same,
-    (const void*)cn_env_kernel_gt_ct, (const void*)cn_env_kernel_gt_ct_same, (const void*)cn_env_kernel_sf, (const void*)cn_env_kernel_sf_same,
-    (const void*)cn_env_kernel_gt_sf, (const void*)cn_env_kernel_gt_sf_same, (const void*)cn_env_kernel_rw, (const void*)cn_env_kernel_rw_same,
-    (const void*)cn_env_kernel_rw_ext, (const void*)cn_env_kernel_orig, (const void*)cn_env_kernel_orig_ext, (const void*)cn_env_kernel_orig_same,
-    (const void*)cn_env_kernel_sfd, (const void*)cn_env_kernel_sfd_same, (const void*)cn_env_kernel_gt_sfd, (const void*)cn_env_kernel_gt_sfd_same,
-    (const void*)cn_env_kernel_wa, (const void*)cn_env_kernel_wa_same, (const void*)cn_env_kernel_gt_wa, (const void*)cn_env_kernel_gt_wa_same,
-    (const void*)cn_env_kernel_seq, (const void*)cn_env_kernel_s360, (const void*)cn_env_kernel_fair_s360, (const void*)cn_env_kernel_seq_s360,
-    (const void*)cn_env_kernel_seq_s720, (const void*)cn_env_kernel_s720, (const void*)cn_env_kernel_fair_s720, (const void*)cn_env_kernel_gt_seq,
-    (const void*)cn_env_kernel_seq_sf, (const void*)cn_env_kernel_seq_sfd, (const void*)cn_env_kernel_seq_wa,
-    (const void*)cn_env_kernel_gt_seq_sf, (const void*)cn_env_kernel_gt_seq_sfd, (const void*)cn_env_kernel_gt_seq_wa,
-    (const void*)cn_env_kernel_s360_w4, (const void*)cn_env_kernel_fair_s360_w4, (const void*)cn_env_kernel_s360_x2,
-    (const void*)cn_env_kernel_seq_ct, (const void*)cn_env_kernel_gt_seq_ct, (const void*)cn_env_kernel_seq_orig, (const void*)cn_env_kernel_seq_rw,
-    (const void*)cn_env_kernel_wide, (const void*)cn_env_kernel_wide_same, (const void*)cn_env_kernel_wide_ext, (const void*)cn_env_kernel_seq_wide};
-static const void* const kPolicyKernels[] = {
-    (const void*)cn_policy_kernel, (const void*)cn_policy_kernel_s360, (const void*)cn_policy_kernel_gt, (const void*)cn_policy_kernel_s720,
-    (const void*)cn_policy_kernel_sf, (const void*)cn_policy_kernel_sfd, (const void*)cn_policy_kernel_wa,
-    (const void*)cn_policy_kernel_gt_sf, (const void*)cn_policy_kernel_gt_sfd, (const void*)cn_policy_kernel_gt_wa,
-    (const void*)cn_policy_kernel_ct, (const void*)cn_policy_kernel_gt_ct, (const void*)cn_policy_kernel_orig, (const void*)cn_policy_kernel_rw,
-    (const void*)cn_policy_kernel_wide};
+// every kernel that takes CnKParams, from the table (crowdnav_variants.h): declarations, then the functions in cn_kernel_info's order --
+// [0, CN_K_N_DYNAMIC) are launched with cn_create's dynamic LDS size, [CN_K_N_DYNAMIC, CN_K_COUNT) are the policy kernels (both ranges
+// get hipFuncAttributeMaxDynamicSharedMemorySize above 64 KiB)
+typedef void (*cn_kernel_fn)(CnKParams);
+#define CN_KERNEL(NAME, TU, COMPACT, GEOMETRY) extern "C" __global__ void NAME(CnKParams p);
+CN_DYNAMIC_LDS_KERNELS CN_POLICY_KERNELS
+#undef CN_KERNEL
+#define CN_KERNEL(NAME, TU, COMPACT, GEOMETRY) NAME,
+static const cn_kernel_fn kKernelFn[] = { CN_DYNAMIC_LDS_KERNELS CN_POLICY_KERNELS };
+#undef CN_KERNEL
+static_assert(sizeof(kKernelFn) / sizeof(kKernelFn[0]) == CN_K_COUNT && CN_K_N_DYNAMIC == 53 && CN_K_COUNT - CN_K_N_DYNAMIC == 15,
+              "the table's 53 dynamic-LDS kernels and 15 policy kernels");
 extern "C" __global__ void cn_bbox_kernel(CnKParams p, double* out);
 extern "C" __global__ void cn_gather_kernel(CnKParams p, float* last_ret, float* run_ret, int32_t* counters);
 
@@ -121,6 +43,7 @@ struct cn_env_s {
     int device;
     int D, max_conf, trk_cap;
     bool wide = false;                // trk_cap > CN_MAX_TRACKS: the tracker table stays in HBM (the _wide kernels)
+    int world = 0;                    // CN_W_*: this configuration's row of CN_WORLDS (crowdnav_variants.h)
     size_t lds;
     CnKParams kp;        // template with state/table pointers filled in
     double *d_lidar = nullptr, *d_poly = nullptr, *d_ped_init = nullptr, *d_ped_preset = nullptr, *d_trk = nullptr;
@@ -321,12 +244,18 @@ static int upload_initial_state(cn_env_s* h)
     return CN_OK;
 }
 
-typedef void (*cn_kernel_fn)(CnKParams);
 struct KernelChoice { cn_kernel_fn fn; const char* name; bool compact = false; int wpb = 1; bool x2 = false; };      // compact: launched with h->lds_shape; wpb: environments (waves) per workgroup
-#define CN_KC(f) KernelChoice{f, #f}
-#define CN_KCC(f) KernelChoice{f, #f, true}
 static size_t lds_of(const cn_env_s* h, const KernelChoice& kc) { return kc.compact ? h->lds_shape : h->lds; }
-static KernelChoice choose_policy_kernel(const cn_env_s* h);
+// Which kernel a call of `form` (CN_FORM_*) on this handle runs: cn_select_kernel's row of the table.  overlapped: a cn_step that is one
+// of several in a cn_step_multi.  fn == nullptr: the world has no such form.
+static CnLaunchFacts launch_facts(const cn_env_s* h, bool overlapped) { return CnLaunchFacts{h->arbitration, overlapped, h->n_cus, h->cfg.n_envs, h->group_envs, h->x2, h->wpb4}; }
+static KernelChoice kernel_of(const cn_env_s* h, int form, bool overlapped = false)
+{
+    const int id = cn_select_kernel(h->world, form, launch_facts(h, overlapped));
+    if (id < 0) return KernelChoice{nullptr, nullptr};
+    const CnKernelInfo& ki = cn_kernel_info[id];
+    return KernelChoice{kKernelFn[id], ki.name, ki.compact, ki.geometry == CN_GEO_W4 ? h->wpb4 : 1, ki.geometry == CN_GEO_X2};
+}
 
 extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
 {
@@ -450,8 +379,11 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
     // Four environments per workgroup for the 360-ray step kernels when the whole launch is resident at once (n_envs <= 16 wavefronts
     // x CUs): a quarter of the workgroups for the dispatcher to create, + 2-3 % in every decomposition at 4096 envs; with several
     // rounds of wavefronts (16384 envs) the coarser release of LDS / wave slots costs 3.6 % instead, and the 720-ray shape (12
-    // wavefronts per CU, 1.33 rounds at 4096) loses 7-25 % (profiles/r05/ab_wpb.txt).  Decided per launch in choose_kernel() from
+    // wavefronts per CU, 1.33 rounds at 4096) loses 7-25 % (profiles/r05/ab_wpb.txt).  Decided per launch in cn_select_kernel() from
     // max(n_envs, cn_set_group_envs).  CN_WPB=1 / 2 / 4 / 8 / 16 overrides for A/B runs.
+    h->world = cn_world_index(c.obs_layout, h->wide, c.risk_mode == CN_RISK_GT, c.wheel_accel > 0.0,
+                              c.ped_mode == 2 && !k.sf_pair_matrix && P <= 128 /* dense social force: per-lane near masks */,
+                              c.ped_mode == 2, c.ped_contact != 0, h->shape360, h->shape720);
     h->wpb4 = 4;
     if (getenv("CN_X2")) h->x2 = atoi(getenv("CN_X2")) ? 1 : 0;
     if (getenv("CN_WPB")) { h->wpb4 = atoi(getenv("CN_WPB")); if (h->wpb4 != 2 && h->wpb4 != 4 && h->wpb4 != 8 && h->wpb4 != 16) h->wpb4 = 0; }
@@ -490,20 +422,20 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
         k.assoc_tab = (const int16_t*)(h->d_poly + 128);
         HIPCHK(hipMemcpy((void*)k.assoc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
     }
-    if (h->shape360 && h->wpb4) {     // the _w4 kernels are only ever launched for the headline shape (choose_kernel)
+    if (h->shape360 && h->wpb4) {     // the _w4 kernels are only ever launched for the headline shape (cn_select_kernel)
         const size_t w4 = (size_t)h->wpb4 * ((h->lds + 15) & ~(size_t)15);      // what launch() asks for
         if (w4 > 160 * 1024) h->wpb4 = 0;                                        // (a CN_WPB override that does not fit a CU's LDS: one per workgroup)
         else if (w4 > 64 * 1024) {
-            HIPCHK(hipFuncSetAttribute((const void*)cn_env_kernel_s360_w4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w4));
-            HIPCHK(hipFuncSetAttribute((const void*)cn_env_kernel_fair_s360_w4, hipFuncAttributeMaxDynamicSharedMemorySize, (int)w4));
+            for (int id : {CN_K_cn_env_kernel_s360_w4, CN_K_cn_env_kernel_fair_s360_w4})
+                HIPCHK(hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)w4));
         }
     }
     if (h->lds > 64 * 1024)
-        for (const void* f : kDynamicLdsKernels) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
+        for (int id = 0; id < CN_K_N_DYNAMIC; ++id) HIPCHK(hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
     {   // cn_rollout_policy: 16 (or 8) environments per workgroup, their working sets 16-byte aligned one after the other (the
         // actor's 16-row tile is laid out compactly over them between two steps), + the workgroup's actions
-        // (whichever kernel choose_policy_kernel picks for this handle: the 720-ray shape's has the compact layout)
-        h->pol_wave_lds = ((choose_policy_kernel(h).compact ? h->lds_shape : h->lds) + 15) & ~(size_t)15;
+        // (this world's policy kernel: the 720-ray shape's has the compact layout)
+        h->pol_wave_lds = (lds_of(h, kernel_of(h, CN_FORM_POLICY)) + 15) & ~(size_t)15;
         const size_t tile = sizeof(float) * (16 * (size_t)(((h->D + 31) & ~31) + 1) + 16 * 257);
         const char* pe_env = getenv("CN_POL_ENVS");             // experiments: CN_POL_ENVS=8 forces the 8-environment workgroups
         // (cn_policy_kernel_rw is compiled for 8 waves: the RW observation needs more than the 128 vector registers a 16-wave workgroup leaves a wave)
@@ -514,7 +446,7 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
             if (tot <= 160 * 1024) { h->pol_lds = tot; h->pol_envs = pe; h->pol_act_off = off; }
         }
         if (h->pol_lds > 64 * 1024)
-            for (const void* f : kPolicyKernels) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->pol_lds));
+            for (int id = CN_K_N_DYNAMIC; id < CN_K_COUNT; ++id) HIPCHK(hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->pol_lds));
     }
     *out = guard.release();
     return CN_OK;
@@ -566,82 +498,10 @@ extern "C" int cn_set_ped_preset_vel(cn_handle h, const double* vxy)
     return CN_OK;
 }
 
-// Does a cn_step launch of this handle use the fair kernel?  (`overlapped`: the call is one of several in a cn_step_multi)
-static bool fair_launch(const cn_env_s* h, bool overlapped)
-{
-    if (h->arbitration == CN_ARB_FAIR) return true;
-    if (h->arbitration == CN_ARB_OLDEST_FIRST || overlapped) return false;
-    return h->n_cus > 0 && h->cfg.n_envs >= 8 * h->n_cus;
-}
-
-
-// Which kernel a launch of this handle runs.  ext: externally supplied /scan + /odom; same: Env.step + same-call reset.
-static KernelChoice choose_kernel(const cn_env_s* h, bool ext, bool same, bool overlapped)
-{
-    const cn_config& c = h->cfg;
-    if (c.obs_layout == CN_LAYOUT_REALWORLD) return ext ? CN_KC(cn_env_kernel_rw_ext) : same ? CN_KC(cn_env_kernel_rw_same) : CN_KC(cn_env_kernel_rw);
-    if (c.obs_layout == CN_LAYOUT_ORIGINAL) return ext ? CN_KC(cn_env_kernel_orig_ext) : same ? CN_KC(cn_env_kernel_orig_same) : CN_KC(cn_env_kernel_orig);
-    if (h->wide) return ext ? CN_KC(cn_env_kernel_wide_ext) : same ? CN_KC(cn_env_kernel_wide_same) : CN_KC(cn_env_kernel_wide);   // (cn_create: layout 0, tracker, plain simulator)
-    if (ext) return c.risk_mode == CN_RISK_GT ? KernelChoice{nullptr, nullptr} : CN_KC(cn_env_kernel_ext);
-    // simulated sensors: {lidar tracker, gt} x {plain, contact, social force, wheel ramp} x {one observation per launch, step + same-call reset}
-    const bool gt = c.risk_mode == CN_RISK_GT, ct = c.ped_contact != 0, sf = c.ped_mode == 2, wa = c.wheel_accel > 0.0;
-    if (wa) return gt ? (same ? CN_KC(cn_env_kernel_gt_wa_same) : CN_KC(cn_env_kernel_gt_wa)) : (same ? CN_KC(cn_env_kernel_wa_same) : CN_KC(cn_env_kernel_wa));
-    const bool sfd = sf && !h->kp.sf_pair_matrix && c.n_peds <= 128;      // dense social-force crowd: per-lane near masks
-    if (sfd) return gt ? (same ? CN_KC(cn_env_kernel_gt_sfd_same) : CN_KC(cn_env_kernel_gt_sfd)) : (same ? CN_KC(cn_env_kernel_sfd_same) : CN_KC(cn_env_kernel_sfd));
-    if (gt) return sf ? (same ? CN_KC(cn_env_kernel_gt_sf_same) : CN_KC(cn_env_kernel_gt_sf))
-                      : ct ? (same ? CN_KC(cn_env_kernel_gt_ct_same) : CN_KC(cn_env_kernel_gt_ct)) : (same ? CN_KC(cn_env_kernel_gt_same) : CN_KC(cn_env_kernel_gt));
-    if (sf) return same ? CN_KC(cn_env_kernel_sf_same) : CN_KC(cn_env_kernel_sf);
-    if (ct) return same ? CN_KC(cn_env_kernel_ct_same) : CN_KC(cn_env_kernel_ct);
-    if (same) return CN_KC(cn_env_kernel_same);
-    const bool fair = fair_launch(h, overlapped);
-    const int64_t resident = h->group_envs > h->cfg.n_envs ? h->group_envs : (int64_t)h->cfg.n_envs;
-    // small grids: two wavefronts per environment while all of them fit at two per SIMD (CN_X2=0 / 1 overrides for A/B runs)
-    if (h->shape360 && h->n_cus > 0 && (h->x2 == 1 || (h->x2 < 0 && resident <= 8 * (int64_t)h->n_cus)))
-        return KernelChoice{cn_env_kernel_s360_x2, "cn_env_kernel_s360_x2", false, 1, true};
-    if (h->shape360 && h->wpb4 && h->n_cus > 0 && resident <= 16 * (int64_t)h->n_cus) return fair ? KernelChoice{cn_env_kernel_fair_s360_w4, "cn_env_kernel_fair_s360_w4", false, h->wpb4} : KernelChoice{cn_env_kernel_s360_w4, "cn_env_kernel_s360_w4", false, h->wpb4};
-    if (h->shape360) return fair ? CN_KC(cn_env_kernel_fair_s360) : CN_KC(cn_env_kernel_s360);
-    if (h->shape720) return fair ? CN_KCC(cn_env_kernel_fair_s720) : CN_KCC(cn_env_kernel_s720);
-    return fair ? CN_KC(cn_env_kernel_fair) : CN_KC(cn_env_kernel);
-}
-// cn_step_sequence / cn_rollout_policy: every configuration cn_create accepts has both (round 6: the contact ticks and the two older
-// observation layouts included) -- the same selection order as choose_kernel
-static KernelChoice choose_sequence_kernel(const cn_env_s* h)
-{
-    const cn_config& c = h->cfg;
-    if (c.obs_layout == CN_LAYOUT_REALWORLD) return CN_KC(cn_env_kernel_seq_rw);
-    if (c.obs_layout == CN_LAYOUT_ORIGINAL) return CN_KC(cn_env_kernel_seq_orig);
-    if (h->wide) return CN_KC(cn_env_kernel_seq_wide);
-    const bool gt = c.risk_mode == CN_RISK_GT, ct = c.ped_contact != 0, sf = c.ped_mode == 2, wa = c.wheel_accel > 0.0;
-    const bool sfd = sf && !h->kp.sf_pair_matrix && c.n_peds <= 128;
-    if (wa) return gt ? CN_KC(cn_env_kernel_gt_seq_wa) : CN_KC(cn_env_kernel_seq_wa);          // (choose_kernel: the wheel ramp comes first)
-    if (sfd) return gt ? CN_KC(cn_env_kernel_gt_seq_sfd) : CN_KC(cn_env_kernel_seq_sfd);
-    if (sf) return gt ? CN_KC(cn_env_kernel_gt_seq_sf) : CN_KC(cn_env_kernel_seq_sf);
-    if (ct) return gt ? CN_KC(cn_env_kernel_gt_seq_ct) : CN_KC(cn_env_kernel_seq_ct);
-    return gt ? CN_KC(cn_env_kernel_gt_seq)
-         : h->shape360 ? CN_KC(cn_env_kernel_seq_s360) : h->shape720 ? CN_KCC(cn_env_kernel_seq_s720) : CN_KC(cn_env_kernel_seq);
-}
-static KernelChoice choose_policy_kernel(const cn_env_s* h)
-{
-    const cn_config& c = h->cfg;
-    if (c.obs_layout == CN_LAYOUT_REALWORLD) return CN_KC(cn_policy_kernel_rw);
-    if (c.obs_layout == CN_LAYOUT_ORIGINAL) return CN_KC(cn_policy_kernel_orig);
-    if (h->wide) return CN_KC(cn_policy_kernel_wide);
-    const bool gt = c.risk_mode == CN_RISK_GT, ct = c.ped_contact != 0, sf = c.ped_mode == 2, wa = c.wheel_accel > 0.0;
-    const bool sfd = sf && !h->kp.sf_pair_matrix && c.n_peds <= 128;
-    if (wa) return gt ? CN_KC(cn_policy_kernel_gt_wa) : CN_KC(cn_policy_kernel_wa);
-    if (sfd) return gt ? CN_KC(cn_policy_kernel_gt_sfd) : CN_KC(cn_policy_kernel_sfd);
-    if (sf) return gt ? CN_KC(cn_policy_kernel_gt_sf) : CN_KC(cn_policy_kernel_sf);
-    if (ct) return gt ? CN_KC(cn_policy_kernel_gt_ct) : CN_KC(cn_policy_kernel_ct);
-    return gt ? CN_KC(cn_policy_kernel_gt)
-         : h->shape360 ? CN_KC(cn_policy_kernel_s360) : h->shape720 ? CN_KCC(cn_policy_kernel_s720) : CN_KC(cn_policy_kernel);
-}
-
 extern "C" const char* cn_kernel_name(cn_handle h, int what)
 {
     if (!h || what < 0 || what > 5) { fail(CN_ERR_ARG, "cn_kernel_name: bad argument"); return nullptr; }
-    if (what == 5) { const char* n_ = choose_policy_kernel(h).name; if (!n_) fail(CN_ERR_CONFIG, "cn_kernel_name: cn_rollout_policy has no kernel for this configuration"); return n_; }
-    if (what == 2) { const char* n_ = choose_sequence_kernel(h).name; if (!n_) fail(CN_ERR_CONFIG, "cn_kernel_name: cn_step_sequence has no kernel for this configuration"); return n_; }
-    return choose_kernel(h, what == 3, what == 1, what == 4).name;
+    return kernel_of(h, what == 4 ? CN_FORM_STEP : what, what == 4).name;      // (every world has cn_step_sequence and cn_rollout_policy; gt has no external kernel: NULL)
 }
 
 // Both counters are per-XCD (two one-thread kernels can land on different dies: their readings do not subtract), so the interval
@@ -667,7 +527,7 @@ static int launch(cn_handle h, const CnKParams& kp, hipStream_t st, bool overlap
 {
     DeviceScope scope(h->device);
     const bool ext = kp.mode == CN_MODE_EXT_STEP || kp.mode == CN_MODE_EXT_RESET;
-    const KernelChoice kc = choose_kernel(h, ext, kp.mode == CN_MODE_STEP && kp.auto_reset == 1, overlapped);
+    const KernelChoice kc = kernel_of(h, ext ? CN_FORM_EXTERNAL : (kp.mode == CN_MODE_STEP && kp.auto_reset == 1) ? CN_FORM_SAME : CN_FORM_STEP, overlapped);
     if (!kc.fn)
         return fail(CN_ERR_CONFIG, "cn_observe_external: risk_mode gt reads the library simulator's pedestrians; "
                                    "external /scan + /odom only exist in lidar_tracker mode");
@@ -724,8 +584,8 @@ extern "C" int cn_set_group_envs(cn_handle h, int64_t total_envs)
 extern "C" int cn_get_arbitration(cn_handle h)
 {
     if (!h) return fail(CN_ERR_ARG, "cn_get_arbitration: null handle");
-    const bool has_variant = !h->wide && h->cfg.obs_layout == CN_LAYOUT_RISK && h->cfg.risk_mode != CN_RISK_GT && !h->cfg.ped_contact && h->cfg.ped_mode != 2 && !(h->cfg.wheel_accel > 0.0);
-    return has_variant && fair_launch(h, false) ? CN_ARB_FAIR : CN_ARB_OLDEST_FIRST;
+    const bool fair = cn_world_has_fair(h->world) && cn_fair_launch(launch_facts(h, false));
+    return fair ? CN_ARB_FAIR : CN_ARB_OLDEST_FIRST;
 }
 
 extern "C" int cn_step_multi(int n, const cn_handle* handles, const cn_step_io* ios, void* const* streams)
@@ -773,6 +633,19 @@ extern "C" int cn_policy_tail(const float* logits, float* action, int n, float m
     return CN_OK;
 }
 
+// An actor kernel whose tile exceeds 64 KiB: raise its dynamic-LDS limit to a CU's 160 KiB on the current device.  hipFuncSetAttribute
+// is per device: once per ordinal (attr_set: the kernel's own 64 flags), under a lock.
+static int allow_full_lds(const void* kernel, int dev, bool* attr_set)
+{
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    if (dev >= 64 || !attr_set[dev]) {
+        HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        if (dev < 64) attr_set[dev] = true;
+    }
+    return CN_OK;
+}
+
 extern "C" __global__ void cn_actor_kernel(const float* obs, int n, int D, int Dp, const float* W1T, const float* b1,
                                            const float* W2T, const float* b2, const float* W3, const float* b3, float* action,
                                            float max_v, float max_w, float sigma, uint64_t seed, uint64_t counter);
@@ -805,15 +678,7 @@ extern "C" int cn_actor_forward(const cn_actor_weights* w, const float* obs, flo
     int dev = device;
     if (dev < 0) HIPCHK(hipGetDevice(&dev));
     DeviceScope scope(dev);
-    if (lds > 64 * 1024) {   // hipFuncSetAttribute is per device: once per ordinal, under a lock
-        static std::mutex mu;
-        static bool attr_set[64] = {false};
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev >= 64 || !attr_set[dev]) {
-            HIPCHK(hipFuncSetAttribute((const void*)cn_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            if (dev < 64) attr_set[dev] = true;
-        }
-    }
+    if (lds > 64 * 1024) { static bool attr_set[64] = {false}; FIELD(allow_full_lds((const void*)cn_actor_kernel, dev, attr_set)); }
     hipLaunchKernelGGL(cn_actor_kernel, dim3((n + 15) / 16), dim3(512), lds, (hipStream_t)stream, obs, n, w->obs_dim, Dp,
                        w->w1p, w->b1, w->w2p, w->b2, w->w3, w->b3, action, max_v, max_w, sigma, seed, counter);
     HIPCHK(hipGetLastError());
@@ -888,15 +753,7 @@ extern "C" int cn_actor_pop_create(const cn_actor_pop_member* members, int n_mem
     HIPCHK(hipMemcpy(jobs, hj.data(), sizeof(CnActorPopJob) * P, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(pack, hp.data(), sizeof(CnActorPopPackJob) * P, hipMemcpyHostToDevice));
     h->jobs = jobs; h->pack = pack;
-    if (lds > 64 * 1024) {   // hipFuncSetAttribute is per device: once per ordinal, under a lock (as cn_actor_forward does for its kernel)
-        static std::mutex mu;
-        static bool attr_set[64] = {false};
-        std::lock_guard<std::mutex> lk(mu);
-        if (dev >= 64 || !attr_set[dev]) {
-            HIPCHK(hipFuncSetAttribute((const void*)cn_actor_pop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            if (dev < 64) attr_set[dev] = true;
-        }
-    }
+    if (lds > 64 * 1024) { static bool attr_set[64] = {false}; FIELD(allow_full_lds((const void*)cn_actor_pop_kernel, dev, attr_set)); }
     *out = h.release();
     return CN_OK;
 }
@@ -1057,20 +914,28 @@ extern "C" int cn_pop_record(cn_pop_record_handle h, float launch, void* stream)
     return CN_OK;
 }
 
-extern "C" int cn_step_sequence(cn_handle h, const cn_sequence_io* io, void* stream)
+// cn_step_sequence / cn_rollout_policy: the handle's argument block for n_steps next-step-reset periods into the caller's slots
+template <typename IO>      // cn_sequence_io, cn_policy_io: the same member names
+static CnKParams roll_params(cn_handle h, const IO* io)
 {
-    if (!h || !io || !io->action || !io->obs || !io->reward || !io->done) return fail(CN_ERR_ARG, "cn_step_sequence: null argument");
-    if (io->n_steps < 0 || io->action_stride < 0 || io->obs_stride < 0 || io->reward_stride < 0 || io->done_stride < 0 || io->topk_stride < 0)
-        return fail(CN_ERR_ARG, "cn_step_sequence: negative step count or stride");
-    if (io->n_steps == 0) return CN_OK;
     CnKParams kp = h->kp;
     kp.mode = CN_MODE_STEP; kp.auto_reset = 2;
     kp.action = io->action; kp.step_counter = nullptr; kp.final_obs = nullptr; kp.obs_f64 = nullptr;
     kp.obs = io->obs; kp.reward = io->reward; kp.done = io->done; kp.topk_idx = io->topk_idx;
     kp.roll_steps = io->n_steps; kp.roll_action_in_stride = io->action_stride; kp.roll_obs_stride = io->obs_stride;
     kp.roll_reward_stride = io->reward_stride; kp.roll_done_stride = io->done_stride; kp.roll_topk_stride = io->topk_stride;
+    return kp;
+}
+
+extern "C" int cn_step_sequence(cn_handle h, const cn_sequence_io* io, void* stream)
+{
+    if (!h || !io || !io->action || !io->obs || !io->reward || !io->done) return fail(CN_ERR_ARG, "cn_step_sequence: null argument");
+    if (io->n_steps < 0 || io->action_stride < 0 || io->obs_stride < 0 || io->reward_stride < 0 || io->done_stride < 0 || io->topk_stride < 0)
+        return fail(CN_ERR_ARG, "cn_step_sequence: negative step count or stride");
+    if (io->n_steps == 0) return CN_OK;
+    CnKParams kp = roll_params(h, io);
     DeviceScope scope(h->device);
-    const KernelChoice kc = choose_sequence_kernel(h);
+    const KernelChoice kc = kernel_of(h, CN_FORM_SEQUENCE);
     hipLaunchKernelGGL(kc.fn, dim3(h->cfg.n_envs), dim3(64), lds_of(h, kc), (hipStream_t)stream, kp);
     HIPCHK(hipGetLastError());
     return CN_OK;
@@ -1088,19 +953,14 @@ extern "C" int cn_rollout_policy(cn_handle h, const cn_actor_weights* w, const c
     if (io->n_steps < 0 || io->action_stride < 0 || io->obs_stride < 0 || io->reward_stride < 0 || io->done_stride < 0 || io->topk_stride < 0)
         return fail(CN_ERR_ARG, "cn_rollout_policy: negative step count or stride");
     if (io->n_steps == 0) return CN_OK;
-    CnKParams kp = h->kp;
-    kp.mode = CN_MODE_STEP; kp.auto_reset = 2;
-    kp.action = io->action; kp.step_counter = nullptr; kp.final_obs = nullptr; kp.obs_f64 = nullptr;
-    kp.obs = io->obs; kp.reward = io->reward; kp.done = io->done; kp.topk_idx = io->topk_idx;
-    kp.roll_steps = io->n_steps; kp.roll_action_in_stride = io->action_stride; kp.roll_obs_stride = io->obs_stride;
-    kp.roll_reward_stride = io->reward_stride; kp.roll_done_stride = io->done_stride; kp.roll_topk_stride = io->topk_stride;
+    CnKParams kp = roll_params(h, io);
     kp.pol_w1p = w->w1p; kp.pol_b1 = w->b1; kp.pol_w2p = w->w2p; kp.pol_b2 = w->b2; kp.pol_w3 = w->w3; kp.pol_b3 = w->b3;
     kp.pol_obs0 = io->obs0; kp.pol_seed = io->seed; kp.pol_counter = io->counter;
     kp.pol_max_v = io->max_v; kp.pol_max_w = io->max_w; kp.pol_sigma = io->sigma;
     kp.pol_D = D; kp.pol_Dp = w->obs_dim_padded; kp.pol_wave_lds = (int32_t)h->pol_wave_lds;
     kp.pol_envs = h->pol_envs; kp.pol_act_off = (int32_t)h->pol_act_off;
     DeviceScope scope(h->device);
-    cn_kernel_fn fn = choose_policy_kernel(h).fn;
+    cn_kernel_fn fn = kernel_of(h, CN_FORM_POLICY).fn;
     hipLaunchKernelGGL(fn, dim3((h->cfg.n_envs + h->pol_envs - 1) / h->pol_envs), dim3(64 * h->pol_envs), h->pol_lds, (hipStream_t)stream, kp);
     HIPCHK(hipGetLastError());
     return CN_OK;

@@ -14,6 +14,7 @@
 // simulator here is defined in DESIGN.md and restated independently by the CPU oracle (test infrastructure).
 #include "crowdnav_device.h"
 #include "crowdnav_kernel.h"
+#include "crowdnav_variants.h"
 
 // One wavefront per workgroup: the LDS processes a wave's DS instructions in issue order, so a
 // cross-lane hand-off through LDS needs no s_barrier and no vmcnt/lgkmcnt drain -- only the compiler
@@ -3240,6 +3241,11 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
     }
     CN_T(19);
 }
+// env_kernel_body's instantiation by name: a world's five template facts (the columns of crowdnav_variants.h) and the form as flags
+enum : unsigned { CN_F_EXT = 1, CN_F_SAME = 2, CN_F_FUSED = 4, CN_F_FAIR = 8, CN_F_X2 = 16 };
+#define CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, FORM) \
+    env_kernel_body<((FORM) & CN_F_EXT) != 0, ((FORM) & CN_F_SAME) != 0, LAYOUT, GT, SIM, ((FORM) & CN_F_FUSED) != 0, ((FORM) & CN_F_FAIR) != 0, SHAPE, ((FORM) & CN_F_X2) != 0, WIDE>
+
 
 // The product kernel (simulated sensors) and its sibling for externally supplied /scan + /odom.  Two
 // instantiations keep the external-data branch out of the hot kernel's registers.
@@ -3254,42 +3260,47 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
 // allocator may use the 168 VGPRs that occupancy allows instead of squeezing into 128 (cn_env_kernel_s720: 66 -> SGPR spills below)
 #define CN_S720_BOUNDS __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 #endif
-// Two translation units (csrc/build.sh): CN_TU 1 = every kernel except the sequence kernels, CN_TU 2 = the sequence kernels alone,
-// compiled with -mllvm -disable-machine-licm.  Their step loop wraps the whole step body; MachineLICM hoists every constant and
-// address the body materialises out of that loop and the register allocator then spills them (cn_env_kernel_seq: 155 SGPR + 6
-// VGPR spills, 28 bytes of scratch; without the pass 6 / 0 / 0 and 3 % faster).  Unset = one unit with everything.
+// The kernels are the rows of CN_WORLDS (crowdnav_variants.h): each family below -- step, sequence, policy -- is one macro that
+// expands a row to its definitions, and the row names the compile unit of each (csrc/build.sh: -DCN_TU=1 ... 5; 6 = the population's
+// actor kernels; unset = one unit with everything).  CN_IN_TU_n(x) is x in unit n and nothing elsewhere.  Unit 1 holds every one-step
+// kernel; units 2-5 the sequence and policy kernels, compiled with -mllvm -disable-machine-licm: their step loop wraps the whole
+// step body; MachineLICM hoists every constant and address the body materialises out of that loop and the register allocator then
+// spills them (cn_env_kernel_seq: 155 SGPR + 6 VGPR spills, 28 bytes of scratch; without the pass 6 / 0 / 0 and 3 % faster).
 #if !defined(CN_TU) || CN_TU == 1
-extern "C" __global__ void CN_HOT_BOUNDS cn_env_kernel(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void CN_HOT_BOUNDS cn_env_kernel_fair(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, true>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void CN_HOT_BOUNDS cn_env_kernel_s360(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, false, 360>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void CN_HOT_BOUNDS cn_env_kernel_fair_s360(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, true, 360>(blockIdx.x, threadIdx.x, cn_smem); }
-// FOUR environments per workgroup (256 threads; one wavefront is still one environment and the four never synchronise): a quarter of
-// the workgroups for the dispatcher to create per launch -- the grid's start-up ramp is part of every step of a one-launch-per-step chain
-#ifdef CN_TIMING
-#define CN_HOT4_BOUNDS __launch_bounds__(1024)
+#define CN_IN_TU_1(...) __VA_ARGS__
 #else
-#define CN_HOT4_BOUNDS __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))
+#define CN_IN_TU_1(...)
 #endif
-extern "C" __global__ void CN_HOT4_BOUNDS cn_env_kernel_s360_w4(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; const int w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); env_kernel_body<false, false, 0, false, 0, false, false, 360>(blockIdx.x * (blockDim.x >> 6) + w_, threadIdx.x & 63, cn_smem + (size_t)w_ * ((KP)__builtin_amdgcn_kernarg_segment_ptr())->wave_lds); }
-extern "C" __global__ void CN_HOT4_BOUNDS cn_env_kernel_fair_s360_w4(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; const int w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); env_kernel_body<false, false, 0, false, 0, false, true, 360>(blockIdx.x * (blockDim.x >> 6) + w_, threadIdx.x & 63, cn_smem + (size_t)w_ * ((KP)__builtin_amdgcn_kernarg_segment_ptr())->wave_lds); }
-// TWO wavefronts per environment (128 threads): small grids -- up to two wavefronts per SIMD would be resident anyway (cn_create: n_envs
-// <= 8 x CUs, BASELINE configs[3]'s 2048-env shard, the N = 1 `Env`) -- where a step is as long as ONE wavefront's dependent chain
-#ifdef CN_TIMING
-#define CN_X2_BOUNDS __launch_bounds__(128)
+#if !defined(CN_TU) || CN_TU == 2
+#define CN_IN_TU_2(...) __VA_ARGS__
 #else
-#define CN_X2_BOUNDS __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4)))
+#define CN_IN_TU_2(...)
 #endif
-extern "C" __global__ void CN_X2_BOUNDS cn_env_kernel_s360_x2(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, false, 360, true>(blockIdx.x, threadIdx.x & 63, cn_smem, 0, nullptr, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); }
-extern "C" __global__ void CN_S720_BOUNDS cn_env_kernel_s720(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, false, 720>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void CN_S720_BOUNDS cn_env_kernel_fair_s720(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, true, 720>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_ext(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<true, false, 0>(blockIdx.x, threadIdx.x, cn_smem); }
-// the wide tracker table (cn_config.track_capacity 128 ... 1024, in HBM): the generic bodies above with WIDE -- both auto-reset
-// conventions and the external-sensor flow
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_wide(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 0, false, false, 0, false, true>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_wide_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, false, 0, false, false, 0, false, true>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_wide_ext(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<true, false, 0, false, 0, false, false, 0, false, true>(blockIdx.x, threadIdx.x, cn_smem); }
+#if !defined(CN_TU) || CN_TU == 3
+#define CN_IN_TU_3(...) __VA_ARGS__
+#else
+#define CN_IN_TU_3(...)
 #endif
+#if !defined(CN_TU) || CN_TU == 4
+#define CN_IN_TU_4(...) __VA_ARGS__
+#else
+#define CN_IN_TU_4(...)
+#endif
+#if !defined(CN_TU) || CN_TU == 5
+#define CN_IN_TU_5(...) __VA_ARGS__
+#else
+#define CN_IN_TU_5(...)
+#endif
+// The step family: a world's kernel for simulated sensors (one observation per launch), and where the row owns them its siblings for
+// Env.step + same-call reset and for externally supplied /scan + /odom.  Separate instantiations keep every branch a world does not
+// take out of its kernels' registers.  One wavefront per workgroup; the last argument is the body's instantiation.
+#define CN_STEP_KERNEL(BOUNDS, NAME, ...) \
+    extern "C" __global__ void BOUNDS NAME(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; __VA_ARGS__(blockIdx.x, threadIdx.x, cn_smem); }
+#define CN_DEF_STEP(ID, LAYOUT, GT, SIM, WIDE, SHAPE, BOUNDS, COMPACT, STEP, SAME_HAS, SAME, EXT_HAS, EXT, SEQ, SEQ_TU, POL, POL_TU, POL_BOUND) \
+    CN_IN_TU_1(CN_STEP_KERNEL(BOUNDS, STEP, CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, 0)) \
+               CN_HAS_##SAME_HAS(CN_STEP_KERNEL(__launch_bounds__(64), SAME, CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, CN_F_SAME))) \
+               CN_HAS_##EXT_HAS(CN_STEP_KERNEL(__launch_bounds__(64), EXT, CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, CN_F_EXT))))
+CN_WORLDS(CN_DEF_STEP)
 #if !defined(CN_TU) || CN_TU == 2 || CN_TU == 3 || CN_TU == 5
 // cn_step_sequence: T control periods per launch with OPEN-LOOP actions (resident in HBM: [T][N][2], or one [N][2] held for T
 // periods).  One wavefront keeps its environment for the whole launch and walks its T steps at its own pace: no launch boundary,
@@ -3309,67 +3320,42 @@ __device__ __forceinline__ void sequence_body()
         asm volatile("" : "+v"(lane_));          // per-step laundering (see env_kernel_body): nothing is hoisted out of the step loop
         lane_ &= 63;
         cn_setprio_uniform((int)(t + wslot) & 3);      // see "issue arbitration" at the top: every slot gets every level in turn
-        env_kernel_body<false, false, LAYOUT, GT, SIM, true, false, SHAPE, false, WIDE>(blockIdx.x, lane_, cn_smem, t);
+        CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, CN_F_FUSED)(blockIdx.x, lane_, cn_smem, t);
     }
 }
 #endif
-#if !defined(CN_TU) || CN_TU == 2
-extern "C" __global__ void CN_HOT_BOUNDS cn_env_kernel_seq(CnKParams p) { sequence_body<false>(); }
-extern "C" __global__ void CN_HOT_BOUNDS cn_env_kernel_seq_s360(CnKParams p) { sequence_body<false, 360>(); }
-extern "C" __global__ void CN_S720_BOUNDS cn_env_kernel_seq_s720(CnKParams p) { sequence_body<false, 720>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_seq(CnKParams p) { sequence_body<true>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_seq_wide(CnKParams p) { sequence_body<false, 0, 0, 0, true>(); }   // the wide tracker table
-#endif
-#if !defined(CN_TU) || CN_TU == 3
-// round 5: the same persistent-wavefront form for the other simulators (SIM 2 / 4: social-force pedestrians, pair matrix / dense;
-// SIM 3: the diff-drive plugin's wheel ramp) -- the worlds one trains in "as Gazebo delivers it" -- in both risk modes
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_seq_sf(CnKParams p) { sequence_body<false, 0, 2>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_seq_sfd(CnKParams p) { sequence_body<false, 0, 4>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_seq_wa(CnKParams p) { sequence_body<false, 0, 3>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_seq_sf(CnKParams p) { sequence_body<true, 0, 2>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_seq_sfd(CnKParams p) { sequence_body<true, 0, 4>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_seq_wa(CnKParams p) { sequence_body<true, 0, 3>(); }
-#endif
-#if !defined(CN_TU) || CN_TU == 5
-// round 6: ... and for the worlds that were still refused -- the contact ticks (SIM 1, both risk modes) and the two older observation
-// layouts (ORIG: 363 inputs, RW: 370 inputs).  Every configuration cn_create accepts now has both one-launch forms.
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_seq_ct(CnKParams p) { sequence_body<false, 0, 1>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_seq_ct(CnKParams p) { sequence_body<true, 0, 1>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_seq_orig(CnKParams p) { sequence_body<false, 0, 0, 1>(); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_seq_rw(CnKParams p) { sequence_body<false, 0, 0, 2>(); }
-#endif
+// every world has the persistent-wavefront form (social force with the pair matrix / dense, the wheel ramp, the contact ticks -- each in
+// both risk modes -- the wide tracker table and the two older observation layouts: ORIG 363 inputs, RW 370)
+#define CN_DEF_SEQ(ID, LAYOUT, GT, SIM, WIDE, SHAPE, BOUNDS, COMPACT, STEP, SAME_HAS, SAME, EXT_HAS, EXT, SEQ, SEQ_TU, POL, POL_TU, POL_BOUND) \
+    CN_IN_TU_##SEQ_TU(extern "C" __global__ void BOUNDS SEQ(CnKParams p) { sequence_body<GT, SHAPE, SIM, LAYOUT, WIDE>(); })
+CN_WORLDS(CN_DEF_SEQ)
 #if !defined(CN_TU) || CN_TU == 1
-// risk_mode gt: the perceived-risk features from the simulator's own pedestrians (no segmentation, no tracker)
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, true>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, true>(blockIdx.x, threadIdx.x, cn_smem); }
-// ped_contact = 1: the simulator with rigid contacts (10 ms physics ticks); separate instantiations keep the default kernels lean
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_ct(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 1>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_ct_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, false, 1>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_ct(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, true, 1>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_ct_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, true, 1>(blockIdx.x, threadIdx.x, cn_smem); }
-// ped_mode = 2: social-force pedestrians (10 ms physics ticks), for both risk modes
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_sf(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 2>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_sf_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, false, 2>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_sf(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, true, 2>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_sf_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, true, 2>(blockIdx.x, threadIdx.x, cn_smem); }
-// ped_mode = 2 with a crowd too large for the pair matrix (up to 128 pedestrians): per-lane near masks (sim_advance_sf<true>)
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_sfd(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 4>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_sfd_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, false, 4>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_sfd(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, true, 4>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_sfd_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, true, 4>(blockIdx.x, threadIdx.x, cn_smem); }
-// wheel_accel > 0: the diff-drive plugin's wheel-speed ramp (10 ms plugin ticks for the robot), for both risk modes
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_wa(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, false, 3>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_wa_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, false, 3>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_wa(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 0, true, 3>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_gt_wa_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 0, true, 3>(blockIdx.x, threadIdx.x, cn_smem); }
-// obs_layout 2 (environment_stage_1_nobonus_realworld.py): the 370-input physical-robot variant
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_rw(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 2>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_rw_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 2>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_rw_ext(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<true, false, 2>(blockIdx.x, threadIdx.x, cn_smem); }
-// obs_layout 1 (environment_stage_1_original.py): same physics and lidar, no tracker
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_orig(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, false, 1>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_orig_same(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<false, true, 1>(blockIdx.x, threadIdx.x, cn_smem); }
-extern "C" __global__ void __launch_bounds__(64) cn_env_kernel_orig_ext(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; env_kernel_body<true, false, 1>(blockIdx.x, threadIdx.x, cn_smem); }
+// The kernels of CN_HEADLINE_KERNELS (crowdnav_variants.h), written out: what only the three plain tracker worlds have.  Their
+// fair-arbitration forms (the same bounds as the row's step kernel) ...
+CN_STEP_KERNEL(CN_HOT_BOUNDS, cn_env_kernel_fair, CN_STEP_BODY(0, false, 0, false, 0, CN_F_FAIR))
+CN_STEP_KERNEL(CN_HOT_BOUNDS, cn_env_kernel_fair_s360, CN_STEP_BODY(0, false, 0, false, 360, CN_F_FAIR))
+CN_STEP_KERNEL(CN_S720_BOUNDS, cn_env_kernel_fair_s720, CN_STEP_BODY(0, false, 0, false, 720, CN_F_FAIR))
+// ... and the headline shape's launch geometries.
+// FOUR environments per workgroup (256 threads; one wavefront is still one environment and the four never synchronise): a quarter of
+// the workgroups for the dispatcher to create per launch -- the grid's start-up ramp is part of every step of a one-launch-per-step chain
+#ifdef CN_TIMING
+#define CN_HOT4_BOUNDS __launch_bounds__(1024)
+#else
+#define CN_HOT4_BOUNDS __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))
+#endif
+#define CN_W4_KERNEL(NAME, FORM) \
+    extern "C" __global__ void CN_HOT4_BOUNDS NAME(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; const int w_ = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); \
+        CN_STEP_BODY(0, false, 0, false, 360, FORM)(blockIdx.x * (blockDim.x >> 6) + w_, threadIdx.x & 63, cn_smem + (size_t)w_ * ((KP)__builtin_amdgcn_kernarg_segment_ptr())->wave_lds); }
+CN_W4_KERNEL(cn_env_kernel_s360_w4, 0)
+CN_W4_KERNEL(cn_env_kernel_fair_s360_w4, CN_F_FAIR)
+// TWO wavefronts per environment (128 threads): small grids -- up to two wavefronts per SIMD would be resident anyway (cn_create: n_envs
+// <= 8 x CUs, BASELINE configs[3]'s 2048-env shard, the N = 1 `Env`) -- where a step is as long as ONE wavefront's dependent chain
+#ifdef CN_TIMING
+#define CN_X2_BOUNDS __launch_bounds__(128)
+#else
+#define CN_X2_BOUNDS __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4)))
+#endif
+extern "C" __global__ void CN_X2_BOUNDS cn_env_kernel_s360_x2(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; CN_STEP_BODY(0, false, 0, false, 360, CN_F_X2)(blockIdx.x, threadIdx.x & 63, cn_smem, 0, nullptr, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); }
 
 // cn_create: bbox_size() at the spawn pose, evaluated once by the same device code the step kernel would run
 extern "C" __global__ void __launch_bounds__(64) cn_bbox_kernel(CnKParams pv, double* out)
@@ -3786,7 +3772,7 @@ __device__ __forceinline__ void policy_sequence_body()
 #if POL_FAIR == 0
             cn_setprio_uniform((t + (int)__builtin_amdgcn_s_getreg(4 | (1 << 11))) & 3);
 #endif
-            env_kernel_body<false, false, LAYOUT, GT, SIM, true, POL_FAIR != 0 && LAYOUT == 0, SHAPE, false, WIDE>(env, lane_, cn_smem + (size_t)wave * ws, t, act_lds + 2 * wave);
+            CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, CN_F_FUSED | (POL_FAIR != 0 && LAYOUT == 0 ? CN_F_FAIR : 0))(env, lane_, cn_smem + (size_t)wave * ws, t, act_lds + 2 * wave);
         }
         POL_T(3);
         __syncthreads();
@@ -3794,30 +3780,11 @@ __device__ __forceinline__ void policy_sequence_body()
     }
 }
 #endif
-#if !defined(CN_TU) || CN_TU == 2
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel(CnKParams p) { policy_sequence_body<0>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_s360(CnKParams p) { policy_sequence_body<360>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_gt(CnKParams p) { policy_sequence_body<0, true>(); }   // risk_mode gt
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_wide(CnKParams p) { policy_sequence_body<0, false, 0, 0, true>(); }   // the wide tracker table
-#endif
-#if !defined(CN_TU) || CN_TU == 4
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_s720(CnKParams p) { policy_sequence_body<720>(); }      // BASELINE configs[4]: 8 per workgroup
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_sf(CnKParams p) { policy_sequence_body<0, false, 2>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_sfd(CnKParams p) { policy_sequence_body<0, false, 4>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_wa(CnKParams p) { policy_sequence_body<0, false, 3>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_gt_sf(CnKParams p) { policy_sequence_body<0, true, 2>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_gt_sfd(CnKParams p) { policy_sequence_body<0, true, 4>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_gt_wa(CnKParams p) { policy_sequence_body<0, true, 3>(); }
-#endif
-#if !defined(CN_TU) || CN_TU == 5
-// round 6: the contact ticks and the two older observation layouts (their actors take 363 / 370 inputs: cn_actor_pack_weights pads
-// any width to a multiple of 32)
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_ct(CnKParams p) { policy_sequence_body<0, false, 1>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_gt_ct(CnKParams p) { policy_sequence_body<0, true, 1>(); }
-extern "C" __global__ void __launch_bounds__(64 * POL_ENVS) cn_policy_kernel_orig(CnKParams p) { policy_sequence_body<0, false, 0, 1>(); }
-// (the RW observation needs 140 vector registers: 8 environments per workgroup -- two waves per SIMD -- so that the cap is 256, not 128)
-extern "C" __global__ void __launch_bounds__(64 * 8) cn_policy_kernel_rw(CnKParams p) { policy_sequence_body<0, false, 0, 2>(); }
-#endif
+// (cn_policy_kernel_rw's bound is 8 waves, two per SIMD: the RW observation needs 140 vector registers and the cap is then 256, not 128;
+//  the 363 / 370 inputs of the older layouts' actors: cn_actor_pack_weights pads any width to a multiple of 32)
+#define CN_DEF_POLICY(ID, LAYOUT, GT, SIM, WIDE, SHAPE, BOUNDS, COMPACT, STEP, SAME_HAS, SAME, EXT_HAS, EXT, SEQ, SEQ_TU, POL, POL_TU, POL_BOUND) \
+    CN_IN_TU_##POL_TU(extern "C" __global__ void __launch_bounds__(POL_BOUND) POL(CnKParams p) { policy_sequence_body<SHAPE, GT, SIM, LAYOUT, WIDE>(); })
+CN_WORLDS(CN_DEF_POLICY)
 
 #if !defined(CN_TU) || CN_TU == 1
 

@@ -58,7 +58,7 @@ def draw(rng):
     if rng.random() < HEADLINE_FRAC:
         # the two BENCHMARKED shapes, whose kernels are compiled for exactly these sizes (cn_env_kernel[_fair]_s360[_w4|_x2], _seq_s360,
         # cn_policy_kernel_s360 and the _s720 family): everything that keeps a world on them stays random, and the grid sizes walk
-        # through the selection rules of choose_kernel (two wavefronts per env up to 2048 envs, 4 envs per workgroup up to 4096, ...)
+        # through the selection rules of cn_select_kernel (two wavefronts per env up to 2048 envs, 4 envs per workgroup up to 4096, ...)
         dense = rng.random() < 0.3
         kw.update(n_peds=100 if dense else 20, n_rays=720 if dense else 360, k_obstacles=8, obs_layout=0, risk_mode=0, ped_mode=0, ped_contact=0,
                   wheel_accel=0.0, sf_tick_ms=0, track_capacity=0, room_half=float(rng.uniform(2.0, 3.2)) if dense else float(rng.uniform(1.0, 3.0)),
