@@ -1,52 +1,69 @@
 #!/bin/bash
 # Builds libcrowdnav.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
-#   build.sh            the product library
-#   build.sh timing     ONLY the profiling sibling libcrowdnav_timing.so (stage time stamps, PMC calibration kernels,
-#                       device-math test kernels; never loaded by the product)
-#   build.sh all        both
+#   build.sh                the product library
+#   build.sh timing         ONLY the profiling sibling libcrowdnav_timing.so (stage time stamps, and crowdnav_debug.hip: PMC calibration
+#                           kernels, device-math test kernels; never loaded by the product)
+#   build.sh all            both
+#   build.sh objects DIR    only compile the product's units into DIR/<object>.o (tools/profc/build.sh links them with its own unit 1:
+#                           CN_SKIP_UNIT=k1 leaves that one out)
 #   -ffp-contract=off : no implicit FMA contraction; every fma() in the sources is explicit, which is
 #                       what makes the simulator bit-reproducible against the CPU oracle
-# crowdnav_kernel.hip is compiled as six units (-DCN_TU=n).  Which kernel is defined in which unit is a column of the kernel table,
-# crowdnav_variants.h: unit 1 holds every one-step kernel, units 2-5 the sequence and policy kernels (their rows name the unit) --
-# compiled with -mllvm -disable-machine-licm: see the note above the kernel definitions -- and unit 6 the population's actor
-# kernels (cn_actor_pop_*: apart, so that unit 1's kernels keep their instruction streams).  The units only spread the compile
-# over processes and flags; the file also compiles as one unit with CN_TU unset.
-# crowdnav_pop_record.hip holds the population recorder's two kernels (cn_pop_record); their bodies, crowdnav_record.h, are the ones
-# crowdnav_td3.hip's cn_replay_write / cn_episode_log_add kernels are made of.
+# One file per subsystem, and UNITS below is the only list of them: the compile loop and the link line both come from it.
+# crowdnav_kernel.hip (the environment's step, sequence and policy kernels) is compiled as five units (-DCN_TU=n).  Which kernel is
+# defined in which unit is a column of the kernel table, crowdnav_variants.h: unit 1 holds every one-step kernel, units 2-5 the sequence
+# and policy kernels (their rows name the unit), compiled with -mllvm -disable-machine-licm: see the note above the kernel definitions.
+# The units only spread the compile over processes and flags.  crowdnav_abi.hip is the environment's host side; the other files each
+# hold a subsystem's kernels next to the host code that launches them: the TD3 actor and the population's actors, the fused learners,
+# the tabular learners, the population's recorder (its bodies, crowdnav_record.h, are shared with crowdnav_td3.hip's replay kernels).
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="$HERE/../lib"
-mkdir -p "$OUT"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-builtin-pow -Wall -Wno-unused-function"
 WHAT="${1:-product}"
+UNITS=(         # object, source, flags of its own
+  "k1    crowdnav_kernel.hip      -DCN_TU=1"
+  "k2    crowdnav_kernel.hip      -DCN_TU=2 -mllvm -disable-machine-licm"
+  "k3    crowdnav_kernel.hip      -DCN_TU=3 -mllvm -disable-machine-licm"
+  "k4    crowdnav_kernel.hip      -DCN_TU=4 -mllvm -disable-machine-licm"
+  "k5    crowdnav_kernel.hip      -DCN_TU=5 -mllvm -disable-machine-licm"
+  "abi   crowdnav_abi.hip"
+  "actor crowdnav_actor.hip"
+  "td3   crowdnav_td3.hip"
+  "tab   crowdnav_tab.hip"
+  "rec   crowdnav_pop_record.hip"
+)
+TIMING_UNITS=("debug crowdnav_debug.hip")      # build.sh timing adds these
+compile_units() {   # $1 = directory for the objects, $2.. = extra flags: every unit of LIST, in parallel; OBJS = the objects, in LIST's order
+  local dir="$1" pids=() failed=0 pid unit obj src own; shift
+  OBJS=()
+  for unit in "${LIST[@]}"; do
+    read -r obj src own <<< "$unit"
+    [ "$obj" = "${CN_SKIP_UNIT:-}" ] && continue
+    "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" $own -c -o "$dir/$obj.o" "$HERE/$src" & pids+=($!)
+    OBJS+=("$dir/$obj.o")
+  done
+  for pid in "${pids[@]}"; do wait "$pid" || failed=1; done     # a bare `wait` returns 0 whatever the jobs returned
+  if [ "$failed" != 0 ]; then echo "build.sh: a compile failed" >&2; return 1; fi
+}
 build_lib() {   # $1 = output name, $2.. = extra flags
   local name="$1"; shift
   local T; T="$(mktemp -d)"
   trap 'rm -rf "$T"' RETURN
-  local pids=()
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -DCN_TU=1 -c -o "$T/k1.o" "$HERE/crowdnav_kernel.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -DCN_TU=2 -mllvm -disable-machine-licm -c -o "$T/k2.o" "$HERE/crowdnav_kernel.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -DCN_TU=3 -mllvm -disable-machine-licm -c -o "$T/k3.o" "$HERE/crowdnav_kernel.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -DCN_TU=4 -mllvm -disable-machine-licm -c -o "$T/k4.o" "$HERE/crowdnav_kernel.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -DCN_TU=5 -mllvm -disable-machine-licm -c -o "$T/k5.o" "$HERE/crowdnav_kernel.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -DCN_TU=6 -c -o "$T/k6.o" "$HERE/crowdnav_kernel.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/abi.o" "$HERE/crowdnav_abi.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/td3.o" "$HERE/crowdnav_td3.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/tab.o" "$HERE/crowdnav_tab.hip" & pids+=($!)
-  "$HIPCC" $FLAGS ${CN_EXTRA_FLAGS:-} "$@" -c -o "$T/rec.o" "$HERE/crowdnav_pop_record.hip" & pids+=($!)
-  local failed=0 pid
-  for pid in "${pids[@]}"; do wait "$pid" || failed=1; done     # a bare `wait` returns 0 whatever the jobs returned
-  if [ "$failed" != 0 ]; then echo "build.sh: a compile of $name failed" >&2; return 1; fi
+  mkdir -p "$OUT"
+  compile_units "$T" "$@"
   # link next to the target and rename: a process that already mapped the old file keeps it, nobody maps a partial one
-  "$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/.$name.$$" "$T/k1.o" "$T/k2.o" "$T/k3.o" "$T/k4.o" "$T/k5.o" "$T/k6.o" "$T/abi.o" "$T/td3.o" "$T/tab.o" "$T/rec.o"
+  "$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/.$name.$$" "${OBJS[@]}"
   mv -f "$OUT/.$name.$$" "$OUT/$name"
 }
+LIST=("${UNITS[@]}")
+if [ "$WHAT" = "objects" ]; then compile_units "$2"; fi
 if [ "$WHAT" = "product" ] || [ "$WHAT" = "all" ]; then
   build_lib libcrowdnav.so
   echo "built $OUT/libcrowdnav.so"
 fi
 if [ "$WHAT" = "timing" ] || [ "$WHAT" = "all" ]; then
+  LIST+=("${TIMING_UNITS[@]}")
   build_lib libcrowdnav_timing.so -DCN_TIMING
   echo "built $OUT/libcrowdnav_timing.so (stage time stamps; profiling only)"
 fi

@@ -6,15 +6,13 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <algorithm>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "crowdnav_device.h"
+#include "crowdnav_host.h"
 #include "crowdnav_kernel.h"
-#include "crowdnav_record.h"
 #include "crowdnav_variants.h"
 
 // every kernel that takes CnKParams, from the table (crowdnav_variants.h): declarations, then the functions in cn_kernel_info's order --
@@ -33,43 +31,7 @@ extern "C" __global__ void cn_bbox_kernel(CnKParams p, double* out);
 extern "C" __global__ void cn_gather_kernel(CnKParams p, float* last_ret, float* run_ret, int32_t* counters);
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string& msg) { g_err = msg; return code; }
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) \
-    return fail(CN_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
-struct cn_env_s {
-    cn_config cfg;
-    int device;
-    int D, max_conf, trk_cap;
-    bool wide = false;                // trk_cap > CN_MAX_TRACKS: the tracker table stays in HBM (the _wide kernels)
-    int world = 0;                    // CN_W_*: this configuration's row of CN_WORLDS (crowdnav_variants.h)
-    size_t lds;
-    CnKParams kp;        // template with state/table pointers filled in
-    double *d_lidar = nullptr, *d_poly = nullptr, *d_ped_init = nullptr, *d_ped_preset = nullptr, *d_trk = nullptr;
-    double* d_ped_aux = nullptr;      // [N, P, 3] ped_mode 2: goal x, goal y, goal counter
-    char* d_state = nullptr;          // N per-env records (crowdnav_kernel.h: sd | si | ped_p | ped_v | pad), `stride` bytes apart
-    size_t stride;
-    std::vector<double> ped_init;
-    int arbitration = CN_ARB_AUTO;    // cn_set_arbitration
-    int n_cus = 0;                    // compute units of `device` (CN_ARB_AUTO: fair from 2 wavefronts per SIMD = 8 x n_cus envs)
-    size_t lds_shape = 0;             // dynamic LDS of the _s720 kernels (compact layout); 0 = this handle has none
-    size_t pol_wave_lds = 0, pol_lds = 0;   // cn_rollout_policy: bytes between the environments' LDS working sets of a workgroup; the workgroup's total (0 = does not fit)
-    int pol_envs = 0;                 // ... environments per workgroup: 16, or 8 where 16 working sets do not fit one CU's LDS
-    size_t pol_act_off = 0;           // ... byte offset of the workgroup's actions (past the working sets and the actor tile)
-    int64_t group_envs = 0;           // cn_set_group_envs: environments in flight together with this handle's (0 = alone)
-    int x2 = -1;                      // cn_env_kernel_s360_x2 (two wavefronts per environment): -1 = by grid size, 0 / 1 = CN_X2 override
-    int wpb4 = 0;                     // 4: the 360-ray step kernels run four environments per workgroup (launches of at most one round of wavefronts); 0: one
-    bool shape360 = false;            // the headline shape (360 rays, 20 pedestrians, K = 8 and cn_create's sizes for it): the _s360 kernels
-    bool shape720 = false;            // BASELINE configs[4] (720 rays, 100 pedestrians, K = 8): the _s720 kernels
-};
-
-// RAII: run on the handle's device even if the calling thread's current device is another one
-struct DeviceScope {
-    int prev = -1, want;
-    explicit DeviceScope(int dev) : want(dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != want) (void)hipSetDevice(want); }
-    ~DeviceScope() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
-};
+int fail(int code, const std::string& msg) { g_err = msg; return code; }
 
 static void destroy_handle(cn_env_s* h)
 {
@@ -194,13 +156,13 @@ static double angle_increment_deg(int R)
 static int field_to_device(cn_env_s* h, size_t off, const void* host, size_t width)
 {
     if (!width) return CN_OK;
-    HIPCHK(hipMemcpy2D(h->d_state + off, h->stride, host, width, width, (size_t)h->cfg.n_envs, hipMemcpyHostToDevice));
+    CN_HIPCHK(fail, hipMemcpy2D(h->d_state + off, h->stride, host, width, width, (size_t)h->cfg.n_envs, hipMemcpyHostToDevice));
     return CN_OK;
 }
 static int field_to_host(cn_env_s* h, size_t off, void* host, size_t width)
 {
     if (!width) return CN_OK;
-    HIPCHK(hipMemcpy2D(host, width, h->d_state + off, h->stride, width, (size_t)h->cfg.n_envs, hipMemcpyDeviceToHost));
+    CN_HIPCHK(fail, hipMemcpy2D(host, width, h->d_state + off, h->stride, width, (size_t)h->cfg.n_envs, hipMemcpyDeviceToHost));
     return CN_OK;
 }
 #define FIELD(call) do { int rc_ = (call); if (rc_ != CN_OK) return rc_; } while (0)
@@ -219,15 +181,15 @@ static int upload_initial_state(cn_env_s* h)
             s[CN_SD_CPROB] = -INFINITY; s[CN_SD_BB] = 0.0210;
         }
     }
-    HIPCHK(hipMemset(h->d_state, 0, (size_t)N * h->stride));
+    CN_HIPCHK(fail, hipMemset(h->d_state, 0, (size_t)N * h->stride));
     FIELD(field_to_device(h, CN_ST_OFF_SD, sd.data(), CN_SD_COUNT * 8));
     FIELD(field_to_device(h, CN_ST_OFF_SI, si.data(), CN_SI_COUNT * 4));
     if (P > 0) {
-        HIPCHK(hipMemcpy(h->d_ped_init, h->ped_init.data(), (size_t)N * P * 16, hipMemcpyHostToDevice));
+        CN_HIPCHK(fail, hipMemcpy(h->d_ped_init, h->ped_init.data(), (size_t)N * P * 16, hipMemcpyHostToDevice));
         FIELD(field_to_device(h, CN_ST_OFF_PED_P, h->ped_init.data(), (size_t)P * 16));
-        HIPCHK(hipMemset(h->d_ped_preset, 0, (size_t)N * P * 16));
+        CN_HIPCHK(fail, hipMemset(h->d_ped_preset, 0, (size_t)N * P * 16));
     }
-    HIPCHK(hipMemset(h->d_trk, 0, (size_t)N * CN_TF_COUNT * h->trk_cap * 8));
+    CN_HIPCHK(fail, hipMemset(h->d_trk, 0, (size_t)N * CN_TF_COUNT * h->trk_cap * 8));
     {   // ped_mode 2: every pedestrian's first goal (goal 0 of its counter-based sequence); zeros otherwise
         std::vector<double> aux((size_t)N * (P > 0 ? P : 1) * 3, 0.0);
         if (c.ped_mode == 2) {
@@ -239,7 +201,7 @@ static int upload_initial_state(cn_env_s* h)
                     a[1] = fma(span, cn_rng_u01(c.seed, c.env_index_base + e, 3u, (uint32_t)i, 1u), lo);
                 }
         }
-        HIPCHK(hipMemcpy(h->d_ped_aux, aux.data(), aux.size() * 8, hipMemcpyHostToDevice));
+        CN_HIPCHK(fail, hipMemcpy(h->d_ped_aux, aux.data(), aux.size() * 8, hipMemcpyHostToDevice));
     }
     return CN_OK;
 }
@@ -335,18 +297,18 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
         lidar[4 * (size_t)R + 2 * q] = lidar[kq]; lidar[4 * (size_t)R + 2 * q + 1] = lidar[R + kq];
     }
     for (int k = 0; k < 64; ++k) { double a = -(double)k * M_PI / 32.0; poly[k] = cos(a); poly[64 + k] = sin(a); }
-    HIPCHK(hipMalloc(&h->d_lidar, lidar.size() * 8));
-    HIPCHK(hipMalloc(&h->d_poly, poly.size() * 8 + 512));      // + the association table (256 shorts, below)
-    HIPCHK(hipMemcpy(h->d_lidar, lidar.data(), lidar.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_poly, poly.data(), poly.size() * 8, hipMemcpyHostToDevice));
+    CN_HIPCHK(fail, hipMalloc(&h->d_lidar, lidar.size() * 8));
+    CN_HIPCHK(fail, hipMalloc(&h->d_poly, poly.size() * 8 + 512));      // + the association table (256 shorts, below)
+    CN_HIPCHK(fail, hipMemcpy(h->d_lidar, lidar.data(), lidar.size() * 8, hipMemcpyHostToDevice));
+    CN_HIPCHK(fail, hipMemcpy(h->d_poly, poly.data(), poly.size() * 8, hipMemcpyHostToDevice));
     size_t pb = (size_t)N * (P > 0 ? P : 1) * 16;
     h->stride = CN_ST_STRIDE(P);
-    HIPCHK(hipMalloc(&h->d_state, (size_t)N * h->stride));
-    HIPCHK(hipMalloc(&h->d_ped_init, pb));
-    HIPCHK(hipMalloc(&h->d_ped_preset, pb));
+    CN_HIPCHK(fail, hipMalloc(&h->d_state, (size_t)N * h->stride));
+    CN_HIPCHK(fail, hipMalloc(&h->d_ped_init, pb));
+    CN_HIPCHK(fail, hipMalloc(&h->d_ped_preset, pb));
     // (a wide handle: + [N][trk_cap] doubles behind the tables, the entries' collision probabilities -- scratch inside one call)
-    HIPCHK(hipMalloc(&h->d_trk, (size_t)N * (CN_TF_COUNT + (h->wide ? 1 : 0)) * h->trk_cap * 8));
-    HIPCHK(hipMalloc(&h->d_ped_aux, (size_t)N * (P > 0 ? P : 1) * 24));
+    CN_HIPCHK(fail, hipMalloc(&h->d_trk, (size_t)N * (CN_TF_COUNT + (h->wide ? 1 : 0)) * h->trk_cap * 8));
+    CN_HIPCHK(fail, hipMalloc(&h->d_ped_aux, (size_t)N * (P > 0 ? P : 1) * 24));
     h->ped_init.resize((size_t)N * P * 2);
     for (int e = 0; e < N; ++e) default_ped_init(c, e, &h->ped_init[(size_t)e * P * 2]);
     int rc = upload_initial_state(h);
@@ -411,27 +373,27 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
     k.ped_preset = h->d_ped_preset; k.trk = h->d_trk; k.ped_aux = h->d_ped_aux;
     {   // the reset path's bounding-box size at the spawn pose (a constant of the configuration), from the device's own arithmetic
         double* d_out = nullptr;
-        HIPCHK(hipMalloc(&d_out, sizeof(double)));
+        CN_HIPCHK(fail, hipMalloc(&d_out, sizeof(double)));
         hipLaunchKernelGGL(cn_bbox_kernel, dim3(1), dim3(64), 0, (hipStream_t)0, k, d_out);
         hipError_t e1 = hipGetLastError(), e2 = hipMemcpy(&k.bb_spawn, d_out, sizeof(double), hipMemcpyDeviceToHost);
         (void)hipFree(d_out);
-        HIPCHK(e1); HIPCHK(e2);
+        CN_HIPCHK(fail, e1); CN_HIPCHK(fail, e2);
         k.bb_spawn_valid = 1;
         int16_t tab[256] = {0};
         build_assoc_table(k, tab);
         k.assoc_tab = (const int16_t*)(h->d_poly + 128);
-        HIPCHK(hipMemcpy((void*)k.assoc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
+        CN_HIPCHK(fail, hipMemcpy((void*)k.assoc_tab, tab, sizeof(tab), hipMemcpyHostToDevice));
     }
     if (h->shape360 && h->wpb4) {     // the _w4 kernels are only ever launched for the headline shape (cn_select_kernel)
         const size_t w4 = (size_t)h->wpb4 * ((h->lds + 15) & ~(size_t)15);      // what launch() asks for
         if (w4 > 160 * 1024) h->wpb4 = 0;                                        // (a CN_WPB override that does not fit a CU's LDS: one per workgroup)
         else if (w4 > 64 * 1024) {
             for (int id : {CN_K_cn_env_kernel_s360_w4, CN_K_cn_env_kernel_fair_s360_w4})
-                HIPCHK(hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)w4));
+                CN_HIPCHK(fail, hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)w4));
         }
     }
     if (h->lds > 64 * 1024)
-        for (int id = 0; id < CN_K_N_DYNAMIC; ++id) HIPCHK(hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
+        for (int id = 0; id < CN_K_N_DYNAMIC; ++id) CN_HIPCHK(fail, hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
     {   // cn_rollout_policy: 16 (or 8) environments per workgroup, their working sets 16-byte aligned one after the other (the
         // actor's 16-row tile is laid out compactly over them between two steps), + the workgroup's actions
         // (this world's policy kernel: the 720-ray shape's has the compact layout)
@@ -446,7 +408,7 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
             if (tot <= 160 * 1024) { h->pol_lds = tot; h->pol_envs = pe; h->pol_act_off = off; }
         }
         if (h->pol_lds > 64 * 1024)
-            for (int id = CN_K_N_DYNAMIC; id < CN_K_COUNT; ++id) HIPCHK(hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->pol_lds));
+            for (int id = CN_K_N_DYNAMIC; id < CN_K_COUNT; ++id) CN_HIPCHK(fail, hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->pol_lds));
     }
     *out = guard.release();
     return CN_OK;
@@ -476,8 +438,8 @@ extern "C" int cn_set_ped_init(cn_handle h, const double* xy)
     DeviceScope scope(h->device);
     size_t cnt = (size_t)h->cfg.n_envs * h->cfg.n_peds * 2;
     h->ped_init.assign(xy, xy + cnt);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(h->d_ped_init, xy, cnt * 8, hipMemcpyHostToDevice));
+    CN_HIPCHK(fail, hipDeviceSynchronize());
+    CN_HIPCHK(fail, hipMemcpy(h->d_ped_init, xy, cnt * 8, hipMemcpyHostToDevice));
     FIELD(field_to_device(h, CN_ST_OFF_PED_P, xy, (size_t)h->cfg.n_peds * 16));
     return CN_OK;
 }
@@ -493,8 +455,8 @@ extern "C" int cn_set_ped_preset_vel(cn_handle h, const double* vxy)
 {
     if (!h || !vxy) return fail(CN_ERR_ARG, "cn_set_ped_preset_vel: null argument");
     DeviceScope scope(h->device);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(h->d_ped_preset, vxy, (size_t)h->cfg.n_envs * h->cfg.n_peds * 16, hipMemcpyHostToDevice));
+    CN_HIPCHK(fail, hipDeviceSynchronize());
+    CN_HIPCHK(fail, hipMemcpy(h->d_ped_preset, vxy, (size_t)h->cfg.n_envs * h->cfg.n_peds * 16, hipMemcpyHostToDevice));
     return CN_OK;
 }
 
@@ -519,7 +481,7 @@ extern "C" int cn_device_clock(int64_t* out_dev, int span_us, int device, void* 
     if (!out_dev || span_us < 1 || span_us > 1000000) return fail(CN_ERR_ARG, "cn_device_clock: null argument or span outside 1 us .. 1 s");
     DeviceScope scope(device);
     hipLaunchKernelGGL(cn_clock_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (long long*)out_dev, (long long)span_us * 100);
-    HIPCHK(hipGetLastError());
+    CN_HIPCHK(fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -541,7 +503,7 @@ static int launch(cn_handle h, const CnKParams& kp, hipStream_t st, bool overlap
         hipLaunchKernelGGL(kc.fn, dim3((kp.N + kc.wpb - 1) / kc.wpb), dim3(64 * kc.wpb), (size_t)k4.wave_lds * kc.wpb, st, k4);
     } else
     hipLaunchKernelGGL(kc.fn, dim3(kp.N), dim3(64), lds_of(h, kc), st, kp);
-    HIPCHK(hipGetLastError());
+    CN_HIPCHK(fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -616,304 +578,6 @@ extern "C" int cn_observe_external(cn_handle h, const cn_external_io* io, void* 
     return launch(h, kp, (hipStream_t)stream);
 }
 
-extern "C" __global__ void cn_policy_tail_kernel(const float* logits, float* action, int n, float max_v, float max_w,
-                                                 float sigma, uint64_t seed, uint64_t counter);
-
-extern "C" int cn_policy_tail(const float* logits, float* action, int n, float max_v, float max_w, float sigma,
-                              uint64_t seed, uint64_t counter, int device, void* stream)
-{
-    if (!logits || !action || n < 0) return fail(CN_ERR_ARG, "cn_policy_tail: bad argument");
-    if (n == 0) return CN_OK;
-    int dev = device;
-    if (dev < 0) HIPCHK(hipGetDevice(&dev));
-    DeviceScope scope(dev);
-    hipLaunchKernelGGL(cn_policy_tail_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, logits, action, n,
-                       max_v, max_w, sigma, seed, counter);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-// An actor kernel whose tile exceeds 64 KiB: raise its dynamic-LDS limit to a CU's 160 KiB on the current device.  hipFuncSetAttribute
-// is per device: once per ordinal (attr_set: the kernel's own 64 flags), under a lock.
-static int allow_full_lds(const void* kernel, int dev, bool* attr_set)
-{
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (dev >= 64 || !attr_set[dev]) {
-        HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (dev < 64) attr_set[dev] = true;
-    }
-    return CN_OK;
-}
-
-extern "C" __global__ void cn_actor_kernel(const float* obs, int n, int D, int Dp, const float* W1T, const float* b1,
-                                           const float* W2T, const float* b2, const float* W3, const float* b3, float* action,
-                                           float max_v, float max_w, float sigma, uint64_t seed, uint64_t counter);
-
-extern "C" __global__ void cn_actor_pack_kernel(const float* wt, int K, float* packed);
-extern "C" int cn_actor_pack_weights(const float* wt, int k_rows, float* packed, int device, void* stream)
-{
-    if (!wt || !packed || wt == packed) return fail(CN_ERR_ARG, "cn_actor_pack_weights: null or aliasing argument");
-    if (k_rows < 32 || (k_rows & 31)) return fail(CN_ERR_CONFIG, "cn_actor_pack_weights: k_rows must be a positive multiple of 32");
-    int dev = device;
-    if (dev < 0) HIPCHK(hipGetDevice(&dev));
-    DeviceScope scope(dev);
-    const int total = k_rows * 256;
-    hipLaunchKernelGGL(cn_actor_pack_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, wt, k_rows, packed);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-extern "C" int cn_actor_forward(const cn_actor_weights* w, const float* obs, float* action, int n, float max_v, float max_w,
-                                float sigma, uint64_t seed, uint64_t counter, int device, void* stream)
-{
-    if (!w || !obs || !action || n < 0 || !w->w1p || !w->b1 || !w->w2p || !w->b2 || !w->w3 || !w->b3)
-        return fail(CN_ERR_ARG, "cn_actor_forward: null argument");
-    if (w->hidden != 256 || w->obs_dim < 1 || w->obs_dim_padded < w->obs_dim || (w->obs_dim_padded & 31))
-        return fail(CN_ERR_CONFIG, "cn_actor_forward: hidden must be 256 and obs_dim_padded a multiple of 32 (the packed layout of cn_actor_pack_weights)");
-    if (n == 0) return CN_OK;
-    const int Dp = w->obs_dim_padded;
-    const size_t lds = sizeof(float) * (16 * (size_t)(Dp + 1) + 16 * 257);         // X (layer 2 reuses it), H
-    if (lds > 160 * 1024) return fail(CN_ERR_CONFIG, "cn_actor_forward: observation too wide for one LDS tile");
-    int dev = device;
-    if (dev < 0) HIPCHK(hipGetDevice(&dev));
-    DeviceScope scope(dev);
-    if (lds > 64 * 1024) { static bool attr_set[64] = {false}; FIELD(allow_full_lds((const void*)cn_actor_kernel, dev, attr_set)); }
-    hipLaunchKernelGGL(cn_actor_kernel, dim3((n + 15) / 16), dim3(512), lds, (hipStream_t)stream, obs, n, w->obs_dim, Dp,
-                       w->w1p, w->b1, w->w2p, w->b2, w->w3, w->b3, action, max_v, max_w, sigma, seed, counter);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-// ---- a population's actors: one forward launch and one pack launch for all members (kernels: crowdnav_kernel.hip, unit 6) ----------
-extern "C" __global__ void cn_actor_pop_kernel(const CnActorPopJob* table, int D, int Dp, int add_noise, CnActorPopCounters ctr);
-extern "C" __global__ void cn_actor_pop_pack_kernel(const CnActorPopPackJob* table, int D, int Dp);
-
-struct cn_actor_pop_s {
-    int device = 0, P = 0, D = 0, Dp = 0, tiles = 0;      // tiles: the widest member's, the grid's x (0: nothing to launch)
-    size_t lds = 0;
-    void* mem = nullptr;                                   // one allocation: the two tables, then every member's w1p and w2p
-    const CnActorPopJob* jobs = nullptr;
-    const CnActorPopPackJob* pack = nullptr;
-    std::vector<cn_actor_weights> weights;
-    cn_actor_pop_s() = default;
-    cn_actor_pop_s(const cn_actor_pop_s&) = delete;
-    ~cn_actor_pop_s() { if (mem) { DeviceScope scope(device); (void)hipFree(mem); } }
-};
-
-extern "C" int cn_actor_pop_create(const cn_actor_pop_member* members, int n_members, int obs_dim, int device, cn_actor_pop_handle* out)
-{
-    const std::string f("cn_actor_pop_create");
-    if (!members) return fail(CN_ERR_ARG, f + ": members is null");
-    if (!out) return fail(CN_ERR_ARG, f + ": out is null");
-    if (n_members < 1 || n_members > CN_ACTOR_POP_MAX) return fail(CN_ERR_ARG, f + ": n_members must be 1 ... 64");
-    if (obs_dim < 1) return fail(CN_ERR_CONFIG, f + ": obs_dim must be at least 1");
-    const int64_t Dp64 = ((int64_t)obs_dim + 31) / 32 * 32;
-    const size_t lds = sizeof(float) * (16 * ((size_t)Dp64 + 1) + 16 * 257);       // cn_actor_forward's tile: X (layer 2 reuses it), H
-    const int P = n_members, D = obs_dim, Dp = (int)Dp64;
-    if (lds > 160 * 1024) return fail(CN_ERR_CONFIG, f + ": obs_dim: observation too wide for one LDS tile");
-    int tiles = 0;
-    for (int p = 0; p < P; ++p) {
-        const cn_actor_pop_member& m = members[p];
-        const std::string who = ": member " + std::to_string(p) + ": ";
-        const float* const ps[6] = {m.actor.w1, m.actor.b1, m.actor.w2, m.actor.b2, m.actor.w3, m.actor.b3};
-        static const char* const pn[6] = {"actor.w1", "actor.b1", "actor.w2", "actor.b2", "actor.w3", "actor.b3"};
-        for (int i = 0; i < 6; ++i)
-            if (!ps[i]) return fail(CN_ERR_ARG, f + who + pn[i] + " is null");
-        if (m.n < 0) return fail(CN_ERR_ARG, f + who + "n is negative");
-        if (m.n > 0 && !m.obs) return fail(CN_ERR_ARG, f + who + "obs is null");
-        if (m.n > 0 && !m.action) return fail(CN_ERR_ARG, f + who + "action is null");
-        tiles = std::max(tiles, (int)(((int64_t)m.n + 15) / 16));
-    }
-    std::unique_ptr<cn_actor_pop_s> h(new (std::nothrow) cn_actor_pop_s());
-    if (!h) return fail(CN_ERR_ARG, f + ": out of memory");
-    int dev = device;
-    if (dev < 0) HIPCHK(hipGetDevice(&dev));
-    h->device = dev; h->P = P; h->D = D; h->Dp = Dp; h->tiles = tiles; h->lds = lds;
-    DeviceScope scope(dev);
-    // [jobs P][pack jobs P] rounded up to 256 bytes, then per member w1p [Dp][256] and w2p [256][256] (16-byte loads: both sizes are
-    // multiples of 1 KB)
-    const size_t n1 = (size_t)Dp * 256, n2 = (size_t)256 * 256;
-    const size_t tab = (sizeof(CnActorPopJob) * P + sizeof(CnActorPopPackJob) * P + 255) & ~(size_t)255;
-    HIPCHK(hipMalloc(&h->mem, tab + sizeof(float) * (n1 + n2) * P));
-    CnActorPopJob* jobs = (CnActorPopJob*)h->mem;
-    CnActorPopPackJob* pack = (CnActorPopPackJob*)(jobs + P);
-    float* wbuf = (float*)((char*)h->mem + tab);
-    std::vector<CnActorPopJob> hj(P);
-    std::vector<CnActorPopPackJob> hp(P);
-    h->weights.resize(P);
-    for (int p = 0; p < P; ++p) {
-        const cn_actor_pop_member& m = members[p];
-        float* w1p = wbuf + (size_t)p * (n1 + n2);
-        float* w2p = w1p + n1;
-        hj[p] = CnActorPopJob{m.obs, w1p, m.actor.b1, w2p, m.actor.b2, m.actor.w3, m.actor.b3, m.action, m.n, m.max_v, m.max_w, m.sigma, m.seed};
-        hp[p] = CnActorPopPackJob{m.actor.w1, m.actor.w2, w1p, w2p};
-        h->weights[p] = cn_actor_weights{w1p, m.actor.b1, w2p, m.actor.b2, m.actor.w3, m.actor.b3, D, Dp, 256, 0};
-    }
-    HIPCHK(hipMemcpy(jobs, hj.data(), sizeof(CnActorPopJob) * P, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pack, hp.data(), sizeof(CnActorPopPackJob) * P, hipMemcpyHostToDevice));
-    h->jobs = jobs; h->pack = pack;
-    if (lds > 64 * 1024) { static bool attr_set[64] = {false}; FIELD(allow_full_lds((const void*)cn_actor_pop_kernel, dev, attr_set)); }
-    *out = h.release();
-    return CN_OK;
-}
-extern "C" void cn_actor_pop_destroy(cn_actor_pop_handle h) { delete h; }
-extern "C" int cn_actor_pop_members(cn_actor_pop_handle h) { return h ? h->P : 0; }
-
-extern "C" int cn_actor_pop_pack(cn_actor_pop_handle h, void* stream)
-{
-    if (!h) return fail(CN_ERR_ARG, "cn_actor_pop_pack: null handle");
-    DeviceScope scope(h->device);
-    // x covers the larger layer: Dp blocks of 256 elements for layer 1, 256 for layer 2
-    hipLaunchKernelGGL(cn_actor_pop_pack_kernel, dim3(std::max(h->Dp, 256), 2, h->P), dim3(256), 0, (hipStream_t)stream, h->pack, h->D, h->Dp);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-extern "C" int cn_actor_pop_forward(cn_actor_pop_handle h, const uint64_t* counters, int add_noise, void* stream)
-{
-    if (!h) return fail(CN_ERR_ARG, "cn_actor_pop_forward: null handle");
-    if (!counters) return fail(CN_ERR_ARG, "cn_actor_pop_forward: counters is null");
-    if (h->tiles == 0) return CN_OK;
-    CnActorPopCounters ctr;
-    memset(&ctr, 0, sizeof(ctr));
-    memcpy(ctr.c, counters, sizeof(uint64_t) * h->P);
-    DeviceScope scope(h->device);
-    hipLaunchKernelGGL(cn_actor_pop_kernel, dim3(h->tiles, 1, h->P), dim3(512), h->lds, (hipStream_t)stream, h->jobs, h->D, h->Dp,
-                       add_noise ? 1 : 0, ctr);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
-extern "C" int cn_actor_pop_weights(cn_actor_pop_handle h, int member, cn_actor_weights* out)
-{
-    if (!h) return fail(CN_ERR_ARG, "cn_actor_pop_weights: null handle");
-    if (!out) return fail(CN_ERR_ARG, "cn_actor_pop_weights: out is null");
-    if (member < 0 || member >= h->P) return fail(CN_ERR_ARG, "cn_actor_pop_weights: member " + std::to_string(member) + " out of range (the handle has " + std::to_string(h->P) + ")");
-    *out = h->weights[member];
-    return CN_OK;
-}
-
-// ---- a population's recorder: every member's replay write and episode log in two launches (kernels: crowdnav_pop_record.hip) -------
-extern "C" __global__ void cn_pop_record_scan_kernel(const CnPopRecordJob* table, float launch);
-extern "C" __global__ void cn_pop_record_copy_kernel(const CnPopRecordJob* table);
-
-struct cn_pop_record_s {
-    int device = 0, P = 0, max_n = 0;                      // max_n: the widest member's rows, launch B's grid x (0: nothing to launch)
-    void* mem = nullptr;                                   // one allocation: the table, then every member's slot scratch and resetting bytes
-    const CnPopRecordJob* jobs = nullptr;
-    std::vector<uint8_t*> resetting;
-    cn_pop_record_s() = default;
-    cn_pop_record_s(const cn_pop_record_s&) = delete;
-    ~cn_pop_record_s() { if (mem) { DeviceScope scope(device); (void)hipFree(mem); } }
-};
-
-extern "C" int cn_pop_record_create(const cn_pop_record_member* members, int n_members, int obs_dim, int device, cn_pop_record_handle* out)
-{
-    const std::string f("cn_pop_record_create");
-    if (!members) return fail(CN_ERR_ARG, f + ": members is null");
-    if (!out) return fail(CN_ERR_ARG, f + ": out is null");
-    if (n_members < 1 || n_members > CN_POP_RECORD_MAX) return fail(CN_ERR_ARG, f + ": n_members must be 1 ... 64");
-    if (obs_dim < 1) return fail(CN_ERR_CONFIG, f + ": obs_dim must be at least 1");
-    const int P = n_members;
-    struct Named { const void* ptr; const char* name; int member; };
-    std::vector<Named> written;                            // what a launch writes, per member: no two members may share any of it
-    int max_n = 0;
-    for (int p = 0; p < P; ++p) {
-        const cn_pop_record_member& m = members[p];
-        const std::string who = ": member " + std::to_string(p) + ": ";
-        if (m.n < 0) return fail(CN_ERR_ARG, f + who + "n is negative");
-        if (m.n > 0) {
-            if (!m.env && !(m.counters && m.last_return))
-                return fail(CN_ERR_ARG, f + who + "neither env nor both counters and last_return are given");
-            if (m.env && m.n != m.env->cfg.n_envs)
-                return fail(CN_ERR_ARG, f + who + "n is " + std::to_string(m.n) + " but env has n_envs " + std::to_string(m.env->cfg.n_envs));
-            const void* const rp[5] = {m.prev, m.obs, m.action, m.reward, m.done};
-            static const char* const rn[5] = {"prev", "obs", "action", "reward", "done"};
-            for (int i = 0; i < 5; ++i)
-                if (!rp[i]) return fail(CN_ERR_ARG, f + who + rn[i] + " is null");
-        }
-        const cn_replay_ring& r = m.ring;
-        if (!r.s || !r.a || !r.r || !r.s2 || !r.d || !r.pos_dev || !r.size_dev || r.capacity < 1 || r.obs_dim < 1)
-            return fail(CN_ERR_ARG, f + who + "incomplete ring");
-        if (!m.log.rows || !m.log.n_dev || !m.log.tot_dev) return fail(CN_ERR_ARG, f + who + "incomplete log");
-        if (m.log.max_rows < 0) return fail(CN_ERR_ARG, f + who + "log.max_rows is negative");
-        if ((int64_t)m.n > r.capacity)
-            return fail(CN_ERR_ARG, f + who + "n exceeds ring.capacity (two rows of one call would share a slot)");
-        if (r.obs_dim != obs_dim)
-            return fail(CN_ERR_CONFIG, f + who + "ring.obs_dim is " + std::to_string(r.obs_dim) + ", obs_dim " + std::to_string(obs_dim));
-        const Named mine[11] = {{r.s, "ring.s", p}, {r.a, "ring.a", p}, {r.r, "ring.r", p}, {r.s2, "ring.s2", p}, {r.d, "ring.d", p},
-                                {r.pos_dev, "ring.pos_dev", p}, {r.size_dev, "ring.size_dev", p}, {m.log.rows, "log.rows", p},
-                                {m.log.n_dev, "log.n_dev", p}, {m.log.tot_dev, "log.tot_dev", p}, {m.prev, "prev", p}};
-        for (const Named& x : mine) {
-            if (!x.ptr) continue;                          // (prev of a member without rows)
-            for (const Named& y : written)
-                if (y.ptr == x.ptr)
-                    return fail(CN_ERR_CONFIG, f + who + x.name + " is also member " + std::to_string(y.member) + "'s " + y.name +
-                                               " (they would race inside a launch)");
-        }
-        written.insert(written.end(), mine, mine + 11);
-        max_n = std::max(max_n, (int)m.n);
-    }
-    std::unique_ptr<cn_pop_record_s> h(new (std::nothrow) cn_pop_record_s());
-    if (!h) return fail(CN_ERR_ARG, f + ": out of memory");
-    int dev = device;
-    if (dev < 0) HIPCHK(hipGetDevice(&dev));
-    h->device = dev; h->P = P; h->max_n = max_n;
-    DeviceScope scope(dev);
-    // [jobs P] rounded up to 256 bytes, then per member slot [n] int32 and resetting [n] bytes, each rounded up to 16 bytes.  The whole
-    // image is made on the host and uploaded by one blocking copy: the flags are zero whatever stream the first call runs on.
-    const size_t tab = (sizeof(CnPopRecordJob) * P + 255) & ~(size_t)255;
-    size_t total = tab;
-    std::vector<size_t> off_slot(P), off_flag(P);
-    for (int p = 0; p < P; ++p) {
-        off_slot[p] = total; total += (sizeof(int32_t) * (size_t)members[p].n + 15) & ~(size_t)15;
-        off_flag[p] = total; total += ((size_t)members[p].n + 15) & ~(size_t)15;
-    }
-    HIPCHK(hipMalloc(&h->mem, total));
-    std::vector<char> image(total, 0);
-    CnPopRecordJob* hj = (CnPopRecordJob*)image.data();
-    h->resetting.resize(P);
-    for (int p = 0; p < P; ++p) {
-        const cn_pop_record_member& m = members[p];
-        CnPopRecordJob& j = hj[p];
-        j.ring = m.ring; j.log = m.log;
-        j.state = m.env ? m.env->d_state : nullptr; j.state_stride = m.env ? (int64_t)m.env->stride : 0;
-        j.counters = m.counters; j.last_return = m.last_return;
-        j.prev = m.prev; j.obs = m.obs; j.action = m.action; j.reward = m.reward; j.done = m.done;
-        j.resetting = h->resetting[p] = (uint8_t*)h->mem + off_flag[p];
-        j.slot = (int32_t*)((char*)h->mem + off_slot[p]);
-        j.n = m.n; j.reserved = 0;
-    }
-    HIPCHK(hipMemcpy(h->mem, image.data(), total, hipMemcpyHostToDevice));
-    h->jobs = (const CnPopRecordJob*)h->mem;
-    *out = h.release();
-    return CN_OK;
-}
-extern "C" void cn_pop_record_destroy(cn_pop_record_handle h) { delete h; }
-extern "C" int cn_pop_record_members(cn_pop_record_handle h) { return h ? h->P : 0; }
-
-extern "C" uint8_t* cn_pop_record_resetting(cn_pop_record_handle h, int member)
-{
-    if (!h) { (void)fail(CN_ERR_ARG, "cn_pop_record_resetting: null handle"); return nullptr; }
-    if (member < 0 || member >= h->P) {
-        (void)fail(CN_ERR_ARG, "cn_pop_record_resetting: member " + std::to_string(member) + " out of range (the handle has " + std::to_string(h->P) + ")");
-        return nullptr;
-    }
-    return h->resetting[member];
-}
-
-extern "C" int cn_pop_record(cn_pop_record_handle h, float launch, void* stream)
-{
-    if (!h) return fail(CN_ERR_ARG, "cn_pop_record: null handle");
-    if (h->max_n == 0) return CN_OK;
-    DeviceScope scope(h->device);
-    hipLaunchKernelGGL(cn_pop_record_scan_kernel, dim3(1, 1, h->P), dim3(1024), 0, (hipStream_t)stream, h->jobs, launch);
-    hipLaunchKernelGGL(cn_pop_record_copy_kernel, dim3(h->max_n, 1, h->P), dim3(256), 0, (hipStream_t)stream, h->jobs);
-    HIPCHK(hipGetLastError());
-    return CN_OK;
-}
-
 // cn_step_sequence / cn_rollout_policy: the handle's argument block for n_steps next-step-reset periods into the caller's slots
 template <typename IO>      // cn_sequence_io, cn_policy_io: the same member names
 static CnKParams roll_params(cn_handle h, const IO* io)
@@ -937,7 +601,7 @@ extern "C" int cn_step_sequence(cn_handle h, const cn_sequence_io* io, void* str
     DeviceScope scope(h->device);
     const KernelChoice kc = kernel_of(h, CN_FORM_SEQUENCE);
     hipLaunchKernelGGL(kc.fn, dim3(h->cfg.n_envs), dim3(64), lds_of(h, kc), (hipStream_t)stream, kp);
-    HIPCHK(hipGetLastError());
+    CN_HIPCHK(fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -962,7 +626,7 @@ extern "C" int cn_rollout_policy(cn_handle h, const cn_actor_weights* w, const c
     DeviceScope scope(h->device);
     cn_kernel_fn fn = kernel_of(h, CN_FORM_POLICY).fn;
     hipLaunchKernelGGL(fn, dim3((h->cfg.n_envs + h->pol_envs - 1) / h->pol_envs), dim3(64 * h->pol_envs), h->pol_lds, (hipStream_t)stream, kp);
-    HIPCHK(hipGetLastError());
+    CN_HIPCHK(fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -973,7 +637,7 @@ extern "C" int cn_get_counters(cn_handle h, int32_t* out, void* stream)
     DeviceScope scope(h->device);
     hipLaunchKernelGGL(cn_gather_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->kp,
                        (float*)nullptr, (float*)nullptr, out);
-    HIPCHK(hipGetLastError());
+    CN_HIPCHK(fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -984,7 +648,7 @@ extern "C" int cn_get_returns(cn_handle h, float* last_return, float* running_re
     DeviceScope scope(h->device);
     hipLaunchKernelGGL(cn_gather_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, h->kp, last_return,
                        running_return, (int32_t*)nullptr);
-    HIPCHK(hipGetLastError());
+    CN_HIPCHK(fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -992,22 +656,22 @@ extern "C" int cn_debug_env(cn_handle h, int env, double* scalars, double* robot
 {
     if (!h || env < 0 || env >= h->cfg.n_envs) return fail(CN_ERR_ARG, "cn_debug_env: bad argument");
     DeviceScope scope(h->device);
-    HIPCHK(hipDeviceSynchronize());
+    CN_HIPCHK(fail, hipDeviceSynchronize());
     const int P = h->cfg.n_peds;
     std::vector<double> sd(CN_SD_COUNT);
     const char* rec = h->d_state + (size_t)env * h->stride;
-    HIPCHK(hipMemcpy(sd.data(), rec + CN_ST_OFF_SD, CN_SD_COUNT * 8, hipMemcpyDeviceToHost));
+    CN_HIPCHK(fail, hipMemcpy(sd.data(), rec + CN_ST_OFF_SD, CN_SD_COUNT * 8, hipMemcpyDeviceToHost));
     if (scalars) memcpy(scalars, sd.data(), CN_SD_COUNT * 8);
     if (robot_ped) {
         memcpy(robot_ped, sd.data(), 5 * 8);
         if (P > 0) {
-            HIPCHK(hipMemcpy(robot_ped + 5, rec + CN_ST_OFF_PED_P, (size_t)P * 32, hipMemcpyDeviceToHost));   // ped_p | ped_v
+            CN_HIPCHK(fail, hipMemcpy(robot_ped + 5, rec + CN_ST_OFF_PED_P, (size_t)P * 32, hipMemcpyDeviceToHost));   // ped_p | ped_v
         }
     }
     if (tracks)
-        HIPCHK(hipMemcpy(tracks, h->d_trk + (size_t)env * CN_TF_COUNT * h->trk_cap, CN_TF_COUNT * h->trk_cap * 8,
+        CN_HIPCHK(fail, hipMemcpy(tracks, h->d_trk + (size_t)env * CN_TF_COUNT * h->trk_cap, CN_TF_COUNT * h->trk_cap * 8,
                          hipMemcpyDeviceToHost));
-    if (ints) HIPCHK(hipMemcpy(ints, rec + CN_ST_OFF_SI, CN_SI_COUNT * 4, hipMemcpyDeviceToHost));
+    if (ints) CN_HIPCHK(fail, hipMemcpy(ints, rec + CN_ST_OFF_SI, CN_SI_COUNT * 4, hipMemcpyDeviceToHost));
     return CN_OK;
 }
 
@@ -1037,7 +701,7 @@ extern "C" int cn_snapshot(cn_handle h, void* buf, size_t size)
     if (!h || !buf) return fail(CN_ERR_ARG, "cn_snapshot: null argument");
     if (size < cn_snapshot_size(h)) return fail(CN_ERR_SIZE, "cn_snapshot: buffer too small");
     DeviceScope scope(h->device);
-    HIPCHK(hipDeviceSynchronize());
+    CN_HIPCHK(fail, hipDeviceSynchronize());
     size_t N = h->cfg.n_envs, P = h->cfg.n_peds;
     char* q = (char*)buf;
     cn_snapshot_header hd;
@@ -1049,11 +713,11 @@ extern "C" int cn_snapshot(cn_handle h, void* buf, size_t size)
         FIELD(field_to_host(h, CN_ST_OFF_PED_P, q, P * 16)); q += N * P * 16;
         FIELD(field_to_host(h, CN_ST_OFF_PED_V(P), q, P * 16)); q += N * P * 16;
     }
-    HIPCHK(hipMemcpy(q, h->d_trk, N * CN_TF_COUNT * h->trk_cap * 8, hipMemcpyDeviceToHost)); q += N * CN_TF_COUNT * h->trk_cap * 8;
+    CN_HIPCHK(fail, hipMemcpy(q, h->d_trk, N * CN_TF_COUNT * h->trk_cap * 8, hipMemcpyDeviceToHost)); q += N * CN_TF_COUNT * h->trk_cap * 8;
     if (P) {
-        HIPCHK(hipMemcpy(q, h->d_ped_init, N * P * 16, hipMemcpyDeviceToHost)); q += N * P * 16;
-        HIPCHK(hipMemcpy(q, h->d_ped_preset, N * P * 16, hipMemcpyDeviceToHost)); q += N * P * 16;
-        HIPCHK(hipMemcpy(q, h->d_ped_aux, N * P * 24, hipMemcpyDeviceToHost)); q += N * P * 24;
+        CN_HIPCHK(fail, hipMemcpy(q, h->d_ped_init, N * P * 16, hipMemcpyDeviceToHost)); q += N * P * 16;
+        CN_HIPCHK(fail, hipMemcpy(q, h->d_ped_preset, N * P * 16, hipMemcpyDeviceToHost)); q += N * P * 16;
+        CN_HIPCHK(fail, hipMemcpy(q, h->d_ped_aux, N * P * 24, hipMemcpyDeviceToHost)); q += N * P * 24;
     }
     return CN_OK;
 }
@@ -1091,7 +755,7 @@ extern "C" int cn_restore(cn_handle h, const void* buf, size_t size)
                                    " differs (a state only means something under the configuration that produced it)");
     if (hd.total_bytes != cn_snapshot_size(h) || size < hd.total_bytes) return fail(CN_ERR_SIZE, "cn_restore: truncated snapshot");
     DeviceScope scope(h->device);
-    HIPCHK(hipDeviceSynchronize());
+    CN_HIPCHK(fail, hipDeviceSynchronize());
     size_t N = h->cfg.n_envs, P = h->cfg.n_peds;
     const char* q = (const char*)buf + sizeof(hd);
     FIELD(field_to_device(h, CN_ST_OFF_SD, q, CN_SD_COUNT * 8)); q += N * CN_SD_COUNT * 8;
@@ -1100,12 +764,12 @@ extern "C" int cn_restore(cn_handle h, const void* buf, size_t size)
         FIELD(field_to_device(h, CN_ST_OFF_PED_P, q, P * 16)); q += N * P * 16;
         FIELD(field_to_device(h, CN_ST_OFF_PED_V(P), q, P * 16)); q += N * P * 16;
     }
-    HIPCHK(hipMemcpy(h->d_trk, q, N * CN_TF_COUNT * h->trk_cap * 8, hipMemcpyHostToDevice)); q += N * CN_TF_COUNT * h->trk_cap * 8;
+    CN_HIPCHK(fail, hipMemcpy(h->d_trk, q, N * CN_TF_COUNT * h->trk_cap * 8, hipMemcpyHostToDevice)); q += N * CN_TF_COUNT * h->trk_cap * 8;
     if (P) {
         h->ped_init.assign((const double*)q, (const double*)q + N * P * 2);
-        HIPCHK(hipMemcpy(h->d_ped_init, q, N * P * 16, hipMemcpyHostToDevice)); q += N * P * 16;
-        HIPCHK(hipMemcpy(h->d_ped_preset, q, N * P * 16, hipMemcpyHostToDevice)); q += N * P * 16;
-        HIPCHK(hipMemcpy(h->d_ped_aux, q, N * P * 24, hipMemcpyHostToDevice)); q += N * P * 24;
+        CN_HIPCHK(fail, hipMemcpy(h->d_ped_init, q, N * P * 16, hipMemcpyHostToDevice)); q += N * P * 16;
+        CN_HIPCHK(fail, hipMemcpy(h->d_ped_preset, q, N * P * 16, hipMemcpyHostToDevice)); q += N * P * 16;
+        CN_HIPCHK(fail, hipMemcpy(h->d_ped_aux, q, N * P * 24, hipMemcpyHostToDevice)); q += N * P * 24;
     }
     return CN_OK;
 }

@@ -15,6 +15,7 @@
 #include "crowdnav_device.h"
 #include "crowdnav_kernel.h"
 #include "crowdnav_variants.h"
+#include "crowdnav_actor.h"
 
 // One wavefront per workgroup: the LDS processes a wave's DS instructions in issue order, so a
 // cross-lane hand-off through LDS needs no s_barrier and no vmcnt/lgkmcnt drain -- only the compiler
@@ -3261,8 +3262,8 @@ enum : unsigned { CN_F_EXT = 1, CN_F_SAME = 2, CN_F_FUSED = 4, CN_F_FAIR = 8, CN
 #define CN_S720_BOUNDS __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 #endif
 // The kernels are the rows of CN_WORLDS (crowdnav_variants.h): each family below -- step, sequence, policy -- is one macro that
-// expands a row to its definitions, and the row names the compile unit of each (csrc/build.sh: -DCN_TU=1 ... 5; 6 = the population's
-// actor kernels; unset = one unit with everything).  CN_IN_TU_n(x) is x in unit n and nothing elsewhere.  Unit 1 holds every one-step
+// expands a row to its definitions, and the row names the compile unit of each (csrc/build.sh: -DCN_TU=1 ... 5;
+// unset = one unit with everything).  CN_IN_TU_n(x) is x in unit n and nothing elsewhere.  Unit 1 holds every one-step
 // kernel; units 2-5 the sequence and policy kernels, compiled with -mllvm -disable-machine-licm: their step loop wraps the whole
 // step body; MachineLICM hoists every constant and address the body materialises out of that loop and the register allocator then
 // spills them (cn_env_kernel_seq: 155 SGPR + 6 VGPR spills, 28 bytes of scratch; without the pass 6 / 0 / 0 and 3 % faster).
@@ -3386,335 +3387,11 @@ extern "C" __global__ void cn_gather_kernel(CnKParams p, float* last_ret, float*
     }
 }
 
-// ---- policy tail of the TD3 actor (the caller of the hot path) ---------------------------
-// One launch instead of ~10 elementwise ones: action heads sigmoid(l0)*max_v / tanh(l1)*max_w (TD3:103-104),
-// Gaussian exploration noise N(0, sigma) (TD3:67-78, 209-211) from a counter-based RNG, clip to
-// v in [0, max_v], w in [-max_w, max_w] (TD3:214-215).
-extern "C" __global__ void cn_policy_tail_kernel(const float* __restrict__ logits, float* __restrict__ action, int n,
-                                                 float max_v, float max_w, float sigma, uint64_t seed, uint64_t counter)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float l0 = logits[2 * i], l1 = logits[2 * i + 1];
-    float v = max_v / (1.0f + __expf(-l0));
-    float w = max_w * tanhf(l1);
-    if (sigma > 0.0f) {
-        uint64_t h = cn_mix64(seed ^ cn_mix64(counter));
-        h = cn_mix64(h ^ (uint64_t)(uint32_t)i);
-        float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777217.0f);   // (0, 1]
-        float u2 = (float)(uint32_t)((h >> 8) & 0xffffffu) * (1.0f / 16777216.0f);
-        float r = sqrtf(-2.0f * __logf(u1)), s_, c_;
-        __sincosf(6.28318530718f * u2, &s_, &c_);
-        v += sigma * r * c_;
-        w += sigma * r * s_;
-    }
-    action[2 * i] = fminf(fmaxf(v, 0.0f), max_v);
-    action[2 * i + 1] = fminf(fmaxf(w, -max_w), max_w);
-}
-
 #endif   // CN_TU 1
-// ---- fused TD3 actor: 3 x Linear(256) + ReLU + output stage in ONE launch (the caller of the hot path, A33) -------
-// (device helpers: both translation units -- cn_actor_kernel is unit 1's, cn_policy_kernel unit 2's)
-// Actor.forward (TD3:96-106) + Agent.act's noise and clip (TD3:209-215) for a tile of 16 environments per workgroup,
-// on the f32-input matrix cores: v_mfma_f32_16x16x4_f32 (exact f32: a k-ordered fmaf chain, same precision as the
-// reference's fp32 PyTorch actor).  Lane l feeds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15].
-// Round 3: every wave runs the FULL K range of its own 256 / NW columns (NW = 8 waves: two interleaved column tiles per wave,
-// col = 32 wave + 2 j + t, one 8-byte load of the K-major weights feeds both MFMAs), so there are no K-split partial sums
-// to park in LDS and re-add: the tile needs X [16][Dp + 1] and one hidden buffer [16][257] -- 42 KB instead of 108 KB, 512
-// threads instead of 1024 -- which is what lets an actor workgroup sit on a CU NEXT TO a dozen environment wavefronts
-// (rollout_groups: one group's actor overlaps the others' env steps; before, it had to wait for 108 KB of LDS to drain).
-// Activations never leave LDS; weights stream from L2 (670 KB, shared by all tiles).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define ACT_H 256
-#define ACT_M 16
-#define ACT_THREADS 512            /* cn_actor_kernel: 8 waves */
-
-// Weights arrive PACKED in the order the matrix cores consume them (cn_actor_pack_weights / cn_actor_pack_kernel below): for a
-// layer with K inputs (a multiple of 32) and 256 outputs, block b = 8 k-steps of 4, wave w = 32 columns, q = a pair of k-steps,
-//   P[((((b 8 + w) 4 + q) 64 + lane) 4 + j] = W^T[k = 32 b + 4 (2 q + (j >> 1)) + (lane >> 4)][c = 32 w + 2 (lane & 15) + (j & 1)]
-// so a lane's operands for one block are FOUR 16-byte loads 1 KB apart and a wave's are 4 KB contiguous.  With the K-major
-// layout the same operands were eight 8-byte loads (16 lanes x 8 B on each of 4 rows per instruction); tools/micro/l2_stream.hip:
-// a workgroup streaming a shared 688 KB array out of L2 gets 70-73 GB/s with global_load_dwordx2 and 114-139 GB/s with
-// dwordx4 -- and the tile's two layers ran at exactly that dwordx2 pace (19.5 B/clk per CU in both), whatever the prefetch depth.
-#define ACT_U 8                    /* k-steps per pipelined block */
-struct ActW { float4 v[ACT_U / 2]; };
-// A lane's operands of block `blk`: uniform base (SGPR pair, advanced per block on the scalar unit) + this lane's 32-bit
-// offset + an immediate -- global_load_dwordx4 v, v_off, s[base] offset:1024 i -- so the loop has no 64-bit vector address
-// arithmetic (with a per-lane pointer every load cost a v_add_co / v_addc pair and their s_nop).
-struct ActWPtr { const float4* base; unsigned off; };
-__device__ __forceinline__ void actor_wload(ActW& w, const ActWPtr bp, int blk)
-{
-    const float4* q = bp.base + (size_t)blk * (8 * 4 * 64);
-#pragma unroll
-    for (int i = 0; i < ACT_U / 2; ++i) w.v[i] = q[bp.off + (unsigned)(i * 64)];
-}
-__device__ __forceinline__ ActWPtr actor_wptr(const float* __restrict__ WP, int wave, int lane)
-{
-    return ActWPtr{reinterpret_cast<const float4*>(WP) + (size_t)wave * (4 * 64), (unsigned)lane};
-}
-#if !defined(CN_TU) || CN_TU == 1
-extern "C" __global__ void cn_actor_pack_kernel(const float* __restrict__ wt, int K, float* __restrict__ packed)
-{
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;        // index into `packed`
-    if (idx >= K * ACT_H) return;
-    const int j = idx & 3, lane = (idx >> 2) & 63, q = (idx >> 8) & 3, w = (idx >> 10) & 7, b = idx >> 13;
-    const int k = 32 * b + 4 * (2 * q + (j >> 1)) + (lane >> 4), c = 32 * w + 2 * (lane & 15) + (j & 1);
-    packed[idx] = wt[(size_t)k * ACT_H + c];
-}
-#endif
-
-// One layer for this wave's 32 columns (two interleaved 16-column tiles: col = 32 wave + 2 j + t):
-// out[r][c] = relu(sum_k A[r][k] W^T[k][c] + bias[c]), K a multiple of 32, k ascending.  `first`: the weights of block 0,
-// requested by the caller BEFORE the barrier that releases A (their L2 round trip overlaps the staging / the previous layer's
-// tail).  The loop keeps the NEXT block -- its weights from L2 AND its A operands from LDS -- in flight while this block's 16
-// MFMAs issue, and its body is BRANCH-FREE on purpose: with `if (blk + 2 < nblk) load` in it the compiler's s_waitcnt counting
-// merged the "loaded" and "not loaded" paths and waited for the block it had just requested.  The last pair re-requests the
-// final block instead (clamped, never skipped).
-struct ActA { float a[ACT_U]; };
-__device__ __forceinline__ void actor_aload(ActA& x, const float* ap, int k0)
-{
-#pragma unroll
-    for (int u = 0; u < ACT_U; ++u) x.a[u] = ap[k0 + 4 * u];
-}
-// FINAL (the second hidden layer): the activations are not written back -- linear3 (TD3:101) is folded into the epilogue: every
-// lane multiplies its 4 rows x 2 columns of relu(h2) by linear3's weights of those columns, a DPP scan sums the 16 lanes
-// (= 32 columns) of each row group, and lane 15 of the group leaves the wave's partial logits in out[(wave 16 + row) 2 + o];
-// the caller adds the eight waves in wave order.  (Before: 16 x 256 activations through LDS, a barrier, 8 k LDS reads.)
-__device__ __forceinline__ float actor_row_sum(float v)      // inclusive scan over the 16 lanes of a DPP row: lane 15 = the sum
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xf, 0xf, false));   // row_shr:1
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xf, 0xf, false));   // row_shr:2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xf, 0xf, false));   // row_shr:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xf, 0xf, false));   // row_shr:8
-    return v;
-}
-template <bool FINAL = false>
-__device__ __forceinline__ void actor_layer(const float* __restrict__ A, int lda, int K, const float* __restrict__ WP,
-                                            const float* __restrict__ bias, float* __restrict__ out, int ldo, int wave, int lane,
-                                            const ActW& first, const float* __restrict__ W3 = nullptr)
-{
-    const int ai = lane & 15, ak = lane >> 4;
-    const int colb = 32 * wave + 2 * ai;
-    float w3[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (FINAL) { w3[0] = W3[colb]; w3[1] = W3[colb + 1]; w3[2] = W3[ACT_H + colb]; w3[3] = W3[ACT_H + colb + 1]; }
-    f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-    const float* ap = A + ai * lda + ak;
-    const ActWPtr bp = actor_wptr(WP, wave, lane);
-    // two register blocks, ping-pong: block b's MFMAs run on one while the other receives block b + 1 (a copy `cur = nxt` at the
-    // end of an iteration would wait for the loads it is supposed to hide).  The scheduling barriers keep the compiler from
-    // sinking the loads below the MFMAs.  (A ring of four blocks, three requests ahead, measured the same 17.5 us: layer 1 7 %
-    // faster, layer 2 10 % slower for its longer ramp -- the loads are not latency-bound any more.)
-    ActW w0 = first, w1;
-    ActA a0, a1;
-    const int nblk = K / (4 * ACT_U);
-    auto mma = [&](const ActW& w, const ActA& x) {
-#pragma unroll
-        for (int i = 0; i < ACT_U / 2; ++i) {
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x.a[2 * i], w.v[i].x, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x.a[2 * i], w.v[i].y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(x.a[2 * i + 1], w.v[i].z, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(x.a[2 * i + 1], w.v[i].w, acc1, 0, 0, 0);
-        }
-    };
-    actor_aload(a0, ap, 0);
-    int blk = 0;
-#ifndef ACT_ABLATE
-#define ACT_ABLATE 0        /* experiments only: 1 = no weight loads in the loop, 2 = no A loads, 3 = neither */
-#endif
-    if (ACT_ABLATE & 1) w1 = w0;
-    if (ACT_ABLATE & 2) a1 = a0;
-    for (; blk + 1 < nblk; blk += 2) {
-        if (!(ACT_ABLATE & 1)) actor_wload(w1, bp, blk + 1);
-        if (!(ACT_ABLATE & 2)) actor_aload(a1, ap, (blk + 1) * 4 * ACT_U);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(w0, a0);
-        __builtin_amdgcn_sched_barrier(0);
-        const int nb = min(blk + 2, nblk - 1);
-        if (!(ACT_ABLATE & 1)) actor_wload(w0, bp, nb);
-        if (!(ACT_ABLATE & 2)) actor_aload(a0, ap, nb * 4 * ACT_U);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(w1, a1);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (blk < nblk) mma(w0, a0);                        // odd block count: the last pair left block nblk - 1 in w0 / a0
-    const int rowb = ak * 4;                            // C/D: col = lane & 15, row = (lane >> 4) * 4 + reg
-    const float bv0 = bias[colb], bv1 = bias[colb + 1];
-    if constexpr (!FINAL) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            out[(rowb + r) * ldo + colb] = fmaxf(acc0[r] + bv0, 0.f);
-            out[(rowb + r) * ldo + colb + 1] = fmaxf(acc1[r] + bv1, 0.f);
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float h0 = fmaxf(acc0[r] + bv0, 0.f), h1 = fmaxf(acc1[r] + bv1, 0.f);
-            const float l0 = actor_row_sum(fmaf(h1, w3[1], h0 * w3[0]));
-            const float l1 = actor_row_sum(fmaf(h1, w3[3], h0 * w3[2]));
-            if (ai == 15) { out[(wave * ACT_M + rowb + r) * 2] = l0; out[(wave * ACT_M + rowb + r) * 2 + 1] = l1; }
-        }
-    }
-}
-
-#if defined(CN_TIMING) && (!defined(CN_TU) || CN_TU == 1)
-// profiling build: s_memtime stamps of workgroup b's wave 0 at [b][8] (tools/actor_timing.py)
-__device__ long long* cn_actor_timing = nullptr;
-extern "C" int cn_debug_set_actor_timing(long long* dev_buf)
-{
-    return hipMemcpyToSymbol(HIP_SYMBOL(cn_actor_timing), &dev_buf, sizeof(dev_buf)) == hipSuccess ? 0 : -4;
-}
-#define ACT_T(k) do { if (cn_actor_timing && threadIdx.x == 0) cn_actor_timing[(size_t)blockIdx.x * 8 + (k)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define ACT_T(k) do { } while (0)
-#endif
-// One tile of 16 environments through the actor (TD3:96-106 + 209-215), by the NW waves of a workgroup (all of its threads must
-// call this).  obs / action: the tile's first row; n_live: rows of the tile that exist; act_sm: 16 (Dp + 1) + 16 * 257 floats of
-// LDS.  Ends with the actions in global memory (the caller synchronises before anyone reads them).
-// `active` (wave-uniform): the policy kernel's workgroups have 16 waves; the eight that do not take part in the tile only keep
-// the barrier count.  action2: a second copy of the actions (LDS, or NULL).
-template <int NW>        // NW = 8 (the packed weight layout is laid out for 8 waves x 32 columns)
-__device__ __forceinline__ void actor_tile(const float* __restrict__ obs, int n_live, int row0, int D, int Dp,
-        const float* __restrict__ W1T, const float* __restrict__ b1, const float* __restrict__ W2T,
-        const float* __restrict__ b2, const float* __restrict__ W3, const float* __restrict__ b3,
-        float* __restrict__ action, float* action2, float max_v, float max_w, float sigma, uint64_t seed, uint64_t counter,
-        float* act_sm, const bool active = true, const int tid_in = -1)
-{
-    static_assert(NW == 8, "packed weights: 8 waves x 32 columns");
-    const int ldx = Dp + 1, ldh = ACT_H + 1;
-    float* X = act_sm;                 // [16][Dp + 1]; layer 2 writes its output here (the observations are dead by then)
-    float* H = X + ACT_M * ldx;        // [16][257] hidden activations of layer 1
-    const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    ActW w1, w2;
-    ACT_T(0);
-    if (active) {
-    actor_wload(w1, actor_wptr(W1T, wave, lane), 0);                   // in flight while the observations are staged
-    // Staging the tile: rows by wave, coalesced.  Every load of a chunk (8 x 64 columns of each of the wave's rows) is issued
-    // before the first store: written as `X[c] = src[c]` the loop paid one L2 round trip per 64 columns, in series -- 7 to 14 of
-    // them, half of the tile's latency.
-    constexpr int RPW = ACT_M / NW, CH = 8;
-    for (int c0 = 0; c0 < Dp; c0 += 64 * CH) {
-        float v[RPW][CH];
-#pragma unroll
-        for (int q = 0; q < RPW; ++q) {
-            const int r = wave + q * NW;
-            const float* src = obs + (size_t)r * D;
-#pragma unroll
-            for (int j = 0; j < CH; ++j) {
-                const int c = c0 + lane + 64 * j;
-                v[q][j] = (r < n_live && c < D) ? src[c] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < RPW; ++q) {
-            const int r = wave + q * NW;
-#pragma unroll
-            for (int j = 0; j < CH; ++j) {
-                const int c = c0 + lane + 64 * j;
-                if (c < Dp) X[r * ldx + c] = v[q][j];
-            }
-        }
-    }
-    }
-    ACT_T(1);
-    __syncthreads();
-    ACT_T(2);
-    if (active) {
-    actor_layer(X, ldx, Dp, W1T, b1, H, ldh, wave, lane, w1);
-    actor_wload(w2, actor_wptr(W2T, wave, lane), 0);                   // ... and while the slowest wave finishes layer 1
-    }
-    ACT_T(3);
-    __syncthreads();
-    ACT_T(4);
-    float* PL = X;                     // [8 waves][16 rows][2]: the waves' partial logits (the observations are dead by now)
-    if (active) actor_layer<true>(H, ldh, ACT_H, W2T, b2, PL, 0, wave, lane, w2, W3);
-    ACT_T(5);
-    __syncthreads();
-    ACT_T(6);
-    if (tid < 2 * ACT_M)
-    {   // heads, exploration noise, clip: thread = (env i, output o)
-        const int i = tid >> 1, o = tid & 1, part = 0;
-        float logit = b3[o];
-#pragma unroll
-        for (int w = 0; w < NW; ++w) logit += PL[(w * ACT_M + i) * 2 + o];
-        const int e = row0 + i;
-        float val = (o == 0) ? max_v / (1.0f + __expf(-logit)) : max_w * tanhf(logit);
-        if (sigma > 0.0f) {   // same generator as cn_policy_tail_kernel: keyed by (seed, counter, env row)
-            uint64_t hh = cn_mix64(seed ^ cn_mix64(counter));
-            hh = cn_mix64(hh ^ (uint64_t)(uint32_t)e);
-            float u1 = ((float)(uint32_t)(hh >> 40) + 1.0f) * (1.0f / 16777217.0f);
-            float u2 = (float)(uint32_t)((hh >> 8) & 0xffffffu) * (1.0f / 16777216.0f);
-            float rr_ = sqrtf(-2.0f * __logf(u1)), s_, c_;
-            __sincosf(6.28318530718f * u2, &s_, &c_);
-            val += sigma * rr_ * ((o == 0) ? c_ : s_);
-        }
-        val = (o == 0) ? fminf(fmaxf(val, 0.0f), max_v) : fminf(fmaxf(val, -max_w), max_w);
-        if (part == 0 && i < n_live) {
-            action[2 * (size_t)i + o] = val;
-            if (action2) action2[2 * (size_t)i + o] = val;
-        }
-    }
-    ACT_T(7);
-}
-
-#if !defined(CN_TU) || CN_TU == 1
-extern "C" __global__ void __launch_bounds__(ACT_THREADS) cn_actor_kernel(const float* __restrict__ obs, int n, int D, int Dp,
-        const float* __restrict__ W1T, const float* __restrict__ b1, const float* __restrict__ W2T,
-        const float* __restrict__ b2, const float* __restrict__ W3, const float* __restrict__ b3,
-        float* __restrict__ action, float max_v, float max_w, float sigma, uint64_t seed, uint64_t counter)
-{
-    extern __shared__ __attribute__((aligned(16))) float act_sm[];
-    const int row0 = blockIdx.x * ACT_M;
-    actor_tile<ACT_THREADS / 64>(obs + (size_t)row0 * D, min(ACT_M, n - row0), row0, D, Dp, W1T, b1, W2T, b2, W3, b3,
-                                 action + 2 * (size_t)row0, nullptr, max_v, max_w, sigma, seed, counter, act_sm);
-}
-#endif
-
-#if !defined(CN_TU) || CN_TU == 6
-// ---- a population's actors: P members' cn_actor_forward in ONE launch, their re-pack in one more (cn_actor_pop_*) --------------
-// (a unit of its own, so that unit 1's kernels -- cn_actor_kernel among them -- stay the instruction streams they were)
-// Member = blockIdx.z, its job a row of a table in device memory that cn_actor_pop_create uploads once (workgroup-uniform: scalar
-// loads); the members' call counters change with every call and travel BY VALUE in the kernel-argument segment (64 x 8 bytes), so a
-// call copies nothing to the device.  The grid's x is the widest member's tile count: a workgroup beyond its own member's rows
-// leaves before the first barrier (the test is workgroup-uniform).  Everything else is actor_tile with the row WITHIN the member --
-// the tile, the noise key (seed_p, counter_p, row) and therefore every bit of the output are cn_actor_kernel's for that member.
-// One tile is 42 KB of LDS at 398 inputs: tiles of different members share a CU, which P launches in series on one stream never do.
-extern "C" __global__ void __launch_bounds__(ACT_THREADS) cn_actor_pop_kernel(const CnActorPopJob* __restrict__ table, int D, int Dp,
-                                                                              int add_noise, CnActorPopCounters ctr)
-{
-    extern __shared__ __attribute__((aligned(16))) float act_sm[];
-    const CnActorPopJob& jb = table[blockIdx.z];
-    const int n = jb.n, row0 = blockIdx.x * ACT_M;
-    if (row0 >= n) return;
-    actor_tile<ACT_THREADS / 64>(jb.obs + (size_t)row0 * D, min(ACT_M, n - row0), row0, D, Dp, jb.w1p, jb.b1, jb.w2p, jb.b2, jb.w3, jb.b3,
-                                 jb.action + 2 * (size_t)row0, nullptr, jb.max_v, jb.max_w, add_noise ? jb.sigma : 0.0f, jb.seed,
-                                 ctr.c[blockIdx.z], act_sm);
-}
-
-// cn_actor_pack_kernel's layout for every member and both layers in one launch, read straight from the nn.Linear storages
-// W[c][k] ([256][K_in] row-major: the transpose that cn_actor_pack_weights' caller stages first never exists).  One thread per packed
-// element; grid (Dp, 2 layers, P) x 256 threads; layer 1 pads k >= D with zeros, so every element of both buffers is written.
-// Pure data movement, once per weight update: neighbouring threads read W 4 K_in bytes apart (about 0.4 MB per member, uncoalesced,
-// out of L2 after the update that wrote it) and write coalesced.  A tile transposed through LDS would mend the read; it is not worth
-// the machinery for a launch whose cost is its latency.
-extern "C" __global__ void __launch_bounds__(256) cn_actor_pop_pack_kernel(const CnActorPopPackJob* __restrict__ table, int D, int Dp)
-{
-    const CnActorPopPackJob& jb = table[blockIdx.z];
-    const int layer = blockIdx.y;
-    const int K = layer ? ACT_H : Dp, K_in = layer ? ACT_H : D;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;        // index into the packed buffer
-    if (idx >= K * ACT_H) return;
-    const float* __restrict__ W = layer ? jb.w2 : jb.w1;
-    float* __restrict__ packed = layer ? jb.w2p : jb.w1p;
-    const int j = idx & 3, lane = (idx >> 2) & 63, q = (idx >> 8) & 3, w = (idx >> 10) & 7, b = idx >> 13;
-    const int k = 32 * b + 4 * (2 * q + (j >> 1)) + (lane >> 4), c = 32 * w + 2 * (lane & 15) + (j & 1);
-    packed[idx] = k < K_in ? W[(size_t)c * K_in + k] : 0.0f;
-}
-#endif
-
 #if !defined(CN_TU) || CN_TU == 2 || CN_TU == 4 || CN_TU == 5
 // ---- cn_rollout_policy: T control periods per launch with the POLICY IN THE LOOP --------------------------------------------
 // A workgroup = 16 environments = 16 wavefronts (one CU's worth at 4 per SIMD).  Per control period: the first eight waves run
-// the TD3 actor (actor_tile above: the arithmetic, noise keys and clip of cn_actor_forward) on the 16 observations the
+// the TD3 actor (actor_tile, crowdnav_actor.h: the arithmetic, noise keys and clip of cn_actor_forward) on the 16 observations the
 // workgroup's environments wrote one period earlier and leave the 16 actions in LDS and in slot t of the caller's action array;
 // a workgroup barrier; every wave advances its environment by one Env.step with its action (exactly cn_env_kernel's step,
 // next-step reset convention) and writes observation / reward / done / indices to slot t; a workgroup barrier.  No launch and
@@ -3785,156 +3462,3 @@ __device__ __forceinline__ void policy_sequence_body()
 #define CN_DEF_POLICY(ID, LAYOUT, GT, SIM, WIDE, SHAPE, BOUNDS, COMPACT, STEP, SAME_HAS, SAME, EXT_HAS, EXT, SEQ, SEQ_TU, POL, POL_TU, POL_BOUND) \
     CN_IN_TU_##POL_TU(extern "C" __global__ void __launch_bounds__(POL_BOUND) POL(CnKParams p) { policy_sequence_body<SHAPE, GT, SIM, LAYOUT, WIDE>(); })
 CN_WORLDS(CN_DEF_POLICY)
-
-#if !defined(CN_TU) || CN_TU == 1
-
-#ifdef CN_TIMING
-// ---- device arithmetic under test (PROFILING BUILD ONLY; tests/test_gpu_parity.py::test_device_math_*): the hand-written
-// replacements for libm / compiler expansions, one element per thread.  op: 0 cn_sqrt(x)  1 cn_div(x, y)  2 cn_hypot(x, y)
-// 3 cn_atan2_t(x, y) = atan2 with x the ordinate (first argument) and y the abscissa  4, 5 sin, cos of cn_det_sincos_t(x)
-__global__ void cn_math_kernel(int op, const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ out, int n,
-                               const double* __restrict__ trig)
-{
-    cn_ktab tab = (cn_ktab)trig;           // the env kernels read this table from their kernel-argument block
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double r = 0.0, s_, c_;
-    switch (op) {
-    case 0: r = cn_sqrt(x[i]); break;
-    case 1: r = cn_div(x[i], y[i]); break;
-    case 2: r = cn_hypot(x[i], y[i]); break;
-    case 3: r = cn_atan2_t(tab, x[i], y[i]); break;
-    case 4: cn_det_sincos_t(tab, x[i], &s_, &c_); r = s_; break;
-    default: cn_det_sincos_t(tab, x[i], &s_, &c_); r = c_; break;
-    }
-    out[i] = r;
-}
-extern "C" int cn_debug_math(int op, const double* x, const double* y, double* out, int n, void* stream)
-{
-    static const double trig[CN_TRIG_COUNT] = CN_TRIG_TABLE;
-    double* d = nullptr;
-    if (hipMalloc(&d, sizeof(trig)) != hipSuccess) return -1;
-    if (hipMemcpy(d, trig, sizeof(trig), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return -1; }
-    hipLaunchKernelGGL(cn_math_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, op, x, y, out, n, (const double*)d);
-    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(d);
-    return e == hipSuccess ? 0 : -1;
-}
-
-// ---- the roundings, the IoU, the bare-instruction and the wave helpers under test (PROFILING BUILD ONLY;
-// tests/test_gpu_device_math.py holds each to Python / numpy, tests/device_math_ref.py).  One element per thread, inputs a..e
-// (an op reads only the ones it names), one float64 per element out; `py2` reaches the device functions as they get it in the
-// env kernels, a 32-bit flag behind a constant-address-space pointer; `s` is the wave-uniform operand, a kernel scalar.
-//    0, 1  cn_round_scaled(a, 1000 | 100)       2, 3  cn_py_round3, cn_py_round2         4, 5  cn_py_round3_t<true>, cn_py_round2_t<true>
-//    6, 7  cn_np_around3, cn_np_around2         8, 9  cn_np_around3_t<true>, cn_np_around2_t<true>
-//   10, 11 cn_round_np64_2_t<true>, <false>    12, 13 cn_div1000, cn_div100             14 cn_div_z(a, b)
-//   15 cn_iou3(a, b, c, d, half = e)           16 cn_iou3_positive (1.0 / 0.0)
-//   17, 18 cn_vmin, cn_vmax (a, b)             19 cn_vmax_s(a, s)     20 cn_vclamp(a, b, c)     21 cn_xorsign(a, b)     22 cn_fma_s(a, b, s)
-// Wave helpers: n is a multiple of 64 (the host refuses anything else), so every wavefront runs them with all 64 lanes active,
-// which is how the env kernels call them.  Integers travel as float64 values, 64-bit words as float64 bit patterns.
-//   30, 31 cn_wave_min_d, cn_wave_max_d        32, 33, 34 cn_wave_min_i, cn_wave_max_i, cn_wave_sum_i      35 cn_shfl_xor_d(a, (int)s)
-//   40..44 cn_row_shr_i<1, 2, 4, 8, 15>(ident = (int)s, a)         45..49 cn_row_shl_i<1, 2, 4, 8, 15>
-//   50 cn_writelane_u64(a, x = b of the wave's lane 0, l)          51 cn_readlane_u64(a, l)       l = the wave's index in the launch mod 64
-__global__ void cn_math_n_kernel(int op, const int32_t* __restrict__ flag, double s, const double* __restrict__ a, const double* __restrict__ b,
-                                 const double* __restrict__ c, const double* __restrict__ d, const double* __restrict__ e,
-                                 double* __restrict__ out, int n)
-{
-    cn_kflag py2 = (cn_kflag)flag;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int wl = __builtin_amdgcn_readfirstlane(i >> 6) & 63;
-    double r = 0.0;
-    switch (op) {
-    case 0: r = cn_round_scaled(a[i], 1000.0, py2); break;
-    case 1: r = cn_round_scaled(a[i], 100.0, py2); break;
-    case 2: r = cn_py_round3(a[i], py2); break;
-    case 3: r = cn_py_round2(a[i], py2); break;
-    case 4: r = cn_py_round3_t<true>(a[i], py2); break;
-    case 5: r = cn_py_round2_t<true>(a[i], py2); break;
-    case 6: r = cn_np_around3(a[i]); break;
-    case 7: r = cn_np_around2(a[i]); break;
-    case 8: r = cn_np_around3_t<true>(a[i]); break;
-    case 9: r = cn_np_around2_t<true>(a[i]); break;
-    case 10: r = cn_round_np64_2_t<true>(a[i], py2); break;
-    case 11: r = cn_round_np64_2_t<false>(a[i], py2); break;
-    case 12: r = cn_div1000(a[i]); break;
-    case 13: r = cn_div100(a[i]); break;
-    case 14: r = cn_div_z(a[i], b[i]); break;
-    case 15: r = cn_iou3(a[i], b[i], c[i], d[i], e[i], py2); break;
-    case 16: r = cn_iou3_positive(a[i], b[i], c[i], d[i], e[i], py2) ? 1.0 : 0.0; break;
-    case 17: r = cn_vmin(a[i], b[i]); break;
-    case 18: r = cn_vmax(a[i], b[i]); break;
-    case 19: r = cn_vmax_s(a[i], s); break;
-    case 20: r = cn_vclamp(a[i], b[i], c[i]); break;
-    case 21: r = cn_xorsign(a[i], b[i]); break;
-    case 22: r = cn_fma_s(a[i], b[i], s); break;
-    case 30: r = cn_wave_min_d(a[i]); break;
-    case 31: r = cn_wave_max_d(a[i]); break;
-    case 32: r = (double)cn_wave_min_i((int)a[i]); break;
-    case 33: r = (double)cn_wave_max_i((int)a[i]); break;
-    case 34: r = (double)cn_wave_sum_i((int)a[i]); break;
-    case 35: r = cn_shfl_xor_d(a[i], (int)s); break;
-    case 40: r = (double)cn_row_shr_i<1>((int)s, (int)a[i]); break;
-    case 41: r = (double)cn_row_shr_i<2>((int)s, (int)a[i]); break;
-    case 42: r = (double)cn_row_shr_i<4>((int)s, (int)a[i]); break;
-    case 43: r = (double)cn_row_shr_i<8>((int)s, (int)a[i]); break;
-    case 44: r = (double)cn_row_shr_i<15>((int)s, (int)a[i]); break;
-    case 45: r = (double)cn_row_shl_i<1>((int)s, (int)a[i]); break;
-    case 46: r = (double)cn_row_shl_i<2>((int)s, (int)a[i]); break;
-    case 47: r = (double)cn_row_shl_i<4>((int)s, (int)a[i]); break;
-    case 48: r = (double)cn_row_shl_i<8>((int)s, (int)a[i]); break;
-    case 49: r = (double)cn_row_shl_i<15>((int)s, (int)a[i]); break;
-    case 50: r = __longlong_as_double((long long)cn_writelane_u64((unsigned long long)__double_as_longlong(a[i]),
-                                                                  (unsigned long long)__double_as_longlong(b[i & ~63]), wl)); break;
-    case 51: r = __longlong_as_double((long long)cn_readlane_u64((unsigned long long)__double_as_longlong(a[i]), wl)); break;
-    default: break;
-    }
-    out[i] = r;
-}
-// a..e: n float64 each on the device (an op's unused inputs may alias a); returns -2 for an op / n it refuses, -1 for a HIP error
-extern "C" int cn_debug_math_n(int op, int py2, double s, const double* a, const double* b, const double* c, const double* d, const double* e,
-                               double* out, int n, void* stream)
-{
-    const bool known = (op >= 0 && op <= 22) || (op >= 30 && op <= 35) || (op >= 40 && op <= 51);
-    if (!known || n <= 0 || !a || !b || !c || !d || !e || !out) return -2;
-    if (op >= 30 && (n & 63) != 0) return -2;          // the wave helpers run under a full exec mask only
-    const int32_t flag = py2 ? 1 : 0;
-    int32_t* f = nullptr;
-    if (hipMalloc(&f, sizeof(flag)) != hipSuccess) return -1;
-    if (hipMemcpy(f, &flag, sizeof(flag), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(f); return -1; }
-    hipLaunchKernelGGL(cn_math_n_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, op, (const int32_t*)f, s, a, b, c, d, e, out, n);
-    const hipError_t err = hipStreamSynchronize((hipStream_t)stream);
-    (void)hipFree(f);
-    return err == hipSuccess ? 0 : -1;
-}
-
-// ---- PMC calibration (PROFILING BUILD ONLY, libcrowdnav_timing.so; tools/calib_pmc.py): known-byte streaming reads / writes at the access widths the
-// env kernel uses, so FETCH_SIZE / WRITE_SIZE can be turned into bytes (MI355X_MICROARCH.md, HBM section).
-template <typename T>
-__global__ void cn_calib_read_kernel(const T* __restrict__ src, size_t n, T* __restrict__ out)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-    T acc = T(0);
-    for (; i < n; i += stride) acc += src[i];
-    if (acc == T(123456789)) out[0] = acc;  // never true for the zero-filled buffer; keeps the loads alive
-}
-template <typename T>
-__global__ void cn_calib_write_kernel(T* __restrict__ dst, size_t n)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) dst[i] = T(1);
-}
-extern "C" void cn_calib_launch(void* buf, size_t bytes, int width, int write, void* stream)
-{
-    hipStream_t st = (hipStream_t)stream;
-    dim3 g(256 * 16), b(256);
-    if (!write) {
-        if (width == 4) hipLaunchKernelGGL(cn_calib_read_kernel<float>, g, b, 0, st, (const float*)buf, bytes / 4, (float*)buf);
-        else hipLaunchKernelGGL(cn_calib_read_kernel<double>, g, b, 0, st, (const double*)buf, bytes / 8, (double*)buf);
-    } else {
-        if (width == 4) hipLaunchKernelGGL(cn_calib_write_kernel<float>, g, b, 0, st, (float*)buf, bytes / 4);
-        else hipLaunchKernelGGL(cn_calib_write_kernel<double>, g, b, 0, st, (double*)buf, bytes / 8);
-    }
-}
-#endif
-#endif

@@ -1,12 +1,15 @@
-// crowdnav_pop_record.hip -- the kernels of cn_pop_record (include/crowdnav.h): a population's transitions and finished episodes in
-// two launches whatever the number of members.  The entry points are in crowdnav_abi.hip (they know an environment handle's state
-// records); the bodies are crowdnav_record.h's, the text cn_replay_write's and cn_episode_log_add's kernels are made of.
+// crowdnav_pop_record.hip -- cn_pop_record (include/crowdnav.h): a population's transitions and finished episodes in two launches
+// whatever the number of members -- the two kernels, then the entry points that launch them (they read an environment handle's state
+// records: crowdnav_host.h; errors go to cn_last_error).  The bodies are crowdnav_record.h's, the text cn_replay_write's and
+// cn_episode_log_add's kernels are made of.
 // Member = blockIdx.z, its job a row of a table in device memory that cn_pop_record_create uploads once (workgroup-uniform: scalar
 // loads, as cn_actor_pop_kernel's); `launch` changes with every call and travels by value.  A unit of its own, so that the units of
 // the step kernels and of the learners keep their instruction streams.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include <algorithm>
+#include <memory>
+#include <new>
 
+#include "crowdnav_host.h"
 #include "crowdnav_record.h"
 
 // Launch A, grid (1, 1, P) x 1024: member z's cn_replay_slot_kernel with keep = !resetting, then its cn_episode_log_kernel with the
@@ -42,4 +45,121 @@ extern "C" __global__ void __launch_bounds__(256) cn_pop_record_copy_kernel(cons
     const float* __restrict__ obs = jb.obs + (size_t)i * D;
     float* prev = jb.prev + (size_t)i * D;
     for (int c = threadIdx.x; c < D; c += blockDim.x) prev[c] = obs[c];
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------------
+struct cn_pop_record_s {
+    int device = 0, P = 0, max_n = 0;                      // max_n: the widest member's rows, launch B's grid x (0: nothing to launch)
+    void* mem = nullptr;                                   // one allocation: the table, then every member's slot scratch and resetting bytes
+    const CnPopRecordJob* jobs = nullptr;
+    std::vector<uint8_t*> resetting;
+    cn_pop_record_s() = default;
+    cn_pop_record_s(const cn_pop_record_s&) = delete;
+    ~cn_pop_record_s() { if (mem) { DeviceScope scope(device); (void)hipFree(mem); } }
+};
+
+extern "C" int cn_pop_record_create(const cn_pop_record_member* members, int n_members, int obs_dim, int device, cn_pop_record_handle* out)
+{
+    const std::string f("cn_pop_record_create");
+    if (!members) return fail(CN_ERR_ARG, f + ": members is null");
+    if (!out) return fail(CN_ERR_ARG, f + ": out is null");
+    if (n_members < 1 || n_members > CN_POP_RECORD_MAX) return fail(CN_ERR_ARG, f + ": n_members must be 1 ... 64");
+    if (obs_dim < 1) return fail(CN_ERR_CONFIG, f + ": obs_dim must be at least 1");
+    const int P = n_members;
+    struct Named { const void* ptr; const char* name; int member; };
+    std::vector<Named> written;                            // what a launch writes, per member: no two members may share any of it
+    int max_n = 0;
+    for (int p = 0; p < P; ++p) {
+        const cn_pop_record_member& m = members[p];
+        const std::string who = ": member " + std::to_string(p) + ": ";
+        if (m.n < 0) return fail(CN_ERR_ARG, f + who + "n is negative");
+        if (m.n > 0) {
+            if (!m.env && !(m.counters && m.last_return))
+                return fail(CN_ERR_ARG, f + who + "neither env nor both counters and last_return are given");
+            if (m.env && m.n != m.env->cfg.n_envs)
+                return fail(CN_ERR_ARG, f + who + "n is " + std::to_string(m.n) + " but env has n_envs " + std::to_string(m.env->cfg.n_envs));
+            const void* const rp[5] = {m.prev, m.obs, m.action, m.reward, m.done};
+            static const char* const rn[5] = {"prev", "obs", "action", "reward", "done"};
+            for (int i = 0; i < 5; ++i)
+                if (!rp[i]) return fail(CN_ERR_ARG, f + who + rn[i] + " is null");
+        }
+        const cn_replay_ring& r = m.ring;
+        if (!r.s || !r.a || !r.r || !r.s2 || !r.d || !r.pos_dev || !r.size_dev || r.capacity < 1 || r.obs_dim < 1)
+            return fail(CN_ERR_ARG, f + who + "incomplete ring");
+        if (!m.log.rows || !m.log.n_dev || !m.log.tot_dev) return fail(CN_ERR_ARG, f + who + "incomplete log");
+        if (m.log.max_rows < 0) return fail(CN_ERR_ARG, f + who + "log.max_rows is negative");
+        if ((int64_t)m.n > r.capacity)
+            return fail(CN_ERR_ARG, f + who + "n exceeds ring.capacity (two rows of one call would share a slot)");
+        if (r.obs_dim != obs_dim)
+            return fail(CN_ERR_CONFIG, f + who + "ring.obs_dim is " + std::to_string(r.obs_dim) + ", obs_dim " + std::to_string(obs_dim));
+        const Named mine[11] = {{r.s, "ring.s", p}, {r.a, "ring.a", p}, {r.r, "ring.r", p}, {r.s2, "ring.s2", p}, {r.d, "ring.d", p},
+                                {r.pos_dev, "ring.pos_dev", p}, {r.size_dev, "ring.size_dev", p}, {m.log.rows, "log.rows", p},
+                                {m.log.n_dev, "log.n_dev", p}, {m.log.tot_dev, "log.tot_dev", p}, {m.prev, "prev", p}};
+        for (const Named& x : mine) {
+            if (!x.ptr) continue;                          // (prev of a member without rows)
+            for (const Named& y : written)
+                if (y.ptr == x.ptr)
+                    return fail(CN_ERR_CONFIG, f + who + x.name + " is also member " + std::to_string(y.member) + "'s " + y.name +
+                                               " (they would race inside a launch)");
+        }
+        written.insert(written.end(), mine, mine + 11);
+        max_n = std::max(max_n, (int)m.n);
+    }
+    std::unique_ptr<cn_pop_record_s> h(new (std::nothrow) cn_pop_record_s());
+    if (!h) return fail(CN_ERR_ARG, f + ": out of memory");
+    int dev = device;
+    if (dev < 0) CN_HIPCHK(fail, hipGetDevice(&dev));
+    h->device = dev; h->P = P; h->max_n = max_n;
+    DeviceScope scope(dev);
+    // [jobs P] rounded up to 256 bytes, then per member slot [n] int32 and resetting [n] bytes, each rounded up to 16 bytes.  The whole
+    // image is made on the host and uploaded by one blocking copy: the flags are zero whatever stream the first call runs on.
+    const size_t tab = (sizeof(CnPopRecordJob) * P + 255) & ~(size_t)255;
+    size_t total = tab;
+    std::vector<size_t> off_slot(P), off_flag(P);
+    for (int p = 0; p < P; ++p) {
+        off_slot[p] = total; total += (sizeof(int32_t) * (size_t)members[p].n + 15) & ~(size_t)15;
+        off_flag[p] = total; total += ((size_t)members[p].n + 15) & ~(size_t)15;
+    }
+    CN_HIPCHK(fail, hipMalloc(&h->mem, total));
+    std::vector<char> image(total, 0);
+    CnPopRecordJob* hj = (CnPopRecordJob*)image.data();
+    h->resetting.resize(P);
+    for (int p = 0; p < P; ++p) {
+        const cn_pop_record_member& m = members[p];
+        CnPopRecordJob& j = hj[p];
+        j.ring = m.ring; j.log = m.log;
+        j.state = m.env ? m.env->d_state : nullptr; j.state_stride = m.env ? (int64_t)m.env->stride : 0;
+        j.counters = m.counters; j.last_return = m.last_return;
+        j.prev = m.prev; j.obs = m.obs; j.action = m.action; j.reward = m.reward; j.done = m.done;
+        j.resetting = h->resetting[p] = (uint8_t*)h->mem + off_flag[p];
+        j.slot = (int32_t*)((char*)h->mem + off_slot[p]);
+        j.n = m.n; j.reserved = 0;
+    }
+    CN_HIPCHK(fail, hipMemcpy(h->mem, image.data(), total, hipMemcpyHostToDevice));
+    h->jobs = (const CnPopRecordJob*)h->mem;
+    *out = h.release();
+    return CN_OK;
+}
+extern "C" void cn_pop_record_destroy(cn_pop_record_handle h) { delete h; }
+extern "C" int cn_pop_record_members(cn_pop_record_handle h) { return h ? h->P : 0; }
+
+extern "C" uint8_t* cn_pop_record_resetting(cn_pop_record_handle h, int member)
+{
+    if (!h) { (void)fail(CN_ERR_ARG, "cn_pop_record_resetting: null handle"); return nullptr; }
+    if (member < 0 || member >= h->P) {
+        (void)fail(CN_ERR_ARG, "cn_pop_record_resetting: member " + std::to_string(member) + " out of range (the handle has " + std::to_string(h->P) + ")");
+        return nullptr;
+    }
+    return h->resetting[member];
+}
+
+extern "C" int cn_pop_record(cn_pop_record_handle h, float launch, void* stream)
+{
+    if (!h) return fail(CN_ERR_ARG, "cn_pop_record: null handle");
+    if (h->max_n == 0) return CN_OK;
+    DeviceScope scope(h->device);
+    hipLaunchKernelGGL(cn_pop_record_scan_kernel, dim3(1, 1, h->P), dim3(1024), 0, (hipStream_t)stream, h->jobs, launch);
+    hipLaunchKernelGGL(cn_pop_record_copy_kernel, dim3(h->max_n, 1, h->P), dim3(256), 0, (hipStream_t)stream, h->jobs);
+    CN_HIPCHK(fail, hipGetLastError());
+    return CN_OK;
 }

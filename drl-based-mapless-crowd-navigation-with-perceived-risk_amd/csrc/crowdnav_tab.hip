@@ -32,12 +32,12 @@
 
 #include "../../include/crowdnav.h"
 #include "crowdnav_device.h"
+#include "crowdnav_host.h"
 
 namespace {
 
 thread_local std::string g_tab_err;
 int tab_fail(int code, const std::string& msg) { g_tab_err = msg; return code; }
-#define TABCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return tab_fail(CN_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 constexpr int TAB_S = CN_TAB_STATES, TAB_A = CN_TAB_ACTIONS, TAB_CELLS = TAB_S * TAB_A;   // 977 x 3 = 2931
 constexpr int TAB_ND = 30, TAB_NH = 32;                 // edges: d in 0..30, h in 0..32
@@ -245,12 +245,6 @@ __global__ void __launch_bounds__(TAB_THREADS) tab_learn_act_kernel(TabArgs p)
     }
 }
 
-struct DevScope {     // the handle's device current for this call
-    int prev = -1, want;
-    explicit DevScope(int dev) : want(dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != want) (void)hipSetDevice(want); }
-    ~DevScope() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
-};
-
 }  // namespace
 
 struct cn_tab_s {
@@ -292,7 +286,7 @@ extern "C" int cn_tab_create(const cn_tab_config* cfg, int device, cn_tab_handle
     float ed[TAB_ND + TAB_NH];
     for (int k = 0; k < TAB_ND; ++k) { h->dist_host[k] = (double)k / 10.0; ed[k] = (float)h->dist_host[k]; }   // round(0.1 k, 2) = the double nearest k / 10
     for (int k = 0; k < TAB_NH; ++k) ed[TAB_ND + k] = (float)RADIAN_BINS[k];
-    DevScope scope(device);
+    DeviceScope scope(device);
     const size_t o_q = 0, o_cnt = o_q + sizeof(double) * TAB_CELLS, o_memo = o_cnt + 2 * sizeof(long long), o_ed = o_memo + sizeof(EpsMemo),
                  o_so = o_ed + sizeof(ed), o_pr = o_so + sizeof(so), total = o_pr + TAB_CELLS;
     hipError_t e = hipMalloc((void**)&h->pool, total);
@@ -315,7 +309,7 @@ extern "C" int cn_tab_create(const cn_tab_config* cfg, int device, cn_tab_handle
 extern "C" void cn_tab_destroy(cn_tab_handle h)
 {
     if (!h) return;
-    DevScope scope(h->device);
+    DeviceScope scope(h->device);
     (void)hipDeviceSynchronize();
     if (h->pool) (void)hipFree(h->pool);
     delete h;
@@ -324,29 +318,29 @@ extern "C" void cn_tab_destroy(cn_tab_handle h)
 extern "C" int cn_tab_set(cn_tab_handle h, const double* q_host, const uint8_t* present_host, const int64_t* counts_host)
 {
     if (!h || !q_host || !present_host) return tab_fail(CN_ERR_ARG, "cn_tab_set: null argument");
-    DevScope scope(h->device);
+    DeviceScope scope(h->device);
     std::vector<double> qv(TAB_CELLS);
     std::vector<uint8_t> pv(TAB_CELLS);
     for (int c = 0; c < TAB_CELLS; ++c) { pv[c] = present_host[c] ? 1 : 0; qv[c] = pv[c] ? q_host[c] : 0.0; }
     long long cn[2] = {counts_host ? (long long)counts_host[0] : 0, counts_host ? (long long)counts_host[1] : 0};
-    TABCHK(hipDeviceSynchronize());
-    TABCHK(hipMemcpy(h->q, qv.data(), sizeof(double) * TAB_CELLS, hipMemcpyHostToDevice));
-    TABCHK(hipMemcpy(h->present, pv.data(), TAB_CELLS, hipMemcpyHostToDevice));
-    TABCHK(hipMemcpy(h->counts, cn, sizeof(cn), hipMemcpyHostToDevice));
-    TABCHK(hipDeviceSynchronize());
+    CN_HIPCHK(tab_fail, hipDeviceSynchronize());
+    CN_HIPCHK(tab_fail, hipMemcpy(h->q, qv.data(), sizeof(double) * TAB_CELLS, hipMemcpyHostToDevice));
+    CN_HIPCHK(tab_fail, hipMemcpy(h->present, pv.data(), TAB_CELLS, hipMemcpyHostToDevice));
+    CN_HIPCHK(tab_fail, hipMemcpy(h->counts, cn, sizeof(cn), hipMemcpyHostToDevice));
+    CN_HIPCHK(tab_fail, hipDeviceSynchronize());
     return CN_OK;
 }
 
 extern "C" int cn_tab_get(cn_tab_handle h, double* q_host, uint8_t* present_host, int64_t* counts_host)
 {
     if (!h || !q_host || !present_host) return tab_fail(CN_ERR_ARG, "cn_tab_get: null argument");
-    DevScope scope(h->device);
-    TABCHK(hipDeviceSynchronize());
-    TABCHK(hipMemcpy(q_host, h->q, sizeof(double) * TAB_CELLS, hipMemcpyDeviceToHost));
-    TABCHK(hipMemcpy(present_host, h->present, TAB_CELLS, hipMemcpyDeviceToHost));
+    DeviceScope scope(h->device);
+    CN_HIPCHK(tab_fail, hipDeviceSynchronize());
+    CN_HIPCHK(tab_fail, hipMemcpy(q_host, h->q, sizeof(double) * TAB_CELLS, hipMemcpyDeviceToHost));
+    CN_HIPCHK(tab_fail, hipMemcpy(present_host, h->present, TAB_CELLS, hipMemcpyDeviceToHost));
     if (counts_host) {
         long long cn[2];
-        TABCHK(hipMemcpy(cn, h->counts, sizeof(cn), hipMemcpyDeviceToHost));
+        CN_HIPCHK(tab_fail, hipMemcpy(cn, h->counts, sizeof(cn), hipMemcpyDeviceToHost));
         counts_host[0] = cn[0]; counts_host[1] = cn[1];
     }
     return CN_OK;
@@ -370,7 +364,7 @@ extern "C" int cn_tab_learn_act(cn_tab_handle h, const cn_tab_io* io, void* stre
     if (io->n < 1 || io->col < 0 || io->obs_ld < (int64_t)io->col + 2) return tab_fail(CN_ERR_CONFIG, "cn_tab_learn_act: n < 1, col < 0 or obs_ld < col + 2");
     if (!(io->epsilon_discount >= 0.0 && io->epsilon_discount <= 1.0) || !(io->epsilon_min > 0.0))
         return tab_fail(CN_ERR_CONFIG, "cn_tab_learn_act: epsilon_discount outside [0, 1] or epsilon_min <= 0");
-    DevScope scope(h->device);
+    DeviceScope scope(h->device);
     TabArgs p;
     p.q = h->q; p.present = h->present; p.counts = h->counts; p.state_of = h->state_of; p.edges = h->edges; p.memo = h->memo;
     p.obs_prev = io->obs_prev; p.obs = io->obs; p.ld = io->obs_ld; p.n = io->n; p.col = io->col; p.learn = io->learn != 0; p.act = io->act != 0;
@@ -379,6 +373,6 @@ extern "C" int cn_tab_learn_act(cn_tab_handle h, const cn_tab_io* io, void* stre
     p.episodes_dev = (const long long*)io->episodes_dev; p.u_learn = io->u_learn; p.u_act = io->u_act; p.seed = h->cfg.seed; p.counter = io->counter;
     p.action = io->action; p.twist = io->twist; p.state = io->state; p.state_prev = io->learn ? io->state_prev : nullptr; p.q_row = io->q_row;
     hipLaunchKernelGGL(tab_learn_act_kernel, dim3(1), dim3(TAB_THREADS), 0, (hipStream_t)stream, p);
-    TABCHK(hipGetLastError());
+    CN_HIPCHK(tab_fail, hipGetLastError());
     return CN_OK;
 }

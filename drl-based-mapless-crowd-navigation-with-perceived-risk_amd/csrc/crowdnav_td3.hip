@@ -29,6 +29,7 @@
 
 #include "../../include/crowdnav.h"
 #include "crowdnav_device.h"
+#include "crowdnav_host.h"
 #include "crowdnav_record.h"
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
@@ -37,7 +38,6 @@ namespace {
 
 thread_local std::string g_td3_err;
 int td3_fail(int code, const std::string& msg) { g_td3_err = msg; return code; }
-#define TD3CHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return td3_fail(CN_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 // ---- the three GEMM kernels ---------------------------------------------------------------------------------------------
 // C[i][j] = sum_r A(i, r) B(r, j) on v_mfma_f32_16x16x4_f32.  These layers are tiny (batch 128 x 256 units x 400 inputs =
@@ -699,12 +699,6 @@ __global__ void __launch_bounds__(1024) cn_episode_log_kernel(EpisodeLogArgs p)
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 namespace {
-struct DevScope {
-    int prev = -1, want;
-    explicit DevScope(int dev) : want(dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != want) (void)hipSetDevice(want); }
-    ~DevScope() { if (prev >= 0 && prev != want) (void)hipSetDevice(prev); }
-};
-
 // A learner's workspace is ONE device allocation that the handle's layout(Pool&) describes once, as a take(field, n) per buffer.
 // learner_create runs it twice: with base == nullptr it only sums (the size hipMalloc gets), then it assigns the fields -- so the
 // size cannot disagree with the carve-up.  Every field is aligned for its own type, wherever it stands.
@@ -740,7 +734,7 @@ struct Learner {
     int sample_mode = CN_SAMPLE_WITH_REPLACEMENT;  // cn_*_set_replay_sample: read on the host when an update is enqueued
     Learner() = default;
     Learner(const Learner&) = delete;
-    ~Learner() { if (pool) { DevScope scope(device); (void)hipFree(pool); } }
+    ~Learner() { if (pool) { DeviceScope scope(device); (void)hipFree(pool); } }
     int start(const char*) { return CN_OK; }       // what create still has to write into the zeroed pool: nothing by default
 };
 // cn_*_create after the checks of the configuration: Hd = the handle (cfg, layout(Pool&), start(fn)), fn = the name in the error texts
@@ -751,7 +745,7 @@ int learner_create(const char* fn, const Cfg& c, int device, Hd** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return td3_fail(CN_ERR_NO_DEVICE, f + ": no HIP device (libcrowdnav has no CPU fallback)");
     if (device < 0 || device >= ndev) return td3_fail(CN_ERR_ARG, f + ": bad device ordinal");
-    DevScope scope(device);
+    DeviceScope scope(device);
     std::unique_ptr<Hd> h(new (std::nothrow) Hd());
     if (!h) return td3_fail(CN_ERR_ARG, f + ": out of memory");
     h->cfg = c; h->device = device; h->B = c.batch; h->D = c.obs_dim; h->H = c.hidden;
@@ -1017,10 +1011,10 @@ struct Td3LaunchNow {                              // cn_td3_update: every launc
 extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* batch, void* stream)
 {
     if (const int rc = check_update("cn_td3_update", h, batch)) return rc;
-    DevScope scope(h->device);
+    DeviceScope scope(h->device);
     Td3LaunchNow em{(hipStream_t)stream};
     td3_chain(h, do_actor, batch, em);
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -1060,7 +1054,7 @@ struct cn_td3_pop_s {
     std::vector<PopStep> chain[2];
     cn_td3_pop_s() = default;
     cn_td3_pop_s(const cn_td3_pop_s&) = delete;
-    ~cn_td3_pop_s() { if (tables) { DevScope scope(device); (void)hipFree(tables); } }
+    ~cn_td3_pop_s() { if (tables) { DeviceScope scope(device); (void)hipFree(tables); } }
 };
 
 extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int device, cn_td3_pop_handle* out)
@@ -1106,7 +1100,7 @@ extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int d
         if (const int rc = learner_create(f.c_str(), cfgs[p], device, &m)) return rc;
         h->mem.emplace_back(m);
     }
-    DevScope scope(device);
+    DeviceScope scope(device);
     // record what a solo update of every member would launch, for both chains (GEMMs, tick); the job tables' size follows from it
     std::vector<Td3Record> rec[2];
     size_t njobs_all = 0;
@@ -1194,7 +1188,7 @@ extern "C" int cn_td3_pop_set_replay_sample(cn_td3_pop_handle h, int mode)
 extern "C" int cn_td3_pop_update(cn_td3_pop_handle h, int do_actor, void* stream)
 {
     if (!h) return td3_fail(CN_ERR_ARG, "cn_td3_pop_update: null handle");
-    DevScope scope(h->device);
+    DeviceScope scope(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int a = do_actor ? 1 : 0;
     hipLaunchKernelGGL(td3_prep_kernel<true>, dim3(h->B, h->P), dim3(256), 0, st, h->prep[h->sample_mode]);
@@ -1205,7 +1199,7 @@ extern "C" int cn_td3_pop_update(cn_td3_pop_handle h, int do_actor, void* stream
         else if (s.mode == GEMM_G) hipLaunchKernelGGL((td3_dgrad_kernel<false, true>), grid, dim3(256), 0, st, ga);
         else hipLaunchKernelGGL((td3_wgrad_kernel<false, true>), grid, dim3(256), 0, st, ga);
     }
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -1253,7 +1247,7 @@ extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void*
     if (const int rc = check_update("cn_ddpg_update", h, batch)) return rc;
     if (batch && batch->target_noise) return td3_fail(CN_ERR_ARG, "cn_ddpg_update: DDPG has no target-policy noise (batch->target_noise must be NULL)");
     const cn_ddpg_config& c = h->cfg;
-    DevScope scope(h->device);
+    DeviceScope scope(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int B = h->B, D = h->D, Dc = D + 2, H = h->H, qnt = h->qnt();
     // 1. sample / gather (ddpg.py:208-214); no noise is drawn
@@ -1307,7 +1301,7 @@ extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void*
     wgrad_job(ga.job[4], h->dz1a, H, h->xs, Dc, D, B, c.actor.w1, c.actor.b1, &h->mom[0][0], h->adam + 2, c.actor_t.w1, c.actor_t.b1);
     wgrad_job(ga.job[5], h->dl, 2, h->a_h2, H, H, B, c.actor.w3, c.actor.b3, &h->mom[0][4], h->adam + 2, c.actor_t.w3, c.actor_t.b3);
     launch_gemm<GEMM_H>(ga, 6, st);
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -1607,7 +1601,7 @@ extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* s
 {
     if (const int rc = check_update("cn_dqn_update", h, batch)) return rc;
     const cn_dqn_config& c = h->cfg;
-    DevScope scope(h->device);
+    DeviceScope scope(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int B = h->B, D = h->D, ld = c.obs_ld, H = h->H;
     DqnPrepArgs pa;
@@ -1668,7 +1662,7 @@ extern "C" int cn_dqn_update(cn_dqn_handle h, const cn_dqn_batch* batch, void* s
     for (int j = 0; j < 6; ++j) { ca.src[j] = src[j]; ca.dst[j] = dst[j]; ca.n[j] = (long long)h->params(j); }
     ca.flags = h->flags; ca.counter = h->counter; ca.kcur = h->kcur;
     hipLaunchKernelGGL(dqn_copy_kernel, dim3(128), dim3(256), 0, st, ca);
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -1680,7 +1674,7 @@ extern "C" int cn_dqn_act(const cn_dqn_act_io* io, int device, void* stream)
         return td3_fail(CN_ERR_CONFIG, "cn_dqn_act: n / obs_dim / obs_ld / hidden out of range (hidden <= 480: two 16-row activations in 64 KB of LDS)");
     if (!(io->epsilon_discount >= 0.0 && io->epsilon_discount <= 1.0) || !(io->epsilon_min > 0.0))
         return td3_fail(CN_ERR_CONFIG, "cn_dqn_act: epsilon_discount outside [0, 1] or epsilon_min <= 0");
-    DevScope scope(device);
+    DeviceScope scope(device);
     DqnActArgs p;
     p.obs = io->obs; p.ld = io->obs_ld; p.n = io->n; p.D = io->obs_dim; p.H = io->hidden; p.Hp = (io->hidden + 31) / 32 * 32;
     p.w1 = io->q.w1; p.b1 = io->q.b1; p.w2 = io->q.w2; p.b2 = io->q.b2; p.w3 = io->q.w3; p.b3 = io->q.b3;
@@ -1688,7 +1682,7 @@ extern "C" int cn_dqn_act(const cn_dqn_act_io* io, int device, void* stream)
     p.seed = io->seed; p.counter = io->counter; p.action = io->action; p.twist = io->twist; p.q = io->q_out;
     const size_t lds = (size_t)2 * 16 * p.Hp * sizeof(float);
     hipLaunchKernelGGL(dqn_act_kernel, dim3((io->n + 15) / 16), dim3(256), lds, (hipStream_t)stream, p);
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -1993,7 +1987,7 @@ extern "C" int cn_sac_update(cn_sac_handle h, const cn_td3_batch* batch, void* s
 {
     if (const int rc = check_update("cn_sac_update", h, batch)) return rc;
     const cn_sac_config& c = h->cfg;
-    DevScope scope(h->device);
+    DeviceScope scope(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int B = h->B, D = h->D, Dc = D + 2, H = h->H, Hv = h->Hv, qnt = h->qnt(), vnt = h->vnt();
     const size_t slot = (size_t)B * h->pnt();
@@ -2079,7 +2073,7 @@ extern "C" int cn_sac_update(cn_sac_handle h, const cn_td3_batch* batch, void* s
         const unsigned blocks = (unsigned)std::min<long long>(1024, (nmax + 1023) / 1024);      // grid-stride: four elements a thread
         hipLaunchKernelGGL(sac_pull_kernel, dim3(blocks), dim3(256), 0, st, sp);
     }
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -2090,7 +2084,7 @@ extern "C" int cn_sac_act(const cn_sac_act_io* io, int device, void* stream)
     if (io->n < 1 || io->obs_dim < 1 || io->obs_ld < io->obs_dim || io->hidden < 1 || io->hidden > 480)
         return td3_fail(CN_ERR_CONFIG, "cn_sac_act: n / obs_dim / obs_ld / hidden out of range (hidden <= 480: two 16-row activations in 64 KB of LDS)");
     if (!(io->log_std_min <= io->log_std_max)) return td3_fail(CN_ERR_CONFIG, "cn_sac_act: log_std_min > log_std_max");
-    DevScope scope(device);
+    DeviceScope scope(device);
     SacActArgs p;
     memset(&p, 0, sizeof(p));
     p.obs = io->obs; p.ld = io->obs_ld; p.n = io->n; p.D = io->obs_dim; p.H = io->hidden; p.Hp = (io->hidden + 31) / 32 * 32;
@@ -2100,7 +2094,7 @@ extern "C" int cn_sac_act(const cn_sac_act_io* io, int device, void* stream)
     p.twist = io->twist; p.mean = io->mean; p.log_std = io->log_std; p.z = io->z;
     const size_t lds = (size_t)2 * 16 * p.Hp * sizeof(float);
     hipLaunchKernelGGL(sac_act_kernel, dim3((io->n + 15) / 16), dim3(256), lds, (hipStream_t)stream, p);
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -2111,10 +2105,10 @@ extern "C" int cn_replay_sample_indices(uint64_t seed, uint64_t counter, int B, 
     if (B < 1) return td3_fail(CN_ERR_ARG, "cn_replay_sample_indices: B < 1");
     if (mode != CN_SAMPLE_WITH_REPLACEMENT && mode != CN_SAMPLE_DISTINCT)
         return td3_fail(CN_ERR_ARG, "cn_replay_sample_indices: mode must be CN_SAMPLE_WITH_REPLACEMENT (0) or CN_SAMPLE_DISTINCT (1)");
-    DevScope scope(device);
+    DeviceScope scope(device);
     hipLaunchKernelGGL(cn_replay_indices_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, (unsigned long long)counter, B,
                        size_dev, mode, rows_dev);
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -2126,13 +2120,13 @@ extern "C" int cn_replay_write(const cn_replay_ring* ring, const float* s, const
         return td3_fail(CN_ERR_ARG, "cn_replay_write: incomplete ring");
     if (n < 1) return td3_fail(CN_ERR_ARG, "cn_replay_write: n < 1");
     if ((int64_t)n > ring->capacity) return td3_fail(CN_ERR_ARG, "cn_replay_write: more rows than the ring holds (two rows of one call would share a slot)");
-    DevScope scope(device);
+    DeviceScope scope(device);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(cn_replay_slot_kernel, dim3(1), dim3(1024), 0, st, keep, n, ring->capacity, ring->pos_dev, ring->size_dev, slot_scratch);
     ReplayCopyArgs ca;
     ca.ring = *ring; ca.s = s; ca.a = a; ca.r = r; ca.s2 = s2; ca.done = done; ca.slot = slot_scratch;
     hipLaunchKernelGGL(cn_replay_copy_kernel, dim3(n), dim3(256), 0, st, ca);
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }
 
@@ -2142,10 +2136,10 @@ extern "C" int cn_episode_log_add(const cn_episode_log* log, const uint8_t* done
     if (!log || !log->rows || !log->n_dev || !log->tot_dev || !done || !counters || !last_return || !transitions)
         return td3_fail(CN_ERR_ARG, "cn_episode_log_add: null argument");
     if (n < 1 || counter_cols < 14 || log->max_rows < 0) return td3_fail(CN_ERR_ARG, "cn_episode_log_add: n < 1, fewer than 14 counter columns or max_rows < 0");
-    DevScope scope(device);
+    DeviceScope scope(device);
     EpisodeLogArgs ea;
     ea.log = *log; ea.done = done; ea.counters = counters; ea.cols = counter_cols; ea.ret = last_return; ea.trans = transitions; ea.launch = launch; ea.n = n;
     hipLaunchKernelGGL(cn_episode_log_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, ea);
-    TD3CHK(hipGetLastError());
+    CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }

@@ -1,5 +1,5 @@
-"""A float64 statement of the fused TD3 actor (actor_tile in csrc/crowdnav_kernel.hip: cn_actor_forward and the policy phase of
-cn_rollout_policy) and of the output stage cn_policy_tail, with the error bounds the GPU tests hold the float32 kernels to.
+"""A float64 statement of the fused TD3 actor (actor_tile in csrc/crowdnav_actor.h: cn_actor_forward, csrc/crowdnav_actor.hip, and the policy
+phase of cn_rollout_policy) and of the output stage cn_policy_tail, with the error bounds the GPU tests hold the float32 kernels to.
 No kernel code and no libcrowdnav: torch float64 for the network, numpy uint64 for the generator.
 
 The operation (crowdnav.td3.Actor, Agent.act):
