@@ -12,7 +12,8 @@
 
 #include "crowdnav_device.h"
 #include "crowdnav_host.h"
-#include "crowdnav_kernel.h"
+#include "crowdnav_actor.h"
+#include "crowdnav_lds.h"
 #include "crowdnav_variants.h"
 
 // every kernel that takes CnKParams, from the table (crowdnav_variants.h): declarations, then the functions in cn_kernel_info's order --
@@ -71,57 +72,11 @@ static void build_assoc_table(CnKParams& k, int16_t* tab)
     k.assoc_k1 = K1; k.assoc_fast = 1;
 }
 
-// regions A + B of the carve below: the simulators' scratch (idle while the world advances)
-// (a wide table, trk_cap > CN_MAX_TRACKS, lives in HBM: region A holds the end points only -- env_kernel_body, WIDE)
-static size_t lds_trk_slots(int trk_cap) { return trk_cap > CN_MAX_TRACKS ? 0 : (size_t)trk_cap; }
-static size_t lds_scratch_bytes(int R, int P, int K, int max_conf, int trk_cap, bool near_separate)
-{
-    size_t n = (size_t)(R - 1), mc = (size_t)max_conf;
-    size_t szA_pts = (10 * n + 7) & ~(size_t)7, szA_trk = 8 * (size_t)CN_TF_COUNT * lds_trk_slots(trk_cap);
-    size_t szA = szA_pts > szA_trk ? szA_pts : szA_trk;
-    size_t szB_g = (6 * n + 7) & ~(size_t)7;
-    size_t szB_c = 32 * mc + 8 * 64 + 8 * (size_t)(8 + 4 * K) + 4 * (size_t)CN_MAX_K;
-    size_t szB = szB_g > szB_c ? szB_g : szB_c;
-    if (szB < 8 * 64) szB = 8 * 64;
-    if (!near_separate && szB < 32 * (size_t)(P + 1)) szB = 32 * (size_t)(P + 1);
-    return szA + szB;
-}
-static size_t lds_bytes_impl(int R, int P, int K, int max_conf, int trk_cap, bool near_separate, int layout = 0, bool compact = false)
-{
-    // must mirror the carve in cn_env_kernel (compact: the 720-ray shape kernels' layout -- int16 end points, 12-byte confirmed
-    // objects, the pedestrians' velocities overlaid on region A)
-    size_t n = (size_t)(R - 1), mc = (size_t)max_conf;
-    size_t szA_pts = ((compact ? 6 : 10) * n + 7) & ~(size_t)7, szA_trk = 8 * (size_t)CN_TF_COUNT * lds_trk_slots(trk_cap);
-    size_t szA = szA_pts > szA_trk ? szA_pts : szA_trk;
-    size_t szB_g = (6 * n + 7) & ~(size_t)7;
-    size_t szC = compact ? ((12 * mc + 7) & ~(size_t)7) : 32 * mc;
-    size_t szB_c = szC + 8 * 64 + 8 * (size_t)(8 + 4 * K) + 4 * (size_t)CN_MAX_K;
-    size_t szB = szB_g > szB_c ? szB_g : szB_c;
-    if (szB < 8 * 64) szB = 8 * 64;
-    if (!near_separate && szB < 32 * (size_t)(P + 1)) szB = 32 * (size_t)(P + 1);   // near-pedestrian list overlaid on region B
-    size_t Wn = (n + 63) >> 6;
-    size_t b = szA + szB;
-    b += 8 * (size_t)(CN_NMASK * Wn);             // bit words
-    b += 8 * ((3 * Wn + 1) / 2);                  // wbase
-    b += 8 * (size_t)(2 * P + 2) * (compact ? 1 : 2);   // ped, pedv (compact: pedv inside region A)
-    if (compact && 8 * (size_t)(2 * P + 2) > szA) return (size_t)1 << 30;
-    if (near_separate) b += 32 * (size_t)(P + 1); // near-pedestrian list in its own region
-    if (layout == CN_LAYOUT_REALWORLD) b = ((b + 15) & ~(size_t)15) + 12 * n + 16;   // filtered list, gradients, types (12 bytes per ray)
-    return (b + 15) & ~(size_t)15;
-}
-
-// The near-pedestrian list (ray loop only) gets its own LDS region when that costs no resident wavefront -- measured
-// 1.5 % faster than sharing region B with the gradients -- and is overlaid on region B otherwise (100 pedestrians x 720
-// rays: 8 instead of 7 wavefronts per CU).
-static int waves_per_cu(size_t lds) { size_t w = (160 * 1024) / (lds ? lds : 1); return (int)(w > 16 ? 16 : w); }
-int cn_near_separate(int R, int P, int K, int max_conf, int trk_cap)
-{
-    return waves_per_cu(lds_bytes_impl(R, P, K, max_conf, trk_cap, true)) ==
-           waves_per_cu(lds_bytes_impl(R, P, K, max_conf, trk_cap, false));
-}
+// An environment's LDS working set is crowdnav_lds.h's map, for cn_create's sizes (env_kernel_body carves the same regions)
+int cn_near_separate(int R, int P, int K, int max_conf, int trk_cap) { return cn_lds_near_separate(R, P, K, max_conf, trk_cap); }
 size_t cn_lds_bytes(int R, int P, int K, int max_conf, int trk_cap)
 {
-    return lds_bytes_impl(R, P, K, max_conf, trk_cap, cn_near_separate(R, P, K, max_conf, trk_cap) != 0);
+    return cn_lds_map(R - 1, P, K, max_conf, cn_lds_trk_slots(trk_cap), cn_near_separate(R, P, K, max_conf, trk_cap), false, false).total;
 }
 
 extern "C" int cn_abi_version(void) { return CN_ABI_VERSION; }
@@ -247,7 +202,7 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
         return fail(CN_ERR_CONFIG, "cn_create: wheel_accel must be >= 0 and needs obs_layout 0, the plain simulator (ped_contact 0, ped_mode 0 / 1) "
                                    "and a positive wheel_separation");
     if (c.ped_mode == 2 && (c.ped_contact || c.obs_layout != CN_LAYOUT_RISK || !(c.sf_tau > 0.0) || !(c.sf_B > 0.0) ||
-                            !(c.sf_wall_B > 0.0) || !(c.sf_goal_eps >= 0.0) || c.sf_tick_ms < 0 || 64 * (size_t)c.n_peds > 16 * (size_t)(c.n_rays - 1)))
+                            !(c.sf_wall_B > 0.0) || !(c.sf_goal_eps >= 0.0) || c.sf_tick_ms < 0 || 64 * (size_t)c.n_peds > cn_lds_sim_scratch(c.n_rays)))
         return fail(CN_ERR_CONFIG, "cn_create: ped_mode 2 (social force) needs obs_layout 0, ped_contact 0, positive sf_tau / sf_B / "
                                    "sf_wall_B and n_peds <= (n_rays - 1) / 4");
     // the pedestrians' repulsion is summed on a 2^-36 grid (include/crowdnav.h): exact while the sum stays below 2^16
@@ -277,10 +232,13 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
     // tools/fuzz_parity.py found a 36-pedestrian gt world with more than 32 of them in range)
     h->trk_cap = c.track_capacity ? c.track_capacity : ((P <= 40 && !(c.risk_mode == CN_RISK_GT && P > 32)) ? 32 : 64);
     h->wide = h->trk_cap > CN_MAX_TRACKS;
-    h->lds = lds_bytes_impl(R, P, K, h->max_conf, h->trk_cap, cn_near_separate(R, P, K, h->max_conf, h->trk_cap) != 0, c.obs_layout);
+    const int near_sep = cn_near_separate(R, P, K, h->max_conf, h->trk_cap);
+    const bool rw_lists = c.obs_layout == CN_LAYOUT_REALWORLD;
+    const CnLdsMap M = cn_lds_map(R - 1, P, K, h->max_conf, cn_lds_trk_slots(h->trk_cap), near_sep, false, rw_lists);
+    h->lds = M.total;
     if (c.ped_contact && c.obs_layout != CN_LAYOUT_RISK)
         return fail(CN_ERR_CONFIG, "cn_create: ped_contact is built for the risk observation layout (obs_layout 0) only");
-    if (c.ped_contact && 32 * (size_t)P > 16 * (size_t)(R - 1))   // contact corrections: 4 doubles per pedestrian in LDS regions A + B
+    if (c.ped_contact && 32 * (size_t)P > cn_lds_sim_scratch(R))   // contact corrections: 4 doubles per pedestrian in LDS regions A + B
         return fail(CN_ERR_CONFIG, "cn_create: ped_contact needs n_peds <= (n_rays - 1) / 2");
     if (h->lds > 160 * 1024) { return fail(CN_ERR_CONFIG, "cn_create: per-env working set exceeds 160 KiB of LDS"); }
     // tables
@@ -324,19 +282,21 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
     k.scan_f32 = c.scan_f32; k.waypoint_reward = c.waypoint_reward; k.wheel_accel = c.wheel_accel; k.wheel_sep = c.wheel_separation;
     k.sf_tau = c.sf_tau; k.sf_A = c.sf_A; k.sf_B = c.sf_B; k.sf_wall_A = c.sf_wall_A; k.sf_wall_B = c.sf_wall_B;
     k.sf_goal_eps2 = c.sf_goal_eps * c.sf_goal_eps; k.sf_tick_ms = c.sf_tick_ms > 0 ? c.sf_tick_ms : 10;
-    // pair matrix G [P][P] + next state + goal records in the simulator's LDS scratch (regions A + B, 16 (R - 1) bytes)?
+    // pair matrix G [P][P] + next state + goal records in the simulator's LDS scratch (regions A + B)?
     {   // dense social force: the near-pair list behind next / aux [8 P] and acc [2 P] doubles of the scratch
-        const size_t scr = lds_scratch_bytes(R, P, K, h->max_conf, h->trk_cap, cn_near_separate(R, P, K, h->max_conf, h->trk_cap) != 0);
-        const size_t used = 80 * (size_t)P;
+        const size_t scr = M.szA + M.szB, used = 80 * (size_t)P;
         size_t cap = scr > used ? (scr - used) / 2 : 0;
         k.sf_pair_cap = (c.ped_mode == 2 && P <= 128) ? (int32_t)(cap > 60000 ? 60000 : cap) : 0;
-        k.sf_reserved = 0;
     }
-    k.sf_pair_matrix = (c.ped_mode == 2 && P >= 2 && P < 256 && 8 * (size_t)P * P + 64 * (size_t)P + (size_t)P * (P - 1) + 16 <= 16 * (size_t)(R - 1)) ? 1 : 0;
-    k.near_sep = cn_near_separate(R, P, K, h->max_conf, h->trk_cap);
-    // the kernels compiled for the headline shape assume exactly these six values (crowdnav_kernel.hip, SHAPE == 360)
-    h->shape360 = R == 360 && P == 20 && K == 8 && h->max_conf == 91 && h->trk_cap == 32 && k.near_sep == 1 && !getenv("CN_NO_SHAPE_KERNELS");
-    h->shape720 = R == 720 && P == 100 && K == 8 && h->max_conf == 181 && h->trk_cap == 64 && k.near_sep == 0 && !getenv("CN_NO_SHAPE_KERNELS")
+    k.sf_pair_matrix = (c.ped_mode == 2 && P >= 2 && P < 256 && 8 * (size_t)P * P + 64 * (size_t)P + (size_t)P * (P - 1) + 16 <= cn_lds_sim_scratch(R)) ? 1 : 0;
+    k.near_sep = near_sep;
+    // the kernels compiled for a shape assume exactly the six values of its row (crowdnav_lds.h; env_kernel_body, SHAPE != 0)
+    auto is_shape = [&](const CnShape& s) {
+        return R == s.R && P == s.P && K == s.K && h->max_conf == s.max_conf && h->trk_cap == s.trk_cap && near_sep == s.near_sep &&
+               !getenv("CN_NO_SHAPE_KERNELS");
+    };
+    h->shape360 = is_shape(cn_shapes[CN_SHAPE_360]);
+    h->shape720 = is_shape(cn_shapes[CN_SHAPE_720])
                   && c.room_half + c.lidar_max + 1.0 < 32.0;       // the _s720 kernels keep end points as int16 thousandths
     // Four environments per workgroup for the 360-ray step kernels when the whole launch is resident at once (n_envs <= 16 wavefronts
     // x CUs): a quarter of the workgroups for the dispatcher to create, + 2-3 % in every decomposition at 4096 envs; with several
@@ -349,7 +309,7 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
     h->wpb4 = 4;
     if (getenv("CN_X2")) h->x2 = atoi(getenv("CN_X2")) ? 1 : 0;
     if (getenv("CN_WPB")) { h->wpb4 = atoi(getenv("CN_WPB")); if (h->wpb4 != 2 && h->wpb4 != 4 && h->wpb4 != 8 && h->wpb4 != 16) h->wpb4 = 0; }
-    if (h->shape720) h->lds_shape = lds_bytes_impl(R, P, K, h->max_conf, h->trk_cap, false, c.obs_layout, true);
+    if (h->shape720) h->lds_shape = cn_lds_map(R - 1, P, K, h->max_conf, cn_lds_trk_slots(h->trk_cap), near_sep, true, rw_lists).total;
     k.max_conf = h->max_conf; k.trk_cap = h->trk_cap; k.env_index_base = c.env_index_base; k.seed = c.seed;
     k.room_half = c.room_half; k.ped_radius = c.ped_radius; k.ped_vmax = c.ped_vmax; k.robot_clearance = c.robot_clearance;
     k.lidar_min = c.lidar_min; k.lidar_max = c.lidar_max; k.lidar_offset_x = c.lidar_offset_x;
@@ -398,7 +358,7 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
         // actor's 16-row tile is laid out compactly over them between two steps), + the workgroup's actions
         // (this world's policy kernel: the 720-ray shape's has the compact layout)
         h->pol_wave_lds = (lds_of(h, kernel_of(h, CN_FORM_POLICY)) + 15) & ~(size_t)15;
-        const size_t tile = sizeof(float) * (16 * (size_t)(((h->D + 31) & ~31) + 1) + 16 * 257);
+        const size_t tile = actor_tile_bytes((h->D + 31) & ~31);
         const char* pe_env = getenv("CN_POL_ENVS");             // experiments: CN_POL_ENVS=8 forces the 8-environment workgroups
         // (cn_policy_kernel_rw is compiled for 8 waves: the RW observation needs more than the 128 vector registers a 16-wave workgroup leaves a wave)
         for (int pe = ((pe_env && atoi(pe_env) == 8) || h->cfg.obs_layout == CN_LAYOUT_REALWORLD) ? 8 : 16; pe >= 8 && !h->pol_lds; pe -= 8) {

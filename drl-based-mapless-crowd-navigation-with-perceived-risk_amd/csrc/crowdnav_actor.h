@@ -17,6 +17,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define ACT_H 256
 #define ACT_M 16
 #define ACT_THREADS 512            /* cn_actor_kernel: 8 waves */
+// A tile's LDS: X [16][Dp + 1] (layer 2 reuses it), then H [16][257].  actor_tile carves it with these leading dimensions and every
+// launch asks for actor_tile_bytes (in size_t: an observation too wide for a tile is refused, not wrapped).
+#define ACT_LDX(Dp) ((Dp) + 1)
+#define ACT_LDH (ACT_H + 1)
+__host__ __device__ constexpr size_t actor_tile_bytes(size_t Dp) { return sizeof(float) * ACT_M * (ACT_LDX(Dp) + ACT_LDH); }
 
 // Weights arrive PACKED in the order the matrix cores consume them (cn_actor_pack_kernel, crowdnav_actor.hip): for a
 // layer with K inputs (a multiple of 32) and 256 outputs, block b = 8 k-steps of 4, wave w = 32 columns, q = a pair of k-steps,
@@ -136,7 +141,7 @@ __device__ __forceinline__ void actor_layer(const float* __restrict__ A, int lda
 }
 
 // One tile of 16 environments through the actor (TD3:96-106 + 209-215), by the NW waves of a workgroup (all of its threads must
-// call this).  obs / action: the tile's first row; n_live: rows of the tile that exist; act_sm: 16 (Dp + 1) + 16 * 257 floats of
+// call this).  obs / action: the tile's first row; n_live: rows of the tile that exist; act_sm: actor_tile_bytes(Dp) of
 // LDS.  Ends with the actions in global memory (the caller synchronises before anyone reads them).
 // `active` (wave-uniform): the policy kernel's workgroups have 16 waves; the eight that do not take part in the tile only keep
 // the barrier count.  action2: a second copy of the actions (LDS, or NULL).
@@ -151,7 +156,7 @@ __device__ __forceinline__ void actor_tile(const float* __restrict__ obs, int n_
         float* act_sm, const bool active = true, const int tid_in = -1)
 {
     static_assert(NW == 8, "packed weights: 8 waves x 32 columns");
-    const int ldx = Dp + 1, ldh = ACT_H + 1;
+    const int ldx = ACT_LDX(Dp), ldh = ACT_LDH;
     float* X = act_sm;                 // [16][Dp + 1]; layer 2 writes its output here (the observations are dead by then)
     float* H = X + ACT_M * ldx;        // [16][257] hidden activations of layer 1
     const int tid = tid_in >= 0 ? tid_in : (int)threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;

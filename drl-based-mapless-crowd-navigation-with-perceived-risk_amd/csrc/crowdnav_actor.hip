@@ -124,7 +124,7 @@ extern "C" int cn_actor_forward(const cn_actor_weights* w, const float* obs, flo
         return fail(CN_ERR_CONFIG, "cn_actor_forward: hidden must be 256 and obs_dim_padded a multiple of 32 (the packed layout of cn_actor_pack_weights)");
     if (n == 0) return CN_OK;
     const int Dp = w->obs_dim_padded;
-    const size_t lds = sizeof(float) * (16 * (size_t)(Dp + 1) + 16 * 257);         // X (layer 2 reuses it), H
+    const size_t lds = actor_tile_bytes(Dp);
     if (lds > 160 * 1024) return fail(CN_ERR_CONFIG, "cn_actor_forward: observation too wide for one LDS tile");
     int dev = device;
     if (dev < 0) CN_HIPCHK(fail, hipGetDevice(&dev));
@@ -196,7 +196,7 @@ extern "C" int cn_actor_pop_create(const cn_actor_pop_member* members, int n_mem
     if (n_members < 1 || n_members > CN_ACTOR_POP_MAX) return fail(CN_ERR_ARG, f + ": n_members must be 1 ... 64");
     if (obs_dim < 1) return fail(CN_ERR_CONFIG, f + ": obs_dim must be at least 1");
     const int64_t Dp64 = ((int64_t)obs_dim + 31) / 32 * 32;
-    const size_t lds = sizeof(float) * (16 * ((size_t)Dp64 + 1) + 16 * 257);       // cn_actor_forward's tile: X (layer 2 reuses it), H
+    const size_t lds = actor_tile_bytes((size_t)Dp64);       // cn_actor_forward's tile
     const int P = n_members, D = obs_dim, Dp = (int)Dp64;
     if (lds > 160 * 1024) return fail(CN_ERR_CONFIG, f + ": obs_dim: observation too wide for one LDS tile");
     int tiles = 0;

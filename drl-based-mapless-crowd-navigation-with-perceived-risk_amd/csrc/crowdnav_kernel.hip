@@ -13,7 +13,7 @@
 // /root/reference/turtlebot3_rl_sim/src).  Gazebo owns the physics in the reference; the
 // simulator here is defined in DESIGN.md and restated independently by the CPU oracle (test infrastructure).
 #include "crowdnav_device.h"
-#include "crowdnav_kernel.h"
+#include "crowdnav_lds.h"
 #include "crowdnav_variants.h"
 #include "crowdnav_actor.h"
 
@@ -75,6 +75,7 @@ struct XMail { double px, py, sy, cy, ox, oy, smin1, pad; int nnear, wall_x, wal
 #define CN_NAN __longlong_as_double(0x7ff8000000000000LL)
 typedef unsigned long long u64;
 enum { M_NONE = 0, M_ZERO, M_EQ, M_NNONE, M_NZERO, M_ISW, M_ISO, M_ALIAS, M_BRK, M_SEG, M_KW, M_KO, M_OCC, M_COUNT };
+static_assert(M_COUNT == CN_NMASK, "the LDS map (crowdnav_lds.h) holds one bit-word array per mask");
 
 namespace {
 // The kernel parameters (~110 dwords) are read from the KERNARG SEGMENT where they are needed, through a constant-address-
@@ -2751,10 +2752,11 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         // loads of these six fields fold to constants everywhere below (the loads are invariant, so one assumption covers every
         // use), which turns the LDS map into immediates, the word loops (W = 6 / 12) into straight-line code and frees the scalar
         // registers that held the map.  launch() only picks an _s360 / _s720 kernel for a handle whose configuration IS that shape.
-        constexpr int SR = SHAPE == 360 ? 360 : 720, SP = SHAPE == 360 ? 20 : 100, SMC = SHAPE == 360 ? 91 : 181, STC = SHAPE == 360 ? 32 : 64,
-                      SNS = SHAPE == 360 ? 1 : 0;
-        static_assert(SHAPE == 360 || SHAPE == 720, "compiled shapes");
-        __builtin_assume(p->R == SR); __builtin_assume(p->P == SP); __builtin_assume(p->K == 8);
+        constexpr int ROW = SHAPE == 360 ? CN_SHAPE_360 : CN_SHAPE_720;                   // (crowdnav_lds.h: cn_create tests the same row)
+        constexpr int SR = cn_shapes[ROW].R, SP = cn_shapes[ROW].P, SK = cn_shapes[ROW].K, SMC = cn_shapes[ROW].max_conf, STC = cn_shapes[ROW].trk_cap,
+                      SNS = cn_shapes[ROW].near_sep;
+        static_assert(SHAPE == SR, "compiled shapes");
+        __builtin_assume(p->R == SR); __builtin_assume(p->P == SP); __builtin_assume(p->K == SK);
         __builtin_assume(p->max_conf == SMC); __builtin_assume(p->trk_cap == STC); __builtin_assume(p->near_sep == SNS);
     }
     if constexpr (!FUSED) {
@@ -2766,7 +2768,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
     // 13.2 KB leaves 12.  Three changes, none of which touches a value: (1) end points as int16 thousandths (|x| <= 32.767 m: cn_create
     // checks the room), (2) confirmed objects as integer thousandths + byte flags (12 instead of 32 bytes each), (3) the pedestrians'
     // velocities live in region A, which is idle whenever the simulator runs, and go to the state record before the observation
-    // overwrites them (a reset brings them back for its settle advance).  crowdnav_abi.hip lds_bytes_impl(compact) mirrors the carve.
+    // overwrites them (a reset brings them back for its settle advance).  cn_lds_map(compact) is this layout for the host.
     constexpr bool CMP = SHAPE == 720;
     static_assert(!CMP || (!EXT && !TWO && LAYOUT == 0 && !GT && SIM == 0), "the compact layout is the 720-ray shape kernels' own");
     // where this step's outputs go: the caller's buffers, or (FUSED) slot t of its trajectory buffers (stride 0 = in place)
@@ -2779,19 +2781,20 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
     Lds L;
     RwLds RQ = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     {
-        // LDS map.  Region A: end points (integer thousandths) | tracker table.
+        // LDS map: a running pointer over crowdnav_lds.h's sizes, in cn_lds_map's order (the host sizes the
+        // launch from that function; tests/test_lds_map.py walks it).  Region A: end points (integer thousandths) | tracker table.
         // Region B: gradients + alias sources | bbox staging | confirmed objects, CP, observation tail.
-        const size_t szA_pts = (size_t)((CMP ? 6 : 10) * n + 7) & ~(size_t)7;
-        const size_t szA_trk = WIDE ? 0 : 8 * (size_t)(CN_TF_COUNT * p->trk_cap);
+        const size_t szA_pts = CN_LDS_SZ_PTS(CMP, n);
+        const size_t szA_trk = WIDE ? 0 : CN_LDS_SZ_TRK(p->trk_cap);
         L.tcap = p->trk_cap;
         const size_t szA = szA_pts > szA_trk ? szA_pts : szA_trk;
         const size_t mc = (size_t)p->max_conf;
-        const size_t szB_g = (size_t)(6 * n + 7) & ~(size_t)7;
-        const size_t szC = CMP ? ((12 * mc + 7) & ~(size_t)7) : 32 * mc;          // the confirmed-object arrays
-        const size_t szB_c = szC + 8 * 64 + 8 * (size_t)(8 + 4 * K) + 4 * (size_t)CN_MAX_K;
+        const size_t szB_g = CN_LDS_SZ_GRAD(n);
+        const size_t szC = CN_LDS_SZ_CONF(CMP, mc);          // the confirmed-object arrays
+        const size_t szB_c = szC + CN_LDS_SZ_CTAIL(K);
         size_t szB = szB_g > szB_c ? szB_g : szB_c;
-        if (szB < 8 * 64) szB = 8 * 64;
-        if (!p->near_sep && szB < 32 * (size_t)(P + 1)) szB = 32 * (size_t)(P + 1);   // near-pedestrian list overlaid on B
+        if (szB < CN_LDS_SZ_STAGE) szB = CN_LDS_SZ_STAGE;
+        if (!p->near_sep && szB < CN_LDS_SZ_NEAR(P)) szB = CN_LDS_SZ_NEAR(P);   // near-pedestrian list overlaid on B
         char* A = smem;
         char* B = A + szA;
         char* Cw = B + szB;
@@ -2808,18 +2811,18 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         L.cpv = (double*)(B + szC);
         L.tail = L.cpv + 64;
         L.kidx = (int*)(L.tail + (8 + 4 * K));
-        const int Wn = (n + 63) >> 6;
+        const int Wn = CN_LDS_WORDS(n);
         L.wstride = Wn;
-        L.w64 = (u64*)Cw; Cw += 8 * (size_t)(M_COUNT * Wn);
-        L.wbase = (int*)Cw; Cw += 8 * (size_t)((3 * Wn + 1) / 2);
-        L.ped = (double*)Cw; Cw += 8 * (size_t)(2 * P + 2);
+        L.w64 = (u64*)Cw; Cw += CN_LDS_SZ_W64(Wn);
+        L.wbase = (int*)Cw; Cw += CN_LDS_SZ_WBASE(Wn);
+        L.ped = (double*)Cw; Cw += CN_LDS_SZ_PED(P);
         if constexpr (CMP) L.pedv = (double*)A;         // (3) above: 8 (2 P + 2) <= szA
-        else { L.pedv = (double*)Cw; Cw += 8 * (size_t)(2 * P + 2); }
+        else { L.pedv = (double*)Cw; Cw += CN_LDS_SZ_PED(P); }
         L.nearp = p->near_sep ? (double*)Cw : (double*)B;   // ray loop only: region B is dead until the gradients are written
-        if (p->near_sep) Cw += 32 * (size_t)(P + 1);
+        if (p->near_sep) Cw += CN_LDS_SZ_NEAR(P);
         L.gtrk = p->trk + (size_t)env * CN_TF_COUNT * p->trk_cap;
         if constexpr (WIDE) L.gcpv = p->trk + (size_t)p->N * CN_TF_COUNT * p->trk_cap + (size_t)env * p->trk_cap;
-        if constexpr (LAYOUT == 2) {   // the real-world layout's own lists: 12 bytes per ray (cn_lds_bytes adds them)
+        if constexpr (LAYOUT == 2) {   // the real-world layout's own lists: 12 bytes per ray (cn_lds_map: rw)
             char* Rw = (char*)(((size_t)Cw + 15) & ~(size_t)15);
             RQ.g = (int*)Rw; Rw += 4 * (size_t)n;
             RQ.fi = (unsigned short*)Rw; Rw += 2 * (size_t)n;
