@@ -3063,7 +3063,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         }
         cold_settle();
         if (!do_reset && !ph_rew) {
-            if (lane == 0) io_done()[env] = (uint8_t)done;           // get_state returns (state, self.done) (ENV:1044)
+            if (ph_obs && lane == 0) io_done()[env] = (uint8_t)done; // get_state returns (state, self.done) (ENV:1044); CN_PHASE_PRE alone returns nothing
             if (ph_obs && io_topk() && lane < K) io_topk()[(size_t)env * K + lane] = LAYOUT != 0 ? -1 : L.kidx[lane];
         } else
         if (!do_reset) {

@@ -203,7 +203,10 @@ typedef struct cn_external_io {
                                   *   CN_PHASE_GET_STATE    Env.get_state(scan, step_counter, action) -> obs, done (ENV:245-1044)
                                   *   CN_PHASE_REWARD       Env.compute_reward(state, step_counter, done) -> reward, done
                                   *                         (ENV:1046-1162): reads state[R-1], state[R] from obs_f64 (or obs)
-                                  *                         and `done` as INPUTS, position from odom[0..1] */
+                                  *                         and `done` as INPUTS, position from odom[0..1]
+                                  * A launch writes only what its pieces return: CN_PHASE_PRE alone writes no output.  Held by
+                                  * tests/test_gpu_external.py: every grouping of the pieces leaves what phase 0 leaves and what
+                                  * the reference returned, and each piece touches only its own part of the state. */
 } cn_external_io;
 enum { CN_PHASE_ALL = 0, CN_PHASE_PRE = 1, CN_PHASE_GET_STATE = 2, CN_PHASE_REWARD = 4 };
 
