@@ -1,4 +1,4 @@
-"""What the TD3, DDPG, DQN and SAC agents share on the way to libcrowdnav's fused learners (csrc/crowdnav_td3.hip): the network
+"""What the TD3, DDPG, DQN and SAC agents share on the way to libcrowdnav's fused learners (csrc/crowdnav_td3.hip, crowdnav_ddpg.hip, crowdnav_dqn.hip, crowdnav_sac.hip): the network
 pointers, views of the library's device memory, and the owners of a learner handle and of a population's handles."""
 import ctypes as C
 

@@ -1,5 +1,5 @@
 """DDPG, the reference's baseline learner (turtlebot3_rl_sim/src/ddpg.py, start_ddpg_training.py), in PyTorch-ROCm with the
-update also available as libcrowdnav's cn_ddpg_update (csrc/crowdnav_td3.hip, 8 launches).
+update also available as libcrowdnav's cn_ddpg_update (csrc/crowdnav_ddpg.hip, 8 launches).
 
 What it keeps from the reference:
 - networks: td3.Actor / td3.Critic (the same 3 x Linear(256) and sigmoid*0.22 / tanh*2.0 heads as TD3, DDPG:67-109) with

@@ -1,5 +1,5 @@
 """DQN, the reference's discrete learner (turtlebot3_rl_sim/src/deepq.py, memory.py, start_dqn_training.py), in PyTorch-ROCm with
-action selection and the update also available as libcrowdnav's cn_dqn_act / cn_dqn_update (csrc/crowdnav_td3.hip).
+action selection and the update also available as libcrowdnav's cn_dqn_act / cn_dqn_update (csrc/crowdnav_dqn.hip).
 
 What it keeps from the reference:
 - network (deepq.py:102-127, TRAIN_DQN:55-57): Linear(361, 300) - ReLU - Linear(300, 300) - ReLU - Linear(300, 3), weights

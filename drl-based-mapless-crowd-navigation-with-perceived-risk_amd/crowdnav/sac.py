@@ -1,5 +1,5 @@
 """SAC, the reference's fourth neural learner (turtlebot3_rl_sim/src/sac.py, start_sac_training.py), in PyTorch-ROCm with the
-update also available as libcrowdnav's cn_sac_update and action selection as cn_sac_act (csrc/crowdnav_td3.hip).
+update also available as libcrowdnav's cn_sac_update and action selection as cn_sac_act (csrc/crowdnav_sac.hip).
 
 start_sac_training.py cannot run (it passes batch_size, memory_size, discount_factor into slots named batch_size, discount_factor,
 buffer_size, and network_inputs = 54); sac.py itself can.  Every value is taken AT ITS NAME -- batch 64, memory 1e6, gamma 0.99 --

@@ -735,7 +735,7 @@ def build_parser():
     ap.add_argument("--reset-mode", default="next", choices=["next", "same"], help="next: the fast kernel, reset launches masked out of the replay; same: same-call reset + final_obs")
     ap.add_argument("--graphs", type=int, default=1, help="1: capture the TD3 update into hipGraphs (Agent.enable_graphs; td3 only; rejected for qlearn / sarsa)")
     ap.add_argument("--learner", default="torch", choices=["torch", "fused"], help="torch: the PyTorch update (td3: eager / hipGraph; ddpg: eager); "
-                    "fused: cn_td3_update / cn_ddpg_update (csrc/crowdnav_td3.hip)")
+                    "fused: cn_td3_update / cn_ddpg_update (csrc/crowdnav_td3.hip, crowdnav_ddpg.hip)")
     ap.add_argument("--actor-final-init", type=float, default=None, help="NOT the reference: U(+-x) initialisation of the actor's output layer (e.g. 0.003)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--population", type=int, default=0, help="P > 0: train P independent TD3 agents, seeds --seed ... --seed + P - 1, their updates "

@@ -14,8 +14,12 @@
 # and policy kernels (their rows name the unit), compiled with -mllvm -disable-machine-licm: see the note above the kernel definitions.
 # The units only spread the compile over processes and flags.  crowdnav_lds.h holds every size of an environment's LDS working
 # set once: the kernels carve with them, crowdnav_abi.hip sizes the launches from cn_lds_map, which composes them.  crowdnav_abi.hip is the environment's host side; the other files each
-# hold a subsystem's kernels next to the host code that launches them: the TD3 actor and the population's actors, the fused learners,
-# the tabular learners, the population's recorder (its bodies, crowdnav_record.h, are shared with crowdnav_td3.hip's replay kernels).
+# hold a subsystem's kernels next to the host code that launches them: the TD3 actor and the population's actors, the tabular
+# learners, the population's recorder (its bodies, crowdnav_record.h, are shared with crowdnav_replay.hip's kernels: one learner's
+# replay writes and episode log), and the fused learners, a unit each -- crowdnav_td3.hip (with the population), crowdnav_ddpg.hip,
+# crowdnav_dqn.hip, crowdnav_sac.hip -- around crowdnav_gemm.hip, the only unit that defines the GEMM and prep kernels they all
+# launch: it exports host launchers (crowdnav_learner.h, with the learners' host scaffold; crowdnav_learner_device.h holds the
+# device helpers that more than one of these units inlines).
 set -euo pipefail
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="$HERE/../lib"
@@ -30,7 +34,12 @@ UNITS=(         # object, source, flags of its own
   "k5    crowdnav_kernel.hip      -DCN_TU=5 -mllvm -disable-machine-licm"
   "abi   crowdnav_abi.hip"
   "actor crowdnav_actor.hip"
+  "gemm  crowdnav_gemm.hip"
   "td3   crowdnav_td3.hip"
+  "ddpg  crowdnav_ddpg.hip"
+  "dqn   crowdnav_dqn.hip"
+  "sac   crowdnav_sac.hip"
+  "replay crowdnav_replay.hip"
   "tab   crowdnav_tab.hip"
   "rec   crowdnav_pop_record.hip"
 )

@@ -1,6 +1,6 @@
 // crowdnav_host.h -- what the host sides of libcrowdnav.so share (host code only): the device scope, the HIP check, the environment
 // handle and the environment's error channel.  The library has three error channels -- cn_last_error (crowdnav_abi.hip; the actor's
-// and the population recorder's entry points report there too), cn_td3_last_error (crowdnav_td3.hip), cn_tab_last_error
+// and the population recorder's entry points report there too), cn_td3_last_error (crowdnav_gemm.hip: every fused learner's, declared in crowdnav_learner.h), cn_tab_last_error
 // (crowdnav_tab.hip) -- and every entry point reports to one of them through that channel's fail function.
 #pragma once
 #include <hip/hip_runtime.h>

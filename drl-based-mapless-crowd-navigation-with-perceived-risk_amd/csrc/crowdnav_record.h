@@ -1,5 +1,5 @@
 // crowdnav_record.h -- the collection loop's bookkeeping on the device: the bodies of cn_replay_write's and cn_episode_log_add's
-// kernels (crowdnav_td3.hip, one member per launch) and of cn_pop_record's (crowdnav_pop_record.hip, member = blockIdx.z).  Both
+// kernels (crowdnav_replay.hip, one member per launch) and of cn_pop_record's (crowdnav_pop_record.hip, member = blockIdx.z).  Both
 // instantiate the SAME text, which is what makes the population's recorder equal the solo calls bit for bit: the slots, the order of
 // the float64 sums and every conversion exist once.  What differs between the two is where a row's inputs come from, and that is a
 // functor: the keep flag (a byte array or NULL / the inverse of `resetting`) and the episode record (the [n][14] counters and the

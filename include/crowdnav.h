@@ -330,7 +330,7 @@ int cn_actor_pop_forward(cn_actor_pop_handle h, const uint64_t* counters, int ad
 int cn_actor_pop_weights(cn_actor_pop_handle h, int member, cn_actor_weights* out);
 
 /* The TD3 update -- Agent.learn (td3.py:225-285) with the hyper-parameters of start_td3_training.py:62-72 -- as a short chain
- * of launches on the caller's stream (crowdnav_td3.hip): the forward and backward GEMMs of the six 3-layer networks on the f32
+ * of launches on the caller's stream (crowdnav_td3.hip; the kernels: crowdnav_gemm.hip): the forward and backward GEMMs of the six 3-layer networks on the f32
  * matrix cores, weight gradients folded into the Adam step (a gradient never exists in memory), the TD target / MSE gradient /
  * heads evaluated inside those GEMMs, replay sampling and target-policy noise drawn on the device.  7 launches for the critic
  * step, 5 more when the actor and the targets move (every policy_delay-th update); through PyTorch the same update is ~150
@@ -439,7 +439,7 @@ const float* cn_td3_pop_batch_dev(cn_td3_pop_handle h, int member, int what); /*
 int cn_td3_pop_set_replay_sample(cn_td3_pop_handle h, int mode);
 
 /* The DDPG update -- Agent.learn of the reference's ddpg.py:198-243, the baseline learner of start_ddpg_training.py -- on the
- * same GEMM kernels as cn_td3_update (crowdnav_td3.hip), 8 launches per update.  One critic and one target critic, no policy
+ * same GEMM kernels as cn_td3_update (crowdnav_gemm.hip; the update: crowdnav_ddpg.hip), 8 launches per update.  One critic and one target critic, no policy
  * delay, no target-policy noise: y = r + (1 - d) gamma Q_t(s2, pi_t(s2)) (ddpg.py:219-222), critic loss mean((Q(s, a) - y)^2)
  * (:228-230), actor loss -mean Q(s, pi(s)) (:216-217) back-propagated through the critic's PRE-update weights (the actor step,
  * :233-235, precedes the critic step, :237-239; the gradient the actor loss leaves on the critic is discarded by the critic's
@@ -472,7 +472,7 @@ const float* cn_ddpg_loss_dev(cn_ddpg_handle h);    /* device pointer: the criti
 const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what);   /* as cn_td3_batch_dev, same indices; what = 4 (no noise): NULL */
 int cn_ddpg_set_replay_sample(cn_ddpg_handle h, int mode);    /* as cn_td3_set_replay_sample */
 
-/* DQN -- the reference's discrete learner (deepq.py, start_dqn_training.py) -- on the same GEMM kernels (crowdnav_td3.hip).
+/* DQN -- the reference's discrete learner (deepq.py, start_dqn_training.py) -- on the same GEMM kernels (crowdnav_gemm.hip; crowdnav_dqn.hip).
  * Network (deepq.py:102-127, TRAIN_DQN:55-57): Linear(obs_dim, H) - ReLU - Linear(H, H) - ReLU - Linear(H, 3), H = 300.
  * One update = learnOnMiniBatch (deepq.py:219-266) with Memory.getMiniBatch (memory.py:22-28):
  *   - B rows sampled on the device: with replacement by default (td3_prep_kernel's hash), or distinct as memory.py:23's
@@ -534,7 +534,7 @@ typedef struct cn_dqn_act_io {
 int cn_dqn_act(const cn_dqn_act_io* io, int device, void* stream);
 
 /* SAC -- the reference's fourth neural learner (sac.py; start_sac_training.py cannot run: its arguments are shifted by one, so
- * every value is taken AT ITS NAME) -- on the same GEMM kernels (crowdnav_td3.hip), float32.
+ * every value is taken AT ITS NAME) -- on the same GEMM kernels (crowdnav_gemm.hip; crowdnav_sac.hip), float32.
  * Networks: actor Linear(D, H) - ReLU - Linear(H, H) - ReLU - {mean_linear (H, 2), log_std_linear (H, 2)} (SAC:43-76);
  * Q Linear(D + 2, H) - ReLU - Linear(H, H) - ReLU - Linear(H, 1) (:109-125); V and its copy V_t Linear(D, Hv) - ReLU -
  * Linear(Hv, Hv) - ReLU - Linear(Hv, 1) with Hv = hidden_v (as the reference constructs them, :175-176, Hv = 2).

@@ -1,7 +1,7 @@
 """A float64 restatement of the reference's DQN update (deepq.py:219-266, memory.py:22-28, Keras fit / mse / RMSprop) and action
 selection, for the parity tests.  Variants that are NOT the reference are switches, so the tests can show the device rejects them.
 
-The second half states what the fused kernels (csrc/crowdnav_td3.hip) add to that: the plan dqn_prep_kernel makes (the drawn
+The second half states what the fused kernels (csrc/crowdnav_dqn.hip) add to that: the plan dqn_prep_kernel makes (the drawn
 Fisher-Yates shuffle, the replay row of every sample, the chunk marks and the flags), and one update as a td3_f64._Pass evaluation
 on the 2B stacked rows [s; s2] the device works on, so that td3_f64.propagated_bounds gives every quantity of it -- Q, Y, the six
 gradients of either chunk, both losses, the stepped weights and accumulators -- a float32 rounding bound (LAMBDA x the propagated

@@ -1,4 +1,4 @@
-"""The fused learners' replay sampling WITHOUT replacement (CN_SAMPLE_DISTINCT: cn_replay_row_distinct in csrc/crowdnav_td3.hip, stated
+"""The fused learners' replay sampling WITHOUT replacement (CN_SAMPLE_DISTINCT: cn_replay_row_distinct in csrc/crowdnav_learner_device.h, stated
 in include/crowdnav.h next to cn_td3_batch_dev) as a CPU statement: exact integers, NumPy uint64 for the hashes and the rows, Python
 ints for a, b and the key.  No kernel code and no libcrowdnav.
 

@@ -1,4 +1,4 @@
-"""The fused learners' replay sampling and TD3's target-policy noise (td3_prep_kernel in csrc/crowdnav_td3.hip, the replay path of
+"""The fused learners' replay sampling and TD3's target-policy noise (td3_prep_kernel in csrc/crowdnav_gemm.hip, the replay path of
 cn_td3_update and cn_ddpg_update) as a CPU statement: exact integers for the indices, float64 for the noise, and the allowance the
 GPU tests hold the float32 noise to.  No kernel code and no libcrowdnav: numpy uint64 for the generator (actor_f64's).
 

@@ -1,5 +1,5 @@
 """A float64 statement of one TD3 update (crowdnav.td3.Agent._update, td3.py:225-285 of the reference) and the tools the
-tests of the fused update (csrc/crowdnav_td3.hip) use to compare float32 kernel output with it:
+tests of the fused update (csrc/crowdnav_td3.hip; its kernels: csrc/crowdnav_gemm.hip) use to compare float32 kernel output with it:
 
 - the reference: forward passes, the TD target, the critics' MSE gradients, the actor's -mean Q1(s, pi(s)) gradient, Adam and
   the soft update, in float64 with torch autograd (no kernel code, no libcrowdnav);

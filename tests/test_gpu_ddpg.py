@@ -1,4 +1,4 @@
-"""cn_ddpg_update (csrc/crowdnav_td3.hip) on the device: the reference's learn() goldens (tests/golden/ddpg.npz), a float64
+"""cn_ddpg_update (csrc/crowdnav_ddpg.hip) on the device: the reference's learn() goldens (tests/golden/ddpg.npz), a float64
 statement of the same update with the gradients observed (tests/ddpg_f64.py), determinism, the replay path, argument checks,
 Adam across four updates against a float64 series (ddpg_f64.series_run), a hipGraph capture, the DDPG agent in the fused collection loop, and the trainer end to end.
 

@@ -1,4 +1,4 @@
-"""cn_dqn_act and cn_dqn_update (csrc/crowdnav_td3.hip) on the device against a float64 statement of the reference's DQN
+"""cn_dqn_act and cn_dqn_update (csrc/crowdnav_dqn.hip) on the device against a float64 statement of the reference's DQN
 (tests/dqn_f64.py): Q values, argmax and the epsilon draw; the update's gradients read back from an invertible RMSprop step, its
 two chunks, the target-net switch and copy; determinism, a hipGraph capture and the replay path.
 

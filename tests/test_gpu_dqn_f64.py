@@ -1,4 +1,4 @@
-"""cn_dqn_act and cn_dqn_update (csrc/crowdnav_td3.hip) held to the float64 statement of tests/dqn_f64.py at the tile edges of the
+"""cn_dqn_act and cn_dqn_update (csrc/crowdnav_dqn.hip) held to the float64 statement of tests/dqn_f64.py at the tile edges of the
 GEMMs only DQN instantiates (GATE = true, td3_wgrad_kernel<true> with the RMSprop epilogue, the I = 3 weight-gradient job, R = 2B
 stacked rows) and at the limits hidden = 4096 and batch = 4096.  Raw cn_dqn handles through crowdnav._abi, so hidden sizes above
 cn_dqn_act's 480 can be updated.  Every tolerance is a bound derived from the arithmetic (dqn_f64.bounded: float32 unit roundoff

@@ -1,4 +1,4 @@
-"""cn_sac_update and cn_sac_act (csrc/crowdnav_td3.hip) on the device: the reference's learn() goldens (tests/golden/sac.npz), a
+"""cn_sac_update and cn_sac_act (csrc/crowdnav_sac.hip) on the device: the reference's learn() goldens (tests/golden/sac.npz), a
 float64 statement of the per-row arithmetic (tests/sac_f64.py) at shapes around the tile edges, wrong variants that must be
 rejected, argument checks, determinism, the replay path, a hipGraph capture, the act kernel, and the trainer end to end.
 `-s` prints the worst error / bound of every quantity."""

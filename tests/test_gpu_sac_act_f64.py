@@ -1,4 +1,4 @@
-"""cn_sac_act (sac_act_kernel in csrc/crowdnav_td3.hip) held to the float64 statement of tests/sac_f64.py (act_pass: run()'s own
+"""cn_sac_act (sac_act_kernel in csrc/crowdnav_sac.hip) held to the float64 statement of tests/sac_f64.py (act_pass: run()'s own
 head, clamp, sample and squash statements) around every tile edge of the kernel: the 16-unit tile and the 32-unit padding of
 hidden, the four head lanes, the ragged block of 16 inputs, eight blocks in flight, the 16-row workgroup, the LDS limit and a grid
 of more than 4096 workgroups.  Raw calls through crowdnav._abi.CnSacActIO.  Every bound is td3_f64.propagated_bounds' (float32
