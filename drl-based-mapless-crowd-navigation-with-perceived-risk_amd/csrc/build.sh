@@ -12,7 +12,8 @@
 # crowdnav_kernel.hip (the environment's step, sequence and policy kernels) is compiled as five units (-DCN_TU=n).  Which kernel is
 # defined in which unit is a column of the kernel table, crowdnav_variants.h: unit 1 holds every one-step kernel, units 2-5 the sequence
 # and policy kernels (their rows name the unit), compiled with -mllvm -disable-machine-licm: see the note above the kernel definitions.
-# The units only spread the compile over processes and flags.  crowdnav_lds.h holds every size of an environment's LDS working
+# The units only spread the compile over processes and flags.  crowdnav_stages.h is the one table of the step kernel's stage stamps
+# (timing slots, the FAIR kernels' s_setprio levels; the profiling tools parse it).  crowdnav_lds.h holds every size of an environment's LDS working
 # set once: the kernels carve with them, crowdnav_abi.hip sizes the launches from cn_lds_map, which composes them.  crowdnav_abi.hip is the environment's host side; the other files each
 # hold a subsystem's kernels next to the host code that launches them: the TD3 actor and the population's actors, the tabular
 # learners, the population's recorder (its bodies, crowdnav_record.h, are shared with crowdnav_replay.hip's kernels: one learner's

@@ -15,6 +15,7 @@
 #include "crowdnav_device.h"
 #include "crowdnav_lds.h"
 #include "crowdnav_variants.h"
+#include "crowdnav_stages.h"
 #include "crowdnav_actor.h"
 
 // One wavefront per workgroup: the LDS processes a wave's DS instructions in issue order, so a
@@ -43,19 +44,19 @@ __device__ __forceinline__ void cn_setprio_uniform(int v)      // v: wave-unifor
     if (v == 0) __builtin_amdgcn_s_setprio(0); else if (v == 1) __builtin_amdgcn_s_setprio(1);
     else if (v == 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(3);
 }
-// at stage stamp k (a literal; FAIR is a template parameter of the enclosing function): the four level changes of a FAIR kernel
+// at stage stamp k (a row of CN_STAGES, crowdnav_stages.h; FAIR is a template parameter of the enclosing function): the level changes of
+// a FAIR kernel, at the rows that carry a fair_level
 // (SFENCE, a constexpr of the enclosing function: the oldest-first 720-ray kernel gets a scheduling fence where its fair sibling has an
 //  s_setprio -- the only difference between the two bodies, and the sibling allocates with 13 scalar spills where this one had 66)
-#define CN_FAIR_AT(k) do { if constexpr (FAIR) { if ((k) == 0) __builtin_amdgcn_s_setprio(3); else if ((k) == 7) __builtin_amdgcn_s_setprio(2); \
-                           else if ((k) == 11) __builtin_amdgcn_s_setprio(1); else if ((k) == 15) __builtin_amdgcn_s_setprio(0); } \
-                           else if constexpr (SFENCE) { if ((k) == 0 || (k) == 7 || (k) == 11 || (k) == 15) __builtin_amdgcn_s_setprio(0); } } while (0)
+#define CN_FAIR_AT(k) do { if constexpr (cn_stage_fair(k) != CN_FAIR_NONE) { \
+                           if constexpr (FAIR) __builtin_amdgcn_s_setprio(cn_stage_fair(k)); else if constexpr (SFENCE) __builtin_amdgcn_s_setprio(0); } } while (0)
 #ifdef CN_TIMING
 #define CN_ABLATE(bit) (p->ablate & (bit))   /* stage-skipping mask of tools/ablate.py: timing build only */
 /* bits 8..15 of the mask: stamp number + 1 at which every wavefront ENDS (tools/stage_instr.py: the PMC counters of a launch cut
    at stamp k are the instructions issued up to k, and the differences between consecutive cuts the dynamic ledger of the stages);
    bit 16: only the wavefronts of environments with (env & 3) != 0 end there (tools/pack_bound_probe.py: an upper bound for what
    sharing the narrow stages between the four environments of a workgroup could buy) */
-#define CN_T(k) do { CN_FAIR_AT(k); if (p->timing && lane == 0) p->timing[(size_t)env * 32 + (k)] = (long long)__builtin_amdgcn_s_memtime(); \
+#define CN_T(k) do { CN_FAIR_AT(k); if (p->timing && lane == 0) p->timing[(size_t)env * CN_STAGE_SLOTS + (k)] = (long long)__builtin_amdgcn_s_memtime(); \
                      if (((p->ablate >> 8) & 0xff) == (k) + 1 && (!((p->ablate >> 16) & 1) || (env & 3) != 0)) __builtin_amdgcn_endpgm(); } while (0)
 #else
 #define CN_ABLATE(bit) 0
@@ -1045,6 +1046,40 @@ __device__ __forceinline__ double bbox_size(KP p, double* stage, int lane, int n
     return sum / (double)n;
 }
 
+// ---- small pieces that observe() and observe_realworld() share ---------------------------------------------------------------
+// order space: position k -> ray (entry).  merged: [0..fe] ++ [ls..n-1] ++ [fe+1..ls-1]; nl = n - ls, the last segment's length
+#define CN_ORDER_IX(merge, fe, ls, nl, k) ((merge) ? ((k) <= (fe) ? (k) : ((k) <= (fe) + (nl) ? (ls) + ((k) - (fe) - 1) : (k) - (nl))) : (k))
+// the collision cone's pre-rejection of a candidate segment (a0 -> (x2, y2)) against a circle (centre c, rr2 = r^2 with slack): the
+// squared distance from the centre to the segment, compared with r^2 without a divide.  false: certainly no intersection
+#define CN_CONE_NEAR(X2, Y2, A0X, A0Y, CX, CY, RR2) ({ \
+    const double ex = (X2) - (A0X), ey = (Y2) - (A0Y), fx = (CX) - (A0X), fy = (CY) - (A0Y); \
+    const double ee = ex * ex + ey * ey, ff = fx * fx + fy * fy, num = fx * ex + fy * ey; \
+    const double rr2 = (RR2); \
+    bool far_; \
+    if (num <= 0.0) far_ = ff > rr2;                                   /* closest point is the agent */ \
+    else if (num >= ee) far_ = (fx - ex) * (fx - ex) + (fy - ey) * (fy - ey) > rr2;  /* ... the far end */ \
+    else far_ = (ff - rr2) * ee > num * num * 1.000001;                /* ... the foot of the perpendicular */ \
+    !far_; })
+// A track's record between HBM (96 bytes, moved as six 16-byte pieces: records are 16-byte aligned) and the LDS table, lane = track.
+// The table shares LDS with the end-point arrays: trk_load once they are dead, trk_store before the next observation reuses them.
+static_assert(CN_TF_COUNT % 2 == 0, "track record in 16-byte pieces");
+__device__ __forceinline__ void trk_load(const Lds& L, double* const T, int lane, int ntracks)
+{
+    if (lane < ntracks) {
+        const double2* rec2 = (const double2*)(L.gtrk + lane * CN_TF_COUNT);
+#pragma unroll
+        for (int f = 0; f < CN_TF_COUNT; f += 2) { const double2 v = rec2[f >> 1]; T[f * L.tcap + lane] = v.x; T[(f + 1) * L.tcap + lane] = v.y; }
+    }
+}
+__device__ __forceinline__ void trk_store(const Lds& L, int lane, int ntracks)
+{
+    if (lane < ntracks) {
+#pragma unroll
+        for (int f = 0; f < CN_TF_COUNT; f += 2)
+            ((double2*)(L.gtrk + lane * CN_TF_COUNT))[f >> 1] = make_double2(L.trk[f * L.tcap + lane], L.trk[(f + 1) * L.tcap + lane]);
+    }
+}
+
 // ---- ENV:656-743 tracker (the same block is RW:478-571), on the confirmed objects L.cfx / cfy / cfd / cft [nconf] ----------
 // WIDE (track_capacity 128 ... 1024): T is the env's table in HBM, used in place in its record layout [tcap][CN_TF_COUNT];
 // otherwise T is the LDS copy, field-major [CN_TF_COUNT][tcap]
@@ -1060,6 +1095,59 @@ template <bool WIDE> __device__ __forceinline__ int trk_ix(int tcap, int f, int 
 #define CN_WIDE_SYNC() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); CN_SYNC(); } while (0)
 #define CN_TSYNC() do { if constexpr (WIDE) CN_WIDE_SYNC(); else CN_SYNC(); } while (0)
 
+// ---- the pieces of the tracker that its two drivers below share, templated on <WIDE, CMP> where they touch TRK ------------------------
+// ENV:688-700, one tile of 8 tracks x 8 objects (lane = track * 8 + object): track `it` (if `valid`) against every confirmed object
+// (walls included), arg-max with the first maximum winning (list.index(max)).  A lane keeps the best of ITS objects across the
+// object tiles (ascending index, strict >), the 8 lanes of a track then reduce with the lower index winning ties.
+// (only lane 0 of each 8-lane group is read by the caller: a reduction tree into it -- lane + 1, lane + 2 by quad permutes,
+// lane + 4 by row_shl:4, all DPP inside the row -- instead of a 3-step xor butterfly of nine ds_bpermute round trips;
+// the order (larger IoU first, then the lower object index) is total, so the tree's shape does not matter)
+struct IouBest { double best; int bj; };
+template <bool WIDE, bool CMP>
+__device__ __forceinline__ IouBest iou_best(KP p, const Lds& L, const double* const T, int lane, bool valid, int it, int nconf)
+{
+    double best = -1.0; int bj = 0x7fffffff;
+    if (valid) {
+        const double tx = TRK(CN_TF_PX, it), ty_ = TRK(CN_TF_PY, it);
+        for (int oj = lane & 7; oj < nconf; oj += 8) {
+            const double u = cn_iou3(tx, ty_, cfx_at<CMP>(L, oj), cfy_at<CMP>(L, oj), 0.0505, PY2);
+            if (u > best) { best = u; bj = oj; }
+        }
+    }
+#define CN_AM_STEP(CTRL) { const double ob = cn_dpp_d<CTRL, 0xf>(best, best); const int ojx = cn_dpp_i<CTRL, 0xf>(bj, bj); \
+                           if (ob > best || (ob == best && ojx < bj)) { best = ob; bj = ojx; } }
+    CN_AM_STEP(0xF5)      /* quad_perm [1,1,3,3] */
+    CN_AM_STEP(0xEE)      /* quad_perm [2,3,2,3] */
+    CN_AM_STEP(0x104)     /* row_shl:4 */
+#undef CN_AM_STEP
+    return {best, bj};
+}
+// ENV:702-712: track `it` takes the place of its object `bj`
+template <bool WIDE, bool CMP>
+__device__ __forceinline__ void trk_matched(const Lds& L, double* const T, int it, int bj, double now)
+{
+    double cxj = cfx_at<CMP>(L, bj), cyj = cfy_at<CMP>(L, bj);
+    TRK(CN_TF_PX, it) = cxj; TRK(CN_TF_PY, it) = cyj; TRK(CN_TF_DIST, it) = cfd_at<CMP>(L, bj);
+    if (TRK(CN_TF_DQLEN, it) < 1.5) { TRK(CN_TF_D1X, it) = cxj; TRK(CN_TF_D1Y, it) = cyj; TRK(CN_TF_DQLEN, it) = 2.0; }
+    TRK(CN_TF_T, it) = now - TRK(CN_TF_T, it);
+    chk_set<CMP>(L, bj, 1);
+}
+// compact the survivors (the lanes with `mine`: their bit of `alive`) behind `base` earlier ones, order preserved: read all, sync, write
+// (rec: the caller's CN_TF_COUNT doubles; declared in the driver, where the record's life is the driver's to see)
+template <bool WIDE>
+__device__ __forceinline__ void trk_compact(const Lds& L, double* const T, double* const rec, int lane, int it, bool mine, u64 alive, int base)
+{
+    if (mine) {
+#pragma unroll
+        for (int f = 0; f < CN_TF_COUNT; ++f) rec[f] = TRK(f, it);
+    }
+    CN_TSYNC();
+    if (mine) {
+        const int slot = base + __popcll(alive & ((1ull << lane) - 1ull));
+#pragma unroll
+        for (int f = 0; f < CN_TF_COUNT; ++f) TRK(f, slot) = rec[f];
+    }
+}
 // The wide tracker: the same ENV:656-743 steps as tracker_stage, over a table of up to 1024 tracks in HBM, 64 tracks per chunk
 // (lane = track - c0).  Chunk by chunk: popleft, the tiled IoU arg-max, the order-dependent walk of ENV:702-717 (`cur` carried
 // from chunk to chunk, one 64-bit alive mask per chunk), the matched tracks' update, and the in-order compaction (slot = the
@@ -1088,26 +1176,12 @@ __device__ __forceinline__ void tracker_stage_wide(KP p, EnvRegs& e, const Lds& 
                 TRK(CN_TF_D0X, it) = TRK(CN_TF_D1X, it); TRK(CN_TF_D0Y, it) = TRK(CN_TF_D1Y, it);
                 TRK(CN_TF_DQLEN, it) = 1.0;
             }
-            // ENV:688-700 arg-max, tiled 8 tracks x 8 objects per pass exactly as in tracker_stage
             int mybj = 0; bool mymatch = false;
             for (int t0 = 0; t0 < cn; t0 += 8) {
                 const int ti = t0 + (lane >> 3);
-                double best = -1.0; int bj = 0x7fffffff;
-                if (ti < cn) {
-                    const double tx = TRK(CN_TF_PX, c0 + ti), ty_ = TRK(CN_TF_PY, c0 + ti);
-                    for (int oj = lane & 7; oj < nconf; oj += 8) {
-                        const double u = cn_iou3(tx, ty_, cfx_at<CMP>(L, oj), cfy_at<CMP>(L, oj), 0.0505, PY2);
-                        if (u > best) { best = u; bj = oj; }
-                    }
-                }
-#define CN_AM_STEP(CTRL) { const double ob = cn_dpp_d<CTRL, 0xf>(best, best); const int ojx = cn_dpp_i<CTRL, 0xf>(bj, bj); \
-                           if (ob > best || (ob == best && ojx < bj)) { best = ob; bj = ojx; } }
-                CN_AM_STEP(0xF5)      /* quad_perm [1,1,3,3] */
-                CN_AM_STEP(0xEE)      /* quad_perm [2,3,2,3] */
-                CN_AM_STEP(0x104)     /* row_shl:4 */
-#undef CN_AM_STEP
-                const u64 posm = __ballot(best > 0.0);
-                const int wb = __shfl(bj, (lane & 7) * 8, 64);
+                const IouBest am = iou_best<WIDE, CMP>(p, L, T, lane, ti < cn, c0 + ti, nconf);
+                const u64 posm = __ballot(am.best > 0.0);
+                const int wb = __shfl(am.bj, (lane & 7) * 8, 64);
                 if ((lane >> 3) == (t0 >> 3)) { mybj = wb; mymatch = ((posm >> (8 * (lane & 7))) & 1ull) != 0ull; }
             }
             const u64 matchm = __ballot(mymatch && lane < cn);
@@ -1117,26 +1191,9 @@ __device__ __forceinline__ void tracker_stage_wide(KP p, EnvRegs& e, const Lds& 
                 else if (cur > c0 + b) cur -= 1;
                 else alive |= (1ull << b);
             }
-            if (lane < cn && ((matchm >> lane) & 1ull)) {           // ENV:702-712
-                double cxj = cfx_at<CMP>(L, mybj), cyj = cfy_at<CMP>(L, mybj);
-                TRK(CN_TF_PX, it) = cxj; TRK(CN_TF_PY, it) = cyj; TRK(CN_TF_DIST, it) = cfd_at<CMP>(L, mybj);
-                if (TRK(CN_TF_DQLEN, it) < 1.5) { TRK(CN_TF_D1X, it) = cxj; TRK(CN_TF_D1Y, it) = cyj; TRK(CN_TF_DQLEN, it) = 2.0; }
-                TRK(CN_TF_T, it) = now - TRK(CN_TF_T, it);
-                chk_set<CMP>(L, mybj, 1);
-            }
-            // compact this chunk's survivors behind the earlier chunks' (order preserved): read all, sync, write
+            if (lane < cn && ((matchm >> lane) & 1ull)) trk_matched<WIDE, CMP>(L, T, it, mybj, now);
             double rec[CN_TF_COUNT];
-            const bool mine = (lane < cn) && ((alive >> lane) & 1ull);
-            if (mine) {
-#pragma unroll
-                for (int f = 0; f < CN_TF_COUNT; ++f) rec[f] = TRK(f, it);
-            }
-            CN_WIDE_SYNC();
-            if (mine) {
-                const int slot = kept + __popcll(alive & ((1ull << lane) - 1ull));
-#pragma unroll
-                for (int f = 0; f < CN_TF_COUNT; ++f) TRK(f, slot) = rec[f];
-            }
+            trk_compact<WIDE>(L, T, rec, lane, it, (lane < cn) && ((alive >> lane) & 1ull), alive, kept);
             kept += __popcll(alive);
             CN_WIDE_SYNC();
         }
@@ -1172,13 +1229,7 @@ __device__ __forceinline__ void tracker_stage(KP p, EnvRegs& e, const Lds& L, do
     constexpr bool WIDE = false;
     // ---- ENV:656-743 tracker -----------------------------------------------------------------------
     // The tracker table shares LDS with the end-point arrays (dead from here on): bring it in now.
-    if (lane < e.ntracks) {
-        // HBM: one 96-byte record per track, moved as six 16-byte pieces (records are 16-byte aligned: 96 = 6 x 16)
-        static_assert(CN_TF_COUNT % 2 == 0, "track record in 16-byte pieces");
-        const double2* rec2 = (const double2*)(L.gtrk + lane * CN_TF_COUNT);
-#pragma unroll
-        for (int f = 0; f < CN_TF_COUNT; f += 2) { const double2 v = rec2[f >> 1]; T[f * L.tcap + lane] = v.x; T[(f + 1) * L.tcap + lane] = v.y; }
-    }
+    trk_load(L, T, lane, e.ntracks);
     CN_SYNC();
     bool add_unchecked = false;
     if (CN_ABLATE(16)) { e.ntracks = 0; nconf = 0; }
@@ -1198,34 +1249,14 @@ __device__ __forceinline__ void tracker_stage(KP p, EnvRegs& e, const Lds& L, do
         } else {
             unsigned long long alive = 0ull;
             int cur = nt0;
-            // ENV:688-700: every track against every confirmed object (walls included), arg-max with the first maximum
-            // winning (list.index(max)).  Tiled 8 tracks x 8 objects per pass, lane = track * 8 + object: a lane keeps the
-            // best of ITS objects across the object tiles (ascending index, strict >), the 8 lanes of a track then reduce
-            // with the lower index winning ties.  One pass in the usual case; a crowded env (> 8 tracks or objects) pays
-            // ceil(nt / 8) * ceil(nconf / 8) passes instead of one serial wave-wide arg-max per track -- and a launch
-            // lasts as long as its most crowded env.
+            // One pass of the arg-max in the usual case; a crowded env (> 8 tracks or objects) pays ceil(nt / 8) * ceil(nconf / 8)
+            // passes instead of one serial wave-wide arg-max per track -- and a launch lasts as long as its most crowded env.
             int mybj = 0; bool mymatch = false;                      // lane = track
             for (int t0 = 0; t0 < nt0; t0 += 8) {
                 const int ti = t0 + (lane >> 3);
-                double best = -1.0; int bj = 0x7fffffff;
-                if (ti < nt0) {
-                    const double tx = TRK(CN_TF_PX, ti), ty_ = TRK(CN_TF_PY, ti);
-                    for (int oj = lane & 7; oj < nconf; oj += 8) {
-                        const double u = cn_iou3(tx, ty_, cfx_at<CMP>(L, oj), cfy_at<CMP>(L, oj), 0.0505, PY2);
-                        if (u > best) { best = u; bj = oj; }
-                    }
-                }
-                // (only lane 0 of each 8-lane group is read below: a reduction tree into it -- lane + 1, lane + 2 by quad permutes,
-                // lane + 4 by row_shl:4, all DPP inside the row -- instead of a 3-step xor butterfly of nine ds_bpermute round trips;
-                // the order (larger IoU first, then the lower object index) is total, so the tree's shape does not matter)
-#define CN_AM_STEP(CTRL) { const double ob = cn_dpp_d<CTRL, 0xf>(best, best); const int ojx = cn_dpp_i<CTRL, 0xf>(bj, bj); \
-                           if (ob > best || (ob == best && ojx < bj)) { best = ob; bj = ojx; } }
-                CN_AM_STEP(0xF5)      /* quad_perm [1,1,3,3] */
-                CN_AM_STEP(0xEE)      /* quad_perm [2,3,2,3] */
-                CN_AM_STEP(0x104)     /* row_shl:4 */
-#undef CN_AM_STEP
-                const u64 posm = __ballot(best > 0.0);             // bit 8 g (any lane of group g): track t0 + g matched
-                const int wb = __shfl(bj, (lane & 7) * 8, 64);     // lane t0 + g <- group g's winner
+                const IouBest am = iou_best<WIDE, CMP>(p, L, T, lane, ti < nt0, ti, nconf);
+                const u64 posm = __ballot(am.best > 0.0);          // bit 8 g (any lane of group g): track t0 + g matched
+                const int wb = __shfl(am.bj, (lane & 7) * 8, 64);  // lane t0 + g <- group g's winner
                 if ((lane >> 3) == (t0 >> 3)) { mybj = wb; mymatch = ((posm >> (8 * (lane & 7))) & 1ull) != 0ull; }
             }
             const u64 matchm = __ballot(mymatch && lane < nt0);
@@ -1234,28 +1265,10 @@ __device__ __forceinline__ void tracker_stage(KP p, EnvRegs& e, const Lds& L, do
                 else if (cur > i) cur -= 1;
                 else alive |= (1ull << i);
             }
-            if (lane < nt0 && ((matchm >> lane) & 1ull)) {          // ENV:702-712
-                const int i = lane;
-                double cxj = cfx_at<CMP>(L, mybj), cyj = cfy_at<CMP>(L, mybj);
-                TRK(CN_TF_PX, i) = cxj; TRK(CN_TF_PY, i) = cyj; TRK(CN_TF_DIST, i) = cfd_at<CMP>(L, mybj);
-                if (TRK(CN_TF_DQLEN, i) < 1.5) { TRK(CN_TF_D1X, i) = cxj; TRK(CN_TF_D1Y, i) = cyj; TRK(CN_TF_DQLEN, i) = 2.0; }
-                TRK(CN_TF_T, i) = now - TRK(CN_TF_T, i);
-                chk_set<CMP>(L, mybj, 1);
-            }
+            if (lane < nt0 && ((matchm >> lane) & 1ull)) trk_matched<WIDE, CMP>(L, T, lane, mybj, now);
             CN_SYNC();
-            // compact the survivors, order preserved
             double rec[CN_TF_COUNT];
-            bool mine = (lane < nt0) && ((alive >> lane) & 1ull);
-            if (mine) {
-#pragma unroll
-                for (int f = 0; f < CN_TF_COUNT; ++f) rec[f] = TRK(f, lane);
-            }
-            CN_SYNC();
-            if (mine) {
-                int slot = __popcll(alive & ((1ull << lane) - 1ull));
-#pragma unroll
-                for (int f = 0; f < CN_TF_COUNT; ++f) TRK(f, slot) = rec[f];
-            }
+            trk_compact<WIDE>(L, T, rec, lane, lane, (lane < nt0) && ((alive >> lane) & 1ull), alive, 0);
             e.ntracks = __popcll(alive);
             add_unchecked = true;  // ENV:723-743
         }
@@ -1305,20 +1318,20 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
     bool wall_x = false, wall_y = false;
     if (w0) {
     // ENV:246-265
-    CN_T(22);
+    CN_T(CN_STG_OBS_ENTRY);
     if (step_counter == 1) waypoint_refresh(p, pg, e, lane, px, py);
     distance_to_goal = cn_round_np64_2_t<!EXT>(dist3(px, py, e.wpx, e.wpy), PY2);   // round(np.float64, 2), ENV:255
     heading = cn_py_round2_t<!EXT>(heading_to_goal(p, e, px, py, yaw), PY2);
-    CN_T(23);
+    CN_T(CN_STG_DIST_HEAD);
     if (step_counter % 5 == 0 || distance_to_goal < e.prev_dist) waypoint_refresh(p, pg, e, lane, px, py);
-    CN_T(24);
+    CN_T(CN_STG_WAYPOINT);
     // ENV:267-268: the angular velocity is used as the angle
     double sw_, cw_;
     if (have_tg) { sw_ = tg.sw; cw_ = tg.cw; } else cn_det_sincos_t(p->trig, w, &sw_, &cw_);
     agent_vel_x = -1.0 * (v * cw_);
     agent_vel_y = v * sw_;
 
-    CN_T(2);
+    CN_T(CN_STG_TWIST);
     // ---- lidar raycast (XACRO:150-178) + UTL:375-392 sanitise + UTL:110-126 end points ----------
     if (have_tg) { sy = tg.sy; cy = tg.cy; } else cn_det_sincos_t(p->trig, yaw, &sy, &cy);
     ox = fma(p->lidar_offset_x, cy, px); oy = fma(p->lidar_offset_x, sy, py);
@@ -1338,7 +1351,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
             nnear = mb->nnear; wall_x = mb->wall_x != 0; wall_y = mb->wall_y != 0;
         }
     }
-    CN_T(3);
+    CN_T(CN_STG_NEAR);
     double smin = 1e300;
     float* o32 = obs32 + (size_t)env * D;
     float* f32 = fin32 ? fin32 + (size_t)env * D : nullptr;
@@ -1406,7 +1419,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
             if (o64) cn_stg(o64, j, so);
         }
     }
-    CN_T(4);
+    CN_T(CN_STG_RAYS);
     // ENV:1011 is the only reader of the scan's minimum, and all it asks is whether ANY range lies below min_scan_range: one compare
     // and a wave vote on the per-lane minima instead of a six-step float64 DPP reduction (min(x) < c <=> some x < c; no NaNs here)
     bool too_close = __ballot(smin < p->min_scan_range) != 0ull;
@@ -1429,7 +1442,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         else { e.dq0x = e.dq1x; e.dq0y = e.dq1y; e.dq1x = qx; e.dq1y = qy; }
     }
 
-    CN_T(5);
+    CN_T(CN_STG_BBOX);
     int ego_hit = 0;
     double* const T = WIDE ? L.gtrk : L.trk;      // track / entry table: [CN_TF_COUNT][tcap], shares LDS with the end points (WIDE: in HBM)
     double* const CPV = WIDE ? L.gcpv : L.cpv;    // collision probability per entry
@@ -1499,7 +1512,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
 #define CHG(a_, b_) (((a_) == GNONE || (b_) == GNONE) ? CN_NAN : fabs(cn_div1000((double)(a_)) - cn_div1000((double)(b_))))
     double clast = CN_NAN;
     if (L.gq[n - 1] != GNONE && lastnn >= 0) clast = CHG(L.gq[lastnn], L.gq[lastnn + 1]);
-    CN_T(6);
+    CN_T(CN_STG_GRAD);
     for (int c0 = 0; c0 < nocc; c0 += 128) {       // two list entries per lane and pass, reads batched
         const int ca = X2 ? c0 + 64 * wv + lane : c0 + lane, cb = X2 ? nocc : ca + 64;
         const int ia = (ca < nocc) ? (int)occlist[ca] : n, ib = (cb < nocc) ? (int)occlist[cb] : n;
@@ -1539,7 +1552,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
     //             !z,nz -> 'w' fresh, last_type = it, du = 1;   !z,!nz,!nn,!eq -> ALIAS of last_type, du = 1
     // so within a 64-ray word the state only changes at the rays that flip du; everything between two
     // flips is a handful of 64-bit mask operations.
-    CN_T(7);
+    CN_T(CN_STG_FLAGS);
     if (w0) {
         // lane = word (W <= 16).  (Round 4 also ran this stage on the SCALAR unit, one word after the other with every mask in SGPRs:
         // 283 -> 164 vector instructions but + 670 scalar ones per observation, and 4-8 % SLOWER in every leg -- the scalar unit
@@ -1641,8 +1654,8 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         if (q < W) { WORD(M_ISW, q) = isw; WORD(M_ISO, q) = iso; WORD(M_NNONE, q) = occraw; }
     }
     CN_SYNC();
-    CN_T(8);
-    CN_T(9);
+    CN_T(CN_STG_TYPES);
+    CN_T(CN_STG_ALIAS);
     // ENV:448-485 association of consecutive rays; brk bit i = a segment closes after ray i.
     // is_associated = round(IoU, 3) > 0 of two squares of half-size bb about consecutive end points.  The end points are
     // integer thousandths, so the decision is a function of (|dx|, |dy|) in thousandths alone as long as no pair sits within
@@ -1758,10 +1771,9 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
     // ENV:490-502 first <-> last with twice the box
     bool merge = (nsegs0 > 1) && cn_iou3_positive(PX(0), PY(0), PX(n - 1), PY(n - 1), e.bb * 2, PY2);
     CN_SYNC();
-    CN_T(10);
+    CN_T(CN_STG_ASSOC);
     // order-space: position k -> ray.  merged: [0..fe] ++ [ls..n-1] ++ [fe+1..ls-1]
     const int nl = n - ls;  // length of the last segment
-#define ORDER(k) (merge ? ((k) <= fe ? (k) : ((k) <= fe + nl ? ls + ((k) - fe - 1) : (k) - nl)) : (k))
     // ENV:508-566 split where free space (0.6) meets occupied; per-position words in order space.
     // Order space is the ray sequence with three ranges moved ([0..fe] ++ [ls..n-1] ++ [fe+1..ls-1]), so the words are
     // built by lane = word with 64-bit field moves (two source words + a funnel shift per range) instead of one
@@ -1815,7 +1827,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         segw_keep = segw;                               // lane 48 + q keeps word q of the segment ends for the list pass below
     }
     CN_SYNC();
-    CN_T(11);
+    CN_T(CN_STG_ORDER);
     // per-word running totals: types seen before word q, last segment end before word q
     int segbase = 0;
     {   // lane = word: exclusive prefix sums / prefix max across the (at most 17) words by shuffles
@@ -1847,7 +1859,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         }
     }
     CN_SYNC();
-    CN_T(12);
+    CN_T(CN_STG_BASES);
     // ENV:568-620 confirmation.  The segment ends (a few dozen at most) are first compacted into one list, in order,
     // so that ONE pass with lane = segment evaluates them all (instead of one pass per 64-ray word, each executing the
     // whole body for its handful of segment-end lanes).  The list lives in the flag words, dead since the type machine.
@@ -1882,7 +1894,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
             const int no = co, nw = cw, nn = len - no - nw;
             const bool occ = (WORD(M_OCC, q) >> bl) & 1ull;  // segments are homogeneous after the split
             if (occ && len >= 4) {
-                m = ORDER(k0 + len / 2);  // ENV:577 Python-2 integer division
+                m = CN_ORDER_IX(merge, fe, ls, nl, k0 + len / 2);  // ENV:577 Python-2 integer division
                 dmi = (int)L.dmil[m];
                 dm = cn_div1000((double)dmi);
                 int est = 3 + (int)floor(cn_div(29 * (p->max_scan_range - dm), p->max_scan_range - p->min_scan_range));   // cn_create: max > min
@@ -1908,7 +1920,6 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         CN_SYNC();
     }
     if (nconf > p->max_conf) { nconf = p->max_conf; e.status |= CN_ST_CONF_OVERFLOW; }
-#undef ORDER
 #undef BIT
 #undef WORD
 #undef PX
@@ -1926,7 +1937,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
     ego_hit = cn_wave_max_i(ego_hit);
     if (n_obst > 0) e.obst_steps += 1;
 
-    CN_T(13);
+    CN_T(CN_STG_CONFIRM);
     if constexpr (WIDE) tracker_stage_wide(p, e, L, T, lane, nconf, now);
     else tracker_stage<CMP>(p, e, L, T, lane, nconf, now);
     } else {
@@ -2002,7 +2013,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         ego_hit = hitm != 0ull;
         CN_SYNC();
     }
-    CN_T(14);
+    CN_T(CN_STG_TRACKER);
     // ENV:745-760 speed of the tracks matched in this call
     if constexpr (WIDE) {
         for (int it = lane; it < e.ntracks; it += 64) {         // (64 tracks per pass)
@@ -2027,7 +2038,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
     e.nent = 0;
     CN_SYNC();
 
-    CN_T(15);
+    CN_T(CN_STG_SPEEDS);
     // ---- ENV:769-996 collision cone / collision probability / top-K -------------------------------
     if (e.dq_len == 2 && !(CN_ABLATE(8))) {
         const double ts = e.ts;
@@ -2090,15 +2101,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
                     if (ti < c1 && x2l > lo) {
                         const double ctx = TRK(CN_TF_PX, ti), cty = TRK(CN_TF_PY, ti);
                         const double y2l = ((double)x2l * gradient) + bb0;
-                        // squared distance from the centre to the segment, compared with r^2 without a divide
-                        const double ex = (double)x2l - a0x, ey = y2l - a0y, fx = ctx - a0x, fy = cty - a0y;
-                        const double ee = ex * ex + ey * ey, ff = fx * fx + fy * fy, num = fx * ex + fy * ey;
-                        const double rr2 = 0.178 * 0.178 * 1.000001;
-                        bool far_;
-                        if (num <= 0.0) far_ = ff > rr2;                                   // closest point is the agent
-                        else if (num >= ee) far_ = (fx - ex) * (fx - ex) + (fy - ey) * (fy - ey) > rr2;  // ... the far end
-                        else far_ = (ff - rr2) * ee > num * num * 1.000001;                // ... the foot of the perpendicular
-                        nearc = !far_;
+                        nearc = CN_CONE_NEAR((double)x2l, y2l, a0x, a0y, ctx, cty, 0.178 * 0.178 * 1.000001);
                     }
                     nearm = __ballot(nearc);
                 }
@@ -2228,7 +2231,7 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         else
         if (!GT && lane < nt) TRK(CN_TF_T, lane) = now;
     }
-    CN_T(16);
+    CN_T(CN_STG_CONE);
     // ENV:998-1005 safety counters
     if (ego_hit) e.ego_viol += 1;
     if (e.ego > 0.4) e.social_viol += 1;
@@ -2252,14 +2255,9 @@ __device__ __forceinline__ void observe(KP p, const Poly& pg, EnvRegs& e, const 
         if (f32) f32[n + i] = (float)so;
         if (o64) o64[n + i] = so;
     }
-    CN_T(17);
+    CN_T(CN_STG_TAIL);
     // tracker table back to HBM (its LDS space is reused by the next observation's end points; WIDE: it never left)
-    if constexpr (!WIDE)
-    if (lane < e.ntracks) {
-#pragma unroll
-        for (int f = 0; f < CN_TF_COUNT; f += 2)
-            ((double2*)(L.gtrk + lane * CN_TF_COUNT))[f >> 1] = make_double2(L.trk[f * L.tcap + lane], L.trk[(f + 1) * L.tcap + lane]);
-    }
+    if constexpr (!WIDE) trk_store(L, lane, e.ntracks);
     CN_SYNC();
     *done_out = e.done;
 }
@@ -2474,7 +2472,6 @@ __device__ __forceinline__ void observe_realworld(KP p, const Poly& pg, EnvRegs&
     int nconf = 0;
     {
         const int nl = M - last_start;
-#define ORD(k) (merged ? ((k) <= first_end ? (k) : ((k) <= first_end + nl ? last_start + ((k) - first_end - 1) : (k) - nl)) : (k))
         int k0 = 0;
         while (k0 < M) {
             int k1 = k0;
@@ -2491,9 +2488,9 @@ __device__ __forceinline__ void observe_realworld(KP p, const Poly& pg, EnvRegs&
             }
             const int len = k1 - k0 + 1;
             int no = 0, nw = 0;
-            for (int k = k0 + lane; k <= k1; k += 64) { const int t_ = Q.et[ORD(k)]; no += (t_ == TY_O); nw += (t_ == TY_W); }
+            for (int k = k0 + lane; k <= k1; k += 64) { const int t_ = Q.et[CN_ORDER_IX(merged, first_end, last_start, nl, k)]; no += (t_ == TY_O); nw += (t_ == TY_W); }
             no = cn_wave_sum_i(no); nw = cn_wave_sum_i(nw);
-            const int ce = ORD(k0 + len / 2);                              // Python-2 integer division
+            const int ce = CN_ORDER_IX(merged, first_end, last_start, nl, k0 + len / 2);                              // Python-2 integer division
             const int ray = ERAY(ce);
             const double dm = cn_div1000((double)(L.dmil[ray] & 0x7fff));
             const int est = 3 + (int)floor(29 * (p->max_scan_range - dm) / (p->max_scan_range - p->min_scan_range));
@@ -2514,7 +2511,6 @@ __device__ __forceinline__ void observe_realworld(KP p, const Poly& pg, EnvRegs&
             }
             k0 = k1 + 1;
         }
-#undef ORD
     }
 #undef ERAY
 #undef PX
@@ -2572,14 +2568,7 @@ __device__ __forceinline__ void observe_realworld(KP p, const Poly& pg, EnvRegs&
                 bool nearc = false;
                 if (lane < 8 && x2l > lo) {
                     const double y2l = ((double)x2l * gradient) + bb0;
-                    const double ex = (double)x2l - a0x, ey = y2l - a0y, fx = tx - a0x, fy = ty_ - a0y;
-                    const double ee = ex * ex + ey * ey, ff = fx * fx + fy * fy, num = fx * ex + fy * ey;
-                    const double rr2 = p->min_scan_range * p->min_scan_range * 1.000001;
-                    bool far_;
-                    if (num <= 0.0) far_ = ff > rr2;
-                    else if (num >= ee) far_ = (fx - ex) * (fx - ex) + (fy - ey) * (fy - ey) > rr2;
-                    else far_ = (ff - rr2) * ee > num * num * 1.000001;
-                    nearc = !far_;
+                    nearc = CN_CONE_NEAR((double)x2l, y2l, a0x, a0y, tx, ty_, p->min_scan_range * p->min_scan_range * 1.000001);
                 }
                 nearm = (unsigned)(__ballot(nearc) & 0xffull);
             }
@@ -2645,11 +2634,7 @@ __device__ __forceinline__ void observe_realworld(KP p, const Poly& pg, EnvRegs&
         if (f32) f32[n + lane] = (float)tv;
         if (o64) o64[n + lane] = tv;
     }
-    if (lane < e.ntracks) {
-#pragma unroll
-        for (int f = 0; f < CN_TF_COUNT; f += 2)
-            ((double2*)(L.gtrk + lane * CN_TF_COUNT))[f >> 1] = make_double2(L.trk[f * L.tcap + lane], L.trk[(f + 1) * L.tcap + lane]);
-    }
+    trk_store(L, lane, e.ntracks);
     CN_SYNC();
     *done_out = e.done;
 }
@@ -2833,11 +2818,11 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         }
     }
 
-    CN_T(0);
+    CN_T(CN_STG_ENTRY);
 #ifdef CN_TIMING
     if (p->timing && lane == 0) {      // where this wavefront runs: HW_ID (wave slot, SIMD, CU, SE) and XCC_ID -- tools/wave_fairness.py
-        p->timing[(size_t)env * 32 + 25] = (long long)__builtin_amdgcn_s_getreg(4 | (31 << 11));
-        p->timing[(size_t)env * 32 + 26] = (long long)__builtin_amdgcn_s_getreg(20 | (31 << 11));
+        p->timing[(size_t)env * CN_STAGE_SLOTS + CN_STG_HW_ID] = (long long)__builtin_amdgcn_s_getreg(4 | (31 << 11));
+        p->timing[(size_t)env * CN_STAGE_SLOTS + CN_STG_XCC_ID] = (long long)__builtin_amdgcn_s_getreg(20 | (31 << 11));
     }
 #endif
     Poly pg;
@@ -2930,7 +2915,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
     auto pedv_save = [&]() { if constexpr (CMP) { for (int i = lane; i < 2 * P; i += 64) gped_v[i] = pedv[i]; } };
     auto pedv_restore = [&]() { if constexpr (CMP) { for (int i = lane; i < 2 * P; i += 64) pedv[i] = gped_v[i]; CN_SYNC(); } };
 
-    CN_T(1);
+    CN_T(CN_STG_LOAD);
     int done = 0;
     constexpr bool ext = EXT;
     const double* od = ext ? p->ext_odom + (size_t)env * 10 : nullptr;
@@ -2992,15 +2977,15 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
                 if constexpr (SIM != 0) sim_advance_ticks<SIM>(p, e, env, lane, L.ped, pedv, (double*)smem, p->dt_ms);
                 else {
                 if constexpr (LAYOUT == 0) { step_trig(p, e, lane, rs1, rc1, rs2, rc2, trig); have_trig = true; }
-                CN_T(27);
+                CN_T(CN_STG_PHYS_TRIG);
                 // pedestrians: ONE pass over [0, dt + scan latency], cut at dt (they are only looked at by the scan)
                 if constexpr (!X2)
                 ped_advance<SHAPE == 360>(p, env, lane, L.ped, pedv, e.crowd_ms, e.crowd_ms + p->dt_ms + p->scan_latency_ms, p->dt_ms);
-                CN_T(28);
+                CN_T(CN_STG_PHYS_PEDS);
                 e.crowd_ms += p->dt_ms + p->scan_latency_ms;
                 if (have_trig) robot_advance_sc(p, e, p->dt_ms, rs1, rc1); else robot_advance(p, e, p->dt_ms);
                 }
-                CN_T(20);
+                CN_T(CN_STG_PHYS);
                 end_timestep = e.clock - t0;                      // ENV:1202
                 if constexpr (LAYOUT == 2)   // RW:876-883: held for dt (0.05 s), booked as `0.05 - 0 + 0.1` on top of the measured 0
                     end_timestep = 0.0 + ((cn_div1000((double)p->dt_ms) - 0.0) + 0.1);
@@ -3020,7 +3005,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
                 e.clock += cn_div1000((double)p->scan_latency_ms);    // wait_for_message('scan') (ENV:1218)
                 if constexpr (SIM != 0) sim_advance_ticks<SIM>(p, e, env, lane, L.ped, pedv, (double*)smem, p->scan_latency_ms);
                 else if (have_trig) robot_advance_sc(p, e, p->scan_latency_ms, rs2, rc2); else robot_advance(p, e, p->scan_latency_ms);
-                CN_T(21);
+                CN_T(CN_STG_SCAN_LAT);
             }
         } else {
             // Env.reset (ENV:1227-1263): gazebo/reset_simulation puts poses back and zeroes twists (the crowd clock keeps running)
@@ -3226,7 +3211,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
     }
     cold_settle();
     asm volatile("" :: "v"(trk_warm));   // keeps the warming load (its value is irrelevant)
-    CN_T(18);
+    CN_T(CN_STG_OUTPUTS);
     // ---- write env state back ---------------------------------------------------------------------
     for (int i = lane; i < 2 * P; i += 64) { gped_p[i] = L.ped[i]; if constexpr (!CMP) gped_v[i] = pedv[i]; }     // (compact: pedv_save() did)
     if (lane == 0) {
@@ -3243,7 +3228,7 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
         si[CN_SI_CROWD_LO] = (int)(unsigned)((unsigned long long)e.crowd_ms & 0xffffffffull);
         si[CN_SI_CROWD_HI] = (int)(unsigned)((unsigned long long)e.crowd_ms >> 32);
     }
-    CN_T(19);
+    CN_T(CN_STG_STORE);
 }
 // env_kernel_body's instantiation by name: a world's five template facts (the columns of crowdnav_variants.h) and the form as flags
 enum : unsigned { CN_F_EXT = 1, CN_F_SAME = 2, CN_F_FUSED = 4, CN_F_FAIR = 8, CN_F_X2 = 16 };
@@ -3437,16 +3422,16 @@ __device__ __forceinline__ void policy_sequence_body()
         //  vector instruction in per MFMA (tools/micro/mfma_valu_mix.hip: 5.5 -> 37.8 cycles per v_fma_f64).  Matrix-core time and
         //  vector time ADD on a SIMD; one workgroup's tile beside another's Env.step overlaps nothing.  profiles/r06/.)
 #ifdef CN_TIMING
-#define POL_T(k) do { if (p->timing && tid_ == 0) p->timing[(size_t)row0 * 32 + 27 + (k)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
+#define POL_T(k) do { if (p->timing && tid_ == 0) p->timing[(size_t)row0 * CN_STAGE_SLOTS + (k)] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define POL_T(k) do { } while (0)
 #endif
-        POL_T(0);
-        POL_T(1);
+        POL_T(CN_STG_POL_PERIOD);
+        POL_T(CN_STG_POL_LOCK);
         actor_tile<8>(ob, min(PE, p->N - row0), row0, D, p->pol_Dp, p->pol_w1p, p->pol_b1, p->pol_w2p, p->pol_b2, p->pol_w3, p->pol_b3,
                       ac, act_lds, p->pol_max_v, p->pol_max_w, p->pol_sigma, p->pol_seed, p->pol_counter + (uint64_t)t, (float*)cn_smem, POL_ACTOR_WAVES(wave), tid_);
         __syncthreads();
-        POL_T(2);
+        POL_T(CN_STG_POL_ACTOR);
         if (env < p->N)
         {
 #if POL_FAIR == 0
@@ -3454,9 +3439,9 @@ __device__ __forceinline__ void policy_sequence_body()
 #endif
             CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, CN_F_FUSED | (POL_FAIR != 0 && LAYOUT == 0 ? CN_F_FAIR : 0))(env, lane_, cn_smem + (size_t)wave * ws, t, act_lds + 2 * wave);
         }
-        POL_T(3);
+        POL_T(CN_STG_POL_STEP);
         __syncthreads();
-        POL_T(4);
+        POL_T(CN_STG_POL_WAIT);
     }
 }
 #endif

@@ -7,8 +7,9 @@ Compiles crowdnav_kernel.hip to assembly with line tables (-gline-tables-only; c
 names an existing file, then walks the kernel's instructions.  Each `.loc` comment carries the whole inlining chain
 (`file:line @[ caller:line @[ ... ] ]`), so an instruction inside cn_round_scaled() inlined into the ray loop is booked
 to the RAY LOOP, not to crowdnav_device.h.  The stage of an instruction = the stage of the first chain element (innermost
-outwards) that lies inside observe() / env_kernel_body(), looked up in the line table below (kept next to the CN_T stamps
-of the source: the table is re-derived from the source's own `CN_T(k)` markers, so it follows edits).
+outwards) that lies inside observe() / env_kernel_body(), looked up in the line table below (re-derived from the source's own
+`CN_T(CN_STG_<NAME>)` stamps, so it follows edits; the stamps' names, slots and labels are the rows of csrc/crowdnav_stages.h,
+which stages() parses for this and the timing tools).
 
 The counts are STATIC (one per instruction in the binary); loops execute their bodies several times.  Dynamic totals per
 env-step come from the PMC counters (profiles/rNN/pmc_extra.txt); this table says where the non-arithmetic instructions
@@ -61,8 +62,38 @@ def classify(op, args):
     return "other"
 
 
+HDR = os.path.join(os.path.dirname(SRC), "crowdnav_stages.h")
+Stage = collections.namedtuple("Stage", "name slot label fair")      # fair: None where the s_setprio level stays
+
+
+def stages(table="CN_STAGES", hdr=HDR):
+    """The rows of one X-macro of crowdnav_stages.h, in the header's order (CN_STAGES: execution order).  The only stage table."""
+    body = re.search(r"#define %s\(X\)((?:.*\\\n)*.*)" % table, open(hdr).read()).group(1)
+    return [Stage(m.group(1), int(m.group(2)), m.group(3), None if m.group(4) in (None, "CN_FAIR_NONE") else int(m.group(4)))
+            for m in re.finditer(r'X\((\w+),\s*(\d+),\s*"([^"]*)"(?:,\s*(\w+))?\)', body)]
+
+
+def cuts(keep=None):
+    """[(slot, label)] of the step kernel's stamps in execution order; with `keep` (slots), only those: where stamps are left
+    out the next one's label reads "first .. last", so a label always names all that ends between two neighbours of the list."""
+    out, held = [], []
+    for st in stages():
+        held.append(st.label)
+        if keep is None or st.slot in keep:
+            out.append((st.slot, held[0] if len(held) == 1 else "%s .. %s" % (held[0], held[-1])))
+            held = []
+    return out
+
+
+# the ledger's name for the code that FOLLOWS a stamp of observe() / env_kernel_body() (stamps not named here open no stage of the ledger)
+AFTER_OBSERVE = {"TWIST": "obs.lidar_setup", "NEAR": "ray.loop", "RAYS": "obs.bbox_deque", "BBOX": "gradients", "GRAD": "flags",
+                 "FLAGS": "type_machine", "ALIAS": "association", "ASSOC": "order_split", "ORDER": "prefix", "BASES": "confirmation",
+                 "TRACKER": "speeds", "SPEEDS": "cone_topk", "CONE": "tail", "TAIL": "trk_writeback"}
+AFTER_BODY = {"LOAD": "body.step", "OUTPUTS": "body.store"}
+
+
 def stage_table(src):
-    """[(first_line, name)] in ascending order, from the source's own structure."""
+    """[(first_line, name)] in ascending order, from the source's own structure: function definitions and CN_T(CN_STG_<NAME>) stamps."""
     lines = open(src).read().split("\n")
 
     def find(pat, start=0):
@@ -71,6 +102,9 @@ def stage_table(src):
             if rx.search(lines[i]):
                 return i + 1
         raise SystemExit("isa_ledger: pattern %r not found in %s" % (pat, src))
+
+    def stamp(name, start):
+        return find(r"CN_T\(CN_STG_%s\);" % name, start)
 
     obs = find(r"^__device__ __forceinline__ void observe\(KP p")
     t = []
@@ -83,36 +117,23 @@ def stage_table(src):
     t.append((find(r"^__device__ __forceinline__ double bbox_size"), "bbox"))
     t.append((find(r"^__device__ __forceinline__ void tracker_stage"), "tracker"))
     t.append((obs, "obs.head"))
-    t.append((find(r"CN_T\(2\);", obs), "obs.lidar_setup"))
-    t.append((find(r"CN_T\(3\);", obs), "ray.loop"))
-    t.append((find(r"CN_T\(4\);", obs), "obs.bbox_deque"))
-    t.append((find(r"CN_T\(5\);", obs), "gradients"))
-    t.append((find(r"CN_T\(6\);", obs), "flags"))
-    t.append((find(r"CN_T\(7\);", obs), "type_machine"))
-    t.append((find(r"CN_T\(9\);", obs), "association"))
-    t.append((find(r"CN_T\(10\);", obs), "order_split"))
-    t.append((find(r"CN_T\(11\);", obs), "prefix"))
-    t.append((find(r"CN_T\(12\);", obs), "confirmation"))
-    t.append((find(r"ENV:637-654", obs), "counters"))
+    t += [(stamp(st.name, obs), AFTER_OBSERVE[st.name]) for st in stages() if st.name in AFTER_OBSERVE]
+    t.append((find(r"ENV:637-654", obs), "counters"))                    # (no stamp stands at these two)
     t.append((find(r"risk_mode gt \(SURVEY", obs), "gt_entries"))
-    t.append((find(r"CN_T\(14\);", obs), "speeds"))
-    t.append((find(r"CN_T\(15\);", obs), "cone_topk"))
-    t.append((find(r"CN_T\(16\);", obs), "tail"))
-    t.append((find(r"CN_T\(17\);", obs), "trk_writeback"))
     t.append((find(r"^struct RwLds"), "layout2"))
     t.append((find(r"^__device__ __forceinline__ double compute_reward\(KP"), "reward"))
     body = find(r"^__device__ __forceinline__ void env_kernel_body")
     t.append((body, "body.setup"))
     t.append((find(r"---- load env state", body), "body.load"))
-    t.append((find(r"CN_T\(1\);", body), "body.step"))
-    t.append((find(r"CN_T\(18\);", body), "body.store"))
-    t.append((find(r"^#ifdef CN_TIMING\n?", find(r"CN_T\(19\);", body)), "kernel.entry"))
+    t += [(stamp(st.name, body), AFTER_BODY[st.name]) for st in stages() if st.name in AFTER_BODY]
+    t.append((find(r"^#ifdef CN_TIMING\n?", stamp("STORE", body)), "kernel.entry"))
     t.sort()
     return t
 
 
 HELPERS = [  # functions of crowdnav_kernel.hip that are called from several stages: skipped when looking for the stage
-    r"heading_to_goal", r"dist3", r"in_box", r"ring_segment", r"bcast_d", r"uni64", r"waypoint_refresh"]
+    r"heading_to_goal", r"dist3", r"in_box", r"ring_segment", r"bcast_d", r"uni64", r"waypoint_refresh",
+    r"trk_load", r"trk_store", r"iou_best", r"trk_matched", r"trk_compact"]     # the tracker's pieces: booked to their driver / caller
 
 
 def helper_ranges(src):

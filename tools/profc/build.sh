@@ -13,7 +13,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-builtin
 INJ="-DCN_TU=1 -DCN_PROFC -include $ROOT/tools/profc/profc_block.h"
 rm -f "$W/units"/*.o
 CN_SKIP_UNIT=k1 bash "$SRC/build.sh" objects "$W/units" & others=$!
-if [ ! -f "$W/k1.ll" ] || [ "$SRC/crowdnav_kernel.hip" -nt "$W/k1.ll" ] || [ "$SRC/crowdnav_device.h" -nt "$W/k1.ll" ]; then
+if [ ! -f "$W/k1.ll" ] || [ "$SRC/crowdnav_kernel.hip" -nt "$W/k1.ll" ] || [ "$SRC/crowdnav_device.h" -nt "$W/k1.ll" ] || [ "$SRC/crowdnav_stages.h" -nt "$W/k1.ll" ]; then
   $HIPCC $FLAGS $INJ -fprofile-instr-generate -fprofile-update=atomic -fcoverage-mapping -gline-tables-only --cuda-device-only -emit-llvm -S \
       -o "$W/k1.ll" "$SRC/crowdnav_kernel.hip" 2>&1 | grep -v "argument unused" || true
 fi

@@ -10,16 +10,14 @@ sys.path.insert(0, os.path.join(ROOT, "drl-based-mapless-crowd-navigation-with-p
 import numpy as np
 import torch
 import crowdnav
+import isa_ledger
 from crowdnav import _abi
 _abi.LIB_PATH = _abi.LIB_PATH.replace("libcrowdnav.so", "libcrowdnav_timing.so")
 _abi.build = lambda force=False: _abi.LIB_PATH
 from crowdnav import Config
 from crowdnav.env import VecEnv
 
-NAMES = ["", "load state", "physics, deque, waypoint/heading/dist", "near-ped list", "ray loop (cast, end points, obs)",
-         "bbox (reset only)", "gradients", "flag words", "type machine", "aliasing", "association (IoU)", "order/split words",
-         "word bases", "confirmation + counters", "tracker", "speeds/defaults", "collision cone + top-K", "counters/done/tail",
-         "reward + outputs", "state write-back"]
+LABEL = dict(isa_ledger.cuts(keep=set(range(20))))   # slots 0..19 ascend in execution order; the later stamps between 1 and 2 fall into 2's row
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 env = VecEnv(Config(n_envs=N, ped_cycle_ms=1400, max_steps=100000)); env.reset()
 tb = torch.zeros((N, 32), dtype=torch.int64, device="cuda")
@@ -43,4 +41,4 @@ for i in range(60):
 acc /= max(cnt, 1)
 print("N = %d, mean s_memtime ticks per stage over %d launches (one wavefront = one env); total %.0f" % (N, cnt, np.mean(tot)))
 for k in range(1, 20):
-    print("  %-36s %9.0f  %5.1f%%" % (NAMES[k], acc[k], 100 * acc[k] / acc[1:].sum()))
+    print("  %-36s %9.0f  %5.1f%%" % (LABEL[k][:36], acc[k], 100 * acc[k] / acc[1:].sum()))

@@ -6,6 +6,7 @@ import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "drl-based-mapless-crowd-navigation-with-perceived-risk_amd"))
 import numpy as np, torch
+import isa_ledger
 from crowdnav import _abi
 _abi.LIB_PATH = _abi.LIB_PATH.replace("libcrowdnav.so", "libcrowdnav_timing.so"); _abi.build = lambda force=False: _abi.LIB_PATH
 from crowdnav import Config
@@ -18,11 +19,9 @@ env.L.cn_debug_set_timing(env.h, C.c_void_p(tb.data_ptr()))
 g = torch.Generator(device="cuda").manual_seed(1)
 acts = torch.stack([torch.rand((16, N), generator=g, device="cuda") * 0.22, torch.rand((16, N), generator=g, device="cuda") * 4 - 2], 2).contiguous()
 step, reset, span = [], [], []
-ORDER = [0, 1, 20, 21, 22, 23, 24] + list(range(2, 20))      # program order of the stamps
-NAMES = {1: "load state", 20: "peds + robot 150 ms", 21: "deque, robot 10 ms", 22: "(pre-observe)", 23: "wp(step 1), dist, heading",
-         24: "wp refresh", 2: "sincos(w)", 3: "near-ped list", 4: "ray loop", 5: "bbox (reset)", 6: "gradients", 7: "flag words",
-         8: "type machine", 9: "aliasing", 10: "association", 11: "order/split", 12: "word bases", 13: "confirmation",
-         14: "tracker", 15: "speeds/defaults", 16: "cone + top-K", 17: "counters/tail", 18: "reward + outputs", 19: "write-back"}
+# the stamps in program order with what ends at each (csrc/crowdnav_stages.h), without the two inside the 150 ms advance
+CUTS = isa_ledger.cuts(keep={st.slot for st in isa_ledger.stages() if st.name not in ("PHYS_TRIG", "PHYS_PEDS")})
+SLOTS = [k for k, _ in CUTS]
 stg = {"median": [], "slowest": [], "reset": []}
 for i in range(300):
     pend = env.counters()[:, 9].clone()
@@ -32,13 +31,13 @@ for i in range(300):
     t = tb.cpu().numpy().astype(np.float64); pr = pend.cpu().numpy() != 0
     life = t[:, 19] - t[:, 0]
     step.append(life[~pr]); reset.append(life[pr])
-    tt = t[:, ORDER]
+    tt = t[:, SLOTS]
     d = np.diff(tt, axis=1)
     ok = (~pr) & (tt > 0).all(1)
     if ok.sum() > 100:
         lo, hi = np.percentile(life[ok], [40, 60]); cut = np.percentile(life[ok], 99.5)
         stg["median"].append(d[ok & (life >= lo) & (life <= hi)].mean(0)); stg["slowest"].append(d[ok & (life >= cut)].mean(0))
-    okr = pr & (t[:, ORDER[2:]] >= 0).all(1)
+    okr = pr & (t[:, SLOTS[2:]] >= 0).all(1)
     span.append((t[:, 19].max() - t[:, 0].min(), np.median(life[~pr]), life.max(), int(pr.sum())))
 s = np.concatenate(step); r = np.concatenate(reset)
 print("stepping envs : n %8d  ticks mean %7.0f  p50 %7.0f  p99 %7.0f  max %7.0f" % (len(s), s.mean(), np.median(s), np.percentile(s, 99), s.max()))
@@ -50,5 +49,5 @@ if stg["median"]:
     m, w = np.mean(stg["median"], 0), np.mean(stg["slowest"], 0)
     print("ticks per stage: median stepping waves (40-60 %%) vs the slowest 0.5 %% of each launch")
     for k in range(len(m)):
-        print("  %-28s %8.0f %8.0f  %+8.0f" % (NAMES.get(ORDER[k + 1], str(ORDER[k + 1])), m[k], w[k], w[k] - m[k]))
+        print("  %-28s %8.0f %8.0f  %+8.0f" % (CUTS[k + 1][1][:28], m[k], w[k], w[k] - m[k]))
     print("  %-28s %8.0f %8.0f" % ("total", m.sum(), w.sum()))
