@@ -4,13 +4,14 @@ ReLU margins, the invertible Adam step).  What is DDPG's own: one critic and one
 Q_t(s2, pi_t(s2)) without target-policy noise, and the actor's gradient through the PRE-update critic -- so both gradients of
 one update are functions of the same parameters and one kernel call yields them together.
 
-The series (series_step, series_run): four updates with both optimisers' moments and step count carried in float64 beside a
-learner -- the device handle, or EmulatedLearner's float32 formula on the CPU; SERIES_VARIANTS restate it wrongly."""
-import math
+The series (series_step; series(): the record adam_series.run walks): four updates with both optimisers' moments and step count
+carried in float64 beside a learner -- the device handle, or EmulatedLearner's float32 formula on the CPU; SERIES_VARIANTS restate it
+wrongly."""
 
 import numpy as np
 import torch
 
+import adam_series as A
 import td3_f64 as R
 
 NETS = ("actor", "actor_t", "critic", "critic_t")
@@ -170,10 +171,6 @@ def series_id(case):
     return "%s-b%g" % ("x".join(map(str, case[0])), round(case[1][0], 3))
 
 
-def _pow2_at_least(x):
-    return 2.0 ** math.ceil(math.log2(max(x, 2.0 ** -60)))
-
-
 def series_grads(P64, b64, cfg, N):
     """{critic, actor: dict(g, bound)} at P64: both gradients of one update, at the pre-update weights."""
     a = actor_grads(P64, b64[0], cfg, N_mask=N)
@@ -184,7 +181,7 @@ def series_grads(P64, b64, cfg, N):
 def series_hp(grads, betas, tau):
     """eps = a power of two >= twice the largest gradient element of the first update; lr = SERIES_LR x (the larger network's top
     |g|) / (its own), the actor's doubled if the two are equal."""
-    top = {n: _pow2_at_least(max(float(v.abs().max()) for v in grads[n]["g"].values())) for n in LOCAL}
+    top = {n: A.pow2_at_least(max(float(v.abs().max()) for v in grads[n]["g"].values())) for n in LOCAL}
     e_ = max(top.values())
     lr_c = SERIES_LR * e_ / top["critic"]
     lr_a = SERIES_LR * e_ / top["actor"]
@@ -194,44 +191,27 @@ def series_hp(grads, betas, tau):
 
 
 def series_state(hp):
-    mk = lambda lr: R.Adam64(lr, hp["beta1"], hp["beta2"], hp["eps"])
-    return dict(t=0, opt=dict(critic=mk(hp["lr_critic"]), actor=mk(hp["lr_actor"])), gerr={})
+    return A.new_state(hp, ("critic", "actor"))
 
 
 def series_step(state, P_pre, grads, hp, variant=None):
     """One update of the series: P_pre the pre-update weights in float64, grads = series_grads at them.  Both optimisers step on
-    every update with one step count; each target follows its stepped network.  -> (predicted tensors, bounds) over the four
-    networks: Adam64's step at td3_f64.adam_step_bound (gerr the running maximum of the gradient bounds), the targets at
-    soft_bound + tau x the step bound."""
+    every update with one step count (adam_series.optimiser_turn / tensor_step); each target follows its stepped network.
+    -> (predicted tensors, bounds) over the four networks, the targets at soft_bound + tau x the step bound."""
     tau = hp["tau"]
     state["t"] += 1
     pred, bound = {}, {}
     for net in LOCAL:
         o = state["opt"][net]
-        o.t = state["t"]
-        o.lr = hp["lr_critic"] if variant == "one_lr" else hp["lr_" + net]
-        o.b1, o.b2 = (hp["beta2"], hp["beta1"]) if variant == "betas_exchanged" else (hp["beta1"], hp["beta2"])
-        if variant == "moments_not_carried":
-            o.m.clear(); o.v.clear()
+        t = A.optimiser_turn(o, state["t"], net, hp, ("critic", "actor"), variant)
         tg = TARGET_OF[net]
         pred[net], bound[net], pred[tg], bound[tg] = {}, {}, {}, {}
         for k in R.NAMES:
-            gb = grads[net]["bound"][k]
-            ge = state["gerr"][(net, k)] = torch.maximum(state["gerr"].get((net, k), torch.zeros_like(gb)), gb)
-            w1, ratio = o.step(k, P_pre[net][k], grads[net]["g"][k], t=1 if variant == "frozen_bias_correction" else None)
-            sb = R.adam_step_bound(w1, ratio, o.lr, hp["eps"], ge)
+            w1, sb = A.tensor_step(o, state["gerr"], net, k, P_pre[net][k], grads[net]["g"][k], grads[net]["bound"][k], hp["eps"], t)
             pred[net][k], bound[net][k] = w1, sb
             src = P_pre[net][k] if variant == "target_from_pre_step_weights" else w1
             pred[tg][k], bound[tg][k] = R.soft_update(P_pre[tg][k], src, tau), R.soft_bound(P_pre[tg][k], src, tau) + tau * sb
     return pred, bound
-
-
-def series_ratios(got, pred, bound):
-    return {(n, k): R.worst_ratio(got[n][k], pred[n][k], bound[n][k]) for n in pred for k in pred[n]}
-
-
-def _net_worst(ratios, net):
-    return max(v for (n, _), v in ratios.items() if n == net)
 
 
 class EmulatedLearner:
@@ -242,20 +222,19 @@ class EmulatedLearner:
         self.P = {n: {k: v.detach().clone().float() for k, v in p.items()} for n, p in P.items()}
         self.hp, self.cfg, self.t, self.mom, self.N = hp, cfg, 0, {}, R.chain_length(*shape)
 
+    def read(self):
+        return {n: {k: v.clone() for k, v in p.items()} for n, p in self.P.items()}
+
+    def write(self, P):
+        self.P = {n: {k: v.clone() for k, v in p.items()} for n, p in P.items()}
+
     def update(self, batch):
-        hp, f = self.hp, np.float32
         g = series_grads(R.to64(self.P), R.batch_double(batch), self.cfg, self.N)
         self.t += 1
-        tau = f(hp["tau"])
+        A.emulated_adam(self.P, self.mom, self.t, self.hp, [(n, R.NAMES) for n in LOCAL], lambda net, k: g[net]["g"][k])
         for net in LOCAL:
             for k in R.NAMES:
-                m0, v0 = self.mom.get((net, k), (None, None))
-                w1, m, v = R.adam_f32_emulation(self.P[net][k].numpy(), g[net]["g"][k].float().numpy(), hp["lr_" + net], hp["eps"], hp["beta1"],
-                                                hp["beta2"], m0, v0, self.t)
-                self.mom[(net, k)] = (m, v)
-                self.P[net][k].copy_(torch.from_numpy(w1))
-                tg = self.P[TARGET_OF[net]][k]
-                tg.copy_(torch.from_numpy((tg.numpy() * (f(1) - tau) + w1 * tau).astype(f)))
+                self.P[TARGET_OF[net]][k] = A.soft_f32(self.P[TARGET_OF[net]][k], self.P[net][k], self.hp["tau"])
 
     def close(self):
         pass
@@ -279,70 +258,22 @@ def series_case(shape, device="cpu", cfg=SERIES_CFG):
     return P, batch, N, dead
 
 
-def _dead_slices(p, dead):
-    u1, u2 = dead
-    return [p["w1"][u1], p["b1"][u1], p["w2"][:, u1], p["w2"][u2], p["b2"][u2], p["w3"][:, u2]]
+def series(shape, betas, device="cpu", cfg=SERIES_CFG):
+    """The record adam_series.run() walks for DDPG: series_case on `device` (a learner's read() / write() tensors live there
+    too), both gradients at the pre-update weights, the margins re-established in place before every update after the first
+    (only the hidden biases move), the planted dead units' weights bit for bit."""
+    c = {}
 
-
-def series_run(make_learner, shape, betas, device="cpu", cfg=SERIES_CFG, log=print):
-    """SERIES_UPDATES updates of `make_learner(P, shape, hp)` (.P: its own float32 tensors on `device`, stepped in place;
-    update(batch); close()) beside the float64 series, the margins re-established in place on the learner's tensors before every
-    update after the first (only the hidden biases move); then a NEW learner on the stepped parameters for one more update.
-    Asserts per update: no ambiguous ReLU mask; eps >= every gradient element; every tensor of the four networks within the
-    series' bound; every wrong variant of SERIES_RULES rejected on each network it concerns from the update at which it can
-    differ; the planted dead units' weights bit for bit.  -> dict(worst={net: ratio}, rejected={variant: smallest rejecting ratio})."""
-    tag = "%s betas %.3g/%.4g" % ("x".join(map(str, shape)), betas[0], betas[1])
-    P, batch, N, dead = series_case(shape, device, cfg)
-    b64 = R.batch_double(batch)
-    grads = series_grads(R.to64(P), b64, cfg, N)
-    hp = series_hp(grads, betas, cfg["tau"])
-    assert hp["lr_critic"] != hp["lr_actor"]
-    log("%s: lr critic %g actor %g, eps %g" % (tag, hp["lr_critic"], hp["lr_actor"], hp["eps"]))
-    right, wrong = series_state(hp), {v: series_state(hp) for v in SERIES_VARIANTS}
-    worst, rejected = {}, {}
-    zeros0 = [x.clone() for n in LOCAL for x in _dead_slices(P[n], dead[n])]
-    be = make_learner(P, shape, hp)
-    try:
-        for u in range(SERIES_UPDATES + 1):
-            if u == SERIES_UPDATES:                            # fresh state at create: a new learner on the stepped parameters
-                stepped = {n: {k: v.clone() for k, v in p.items()} for n, p in be.P.items()}
-                be.close()
-                be = make_learner(stepped, shape, hp)
-            if u:
-                establish_margins(be.P, batch, cfg, N, rescale=False)
-                grads = series_grads(R.to64(be.P), b64, cfg, N)
-            assert margin_report(be.P, batch, cfg, N) >= 1.0, (tag, u, "margins")
-            pre = {n: {k: v.clone() for k, v in p.items()} for n, p in R.to64(be.P).items()}
-            top = max(float(v.abs().max()) for n in LOCAL for v in grads[n]["g"].values())
-            assert top <= hp["eps"], (tag, u, "eps %g below the largest gradient element %g" % (hp["eps"], top))
-            be.update(batch)
-            got = R.to64(be.P)
-            z_ = [x for n in LOCAL for x in _dead_slices(be.P[n], dead[n])]
-            assert all(torch.equal(a_, b_) for a_, b_ in zip(z_, zeros0)), (tag, u, "a dead unit's weight moved")
-            if u == SERIES_UPDATES:
-                fresh = series_ratios(got, *series_step(series_state(hp), pre, grads, hp))
-                carried = series_ratios(got, *series_step(right, pre, grads, hp))
-                log("%s: new handle: fresh Adam %.3g, the carried one %s" % (tag, max(fresh.values()), {n: "%.3g" % _net_worst(carried, n) for n in LOCAL}))
-                assert max(fresh.values()) <= 1.0, (tag, "fresh state at create", fresh)
-                for n in LOCAL:
-                    assert _net_worst(carried, n) > 1.0, (tag, "carried state accepted after create", n)
-                    rejected["carried_after_create"] = min(rejected.get("carried_after_create", math.inf), _net_worst(carried, n))
-                break
-            ratios = series_ratios(got, *series_step(right, pre, grads, hp))
-            for n in NETS:
-                worst[n] = max(worst.get(n, 0.0), _net_worst(ratios, n))
-            log("%s: update %d worst/bound %s" % (tag, u, {n: "%.3g" % _net_worst(ratios, n) for n in NETS}))
-            assert max(ratios.values()) <= 1.0, (tag, u, {k: v for k, v in ratios.items() if v > 1.0})
-            for var in SERIES_VARIANTS:
-                rv = series_ratios(got, *series_step(wrong[var], pre, grads, hp, variant=var))
-                first, nets = SERIES_RULES[var]
-                if u < first:
-                    continue
-                per = {n: _net_worst(rv, n) for n in nets}
-                log("%s: update %d %s %s" % (tag, u, var, {n: "%.3g" % v for n, v in per.items()}))
-                for n, v in per.items():
-                    assert v > 1.0, (tag, u, var, n, v)
-                    rejected[var] = min(rejected.get(var, math.inf), v)
-    finally:
-        be.close()
-    return dict(worst=worst, rejected=rejected, hp=hp)
+    def case():
+        P, c["batch"], c["N"], c["dead"] = series_case(shape, device, cfg)
+        return P
+    return A.series(
+        tag="%s betas %.3g/%.4g" % ("x".join(map(str, shape)), betas[0], betas[1]), shape=shape, case=case,
+        reference=lambda P: series_grads(R.to64(P), R.batch_double(c["batch"]), cfg, c["N"]),
+        hp=lambda grads: series_hp(grads, betas, cfg["tau"]), lr_nets=("critic", "actor"), local=LOCAL, state=series_state,
+        step=series_step,
+        replant=lambda P: establish_margins(P, c["batch"], cfg, c["N"], rescale=False),
+        margins_ok=lambda P: margin_report(P, c["batch"], cfg, c["N"]) >= 1.0,
+        top=lambda grads: max(float(v.abs().max()) for n in LOCAL for v in grads[n]["g"].values()), inputs=lambda: (c["batch"],),
+        frozen=lambda P: [x for n in LOCAL for x in A.dead_slices(P[n], c["dead"][n])], frozen_msg="a dead unit's weight moved",
+        before=None, after=None, variants=SERIES_VARIANTS, rules=SERIES_RULES, report=NETS, alias=None)

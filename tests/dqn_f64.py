@@ -14,6 +14,7 @@ import torch
 import sampling_f64 as S
 import td3_f64 as R
 from actor_f64 import MASK64, noise_key
+from adam_series import pow2_at_least             # noqa: F401 (dqn_f64.pow2_at_least to its tests)
 
 TWISTS = np.array([[0.22, 0.0], [0.22, 2.0], [0.22, -2.0]])
 
@@ -198,10 +199,7 @@ def plant_dead_units(p, hidden):
 
 def dead_slices(p, dead):
     """The slices of the six tensors a dead pair of units owns (in and out): every one must come back bit for bit."""
-    if dead is None:
-        return []
-    u1, u2 = dead
-    return [p["w1"][u1], p["b1"][u1], p["w2"][:, u1], p["w2"][u2], p["b2"][u2], p["w3"][:, u2]]
+    return [] if dead is None else R.dead_slices(p, dead)
 
 
 def establish_margins(p, X2, N, pt=None):
@@ -371,10 +369,6 @@ UPDATE_SHAPES = ([PRODUCT] + [(45, 47, h, 40) for h in (1, 3, 15, 16, 17, 31, 32
 DISCRIMINATE = (PRODUCT, RAGGED)
 SERIES_F = (3, 0, 0, None, 0, 1, 0, 0)                           # None = B: every sample final
 LR_RECOVER = 1024.0                                              # rho = 0: w' = w - lr g / (|g| + eps), inverted per element
-
-
-def pow2_at_least(x):
-    return 2.0 ** int(np.ceil(np.log2(max(float(x), 2.0 ** -60))))
 
 
 def make_case(shape, n_final=0, seed=0, device="cpu", margins=True, scale3=1.0):

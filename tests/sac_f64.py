@@ -10,17 +10,19 @@ act_case builds its inputs with margins on every row from make_case's own pieces
 Parameters are dicts {net: {name: tensor}} like tests/td3_f64.py's: actor = w1, b1, w2, b2, mean_w, mean_b, ls_w, ls_b;
 q, v, v_t = td3_f64.NAMES.  `variant` restates the update WRONGLY in one named way (the discrimination tests).
 
-The series (series_step, series_run): four updates with Adam's moments, the shared step count and V's soft update carried in
-float64 beside a learner -- the device handle, or EmulatedLearner's float32 formula on the CPU -- whose weights are read back
-before and after every update; SERIES_VARIANTS restate the series wrongly, one way at a time."""
-import copy
+The series (series_step; series(): the record adam_series.run walks): four updates with Adam's moments, the shared step count and
+V's soft update carried in float64 beside a learner -- the device handle, or EmulatedLearner's float32 formula on the CPU -- whose
+weights are read back before and after every update; SERIES_VARIANTS restate the series wrongly, one way at a time."""
 import functools
 import math
 
 import numpy as np
 import torch
 
+import adam_series as A
 import td3_f64 as R
+from actor_f64 import uniforms
+from sampling_f64 import angle_f32, noise_hash
 from td3_f64 import NAMES                      # ("w1", "b1", "w2", "b2", "w3", "b3")
 
 ACTOR_NAMES = ("w1", "b1", "w2", "b2", "mean_w", "mean_b", "ls_w", "ls_b")
@@ -212,10 +214,35 @@ def run(ps, P, batch, eps, cfg=CFG, variant=None, eps_first=None):
     return out
 
 
-def reference(P, batch, eps, cfg=CFG, variant=None, eps_first=None):
+def reference(P, batch, eps, cfg=CFG, variant=None, eps_first=None, device=None):
     """(float64 values, bounds) of everything run() returns: the bounds are td3_f64.propagated_bounds' LAMBDA x the RMS change over
-    perturbed runs -- they follow the float32 error of each element (an exact zero has bound zero), not its worst case."""
-    return R.propagated_bounds(lambda ps: run(ps, P, batch, eps, cfg, variant, eps_first))
+    perturbed runs -- they follow the float32 error of each element (an exact zero has bound zero), not its worst case.
+    device: the inputs, of any float type, are taken to float64 on it first (the GPU tests' "cuda"); the results are on the CPU."""
+    if device is not None:
+        d = lambda x: None if x is None else x.double().to(device)
+        P, batch, eps, eps_first = {n: {k: d(v) for k, v in p.items()} for n, p in P.items()}, tuple(d(x) for x in batch), d(eps), d(eps_first)
+    want, bound = R.propagated_bounds(lambda ps: run(ps, P, batch, eps, cfg, variant, eps_first))
+    return {k: v.cpu() for k, v in want.items()}, {k: v.cpu() for k, v in bound.items()}
+
+
+def cuda(batch):
+    return tuple(x.float().cuda().contiguous() for x in batch)
+
+
+SCALE_ERR = 1e-3                               # the uniform gradient scale error the discrimination tests must reject
+
+
+def handle_config(P, shape, lr=3e-4, replay=None, soft_update=0, tau=5e-3, seed=7, **over):
+    """The cn_sac_config of a raw handle (learner_handle.LearnerHandle("sac", ..)) on the float32 device tensors P."""
+    from learner_handle import lib, mlp_struct, ring_fields
+    c = CFG
+    kw = dict(obs_dim=shape[0], hidden=shape[1], hidden_v=shape[2], batch=shape[3], gamma=c["gamma"], tau=tau, lr_actor=lr, lr_v=lr,
+              lr_q=lr, beta1=0.9, beta2=0.999, eps=1e-8, max_v=c["max_v"], max_w=c["max_w"], log_std_min=c["ls_min"],
+              log_std_max=c["ls_max"], mean_lambda=c["mean_lambda"], std_lambda=c["std_lambda"], z_lambda=c["z_lambda"],
+              logp_eps=c["logp_eps"], soft_update=soft_update, reserved=0, actor=mlp_struct(P["actor"], ACTOR_NAMES, "CnSacActor"),
+              seed=seed, **{n: mlp_struct(P[n], NAMES) for n in ("q", "v", "v_t")})
+    kw.update(ring_fields(replay)); kw.update(over)
+    return lib()[0].CnSacConfig(**kw)
 
 
 GRADS = tuple(("q", k) for k in NAMES) + tuple(("v", k) for k in NAMES) + tuple(("actor", k) for k in ACTOR_NAMES)
@@ -461,44 +488,13 @@ def act_case(hidden, obs_dim, ld, n, seed=0):
 
 
 # ---- the draw -----------------------------------------------------------------------------------------------------------------
-_M64 = (1 << 64) - 1
-
-
-def _mix64(x):
-    """cn_mix64 (csrc/crowdnav_device.h): splitmix64's increment, then its finaliser.  A Python int -> a Python int; anything else
-    as a numpy uint64 array, wrapping as the device's 64-bit integers do."""
-    scalar = isinstance(x, int)
-    z = np.asarray([x & _M64] if scalar else x, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = z + np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
-    z = z ^ (z >> np.uint64(31))
-    return int(z[0]) if scalar else z
-
-
-def draw_hash(seed, counter, rows):
-    """h = mix64(mix64(seed ^ mix64(counter ^ 0x5bd1e995)) ^ (uint32) row): the key of td3_prep_kernel's and sac_act_kernel's eps."""
-    base = _mix64((int(seed) & _M64) ^ _mix64((int(counter) & _M64) ^ 0x5bd1e995))
-    return _mix64(np.uint64(base) ^ (np.asarray(rows, dtype=np.int64).astype(np.uint64) & np.uint64(0xFFFFFFFF)))
-
-
-def uniforms(h):
-    """(u1, u2) of a hash, the float32 values the kernels compute: u1 = (k + 1) 2^-24 over k = h >> 40, in (0, 1] (the literal
-    1.0f / 16777217.0f is 2^-24: 16777217.0f rounds to 16777216; u1 = 1 at k = 2^24 - 1 alone, where eps = 0),
-    u2 = k' 2^-24 over k' = (h >> 8) & 0xffffff, in [0, 1)."""
-    h = np.asarray(h, dtype=np.uint64)
-    u1 = ((h >> np.uint64(40)).astype(np.float32) + np.float32(1)) * (np.float32(1) / np.float32(16777217.0))
-    u2 = ((h >> np.uint64(8)) & np.uint64(0xFFFFFF)).astype(np.float32) * (np.float32(1) / np.float32(16777216.0))
-    return u1, u2
-
-
 def box_muller_draw(seed, counter, rows):
-    """The documented draw of row `rows` of call `counter`: eps = (r cos a, r sin a), r = sqrt(-2 ln u1), a = fl32(6.28318530718f u2)
-    -- the angle as the kernel rounds it, everything else in float64.  -> float64 [len(rows), 2]."""
-    u1, u2 = uniforms(draw_hash(seed, counter, rows))
-    r = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
-    a = (np.float32(6.28318530718) * u2).astype(np.float64)
+    """The documented draw of row `rows` of call `counter`, under td3_prep_kernel's and sac_act_kernel's key
+    sampling_f64.noise_hash: eps = (r cos a, r sin a), r = sqrt(-2 ln u1), a = fl32(6.28318530718f u2) -- the angle as the kernel
+    rounds it (sampling_f64.angle_f32), everything else in float64 on actor_f64.uniforms' exact u1 in (0, 1] (1 at k = 2^24 - 1
+    alone, where eps = 0) and u2 in [0, 1).  -> float64 [len(rows), 2]."""
+    u1, u2 = uniforms(noise_hash(seed, counter, None, rows))
+    r, a = np.sqrt(-2.0 * np.log(u1)), angle_f32(u2)
     return np.stack([r * np.cos(a), r * np.sin(a)], 1)
 
 
@@ -533,15 +529,11 @@ def series_id(case):
     return "%s-b%g-soft%d%s" % ("x".join(map(str, shape)), round(betas[0], 3), mode, "-clamped" if clamp_all else "")
 
 
-def _pow2_at_least(x):
-    return 2.0 ** math.ceil(math.log2(max(x, 2.0 ** -60)))
-
-
 def series_hp(want, betas, soft_update, tau=SERIES_TAU):
     """The hyper-parameters of a series from the first update's float64 gradients `want`: eps = a power of two >= twice the
     largest gradient element; each optimiser's lr = SERIES_LR x (the largest network's top |g|) / (its own), powers of two,
     a later one doubled until the three differ (one_lr must show on V and on the actor)."""
-    top = {n: _pow2_at_least(max(float(want[k].abs().max()) for k in GRADS if k[0] == n)) for n in ("q", "v", "actor")}
+    top = {n: A.pow2_at_least(max(float(want[k].abs().max()) for k in GRADS if k[0] == n)) for n in ("q", "v", "actor")}
     e_ = max(top.values())
     lr, seen = {}, set()
     for n in ("q", "v", "actor"):
@@ -554,10 +546,8 @@ def series_hp(want, betas, soft_update, tau=SERIES_TAU):
 
 
 def series_state(hp):
-    """What a series carries from update to update: the shared step count, three td3_f64.Adam64 (Q, V, actor: each its own lr and
-    moments), the running element-wise maximum of the gradient bounds, and (pull_not_seen_by_moments) V's last un-pulled step."""
-    mk = lambda lr: R.Adam64(lr, hp["beta1"], hp["beta2"], hp["eps"])
-    return dict(t=0, opt=dict(q=mk(hp["lr_q"]), v=mk(hp["lr_v"]), actor=mk(hp["lr_actor"])), gerr={}, unpulled=None)
+    """adam_series.new_state for Q, V and the actor, and (pull_not_seen_by_moments) V's last un-pulled step."""
+    return dict(A.new_state(hp, ("q", "v", "actor")), unpulled=None)
 
 
 def series_step(state, P_pre, batch, eps, cfg, hp, variant=None, ref=None):
@@ -580,11 +570,7 @@ def series_step(state, P_pre, batch, eps, cfg, hp, variant=None, ref=None):
     pred, bound = {}, {}
     for net, names in NET_NAMES:
         o = state["opt"][net]
-        o.t = state["t"]
-        o.lr = hp["lr_q"] if variant == "one_lr" else hp["lr_" + net]
-        o.b1, o.b2 = (hp["beta2"], hp["beta1"]) if variant == "betas_exchanged" else (hp["beta1"], hp["beta2"])
-        if variant == "moments_not_carried":
-            o.m.clear(); o.v.clear()
+        t = A.optimiser_turn(o, state["t"], net, hp, ("q", "v", "actor"), variant)
         if variant == "head_moments_exchanged" and net == "actor":
             for a_, b_ in (("mean_w", "ls_w"), ("mean_b", "ls_b")):
                 for mom in (o.m, o.v):
@@ -592,12 +578,10 @@ def series_step(state, P_pre, batch, eps, cfg, hp, variant=None, ref=None):
                         mom[a_], mom[b_] = mom[b_], mom[a_]
         pred[net], bound[net] = {}, {}
         for k in names:
-            ge = state["gerr"][(net, k)] = torch.maximum(state["gerr"].get((net, k), torch.zeros_like(Bd[(net, k)])), Bd[(net, k)])
             w0 = P_pre[net][k]
             if net == "v" and variant == "pull_before_adam":
                 w0 = R.soft_update(w0, P_pre["v_t"][k], tau)
-            w1, ratio = o.step(k, w0, want[(net, k)], t=1 if variant == "frozen_bias_correction" else None)
-            pred[net][k], bound[net][k] = w1, R.adam_step_bound(w1, ratio, o.lr, hp["eps"], ge)
+            pred[net][k], bound[net][k] = A.tensor_step(o, state["gerr"], net, k, w0, want[(net, k)], Bd[(net, k)], hp["eps"], t)
     pred["v_t"], bound["v_t"] = {}, {}
     unpulled = {}
     for k in NAMES:
@@ -612,17 +596,6 @@ def series_step(state, P_pre, batch, eps, cfg, hp, variant=None, ref=None):
             unpulled[k] = v1 - pred["v"][k]
     state["unpulled"] = unpulled if mode == 0 else None
     return pred, bound
-
-
-def series_ratios(got, pred, bound):
-    """{(net, name): worst |got - pred| / bound}"""
-    return {(n, k): R.worst_ratio(got[n][k], pred[n][k], bound[n][k]) for n in pred for k in pred[n]}
-
-
-def _net_worst(ratios, net):
-    if net == "heads":
-        return max(ratios[("actor", k)] for k in HEADS)
-    return max(v for (n, _), v in ratios.items() if n == net)
 
 
 class EmulatedLearner:
@@ -642,20 +615,12 @@ class EmulatedLearner:
                 self.P[n][k].copy_(P[n][k])
 
     def update(self, batch, eps):
-        hp, f = self.hp, np.float32
         g = run(R._Pass(), to64(self.P), tuple(x.double() for x in batch), eps.double())
         self.t += 1
-        for net, names in NET_NAMES:
-            for k in names:
-                m0, v0 = self.mom.get((net, k), (None, None))
-                w1, m, v = R.adam_f32_emulation(self.P[net][k].numpy(), g[(net, k)].float().numpy(), hp["lr_" + net], hp["eps"], hp["beta1"], hp["beta2"],
-                                                m0, v0, self.t)
-                self.mom[(net, k)] = (m, v)
-                self.P[net][k] = torch.from_numpy(w1)
-        tau = f(hp["tau"])
-        moved, toward = ("v_t", "v") if hp["soft_update"] == 1 else ("v", "v_t")
+        A.emulated_adam(self.P, self.mom, self.t, self.hp, NET_NAMES, lambda net, k: g[(net, k)])
+        moved, toward = ("v_t", "v") if self.hp["soft_update"] == 1 else ("v", "v_t")
         for k in NAMES:
-            self.P[moved][k] = torch.from_numpy((self.P[moved][k].numpy() * (f(1) - tau) + self.P[toward][k].numpy() * tau).astype(f))
+            self.P[moved][k] = A.soft_f32(self.P[moved][k], self.P[toward][k], self.hp["tau"])
 
     def close(self):
         pass
@@ -685,83 +650,40 @@ def _replant(P, batch, eps, chain, cc):
     establish_margins(P, batch, eps, chain, which="rest")
 
 
-def _dead_slices(p, dead):
-    u1, u2 = dead
-    return [p["w1"][u1], p["b1"][u1], p["w2"][:, u1], p["w2"][u2], p["b2"][u2], p["w3"][:, u2]]
-
-
-def series_run(make_learner, shape, betas, soft_update, reference_fn=None, clamp_all=False, log=print):
-    """SERIES_UPDATES updates of `make_learner(P, shape, hp)` (read() / write(P) float32 CPU dicts, update(batch, eps), close())
-    beside the float64 series, a fresh eps per update, margins re-planted before every update after the first; then a NEW learner
-    on the stepped parameters for one more update (fresh state at create).  Asserts, per update: margins_ok; eps >= every gradient
-    element; every tensor of Q, V, V_t and the actor within the series' bound; every wrong variant of SERIES_RULES rejected on each
-    network it concerns from the update at which it can differ; the planted zeros bit for bit.  -> dict(worst={net: ratio},
-    rejected={variant: smallest rejecting ratio})."""
-    ref_fn = reference_fn or (lambda P_, b_, e_: reference(to64(P_), tuple(x.double() for x in b_), e_.double()))
+def series(shape, betas, soft_update, clamp_all=False, device="cpu"):
+    """The record adam_series.run() walks for SAC: series_case, reference() on `device`, a fresh tamed eps per update (seeded by
+    the shape), the margins re-planted before every update after the first; Q's planted dead units and, with clamp_all, the
+    log_std head's row 1 bit for bit; V_t bit for bit under soft_update 0."""
     tag = "%s betas %.3g/%.4g soft_update %d%s" % ("x".join(map(str, shape)), betas[0], betas[1], soft_update, " clamp_all" if clamp_all else "")
-    P, batch, eps, chain, cc, dead = series_case(shape, clamp_all)
-    ref = ref_fn(P, batch, eps)
-    hp = series_hp(ref[0], betas, soft_update)
-    assert len({hp["lr_q"], hp["lr_v"], hp["lr_actor"]}) == 3
-    log("%s: lr q %g v %g actor %g, eps %g" % (tag, hp["lr_q"], hp["lr_v"], hp["lr_actor"], hp["eps"]))
     variants = [v for v in SERIES_VARIANTS if soft_update in SERIES_RULES[v][0]]
-    right, wrong = series_state(hp), {v: series_state(hp) for v in variants}
-    worst, rejected = {}, {}
     gen = torch.Generator().manual_seed(4242 + shape[1] + shape[3])
-    vt0 = {k: v.clone() for k, v in P["v_t"].items()}
-    zeros0 = None
-    be = make_learner(P, shape, hp)
-    try:
-        for u in range(SERIES_UPDATES + 1):
-            if u == SERIES_UPDATES:                            # fresh state at create: a new learner on the stepped parameters
-                stepped = be.read()
-                be.close()
-                be = make_learner(stepped, shape, hp)
-            cur = be.read()
-            if u:
-                eps = torch.randn(eps.shape, generator=gen).clamp(-3, 3)
-                _replant(cur, batch, eps, chain, cc)
-                be.write(cur)
-                ref = ref_fn(cur, batch, eps)
-            P64, b64, e64 = to64(cur), tuple(x.double() for x in batch), eps.double()
-            assert margins_ok(P64, b64, e64, chain, cc), (tag, u, "margins")
-            top = max(float(ref[0][k].abs().max()) for k in GRADS)
-            assert top <= hp["eps"], (tag, u, "eps %g below the largest gradient element %g" % (hp["eps"], top))
-            if clamp_all:
-                assert bool((ref[0]["raw"][:, 1] < CFG["ls_min"]).all()) and bool((ref[0]["dl"][:, 3] == 0).all())
-            z_ = _dead_slices(cur["q"], dead["q"]) + ([cur["actor"]["ls_w"][1], cur["actor"]["ls_b"][1]] if clamp_all else [])
-            zeros0 = [x.clone() for x in z_] if zeros0 is None else zeros0
-            be.update(tuple(batch), eps)
-            post = be.read()
-            got = to64(post)
-            z_ = _dead_slices(post["q"], dead["q"]) + ([post["actor"]["ls_w"][1], post["actor"]["ls_b"][1]] if clamp_all else [])
-            assert all(torch.equal(a_, b_) for a_, b_ in zip(z_, zeros0)), (tag, u, "a weight with zero gradient and zero moments moved")
-            if u == SERIES_UPDATES:
-                fresh = series_ratios(got, *series_step(series_state(hp), P64, b64, e64, CFG, hp, ref=ref))
-                carried = series_ratios(got, *series_step(right, P64, b64, e64, CFG, hp, ref=ref))
-                log("%s: new handle: fresh Adam %.3g, the carried one %s" % (tag, max(fresh.values()), {n: "%.3g" % _net_worst(carried, n) for n in ("q", "v", "actor")}))
-                assert max(fresh.values()) <= 1.0, (tag, "fresh state at create", fresh)
-                for n in ("q", "v", "actor"):
-                    assert _net_worst(carried, n) > 1.0, (tag, "carried state accepted after create", n)
-                    rejected["carried_after_create"] = min(rejected.get("carried_after_create", math.inf), _net_worst(carried, n))
-                break
-            ratios = series_ratios(got, *series_step(right, P64, b64, e64, CFG, hp, ref=ref))
-            for n in ("q", "v", "v_t", "actor"):
-                worst[n] = max(worst.get(n, 0.0), _net_worst(ratios, n))
-            log("%s: update %d worst/bound %s" % (tag, u, {n: "%.3g" % _net_worst(ratios, n) for n in ("q", "v", "v_t", "actor")}))
-            assert max(ratios.values()) <= 1.0, (tag, u, {k: v for k, v in ratios.items() if v > 1.0})
-            for var in variants:
-                rv = series_ratios(got, *series_step(wrong[var], P64, b64, e64, CFG, hp, variant=var, ref=ref))
-                _, first, nets = SERIES_RULES[var]
-                if u < first:
-                    continue
-                per = {n: _net_worst(rv, n) for n in nets}
-                log("%s: update %d %s %s" % (tag, u, var, {n: "%.3g" % v for n, v in per.items()}))
-                for n, v in per.items():
-                    assert v > 1.0, (tag, u, var, n, v)
-                    rejected[var] = min(rejected.get(var, math.inf), v)
-            if soft_update == 0:
-                assert all(torch.equal(post["v_t"][k], vt0[k]) for k in NAMES), (tag, u, "V_t moved")
-    finally:
-        be.close()
-    return dict(worst=worst, rejected=rejected, hp=hp)
+    c = {}
+
+    def case():
+        P, c["batch"], c["eps"], c["chain"], c["cc"], c["dead"] = series_case(shape, clamp_all)
+        c["vt0"] = {k: v.clone() for k, v in P["v_t"].items()}
+        return P
+
+    def replant(P):
+        c["eps"] = torch.randn(c["eps"].shape, generator=gen).clamp(-3, 3)
+        _replant(P, c["batch"], c["eps"], c["chain"], c["cc"])
+
+    def b64():
+        return tuple(x.double() for x in c["batch"])
+
+    def before(u, ref):
+        if clamp_all:
+            assert bool((ref[0]["raw"][:, 1] < CFG["ls_min"]).all()) and bool((ref[0]["dl"][:, 3] == 0).all())
+
+    def after(u, post):
+        if soft_update == 0:
+            assert all(torch.equal(post["v_t"][k], c["vt0"][k]) for k in NAMES), (tag, u, "V_t moved")
+    return A.series(
+        tag=tag, shape=shape, case=case, reference=lambda P: reference(P, c["batch"], c["eps"], device=device),
+        hp=lambda ref: series_hp(ref[0], betas, soft_update), lr_nets=("q", "v", "actor"), local=("q", "v", "actor"), state=series_state,
+        step=lambda state, P64, ref, hp, var: series_step(state, P64, b64(), c["eps"].double(), CFG, hp, variant=var, ref=ref),
+        replant=replant, margins_ok=lambda P: margins_ok(to64(P), b64(), c["eps"].double(), c["chain"], c["cc"]),
+        top=lambda ref: max(float(ref[0][k].abs().max()) for k in GRADS), inputs=lambda: (tuple(c["batch"]), c["eps"]),
+        frozen=lambda P: A.dead_slices(P["q"], c["dead"]["q"]) + ([P["actor"]["ls_w"][1], P["actor"]["ls_b"][1]] if clamp_all else []),
+        frozen_msg="a weight with zero gradient and zero moments moved", before=before, after=after, variants=variants,
+        rules={v: SERIES_RULES[v][1:] for v in variants}, report=("q", "v", "v_t", "actor"), alias={"heads": ("actor", HEADS)})

@@ -367,6 +367,27 @@ def compare_grads(got, want, bound, extra=None):
     return {k: worst_ratio(got[k], want[k], bound[k] + (extra[k] if extra is not None else 0.0)) for k in NAMES}
 
 
+def recover(P0, P1, net, lr, eps):
+    """(the gradients invert_step reads from net's step P0 -> P1, their inversion bounds), per tensor."""
+    g = {k: invert_step(P0[net][k], P1[net][k], lr, eps) for k in NAMES}
+    return g, {k: inversion_bound(g[k], P0[net][k], P1[net][k], lr, eps) for k in NAMES}
+
+
+def accept(ratios):
+    return max(ratios.values()) <= 1.0
+
+
+def same(P0, P1, net):
+    return all(torch.equal(P0[net][k], P1[net][k]) for k in NAMES)
+
+
+def rejects_gross(g, ref, extra, net):
+    """at every shape: a zero gradient (a network that is never stepped) and one twice too large are rejected"""
+    if any(bool((v != 0).any()) for v in ref["g"].values()):
+        assert not accept(compare_grads(g, {k: torch.zeros_like(v) for k, v in ref["g"].items()}, ref["bound"], extra)), net
+        assert not accept(compare_grads(g, {k: 2 * v for k, v in ref["g"].items()}, ref["bound"], extra)), net
+
+
 def zero_tile(g, i0=0, j0=0, size=16):
     g = g.clone()
     if g.dim() == 2:
@@ -390,6 +411,19 @@ def plant_dead_units(P, hidden, nets=LOCAL):
         P[n]["w2"][u2].zero_(); P[n]["b2"][u2] = 0
         dead[n] = (u1, u2)
     return dead
+
+
+def dead_slices(p, dead):
+    """The slices of a network's six tensors that its dead pair of units owns (in and out): each must keep every bit."""
+    u1, u2 = dead
+    return [p["w1"][u1], p["b1"][u1], p["w2"][:, u1], p["w2"][u2], p["b2"][u2], p["w3"][:, u2]]
+
+
+def check_dead(P0, P1, net, dead):
+    if net not in dead:
+        return
+    for a, b in zip(dead_slices(P0[net], dead[net]), dead_slices(P1[net], dead[net])):
+        assert torch.equal(a, b), net
 
 
 def _is_dead(w, b):

@@ -13,6 +13,7 @@ import pytest
 
 import actor_pop_ref as R
 from conftest import ROOT
+from learner_handle import lib
 
 CN_ERR_ARG, CN_ERR_CONFIG = -1, -2
 NAMES = ("cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", "cn_actor_pop_pack", "cn_actor_pop_forward",
@@ -20,13 +21,8 @@ NAMES = ("cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", 
 FAKE = 0x1000        # a non-null "device pointer": the checks compare with NULL and never dereference
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
 def test_member_struct_matches_its_mirror_field_by_field(tmp_path):
-    _abi, _ = _lib()
+    _abi, _ = lib()
     if shutil.which("gcc") is None:
         pytest.skip("no gcc")
     cls = _abi.CnActorPopMember
@@ -63,7 +59,7 @@ def test_member_struct_matches_its_mirror_field_by_field(tmp_path):
 
 
 def test_the_six_names_are_exported_with_prototypes():
-    _abi, L = _lib()
+    _abi, L = lib()
     for name in NAMES:
         assert name in _abi.EXPORTS
         assert getattr(L, name).argtypes is not None, name
@@ -96,7 +92,7 @@ def _create(L, members, n_members, obs_dim, want_rc, *texts, out="fresh"):
 
 
 def test_create_refusals_name_the_field_and_the_member():
-    _abi, L = _lib()
+    _abi, L = lib()
     arr = lambda *ms: (_abi.CnActorPopMember * len(ms))(*ms)
     good = _member(_abi)
     _create(L, None, 1, 398, CN_ERR_ARG, "members")
@@ -120,7 +116,7 @@ def test_create_refusals_name_the_field_and_the_member():
 
 
 def test_null_handles_are_refused_everywhere():
-    _abi, L = _lib()
+    _abi, L = lib()
     counters = (C.c_uint64 * 64)()
     w = _abi.CnActorWeights()
     assert L.cn_actor_pop_pack(None, None) == CN_ERR_ARG and b"cn_actor_pop_pack: null handle" in L.cn_last_error()

@@ -3,6 +3,7 @@ the power of its acceptance rule on every case the GPU test runs."""
 import pytest
 import torch
 
+import adam_series as A
 import ddpg_f64 as D
 import td3_f64 as R
 
@@ -58,7 +59,7 @@ def test_the_series_rule_accepts_a_float32_emulation_and_rejects_each_wrong_vari
     float32-rounded float64 gradients, carried moments, one step count) in the handle's place: inside the series' bound at every
     update, every wrong variant outside it on each network it concerns."""
     shape, betas = case
-    res = D.series_run(D.EmulatedLearner, shape, betas, log=lambda s: None)
+    res = A.run(D.series(shape, betas), D.EmulatedLearner, log=lambda s: None)
     print(D.series_id(case), {n: "%.3g" % v for n, v in res["worst"].items()}, {k: "%.3g" % v for k, v in res["rejected"].items()})
     assert max(res["worst"].values()) <= 1.0
     assert set(res["rejected"]) == set(D.SERIES_VARIANTS) | {"carried_after_create"} and min(res["rejected"].values()) > 1.0

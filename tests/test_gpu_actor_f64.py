@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import actor_f64 as A
+from learner_handle import lib, stream
 from td3_f64 import worst_ratio
 
 pytestmark = pytest.mark.gpu
@@ -41,15 +42,6 @@ EDGE_SCALE = 256.0          # edge columns' observations x 256: one such column'
 WIDEST_WORLD = dict(n_rays=965, k_obstacles=16, n_peds=0, room_half=3.0)
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def make_actor(D, seed, obs):
     """nn.Linear's initialisation as float32 values (float64 tensors on the device), linear3 rescaled per output so that the
     logits on `obs` span +-4."""
@@ -70,15 +62,15 @@ class Packed:
     """p in cn_actor_pack_weights' layout (as crowdnav.td3.FusedActorMixin.sync_fused_weights lays it out)."""
 
     def __init__(self, p):
-        _abi, L = _lib()
+        _abi, L = lib()
         D = p["w1"].shape[1]
         Dp = (D + 31) // 32 * 32
         w1t = torch.zeros((Dp, 256), dtype=torch.float32, device="cuda")
         w1t[:D] = p["w1"].T.float()
         w2t = p["w2"].T.float().contiguous()
         self.w1p, self.w2p = torch.empty_like(w1t), torch.empty_like(w2t)
-        _abi.check(L.cn_actor_pack_weights(C.c_void_p(w1t.data_ptr()), Dp, C.c_void_p(self.w1p.data_ptr()), 0, _stream()))
-        _abi.check(L.cn_actor_pack_weights(C.c_void_p(w2t.data_ptr()), 256, C.c_void_p(self.w2p.data_ptr()), 0, _stream()))
+        _abi.check(L.cn_actor_pack_weights(C.c_void_p(w1t.data_ptr()), Dp, C.c_void_p(self.w1p.data_ptr()), 0, stream()))
+        _abi.check(L.cn_actor_pack_weights(C.c_void_p(w2t.data_ptr()), 256, C.c_void_p(self.w2p.data_ptr()), 0, stream()))
         self.f = {k: p[k].float().contiguous() for k in ("b1", "b2", "w3", "b3")}
         self.w = _abi.CnActorWeights(w1p=self.w1p.data_ptr(), b1=self.f["b1"].data_ptr(), w2p=self.w2p.data_ptr(),
                                      b2=self.f["b2"].data_ptr(), w3=self.f["w3"].data_ptr(), b3=self.f["b3"].data_ptr(),
@@ -86,10 +78,10 @@ class Packed:
         torch.cuda.synchronize()
 
     def forward(self, obs, sigma=0.0, seed=0, counter=0, max_v=MAX_V, max_w=MAX_W):
-        _abi, L = _lib()
+        _abi, L = lib()
         out = torch.full((obs.shape[0], 2), float("nan"), device="cuda")
         _abi.check(L.cn_actor_forward(C.byref(self.w), C.c_void_p(obs.data_ptr()), C.c_void_p(out.data_ptr()), obs.shape[0],
-                                      max_v, max_w, sigma, seed, counter, 0, _stream()))
+                                      max_v, max_w, sigma, seed, counter, 0, stream()))
         torch.cuda.synchronize()
         return out
 
@@ -176,7 +168,7 @@ def test_actor_forward_batches(n):
 
 def test_actor_forward_refuses_past_its_lds_tile():
     """obs_dim 2273 (Dp 2304) needs more than 160 KiB of LDS: CN_ERR_CONFIG, before anything is launched."""
-    _abi, L = _lib()
+    _abi, L = lib()
     z = torch.zeros(16, device="cuda")
     for D, rc in ((2273, CN_ERR_CONFIG), (4000, CN_ERR_CONFIG)):
         w = _abi.CnActorWeights(w1p=z.data_ptr(), b1=z.data_ptr(), w2p=z.data_ptr(), b2=z.data_ptr(), w3=z.data_ptr(),
@@ -187,10 +179,10 @@ def test_actor_forward_refuses_past_its_lds_tile():
 
 
 def _tail(lg, max_v, max_w, sigma, seed, counter):
-    _abi, L = _lib()
+    _abi, L = lib()
     out = torch.full_like(lg, float("nan"))
     _abi.check(L.cn_policy_tail(C.c_void_p(lg.data_ptr()), C.c_void_p(out.data_ptr()), lg.shape[0], max_v, max_w, sigma, seed,
-                                counter, 0, _stream()))
+                                counter, 0, stream()))
     torch.cuda.synchronize()
     return out
 

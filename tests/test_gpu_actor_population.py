@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import actor_f64 as A
+from learner_handle import lib, stream
 from td3_f64 import worst_ratio
 
 pytestmark = pytest.mark.gpu
@@ -31,15 +32,6 @@ def _f32(x):
     return float(np.float32(x))
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _actor(D, seed):
     from crowdnav.td3 import Actor
     torch.manual_seed(1000 + seed)
@@ -57,15 +49,15 @@ class Solo:
     """The per-agent path for one actor: W^T staged and zero-padded, cn_actor_pack_weights twice, cn_actor_forward."""
 
     def __init__(self, actor):
-        _abi, L = _lib()
+        _abi, L = lib()
         D = actor.linear1.in_features
         Dp = (D + 31) // 32 * 32
         w1t = torch.zeros((Dp, 256), device="cuda")
         w1t[:D] = actor.linear1.weight.detach().t()
         w2t = actor.linear2.weight.detach().t().contiguous()
         self.w1p, self.w2p = torch.empty_like(w1t), torch.empty_like(w2t)
-        _abi.check(L.cn_actor_pack_weights(C.c_void_p(w1t.data_ptr()), Dp, C.c_void_p(self.w1p.data_ptr()), 0, _stream()))
-        _abi.check(L.cn_actor_pack_weights(C.c_void_p(w2t.data_ptr()), 256, C.c_void_p(self.w2p.data_ptr()), 0, _stream()))
+        _abi.check(L.cn_actor_pack_weights(C.c_void_p(w1t.data_ptr()), Dp, C.c_void_p(self.w1p.data_ptr()), 0, stream()))
+        _abi.check(L.cn_actor_pack_weights(C.c_void_p(w2t.data_ptr()), 256, C.c_void_p(self.w2p.data_ptr()), 0, stream()))
         torch.cuda.synchronize()
         self.keep = actor
         self.w = _abi.CnActorWeights(w1p=self.w1p.data_ptr(), b1=actor.linear1.bias.data_ptr(), w2p=self.w2p.data_ptr(),
@@ -73,10 +65,10 @@ class Solo:
                                      b3=actor.linear3.bias.data_ptr(), obs_dim=D, obs_dim_padded=Dp, hidden=256, reserved=0)
 
     def forward(self, obs, n, max_v, max_w, sigma, seed, counter, w=None):
-        _abi, L = _lib()
+        _abi, L = lib()
         out = torch.full((n + PAD, 2), SENTINEL, device="cuda")
         _abi.check(L.cn_actor_forward(C.byref(self.w if w is None else w), C.c_void_p(obs.data_ptr()), C.c_void_p(out.data_ptr()), n,
-                                      max_v, max_w, sigma, seed, counter, 0, _stream()))
+                                      max_v, max_w, sigma, seed, counter, 0, stream()))
         torch.cuda.synchronize()
         return out
 
@@ -230,14 +222,14 @@ def test_a_member_does_not_depend_on_its_place_or_its_neighbours():
 
 
 def test_all_members_empty_launches_nothing_and_live_handle_refusals():
-    _abi, L = _lib()
+    _abi, L = lib()
     D = 33
     ms = [Member(_actor(D, p), 0, p, 1, 0.1, 0.22, 2.0, p) for p in range(2)]
     got = _run(ms, 1)
     assert all(bool((g == SENTINEL).all()) for g in got)
     h = _handle([Member(_actor(D, 3), 4, 1, 1, 0.1, 0.22, 2.0, 3)])
     assert L.cn_actor_pop_members(h.h) == 1
-    assert L.cn_actor_pop_forward(h.h, None, 1, _stream()) == CN_ERR_ARG and b"counters" in L.cn_last_error()
+    assert L.cn_actor_pop_forward(h.h, None, 1, stream()) == CN_ERR_ARG and b"counters" in L.cn_last_error()
     w = _abi.CnActorWeights()
     for member in (-1, 1, 64):
         assert L.cn_actor_pop_weights(h.h, member, C.byref(w)) == CN_ERR_ARG

@@ -1,6 +1,6 @@
 """cn_ddpg_update (csrc/crowdnav_ddpg.hip) on the device: the reference's learn() goldens (tests/golden/ddpg.npz), a float64
 statement of the same update with the gradients observed (tests/ddpg_f64.py), determinism, the replay path, argument checks,
-Adam across four updates against a float64 series (ddpg_f64.series_run), a hipGraph capture, the DDPG agent in the fused collection loop, and the trainer end to end.
+Adam across four updates against a float64 series (adam_series.run), a hipGraph capture, the DDPG agent in the fused collection loop, and the trainer end to end.
 
 Adam with beta1 = beta2 = 0 steps w' = w - lr g / (|g| + eps); the tests invert that per element.  Both DDPG gradients are taken
 at the pre-update weights (ddpg.py:216-239), so ONE call with large learning rates for both optimizers yields the critic's and
@@ -15,9 +15,11 @@ import numpy as np
 import pytest
 import torch
 
+import adam_series as A
 import ddpg_f64 as D
 import td3_f64 as R
 from conftest import ROOT
+from learner_handle import LearnerHandle, batch_struct, lib, mlp_struct, ring_fields
 
 pytestmark = pytest.mark.gpu
 
@@ -35,11 +37,6 @@ SHAPES = [
 ALL_DONE = (45, 17, 40)                                # y = r in every row
 DISCRIMINATE = ((398, 256, 64), (45, 33, 40))
 SCALE_ERR = 1e-3
-
-
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
 
 
 def make_case(shape, seed=0, margins=True):
@@ -64,78 +61,21 @@ def make_case(shape, seed=0, margins=True):
     return P, batch, nz, N, dead
 
 
-class Fused:
+class Fused(LearnerHandle):
     """One cn_ddpg handle on its own float32 copies of the parameters."""
 
     def __init__(self, P, shape, lr_c, lr_a, eps, beta1=0.0, beta2=0.0, tau=CFG["tau"], replay=None):
-        _abi, L = _lib()
-        self.L = L
         self.P = {n: {k: v.detach().clone().contiguous() for k, v in p.items()} for n, p in P.items()}
-        mlp = lambda n: _abi.CnTd3Mlp(*[self.P[n][k].data_ptr() for k in R.NAMES])
-        rp = {}
-        if replay is not None:
-            rp = dict(replay_s=replay["s"].data_ptr(), replay_a=replay["a"].data_ptr(), replay_r=replay["r"].data_ptr(),
-                      replay_s2=replay["s2"].data_ptr(), replay_d=replay["d"].data_ptr(), replay_size_dev=replay["size"].data_ptr())
-        self.cfg = _abi.CnDdpgConfig(obs_dim=shape[0], hidden=shape[1], batch=shape[2], gamma=CFG["gamma"], tau=tau, lr_actor=lr_a,
-                                     lr_critic=lr_c, beta1=beta1, beta2=beta2, eps=eps, max_v=CFG["max_v"], max_w=CFG["max_w"],
-                                     actor=mlp("actor"), actor_t=mlp("actor_t"), critic=mlp("critic"), critic_t=mlp("critic_t"),
-                                     seed=7, **rp)
-        self.h = C.c_void_p()
-        rc = L.cn_ddpg_create(C.byref(self.cfg), 0, C.byref(self.h))
-        assert rc == 0, L.cn_td3_last_error()
+        cfg = lib()[0].CnDdpgConfig(obs_dim=shape[0], hidden=shape[1], batch=shape[2], gamma=CFG["gamma"], tau=tau, lr_actor=lr_a,
+                                    lr_critic=lr_c, beta1=beta1, beta2=beta2, eps=eps, max_v=CFG["max_v"], max_w=CFG["max_w"], seed=7,
+                                    **{n: mlp_struct(self.P[n], R.NAMES) for n in D.NETS}, **ring_fields(replay))
+        super().__init__("ddpg", cfg, (self.P, replay))
 
     def update(self, batch, sync=True):
-        _abi, L = _lib()
-        bp = None
-        if batch is not None:
-            self._keep = batch
-            bp = C.byref(_abi.CnTd3Batch(*[x.data_ptr() for x in batch], None))
-        rc = L.cn_ddpg_update(self.h, bp, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        assert rc == 0, L.cn_td3_last_error()
-        if sync:
-            torch.cuda.synchronize()
+        super().update(batch=batch_struct(batch), sync=sync)
 
     def loss(self):
-        from crowdnav.td3 import _device_scalar_view
-        return float(_device_scalar_view(self.L.cn_ddpg_loss_dev(self.h), torch.device("cuda")))
-
-    def close(self):
-        if self.h:
-            self.L.cn_ddpg_destroy(self.h)
-            self.h = None
-
-
-def _pow2_at_least(x):
-    return 2.0 ** math.ceil(math.log2(max(x, 2.0 ** -60)))
-
-
-def _recover(P0, P1, net, lr, eps):
-    g = {k: R.invert_step(P0[net][k], P1[net][k], lr, eps) for k in R.NAMES}
-    return g, {k: R.inversion_bound(g[k], P0[net][k], P1[net][k], lr, eps) for k in R.NAMES}
-
-
-def _accept(ratios):
-    return max(ratios.values()) <= 1.0
-
-
-def _same(P0, P1, net):
-    return all(torch.equal(P0[net][k], P1[net][k]) for k in R.NAMES)
-
-
-def _check_dead(P0, P1, net, dead):
-    if net not in dead:
-        return
-    u1, u2 = dead[net]
-    for a, b in ((P0[net]["w1"][u1], P1[net]["w1"][u1]), (P0[net]["b1"][u1], P1[net]["b1"][u1]),
-                 (P0[net]["w2"][:, u1], P1[net]["w2"][:, u1]), (P0[net]["w2"][u2], P1[net]["w2"][u2]),
-                 (P0[net]["b2"][u2], P1[net]["b2"][u2]), (P0[net]["w3"][:, u2], P1[net]["w3"][:, u2])):
-        assert torch.equal(a, b), net
-
-
-def _rejects_gross(g, ref, extra, net):
-    if any(bool((v != 0).any()) for v in ref["g"].values()):
-        assert not _accept(R.compare_grads(g, {k: torch.zeros_like(v) for k, v in ref["g"].items()}, ref["bound"], extra)), net
-        assert not _accept(R.compare_grads(g, {k: 2 * v for k, v in ref["g"].items()}, ref["bound"], extra)), net
+        return float(super().loss())
 
 
 def test_fused_ddpg_update_on_the_reference_learn_goldens():
@@ -187,8 +127,8 @@ def _gradients(shape, report):
     elif B >= 2:
         assert 0 < float(b64[4].mean()) < 1
     assert float(R.actor_fwd(P64["actor"], b64[0], CFG)["logits"].abs().max()) >= 7.0
-    eps_c = _pow2_at_least(max(float(v.abs().max()) for v in refc["g"].values()))
-    eps_a = _pow2_at_least(max(float(v.abs().max()) for v in refa["g"].values()))
+    eps_c = A.pow2_at_least(max(float(v.abs().max()) for v in refc["g"].values()))
+    eps_a = A.pow2_at_least(max(float(v.abs().max()) for v in refa["g"].values()))
     lr_c, lr_a = LR, LR * eps_c / eps_a          # the actor's step as large relative to its gradient as the critic's (powers of two)
     k_ = Fused(P0, shape, lr_c, lr_a, eps_c)
     k_.update(batch)
@@ -198,12 +138,12 @@ def _gradients(shape, report):
     report.append("%s: loss %.9g float64 %.9g" % (shape, loss, l_))
     assert abs(loss - l_) <= 1e-5 * abs(l_), (loss, l_)
     for net, ref, lr in (("critic", refc, lr_c), ("actor", refa, lr_a)):
-        g, extra = _recover(P0, P1, net, lr, eps_c)
+        g, extra = R.recover(P0, P1, net, lr, eps_c)
         ratios = R.compare_grads(g, ref["g"], ref["bound"], extra)
         report.append("%-7s worst/bound " % net + " ".join("%s %.3g" % kv for kv in ratios.items()))
-        assert _accept(ratios), (net, ratios)
-        _check_dead(P0, P1, net, dead)
-        _rejects_gross(g, ref, extra, net)
+        assert R.accept(ratios), (net, ratios)
+        R.check_dead(P0, P1, net, dead)
+        R.rejects_gross(g, ref, extra, net)
         if net == "critic":
             gc, xc = g, extra
         else:
@@ -219,20 +159,28 @@ def _gradients(shape, report):
     if shape in DISCRIMINATE:
         # the actor's gradient fits the pre-update critic and NOT the critic this very update produced (TD3's order)
         post = D.actor_grads(P64, b64[0], CFG, critic=R.to64(P1)["critic"])
-        assert not _accept(R.compare_grads(ga, post["g"], post["bound"], xa)), "actor through the post-update critic accepted"
+        assert not R.accept(R.compare_grads(ga, post["g"], post["bound"], xa)), "actor through the post-update critic accepted"
         for wrong in ("twin", "noise"):
             w = D.critic_grads(P64, b64, CFG, y_from=wrong, nz=nz)
-            assert not _accept(R.compare_grads(gc, w["g"], w["bound"], xc)), "y = %s accepted" % wrong
+            assert not R.accept(R.compare_grads(gc, w["g"], w["bound"], xc)), "y = %s accepted" % wrong
         for net, ref, g, x in (("critic", refc, gc, xc), ("actor", refa, ga, xa)):
             scaled = {kk: v * (1 + SCALE_ERR) for kk, v in ref["g"].items()}
-            assert not _accept(R.compare_grads(g, scaled, ref["bound"], x)), "%s x (1 + %g) accepted" % (net, SCALE_ERR)
+            assert not R.accept(R.compare_grads(g, scaled, ref["bound"], x)), "%s x (1 + %g) accepted" % (net, SCALE_ERR)
 
 
 class _SeriesHandle(Fused):
-    """ddpg_f64.series_run's learner: one cn_ddpg handle on its own tensors (.P), stepped and re-margined in place."""
+    """adam_series.run's learner: one cn_ddpg handle; read() / write() copy from / into the device tensors it points at."""
 
     def __init__(self, P, shape, hp):
         super().__init__(P, shape, hp["lr_critic"], hp["lr_actor"], hp["eps"], beta1=hp["beta1"], beta2=hp["beta2"], tau=hp["tau"])
+
+    def read(self):
+        return {n: {k: v.clone() for k, v in p.items()} for n, p in self.P.items()}
+
+    def write(self, P):
+        for n in P:
+            for k in P[n]:
+                self.P[n][k].copy_(P[n][k])
 
 
 @pytest.mark.parametrize("case", D.SERIES_CASES, ids=D.series_id)
@@ -245,13 +193,13 @@ def test_fused_ddpg_adam_across_four_updates_matches_float64(case):
     power-of-two learning rates; tau = 2^-4.  Moments are observed only through the weights, and the margins are re-established
     between updates: not a free-running trajectory.  tests/test_ddpg_f64_helpers.py runs the same cases on the CPU."""
     shape, betas = case
-    res = D.series_run(_SeriesHandle, shape, betas, device="cuda", cfg=dict(CFG))
+    res = A.run(D.series(shape, betas, device="cuda", cfg=dict(CFG)), _SeriesHandle)
     print("worst/bound %s; smallest rejecting ratio %s" % ({n: "%.3g" % v for n, v in res["worst"].items()}, {k: "%.3g" % v for k, v in res["rejected"].items()}))
     assert max(res["worst"].values()) <= 1.0
 
 
 def test_cn_ddpg_create_and_update_reject_bad_arguments():
-    _abi, L = _lib()
+    _abi, L = lib()
     z = torch.zeros(16, device="cuda")
     m = _abi.CnTd3Mlp(*([z.data_ptr()] * 6))
     for obs_dim, hidden, batch in ((8, 16, 0), (8, 16, 4097), (8, 0, 16), (8, 4097, 16), (0, 16, 16)):
@@ -270,7 +218,7 @@ def test_cn_ddpg_create_and_update_reject_bad_arguments():
         assert b"target_noise" in L.cn_td3_last_error()
         assert L.cn_ddpg_update(k_.h, None, None) != 0                  # no batch and no replay ring
         torch.cuda.synchronize()
-        assert all(_same(P0, k_.P, n) for n in D.NETS)                  # nothing was enqueued
+        assert all(R.same(P0, k_.P, n) for n in D.NETS)                  # nothing was enqueued
     finally:
         k_.close()
 
@@ -284,9 +232,9 @@ def test_two_handles_on_identical_parameters_end_bit_identical():
         for _ in range(4):
             a.update(batch)
             b.update(batch)
-        assert all(_same(a.P, b.P, n) for n in D.NETS)
+        assert all(R.same(a.P, b.P, n) for n in D.NETS)
         assert a.loss() == b.loss()
-        assert not _same(P0, a.P, "critic") and not _same(P0, a.P, "actor_t")
+        assert not R.same(P0, a.P, "critic") and not R.same(P0, a.P, "actor_t")
     finally:
         a.close(); b.close()
 
@@ -318,8 +266,8 @@ def test_replay_path_samples_only_live_rows():
     try:
         for _ in range(3):
             hs[0].update(None); hs[1].update(None); hs[2].update(batch)
-        assert all(_same(hs[0].P, hs[2].P, n) for n in D.NETS)
-        assert all(_same(hs[0].P, hs[1].P, n) for n in D.NETS)
+        assert all(R.same(hs[0].P, hs[2].P, n) for n in D.NETS)
+        assert all(R.same(hs[0].P, hs[1].P, n) for n in D.NETS)
     finally:
         for h in hs:
             h.close()
@@ -331,7 +279,7 @@ def test_replay_path_samples_only_live_rows():
                     h.update(None)
                     assert h.loss() < 1e3, (fill, size, step, h.loss())
                 assert all(bool(torch.isfinite(v).all()) for p in h.P.values() for v in p.values()), (fill, size)
-                assert not _same(P0, h.P, "critic")
+                assert not R.same(P0, h.P, "critic")
             finally:
                 h.close()
 
@@ -351,11 +299,11 @@ def test_graph_capture_of_the_update_replays_bit_for_bit():
         with torch.cuda.graph(g):
             graphed.update(None, sync=False)
         torch.cuda.synchronize()
-        assert all(_same(P0, graphed.P, n) for n in D.NETS)         # capturing ran nothing
+        assert all(R.same(P0, graphed.P, n) for n in D.NETS)         # capturing ran nothing
         for _ in range(3):
             g.replay()
         torch.cuda.synchronize()
-        assert all(_same(eager.P, graphed.P, n) for n in D.NETS)
+        assert all(R.same(eager.P, graphed.P, n) for n in D.NETS)
         assert eager.loss() == graphed.loss()
     finally:
         eager.close(); graphed.close()

@@ -15,6 +15,7 @@ import torch
 
 import dqn_f64 as Q
 import td3_f64 as R
+from learner_handle import LearnerHandle, batch_struct, lib, mlp_struct, ring_fields, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -24,74 +25,39 @@ CN_ERR_CONFIG = -2
 SHAPE_IDS = ["%d|%dx%dx%d" % s for s in Q.UPDATE_SHAPES]
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _mlp(p):
-    _abi, _ = _lib()
-    return _abi.CnTd3Mlp(*[p[k].data_ptr() for k in R.NAMES])
+    return mlp_struct(p, R.NAMES)
 
 
-class Fused:
+class Fused(LearnerHandle):
     """One cn_dqn handle on its own float32 copies of the online and target parameters."""
 
     def __init__(self, p, pt, shape, lr, rho, eps, target_every=1 << 30, learn_start=0, seed=7, replay=None):
-        _abi, L = _lib()
-        self.L, self.shape = L, shape
+        self.shape = shape
         self.p = {k: v.detach().clone().contiguous() for k, v in p.items()}
         self.pt = {k: v.detach().clone().contiguous() for k, v in pt.items()}
-        rp = {}
-        if replay is not None:
-            self._ring = replay
-            rp = dict(replay_s=replay["s"].data_ptr(), replay_a=replay["a"].data_ptr(), replay_r=replay["r"].data_ptr(),
-                      replay_s2=replay["s2"].data_ptr(), replay_d=replay["d"].data_ptr(), replay_size_dev=replay["size"].data_ptr())
         D, ld, H, B = shape
-        self.cfg = _abi.CnDqnConfig(obs_dim=D, obs_ld=ld, hidden=H, batch=B, gamma=GAMMA, lr=lr, rho=rho, eps=eps,
-                                    target_every=target_every, learn_start=learn_start, q=_mlp(self.p), q_t=_mlp(self.pt), seed=seed, **rp)
-        self.h = C.c_void_p()
-        rc = L.cn_dqn_create(C.byref(self.cfg), 0, C.byref(self.h))
-        assert rc == 0, L.cn_td3_last_error()
+        cfg = lib()[0].CnDqnConfig(obs_dim=D, obs_ld=ld, hidden=H, batch=B, gamma=GAMMA, lr=lr, rho=rho, eps=eps, target_every=target_every,
+                                    learn_start=learn_start, q=_mlp(self.p), q_t=_mlp(self.pt), seed=seed, **ring_fields(replay))
+        super().__init__("dqn", cfg, (self.p, self.pt, replay))
 
     def update(self, batch=None, perm=None, sync=True):
-        _abi, L = _lib()
-        bp = None
         if batch is not None:
-            s, a, r, s2, d = batch
             pm = None if perm is None else (perm if torch.is_tensor(perm) else torch.as_tensor(np.asarray(perm), dtype=torch.int32).to(DEV))
-            self._keep = (batch, pm)
-            bp = C.byref(_abi.CnDqnBatch(s.data_ptr(), a.data_ptr(), r.data_ptr(), s2.data_ptr(), d.data_ptr(),
-                                         pm.data_ptr() if pm is not None else None))
-        rc = L.cn_dqn_update(self.h, bp, _stream())
-        assert rc == 0, L.cn_td3_last_error()
-        if sync:
-            torch.cuda.synchronize()
+            batch = batch_struct(tuple(batch) + (pm,), "CnDqnBatch")
+        super().update(batch=batch, sync=sync)
 
     def view(self, what, shape, dtype=torch.float32):
-        from crowdnav.td3 import _device_view
-        torch.cuda.synchronize()
-        return _device_view(self.L.cn_dqn_batch_dev(self.h, what), shape, dtype, torch.device(DEV)).clone()
+        return self.batch_dev(what, shape, {torch.float32: "<f4", torch.int32: "<i4", torch.int64: "<i8"}[dtype])
 
     def loss(self):
-        from crowdnav.td3 import _device_view
-        torch.cuda.synchronize()
-        return _device_view(self.L.cn_dqn_loss_dev(self.h), (2,), torch.float32, torch.device(DEV)).double().cpu().numpy()
+        return super().loss((2,)).double().cpu().numpy()
 
     def flags(self):
         return self.view(5, (8,), torch.int32).cpu().numpy()[:5]
 
     def counter(self):
         return int(self.view(8, (1,), torch.int64)[0])
-
-    def close(self):
-        if self.h:
-            self.L.cn_dqn_destroy(self.h)
-            self.h = None
 
 
 def _same(p0, p1):
@@ -104,14 +70,14 @@ def _fmt(r):
 
 # ---- cn_dqn_act --------------------------------------------------------------------------------------------------------------
 def _act(p, x, D, H, n):
-    _abi, L = _lib()
+    _abi, L = lib()
     q = torch.full((n, 3), float("nan"), device=DEV)
     act = torch.full((n,), -1, dtype=torch.int32, device=DEV)
     tw = torch.zeros((n, 2), device=DEV)
     io = _abi.CnDqnActIO(obs=x.data_ptr(), obs_ld=x.stride(0), n=n, obs_dim=D, hidden=H, reserved=0, q=_mlp(p), epsilon=0.0,
                          epsilon_discount=0.995, epsilon_min=0.05, episodes_dev=None, seed=1, counter=0, action=act.data_ptr(),
                          twist=tw.data_ptr(), q_out=q.data_ptr())
-    rc = L.cn_dqn_act(C.byref(io), 0, _stream())
+    rc = L.cn_dqn_act(C.byref(io), 0, stream())
     torch.cuda.synchronize()
     return rc, q, act, tw
 
@@ -150,7 +116,7 @@ def test_act_q_within_the_forward_bound_and_argmax_of_its_own_q(H):
 def test_act_refuses_hidden_481():
     p, x = Q.act_case(481, 16, 16, 4, device=DEV)
     rc, q, act, _ = _act(p, x, 16, 481, 4)
-    _, L = _lib()
+    _, L = lib()
     assert rc == CN_ERR_CONFIG and b"hidden" in L.cn_td3_last_error()
     assert bool(torch.isnan(q).all()) and bool((act == -1).all())          # nothing was enqueued
 

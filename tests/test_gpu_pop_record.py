@@ -9,19 +9,11 @@ import pytest
 import torch
 
 import pop_record_ref as R
+from learner_handle import lib, stream
 
 pytestmark = pytest.mark.gpu
 
 CN_ERR_ARG = -1
-
-
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _dev(m):
@@ -51,7 +43,7 @@ def _struct(_abi, t, m):
 
 class Recorder:
     def __init__(self, structs, obs_dim):
-        self._abi, self.L = _lib()
+        self._abi, self.L = lib()
         self.arr = (self._abi.CnPopRecordMember * len(structs))(*structs)
         self.h = C.c_void_p()
         rc = self.L.cn_pop_record_create(self.arr, len(structs), obs_dim, 0, C.byref(self.h))
@@ -70,7 +62,7 @@ class Recorder:
         return torch.as_tensor(_Arr(), device="cuda")
 
     def record(self, launch):
-        rc = self.L.cn_pop_record(self.h, float(launch), _stream())
+        rc = self.L.cn_pop_record(self.h, float(launch), stream())
         assert rc == 0, self.L.cn_last_error().decode()
 
     def close(self):
@@ -82,7 +74,7 @@ class Recorder:
 def _reference(t, m, launch):
     """What the call replaces, for one member, in place on t: cn_replay_write and cn_episode_log_add with keep = !resetting, then
     resetting <- done and prev <- obs."""
-    _abi, L = _lib()
+    _abi, L = lib()
     n = m["n"]
     if n == 0:
         return
@@ -91,9 +83,9 @@ def _reference(t, m, launch):
     ring, log = _ring(_abi, t, m), _log(_abi, t, m)
     vp = lambda x: C.c_void_p(x.data_ptr())
     rc = L.cn_replay_write(C.byref(ring), vp(t["prev"]), vp(t["action"]), vp(t["reward"]), vp(t["obs"]), vp(t["done"]), vp(keep), n, vp(slot),
-                           0, _stream())
+                           0, stream())
     assert rc == 0, L.cn_td3_last_error().decode()
-    rc = L.cn_episode_log_add(C.byref(log), vp(t["done"]), vp(t["counters"]), 14, vp(t["last_return"]), vp(keep), float(launch), n, 0, _stream())
+    rc = L.cn_episode_log_add(C.byref(log), vp(t["done"]), vp(t["counters"]), 14, vp(t["last_return"]), vp(keep), float(launch), n, 0, stream())
     assert rc == 0, L.cn_td3_last_error().decode()
     t["resetting"][:n] = t["done"][:n] != 0
     t["prev"][:n] = t["obs"][:n]
@@ -111,7 +103,7 @@ def _run(ms, launches=(7,), mutate=None):
     """Members ms through ONE handle for the given launches, against the per-member kernels on second copies.  The handle's flags are
     written by the caller before the first call and read back after the last.  mutate(t, m, call): new inputs between calls, applied
     to both sides.  Returns (got, want) per member."""
-    _abi, _ = _lib()
+    _abi, _ = lib()
     got, want = [_dev(m) for m in ms], [_dev(m) for m in ms]
     rec = Recorder([_struct(_abi, t, m) for t, m in zip(got, ms)], ms[0]["D"])
     for p, (t, m) in enumerate(zip(got, ms)):
@@ -287,7 +279,7 @@ def test_flags_written_by_the_caller_are_honoured():
 def test_captured_in_a_graph_and_replayed():
     """One direct call, then the call captured on one stream (a single linear branch: two kernel nodes) and replayed twice, against three
     direct calls with the same launch on second copies."""
-    _abi, _ = _lib()
+    _abi, _ = lib()
     ms = _population(15)
     got, want = [_dev(m) for m in ms], [_dev(m) for m in ms]
     rec = Recorder([_struct(_abi, t, m) for t, m in zip(got, ms)], ms[0]["D"])
@@ -316,7 +308,7 @@ def test_captured_in_a_graph_and_replayed():
 def test_the_two_refusals_that_need_a_live_handle():
     from crowdnav import Config
     from crowdnav.env import VecEnv
-    _abi, L = _lib()
+    _abi, L = lib()
     m = R.make_member(np.random.default_rng(16), 4, 398)
     t = _dev(m)
     rec = Recorder([_struct(_abi, t, m)], 398)

@@ -12,6 +12,7 @@ import torch
 
 import replay_distinct_ref as S
 import sampling_f64
+from learner_handle import LearnerHandle, err, lib, ring_fields, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -20,30 +21,11 @@ FAMILIES = ("td3", "ddpg", "dqn", "sac")
 CAP = 8192                                      # the learners' ring: past every live size they are given
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _alias(ptr, shape, typestr="<f4"):
-    class _Arr:
-        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2}
-    return torch.as_tensor(_Arr(), device="cuda")
-
-
-def _err():
-    return _lib()[1].cn_td3_last_error().decode()
-
-
 # ---- cn_replay_sample_indices ---------------------------------------------------------------------------------------------------
 def _sample_indices(seed, counter, B, size_dev, mode, out):
-    _abi, L = _lib()
-    rc = L.cn_replay_sample_indices(seed, counter, B, C.c_void_p(size_dev.data_ptr()), mode, C.c_void_p(out.data_ptr()), 0, _stream())
-    assert rc == 0, _err()
+    _abi, L = lib()
+    rc = L.cn_replay_sample_indices(seed, counter, B, C.c_void_p(size_dev.data_ptr()), mode, C.c_void_p(out.data_ptr()), 0, stream())
+    assert rc == 0, err()
 
 
 @pytest.fixture(scope="module")
@@ -90,13 +72,13 @@ def test_sample_indices_mode_0_equals_the_draw_with_replacement(seam):
 
 
 def test_sample_indices_refusals():
-    _abi, L = _lib()
+    _abi, L = lib()
     size_dev = torch.ones(1, dtype=torch.int64, device="cuda")
     out = torch.zeros(4, dtype=torch.int64, device="cuda")
     sp, op = C.c_void_p(size_dev.data_ptr()), C.c_void_p(out.data_ptr())
     for args, text in (((1, 0, 4, None, 1, op), "null"), ((1, 0, 4, sp, 1, None), "null"), ((1, 0, 0, sp, 1, op), "B < 1"),
                        ((1, 0, 4, sp, 2, op), "mode"), ((1, 0, 4, sp, -1, op), "mode")):
-        assert L.cn_replay_sample_indices(*args, 0, _stream()) == -1 and text in _err(), (args, _err())
+        assert L.cn_replay_sample_indices(*args, 0, stream()) == -1 and text in err(), (args, err())
     torch.cuda.synchronize()
     assert not out.any()
 
@@ -104,7 +86,7 @@ def test_sample_indices_refusals():
 # ---- the four learners ----------------------------------------------------------------------------------------------------------
 def _mlp(g, n_in, H, n_out):
     """(struct, tensors): Linear(n_in, H) - Linear(H, H) - Linear(H, n_out), small weights."""
-    _abi, _ = _lib()
+    _abi, _ = lib()
     shapes = ((H, n_in), (H,), (H, H), (H,), (n_out, H), (n_out,))
     ts = [(torch.randn(s, generator=g) * 0.1).cuda().contiguous() for s in shapes]
     return _abi.CnTd3Mlp(*[t.data_ptr() for t in ts]), ts
@@ -122,21 +104,20 @@ def _ring(n):
                 d=((7 * i) % 5 == 0).float().contiguous(), size=torch.tensor([n], dtype=torch.int64, device="cuda"))
 
 
-class Handle:
+class Handle(LearnerHandle):
     """One learner handle of `family` on its own tiny networks, sampling the ring `rg`."""
 
     def __init__(self, family, B, seed, rg):
-        _abi, L = _lib()
-        self.L, self.family, self.B, self.seed, self.rg = L, family, B, seed, rg
+        _abi, _ = lib()
+        self.B, self.seed, self.rg = B, seed, rg
         g = torch.Generator().manual_seed(1)
-        self._keep = []
+        keep = [rg]
 
         def mlp(n_in, n_out, H=HID):
             st, ts = _mlp(g, n_in, H, n_out)
-            self._keep.append(ts)
+            keep.append(ts)
             return st
-        rp = dict(replay_s=rg["s"].data_ptr(), replay_a=rg["a"].data_ptr(), replay_r=rg["r"].data_ptr(), replay_s2=rg["s2"].data_ptr(),
-                  replay_d=rg["d"].data_ptr(), replay_size_dev=rg["size"].data_ptr(), seed=seed)
+        rp = dict(ring_fields(rg), seed=seed)
         adam = dict(gamma=0.99, beta1=0.9, beta2=0.999, eps=1e-8, max_v=0.22, max_w=2.0)
         if family == "td3":
             cfg = _abi.CnTd3Config(obs_dim=OBS, hidden=HID, batch=B, policy_delay=2, tau=0.005, lr_actor=3e-4, lr_critic=3e-4, noise_std=0.2,
@@ -151,40 +132,26 @@ class Handle:
         else:
             st, ts = _mlp(g, OBS, HID, 2)
             extra = [(torch.randn(s, generator=g) * 0.1).cuda().contiguous() for s in ((2, HID), (2,))]
-            self._keep += [ts, extra]
+            keep += [ts, extra]
             actor = _abi.CnSacActor(*[t.data_ptr() for t in ts + extra])
             cfg = _abi.CnSacConfig(obs_dim=OBS, hidden=HID, hidden_v=2, batch=B, gamma=0.99, tau=5e-3, lr_actor=3e-4, lr_v=3e-4, lr_q=3e-4,
                                    beta1=0.9, beta2=0.999, eps=1e-8, max_v=0.22, max_w=2.0, log_std_min=-20.0, log_std_max=2.0,
                                    mean_lambda=1e-3, std_lambda=1e-3, z_lambda=0.0, logp_eps=1e-6, soft_update=0, reserved=0, actor=actor,
                                    q=mlp(OBS + 2, 1), v=mlp(OBS, 1, 2), v_t=mlp(OBS, 1, 2), **rp)
-        self.cfg, self.h = cfg, C.c_void_p()
-        rc = getattr(L, "cn_%s_create" % family)(C.byref(cfg), 0, C.byref(self.h))
-        assert rc == 0, _err()
-
-    def set_mode(self, mode):
-        return getattr(self.L, "cn_%s_set_replay_sample" % self.family)(self.h, mode)
+        super().__init__(family, cfg, keep)
 
     def update(self, k=0, sync=True):
-        f = getattr(self.L, "cn_%s_update" % self.family)
-        rc = f(self.h, int(k % 2 == 1), None, _stream()) if self.family == "td3" else f(self.h, None, _stream())
-        assert rc == 0, _err()
-        if sync:
-            torch.cuda.synchronize()
-
-    def view(self, what, shape, typestr="<f4"):
-        p = getattr(self.L, "cn_%s_batch_dev" % self.family)(self.h, what)
-        assert p, (self.family, what)
-        return _alias(p, shape, typestr).clone()
+        super().update(*([int(k % 2 == 1)] if self.family == "td3" else []), sync=sync)
 
     def gathered(self):
         """(slots int64 [B], dict of what the update gathered for its B rows) of the last update."""
         B = self.B
         if self.family == "dqn":
-            x = self.view(0, (2 * B, OBS))
-            got = dict(s=x[:B], s2=x[B:], r=self.view(1, (B,)), d=self.view(2, (B,)), a0=self.view(3, (B,), "<i4").float())
+            x = self.batch_dev(0, (2 * B, OBS))
+            got = dict(s=x[:B], s2=x[B:], r=self.batch_dev(1, (B,)), d=self.batch_dev(2, (B,)), a0=self.batch_dev(3, (B,), "<i4").float())
         else:
-            xs, x2 = self.view(0, (B, OBS + 2)), self.view(1, (B, OBS + 2))
-            got = dict(s=xs[:, :OBS], s2=x2[:, :OBS], r=self.view(2, (B,)), d=self.view(3, (B,)), a=xs[:, OBS:])
+            xs, x2 = self.batch_dev(0, (B, OBS + 2)), self.batch_dev(1, (B, OBS + 2))
+            got = dict(s=xs[:, :OBS], s2=x2[:, :OBS], r=self.batch_dev(2, (B,)), d=self.batch_dev(3, (B,)), a=xs[:, OBS:])
         return got["s"][:, 0].long(), got
 
     def check(self, want):
@@ -200,11 +167,6 @@ class Handle:
         else:
             assert torch.equal(got["a0"], rg["a"][w][:, 0]), self.family
 
-    def close(self):
-        if self.h:
-            getattr(self.L, "cn_%s_destroy" % self.family)(self.h)
-            self.h = None
-
 
 def _check_dqn_plan(h, want):
     """flags[2] = F, the number of final rows among the sample; chunk marks exactly B + F stacked rows: the B s rows and the s2 row
@@ -212,8 +174,8 @@ def _check_dqn_plan(h, want):
     B = h.B
     final = (h.rg["d"][torch.from_numpy(want).cuda()] != 0).cpu().numpy()
     F = int(final.sum())
-    flags = h.view(5, (8,), "<i4").cpu().numpy()
-    chunk = h.view(4, (2 * B,), "<i4").cpu().numpy()
+    flags = h.batch_dev(5, (8,), "<i4").cpu().numpy()
+    chunk = h.batch_dev(4, (2 * B,), "<i4").cpu().numpy()
     assert flags[0] == 1 and flags[2] == F and flags[1] == (1 if F else 0), (flags.tolist(), F)
     assert (chunk[:B] != 0).all() and np.array_equal(chunk[B:] != 0, final), (chunk.tolist(), final.tolist())
     assert int((chunk != 0).sum()) == B + F and int((chunk == 1).sum()) == B and int((chunk == 2).sum()) == F
@@ -229,7 +191,7 @@ def test_learners_gather_the_statements_rows(family, n, B):
     seed = 0x243F6A8885A308D3
     h = Handle(family, B, seed, rg)
     try:
-        assert h.set_mode(1) == 0, _err()
+        assert h.set_replay_sample(1) == 0, err()
         for k in range(3):
             h.update(k)
             want = S.rows(seed, k, B, n)
@@ -243,7 +205,7 @@ def test_learners_gather_the_statements_rows(family, n, B):
                 assert set(np.bincount(slot, minlength=n).tolist()) <= {B // n, -(-B // n)}
             if family == "dqn":
                 _check_dqn_plan(h, want)
-                assert int(h.view(8, (2,), "<i4").cpu().numpy().view(np.uint64)[0]) == k + 1
+                assert int(h.batch_dev(8, (2,), "<i4").cpu().numpy().view(np.uint64)[0]) == k + 1
     finally:
         h.close()
 
@@ -253,7 +215,7 @@ def test_live_size_rewritten_on_the_device_between_updates():
     rg = _ring(37)
     h = Handle("td3", B, seed, rg)
     try:
-        assert h.set_mode(1) == 0
+        assert h.set_replay_sample(1) == 0
         h.update(0)
         h.check(S.rows(seed, 0, B, 37))
         rg["size"].fill_(5003)                      # a device-side write, as cn_replay_write's
@@ -272,20 +234,20 @@ def test_default_mode_is_the_draw_with_replacement_and_bad_modes_are_refused(fam
     rg = _ring(n)
     fresh, zero = Handle(family, B, seed, rg), Handle(family, B, seed, rg)
     try:
-        assert zero.set_mode(0) == 0
+        assert zero.set_replay_sample(0) == 0
         for h in (fresh, zero):
             for k in range(2):
                 h.update(k)
                 h.check(sampling_f64.indices(seed, k, B, n))
         h = fresh
         for before in (0, 1):                       # a refused mode leaves the handle's mode alone, whichever it is
-            assert h.set_mode(before) == 0
+            assert h.set_replay_sample(before) == 0
             for bad in (2, -1):
-                assert h.set_mode(bad) == -1 and "cn_%s_set_replay_sample" % family in _err() and "mode" in _err(), _err()
+                assert h.set_replay_sample(bad) == -1 and "cn_%s_set_replay_sample" % family in err() and "mode" in err(), err()
         k = 2
         h.update(k)                                 # still mode 1
         h.check(S.rows(seed, k, B, n))
-        assert getattr(h.L, "cn_%s_set_replay_sample" % family)(None, 1) == -1 and "null handle" in _err()
+        assert getattr(h.L, "cn_%s_set_replay_sample" % family)(None, 1) == -1 and "null handle" in err()
     finally:
         fresh.close(); zero.close()
 
@@ -297,7 +259,7 @@ def test_captured_update_keeps_its_mode_and_follows_the_counter():
     rg = _ring(n)
     h = Handle("td3", B, seed, rg)
     try:
-        assert h.set_mode(1) == 0
+        assert h.set_replay_sample(1) == 0
         for k in range(2):
             h.update(k)
             h.check(S.rows(seed, k, B, n))
@@ -306,7 +268,7 @@ def test_captured_update_keeps_its_mode_and_follows_the_counter():
             h.update(0, sync=False)
         torch.cuda.synchronize()
         h.check(S.rows(seed, 1, B, n))                                  # capturing ran nothing
-        assert h.set_mode(0) == 0
+        assert h.set_replay_sample(0) == 0
         for j in range(3):
             g.replay()
             torch.cuda.synchronize()

@@ -4,6 +4,7 @@ rejected, argument checks, determinism, the replay path, a hipGraph capture, the
 `-s` prints the worst error / bound of every quantity."""
 import csv
 import ctypes as C
+import functools
 import glob
 import math
 import os
@@ -12,8 +13,11 @@ import numpy as np
 import pytest
 import torch
 
+import adam_series as A
 import sac_f64 as S
 import td3_f64 as R
+from learner_handle import LearnerHandle, batch_struct, lib
+from replay_distinct_ref import _mix_int
 
 pytestmark = pytest.mark.gpu
 
@@ -26,53 +30,22 @@ SHAPES = [                                             # (obs_dim, hidden, hidde
 DISCRIMINATE = ((46, 32, 2, 16), (45, 33, 3, 40), (363, 256, 2, 64))
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
-class Fused:
+class Fused(LearnerHandle):
     """One cn_sac handle on its own float32 copies of the parameters (a dict as tests/sac_f64.py's)."""
 
     def __init__(self, P, shape, lr=3e-4, replay=None, soft_update=0, tau=5e-3, seed=7, **over):
-        _abi, L = _lib()
-        self.L, self.shape = L, shape
+        self.shape = shape
         self.P = {n: {k: v.detach().clone().float().cuda().contiguous() for k, v in p.items()} for n, p in P.items()}
-        mlp = lambda n: _abi.CnTd3Mlp(*[self.P[n][k].data_ptr() for k in S.NAMES])
-        rp = {}
-        if replay is not None:
-            rp = dict(replay_s=replay["s"].data_ptr(), replay_a=replay["a"].data_ptr(), replay_r=replay["r"].data_ptr(),
-                      replay_s2=replay["s2"].data_ptr(), replay_d=replay["d"].data_ptr(), replay_size_dev=replay["size"].data_ptr())
-        c = S.CFG
-        kw = dict(obs_dim=shape[0], hidden=shape[1], hidden_v=shape[2], batch=shape[3], gamma=c["gamma"], tau=tau, lr_actor=lr, lr_v=lr,
-                  lr_q=lr, beta1=0.9, beta2=0.999, eps=1e-8, max_v=c["max_v"], max_w=c["max_w"], log_std_min=c["ls_min"],
-                  log_std_max=c["ls_max"], mean_lambda=c["mean_lambda"], std_lambda=c["std_lambda"], z_lambda=c["z_lambda"],
-                  logp_eps=c["logp_eps"], soft_update=soft_update, reserved=0,
-                  actor=_abi.CnSacActor(*[self.P["actor"][k].data_ptr() for k in S.ACTOR_NAMES]), q=mlp("q"), v=mlp("v"), v_t=mlp("v_t"), seed=seed)
-        kw.update(rp); kw.update(over)
-        self.cfg = _abi.CnSacConfig(**kw)
-        self.h = C.c_void_p()
-        rc = L.cn_sac_create(C.byref(self.cfg), 0, C.byref(self.h))
-        assert rc == 0, L.cn_td3_last_error()
+        super().__init__("sac", S.handle_config(self.P, shape, lr, replay, soft_update, tau, seed, **over), (self.P, replay))
 
     def update(self, batch, eps=None, sync=True):
-        _abi, L = _lib()
-        bp = None
-        if batch is not None:
-            self._keep = (batch, eps)
-            bp = C.byref(_abi.CnTd3Batch(*[x.data_ptr() for x in batch], eps.data_ptr() if eps is not None else None))
-        rc = L.cn_sac_update(self.h, bp, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        assert rc == 0, L.cn_td3_last_error()
-        if sync:
-            torch.cuda.synchronize()
+        super().update(batch=None if batch is None else batch_struct(tuple(batch) + (eps,)), sync=sync)
 
     def dev(self, what, shape):
-        from crowdnav._fused import _device_view
-        return _device_view(self.L.cn_sac_batch_dev(self.h, what), shape, torch.float32, torch.device("cuda:0")).cpu().double()
+        return self.batch_dev(what, shape).cpu().double()
 
     def loss(self):
-        from crowdnav._fused import _device_view
-        return _device_view(self.L.cn_sac_loss_dev(self.h), (3,), torch.float32, torch.device("cuda:0")).cpu().double()
+        return super().loss((3,)).cpu().double()
 
     def rows(self):
         B = self.shape[3]
@@ -80,14 +53,8 @@ class Fused:
         return dict(mean=rec[:, 0:2], log_std=rec[:, 2:4], raw=rec[:, 4:6], z=rec[:, 6:8], logp=rec[:, 8], qn=rec[:, 9], a_new=rec[:, 10:12],
                     dl=self.dev(6, (B, 4)), dq=self.dev(7, (B,)), dv=self.dev(8, (B,)), loss=self.loss())
 
-    def close(self):
-        if self.h:
-            self.L.cn_sac_destroy(self.h)
-            self.h = None
 
-
-def _cuda(batch):
-    return tuple(x.float().cuda().contiguous() for x in batch)
+_cuda, _reference = S.cuda, functools.partial(S.reference, device="cuda")
 
 
 def _same(Pa, Pb):
@@ -125,25 +92,13 @@ def test_fused_sac_update_on_the_reference_learn_goldens():
         f.close()
 
 
-def _pow2_at_least(x):
-    return 2.0 ** math.ceil(math.log2(max(x, 2.0 ** -60)))
-
-
-def _reference(P, batch, eps, **kw):
-    """sac_f64.reference on the device in float64 -> everything on the CPU."""
-    P64 = {n: {k: v.double().cuda() for k, v in p.items()} for n, p in P.items()}
-    want, bound = S.reference(P64, tuple(x.double().cuda() for x in batch), eps.double().cuda(),
-                              eps_first=kw.pop("eps_first").double().cuda() if "eps_first" in kw else None, **kw)
-    return {k: v.cpu() for k, v in want.items()}, {k: v.cpu() for k, v in bound.items()}
-
-
 def _run_case(shape):
     """One update with beta1 = beta2 = 0 (w' = w - lr g / (|g| + eps): invertible per element), eps = a power of two >= every
     gradient element, each optimiser's lr as large against its own gradients as Q's.  -> the case, the float64 reference and its
     bounds, the kernel's rows, its recovered weight gradients {(net, name): g} and their inversion bounds, V_t before, P after."""
     P, batch, eps, eps1, chain = S.make_case(*shape)
     want, Bd = _reference(P, batch, eps)
-    top = {n: _pow2_at_least(max(float(want[k].abs().max()) for k in S.GRADS if k[0] == n)) for n in ("q", "v", "actor")}
+    top = {n: A.pow2_at_least(max(float(want[k].abs().max()) for k in S.GRADS if k[0] == n)) for n in ("q", "v", "actor")}
     e_ = max(top.values())
     lr = {n: LR * e_ / top[n] for n in top}
     f = Fused(P, shape, soft_update=1, tau=2.0 ** -4, lr_q=lr["q"], lr_v=lr["v"], lr_actor=lr["actor"], eps=e_, beta1=0.0, beta2=0.0)
@@ -211,7 +166,7 @@ def test_fused_sac_rows_losses_and_gradients_match_float64(shape):
     assert all(bool(torch.isfinite(v).all()) for p in P1.values() for v in p.values())
 
 
-SCALE_ERR = 1e-3
+SCALE_ERR = S.SCALE_ERR
 SCALED = ("dl", "dq", "dv", "loss") + S.GRADS
 
 
@@ -278,7 +233,7 @@ def test_soft_update_as_written_pulls_the_stepped_v_and_leaves_the_target(shape)
 
 
 def test_cn_sac_create_update_and_act_reject_bad_arguments():
-    _abi, L = _lib()
+    _abi, L = lib()
     shape = (20, 16, 2, 8)
     P, batch, eps, _, _ = S.make_case(*shape)
     err = lambda: L.cn_td3_last_error().decode()
@@ -332,7 +287,7 @@ def test_two_handles_on_identical_parameters_end_bit_identical():
         a.close(); b.close()
 
 
-_mix64 = S._mix64          # cn_mix64: stated once, in tests/sac_f64.py
+_mix64 = _mix_int           # cn_mix64 on Python ints: stated once, in tests/actor_f64.py
 
 
 def test_replay_path_samples_only_live_rows_and_its_eps_is_the_documented_draw():

@@ -13,7 +13,8 @@ import torch
 
 import sac_f64 as S
 import td3_f64 as R
-from test_gpu_sac import SCALE_ERR
+from learner_handle import lib, stream
+from sac_f64 import SCALE_ERR
 
 pytestmark = pytest.mark.gpu
 
@@ -25,11 +26,6 @@ OUTS = ("mean", "log_std", "z")
 c = S.CFG
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
 def _dev(pa):
     return {k: v.detach().float().to(DEV).contiguous() for k, v in pa.items()}
 
@@ -37,7 +33,7 @@ def _dev(pa):
 def _act(pd, obs, D, H, n, eps=None, det=False, seed=1, counter=0, outs=OUTS, expect=0, **over):
     """One cn_sac_act on device tensors -> {twist, mean, log_std, z} (the first n rows of each buffer asked for).  The SPARE rows
     behind them must keep every bit; with expect != 0 the call must be refused with that code and ALL rows keep every bit."""
-    _abi, L = _lib()
+    _abi, L = lib()
     buf = {k: torch.full((n + SPARE, 2), SENTINEL, device=DEV) for k in ("twist",) + tuple(outs)}
     ptr = lambda k: buf[k].data_ptr() if k in buf else None
     kw = dict(obs=obs.data_ptr(), obs_ld=obs.stride(0), n=n, obs_dim=D, hidden=H, deterministic=int(det),
@@ -45,7 +41,7 @@ def _act(pd, obs, D, H, n, eps=None, det=False, seed=1, counter=0, outs=OUTS, ex
               log_std_min=c["ls_min"], log_std_max=c["ls_max"], eps=eps.data_ptr() if eps is not None else None, seed=seed, counter=counter,
               twist=ptr("twist"), mean=ptr("mean"), log_std=ptr("log_std"), z=ptr("z"))
     kw.update(over)
-    rc = L.cn_sac_act(C.byref(_abi.CnSacActIO(**kw)), 0, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    rc = L.cn_sac_act(C.byref(_abi.CnSacActIO(**kw)), 0, stream())
     torch.cuda.synchronize()
     assert rc == expect, (rc, L.cn_td3_last_error())
     keep = 0 if expect else n
@@ -246,7 +242,7 @@ def test_the_agents_call_counter_keys_its_draws():
 
 
 def test_act_refuses_hidden_481_and_a_reversed_clamp_with_nothing_enqueued():
-    _, L = _lib()
+    _, L = lib()
     g = torch.Generator().manual_seed(3)
     for H, over, text in ((481, {}, b"hidden <= 480"), (32, dict(log_std_min=3.0), b"log_std_min > log_std_max")):
         pd = _dev(S.new_params(16, H, 1, g)["actor"])

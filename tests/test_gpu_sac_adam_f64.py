@@ -1,4 +1,4 @@
-"""cn_sac_update's Adam across four updates against the float64 series of tests/sac_f64.py (series_run): the tick's step count
+"""cn_sac_update's Adam across four updates against the float64 series of tests/sac_f64.py (adam_series.run): the tick's step count
 and three bias-correction pairs, the moments of Q, V, the actor's trunk and its two head jobs, and V's soft update in both
 soft_update modes, observed through every weight read back before and after every update; then a new handle on the stepped
 parameters (fresh state at create).  Each wrong restatement of the series (sac_f64.SERIES_VARIANTS) must be rejected on the
@@ -7,32 +7,32 @@ tests/test_sac_f64_helpers.py runs the same cases on the CPU with the kernel's f
 `-s` prints the worst error / bound per network and update and every variant's ratios."""
 import pytest
 
+import adam_series as A
 import sac_f64 as S
-from test_gpu_sac import Fused, _cuda, _reference
+from learner_handle import LearnerHandle, batch_struct
 
 pytestmark = pytest.mark.gpu
 
 
-class Handle:
-    """sac_f64.series_run's learner: one cn_sac handle; write() copies into the tensors whose pointers the handle holds."""
+class Handle(LearnerHandle):
+    """adam_series.run's learner: one cn_sac handle; write() copies into the tensors whose pointers the handle holds."""
 
     def __init__(self, P, shape, hp):
-        self.f = Fused(P, shape, soft_update=hp["soft_update"], tau=hp["tau"], lr_q=hp["lr_q"], lr_v=hp["lr_v"], lr_actor=hp["lr_actor"],
-                       eps=hp["eps"], beta1=hp["beta1"], beta2=hp["beta2"])
+        self.P = {n: {k: v.detach().clone().float().cuda().contiguous() for k, v in p.items()} for n, p in P.items()}
+        cfg = S.handle_config(self.P, shape, soft_update=hp["soft_update"], tau=hp["tau"], lr_q=hp["lr_q"], lr_v=hp["lr_v"],
+                              lr_actor=hp["lr_actor"], eps=hp["eps"], beta1=hp["beta1"], beta2=hp["beta2"])
+        super().__init__("sac", cfg, self.P)
 
     def read(self):
-        return {n: {k: v.cpu() for k, v in p.items()} for n, p in self.f.P.items()}
+        return {n: {k: v.cpu() for k, v in p.items()} for n, p in self.P.items()}
 
     def write(self, P):
         for n in P:
             for k in P[n]:
-                self.f.P[n][k].copy_(P[n][k])
+                self.P[n][k].copy_(P[n][k])
 
     def update(self, batch, eps):
-        self.f.update(_cuda(batch), eps.float().cuda().contiguous())
-
-    def close(self):
-        self.f.close()
+        super().update(batch=batch_struct(S.cuda(batch) + (eps.float().cuda().contiguous(),)))
 
 
 @pytest.mark.parametrize("case", S.SERIES_CASES, ids=S.series_id)
@@ -46,6 +46,6 @@ def test_fused_sac_adam_across_four_updates_matches_float64(case):
     Moments are observed only through the weights, and the margins are re-planted between updates: this is not a free-running
     trajectory."""
     shape, betas, mode, clamp_all = case
-    res = S.series_run(Handle, shape, betas, mode, reference_fn=_reference, clamp_all=clamp_all)
+    res = A.run(S.series(shape, betas, mode, clamp_all, device="cuda"), Handle)
     print("worst/bound %s; smallest rejecting ratio %s" % ({n: "%.3g" % v for n, v in res["worst"].items()}, {k: "%.3g" % v for k, v in res["rejected"].items()}))
     assert max(res["worst"].values()) <= 1.0

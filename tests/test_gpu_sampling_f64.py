@@ -6,8 +6,6 @@ noise element by element within its float64 allowance, at the generator's extrem
 breaking the allowance; the gathered batch being what the update's GEMMs consumed; and the Python agents' wiring of seed and live
 size.  The networks are tiny (obs_dim 4, hidden 8): the GEMMs do not matter here.  `-s` prints the worst noise error / allowance
 of every setting and the number of indices compared."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -15,6 +13,7 @@ import torch
 import ddpg_f64 as D
 import sampling_f64 as S
 import td3_f64 as R
+from learner_handle import LearnerHandle, alias, batch_struct, lib, mlp_struct, ring_fields
 
 pytestmark = pytest.mark.gpu
 
@@ -23,86 +22,39 @@ CFG = dict(gamma=0.99, tau=0.005, lr_actor=3e-4, lr_critic=3e-4, beta1=0.9, beta
 COUNT = dict(indices=0)
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _alias(ptr, shape):
-    class _Arr:
-        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
-    return torch.as_tensor(_Arr(), device="cuda")
-
-
 def _bits(t):
     return t.contiguous().view(torch.int32)
 
 
-class Handle:
+class Handle(LearnerHandle):
     """One cn_td3 / cn_ddpg handle on its own copies of the parameters; `ring` (dict of device tensors, "size" an int64 [1]) or
     None for explicit batches only."""
 
     def __init__(self, algo, B, seed, ring=None, noise_std=0.2, noise_clip=0.5, P=None, pseed=0):
-        _abi, L = _lib()
-        self.L, self.algo, self.B, self.seed = L, algo, B, seed
+        self.algo, self.B, self.seed = algo, B, seed
         if P is None:
             g = torch.Generator().manual_seed(pseed)
             P = R.new_params(OBS, HID, g, dtype=torch.float32, device="cuda") if algo == "td3" else D.new_params(OBS, HID, g, device="cuda")
         self.P = {n: {k: v.detach().clone().contiguous() for k, v in p.items()} for n, p in P.items()}
-        mlp = lambda n: _abi.CnTd3Mlp(*[self.P[n][k].data_ptr() for k in R.NAMES])
-        rp = {}
-        if ring is not None:
-            rp = dict(replay_s=ring["s"].data_ptr(), replay_a=ring["a"].data_ptr(), replay_r=ring["r"].data_ptr(),
-                      replay_s2=ring["s2"].data_ptr(), replay_d=ring["d"].data_ptr(), replay_size_dev=ring["size"].data_ptr())
-        self.h = C.c_void_p()
+        kw = dict(CFG, obs_dim=OBS, hidden=HID, batch=B, seed=seed, **{n: mlp_struct(self.P[n], R.NAMES) for n in self.P}, **ring_fields(ring))
         if algo == "td3":
-            self.cfg = _abi.CnTd3Config(obs_dim=OBS, hidden=HID, batch=B, policy_delay=2, noise_std=noise_std, noise_clip=noise_clip,
-                                        reserved=0.0, actor=mlp("actor"), actor_t=mlp("actor_t"), q1=mlp("q1"), q1_t=mlp("q1_t"),
-                                        q2=mlp("q2"), q2_t=mlp("q2_t"), seed=seed, **CFG, **rp)
-            rc = L.cn_td3_create(C.byref(self.cfg), 0, C.byref(self.h))
+            cfg = lib()[0].CnTd3Config(policy_delay=2, noise_std=noise_std, noise_clip=noise_clip, reserved=0.0, **kw)
         else:
-            self.cfg = _abi.CnDdpgConfig(obs_dim=OBS, hidden=HID, batch=B, actor=mlp("actor"), actor_t=mlp("actor_t"),
-                                         critic=mlp("critic"), critic_t=mlp("critic_t"), seed=seed, **CFG, **rp)
-            rc = L.cn_ddpg_create(C.byref(self.cfg), 0, C.byref(self.h))
-        assert rc == 0, L.cn_td3_last_error()
+            cfg = lib()[0].CnDdpgConfig(**kw)
+        super().__init__(algo, cfg, (self.P, ring))
 
     def update(self, batch=None, do_actor=True, sync=True):
-        _abi, L = _lib()
-        bp = None
-        if batch is not None:
-            self._keep = batch
-            bp = C.byref(_abi.CnTd3Batch(*[x.data_ptr() if x is not None else None for x in batch]))
-        if self.algo == "td3":
-            rc = L.cn_td3_update(self.h, int(do_actor), bp, _stream())
-        else:
-            rc = L.cn_ddpg_update(self.h, bp, _stream())
-        assert rc == 0, L.cn_td3_last_error()
-        if sync:
-            torch.cuda.synchronize()
+        super().update(*([int(do_actor)] if self.algo == "td3" else []), batch=batch_struct(batch), sync=sync)
 
     def ptr(self, what):
-        f = self.L.cn_td3_batch_dev if self.algo == "td3" else self.L.cn_ddpg_batch_dev
-        return f(self.h, what)
+        return self._f("batch_dev")(self.h, what)
 
     def view(self, what):
         """A copy of the gathered buffer `what` (0: [s|a], 1: [s2|.], 2: r, 3: d, 4: noise)."""
-        shape = {0: (self.B, OBS + 2), 1: (self.B, OBS + 2), 2: (self.B,), 3: (self.B,), 4: (self.B, 2)}[what]
-        p = self.ptr(what)
-        assert p, (self.algo, what)
-        return _alias(p, shape).clone()
+        return self.batch_dev(what, {0: (self.B, OBS + 2), 1: (self.B, OBS + 2), 2: (self.B,), 3: (self.B,), 4: (self.B, 2)}[what])
 
     def loss(self):
-        f = self.L.cn_td3_loss_dev if self.algo == "td3" else self.L.cn_ddpg_loss_dev
-        return _alias(f(self.h), (1,)).clone()
-
-    def close(self):
-        if self.h:
-            (self.L.cn_td3_destroy if self.algo == "td3" else self.L.cn_ddpg_destroy)(self.h)
-            self.h = None
+        return super().loss((1,))
 
 
 @pytest.fixture(scope="module")
@@ -136,7 +88,7 @@ def _check_indices(h, rg, k, size):
 
 
 def test_batch_view_arguments():
-    _abi, L = _lib()
+    _abi, L = lib()
     for f in (L.cn_td3_batch_dev, L.cn_ddpg_batch_dev):
         for what in (-1, 0, 4, 5):
             assert f(None, what) is None
@@ -353,7 +305,7 @@ def test_agent_replay_indices_follow_the_statement(algo):
     ring wraps, learn() between the writes: update k samples S.indices(agent._noise_seed, k, B, live size at that moment), and
     every sampled slot holds the transition the host expects there.  Catches a replay_size_dev bound to the wrong scalar and a
     seed other than the documented one."""
-    _abi, L = _lib()
+    _abi, L = lib()
     if algo == "td3":
         from crowdnav.td3 import Agent
     else:
@@ -385,7 +337,7 @@ def test_agent_replay_indices_follow_the_statement(algo):
         if loss is None:
             continue
         torch.cuda.synchronize()
-        xs = _alias(view(hnd, 0), (B, OBS + 2)).clone()
+        xs = alias(view(hnd, 0), (B, OBS + 2)).clone()
         got_t = ((xs[:, 0].long() << 12) + xs[:, 1].long()).cpu().numpy()
         want = S.indices(agent._noise_seed, k, B, live)
         assert np.array_equal(got_t % cap, want), (algo, launch, k, live)

@@ -9,12 +9,13 @@ unambiguous by construction (td3_f64.establish_margins) and dead units are plant
 `-s` prints the worst error / bound of every tensor."""
 import copy
 import ctypes as C
-import math
 
 import pytest
 import torch
 
+import adam_series as A
 import td3_f64 as R
+from learner_handle import LearnerHandle, batch_struct, lib, mlp_struct, ring_fields
 
 pytestmark = pytest.mark.gpu
 
@@ -36,11 +37,6 @@ SHAPES = [
 ALL_DONE = (45, 17, 40)                                # y = r in every row
 DISCRIMINATE = ((398, 256, 128), (45, 33, 40))         # the wrong-variant checks
 SCALE_ERR = 1e-3                                      # the uniform gradient scale error the DISCRIMINATE shapes must reject
-
-
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
 
 
 def make_case(shape, seed=0, margins=True):
@@ -65,63 +61,22 @@ def make_case(shape, seed=0, margins=True):
     return P, batch, N, dead, rep
 
 
-class Fused:
+class Fused(LearnerHandle):
     """One cn_td3 handle on its own float32 copies of the parameters."""
 
     def __init__(self, P, shape, lr_c, lr_a, eps, beta1=0.0, beta2=0.0, tau=CFG["tau"], replay=None, noise_std=CFG["noise_std"]):
-        _abi, L = _lib()
-        self.L = L
         self.P = {n: {k: v.detach().clone().contiguous() for k, v in p.items()} for n, p in P.items()}
-        mlp = lambda n: _abi.CnTd3Mlp(*[self.P[n][k].data_ptr() for k in R.NAMES])
-        rp = dict(replay_s=None, replay_a=None, replay_r=None, replay_s2=None, replay_d=None, replay_size_dev=None)
-        if replay is not None:
-            rp = dict(replay_s=replay["s"].data_ptr(), replay_a=replay["a"].data_ptr(), replay_r=replay["r"].data_ptr(),
-                      replay_s2=replay["s2"].data_ptr(), replay_d=replay["d"].data_ptr(), replay_size_dev=replay["size"].data_ptr())
-        self.cfg = _abi.CnTd3Config(obs_dim=shape[0], hidden=shape[1], batch=shape[2], policy_delay=2, gamma=CFG["gamma"], tau=tau,
-                                    lr_actor=lr_a, lr_critic=lr_c, beta1=beta1, beta2=beta2, eps=eps, noise_std=noise_std,
-                                    noise_clip=CFG["noise_clip"], max_v=CFG["max_v"], max_w=CFG["max_w"], reserved=0.0,
-                                    actor=mlp("actor"), actor_t=mlp("actor_t"), q1=mlp("q1"), q1_t=mlp("q1_t"), q2=mlp("q2"),
-                                    q2_t=mlp("q2_t"), seed=7, **rp)
-        self.h = C.c_void_p()
-        rc = L.cn_td3_create(C.byref(self.cfg), 0, C.byref(self.h))
-        assert rc == 0, L.cn_td3_last_error()
+        cfg = lib()[0].CnTd3Config(obs_dim=shape[0], hidden=shape[1], batch=shape[2], policy_delay=2, gamma=CFG["gamma"], tau=tau,
+                                   lr_actor=lr_a, lr_critic=lr_c, beta1=beta1, beta2=beta2, eps=eps, noise_std=noise_std,
+                                   noise_clip=CFG["noise_clip"], max_v=CFG["max_v"], max_w=CFG["max_w"], reserved=0.0, seed=7,
+                                   **{n: mlp_struct(self.P[n], R.NAMES) for n in R.NETS}, **ring_fields(replay))
+        super().__init__("td3", cfg, (self.P, replay))
 
     def update(self, batch, do_actor):
-        _abi, L = _lib()
-        bp = None
-        if batch is not None:
-            self._keep = batch
-            bp = C.byref(_abi.CnTd3Batch(*[x.data_ptr() for x in batch]))
-        rc = L.cn_td3_update(self.h, int(do_actor), bp, C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        assert rc == 0, L.cn_td3_last_error()
-        torch.cuda.synchronize()
+        super().update(int(do_actor), batch=batch_struct(batch))
 
     def loss(self):
-        from crowdnav.td3 import _device_scalar_view
-        return float(_device_scalar_view(self.L.cn_td3_loss_dev(self.h), torch.device("cuda")))
-
-    def close(self):
-        if self.h:
-            self.L.cn_td3_destroy(self.h)
-            self.h = None
-
-
-def _pow2_at_least(x):
-    return 2.0 ** math.ceil(math.log2(max(x, 2.0 ** -60)))
-
-
-def _recover(P0, P1, net, lr, eps):
-    g = {k: R.invert_step(P0[net][k], P1[net][k], lr, eps) for k in R.NAMES}
-    extra = {k: R.inversion_bound(g[k], P0[net][k], P1[net][k], lr, eps) for k in R.NAMES}
-    return g, extra
-
-
-def _accept(ratios):
-    return max(ratios.values()) <= 1.0
-
-
-def _same(P0, P1, net):
-    return all(torch.equal(P0[net][k], P1[net][k]) for k in R.NAMES)
+        return float(super().loss())
 
 
 def _check_soft(P0, P1, tgt, src, tau, report, label):
@@ -141,23 +96,6 @@ def _check_soft(P0, P1, tgt, src, tau, report, label):
 def _tightness(ref):
     """sum of the bound over sum of |g|, worst tensor: how wide the tolerance is relative to the gradient"""
     return max([float(ref["bound"][k].sum() / ref["g"][k].abs().sum()) for k in R.NAMES if bool((ref["g"][k] != 0).any())] or [0.0])
-
-
-def _rejects_gross(g, ref, extra, net):
-    """at every shape: a zero gradient (a network that is never stepped) and one twice too large are rejected"""
-    if any(bool((v != 0).any()) for v in ref["g"].values()):
-        assert not _accept(R.compare_grads(g, {k: torch.zeros_like(v) for k, v in ref["g"].items()}, ref["bound"], extra)), net
-        assert not _accept(R.compare_grads(g, {k: 2 * v for k, v in ref["g"].items()}, ref["bound"], extra)), net
-
-
-def _check_dead(P0, P1, net, dead):
-    if net not in dead:
-        return
-    u1, u2 = dead[net]
-    for a, b in ((P0[net]["w1"][u1], P1[net]["w1"][u1]), (P0[net]["b1"][u1], P1[net]["b1"][u1]),
-                 (P0[net]["w2"][:, u1], P1[net]["w2"][:, u1]), (P0[net]["w2"][u2], P1[net]["w2"][u2]),
-                 (P0[net]["b2"][u2], P1[net]["b2"][u2]), (P0[net]["w3"][:, u2], P1[net]["w3"][:, u2])):
-        assert torch.equal(a, b), net
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=["%dx%dx%d" % s for s in SHAPES])
@@ -189,7 +127,7 @@ def _gradients_losses_and_soft_updates(shape, report):
         assert torch.equal(t["y"], b64[2])
     lg = R.actor_fwd(P64["actor"], b64[0], CFG)["logits"]
     assert float(lg.abs().max()) >= 7.0
-    eps_c = _pow2_at_least(max(float(ref[n]["g"][k].abs().max()) for n in ("q1", "q2") for k in R.NAMES))
+    eps_c = A.pow2_at_least(max(float(ref[n]["g"][k].abs().max()) for n in ("q1", "q2") for k in R.NAMES))
     for do_actor in (0, 1):
         k_ = Fused(P0, shape, LR, 0.0, eps_c)
         k_.update(batch, do_actor)
@@ -199,51 +137,51 @@ def _gradients_losses_and_soft_updates(shape, report):
         l1 = float(ref["l1"])
         report.append("loss %.9g float64 %.9g (relative %.2g)" % (loss, l1, abs(loss - l1) / abs(l1)))
         assert abs(loss - l1) <= 1e-5 * abs(l1), (loss, l1)
-        assert _same(P0, P1, "actor")
+        assert R.same(P0, P1, "actor")
         for net in ("q1", "q2"):
-            g, extra = _recover(P0, P1, net, LR, eps_c)
+            g, extra = R.recover(P0, P1, net, LR, eps_c)
             ratios = R.compare_grads(g, ref[net]["g"], ref[net]["bound"], extra)
             report.append("critic do_actor=%d %-7s worst/bound " % (do_actor, net) + " ".join("%s %.3g" % kv for kv in ratios.items())
                           + "   bound/|g| %.2g" % _tightness(ref[net]))
-            assert _accept(ratios), (net, ratios)
-            _check_dead(P0, P1, net, dead)
-            _rejects_gross(g, ref[net], extra, net)
+            assert R.accept(ratios), (net, ratios)
+            R.check_dead(P0, P1, net, dead)
+            R.rejects_gross(g, ref[net], extra, net)
             if shape in DISCRIMINATE and do_actor == 0:
                 scaled = {kk: v * (1 + SCALE_ERR) for kk, v in ref[net]["g"].items()}
                 tiled = dict(ref[net]["g"], w2=R.zero_tile(ref[net]["g"]["w2"]))
-                assert not _accept(R.compare_grads(g, scaled, ref[net]["bound"], extra)), "x (1 + %g) accepted" % SCALE_ERR
-                assert not _accept(R.compare_grads(g, tiled, ref[net]["bound"], extra)), "zeroed tile accepted"
+                assert not R.accept(R.compare_grads(g, scaled, ref[net]["bound"], extra)), "x (1 + %g) accepted" % SCALE_ERR
+                assert not R.accept(R.compare_grads(g, tiled, ref[net]["bound"], extra)), "zeroed tile accepted"
                 if net == "q1":
                     wy = R.critic_grads(P64, b64, CFG, y_from="q1t")
-                    assert not _accept(R.compare_grads(g, wy["q1"]["g"], wy["q1"]["bound"], extra)), "y from Q1_t alone accepted"
+                    assert not R.accept(R.compare_grads(g, wy["q1"]["g"], wy["q1"]["bound"], extra)), "y from Q1_t alone accepted"
         if do_actor:
             wrong = [_check_soft(P0, P1, tg, src, CFG["tau"], report, "critic call")
                      for tg, src in (("q1_t", "q1"), ("q2_t", "q2"), ("actor_t", "actor"))]
             assert min(wrong[:2]) > 100.0              # the pre-step soft update fails by orders of magnitude
         else:
-            assert all(_same(P0, P1, n) for n in ("q1_t", "q2_t", "actor_t"))
+            assert all(R.same(P0, P1, n) for n in ("q1_t", "q2_t", "actor_t"))
     # the actor's gradient: lr_critic = 0, so Q1 is the critic the actor loss runs through
     refa = R.actor_grads(P64, b64[0], CFG, N_mask=N)
     assert refa["flip_rows"] == 0
-    eps_a = _pow2_at_least(max(float(refa["g"][k].abs().max()) for k in R.NAMES))
+    eps_a = A.pow2_at_least(max(float(refa["g"][k].abs().max()) for k in R.NAMES))
     k_ = Fused(P0, shape, 0.0, LR, eps_a)
     k_.update(batch, 1)
     P1 = k_.P
     k_.close()
-    assert _same(P0, P1, "q1") and _same(P0, P1, "q2")
-    g, extra = _recover(P0, P1, "actor", LR, eps_a)
+    assert R.same(P0, P1, "q1") and R.same(P0, P1, "q2")
+    g, extra = R.recover(P0, P1, "actor", LR, eps_a)
     ratios = R.compare_grads(g, refa["g"], refa["bound"], extra)
     report.append("actor             worst/bound " + " ".join("%s %.3g" % kv for kv in ratios.items())
                   + "   bound/|g| %.2g" % _tightness(refa))
-    assert _accept(ratios), ratios
-    _check_dead(P0, P1, "actor", dead)
-    _rejects_gross(g, refa, extra, "actor")
+    assert R.accept(ratios), ratios
+    R.check_dead(P0, P1, "actor", dead)
+    R.rejects_gross(g, refa, extra, "actor")
     if hidden >= 4:    # (hidden 1: the lone Q1 unit can be inactive on every (s, pi(s)) row, and the actor's gradient exactly 0)
         assert any(bool((v != 0).any()) for v in refa["g"].values())
     if shape in DISCRIMINATE:
         scaled = {kk: v * (1 + SCALE_ERR) for kk, v in refa["g"].items()}
-        assert not _accept(R.compare_grads(g, scaled, refa["bound"], extra)), "actor x (1 + %g) accepted" % SCALE_ERR
-        assert not _accept(R.compare_grads(g, dict(refa["g"], w2=R.zero_tile(refa["g"]["w2"])), refa["bound"], extra))
+        assert not R.accept(R.compare_grads(g, scaled, refa["bound"], extra)), "actor x (1 + %g) accepted" % SCALE_ERR
+        assert not R.accept(R.compare_grads(g, dict(refa["g"], w2=R.zero_tile(refa["g"]["w2"])), refa["bound"], extra))
     for tg, src in (("q1_t", "q1"), ("q2_t", "q2"), ("actor_t", "actor")):
         _check_soft(P0, P1, tg, src, CFG["tau"], report, "actor call")
 
@@ -258,7 +196,7 @@ def test_fused_td3_adam_across_four_updates_matches_float64(shape):
     P0, batch, N, dead, _ = make_case(shape, seed=5)
     b64 = R.batch_double(batch)
     ref0 = R.critic_grads(R.to64(P0), b64, CFG)
-    eps = 2 * _pow2_at_least(max(float(ref0[n]["g"][k].abs().max()) for n in ("q1", "q2") for k in R.NAMES))
+    eps = 2 * A.pow2_at_least(max(float(ref0[n]["g"][k].abs().max()) for n in ("q1", "q2") for k in R.NAMES))
     lr_c, lr_a, b1, b2 = 2.0 ** -2, 2.0 ** -8, 0.5, 0.75
     k_ = Fused(P0, shape, lr_c, lr_a, eps, beta1=b1, beta2=b2)
     oc = {n: R.Adam64(lr_c, b1, b2, eps) for n in ("q1", "q2")}
@@ -280,9 +218,8 @@ def test_fused_td3_adam_across_four_updates_matches_float64(shape):
             for n in ("q1", "q2"):
                 oc[n].t += 1
                 for kk in R.NAMES:
-                    ge = gerr[(n, kk)] = torch.maximum(gerr.get((n, kk), torch.zeros_like(c[n]["bound"][kk])), c[n]["bound"][kk])
-                    w_pred, ratio = oc[n].step(kk, pre[n][kk], c[n]["g"][kk])
-                    worst = max(worst, R.worst_ratio(post[n][kk], w_pred, R.adam_step_bound(w_pred, ratio, lr_c, eps, ge)))
+                    w_pred, sb = A.tensor_step(oc[n], gerr, n, kk, pre[n][kk], c[n]["g"][kk], c[n]["bound"][kk], eps)
+                    worst = max(worst, R.worst_ratio(post[n][kk], w_pred, sb))
             report.append("update %d critics worst/bound %.3g" % (step, worst))
             assert worst <= 1.0
             if do_actor:
@@ -294,12 +231,10 @@ def test_fused_td3_adam_across_four_updates_matches_float64(shape):
                 for name, ag, tt in (("right", a_ok, None), ("pre-update Q1", a_pre, None), ("critics' step count", a_ok, oc["q1"].t)):
                     o = copy.deepcopy(before) if name != "right" else oa
                     w = 0.0
+                    ge = gerr if name == "right" else dict(gerr)      # only the right series' bounds are carried on
                     for kk in R.NAMES:
-                        ge = torch.maximum(gerr.get(("actor", kk), torch.zeros_like(ag["bound"][kk])), ag["bound"][kk])
-                        if name == "right":
-                            gerr[("actor", kk)] = ge
-                        w_pred, ratio = o.step(kk, pre["actor"][kk], ag["g"][kk], t=tt)
-                        w = max(w, R.worst_ratio(post["actor"][kk], w_pred, R.adam_step_bound(w_pred, ratio, lr_a, eps, ge)))
+                        w_pred, sb = A.tensor_step(o, ge, "actor", kk, pre["actor"][kk], ag["g"][kk], ag["bound"][kk], eps, t=tt)
+                        w = max(w, R.worst_ratio(post["actor"][kk], w_pred, sb))
                     res[name] = w
                 report.append("update %d actor worst/bound %.3g (ambiguous rows %d); pre-update Q1 %.3g; critics' step count %.3g" % (
                     step, res["right"], a_ok["flip_rows"], res["pre-update Q1"], res["critics' step count"]))
@@ -316,7 +251,7 @@ def test_fused_td3_adam_across_four_updates_matches_float64(shape):
 
 
 def test_cn_td3_create_rejects_shapes_out_of_range():
-    _abi, L = _lib()
+    _abi, L = lib()
     z = torch.zeros(16, device="cuda")
     m = _abi.CnTd3Mlp(*([z.data_ptr()] * 6))
     for obs_dim, hidden, batch in ((8, 16, 0), (8, 16, 4097), (8, 0, 16), (8, 4097, 16), (0, 16, 16)):
@@ -336,7 +271,7 @@ def test_two_handles_on_identical_parameters_end_bit_identical():
         for step in range(4):
             a.update(batch, step % 2 == 0)
             b.update(batch, step % 2 == 0)
-        assert all(_same(a.P, b.P, n) for n in R.NETS)
+        assert all(R.same(a.P, b.P, n) for n in R.NETS)
         assert a.loss() == b.loss()
     finally:
         a.close(); b.close()
@@ -376,8 +311,8 @@ def test_replay_path_samples_only_live_rows():
             hs[0].update(None, step % 2 == 0)
             hs[1].update(None, step % 2 == 0)
             hs[2].update(batch, step % 2 == 0)
-        assert all(_same(hs[0].P, hs[2].P, n) for n in R.NETS)
-        assert all(_same(hs[0].P, hs[1].P, n) for n in R.NETS)
+        assert all(R.same(hs[0].P, hs[2].P, n) for n in R.NETS)
+        assert all(R.same(hs[0].P, hs[1].P, n) for n in R.NETS)
     finally:
         for h in hs:
             h.close()
@@ -392,6 +327,6 @@ def test_replay_path_samples_only_live_rows():
                     h.update(None, step % 2 == 0)
                     assert h.loss() < 1e3, (fill, size, step, h.loss())
                 assert all(bool(torch.isfinite(v).all()) for p in h.P.values() for v in p.values()), (fill, size)
-                assert not _same(P0, h.P, "q1")
+                assert not R.same(P0, h.P, "q1")
             finally:
                 h.close()

@@ -8,35 +8,14 @@ import ctypes as C
 import pytest
 import torch
 
+from learner_handle import LearnerHandle, alias, err, lib, ring_fields, stream
+
 pytestmark = pytest.mark.gpu
 
 DO_ACTOR = (0, 1, 0, 1)
 NETS = ("actor", "actor_t", "q1", "q1_t", "q2", "q2_t")
 SHAPES = [(45, 33, 40, 3), (1, 17, 33, 2), (30, 16, 17, 5), (20, 48, 129, 2), (45, 1, 3, 4), (398, 256, 128, 2), (45, 33, 40, 1)]
 CN_ERR_ARG, CN_ERR_CONFIG = -1, -2
-
-
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _alias(ptr, shape):
-    n = 1
-    for x in shape:
-        n *= int(x)
-
-    class _Arr:
-        __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
-    return torch.as_tensor(_Arr(), device="cuda").reshape(tuple(shape))
-
-
-def _err():
-    return _lib()[1].cn_td3_last_error().decode()
 
 
 class Member:
@@ -69,16 +48,14 @@ class Instance:
     """A member's state on the device and the cn_td3_config that points at it."""
 
     def __init__(self, m):
-        _abi, _ = _lib()
+        _abi, _ = lib()
         self.m = m
         self.nets = {k: [t.cuda().contiguous() for t in ts] for k, ts in m.nets.items()}
         self.ring = {k: t.cuda().contiguous() for k, t in m.ring.items()}
         self.size = torch.tensor([m.live], dtype=torch.int64, device="cuda")
         mlps = {k: _abi.CnTd3Mlp(*[t.data_ptr() for t in ts]) for k, ts in self.nets.items()}
-        rg = self.ring
-        self.cfg = _abi.CnTd3Config(obs_dim=m.D, hidden=m.H, batch=m.B, reserved=0.0, seed=m.seed, replay_s=rg["s"].data_ptr(),
-                                    replay_a=rg["a"].data_ptr(), replay_r=rg["r"].data_ptr(), replay_s2=rg["s2"].data_ptr(),
-                                    replay_d=rg["d"].data_ptr(), replay_size_dev=self.size.data_ptr(), **m.hyper, **mlps)
+        self.cfg = _abi.CnTd3Config(obs_dim=m.D, hidden=m.H, batch=m.B, reserved=0.0, seed=m.seed, **ring_fields(dict(self.ring, size=self.size)),
+                                    **m.hyper, **mlps)
 
     def params(self):
         return [t.clone() for k in NETS for t in self.nets[k]]
@@ -94,44 +71,41 @@ def _snapshot(inst, loss, batch_ptr):
     for what, shape in enumerate(inst.batch_shapes()):
         ptr = batch_ptr(what)
         assert ptr, what
-        out.append(_alias(ptr, shape).clone())
+        out.append(alias(ptr, shape).clone())
     return out
 
 
 def run_solo(member, mode=0, seq=DO_ACTOR):
     """A solo handle on a fresh instance of `member`: the snapshot after each update of `seq`."""
-    _abi, L = _lib()
     inst = member.instance()
-    h = C.c_void_p()
-    assert L.cn_td3_create(C.byref(inst.cfg), 0, C.byref(h)) == 0, _err()
+    h = LearnerHandle("td3", inst.cfg, inst)
     try:
-        assert L.cn_td3_set_replay_sample(h, mode) == 0, _err()
-        loss = _alias(L.cn_td3_loss_dev(h), ())
+        assert h.set_replay_sample(mode) == 0, err()
+        loss = alias(h.L.cn_td3_loss_dev(h.h), ())
         snaps = []
         for a in seq:
-            assert L.cn_td3_update(h, a, None, _stream()) == 0, _err()
-            torch.cuda.synchronize()
-            snaps.append(_snapshot(inst, loss, lambda what: L.cn_td3_batch_dev(h, what)))
+            h.update(a)
+            snaps.append(_snapshot(inst, loss, lambda what: h.L.cn_td3_batch_dev(h.h, what)))
         return snaps
     finally:
-        L.cn_td3_destroy(h)
+        h.close()
 
 
 class Pop:
     def __init__(self, members, mode=0):
-        _abi, L = _lib()
+        _abi, L = lib()
         self.L, self.insts = L, [m.instance() for m in members]
         self.P = len(members)
         self.cfgs = (_abi.CnTd3Config * self.P)(*[i.cfg for i in self.insts])
         self.h = C.c_void_p()
-        assert L.cn_td3_pop_create(self.cfgs, self.P, 0, C.byref(self.h)) == 0, _err()
+        assert L.cn_td3_pop_create(self.cfgs, self.P, 0, C.byref(self.h)) == 0, err()
         assert L.cn_td3_pop_members(self.h) == self.P
         if mode:
-            assert L.cn_td3_pop_set_replay_sample(self.h, mode) == 0, _err()
-        self.loss = _alias(L.cn_td3_pop_loss_dev(self.h), (self.P,))
+            assert L.cn_td3_pop_set_replay_sample(self.h, mode) == 0, err()
+        self.loss = alias(L.cn_td3_pop_loss_dev(self.h), (self.P,))
 
     def update(self, a):
-        assert self.L.cn_td3_pop_update(self.h, a, _stream()) == 0, _err()
+        assert self.L.cn_td3_pop_update(self.h, a, stream()) == 0, err()
 
     def snapshot(self):
         torch.cuda.synchronize()
@@ -241,7 +215,7 @@ def test_captured_pair_replayed_twice_equals_four_eager_updates():
 
 
 def test_refusals():
-    _abi, L = _lib()
+    _abi, L = lib()
     D, H, B = 20, 16, 8
     h = C.c_void_p()
 
@@ -249,13 +223,13 @@ def test_refusals():
         cfgs = (_abi.CnTd3Config * len(insts))(*[i.cfg for i in insts])
         rc = L.cn_td3_pop_create(cfgs, len(insts) if n is None else n, 0, C.byref(h))
         assert not h.value
-        return rc, _err()
+        return rc, err()
 
     base = [Member(D, H, B, key=p).instance() for p in range(3)]
     for n in (0, -1, 65):
         rc, msg = create(base, n)
         assert rc == CN_ERR_ARG and "n_members" in msg, (n, rc, msg)
-    assert L.cn_td3_pop_create(None, 1, 0, C.byref(h)) == CN_ERR_ARG and "null" in _err()
+    assert L.cn_td3_pop_create(None, 1, 0, C.byref(h)) == CN_ERR_ARG and "null" in err()
     # every shared field, at member 2
     for field, val in (("obs_dim", D + 1), ("hidden", H + 1), ("batch", B + 1), ("policy_delay", 3), ("beta1", 0.8), ("beta2", 0.99),
                        ("eps", 1e-7), ("tau", 0.01), ("max_v", 0.3), ("max_w", 1.0)):
@@ -279,8 +253,8 @@ def test_refusals():
     rc, msg = create(insts)
     assert rc == CN_ERR_CONFIG and "same parameter tensor" in msg and "members 0" in msg and "and 2" in msg, (rc, msg)
     # the handle's calls
-    assert L.cn_td3_pop_update(None, 0, _stream()) == CN_ERR_ARG and "null handle" in _err()
-    assert L.cn_td3_pop_set_replay_sample(None, 0) == CN_ERR_ARG and "null handle" in _err()
+    assert L.cn_td3_pop_update(None, 0, stream()) == CN_ERR_ARG and "null handle" in err()
+    assert L.cn_td3_pop_set_replay_sample(None, 0) == CN_ERR_ARG and "null handle" in err()
     assert L.cn_td3_pop_members(None) == 0 and not L.cn_td3_pop_loss_dev(None) and not L.cn_td3_pop_batch_dev(None, 0, 0)
     members = [Member(D, H, B, key=p, live=500) for p in range(2)]
     pop = Pop(members, mode=1)
@@ -288,7 +262,7 @@ def test_refusals():
         for member, what in ((-1, 0), (2, 0), (0, -1), (0, 5)):
             assert not L.cn_td3_pop_batch_dev(pop.h, member, what), (member, what)
         for bad in (2, -1):
-            assert L.cn_td3_pop_set_replay_sample(pop.h, bad) == CN_ERR_ARG and "cn_td3_pop_set_replay_sample" in _err() and "mode" in _err()
+            assert L.cn_td3_pop_set_replay_sample(pop.h, bad) == CN_ERR_ARG and "cn_td3_pop_set_replay_sample" in err() and "mode" in err()
         pop.update(0)                              # still mode 1
         got = pop.snapshot()
         for p, m in enumerate(members):

@@ -14,6 +14,7 @@ import pytest
 
 import pop_record_ref as R
 from conftest import ROOT
+from learner_handle import lib
 
 CN_ERR_ARG, CN_ERR_CONFIG = -1, -2
 NAMES = ("cn_pop_record_create", "cn_pop_record_destroy", "cn_pop_record_members", "cn_pop_record_resetting", "cn_pop_record")
@@ -21,13 +22,8 @@ FAKE = 0x1000        # a non-null "device pointer"
 FIELDS = ["env", "counters", "last_return", "prev", "obs", "action", "reward", "done", "ring", "log", "n", "reserved"]
 
 
-def _lib():
-    from crowdnav import _abi
-    return _abi, _abi.lib()
-
-
 def test_member_struct_matches_its_mirror_field_by_field(tmp_path):
-    _abi, _ = _lib()
+    _abi, _ = lib()
     if shutil.which("gcc") is None:
         pytest.skip("no gcc")
     cls = _abi.CnPopRecordMember
@@ -62,7 +58,7 @@ def test_member_struct_matches_its_mirror_field_by_field(tmp_path):
 
 
 def test_the_five_names_are_exported_with_prototypes():
-    _abi, L = _lib()
+    _abi, L = lib()
     for name in NAMES:
         assert name in _abi.EXPORTS
         assert getattr(L, name).argtypes is not None, name
@@ -104,7 +100,7 @@ def _create(L, members, n_members, obs_dim, want_rc, *texts, out="fresh"):
 
 
 def test_create_refusals_name_the_field_and_the_member():
-    _abi, L = _lib()
+    _abi, L = lib()
     arr = lambda *ms: (_abi.CnPopRecordMember * len(ms))(*ms)
     A, B, Cc = 0x10000, 0x20000, 0x30000
     good = lambda base=A, **kw: _member(_abi, base, **kw)
@@ -150,7 +146,7 @@ def test_create_refusals_name_the_field_and_the_member():
 
 
 def test_null_handles_are_refused_everywhere():
-    _abi, L = _lib()
+    _abi, L = lib()
     assert L.cn_pop_record(None, 1.0, None) == CN_ERR_ARG and b"cn_pop_record: null handle" in L.cn_last_error()
     assert L.cn_pop_record_resetting(None, 0) is None and b"cn_pop_record_resetting: null handle" in L.cn_last_error()
     assert L.cn_pop_record_members(None) == 0

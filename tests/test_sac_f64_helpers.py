@@ -8,8 +8,12 @@ import numpy as np
 import pytest
 import torch
 
+import adam_series as A
 import sac_f64 as S
 import td3_f64 as R
+from actor_f64 import mix64, uniforms
+from replay_distinct_ref import _mix_int
+from sampling_f64 import noise_hash
 
 
 def _autograd(P, batch, eps, variant=None):
@@ -209,19 +213,23 @@ def test_every_wrong_act_variant_differs_by_more_than_twice_the_bound(shape):
 
 
 def test_mix64_is_splitmix64_and_the_same_on_ints_and_arrays():
-    """splitmix64's first outputs from state 0 (Vigna's reference implementation) are mix64(0), mix64(0x9E3779B97F4A7C15), ..."""
-    assert S._mix64(0) == 0xE220A8397B1DCDAF and S._mix64(0x9E3779B97F4A7C15) == 0x6E789E6AA1B965F4
+    """splitmix64's first outputs from state 0 (Vigna's reference implementation) are mix64(0), mix64(0x9E3779B97F4A7C15), ...:
+    of actor_f64.mix64, the one statement of cn_mix64, and of its form on Python ints, replay_distinct_ref._mix_int."""
+    for mix in (_mix_int, lambda x: int(mix64(np.array([x], dtype=np.uint64))[0])):
+        assert mix(0) == 0xE220A8397B1DCDAF and mix(0x9E3779B97F4A7C15) == 0x6E789E6AA1B965F4
     xs = [0, 1, 7, (1 << 63) + 5, (1 << 64) - 1]
-    assert S._mix64(np.array(xs, dtype=np.uint64)).tolist() == [S._mix64(x) for x in xs]
+    assert mix64(np.array(xs, dtype=np.uint64)).tolist() == [_mix_int(x) for x in xs]
 
 
 def test_box_muller_draw_keeps_what_the_device_draw_promises():
-    """Over 2^20 rows: every u1 in (0, 1), u2 in [0, 1), every value finite, mean and variance those of unit normals within 5
-    standard errors; rows and counters give different values.  The edges of the 24-bit integers: u1's smallest value is 2^-24
-    (r = 5.77), its largest -- at k = 2^24 - 1 alone, one hash in 2^24 -- is exactly 1, where r = 0 and eps = (0, 0): finite."""
+    """Over 2^20 rows: every u1 in (0, 1), u2 in [0, 1), each exactly a float32 value, every eps finite, mean and variance those
+    of unit normals within 5 standard errors; rows and counters give different values.  The edges of the 24-bit integers: u1's
+    smallest value is 2^-24 (r = 5.77), its largest -- at k = 2^24 - 1 alone, one hash in 2^24 -- is exactly 1, where r = 0 and
+    eps = (0, 0): finite."""
     rows = np.arange(1 << 20)
-    u1, u2 = S.uniforms(S.draw_hash(7, 3, rows))
-    assert u1.dtype == np.float32 and bool((u1 > 0).all()) and bool((u1 < 1).all()) and bool((u2 >= 0).all()) and bool((u2 < 1).all())
+    u1, u2 = uniforms(noise_hash(7, 3, None, rows))
+    assert all(np.array_equal(u, u.astype(np.float32)) for u in (u1, u2))
+    assert bool((u1 > 0).all()) and bool((u1 < 1).all()) and bool((u2 >= 0).all()) and bool((u2 < 1).all())
     e = S.box_muller_draw(7, 3, rows)
     assert e.shape == (1 << 20, 2) and bool(np.isfinite(e).all())
     k = e.size
@@ -230,10 +238,10 @@ def test_box_muller_draw_keeps_what_the_device_draw_promises():
     assert not np.array_equal(e[:64], S.box_muller_draw(7, 4, rows[:64])) and not np.array_equal(e[:64], S.box_muller_draw(8, 3, rows[:64]))
     assert np.array_equal(S.box_muller_draw(7 + (1 << 64), 3, rows[:64]), e[:64])          # seed and counter are 64-bit
     edge = np.array([0, (1 << 64) - 1, ((1 << 24) - 1) << 40], dtype=np.uint64)
-    eu1, eu2 = S.uniforms(edge)
+    eu1, eu2 = uniforms(edge)
     assert eu1.tolist() == [2.0 ** -24, 1.0, 1.0] and eu2.tolist() == [0.0, 1 - 2.0 ** -24, 0.0]
-    h = S.draw_hash(0xD1B54A32D192ED03, (1 << 63) + 5, [0, 1, 4098])
-    assert h.tolist() == [S._mix64(S._mix64(0xD1B54A32D192ED03 ^ S._mix64(((1 << 63) + 5) ^ 0x5bd1e995)) ^ m) for m in (0, 1, 4098)]
+    h = noise_hash(0xD1B54A32D192ED03, (1 << 63) + 5, None, [0, 1, 4098])
+    assert h.tolist() == [_mix_int(_mix_int(0xD1B54A32D192ED03 ^ _mix_int(((1 << 63) + 5) ^ 0x5bd1e995)) ^ m) for m in (0, 1, 4098)]
 
 
 # ---- the series of four updates -----------------------------------------------------------------------------------------------
@@ -299,7 +307,7 @@ def test_the_series_rule_accepts_a_float32_emulation_and_rejects_each_wrong_vari
     inside the series' bound at every update and every wrong variant outside it on each network it concerns, before anything
     runs on a GPU."""
     shape, betas, mode, clamp_all = case
-    res = S.series_run(S.EmulatedLearner, shape, betas, mode, clamp_all=clamp_all, log=lambda s: None)
+    res = A.run(S.series(shape, betas, mode, clamp_all), S.EmulatedLearner, log=lambda s: None)
     print(S.series_id(case), {n: "%.3g" % v for n, v in res["worst"].items()}, {k: "%.3g" % v for k, v in res["rejected"].items()})
     assert max(res["worst"].values()) <= 1.0
     want = {v for v in S.SERIES_VARIANTS if mode in S.SERIES_RULES[v][0]} | {"carried_after_create"}
