@@ -34,7 +34,7 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_policy_tail", "cn_actor_pack_weights", "cn_actor_forward", "cn_step_sequence", "cn_rollout_policy", "cn_get_counters",
            "cn_get_returns", "cn_debug_env", "cn_lds_bytes", "cn_near_separate", "cn_snapshot_size", "cn_snapshot", "cn_restore",
            "cn_td3_create", "cn_td3_destroy", "cn_td3_update", "cn_td3_loss_dev", "cn_td3_batch_dev", "cn_td3_last_error",
-           "cn_ddpg_create", "cn_ddpg_destroy", "cn_ddpg_update", "cn_ddpg_loss_dev", "cn_ddpg_batch_dev",
+           "cn_ddpg_create", "cn_ddpg_destroy", "cn_ddpg_update", "cn_ddpg_loss_dev", "cn_ddpg_batch_dev", "cn_ddpg_act",
            "cn_dqn_create", "cn_dqn_destroy", "cn_dqn_update", "cn_dqn_loss_dev", "cn_dqn_batch_dev", "cn_dqn_act",
            "cn_sac_create", "cn_sac_destroy", "cn_sac_update", "cn_sac_loss_dev", "cn_sac_batch_dev", "cn_sac_act",
            "cn_tab_create", "cn_tab_destroy", "cn_tab_set", "cn_tab_get", "cn_tab_tables", "cn_tab_learn_act", "cn_tab_last_error",
@@ -156,6 +156,14 @@ class CnDdpgConfig(C.Structure):
                 ("actor", CnTd3Mlp), ("actor_t", CnTd3Mlp), ("critic", CnTd3Mlp), ("critic_t", CnTd3Mlp),
                 ("replay_s", C.c_void_p), ("replay_a", C.c_void_p), ("replay_r", C.c_void_p), ("replay_s2", C.c_void_p), ("replay_d", C.c_void_p),
                 ("replay_size_dev", C.c_void_p), ("seed", C.c_uint64)]
+
+
+class CnDdpgActIO(C.Structure):
+    """Mirror of `cn_ddpg_act_io` (include/crowdnav.h)."""
+    _fields_ = [("obs", C.c_void_p), ("state", C.c_void_p), ("reset", C.c_void_p), ("u", C.c_void_p), ("action", C.c_void_p),
+                ("noise_out", C.c_void_p), ("mu", C.c_double), ("theta", C.c_double), ("sigma", C.c_double),
+                ("seed", C.c_uint64), ("counter", C.c_uint64), ("max_v", C.c_float), ("max_w", C.c_float),
+                ("n", C.c_int32), ("add_noise", C.c_int32)]
 
 
 class CnDqnConfig(C.Structure):
@@ -384,6 +392,7 @@ def lib():
         L.cn_ddpg_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]
         L.cn_ddpg_loss_dev.argtypes = [vp]; L.cn_ddpg_loss_dev.restype = vp
         L.cn_ddpg_batch_dev.argtypes = [vp, C.c_int]; L.cn_ddpg_batch_dev.restype = vp
+        L.cn_ddpg_act.argtypes = [C.POINTER(CnActorWeights), C.POINTER(CnDdpgActIO), C.c_int, vp]
         L.cn_dqn_create.argtypes = [C.POINTER(CnDqnConfig), C.c_int, C.POINTER(vp)]
         L.cn_dqn_destroy.argtypes = [vp]; L.cn_dqn_destroy.restype = None
         L.cn_dqn_update.argtypes = [vp, C.POINTER(CnDqnBatch), vp]

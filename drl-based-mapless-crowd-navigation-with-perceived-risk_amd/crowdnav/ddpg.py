@@ -11,7 +11,8 @@ What it keeps from the reference:
   back-propagated and stepped BEFORE the critic's step, i.e. through the pre-update critic; then the critic's step (the
   actor loss's gradients on the critic are cleared by its zero_grad) and the soft updates of critic and actor;
 - collection without exploration noise (TRAIN_DDPG:100, add_noise=False): explore_sigma = 0 in every fused actor path;
-  Ornstein-Uhlenbeck noise (DDPG:44-64) as an opt-in host-side term, with the reference's uniform (not Gaussian) increments;
+  Ornstein-Uhlenbeck noise (DDPG:44-64) as an opt-in term, with the reference's uniform (not Gaussian) increments: in PyTorch
+  (act(add_noise=True)) or with the actor in one launch (act_ou_fused: cn_ddpg_act), on one shared state;
 - checkpoints of the TARGET networks as ddpg_{actor,critic}_model_ep<N>.pt (DDPG:262-266); load_models loads the locals and
   hard-copies them to the targets (DDPG:268-272)."""
 import os
@@ -50,8 +51,12 @@ class OUNoise:
             u = torch.rand(x.shape, generator=self.gen, dtype=torch.float64, device=x.device)
         dx = self.theta * (self.mu - x) + self.sigma * u.to(torch.float64)
         self.state = x + dx
-        self.sigma = self.max_sigma - (self.max_sigma - self.min_sigma) * min(1.0, step / self.decay_period)
+        self.decay(step)
         return self.state
+
+    def decay(self, step):
+        """DDPG:63: the sigma of the NEXT sample."""
+        self.sigma = self.max_sigma - (self.max_sigma - self.min_sigma) * min(1.0, step / self.decay_period)
 
 
 class Agent(FusedActorMixin):
@@ -104,6 +109,94 @@ class Agent(FusedActorMixin):
     def reset_noise(self, mask=None):
         """agent.noise.reset() at an episode's end (TRAIN_DDPG:161), for the rows where `mask` is set."""
         self.noise.reset(mask)
+
+    def _ou_io(self, obs, out, reset, u, add_noise):
+        """cn_ddpg_act's io for these buffers; state, sigma and counter are filled in per call."""
+        from . import _abi
+        ns = self.noise
+        return _abi.CnDdpgActIO(obs=obs.data_ptr(), reset=None if reset is None else reset.data_ptr(), u=None if u is None else u.data_ptr(),
+                                action=out.data_ptr(), noise_out=None, mu=ns.mu, theta=ns.theta, seed=self._noise_seed,
+                                max_v=self.max_v, max_w=self.max_w, n=obs.shape[0], add_noise=1 if add_noise else 0)
+
+    def _ou_check(self, obs, reset, u, add_noise):
+        """The buffers as cn_ddpg_act reads them: the row count of act(), a byte per row of `reset`, float64 uniforms."""
+        n, st = obs.shape[0], self.noise.state
+        if add_noise and st.shape[0] != n:
+            raise ValueError("OU noise has %d states for %d observations (Agent(n_envs=...))" % (st.shape[0], n))
+        if reset is not None:
+            reset = reset.reshape(-1)
+            if reset.dtype not in (torch.uint8, torch.bool):
+                reset = reset != 0
+            reset = reset.contiguous()
+            if reset.shape[0] != n:
+                raise ValueError("reset has %d rows for %d observations" % (reset.shape[0], n))
+        if u is not None:
+            u = u.to(device=self.device, dtype=torch.float64).contiguous()
+            if tuple(u.shape) != (n, 2):
+                raise ValueError("u must be [%d, 2], not %s" % (n, tuple(u.shape)))
+        return reset, u
+
+    @torch.no_grad()
+    def act_ou_fused(self, obs, reset=None, step=0, out=None, u=None, add_noise=True):
+        """act(obs, add_noise=True, step=step) preceded by reset_noise(reset), as ONE kernel (cn_ddpg_act, csrc/crowdnav_ddpg.hip):
+        act_mfma's actor tile with the Ornstein-Uhlenbeck update and numpy's float64 `action += noise` as its output stage.
+        It updates `self.noise.state` itself, in place, so this path and act(add_noise=True) / reset_noise share one state and can be
+        mixed call by call.  reset: [n] uint8 / bool (the previous step's `done`) or None; u: the uniforms [n, 2] float64, or None =
+        drawn on the device from (the agent's noise seed, its call counter, row, component).  This call uses `self.noise.sigma`,
+        then sets the next call's from `step` as OUNoise.sample does.  add_noise=False: the deterministic policy; the state, `reset`
+        and sigma stay as they are."""
+        import ctypes as C
+        from . import _abi
+        if not hasattr(self, "_fw_struct"):
+            self.sync_fused_weights()
+        obs = obs.contiguous()
+        reset, u = self._ou_check(obs, reset, u, add_noise)
+        if out is None:
+            out = torch.empty((obs.shape[0], 2), dtype=torch.float32, device=self.device)
+        ns = self.noise
+        state = ns.state if ns.state.is_contiguous() else ns.state.contiguous()
+        io = self._ou_io(obs, out, reset, u, add_noise)
+        self._fused_calls += 1
+        io.state, io.sigma, io.counter = state.data_ptr(), ns.sigma, self._fused_calls
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        _abi.check(_abi.lib().cn_ddpg_act(C.byref(self._fw_struct), C.byref(io), self._dev_index, st))
+        if add_noise:
+            ns.state = state
+            ns.decay(step)
+        return out
+
+    def bind_act_ou_fused(self, obs, out, reset, u=None):
+        """Pre-marshalled act_ou_fused for fixed obs / out / reset (and, optionally, u) buffers: a callable `call(step=0)` that only
+        enqueues.  Each call reads where `self.noise.state` lives NOW (the torch path replaces that tensor), this call's sigma and the
+        call counter on the host and passes them by value; `step` sets the next call's sigma.  So a call captured into a graph keeps
+        the state's address, the sigma and the counter it was captured with: keep to the fused path while replaying (it updates the
+        state in place), and give `u` -- a buffer refilled before every replay -- because the device draw of a frozen counter
+        repeats."""
+        import ctypes as C
+        from . import _abi
+        if not hasattr(self, "_fw_struct"):
+            self.sync_fused_weights()
+        assert obs.is_contiguous() and out.is_contiguous()
+        reset_c, u_c = self._ou_check(obs, reset, u, True)
+        assert (reset is None or reset_c.data_ptr() == reset.data_ptr()) and (u is None or u_c.data_ptr() == u.data_ptr()), \
+            "reset must be contiguous uint8 / bool and u contiguous float64 on the agent's device: the call reads these buffers"
+        io = self._ou_io(obs, out, reset_c, u_c, True)
+        fn, check, w, pio = _abi.lib().cn_ddpg_act, _abi.check, C.byref(self._fw_struct), C.byref(io)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        ns, dv, n = self.noise, self._dev_index, obs.shape[0]
+        keep = (obs, out, reset_c, u_c, io, self._fw_struct, self._fw)
+
+        def call(step=0, _keep=keep):
+            state = ns.state
+            if state.shape[0] != n or not state.is_contiguous():
+                raise ValueError("OU noise has %d states for %d observations (Agent(n_envs=...))" % (state.shape[0], n))
+            self._fused_calls = c = self._fused_calls + 1
+            io.state, io.sigma, io.counter = state.data_ptr(), ns.sigma, c
+            rc = fn(w, pio, dv, st)
+            if rc:
+                check(rc)
+            ns.decay(step)
+        return call
 
     # ---- the update --------------------------------------------------------------------------------------------------------
     def _update(self, s, a, r, s2, d):

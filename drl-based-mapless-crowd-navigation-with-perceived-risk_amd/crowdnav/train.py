@@ -9,7 +9,7 @@ count at a log interval is rarely a round number); every save also rewrites `lat
 
 `--algo ddpg` trains the reference's baseline learner instead (start_ddpg_training.py, ddpg.py; crowdnav.ddpg): batch 64, actor
 lr 1e-4, critic lr 1e-3, tau 0.001 unless --batch / --lr-actor / --lr-critic / --tau are given, no exploration noise
-(TRAIN_DDPG:100) unless --ou-noise, checkpoints ddpg_{actor,critic}_model_ep<N>.pt, CSV ddpg_training.csv; `--learner fused` is
+(TRAIN_DDPG:100) unless --ou-noise (with --ou-act fused: actor and Ornstein-Uhlenbeck noise in one cn_ddpg_act launch), checkpoints ddpg_{actor,critic}_model_ep<N>.pt, CSV ddpg_training.csv; `--learner fused` is
 cn_ddpg_update.  `--obs-layout 1` is the 363-input observation of the shipped DDPG checkpoints.
 
 `--algo dqn` trains the reference's discrete learner (start_dqn_training.py, deepq.py; crowdnav.dqn) on obs_layout 1 with
@@ -280,7 +280,9 @@ class Td3(Learner):
         elif a.graphs and a.algo == "td3":
             self.agent.enable_graphs()         # a TD3 update as one hipGraph launch (the eager update is launch-bound at batch 128)
         self.warned_overflow = False
-        if a.algo == "ddpg" and a.ou_noise:    # OU noise: the act -> step loop (DDPG:170-196, add_noise=True)
+        if a.algo == "ddpg" and a.ou_noise and a.ou_act == "fused":    # the same loop, actor + OU noise + noise.reset() as ONE launch (cn_ddpg_act)
+            self.act = self.act_ou_fused
+        elif a.algo == "ddpg" and a.ou_noise:  # OU noise: the act -> step loop (DDPG:170-196, add_noise=True)
             self.act, self.consume = self.act_ou, self.consume_ou
 
     def start(self, obs, elog):
@@ -291,6 +293,10 @@ class Td3(Learner):
 
     def act_ou(self, obs, it):
         return self.agent.act(obs, add_noise=True, step=it - 1)
+
+    def act_ou_fused(self, obs, it):
+        # TRAIN_DDPG:161's noise.reset() rides in the act launch: env.done still holds the previous step's flags here
+        return self.agent.act_ou_fused(obs, reset=self.env.done if it > 1 else None, step=it - 1)
 
     def consume_ou(self, prev, act, reward, obs, done, keep):
         self.agent.memory.add_masked(prev, act, reward, obs, done, keep)
@@ -717,6 +723,8 @@ def build_parser():
     ap.add_argument("--tau", type=float, default=None, help="default: the algorithm's (td3 0.005, ddpg 0.001)")
     ap.add_argument("--ou-noise", action="store_true", help="ddpg only: Agent.act(add_noise=True)'s Ornstein-Uhlenbeck noise (DDPG:44-64), "
                     "host-side, one state per env; collection goes act -> step.  Off by default, as in TRAIN_DDPG:100")
+    ap.add_argument("--ou-act", default=None, choices=["torch", "fused"], help="--ou-noise only: torch (default) = Agent.act(add_noise=True) "
+                    "and reset_noise, eager PyTorch; fused = Agent.act_ou_fused: actor, OU update, noise.reset() and clip in one cn_ddpg_act launch")
     ap.add_argument("--obs-layout", type=int, default=None, choices=[0, 1, 2], help="cn_config.obs_layout: 0 = 366 + 4K inputs (default); "
                     "1 = environment_stage_1_original's 363 (the shipped DDPG checkpoints); 2 = 370")
     ap.add_argument("--memory", type=int, default=1_000_000, help="TRAIN:63 (not qlearn / sarsa: no replay)")
@@ -809,6 +817,10 @@ def parse_args(argv=None):
         a.population_record = "one-call"
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
+    if a.ou_act is not None and not a.ou_noise:
+        ap.error("--ou-act selects how --ou-noise acts: it needs --ou-noise")
+    if a.ou_act is None:
+        a.ou_act = "torch"
     return a
 
 

@@ -1,7 +1,8 @@
 // crowdnav_actor.h -- the fused TD3 actor's tile (device code): 3 x Linear(256) + ReLU + output stage in ONE launch (the caller of
-// the hot path, A33).  Shared by crowdnav_actor.hip (cn_actor_kernel, cn_actor_pop_kernel) and the policy kernels of
-// crowdnav_kernel.hip (cn_rollout_policy; units 2, 4 and 5).
+// the hot path, A33).  Shared by crowdnav_actor.hip (cn_actor_kernel, cn_actor_pop_kernel), the policy kernels of
+// crowdnav_kernel.hip (cn_rollout_policy; units 2, 4 and 5) and crowdnav_ddpg.hip (cn_ddpg_act_kernel: the tile with DDPG's noise).
 #pragma once
+#include <type_traits>
 #include "crowdnav_device.h"
 
 // Actor.forward (TD3:96-106) + Agent.act's noise and clip (TD3:209-215) for a tile of 16 environments per workgroup,
@@ -147,13 +148,19 @@ __device__ __forceinline__ void actor_layer(const float* __restrict__ A, int lda
 // the barrier count.  action2: a second copy of the actions (LDS, or NULL).
 // STAMP (cn_actor_kernel alone): the eight actor_stamp points are time stamps in the profiling build, which specialises
 // actor_stamp<true> (crowdnav_actor.hip), and nothing anywhere else.
+// NOISE: what the output stage adds to a head's value before the clip.  void: TD3's Gaussian term (sigma, seed, counter).  Otherwise
+// a type with `float operator()(float head, int row, int o, bool live) const`, called by the 32 threads (tile row i, output o) with
+// row = row0 + i and live = the row exists, whose result is clipped and stored (cn_ddpg_act_kernel: the Ornstein-Uhlenbeck term);
+// sigma, seed and counter are not read then.  The choice is made by `if constexpr` inside the one body, not by splitting the tile into
+// functions: the compiler simplifies a function before it inlines it, and a split tile came out of every kernel with other address
+// arithmetic or another register allocation than the whole one.
 template <bool STAMP> __device__ __forceinline__ void actor_stamp(int k) {}
-template <int NW, bool STAMP = false>        // NW = 8 (the packed weight layout is laid out for 8 waves x 32 columns)
+template <int NW, bool STAMP = false, class NOISE = void>        // NW = 8 (the packed weight layout is laid out for 8 waves x 32 columns)
 __device__ __forceinline__ void actor_tile(const float* __restrict__ obs, int n_live, int row0, int D, int Dp,
         const float* __restrict__ W1T, const float* __restrict__ b1, const float* __restrict__ W2T,
         const float* __restrict__ b2, const float* __restrict__ W3, const float* __restrict__ b3,
         float* __restrict__ action, float* action2, float max_v, float max_w, float sigma, uint64_t seed, uint64_t counter,
-        float* act_sm, const bool active = true, const int tid_in = -1)
+        float* act_sm, const bool active = true, const int tid_in = -1, const NOISE* noise = nullptr)
 {
     static_assert(NW == 8, "packed weights: 8 waves x 32 columns");
     const int ldx = ACT_LDX(Dp), ldh = ACT_LDH;
@@ -214,6 +221,7 @@ __device__ __forceinline__ void actor_tile(const float* __restrict__ obs, int n_
         for (int w = 0; w < NW; ++w) logit += PL[(w * ACT_M + i) * 2 + o];
         const int e = row0 + i;
         float val = (o == 0) ? max_v / (1.0f + __expf(-logit)) : max_w * tanhf(logit);
+        if constexpr (std::is_void<NOISE>::value) {
         if (sigma > 0.0f) {   // same generator as cn_policy_tail_kernel: keyed by (seed, counter, env row)
             uint64_t hh = cn_mix64(seed ^ cn_mix64(counter));
             hh = cn_mix64(hh ^ (uint64_t)(uint32_t)e);
@@ -223,6 +231,7 @@ __device__ __forceinline__ void actor_tile(const float* __restrict__ obs, int n_
             __sincosf(6.28318530718f * u2, &s_, &c_);
             val += sigma * rr_ * ((o == 0) ? c_ : s_);
         }
+        } else val = (*noise)(val, e, o, i < n_live);
         val = (o == 0) ? fminf(fmaxf(val, 0.0f), max_v) : fminf(fmaxf(val, -max_w), max_w);
         if (part == 0 && i < n_live) {
             action[2 * (size_t)i + o] = val;

@@ -103,8 +103,9 @@ extern "C" __global__ void __launch_bounds__(ACT_THREADS) cn_actor_kernel(const 
 }
 
 // An actor kernel whose tile exceeds 64 KiB: raise its dynamic-LDS limit to a CU's 160 KiB on the current device.  hipFuncSetAttribute
-// is per device: once per ordinal (attr_set: the kernel's own 64 flags), under a lock.
-static int allow_full_lds(const void* kernel, int dev, bool* attr_set)
+// is per device: once per ordinal (attr_set: the kernel's own 64 flags), under a lock.  (Declared in crowdnav_host.h: cn_ddpg_act's
+// kernel, crowdnav_ddpg.hip, runs the same tile.)
+int allow_full_lds(const void* kernel, int dev, bool* attr_set)
 {
     static std::mutex mu;
     std::lock_guard<std::mutex> lk(mu);

@@ -5,10 +5,13 @@
 // launches.  8 launches:  prep | actor_t L1 (+ actor L1) | L2 (+ L2) | critic_t L1 on (s2, pi_t(s2)), critic L1 on (s, a) and on
 // (s, pi(s)) | their L2 (+ q partials of critic_t and critic, dz on the pi(s) branch, tick) | G (critic: dq, dz2 evaluated;
 // pi(s) branch: da partials) | G (actor: dl, dz2a evaluated) | H (six jobs: critic and actor W1 / W2 / W3 + Adam + soft updates).
+// And cn_ddpg_act: Agent.act(add_noise=True) (ddpg.py:170-196) with OUNoise (:44-64) as ONE launch -- the TD3 actor's tile
+// (crowdnav_actor.h: cn_actor_forward's, same matrix work and heads) with the Ornstein-Uhlenbeck term as its output stage's noise.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include "../../include/crowdnav.h"
+#include "crowdnav_actor.h"
 #include "crowdnav_learner.h"
 
 struct cn_ddpg_s : ActorCritic {
@@ -104,5 +107,90 @@ extern "C" int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void*
     wgrad_job(ga.job[5], h->dl, 2, h->a_h2, H, H, B, c.actor.w3, c.actor.b3, &h->mom[0][4], h->adam + 2, c.actor_t.w3, c.actor_t.b3);
     launch_gemm(GEMM_H, false, ga, 6, st);
     CN_HIPCHK(td3_fail, hipGetLastError());
+    return CN_OK;
+}
+
+// ---- cn_ddpg_act: the actor and its Ornstein-Uhlenbeck noise in one launch ------------------------------------------------------------
+// A tile of 16 rows per workgroup, 8 waves: actor_tile (crowdnav_actor.h) as cn_actor_kernel runs it -- same packed weights, same k
+// order, same heads, so pi is cn_actor_forward's head value bit for bit -- with OuNoise as the output stage's noise: thread = (row,
+// component o), OUNoise.sample and numpy's `action += noise` in float64; the tile clips and stores.  Errors go to the environment's
+// channel, cn_last_error, like cn_actor_forward's.
+// x + (theta (mu - x) + sigma U) as ddpg.py:59-61 evaluates it: four float64 operations, each rounded on its own (no FMA)
+__device__ __forceinline__ double ou_step(double x, double mu, double theta, double sigma, double U)
+{
+#pragma clang fp contract(off)
+    const double drift = theta * (mu - x);
+    const double kick = sigma * U;
+    const double dx = drift + kick;
+    return x + dx;
+}
+// the device draw (include/crowdnav.h states it): 53 bits keyed by (seed, counter, row, component) and by nothing else
+__device__ __forceinline__ double ou_uniform(uint64_t seed, uint64_t counter, uint64_t row, int o)
+{
+    const uint64_t h = cn_mix64(cn_mix64(seed ^ cn_mix64(counter ^ 0x4F55ull)) ^ (2ull * row + (uint64_t)o));
+    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
+}
+struct OuNoise {
+    double* state; const uint8_t* reset; const double* u; double* noise_out;
+    double mu, theta, sigma;
+    uint64_t seed, counter;
+    int add_noise;
+    __device__ __forceinline__ float operator()(float pi, int row, int o, bool live) const
+    {
+        if (!add_noise || !live) return pi;
+        const size_t at = 2 * (size_t)row + o;
+        const double x0 = (reset && reset[row]) ? mu : state[at];
+        const double U = u ? u[at] : ou_uniform(seed, counter, (uint64_t)row, o);
+        const double x1 = ou_step(x0, mu, theta, sigma, U);
+        state[at] = x1;
+        if (noise_out) noise_out[at] = x1;
+        return (float)((double)pi + x1);
+    }
+};
+struct DdpgActArgs {
+    const float* obs; const float *w1p, *b1, *w2p, *b2, *w3, *b3; float* action;
+    OuNoise ou;
+    float max_v, max_w;
+    int n, D, Dp;
+};
+extern "C" __global__ void __launch_bounds__(ACT_THREADS) cn_ddpg_act_kernel(const DdpgActArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float act_sm[];
+    const int row0 = blockIdx.x * ACT_M;
+    actor_tile<ACT_THREADS / 64, false, OuNoise>(a.obs + (size_t)row0 * a.D, min(ACT_M, a.n - row0), row0, a.D, a.Dp, a.w1p, a.b1, a.w2p, a.b2,
+                                                 a.w3, a.b3, a.action + 2 * (size_t)row0, nullptr, a.max_v, a.max_w, 0.0f, 0, 0, act_sm, true, -1, &a.ou);
+}
+
+extern "C" int cn_ddpg_act(const cn_actor_weights* actor, const cn_ddpg_act_io* io, int device, void* stream)
+{
+    const std::string f("cn_ddpg_act");
+    if (!actor) return fail(CN_ERR_ARG, f + ": actor is null");
+    if (!io) return fail(CN_ERR_ARG, f + ": io is null");
+    const cn_actor_weights& w = *actor;
+    const float* const ps[6] = {w.w1p, w.b1, w.w2p, w.b2, w.w3, w.b3};
+    static const char* const pn[6] = {"actor->w1p", "actor->b1", "actor->w2p", "actor->b2", "actor->w3", "actor->b3"};
+    for (int i = 0; i < 6; ++i)
+        if (!ps[i]) return fail(CN_ERR_ARG, f + ": " + pn[i] + " is null");
+    if (!io->obs) return fail(CN_ERR_ARG, f + ": io->obs is null");
+    if (!io->action) return fail(CN_ERR_ARG, f + ": io->action is null");
+    if (io->add_noise && !io->state) return fail(CN_ERR_ARG, f + ": io->state is null with add_noise set");
+    if (io->n < 0) return fail(CN_ERR_ARG, f + ": io->n is negative");
+    if (w.hidden != 256) return fail(CN_ERR_CONFIG, f + ": actor->hidden must be 256");
+    if (w.obs_dim < 1) return fail(CN_ERR_CONFIG, f + ": actor->obs_dim must be at least 1");
+    if (w.obs_dim_padded < w.obs_dim || (w.obs_dim_padded & 31))
+        return fail(CN_ERR_CONFIG, f + ": actor->obs_dim_padded must be obs_dim rounded up to a multiple of 32 (the packed layout of cn_actor_pack_weights)");
+    const int Dp = w.obs_dim_padded;
+    const size_t lds = actor_tile_bytes((size_t)Dp);       // cn_actor_forward's tile
+    if (lds > 160 * 1024) return fail(CN_ERR_CONFIG, f + ": actor->obs_dim: observation too wide for one LDS tile");
+    if (io->n == 0) return CN_OK;
+    int dev = device;
+    if (dev < 0) CN_HIPCHK(fail, hipGetDevice(&dev));
+    DeviceScope scope(dev);
+    if (lds > 64 * 1024) { static bool attr_set[64] = {false}; const int rc = allow_full_lds((const void*)cn_ddpg_act_kernel, dev, attr_set); if (rc != CN_OK) return rc; }
+    const DdpgActArgs a{io->obs, w.w1p, w.b1, w.w2p, w.b2, w.w3, w.b3, io->action,
+                        OuNoise{io->state, io->reset, io->u, io->noise_out, io->mu, io->theta, io->sigma, io->seed, io->counter, io->add_noise ? 1 : 0},
+                        io->max_v, io->max_w, io->n, w.obs_dim, Dp};
+    hipLaunchKernelGGL(cn_ddpg_act_kernel, dim3((io->n + 15) / 16), dim3(ACT_THREADS), lds, (hipStream_t)stream, a);
+    CN_HIPCHK(fail, hipGetLastError());
     return CN_OK;
 }

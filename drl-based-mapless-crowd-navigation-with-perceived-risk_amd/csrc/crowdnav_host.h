@@ -23,6 +23,9 @@ struct DeviceScope {
 // the environment's error channel: the thread's cn_last_error() string (crowdnav_abi.hip); returns `code`
 __attribute__((visibility("hidden"))) int fail(int code, const std::string& msg);
 
+// an actor-tile kernel whose tile exceeds 64 KiB: its dynamic-LDS limit raised to a CU's 160 KiB on `dev` (crowdnav_actor.hip)
+__attribute__((visibility("hidden"))) int allow_full_lds(const void* kernel, int dev, bool* attr_set);
+
 struct cn_env_s {
     cn_config cfg;
     int device;

@@ -471,6 +471,40 @@ int cn_ddpg_update(cn_ddpg_handle h, const cn_td3_batch* batch, void* stream);
 const float* cn_ddpg_loss_dev(cn_ddpg_handle h);    /* device pointer: the critic's MSE loss of the last update (ddpg.py:230) */
 const float* cn_ddpg_batch_dev(cn_ddpg_handle h, int what);   /* as cn_td3_batch_dev, same indices; what = 4 (no noise): NULL */
 int cn_ddpg_set_replay_sample(cn_ddpg_handle h, int mode);    /* as cn_td3_set_replay_sample */
+/* Agent.act(state, step, add_noise=True) (ddpg.py:170-196) with its OUNoise (:44-64) and the trainer's noise.reset() at an episode's
+ * end (start_ddpg_training.py:161) for n rows as ONE launch on the caller's stream (no handle; capturable; copies nothing between
+ * host and device, reads nothing back).  The matrix part is cn_actor_forward's tile on the same packed weights (cn_actor_weights: 16
+ * rows per workgroup, v_mfma_f32_16x16x4_f32), so pi below is the float32 head value cn_actor_forward computes, bit for bit.
+ * Per row e and component o (0: v, 1: w), every float64 operation rounded on its own (no FMA):
+ *   x0 = reset && reset[e] ? mu : state[e][o]
+ *   x1 = x0 + (theta * (mu - x0) + sigma * U)              ddpg.py:59-61
+ *   state[e][o] = x1;  noise_out[e][o] = x1 (if given)
+ *   action[e][o] = clip((float)((double)pi + x1))          numpy's float32 `action += noise` with a float64 noise, then :191-192:
+ *                                                          v to [0, max_v], w to [-max_w, max_w]
+ * U = u[e][o], or with u == NULL drawn on the device, a multiple of 2^-53 in [0, 1) like random.random():
+ *   U = (mix64(mix64(seed ^ mix64(counter ^ 0x4F55)) ^ (2 e + o)) >> 11) * 2^-53,
+ *   mix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31)
+ * (64-bit wrap-around; e = the row within this call).  A row's draw depends on (seed, counter, e, o) alone: not on n, not on the tile.
+ * The caller owns sigma's decay (ddpg.py:63), as OUNoise.sample does: sigma is this call's value.
+ * add_noise == 0: the deterministic policy, action = clip(pi); state, reset, u and noise_out are not touched (and may be NULL).
+ * Rows at and beyond n are not touched.  device: HIP ordinal, -1 = current.
+ * Refused before any device work, text in cn_last_error naming the field: a NULL actor / io / pointer inside actor / obs / action, a
+ * NULL state with add_noise != 0, n < 0 -- CN_ERR_ARG; actor->hidden other than 256, obs_dim < 1, an obs_dim_padded that is not
+ * obs_dim rounded up to a multiple of 32, an obs_dim whose tile exceeds 160 KiB of LDS (from 2273, as cn_actor_forward) --
+ * CN_ERR_CONFIG.  n == 0 launches nothing and returns 0. */
+typedef struct cn_ddpg_act_io {
+    const float* obs;            /* dev [n][obs_dim] float32 */
+    double* state;               /* dev [n][2] float64: the OU state, read and written in place; the caller's */
+    const uint8_t* reset;        /* dev [n] or NULL; non-zero = the row's state is mu before this call's update */
+    const double* u;             /* dev [n][2] float64 uniforms, or NULL = drawn on the device */
+    float* action;               /* dev [n][2] float32, output */
+    double* noise_out;           /* dev [n][2] float64 or NULL: the new state beside the action */
+    double mu, theta, sigma;     /* ddpg.py:45-52 -> 0.0, 0.15, 0.2 */
+    uint64_t seed, counter;      /* key of the device draw */
+    float max_v, max_w;          /* the heads' ranges: 0.22, 2.0 */
+    int32_t n, add_noise;        /* n >= 0 rows; add_noise 0 = the deterministic policy */
+} cn_ddpg_act_io;
+int cn_ddpg_act(const cn_actor_weights* actor, const cn_ddpg_act_io* io, int device, void* stream);
 
 /* DQN -- the reference's discrete learner (deepq.py, start_dqn_training.py) -- on the same GEMM kernels (crowdnav_gemm.hip; crowdnav_dqn.hip).
  * Network (deepq.py:102-127, TRAIN_DQN:55-57): Linear(obs_dim, H) - ReLU - Linear(H, H) - ReLU - Linear(H, 3), H = 300.
