@@ -82,38 +82,42 @@ class CnSnapshotHeader(C.Structure):
                 ("total_bytes", C.c_uint64), ("config", CnConfig)]
 
 
+# What follows the header in a cn_snapshot blob, in order (include/crowdnav.h): name, dtype, shape from the header's N, P, tracker
+# slots and record counts.  split_snapshot, join_snapshot and VecEnv.load_snapshot walk this list.
+SNAPSHOT_SECTIONS = (
+    ("sd", "float64", lambda N, P, cap, hd: (N, hd.sd_count)),
+    ("si", "int32", lambda N, P, cap, hd: (N, hd.si_count)),
+    ("ped_p", "float64", lambda N, P, cap, hd: (N, P, 2)),
+    ("ped_v", "float64", lambda N, P, cap, hd: (N, P, 2)),
+    ("trk", "float64", lambda N, P, cap, hd: (N, cap, hd.tf_count)),
+    ("ped_init", "float64", lambda N, P, cap, hd: (N, P, 2)),
+    ("ped_preset", "float64", lambda N, P, cap, hd: (N, P, 2)),
+    ("ped_aux", "float64", lambda N, P, cap, hd: (N, P, 3)),
+)
+
+
 def split_snapshot(buf):
     """A cn_snapshot blob (uint8 array) -> (header, dict of arrays): sd [N,24] f64, si [N,16] i32, ped_p / ped_v [N,P,2],
     trk [N,cap,12], ped_init / ped_preset [N,P,2], ped_aux [N,P,3].  Views into `buf`."""
     import numpy as np
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    if buf.size < C.sizeof(CnSnapshotHeader):
+        raise CrowdNavError("truncated snapshot: %d bytes are less than a header" % buf.size)
     hd = CnSnapshotHeader.from_buffer_copy(buf[:C.sizeof(CnSnapshotHeader)].tobytes())
     if hd.magic != CN_SNAPSHOT_MAGIC or hd.header_bytes != C.sizeof(CnSnapshotHeader):
         raise CrowdNavError("not a libcrowdnav snapshot (magic / header size)")
-    N, P, cap = hd.config.n_envs, hd.config.n_peds, hd.track_capacity
-    off = [hd.header_bytes]
-
-    def take(shape, dtype):
-        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-        a = buf[off[0]:off[0] + n].view(dtype).reshape(shape)
-        off[0] += n
-        return a
-    out = dict(sd=take((N, hd.sd_count), np.float64), si=take((N, hd.si_count), np.int32), ped_p=take((N, P, 2), np.float64),
-               ped_v=take((N, P, 2), np.float64), trk=take((N, cap, hd.tf_count), np.float64), ped_init=take((N, P, 2), np.float64),
-               ped_preset=take((N, P, 2), np.float64), ped_aux=take((N, P, 3), np.float64))
-    if off[0] != hd.total_bytes or off[0] > buf.size:
+    shapes = [shape(hd.config.n_envs, hd.config.n_peds, hd.track_capacity, hd) for _, _, shape in SNAPSHOT_SECTIONS]
+    ends = np.cumsum([hd.header_bytes] + [int(np.prod(s)) * np.dtype(dt).itemsize for s, (_, dt, _) in zip(shapes, SNAPSHOT_SECTIONS)])
+    if ends[-1] != hd.total_bytes or ends[-1] > buf.size:      # before any view is taken: a short blob is this error, not numpy's
         raise CrowdNavError("truncated snapshot: %d bytes, header says %d" % (buf.size, hd.total_bytes))
-    return hd, out
+    return hd, {name: buf[ends[i]:ends[i + 1]].view(dt).reshape(shapes[i]) for i, (name, dt, _) in enumerate(SNAPSHOT_SECTIONS)}
 
 
 def join_snapshot(hd, arrays):
     """Inverse of split_snapshot: header + arrays -> blob for cn_restore."""
     import numpy as np
-    parts = [np.frombuffer(bytes(hd), dtype=np.uint8)]
-    for k, dt in (("sd", np.float64), ("si", np.int32), ("ped_p", np.float64), ("ped_v", np.float64), ("trk", np.float64),
-                  ("ped_init", np.float64), ("ped_preset", np.float64), ("ped_aux", np.float64)):
-        parts.append(np.ascontiguousarray(arrays[k], dtype=dt).reshape(-1).view(np.uint8))
-    return np.concatenate(parts)
+    return np.concatenate([np.frombuffer(bytes(hd), dtype=np.uint8)] +
+                          [np.ascontiguousarray(arrays[k], dtype=dt).reshape(-1).view(np.uint8) for k, dt, _ in SNAPSHOT_SECTIONS])
 
 
 def config_to_dict(c):

@@ -9,6 +9,7 @@ PyTorch is used only for device memory and streams.
 """
 import contextlib
 import ctypes as C
+import math
 import time
 
 import numpy as np
@@ -20,6 +21,110 @@ from .config import Config
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+# ---- the io structs of include/crowdnav.h, each built in ONE place.  The builders read the tensors they are given (data_ptr, shape,
+# dtype, stride, is_contiguous) and the handle's N, D, K, device and output buffers: no library, no GPU (tests/test_env_marshalling.py).
+AUTO_RESET = {False: 0, None: 0, True: 1, "same": 1, "next": 2}      # cn_step_io.auto_reset; any other value goes through as it is
+
+
+def _is_action(a, e):
+    return a.device == e.device and a.dtype == torch.float32 and a.is_contiguous()
+
+
+def step_io(e, action, step_counter=None, auto_reset="next", want_final=False):
+    """cn_step_io: one step of handle `e` from `action` (and `step_counter`, or None) into e's own output buffers."""
+    return _abi.CnStepIO(action=action.data_ptr(), step_counter=step_counter.data_ptr() if step_counter is not None else None,
+                         obs=e.obs.data_ptr(), final_obs=e.final_obs.data_ptr() if want_final else None,
+                         obs_f64=e.obs_f64.data_ptr() if e.obs_f64 is not None else None,
+                         reward=e.reward.data_ptr(), done=e.done.data_ptr(), topk_idx=e.topk_idx.data_ptr(),
+                         auto_reset=AUTO_RESET.get(auto_reset, auto_reset), reserved=0)
+
+
+def _slots(e, io, T, traj, action_out=False):
+    """The output members cn_sequence_io and cn_policy_io share (the action is an output of the policy form only).  traj None: e's
+    own buffers, every stride 0 (each step overwrites them).  Else slot t of traj[name], a contiguous [T, *row] tensor of the
+    slot's dtype, one row's elements apart; topk_idx is optional."""
+    if traj is None:
+        io.obs, io.reward, io.done, io.topk_idx = e.obs.data_ptr(), e.reward.data_ptr(), e.done.data_ptr(), e.topk_idx.data_ptr()
+        return
+    for name, stride, row, dtype in (("action", "action_stride", (e.N, 2), torch.float32), ("obs", "obs_stride", (e.N, e.D), torch.float32),
+                                     ("reward", "reward_stride", (e.N,), torch.float32), ("done", "done_stride", (e.N,), torch.uint8),
+                                     ("topk_idx", "topk_stride", (e.N, e.K), torch.int32)):
+        if name == "action" and not action_out:
+            continue
+        t = traj.get(name) if name == "topk_idx" else traj[name]
+        if t is not None:
+            assert tuple(t.shape) == (T,) + row and t.dtype == dtype and t.is_contiguous(), name
+            setattr(io, name, t.data_ptr())
+            setattr(io, stride, math.prod(row))
+
+
+def sequence_io(e, actions, traj=None):
+    """cn_sequence_io: T = len(actions) open-loop steps of handle `e`; actions [T, N, 2] float32, contiguous or an expanded [N, 2]."""
+    a = actions
+    assert isinstance(a, torch.Tensor) and a.device == e.device and a.dtype == torch.float32 and a.dim() == 3 and a.shape[1:] == (e.N, 2)
+    T = int(a.shape[0])
+    if T > 1 and a.stride(0) == 0:
+        astride = 0                                  # an expanded [N, 2]: the same actions held for T steps
+        assert a[0].is_contiguous()
+    else:
+        assert a.is_contiguous()
+        astride = 2 * e.N
+    io = _abi.CnSequenceIO()
+    io.action, io.action_stride, io.n_steps = a.data_ptr(), astride, T
+    _slots(e, io, T, traj)
+    return io
+
+
+def policy_io(e, agent, T, traj=None, add_noise=True, noise_seed=None, obs0=None):
+    """(cn_policy_io, what it points into) for T periods of `agent`'s packed actor (Agent.sync_fused_weights) on handle `e`;
+    `counter` is the caller's to fill per launch."""
+    if not hasattr(agent, "_fw_struct"):
+        agent.sync_fused_weights()
+    io = _abi.CnPolicyIO()
+    o0 = e.obs if obs0 is None else obs0
+    assert o0.device == e.device and o0.dtype == torch.float32 and o0.is_contiguous() and tuple(o0.shape) == (e.N, e.D)
+    io.obs0, io.n_steps = o0.data_ptr(), int(T)
+    io.max_v, io.max_w, io.sigma = agent.max_v, agent.max_w, (agent.explore_sigma if add_noise else 0.0)
+    io.seed = agent._noise_seed if noise_seed is None else int(noise_seed)
+    if traj is None:
+        if not hasattr(e, "_pol_action"):
+            e._pol_action = torch.zeros((e.N, 2), dtype=torch.float32, device=e.device)
+        io.action = e._pol_action.data_ptr()
+    _slots(e, io, int(T), traj, action_out=True)
+    return io, (o0, traj, agent._fw_struct, agent._fw)
+
+
+def multi_io(envs, actions, auto_reset="next", want_final=False):
+    """cn_step_multi's arguments (n, handles, ios, streams) and what they point into: len(actions) steps of every handle of `envs`,
+    step-major (entry i * G + g = step i of group g); each [N_total, 2] action tensor is read by consecutive row slices, envs[g].N rows each."""
+    G = len(envs)
+    n = G * len(actions)
+    ios, hs, sts = (_abi.CnStepIO * n)(), (C.c_void_p * n)(), (C.c_void_p * n)()
+    keep = [actions]
+    for i, action in enumerate(actions):
+        r0 = 0
+        for g, e in enumerate(envs):
+            a = action[r0:r0 + e.N]
+            r0 += e.N
+            assert _is_action(a, e)
+            keep.append(a)
+            j = i * G + g
+            ios[j] = step_io(e, a, None, auto_reset, want_final)
+            hs[j], sts[j] = e.h.value, e._stream().value
+    return (n, hs, ios, sts), keep
+
+
+def _enqueuer(fn, args, keep):
+    """A zero-argument callable that only enqueues fn(*args): everything resolved here, `keep` alive as long as the callable."""
+    check = _abi.check
+
+    def call(_keep=keep):
+        rc = fn(*args)
+        if rc:
+            check(rc)
+    return call
 
 
 class VecEnv:
@@ -177,13 +282,7 @@ class VecEnv:
         if step_counter is not None:
             sc = self._dev(step_counter, torch.int32)
         self._keep_step = (a, sc)     # alive until the next call: the launch is asynchronous
-        io = _abi.CnStepIO(action=a.data_ptr(), step_counter=sc.data_ptr() if sc is not None else None,
-                           obs=self.obs.data_ptr(), final_obs=self.final_obs.data_ptr() if want_final else None,
-                           obs_f64=self.obs_f64.data_ptr() if self.obs_f64 is not None else None,
-                           reward=self.reward.data_ptr(), done=self.done.data_ptr(), topk_idx=self.topk_idx.data_ptr(),
-                           auto_reset={False: 0, None: 0, True: 1, "same": 1, "next": 2}.get(auto_reset, auto_reset),
-                           reserved=0)
-        _abi.check(self.L.cn_step(self.h, C.byref(io), self._stream()))
+        _abi.check(self.L.cn_step(self.h, C.byref(step_io(self, a, sc, auto_reset, want_final)), self._stream()))
         return self.obs, self.reward, self.done
 
     def bind_step(self, action, auto_reset="next", want_final=False):
@@ -191,21 +290,9 @@ class VecEnv:
         (a fraction of the host time of step(), tools/host_overhead.py).  For rollouts that call several handles per step
         (VecEnvGroups): the action tensor is written in place by the policy, outputs land in self.obs/reward/done.
         Needs a bound stream (VecEnv(stream=...)) or uses the stream current at bind time."""
-        assert action.device == self.device and action.dtype == torch.float32 and action.is_contiguous()
-        io = _abi.CnStepIO(action=action.data_ptr(), step_counter=None, obs=self.obs.data_ptr(),
-                           final_obs=self.final_obs.data_ptr() if want_final else None,
-                           obs_f64=self.obs_f64.data_ptr() if self.obs_f64 is not None else None,
-                           reward=self.reward.data_ptr(), done=self.done.data_ptr(), topk_idx=self.topk_idx.data_ptr(),
-                           auto_reset={False: 0, True: 1, None: 0, "same": 1, "next": 2}.get(auto_reset, auto_reset),
-                           reserved=0)
-        ref, st, h, fn, check = C.byref(io), self._stream(), self.h, self.L.cn_step, _abi.check
-        keep = (io, action)
-
-        def call(_keep=keep):
-            rc = fn(h, ref, st)
-            if rc:
-                check(rc)
-        return call
+        assert _is_action(action, self)
+        io = step_io(self, action, None, auto_reset, want_final)
+        return _enqueuer(self.L.cn_step, (self.h, C.byref(io), self._stream()), (io, action))
 
     def step_sequence(self, actions, traj=None):
         """T = len(actions) calls of step(auto_reset="next") with OPEN-LOOP actions as ONE launch (cn_step_sequence): every
@@ -214,71 +301,22 @@ class VecEnv:
         traj: None -- every step overwrites self.obs / reward / done / topk_idx in place -- or a dict of preallocated device
         tensors obs [T, N, D], reward [T, N], done [T, N] uint8, optionally topk_idx [T, N, K] (slot t = what step t returned).
         Bit-identical to the T calls.  Enqueues only; returns env-steps issued."""
-        a = actions
-        assert isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float32 and a.dim() == 3 and a.shape[1:] == (self.N, 2)
-        T = int(a.shape[0])
-        if T > 1 and a.stride(0) == 0:
-            astride = 0                                  # an expanded [N, 2]: the same actions held for T steps
-            assert a[0].is_contiguous()
-        else:
-            assert a.is_contiguous()
-            astride = 2 * self.N
-        io = _abi.CnSequenceIO()
-        io.action, io.action_stride, io.n_steps = a.data_ptr(), astride, T
-        if traj is None:
-            io.obs, io.reward, io.done, io.topk_idx = self.obs.data_ptr(), self.reward.data_ptr(), self.done.data_ptr(), self.topk_idx.data_ptr()
-        else:
-            N, D, K = self.N, self.D, self.K
-            o, r, d = traj["obs"], traj["reward"], traj["done"]
-            assert tuple(o.shape) == (T, N, D) and o.dtype == torch.float32 and o.is_contiguous()
-            assert tuple(r.shape) == (T, N) and r.dtype == torch.float32 and r.is_contiguous()
-            assert tuple(d.shape) == (T, N) and d.dtype == torch.uint8 and d.is_contiguous()
-            io.obs, io.reward, io.done = o.data_ptr(), r.data_ptr(), d.data_ptr()
-            io.obs_stride, io.reward_stride, io.done_stride = N * D, N, N
-            tk = traj.get("topk_idx")
-            if tk is not None:
-                assert tuple(tk.shape) == (T, N, K) and tk.dtype == torch.int32 and tk.is_contiguous()
-                io.topk_idx, io.topk_stride = tk.data_ptr(), N * K
+        io = sequence_io(self, actions, traj)
         _abi.check(self.L.cn_step_sequence(self.h, C.byref(io), self._stream()))
-        self._keep_seq = (io, a, traj)
+        self._keep_seq = (io, actions, traj)
+        T = io.n_steps
         if traj is not None:
-            with self._on_stream():
-                self.obs.copy_(traj["obs"][T - 1]); self.reward.copy_(traj["reward"][T - 1]); self.done.copy_(traj["done"][T - 1])
-                if traj.get("topk_idx") is not None:
-                    self.topk_idx.copy_(traj["topk_idx"][T - 1])
-                else:
-                    self.topk_idx.fill_(-1)      # not produced by this call: never left stale next to the new observation
+            self._adopt_last_slot(traj, T)
         return T * self.N
 
-    def _policy_io(self, agent, T, traj, add_noise, noise_seed, obs0):
-        """cn_policy_io for T periods of `agent`'s packed actor (Agent.sync_fused_weights) on this handle's buffers."""
-        if not hasattr(agent, "_fw_struct"):
-            agent.sync_fused_weights()
-        N, D, K = self.N, self.D, self.K
-        io = _abi.CnPolicyIO()
-        o0 = self.obs if obs0 is None else obs0
-        assert o0.device == self.device and o0.dtype == torch.float32 and o0.is_contiguous() and tuple(o0.shape) == (N, D)
-        io.obs0, io.n_steps = o0.data_ptr(), int(T)
-        io.max_v, io.max_w, io.sigma = agent.max_v, agent.max_w, (agent.explore_sigma if add_noise else 0.0)
-        io.seed = agent._noise_seed if noise_seed is None else int(noise_seed)
-        if traj is None:
-            if not hasattr(self, "_pol_action"):
-                self._pol_action = torch.zeros((N, 2), dtype=torch.float32, device=self.device)
-            io.action = self._pol_action.data_ptr()
-            io.obs, io.reward, io.done, io.topk_idx = self.obs.data_ptr(), self.reward.data_ptr(), self.done.data_ptr(), self.topk_idx.data_ptr()
-        else:
-            a, o, r, d = traj["action"], traj["obs"], traj["reward"], traj["done"]
-            assert tuple(a.shape) == (T, N, 2) and a.dtype == torch.float32 and a.is_contiguous()
-            assert tuple(o.shape) == (T, N, D) and o.dtype == torch.float32 and o.is_contiguous()
-            assert tuple(r.shape) == (T, N) and r.dtype == torch.float32 and r.is_contiguous()
-            assert tuple(d.shape) == (T, N) and d.dtype == torch.uint8 and d.is_contiguous()
-            io.action, io.obs, io.reward, io.done = a.data_ptr(), o.data_ptr(), r.data_ptr(), d.data_ptr()
-            io.action_stride, io.obs_stride, io.reward_stride, io.done_stride = 2 * N, N * D, N, N
-            tk = traj.get("topk_idx")
-            if tk is not None:
-                assert tuple(tk.shape) == (T, N, K) and tk.dtype == torch.int32 and tk.is_contiguous()
-                io.topk_idx, io.topk_stride = tk.data_ptr(), N * K
-        return io, (o0, traj, agent._fw_struct, agent._fw)
+    def _adopt_last_slot(self, traj, T):
+        """After a launch into a trajectory, self.obs / reward / done / topk_idx show its last slot, as after the T single calls."""
+        with self._on_stream():
+            self.obs.copy_(traj["obs"][T - 1]); self.reward.copy_(traj["reward"][T - 1]); self.done.copy_(traj["done"][T - 1])
+            if traj.get("topk_idx") is not None:
+                self.topk_idx.copy_(traj["topk_idx"][T - 1])
+            else:
+                self.topk_idx.fill_(-1)      # not produced by this call: never left stale next to the new observation
 
     def rollout_policy(self, agent, n_steps, traj=None, add_noise=True, noise_seed=None, obs0=None):
         """n_steps periods of (agent.act_mfma -> step(auto_reset="next")) as ONE launch (cn_rollout_policy): the packed actor
@@ -291,18 +329,13 @@ class VecEnv:
         spent the period on its reset, i.e. where done[t - 1] was set).
         Bit-identical to the n_steps pairs of calls; advances the agent's noise counter by n_steps.  Enqueues only."""
         T = int(n_steps)
-        io, keep = self._policy_io(agent, T, traj, add_noise, noise_seed, obs0)
+        io, keep = policy_io(self, agent, T, traj, add_noise, noise_seed, obs0)
         io.counter = agent._fused_calls + 1
         agent._fused_calls += T
         _abi.check(self.L.cn_rollout_policy(self.h, C.byref(agent._fw_struct), C.byref(io), self._stream()))
         self._keep_pol = (io, keep)
         if traj is not None:
-            with self._on_stream():
-                self.obs.copy_(traj["obs"][T - 1]); self.reward.copy_(traj["reward"][T - 1]); self.done.copy_(traj["done"][T - 1])
-                if traj.get("topk_idx") is not None:
-                    self.topk_idx.copy_(traj["topk_idx"][T - 1])
-                else:
-                    self.topk_idx.fill_(-1)
+            self._adopt_last_slot(traj, T)
         return T * self.N
 
     @property
@@ -312,43 +345,22 @@ class VecEnv:
     def bind_rollout_policy(self, agent, n_steps, add_noise=True, noise_seed=None):
         """Pre-marshalled rollout_policy (in place): a zero-argument callable that only enqueues."""
         T = int(n_steps)
-        io, keep = self._policy_io(agent, T, None, add_noise, noise_seed, None)
-        ref, w, st, h, fn, check = C.byref(io), C.byref(agent._fw_struct), self._stream(), self.h, self.L.cn_rollout_policy, _abi.check
+        io, keep = policy_io(self, agent, T, None, add_noise, noise_seed, None)
+        enqueue = _enqueuer(self.L.cn_rollout_policy, (self.h, C.byref(agent._fw_struct), C.byref(io), self._stream()), (io, keep))
 
-        def call(_keep=(io, keep)):
+        def call():
             io.counter = agent._fused_calls + 1
             agent._fused_calls += T
-            rc = fn(h, w, ref, st)
-            if rc:
-                check(rc)
+            enqueue()
         return call
 
     def bind_step_sequence(self, actions, traj=None):
-        """Pre-marshalled step_sequence for a fixed [T, N, 2] action tensor: a zero-argument callable that only enqueues.  traj None:
-        outputs in place (every step overwrites self.obs / reward / done / topk_idx); traj = dict(obs [T, N, D], reward [T, N],
-        done [T, N] uint8): step t's outputs land in slot t of the caller's trajectory buffers (self.obs is NOT refreshed)."""
-        a = actions
-        assert a.device == self.device and a.dtype == torch.float32 and a.is_contiguous() and a.shape[1:] == (self.N, 2)
-        io = _abi.CnSequenceIO()
-        T = int(a.shape[0])
-        io.action, io.action_stride, io.n_steps = a.data_ptr(), 2 * self.N, T
-        if traj is None:
-            io.obs, io.reward, io.done, io.topk_idx = self.obs.data_ptr(), self.reward.data_ptr(), self.done.data_ptr(), self.topk_idx.data_ptr()
-        else:
-            o, r, d = traj["obs"], traj["reward"], traj["done"]
-            assert tuple(o.shape) == (T, self.N, self.D) and o.dtype == torch.float32 and o.is_contiguous()
-            assert tuple(r.shape) == (T, self.N) and r.dtype == torch.float32 and r.is_contiguous()
-            assert tuple(d.shape) == (T, self.N) and d.dtype == torch.uint8 and d.is_contiguous()
-            io.obs, io.reward, io.done = o.data_ptr(), r.data_ptr(), d.data_ptr()
-            io.obs_stride, io.reward_stride, io.done_stride = self.N * self.D, self.N, self.N
-        ref, st, h, fn, check = C.byref(io), self._stream(), self.h, self.L.cn_step_sequence, _abi.check
-        keep = (io, a, traj)
-
-        def call(_keep=keep):
-            rc = fn(h, ref, st)
-            if rc:
-                check(rc)
-        return call
+        """Pre-marshalled step_sequence for a fixed [T, N, 2] action tensor (or an expanded [N, 2], as step_sequence takes): a
+        zero-argument callable that only enqueues.  traj None: outputs in place (every step overwrites self.obs / reward / done /
+        topk_idx); traj = dict(obs [T, N, D], reward [T, N], done [T, N] uint8, optionally topk_idx [T, N, K]): step t's outputs
+        land in slot t of the caller's trajectory buffers (self.obs is NOT refreshed)."""
+        io = sequence_io(self, actions, traj)
+        return _enqueuer(self.L.cn_step_sequence, (self.h, C.byref(io), self._stream()), (io, actions, traj))
 
     def observe_external(self, ranges, odom, step_counter=None, is_reset=False, phase=0):
         """Env.get_state + Env.compute_reward on externally supplied /scan and /odom (Gazebo, a physical robot,
@@ -465,7 +477,7 @@ class VecEnv:
         if str(z["format"]) != "crowdnav-snapshot-1":
             raise _abi.CrowdNavError("%s is not a crowdnav snapshot file" % path)
         hd, _ = _abi.split_snapshot(z["blob"])
-        self.restore(_abi.join_snapshot(hd, {k: z[k] for k in ("sd", "si", "ped_p", "ped_v", "trk", "ped_init", "ped_preset", "ped_aux")}))
+        self.restore(_abi.join_snapshot(hd, {k: z[k] for k, _, _ in _abi.SNAPSHOT_SECTIONS}))
 
 
 def concurrent_streams(want, device=0, candidates=None):
@@ -604,61 +616,17 @@ class VecEnvGroups:
         (each group reads its slice).  Returns a zero-argument callable that enqueues one step of every group with ONE
         foreign call; outputs land in each group's obs / reward / done.  No fork / join: callers that need the groups ordered
         against another stream use fork() / join() around their loop."""
-        G = self.G
-        ios = (_abi.CnStepIO * G)()
-        hs = (C.c_void_p * G)()
-        sts = (C.c_void_p * G)()
-        keep = [action]
-        ar = {False: 0, True: 1, None: 0, "same": 1, "next": 2}.get(auto_reset, auto_reset)
-        for g, e in enumerate(self.envs):
-            a = action[self.rows(g)]
-            assert a.device == e.device and a.dtype == torch.float32 and a.is_contiguous()
-            keep.append(a)
-            ios[g] = _abi.CnStepIO(action=a.data_ptr(), step_counter=None, obs=e.obs.data_ptr(),
-                                   final_obs=e.final_obs.data_ptr() if want_final else None,
-                                   obs_f64=e.obs_f64.data_ptr() if e.obs_f64 is not None else None,
-                                   reward=e.reward.data_ptr(), done=e.done.data_ptr(), topk_idx=e.topk_idx.data_ptr(),
-                                   auto_reset=ar, reserved=0)
-            hs[g] = e.h.value
-            sts[g] = e._stream().value
-        fn, check = self.envs[0].L.cn_step_multi, _abi.check
-
-        def call(_keep=(keep, ios, hs, sts)):
-            rc = fn(G, hs, ios, sts)
-            if rc:
-                check(rc)
-        return call
+        return self._bind_steps([action], auto_reset, want_final)
 
     def bind_step_sequence(self, actions, auto_reset="next"):
         """K open-loop steps of every group behind ONE foreign call (cn_step_multi with K x G entries, step-major: the same
         launches in the same order as K calls of bind_step_all's callable, enqueued by a C loop instead of a Python one).
         actions: a sequence of K [N, 2] float32 device tensors (entries may repeat).  Returns a zero-argument callable."""
-        G, K = self.G, len(actions)
-        n = G * K
-        ios = (_abi.CnStepIO * n)()
-        hs = (C.c_void_p * n)()
-        sts = (C.c_void_p * n)()
-        keep = [actions]
-        ar = {False: 0, True: 1, None: 0, "same": 1, "next": 2}.get(auto_reset, auto_reset)
-        for i, action in enumerate(actions):
-            for g, e in enumerate(self.envs):
-                a = action[self.rows(g)]
-                assert a.device == e.device and a.dtype == torch.float32 and a.is_contiguous()
-                keep.append(a)
-                j = i * G + g
-                ios[j] = _abi.CnStepIO(action=a.data_ptr(), step_counter=None, obs=e.obs.data_ptr(), final_obs=None,
-                                       obs_f64=e.obs_f64.data_ptr() if e.obs_f64 is not None else None,
-                                       reward=e.reward.data_ptr(), done=e.done.data_ptr(), topk_idx=e.topk_idx.data_ptr(),
-                                       auto_reset=ar, reserved=0)
-                hs[j] = e.h.value
-                sts[j] = e._stream().value
-        fn, check = self.envs[0].L.cn_step_multi, _abi.check
+        return self._bind_steps(actions, auto_reset, False)
 
-        def call(_keep=(keep, ios, hs, sts)):
-            rc = fn(n, hs, ios, sts)
-            if rc:
-                check(rc)
-        return call
+    def _bind_steps(self, actions, auto_reset, want_final):
+        args, keep = multi_io(self.envs, actions, auto_reset, want_final)
+        return _enqueuer(self.envs[0].L.cn_step_multi, args, (keep, args))
 
     def step_group(self, g, action, **kw):
         """Env.step for group g on its own stream; `action` is that group's [n, 2] slice."""

@@ -107,17 +107,11 @@ static double angle_increment_deg(int R)
     return 360.0 / (double)(R - 1);
 }
 
-// One field of every env's record <-> a dense host array [N, width bytes]
+// One field of every env's record <- a dense host array [N, width bytes]
 static int field_to_device(cn_env_s* h, size_t off, const void* host, size_t width)
 {
     if (!width) return CN_OK;
     CN_HIPCHK(fail, hipMemcpy2D(h->d_state + off, h->stride, host, width, width, (size_t)h->cfg.n_envs, hipMemcpyHostToDevice));
-    return CN_OK;
-}
-static int field_to_host(cn_env_s* h, size_t off, void* host, size_t width)
-{
-    if (!width) return CN_OK;
-    CN_HIPCHK(fail, hipMemcpy2D(host, width, h->d_state + off, h->stride, width, (size_t)h->cfg.n_envs, hipMemcpyDeviceToHost));
     return CN_OK;
 }
 #define FIELD(call) do { int rc_ = (call); if (rc_ != CN_OK) return rc_; } while (0)
@@ -550,12 +544,18 @@ static CnKParams roll_params(cn_handle h, const IO* io)
     kp.roll_reward_stride = io->reward_stride; kp.roll_done_stride = io->done_stride; kp.roll_topk_stride = io->topk_stride;
     return kp;
 }
+template <typename IO>
+static bool roll_null(const IO* io) { return !io || !io->action || !io->obs || !io->reward || !io->done; }
+template <typename IO>
+static bool roll_negative(const IO* io)
+{
+    return io->n_steps < 0 || io->action_stride < 0 || io->obs_stride < 0 || io->reward_stride < 0 || io->done_stride < 0 || io->topk_stride < 0;
+}
 
 extern "C" int cn_step_sequence(cn_handle h, const cn_sequence_io* io, void* stream)
 {
-    if (!h || !io || !io->action || !io->obs || !io->reward || !io->done) return fail(CN_ERR_ARG, "cn_step_sequence: null argument");
-    if (io->n_steps < 0 || io->action_stride < 0 || io->obs_stride < 0 || io->reward_stride < 0 || io->done_stride < 0 || io->topk_stride < 0)
-        return fail(CN_ERR_ARG, "cn_step_sequence: negative step count or stride");
+    if (!h || roll_null(io)) return fail(CN_ERR_ARG, "cn_step_sequence: null argument");
+    if (roll_negative(io)) return fail(CN_ERR_ARG, "cn_step_sequence: negative step count or stride");
     if (io->n_steps == 0) return CN_OK;
     CnKParams kp = roll_params(h, io);
     DeviceScope scope(h->device);
@@ -567,15 +567,14 @@ extern "C" int cn_step_sequence(cn_handle h, const cn_sequence_io* io, void* str
 
 extern "C" int cn_rollout_policy(cn_handle h, const cn_actor_weights* w, const cn_policy_io* io, void* stream)
 {
-    if (!h || !w || !io || !io->obs0 || !io->action || !io->obs || !io->reward || !io->done || !w->w1p || !w->b1 || !w->w2p || !w->b2 || !w->w3 || !w->b3)
+    if (!h || !w || roll_null(io) || !io->obs0 || !w->w1p || !w->b1 || !w->w2p || !w->b2 || !w->w3 || !w->b3)
         return fail(CN_ERR_ARG, "cn_rollout_policy: null argument");
     if (!h->pol_lds)
         return fail(CN_ERR_CONFIG, "cn_rollout_policy: not even 8 environments of this shape fit one CU's LDS (160 KiB)");
     const int D = h->D;      // 366 + 4 K, or 363 / 370 at 360 rays for the two older layouts
     if (w->hidden != 256 || w->obs_dim != D || w->obs_dim_padded != ((D + 31) & ~31))
         return fail(CN_ERR_CONFIG, "cn_rollout_policy: the actor must be cn_actor_pack_weights' layout for this handle's observation width (hidden 256, obs_dim_padded = obs_dim rounded up to 32)");
-    if (io->n_steps < 0 || io->action_stride < 0 || io->obs_stride < 0 || io->reward_stride < 0 || io->done_stride < 0 || io->topk_stride < 0)
-        return fail(CN_ERR_ARG, "cn_rollout_policy: negative step count or stride");
+    if (roll_negative(io)) return fail(CN_ERR_ARG, "cn_rollout_policy: negative step count or stride");
     if (io->n_steps == 0) return CN_OK;
     CnKParams kp = roll_params(h, io);
     kp.pol_w1p = w->w1p; kp.pol_b1 = w->b1; kp.pol_w2p = w->w2p; kp.pol_b2 = w->b2; kp.pol_w3 = w->w3; kp.pol_b3 = w->b3;
@@ -636,10 +635,40 @@ extern "C" int cn_debug_env(cn_handle h, int env, double* scalars, double* robot
 }
 
 // snapshot layout (include/crowdnav.h): cn_snapshot_header | sd | si | ped_p | ped_v | trk | ped_init | ped_preset | ped_aux
+// One section: N rows of `width` bytes, `pitch` bytes apart on the device (a field of the env records) or dense (pitch 0: an array of
+// its own; of a wide handle's d_trk the N tables, not the scratch column behind them).  Width 0 (no pedestrians): nothing to copy.
+struct SnapSection { void* dev; size_t pitch, width; std::vector<double>* host_copy; };
+static std::vector<SnapSection> snapshot_sections(cn_handle h)
+{
+    const size_t P = h->cfg.n_peds, S = h->stride;
+    char* st = h->d_state;
+    return {{st + CN_ST_OFF_SD, S, CN_SD_COUNT * 8, nullptr},     {st + CN_ST_OFF_SI, S, CN_SI_COUNT * 4, nullptr},
+            {st + CN_ST_OFF_PED_P, S, P * 16, nullptr},           {st + CN_ST_OFF_PED_V(P), S, P * 16, nullptr},
+            {h->d_trk, 0, (size_t)CN_TF_COUNT * h->trk_cap * 8, nullptr},
+            {h->d_ped_init, 0, P * 16, &h->ped_init},             // (cn_reset re-uploads the host copy: a restore refreshes it)
+            {h->d_ped_preset, 0, P * 16, nullptr},                {h->d_ped_aux, 0, P * 24, nullptr}};
+}
+// every section to (restore = false) or from (true) the payload at `q`
+static int snapshot_copy(cn_handle h, char* q, bool restore)
+{
+    const size_t N = h->cfg.n_envs;
+    for (const SnapSection& s : snapshot_sections(h)) {
+        if (!s.width) continue;
+        if (restore && s.host_copy) s.host_copy->assign((const double*)q, (const double*)(q + N * s.width));
+        const hipMemcpyKind kind = restore ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+        void* dst = restore ? s.dev : (void*)q;
+        const void* src = restore ? (const void*)q : s.dev;
+        if (s.pitch) CN_HIPCHK(fail, hipMemcpy2D(dst, restore ? s.pitch : s.width, src, restore ? s.width : s.pitch, s.width, N, kind));
+        else CN_HIPCHK(fail, hipMemcpy(dst, src, N * s.width, kind));
+        q += N * s.width;
+    }
+    return CN_OK;
+}
 static size_t snapshot_payload(cn_handle h)
 {
-    size_t N = h->cfg.n_envs, P = h->cfg.n_peds;
-    return N * (CN_SD_COUNT * 8 + CN_SI_COUNT * 4 + 2 * P * 16 + (size_t)CN_TF_COUNT * h->trk_cap * 8 + 2 * P * 16 + P * 24);
+    size_t row = 0;
+    for (const SnapSection& s : snapshot_sections(h)) row += s.width;
+    return row * h->cfg.n_envs;
 }
 extern "C" size_t cn_snapshot_size(cn_handle h)
 {
@@ -662,24 +691,10 @@ extern "C" int cn_snapshot(cn_handle h, void* buf, size_t size)
     if (size < cn_snapshot_size(h)) return fail(CN_ERR_SIZE, "cn_snapshot: buffer too small");
     DeviceScope scope(h->device);
     CN_HIPCHK(fail, hipDeviceSynchronize());
-    size_t N = h->cfg.n_envs, P = h->cfg.n_peds;
-    char* q = (char*)buf;
     cn_snapshot_header hd;
     fill_header(h, &hd);
-    memcpy(q, &hd, sizeof(hd)); q += sizeof(hd);
-    FIELD(field_to_host(h, CN_ST_OFF_SD, q, CN_SD_COUNT * 8)); q += N * CN_SD_COUNT * 8;
-    FIELD(field_to_host(h, CN_ST_OFF_SI, q, CN_SI_COUNT * 4)); q += N * CN_SI_COUNT * 4;
-    if (P) {
-        FIELD(field_to_host(h, CN_ST_OFF_PED_P, q, P * 16)); q += N * P * 16;
-        FIELD(field_to_host(h, CN_ST_OFF_PED_V(P), q, P * 16)); q += N * P * 16;
-    }
-    CN_HIPCHK(fail, hipMemcpy(q, h->d_trk, N * CN_TF_COUNT * h->trk_cap * 8, hipMemcpyDeviceToHost)); q += N * CN_TF_COUNT * h->trk_cap * 8;
-    if (P) {
-        CN_HIPCHK(fail, hipMemcpy(q, h->d_ped_init, N * P * 16, hipMemcpyDeviceToHost)); q += N * P * 16;
-        CN_HIPCHK(fail, hipMemcpy(q, h->d_ped_preset, N * P * 16, hipMemcpyDeviceToHost)); q += N * P * 16;
-        CN_HIPCHK(fail, hipMemcpy(q, h->d_ped_aux, N * P * 24, hipMemcpyDeviceToHost)); q += N * P * 24;
-    }
-    return CN_OK;
+    memcpy(buf, &hd, sizeof(hd));
+    return snapshot_copy(h, (char*)buf + sizeof(hd), false);
 }
 
 // first field of the two configurations that differs (nullptr: identical)
@@ -716,20 +731,5 @@ extern "C" int cn_restore(cn_handle h, const void* buf, size_t size)
     if (hd.total_bytes != cn_snapshot_size(h) || size < hd.total_bytes) return fail(CN_ERR_SIZE, "cn_restore: truncated snapshot");
     DeviceScope scope(h->device);
     CN_HIPCHK(fail, hipDeviceSynchronize());
-    size_t N = h->cfg.n_envs, P = h->cfg.n_peds;
-    const char* q = (const char*)buf + sizeof(hd);
-    FIELD(field_to_device(h, CN_ST_OFF_SD, q, CN_SD_COUNT * 8)); q += N * CN_SD_COUNT * 8;
-    FIELD(field_to_device(h, CN_ST_OFF_SI, q, CN_SI_COUNT * 4)); q += N * CN_SI_COUNT * 4;
-    if (P) {
-        FIELD(field_to_device(h, CN_ST_OFF_PED_P, q, P * 16)); q += N * P * 16;
-        FIELD(field_to_device(h, CN_ST_OFF_PED_V(P), q, P * 16)); q += N * P * 16;
-    }
-    CN_HIPCHK(fail, hipMemcpy(h->d_trk, q, N * CN_TF_COUNT * h->trk_cap * 8, hipMemcpyHostToDevice)); q += N * CN_TF_COUNT * h->trk_cap * 8;
-    if (P) {
-        h->ped_init.assign((const double*)q, (const double*)q + N * P * 2);
-        CN_HIPCHK(fail, hipMemcpy(h->d_ped_init, q, N * P * 16, hipMemcpyHostToDevice)); q += N * P * 16;
-        CN_HIPCHK(fail, hipMemcpy(h->d_ped_preset, q, N * P * 16, hipMemcpyHostToDevice)); q += N * P * 16;
-        CN_HIPCHK(fail, hipMemcpy(h->d_ped_aux, q, N * P * 24, hipMemcpyHostToDevice)); q += N * P * 24;
-    }
-    return CN_OK;
+    return snapshot_copy(h, (char*)buf + sizeof(hd), true);      // (only read from)
 }
