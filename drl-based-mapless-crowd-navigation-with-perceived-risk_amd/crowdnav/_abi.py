@@ -42,12 +42,15 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_replay_sample_indices", "cn_replay_write", "cn_episode_log_add",
            "cn_td3_pop_create", "cn_td3_pop_destroy", "cn_td3_pop_update", "cn_td3_pop_members", "cn_td3_pop_loss_dev",
            "cn_td3_pop_batch_dev", "cn_td3_pop_set_replay_sample",
+           "cn_td3_pop_pbt_bind", "cn_td3_pop_exploit", "cn_td3_pop_pbt_state_dev",
            "cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", "cn_actor_pop_pack", "cn_actor_pop_forward",
            "cn_actor_pop_weights",
            "cn_pop_record_create", "cn_pop_record_destroy", "cn_pop_record_members", "cn_pop_record_resetting", "cn_pop_record"]
 CN_TD3_POP_MAX = 64         # include/crowdnav.h: cn_td3_pop_create's n_members is 1 ... 64
 CN_ACTOR_POP_MAX = 64       # include/crowdnav.h: cn_actor_pop_create's n_members is 1 ... 64
 CN_POP_RECORD_MAX = 64      # include/crowdnav.h: cn_pop_record_create's n_members is 1 ... 64
+CN_PBT_HYPER_NAMES = ("lr_actor", "lr_critic", "gamma", "noise_std", "noise_clip")      # include/crowdnav.h: CN_PBT_LR_ACTOR ... in order
+CN_PBT_HYPERS = len(CN_PBT_HYPER_NAMES)
 CN_SAMPLE_WITH_REPLACEMENT, CN_SAMPLE_DISTINCT = 0, 1      # include/crowdnav.h: cn_*_set_replay_sample
 REPLAY_SAMPLE = {"with": CN_SAMPLE_WITH_REPLACEMENT, "without": CN_SAMPLE_DISTINCT}
 
@@ -252,6 +255,22 @@ class CnEpisodeLog(C.Structure):
     _fields_ = [("rows", C.c_void_p), ("max_rows", C.c_int64), ("n_dev", C.c_void_p), ("tot_dev", C.c_void_p)]
 
 
+class CnTd3PbtConfig(C.Structure):
+    """Mirror of `cn_td3_pbt_config` (include/crowdnav.h)."""
+    _fields_ = [("n_replace", C.c_int32), ("min_episodes", C.c_int32), ("explore_mask", C.c_uint32), ("reserved", C.c_int32),
+                ("factor", C.c_float * 2), ("lo", C.c_float * CN_PBT_HYPERS), ("hi", C.c_float * CN_PBT_HYPERS), ("seed", C.c_uint64)]
+
+
+class CnTd3PbtMember(C.Structure):
+    """Mirror of `cn_td3_pbt_member` (include/crowdnav.h)."""
+    _fields_ = [("src", C.c_int32), ("generation", C.c_int32), ("fitness", C.c_float), ("hyper", C.c_float * CN_PBT_HYPERS)]
+
+
+class CnTd3PbtState(C.Structure):
+    """Mirror of `cn_td3_pbt_state` (include/crowdnav.h)."""
+    _fields_ = [("calls", C.c_uint64), ("applied", C.c_uint64), ("member", CnTd3PbtMember * CN_TD3_POP_MAX)]
+
+
 class CnPopRecordMember(C.Structure):
     """Mirror of `cn_pop_record_member` (include/crowdnav.h): one member of cn_pop_record_create."""
     _fields_ = [("env", C.c_void_p), ("counters", C.c_void_p), ("last_return", C.c_void_p), ("prev", C.c_void_p), ("obs", C.c_void_p),
@@ -380,6 +399,9 @@ def lib():
         L.cn_td3_pop_loss_dev.argtypes = [vp]; L.cn_td3_pop_loss_dev.restype = vp
         L.cn_td3_pop_batch_dev.argtypes = [vp, C.c_int, C.c_int]; L.cn_td3_pop_batch_dev.restype = vp
         L.cn_td3_pop_set_replay_sample.argtypes = [vp, C.c_int]
+        L.cn_td3_pop_pbt_bind.argtypes = [vp, C.POINTER(CnTd3PbtConfig), C.POINTER(CnEpisodeLog)]      # logs: an array of n_members, or None
+        L.cn_td3_pop_exploit.argtypes = [vp, vp, vp]
+        L.cn_td3_pop_pbt_state_dev.argtypes = [vp]; L.cn_td3_pop_pbt_state_dev.restype = vp
         L.cn_actor_pop_create.argtypes = [C.POINTER(CnActorPopMember), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]      # an array of members
         L.cn_actor_pop_destroy.argtypes = [vp]; L.cn_actor_pop_destroy.restype = None
         L.cn_actor_pop_members.argtypes = [vp]

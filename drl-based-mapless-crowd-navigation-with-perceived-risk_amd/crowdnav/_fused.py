@@ -119,6 +119,36 @@ class FusedPopulation:
             raise _abi.CrowdNavError("cn_td3_pop_batch_dev: member %r / what %r out of range" % (member, what))
         return _device_view(ptr, shape, dtype, self.device)
 
+    def pbt_bind(self, cfg, logs=None, keep=None):
+        """cn_td3_pop_pbt_bind: cfg a CnTd3PbtConfig, logs the members' CnEpisodeLog in member order or None; keep: what the logs
+        point into.  Synchronises (it uploads the state); binding again starts over."""
+        arr = (_abi.CnEpisodeLog * self.P)(*logs) if logs is not None else None
+        self._check("pbt_bind", self._L.cn_td3_pop_pbt_bind(self.h, C.byref(cfg), arr))
+        self._pbt_keep = (cfg, arr, keep)
+        nbytes = C.sizeof(_abi.CnTd3PbtState)
+        ptr = self._L.cn_td3_pop_pbt_state_dev(self.h)
+
+        class _Arr:
+            __cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+        self._pbt_state = torch.as_tensor(_Arr(), device=self.device)
+        self._pbt_host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+
+    def exploit(self, fitness=None):
+        """cn_td3_pop_exploit on torch's current stream: two launches, enqueue-only.  fitness: float32 [P] on the device, or None = from
+        the bound logs."""
+        if fitness is not None and not (fitness.dtype == torch.float32 and fitness.is_cuda and fitness.is_contiguous() and fitness.numel() == self.P):
+            raise ValueError("fitness must be a contiguous float32 tensor of %d values on %s" % (self.P, self.device))
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._pbt_fitness = fitness                # alive until the next call: the launches are asynchronous
+        self._check("exploit", self._L.cn_td3_pop_exploit(self.h, None if fitness is None else C.c_void_p(fitness.data_ptr()), st))
+
+    def pbt_state(self):
+        """One device-to-host copy of cn_td3_pbt_state (it waits for the stream) -> a CnTd3PbtState."""
+        if getattr(self, "_pbt_state", None) is None:
+            raise _abi.CrowdNavError("cn_td3_pop_pbt_state_dev: no cn_td3_pop_pbt_bind yet")
+        self._pbt_host.copy_(self._pbt_state)
+        return _abi.CnTd3PbtState.from_buffer_copy(self._pbt_host.numpy().tobytes())
+
     def __del__(self):
         try:
             if self.h:

@@ -692,6 +692,73 @@ class Population:
             raise RuntimeError("Population.bind_record first")
         return self._recorder.resetting(p)
 
+    # ---- population-based training: cn_td3_pop_pbt_bind / cn_td3_pop_exploit (include/crowdnav.h) -----------------------------------
+    PBT_BOUNDS = dict(lr_actor=(1e-5, 1e-2), lr_critic=(1e-5, 1e-2), gamma=(0.9, 0.9999), noise_std=(0.02, 1.0), noise_clip=(0.05, 2.0))
+
+    def bind_pbt(self, n_replace, factor=(0.8, 1.2), explore=("lr_actor", "lr_critic", "noise_std"), bounds=None, min_episodes=10, seed=0,
+                 elogs=None):
+        """Set up exploit / explore: at every exploit() the n_replace worst members take over the networks and the optimizer state of
+        members among the n_replace best, and the hyper-parameters named in `explore` (of lr_actor, lr_critic, gamma, noise_std,
+        noise_clip) are multiplied by one of the two factors and clamped to bounds[name] = (lo, hi); the others are inherited.
+        bounds: a dict overriding PBT_BOUNDS per name; a default bound is widened to hold every member's starting value.  elogs: the
+        members' episode logs (as bind_record takes them; tot is read as CUMULATIVE totals) -- exploit() without a fitness then ranks
+        by the mean return of the episodes finished since the last applied call and does nothing while a member has fewer than
+        min_episodes new ones."""
+        from . import _abi
+        names = _abi.CN_PBT_HYPER_NAMES
+        unknown = [n for n in tuple(explore) + tuple(bounds or ()) if n not in names]
+        if unknown:
+            raise ValueError("unknown hyper-parameter(s) %s: population-based training knows %s" % (", ".join(map(repr, unknown)), ", ".join(names)))
+        start = [self._pbt_hypers(a) for a in self.agents]
+        lo, hi = [], []
+        for k, n in enumerate(names):
+            if bounds and n in bounds:
+                l, h = bounds[n]
+            else:
+                l, h = self.PBT_BOUNDS[n]
+                l, h = min([l] + [s[k] for s in start]), max([h] + [s[k] for s in start])
+            lo.append(l); hi.append(h)
+        cfg = _abi.CnTd3PbtConfig(n_replace=int(n_replace), min_episodes=int(min_episodes), explore_mask=sum(1 << names.index(n) for n in set(explore)),
+                                  reserved=0, factor=tuple(float(f) for f in factor), lo=tuple(lo), hi=tuple(hi), seed=int(seed) & (2 ** 64 - 1))
+        logs = None
+        if elogs is not None:
+            elogs = list(elogs)
+            if len(elogs) != len(self.agents):
+                raise ValueError("bind_pbt takes one episode log per member")
+            logs = [_abi.CnEpisodeLog(rows=lg.rows.data_ptr(), max_rows=lg.max_rows, n_dev=lg.n.data_ptr(), tot_dev=lg.tot.data_ptr()) for lg in elogs]
+        self._fused.pbt_bind(cfg, logs, keep=elogs)
+        return self
+
+    @staticmethod
+    def _pbt_hypers(a):
+        """An agent's five hyper-parameters in CN_PBT_* order, as fused_config() hands them to the library."""
+        return [a.opt_a.param_groups[0]["lr"], a.opt_q1.param_groups[0]["lr"], a.gamma, a.noise_std, a.noise_clip]
+
+    def exploit(self, fitness=None):
+        """One exploit / explore step (cn_td3_pop_exploit: two launches on torch's current stream, no host read), then sync_actors()
+        when the actors are bound: the re-pack reads the nn.Linear storages that were just overwritten.  fitness: float32 [P] on the
+        device, higher is better; None = from the logs bound by bind_pbt."""
+        self._fused.exploit(fitness)
+        if self._actors is not None:
+            self.sync_actors()
+
+    def pbt_state(self):
+        """One device-to-host copy of the PBT state -> dict(calls, applied, members=[dict(src, generation, fitness, lr_actor, lr_critic,
+        gamma, noise_std, noise_clip)]).  Also brings the agents' Python-side hyper-parameters (the optimizers' lr, actor_lr,
+        critic_lr, gamma, noise_std, noise_clip) up to what the device trains with, so that checkpoints and logs show those."""
+        from . import _abi
+        st = self._fused.pbt_state()
+        members = []
+        for p, a in enumerate(self.agents):
+            m = st.member[p]
+            row = dict(src=int(m.src), generation=int(m.generation), fitness=float(m.fitness))
+            row.update({n: float(m.hyper[k]) for k, n in enumerate(_abi.CN_PBT_HYPER_NAMES)})
+            members.append(row)
+            a.actor_lr, a.critic_lr, a.gamma, a.noise_std, a.noise_clip = (row[n] for n in _abi.CN_PBT_HYPER_NAMES)
+            a.opt_a.param_groups[0]["lr"] = a.actor_lr
+            a.opt_q1.param_groups[0]["lr"] = a.opt_q2.param_groups[0]["lr"] = a.critic_lr
+        return dict(calls=int(st.calls), applied=int(st.applied), members=members)
+
     def set_replay_sample(self, replay_sample):
         self._fused.set_replay_sample(replay_sample)
 

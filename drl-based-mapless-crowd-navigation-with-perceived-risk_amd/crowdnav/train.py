@@ -565,6 +565,25 @@ class MemberEnvs(VecEnvGroups):
         return self._cfgs[g]
 
 
+PBT_CSV_COLUMNS = ("launch", "call", "member", "src", "generation", "fitness", "lr_actor", "lr_critic", "gamma", "noise_std", "noise_clip")
+PBT_HYPERS = PBT_CSV_COLUMNS[6:]
+
+
+def _mix64(z):
+    """splitmix64's finaliser on Python integers (include/crowdnav.h: mix64)."""
+    m = (1 << 64) - 1
+    z = (z + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+def pbt_spread_factors(seed, member, spread):
+    """--pbt-spread S: member p's factors for (lr_actor, lr_critic, noise_std), log-uniform in [1/S, S], a function of (seed, p) alone."""
+    key = _mix64((int(seed) & ((1 << 64) - 1)) ^ 0x504254)
+    return [float(spread) ** (2.0 * ((_mix64(key ^ (8 * member + k)) >> 11) * 2.0 ** -53) - 1.0) for k in range(3)]
+
+
 def train_population(a):
     """--population P: P independent TD3 runs, seeds a.seed ... a.seed + P - 1, whose updates are ONE cn_td3_pop_update per update
     (crowdnav.td3.Population) instead of P processes.  Member p has what `train()` with --seed <seed + p> has -- its environment
@@ -575,10 +594,17 @@ def train_population(a):
     copies around them); once EVERY member's replay holds more than a batch, --updates population updates and ONE re-pack of the P
     actors (per-member: P sync_fused_weights, 4 launches each).
     The two --population-act values give the same run, bit for bit, and so do the two --population-record values.
-    Member p's run IS the solo run --seed <seed + p> --learner fused (same parameters, same CSV rows) as long as the members' rings pass
+    While PBT is off (--pbt-every 0, --pbt-spread 0: the default), member p's run IS the solo run --seed <seed + p> --learner fused
+    (same parameters, same CSV rows) as long as the members' rings pass
     the batch size on the same launch: a member whose ring is not ready yet (it lost rows to reset launches) holds the others back, so
     that the update counters -- which key the sampling and drive policy_delay -- stay aligned; from then on that member's solo run
-    would have started its updates earlier."""
+    would have started its updates earlier.
+    --pbt-every L > 0 (population-based training): after the updates of every L-th launch, once learning has begun, ONE
+    Population.exploit() -- two launches that rank the members by the mean return of the episodes each finished since the last applied
+    call, copy the best members' networks and optimizer state over the worst --pbt-fraction of them, and perturb the hyper-parameters
+    of --pbt-explore by one of --pbt-factor -- then one read of the PBT state (the only host read PBT adds), whose rows go to
+    <out>/pbt_log.csv.  --pbt-spread S > 0 starts member p with lr_actor, lr_critic and noise_std multiplied by a keyed log-uniform
+    factor in [1/S, S]: the sweep PBT then acts on."""
     fill_defaults(a)
     dev = a.device
     P = a.population
@@ -595,7 +621,13 @@ def train_population(a):
             e.set_ped_init(init)
         if vel is not None:
             e.set_ped_preset_vel(vel)
-    agents = [make_agent(m, envs.D, "cuda:%d" % dev, memory_size=a.memory, actor_final_init=a.actor_final_init) for m in members]
+    spread = [{} for _ in members]
+    if a.pbt_spread > 0:
+        for p, m in enumerate(members):
+            f = pbt_spread_factors(a.seed, p, a.pbt_spread)
+            m.lr_actor, m.lr_critic = (a.lr_actor or 3e-4) * f[0], (a.lr_critic or 3e-4) * f[1]
+            spread[p] = dict(noise_std=0.2 * f[2])
+    agents = [make_agent(m, envs.D, "cuda:%d" % dev, memory_size=a.memory, actor_final_init=a.actor_final_init, **kw) for m, kw in zip(members, spread)]
     pop = td3.Population(agents)
     obs = envs.reset()
     step_s = (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0
@@ -621,6 +653,17 @@ def train_population(a):
     if one_call:
         prev.copy_(obs)                                                # once: every record() leaves the new observation in prev
         pop.bind_record(envs.envs, *[[x[r] for r in rows] for x in (prev, obs, act, reward, done)], elogs)
+    if a.pbt_every:
+        # the logs' totals restart at every flush; PBT ranks on totals that never do: what was flushed so far + the running ones
+        pbt_flushed = torch.zeros((P, 5), dtype=torch.float64, device=obs.device)
+        pbt_tot = torch.zeros((P, 5), dtype=torch.float64, device=obs.device)
+        pop.bind_pbt(a.pbt_n_replace, factor=a.pbt_factor, explore=a.pbt_explore, min_episodes=a.pbt_min_episodes, seed=a.seed,
+                     elogs=[argparse.Namespace(rows=e.rows, max_rows=e.max_rows, n=e.n, tot=pbt_tot[p]) for p, e in enumerate(elogs)])
+        pbt_applied = 0
+        os.makedirs(a.out, exist_ok=True)
+        pbt_csv = open(os.path.join(a.out, "pbt_log.csv"), "a")
+        if pbt_csv.tell() == 0:
+            pbt_csv.write(",".join(PBT_CSV_COLUMNS) + "\n")
     for it in range(1, a.launches + 1):
         if one_launch:
             pop.act(add_noise=True)
@@ -655,12 +698,29 @@ def train_population(a):
             else:
                 for ag in agents:
                     ag.sync_fused_weights()
+            if a.pbt_every and it % a.pbt_every == 0:
+                torch.add(pbt_flushed, torch.stack([e.tot for e in elogs]), out=pbt_tot)
+                pop.exploit()                                          # (re-packs the bound actors)
+                if not one_launch:
+                    for ag in agents:
+                        ag.sync_fused_weights()
+                st = pop.pbt_state()                                   # the one host read PBT adds: once per --pbt-every launches
+                if st["applied"] > pbt_applied:
+                    pbt_applied = st["applied"]
+                    for p, m in enumerate(st["members"]):
+                        pbt_csv.write(",".join(["%d" % it, "%d" % (st["calls"] - 1), "%d" % p, "%d" % m["src"], "%d" % m["generation"]] +
+                                               ["%.9g" % m[k] for k in PBT_CSV_COLUMNS[5:]]) + "\n")
+                    pbt_csv.flush()
         last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
         if it % a.log_every == 0 or last_launch:
+            if a.pbt_every:
+                pbt_flushed.add_(torch.stack([e.tot for e in elogs]))     # (RunLog.log flushes: the totals restart)
             for run in runs:
                 run.log(it, updates_done)
             if last_launch:
                 break
+    if a.pbt_every:
+        pbt_csv.close()
     for run in runs:
         run.finish(updates_done)
     return agents, [run.episodes for run in runs]
@@ -755,6 +815,20 @@ def build_parser():
     ap.add_argument("--population-record", default=None, choices=["one-call", "per-member"], help="--population only: one-call (default) = all "
                     "members' replay writes and episode logs in one cn_pop_record (two launches) per training launch; per-member = one "
                     "cn_replay_write, cn_get_counters, cn_get_returns and cn_episode_log_add per member.  Same results, bit for bit")
+    ap.add_argument("--pbt-every", type=int, default=None, help="--population only: L > 0 = population-based training, one Population.exploit() "
+                    "(cn_td3_pop_exploit) after the updates of every L-th launch once learning has begun: the worst members copy the best "
+                    "members' networks and optimizer state and perturb their hyper-parameters, on the device; rows go to <out>/pbt_log.csv.  "
+                    "Default 0 = off (needs --population >= 2)")
+    ap.add_argument("--pbt-fraction", type=float, default=None, help="--population only: the fraction f of the members replaced per exploit, "
+                    "n_replace = max(1, floor(P f)) <= P / 2 (default 0.25)")
+    ap.add_argument("--pbt-factor", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="--population only: an explored "
+                    "hyper-parameter is multiplied by one of these two (default 0.8 1.2)")
+    ap.add_argument("--pbt-explore", default=None, help="--population only: comma-separated names of the hyper-parameters a replaced member "
+                    "perturbs, of " + ", ".join(PBT_HYPERS) + " (default lr_actor,lr_critic,noise_std); the others are inherited unchanged")
+    ap.add_argument("--pbt-min-episodes", type=int, default=None, help="--population only: an exploit changes nothing while a member has "
+                    "finished fewer than this many episodes since the last one that applied (default 10)")
+    ap.add_argument("--pbt-spread", type=float, default=None, help="--population only: S > 0 = member p starts with lr_actor, lr_critic and "
+                    "noise_std multiplied by a keyed log-uniform factor in [1/S, S] (default 0 = all members start alike)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="default: runs/<algo>")
     ap.add_argument("--csv", action="store_true", help="one CSV row per finished episode in the reference's 8-column schema (recorded on the device, appended to the file at "
@@ -815,6 +889,31 @@ def parse_args(argv=None):
         ap.error("--population-record selects how a --population records its transitions: it needs --population")
     if a.population_record is None:
         a.population_record = "one-call"
+    pbt_given = [k for k in ("pbt_every", "pbt_fraction", "pbt_factor", "pbt_explore", "pbt_min_episodes", "pbt_spread") if getattr(a, k) is not None]
+    if pbt_given and not a.population:
+        ap.error("%s: population-based training acts on a --population: it needs --population" % ", ".join("--" + k.replace("_", "-") for k in pbt_given))
+    for k, v in (("pbt_every", 0), ("pbt_fraction", 0.25), ("pbt_factor", [0.8, 1.2]), ("pbt_explore", "lr_actor,lr_critic,noise_std"),
+                 ("pbt_min_episodes", 10), ("pbt_spread", 0.0)):
+        if getattr(a, k) is None:
+            setattr(a, k, v)
+    a.pbt_factor = tuple(a.pbt_factor)
+    a.pbt_explore = tuple(n for n in a.pbt_explore.split(",") if n)
+    a.pbt_n_replace = 0
+    if pbt_given:
+        if a.pbt_every < 0 or a.pbt_min_episodes < 1 or a.pbt_spread < 0 or not all(0 < f < float("inf") for f in a.pbt_factor):
+            ap.error("--pbt-every and --pbt-spread must be >= 0, --pbt-min-episodes >= 1 and both --pbt-factor values finite and > 0")
+        unknown = [n for n in a.pbt_explore if n not in PBT_HYPERS]
+        if unknown:
+            ap.error("--pbt-explore: unknown hyper-parameter(s) %s; known: %s" % (", ".join(unknown), ", ".join(PBT_HYPERS)))
+        if not 0 <= a.pbt_fraction <= 1:
+            ap.error("--pbt-fraction must be a fraction of the population, 0 ... 1")
+    if a.pbt_every:
+        if a.population < 2:
+            ap.error("--pbt-every needs --population >= 2: the worst member copies from another")
+        a.pbt_n_replace = max(1, int(a.population * a.pbt_fraction))
+        if a.pbt_n_replace > a.population // 2:
+            ap.error("--pbt-fraction %g of --population %d replaces %d members: at most half (%d) can be replaced, the others are the sources"
+                     % (a.pbt_fraction, a.population, a.pbt_n_replace, a.population // 2))
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     if a.ou_act is not None and not a.ou_noise:

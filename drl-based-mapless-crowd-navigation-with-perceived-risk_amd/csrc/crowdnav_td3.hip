@@ -17,7 +17,8 @@
 // partials) | G (dl, dz2a evaluated) | H (three jobs).
 // The parameters are the caller's (PyTorch nn.Linear storages, weight [out][in]); Adam's moments and step counters live here.
 // The kernels are crowdnav_gemm.hip's, reached through its launchers; the handle's scaffold and the job builders, which DDPG, DQN
-// and SAC use as well, are crowdnav_learner.h.  This file is TD3 itself: the handle, the chain of launches, and the population.
+// and SAC use as well, are crowdnav_learner.h.  This file is TD3 itself: the handle, the chain of launches, and the population --
+// with the only two kernels defined here, population-based training's plan and copy (td3_pbt_plan_kernel, td3_pbt_copy_kernel).
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <algorithm>
@@ -27,6 +28,7 @@
 #include <vector>
 
 #include "../../include/crowdnav.h"
+#include "crowdnav_device.h"
 #include "crowdnav_learner.h"
 
 namespace {
@@ -52,7 +54,109 @@ struct Td3Record {                                 // td3_chain's emitter at cre
         for (int z = 0; z < njobs; ++z) s.job[z] = ga.job[z];
     }
 };
+// Population-based training's two launches (cn_td3_pop_exploit, at the end of this file; the statement: include/crowdnav.h).
+enum { PBT_TENSORS = 36 + 36 + 3 };                // per member: the parameters, Adam's moments, and adam[4], steps[2], pw[4] of the tick
+struct PbtTensor { float* p; uint32_t n, reserved; };                  // n floats at p (pw: 4 doubles = 8 floats)
+struct PbtPlan { int32_t applied, n; int32_t dst[32], src[32]; };      // launch A's word to launch B: bottom[k] = dst[k] copies from src[k]
+struct PbtPlanArgs {
+    cn_td3_pbt_config cfg;
+    cn_td3_pbt_state* state;
+    PbtPlan* plan;
+    double* last;                                  // [P][2]: the logs' {episodes, return sum} at the last applied call
+    const double* const* tot;                      // [P]: the bound logs' tot_dev, or null
+    PrepArgs* prep[2]; TickArgs* tick[2]; GemmJob* jobs;                // the update's tables, which hold the hyper-parameters by value
+    const int* gamma_jobs; int n_gamma;            // [P][n_gamma]: where `jobs` holds member p's gamma
+    const float* fitness;                          // [P] or null = from tot
+    int P;
+};
 }  // namespace
+
+// Launch A, one wavefront, thread p = member p: fitness, rank, plan; the state and the tables' hyper-parameters of the replaced.
+__global__ __launch_bounds__(64) void td3_pbt_plan_kernel(const PbtPlanArgs a)
+{
+    __shared__ float fit[64];
+    __shared__ int order[64];
+    const int p = threadIdx.x, P = a.P, n = a.cfg.n_replace;
+    const bool live = p < P;
+    const uint64_t c = a.state->calls;
+    float f = 0.f;
+    double e_now = 0.0, r_now = 0.0;
+    int few = 0;
+    if (live) {
+        if (a.fitness) f = a.fitness[p];
+        else {
+            e_now = a.tot[p][0]; r_now = a.tot[p][2];
+            const double de = e_now - a.last[2 * p], dr = r_now - a.last[2 * p + 1];
+            few = !(de >= (double)a.cfg.min_episodes);
+            f = (float)(dr / de);
+        }
+    }
+    if (__syncthreads_or(few)) {                   // skipped: the call counts and nothing else moves (every thread has read `calls`)
+        if (p == 0) { a.state->calls = c + 1; a.plan->applied = 0; }
+        return;
+    }
+    fit[p] = f;
+    __syncthreads();
+    int rank = 0;                                  // how many members stand before p: fitness descending, NaN last, then the index
+    if (live) {
+        const bool fn = f != f;
+        for (int q = 0; q < P; ++q) {
+            const float g = fit[q];
+            const bool gn = g != g;
+            const bool tie = (gn && fn) || (!gn && !fn && g == f);
+            rank += ((!gn && fn) || (!gn && !fn && g > f) || (tie && q < p)) ? 1 : 0;
+        }
+        order[rank] = p;
+    }
+    __syncthreads();
+    if (live) {
+        const uint64_t K = cn_mix64(a.cfg.seed ^ cn_mix64(c));
+        cn_td3_pbt_member& me = a.state->member[p];
+        const int k = P - 1 - rank;                // p = bottom[k]
+        me.fitness = f;
+        if (k < n) {
+            const int src = order[cn_mix64(K ^ (uint64_t)(k + 1)) % (uint64_t)n];
+            a.plan->dst[k] = p; a.plan->src[k] = src;
+            me.src = src; me.generation += 1;
+            float v[CN_PBT_HYPERS];
+            for (int j = 0; j < CN_PBT_HYPERS; ++j) {
+                float x = a.state->member[src].hyper[j];
+                if ((a.cfg.explore_mask >> j) & 1u) x = x * a.cfg.factor[cn_mix64(K ^ cn_mix64((uint64_t)(0x100 + 8 * p + j))) >> 63];
+                x = fminf(fmaxf(x, a.cfg.lo[j]), a.cfg.hi[j]);
+                me.hyper[j] = v[j] = x;
+            }
+            for (int q = 0; q < 2; ++q) {          // both chains' tick tables, both sampling modes' prep tables
+                a.tick[q][p].lr_actor = v[CN_PBT_LR_ACTOR]; a.tick[q][p].lr_critic = v[CN_PBT_LR_CRITIC];
+                a.prep[q][p].noise_std = v[CN_PBT_NOISE_STD]; a.prep[q][p].noise_clip = v[CN_PBT_NOISE_CLIP];
+            }
+            for (int g = 0; g < a.n_gamma; ++g) a.jobs[a.gamma_jobs[p * a.n_gamma + g]].hb_gamma = v[CN_PBT_GAMMA];
+        } else {
+            me.src = p;
+        }
+        if (!a.fitness) { a.last[2 * p] = e_now; a.last[2 * p + 1] = r_now; }
+    }
+    if (p == 0) { a.state->calls = c + 1; a.state->applied += 1; a.plan->applied = 1; a.plan->n = n; }
+}
+
+// Launch B, grid (chunks, PBT_TENSORS, n_replace): tensor y of member dst[z] <- that of src[z], bit for bit.  Any float count and any
+// 4-byte alignment: 16-byte accesses where the two pointers reach a 16-byte boundary together, single floats before, after and otherwise.
+__global__ __launch_bounds__(256) void td3_pbt_copy_kernel(const PbtPlan* plan, const PbtTensor* tens)
+{
+    if (!plan->applied) return;
+    const PbtTensor s = tens[plan->src[blockIdx.z] * PBT_TENSORS + blockIdx.y], d = tens[plan->dst[blockIdx.z] * PBT_TENSORS + blockIdx.y];
+    const float* sp = s.p;
+    float* dp = d.p;
+    const size_t n = d.n, tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+    const uintptr_t sa = (uintptr_t)sp, da = (uintptr_t)dp;
+    size_t head = n;
+    if (((sa ^ da) & 15) == 0) head = std::min(n, (size_t)(((16 - (sa & 15)) & 15) / 4));
+    const size_t n4 = (n - head) / 4;
+    for (size_t i = tid; i < head; i += stride) dp[i] = sp[i];
+    const float4* s4 = (const float4*)(sp + head);
+    float4* d4 = (float4*)(dp + head);
+    for (size_t i = tid; i < n4; i += stride) d4[i] = s4[i];
+    for (size_t i = head + 4 * n4 + tid; i < n; i += stride) dp[i] = sp[i];
+}
 
 // ---- TD3 --------------------------------------------------------------------------------------------------------------------
 struct cn_td3_s : ActorCritic {
@@ -191,9 +295,17 @@ struct cn_td3_pop_s {
     const TickArgs* tick[2] = {nullptr, nullptr};
     const GemmJob* jobs = nullptr;
     std::vector<PopStep> chain[2];
+    // population-based training (cn_td3_pop_pbt_bind / cn_td3_pop_exploit, below)
+    std::vector<int> gamma_jobs;                   // [P][n]: the indices into `jobs` where critic_bwd_job put member p's gamma, both chains
+    void* pbt = nullptr;                           // one allocation at bind: state, plan, last, the tensor table, the gamma indices, the logs' totals
+    cn_td3_pbt_config pbt_cfg;
+    PbtPlanArgs pbt_args;                          // launch A's arguments but for the fitness; the device pointers never change after the bind
+    const PbtTensor* pbt_tensors = nullptr;
+    int pbt_chunks = 0;
+    bool pbt_logs = false;
     cn_td3_pop_s() = default;
     cn_td3_pop_s(const cn_td3_pop_s&) = delete;
-    ~cn_td3_pop_s() { if (tables) { DeviceScope scope(device); (void)hipFree(tables); } }
+    ~cn_td3_pop_s() { if (tables || pbt) { DeviceScope scope(device); (void)hipFree(tables); (void)hipFree(pbt); } }
 };
 
 extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int device, cn_td3_pop_handle* out)
@@ -268,6 +380,8 @@ extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int d
     std::vector<TickArgs> htick((size_t)2 * P);
     std::vector<GemmJob> hjobs(njobs_all);
     size_t first = 0;
+    struct GammaAt { int job0, njobs; };           // a job of member 0 that carries gamma, and its step's jobs per member
+    std::vector<GammaAt> gamma_at;
     for (int a = 0; a < 2; ++a) {
         for (int p = 0; p < P; ++p) {
             cn_td3_s* m = h->mem[p].get();
@@ -287,10 +401,14 @@ extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int d
             if (first + (size_t)P * s0.njobs > hjobs.size()) return td3_fail(CN_ERR_ARG, f + ": job table size");      // (never: counted above)
             for (int p = 0; p < P; ++p)
                 for (int z = 0; z < s0.njobs; ++z) hjobs[first + (size_t)p * s0.njobs + z] = rec[a][p].step[k].job[z];
+            for (int z = 0; z < s0.njobs; ++z)                          // critic_bwd_job's jobs hold gamma by value: cn_td3_pop_exploit rewrites it
+                if (s0.job[z].hb_h2) gamma_at.push_back({(int)first + z, s0.njobs});
             first += (size_t)P * s0.njobs;
             h->chain[a].push_back(ps);
         }
     }
+    for (int p = 0; p < P; ++p)
+        for (const GammaAt& g : gamma_at) h->gamma_jobs.push_back(g.job0 + p * g.njobs);
     static_assert(CN_SAMPLE_WITH_REPLACEMENT == 0 && CN_SAMPLE_DISTINCT == 1, "the prep tables are indexed by the mode");
     for (int q = 0; q < 2; ++q) {
         e = hipMemcpy(prep[q], hprep.data() + (size_t)q * P, sizeof(PrepArgs) * P, hipMemcpyHostToDevice);
@@ -326,4 +444,128 @@ extern "C" int cn_td3_pop_update(cn_td3_pop_handle h, int do_actor, void* stream
     }
     CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
+}
+
+// ---- population-based training: exploit and explore on the device (the statement: include/crowdnav.h) ---------------------------
+// The hyper-parameters a member trains with lie by value in the tables above; launch A rewrites them for the replaced members, launch
+// B copies what the replaced take over.  Everything either launch reads is device memory that the bind laid out once.
+extern "C" int cn_td3_pop_pbt_bind(cn_td3_pop_handle h, const cn_td3_pbt_config* cfg, const cn_episode_log* logs)
+{
+    const std::string f("cn_td3_pop_pbt_bind");
+    if (!h || !cfg) return td3_fail(CN_ERR_ARG, f + ": null " + (h ? "cfg" : "handle"));
+    const cn_td3_pbt_config& c = *cfg;
+    const int P = h->P;
+    if (c.n_replace < 1 || c.n_replace > P / 2)
+        return td3_fail(CN_ERR_ARG, f + ": n_replace must be 1 ... n_members / 2 = " + std::to_string(P / 2) + " (the replaced and their sources are disjoint)");
+    if (c.min_episodes < 1) return td3_fail(CN_ERR_ARG, f + ": min_episodes must be >= 1");
+    for (int i = 0; i < 2; ++i)
+        if (!std::isfinite(c.factor[i]) || !(c.factor[i] > 0.f)) return td3_fail(CN_ERR_ARG, f + ": factor[" + std::to_string(i) + "] must be finite and > 0");
+    static const char* const hname[CN_PBT_HYPERS] = {"lr_actor", "lr_critic", "gamma", "noise_std", "noise_clip"};
+    for (int k = 0; k < CN_PBT_HYPERS; ++k)
+        if (!std::isfinite(c.lo[k]) || !std::isfinite(c.hi[k]) || c.lo[k] > c.hi[k])
+            return td3_fail(CN_ERR_ARG, f + ": lo / hi of " + hname[k] + " must be finite with lo <= hi");
+    if (c.explore_mask >> CN_PBT_HYPERS) return td3_fail(CN_ERR_ARG, f + ": explore_mask has bits at or above CN_PBT_HYPERS");
+    if (logs)
+        for (int p = 0; p < P; ++p)
+            if (!logs[p].rows || !logs[p].n_dev || !logs[p].tot_dev || logs[p].max_rows < 0)
+                return td3_fail(CN_ERR_ARG, f + ": member " + std::to_string(p) + ": incomplete log");
+    std::vector<cn_td3_pbt_member> member((size_t)P);
+    for (int p = 0; p < P; ++p) {
+        const cn_td3_config& m = h->mem[p]->cfg;
+        const float start[CN_PBT_HYPERS] = {m.lr_actor, m.lr_critic, m.gamma, m.noise_std, m.noise_clip};
+        member[p].src = p; member[p].generation = 0; member[p].fitness = 0.f;
+        for (int k = 0; k < CN_PBT_HYPERS; ++k) {
+            if (!(start[k] >= c.lo[k] && start[k] <= c.hi[k]))
+                return td3_fail(CN_ERR_CONFIG, f + ": member " + std::to_string(p) + ": " + hname[k] + " starts outside [lo, hi]");
+            member[p].hyper[k] = start[k];
+        }
+    }
+    DeviceScope scope(h->device);
+    // the tensors a replaced member takes over, in one order for all members
+    std::vector<PbtTensor> tens((size_t)P * PBT_TENSORS);
+    uint32_t longest = 0;
+    for (int p = 0; p < P; ++p) {
+        cn_td3_s* m = h->mem[p].get();
+        const cn_td3_mlp* nets[6] = {&m->cfg.actor, &m->cfg.actor_t, &m->cfg.q1, &m->cfg.q1_t, &m->cfg.q2, &m->cfg.q2_t};
+        PbtTensor* t = tens.data() + (size_t)p * PBT_TENSORS;
+        for (int net = 0; net < 6; ++net) {
+            const float* w[6] = {nets[net]->w1, nets[net]->b1, nets[net]->w2, nets[net]->b2, nets[net]->w3, nets[net]->b3};
+            for (int j = 0; j < 6; ++j) *t++ = {(float*)w[j], (uint32_t)param_count(net < 2 ? m->D : m->D + 2, net < 2 ? 2 : 1, m->H, j), 0};
+        }
+        for (int net = 0; net < 3; ++net) for (int j = 0; j < 6; ++j) for (int k = 0; k < 2; ++k)
+            *t++ = {m->mom[net][j][k], (uint32_t)param_count(net == 0 ? m->D : m->D + 2, net == 0 ? 2 : 1, m->H, j), 0};
+        *t++ = {m->adam, 4, 0}; *t++ = {m->steps, 2, 0}; *t++ = {(float*)m->pw, 8, 0};
+        for (int j = 0; j < PBT_TENSORS; ++j) longest = std::max(longest, tens[(size_t)p * PBT_TENSORS + j].n);
+    }
+    const int n_gamma = (int)(h->gamma_jobs.size() / (size_t)P);
+    std::vector<const double*> tot((size_t)P, nullptr);
+    if (logs) for (int p = 0; p < P; ++p) tot[p] = logs[p].tot_dev;
+    cn_td3_pbt_state* state = nullptr; PbtPlan* plan = nullptr; double* last = nullptr; const double** totd = nullptr;
+    PbtTensor* tensd = nullptr; int* gammad = nullptr;
+    auto layout = [&](Pool& pl) {
+        pl.take(state, 1); pl.take(last, (size_t)2 * P); pl.take(totd, (size_t)P); pl.take(tensd, tens.size());
+        pl.take(plan, 1); pl.take(gammad, h->gamma_jobs.size());
+    };
+    Pool count{nullptr};
+    layout(count);
+    void* block = nullptr;
+    hipError_t e = hipMalloc(&block, count.size);
+    if (e != hipSuccess) return td3_fail(CN_ERR_HIP, f + ": hipMalloc: " + hipGetErrorString(e));
+    Pool assign{(char*)block};
+    layout(assign);
+    e = hipMemset(block, 0, count.size);
+    if (e == hipSuccess) e = hipMemcpy(state->member, member.data(), sizeof(cn_td3_pbt_member) * P, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(totd, tot.data(), sizeof(double*) * P, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(tensd, tens.data(), sizeof(PbtTensor) * tens.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(gammad, h->gamma_jobs.data(), sizeof(int) * h->gamma_jobs.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && h->pbt) {               // binding again starts over: the tables go back to what the members' configurations say
+        e = hipDeviceSynchronize();
+        std::vector<TickArgs> tk((size_t)P);
+        std::vector<PrepArgs> pr((size_t)P);
+        std::vector<GemmJob> jb(h->gamma_jobs.size());
+        for (int q = 0; q < 2 && e == hipSuccess; ++q) {
+            e = hipMemcpy(tk.data(), h->tick[q], sizeof(TickArgs) * P, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(pr.data(), h->prep[q], sizeof(PrepArgs) * P, hipMemcpyDeviceToHost);
+            for (int p = 0; p < P; ++p) {
+                const cn_td3_config& m = h->mem[p]->cfg;
+                tk[p].lr_actor = m.lr_actor; tk[p].lr_critic = m.lr_critic; pr[p].noise_std = m.noise_std; pr[p].noise_clip = m.noise_clip;
+            }
+            if (e == hipSuccess) e = hipMemcpy((void*)h->tick[q], tk.data(), sizeof(TickArgs) * P, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy((void*)h->prep[q], pr.data(), sizeof(PrepArgs) * P, hipMemcpyHostToDevice);
+        }
+        for (size_t i = 0; i < h->gamma_jobs.size() && e == hipSuccess; ++i) {
+            const float gamma = h->mem[i / (size_t)n_gamma]->cfg.gamma;
+            e = hipMemcpy((char*)(h->jobs + h->gamma_jobs[i]) + offsetof(GemmJob, hb_gamma), &gamma, sizeof(float), hipMemcpyHostToDevice);
+        }
+    }
+    if (e != hipSuccess) { (void)hipFree(block); return td3_fail(CN_ERR_HIP, f + ": " + hipGetErrorString(e)); }
+    if (h->pbt) (void)hipFree(h->pbt);
+    h->pbt = block;
+    h->pbt_cfg = c; h->pbt_logs = logs != nullptr; h->pbt_tensors = tensd;
+    h->pbt_chunks = (int)std::min<uint32_t>(64u, std::max<uint32_t>(1u, (longest + 4095u) / 4096u));
+    PbtPlanArgs& a = h->pbt_args;
+    memset(&a, 0, sizeof(a));
+    a.cfg = c; a.state = state; a.plan = plan; a.last = last; a.tot = logs ? totd : nullptr;
+    for (int q = 0; q < 2; ++q) { a.prep[q] = const_cast<PrepArgs*>(h->prep[q]); a.tick[q] = const_cast<TickArgs*>(h->tick[q]); }
+    a.jobs = const_cast<GemmJob*>(h->jobs); a.gamma_jobs = gammad; a.n_gamma = n_gamma; a.P = P;
+    return CN_OK;
+}
+
+extern "C" int cn_td3_pop_exploit(cn_td3_pop_handle h, const float* fitness_dev, void* stream)
+{
+    if (!h) return td3_fail(CN_ERR_ARG, "cn_td3_pop_exploit: null handle");
+    if (!h->pbt) return td3_fail(CN_ERR_ARG, "cn_td3_pop_exploit: cn_td3_pop_pbt_bind first");
+    if (!fitness_dev && !h->pbt_logs) return td3_fail(CN_ERR_ARG, "cn_td3_pop_exploit: no fitness_dev and no logs were bound");
+    DeviceScope scope(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    PbtPlanArgs a = h->pbt_args;
+    a.fitness = fitness_dev;
+    hipLaunchKernelGGL(td3_pbt_plan_kernel, dim3(1), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(td3_pbt_copy_kernel, dim3(h->pbt_chunks, PBT_TENSORS, h->pbt_cfg.n_replace), dim3(256), 0, st, a.plan, h->pbt_tensors);
+    CN_HIPCHK(td3_fail, hipGetLastError());
+    return CN_OK;
+}
+extern "C" const cn_td3_pbt_state* cn_td3_pop_pbt_state_dev(cn_td3_pop_handle h)
+{
+    return (h && h->pbt) ? h->pbt_args.state : nullptr;
 }

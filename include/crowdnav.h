@@ -789,6 +789,63 @@ int cn_pop_record_members(cn_pop_record_handle h);
 uint8_t* cn_pop_record_resetting(cn_pop_record_handle h, int member);        /* dev [n_member] bytes, owned by the handle */
 int cn_pop_record(cn_pop_record_handle h, float launch, void* stream);        /* at most TWO launches */
 
+/* Population-based training on a cn_td3_pop handle: every so often the n_replace worst members take over the networks and the
+ * optimizer state of members among the n_replace best (exploit) and perturb the hyper-parameters they inherit (explore).  The
+ * hyper-parameters lie by value in the device tables that cn_td3_pop_create built; cn_td3_pop_exploit rewrites them there, so
+ * the cn_td3_pop_update calls after it train with the new values and cost what they cost before.
+ * cn_td3_pop_pbt_bind(h, cfg, logs): allocates the device state (zero: calls, applied, generation, fitness, last; src = the member's
+ * own index; hyper[] = the members' cn_td3_config values) and keeps cfg.  logs: n_members episode logs whose tot_dev feed the
+ * fitness, or NULL (every cn_td3_pop_exploit then passes fitness_dev).  Binding again starts over.  Not enqueue-only.
+ * cn_td3_pop_exploit(h, fitness_dev, stream): at most TWO launches, enqueue-only, no host read and no copy, capturable on one stream
+ * like cn_td3_pop_update.  Statement, with P = n_members, n = n_replace, c = state.calls before the call:
+ *   fitness   fitness_dev != NULL: fitness_p = fitness_dev[p] and the call is applied.  NULL: with e_p = tot_p[0] - last_p[0] (new
+ *             episodes) and r_p = tot_p[2] - last_p[1] (their returns' sum), last_p[2] float64 owned by the handle: if any e_p <
+ *             min_episodes the call is SKIPPED -- calls = c + 1 and nothing else on the device changes; else fitness_p = (float)(r_p /
+ *             e_p), the quotient in float64, and after the call last_p = {tot_p[0], tot_p[2]} for every member.
+ *   rank      p stands before q when fitness_p > fitness_q (float comparison: -0.0 equals 0.0), or when q's is NaN and p's is not, or when
+ *             neither holds either way and p < q.  top[k] = the k-th member of that order, bottom[k] = the (P - 1 - k)-th, k = 0 .. n-1:
+ *             disjoint, since n <= P / 2.
+ *   source    K = mix64(seed ^ mix64(c));  bottom[k] copies from top[mix64(K ^ (k + 1)) % n]   (mix64: cn_td3_batch_dev's, above)
+ *   exploit   dst receives, BIT FOR BIT, src's 36 parameter tensors (the six networks, targets included), Adam's moments of the three
+ *             optimised networks, the bias corrections, step counters and running beta products of the tick (adam[4], steps[2],
+ *             pw[4]).  It keeps its own update counter, seed, replay ring, workspaces and loss slot.
+ *   explore   for k < CN_PBT_HYPERS: v = state.member[src].hyper[k]; if bit k of explore_mask is set, v = v * factor[mix64(K ^
+ *             mix64(0x100 + 8 dst + k)) >> 63] (float32); v = min(max(v, lo[k]), hi[k]); state.member[dst].hyper[k] = v, and v is
+ *             written wherever the update tables hold hyper-parameter k of member dst.
+ *   state     member[dst] = {src, generation + 1, fitness_dst, hyper as above}; a member that is not replaced: {its own index,
+ *             generation unchanged, fitness_p, hyper unchanged}, and nothing of it is written besides.  calls = c + 1, applied + 1.
+ * The second launch copies; no member is both read and written.  After an applied call a member that was replaced equals its source
+ * in everything an update reads except the counter, the seed, the ring and the hyper-parameters that were perturbed.
+ * Refused before any device work, text in cn_td3_last_error -- CN_ERR_ARG: a NULL handle or cfg; n_replace outside 1 ... n_members / 2
+ * (a population of one cannot bind); min_episodes < 1; a factor that is not finite and > 0; lo > hi or a bound that is not finite;
+ * explore_mask bits at or above CN_PBT_HYPERS; a log with a NULL rows, n_dev or tot_dev or a negative max_rows; cn_td3_pop_exploit before a
+ * bind, or with fitness_dev NULL when no logs were bound.  CN_ERR_CONFIG: a member whose hyper-parameter starts outside [lo, hi].
+ * cn_td3_pop_pbt_state_dev: the device state, read-only for the caller, valid until the next bind or the handle's end; NULL before
+ * a bind or for a NULL handle. */
+enum { CN_PBT_LR_ACTOR = 0, CN_PBT_LR_CRITIC, CN_PBT_GAMMA, CN_PBT_NOISE_STD, CN_PBT_NOISE_CLIP, CN_PBT_HYPERS };   /* 5 */
+typedef struct cn_td3_pbt_config {
+    int32_t  n_replace;      /* the n worst members copy from the n best; 1 ... n_members / 2 */
+    int32_t  min_episodes;   /* log-fed fitness: every member needs this many NEW episodes, else the call changes nothing; >= 1 */
+    uint32_t explore_mask;   /* bit k: hyper-parameter k of a replaced member is perturbed; the others are taken from its source unchanged */
+    int32_t  reserved;
+    float    factor[2];      /* e.g. 0.8, 1.2; both finite and > 0 */
+    float    lo[CN_PBT_HYPERS], hi[CN_PBT_HYPERS];   /* clamp after the perturbation; lo <= hi, finite */
+    uint64_t seed;           /* keys source choice and factor choice with the call counter */
+} cn_td3_pbt_config;
+typedef struct cn_td3_pbt_member {  /* device, read-only for the caller */
+    int32_t src;             /* last applied call: the member copied from, or its own index if it survived */
+    int32_t generation;      /* how many times this member has been replaced */
+    float   fitness;         /* as ranked in the last applied call */
+    float   hyper[CN_PBT_HYPERS];   /* what the update tables hold for this member NOW */
+} cn_td3_pbt_member;
+typedef struct cn_td3_pbt_state {   /* device */
+    uint64_t calls, applied;        /* every cn_td3_pop_exploit counts in calls; applied counts only those that were not skipped */
+    cn_td3_pbt_member member[64];
+} cn_td3_pbt_state;
+int cn_td3_pop_pbt_bind(cn_td3_pop_handle h, const cn_td3_pbt_config* cfg, const cn_episode_log* logs /* [n_members] or NULL */);
+int cn_td3_pop_exploit(cn_td3_pop_handle h, const float* fitness_dev /* [n_members], or NULL = from the bound logs */, void* stream);
+const cn_td3_pbt_state* cn_td3_pop_pbt_state_dev(cn_td3_pop_handle h);
+
 /* n_steps calls of cn_step (auto_reset = 2, the next-step reset convention) with OPEN-LOOP actions -- scripted or recorded
  * actions, action repeat, the uniform-random warm-up phase of an off-policy learner -- as ONE launch: a wavefront keeps its
  * environment for the whole launch and walks its steps at its own pace (no launch boundary and no device-wide join between
