@@ -45,7 +45,12 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_td3_pop_pbt_bind", "cn_td3_pop_exploit", "cn_td3_pop_pbt_state_dev",
            "cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", "cn_actor_pop_pack", "cn_actor_pop_forward",
            "cn_actor_pop_weights",
-           "cn_pop_record_create", "cn_pop_record_destroy", "cn_pop_record_members", "cn_pop_record_resetting", "cn_pop_record"]
+           "cn_pop_record_create", "cn_pop_record_destroy", "cn_pop_record_members", "cn_pop_record_resetting", "cn_pop_record",
+           "cn_eval_create", "cn_eval_destroy", "cn_eval_jobs", "cn_eval_reset", "cn_eval_record", "cn_eval_finish", "cn_eval_state_dev"]
+CN_EVAL_MAX = 64            # include/crowdnav.h: cn_eval_create's n_jobs and n_groups are 1 ... 64
+CN_EVAL_COLS = 12           # include/crowdnav.h: the columns of cn_eval_state.sums[j]
+CN_EVAL_SUCCESS_RATE, CN_EVAL_MEAN_RETURN = 0, 1      # include/crowdnav.h: cn_eval_finish's metric
+EVAL_METRIC = {"success": CN_EVAL_SUCCESS_RATE, "return": CN_EVAL_MEAN_RETURN}
 CN_TD3_POP_MAX = 64         # include/crowdnav.h: cn_td3_pop_create's n_members is 1 ... 64
 CN_ACTOR_POP_MAX = 64       # include/crowdnav.h: cn_actor_pop_create's n_members is 1 ... 64
 CN_POP_RECORD_MAX = 64      # include/crowdnav.h: cn_pop_record_create's n_members is 1 ... 64
@@ -278,6 +283,18 @@ class CnPopRecordMember(C.Structure):
                 ("n", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CnEvalJob(C.Structure):
+    """Mirror of `cn_eval_job` (include/crowdnav.h): one job of cn_eval_create."""
+    _fields_ = [("env", C.c_void_p), ("counters", C.c_void_p), ("last_return", C.c_void_p), ("done", C.c_void_p), ("log", CnEpisodeLog),
+                ("n", C.c_int32), ("quota", C.c_int32), ("group", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CnEvalState(C.Structure):
+    """Mirror of `cn_eval_state` (include/crowdnav.h)."""
+    _fields_ = [("remaining", C.c_int32 * CN_EVAL_MAX), ("sums", (C.c_double * CN_EVAL_COLS) * CN_EVAL_MAX),
+                ("summary", (C.c_float * 8) * CN_EVAL_MAX), ("fitness", C.c_float * CN_EVAL_MAX)]
+
+
 class CnSequenceIO(C.Structure):
     """Mirror of `cn_sequence_io` (include/crowdnav.h)."""
     _fields_ = [("action", C.c_void_p), ("obs", C.c_void_p), ("reward", C.c_void_p), ("done", C.c_void_p), ("topk_idx", C.c_void_p),
@@ -413,6 +430,13 @@ def lib():
         L.cn_pop_record_members.argtypes = [vp]
         L.cn_pop_record_resetting.argtypes = [vp, C.c_int]; L.cn_pop_record_resetting.restype = vp
         L.cn_pop_record.argtypes = [vp, C.c_float, vp]
+        L.cn_eval_create.argtypes = [C.POINTER(CnEvalJob), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]      # an array of jobs
+        L.cn_eval_destroy.argtypes = [vp]; L.cn_eval_destroy.restype = None
+        L.cn_eval_jobs.argtypes = [vp]
+        L.cn_eval_reset.argtypes = [vp, vp]
+        L.cn_eval_record.argtypes = [vp, C.c_float, vp]
+        L.cn_eval_finish.argtypes = [vp, C.c_int, vp, vp]
+        L.cn_eval_state_dev.argtypes = [vp]; L.cn_eval_state_dev.restype = vp
         L.cn_ddpg_create.argtypes = [C.POINTER(CnDdpgConfig), C.c_int, C.POINTER(vp)]
         L.cn_ddpg_destroy.argtypes = [vp]; L.cn_ddpg_destroy.restype = None
         L.cn_ddpg_update.argtypes = [vp, C.POINTER(CnTd3Batch), vp]

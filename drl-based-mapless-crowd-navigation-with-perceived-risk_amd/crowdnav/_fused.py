@@ -1,5 +1,5 @@
 """What the TD3, DDPG, DQN and SAC agents share on the way to libcrowdnav's fused learners (csrc/crowdnav_td3.hip, crowdnav_ddpg.hip, crowdnav_dqn.hip, crowdnav_sac.hip): the network
-pointers, views of the library's device memory, and the owners of a learner handle and of a population's handles."""
+pointers, views of the library's device memory, and the owners of a learner handle, of a population's handles and of an evaluator's."""
 import ctypes as C
 
 import torch
@@ -248,6 +248,65 @@ class FusedPopulationRecorder:
         try:
             if self.h:
                 self._L.cn_pop_record_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+class FusedEvaluator:
+    """Owns one cn_eval handle: the evaluation bookkeeping of J jobs as one launch per step (include/crowdnav.h, cn_eval_create).
+    jobs: the CnEvalJob of every job, in job order; keep: whatever their pointers point into (the handle holds them for its lifetime).
+    Errors raise CrowdNavError("<function>: <cn_last_error>")."""
+
+    def __init__(self, jobs, n_groups, device, dev_index, keep=None):
+        self._L = L = _abi.lib()
+        self.device, self.J, self.G, self._keep = device, len(jobs), int(n_groups), keep
+        self.jobs = (_abi.CnEvalJob * self.J)(*jobs)
+        self.h = C.c_void_p()
+        self._check("create", L.cn_eval_create(self.jobs, self.J, self.G, dev_index, C.byref(self.h)))
+        nbytes = C.sizeof(_abi.CnEvalState)
+        ptr = L.cn_eval_state_dev(self.h)
+
+        class _Arr:
+            __cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+        self._state = torch.as_tensor(_Arr(), device=device)
+        self._host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+        self.remaining_dev = _device_view(ptr + _abi.CnEvalState.remaining.offset, (_abi.CN_EVAL_MAX,), torch.int32, device)[:self.J]
+        self.summary_dev = _device_view(ptr + _abi.CnEvalState.summary.offset, (_abi.CN_EVAL_MAX, 8), torch.float32, device)[:self.J]
+        self.fitness_dev = _device_view(ptr + _abi.CnEvalState.fitness.offset, (_abi.CN_EVAL_MAX,), torch.float32, device)[:self.G]
+
+    def _check(self, what, rc):
+        if rc != 0:
+            raise _abi.CrowdNavError("cn_eval_%s: %s" % (what, self._L.cn_last_error().decode()))
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self):
+        """cn_eval_reset on torch's current stream: one launch; every job's counts, sums and log start over."""
+        self._check("reset", self._L.cn_eval_reset(self.h, self._stream()))
+
+    def record(self, launch):
+        """cn_eval_record on torch's current stream: one launch; `launch` is the index the counted episodes' rows carry."""
+        self._check("record", self._L.cn_eval_record(self.h, float(launch), self._stream()))
+
+    def finish(self, metric, fitness=None):
+        """cn_eval_finish on torch's current stream: one launch; metric CN_EVAL_SUCCESS_RATE | CN_EVAL_MEAN_RETURN; fitness: float32
+        [n_groups] on the device that also receives the groups' fitness, or None."""
+        if fitness is not None and not (fitness.dtype == torch.float32 and fitness.is_cuda and fitness.is_contiguous() and fitness.numel() == self.G):
+            raise ValueError("fitness must be a contiguous float32 tensor of %d values on %s" % (self.G, self.device))
+        self._fitness = fitness                    # alive until the next call: the launch is asynchronous
+        self._check("finish", self._L.cn_eval_finish(self.h, int(metric), None if fitness is None else C.c_void_p(fitness.data_ptr()), self._stream()))
+
+    def state(self):
+        """One device-to-host copy of cn_eval_state (it waits for the stream) -> a CnEvalState."""
+        self._host.copy_(self._state)
+        return _abi.CnEvalState.from_buffer_copy(self._host.numpy().tobytes())
+
+    def __del__(self):
+        try:
+            if self.h:
+                self._L.cn_eval_destroy(self.h)
                 self.h = None
         except Exception:
             pass

@@ -686,6 +686,20 @@ class VecEnvGroups:
         return tot
 
 
+class MemberEnvs(VecEnvGroups):
+    """The environments of a population, or of an evaluation's jobs: group p is member p's own environment handle -- its own seed, the
+    same env indices as a solo run's -- instead of a slice of one configuration, so cn_step_multi steps all members with one call and
+    member p sees the trajectory of VecEnv(cfgs[p]).  The configurations agree in n_envs and in the observation's width."""
+
+    def __init__(self, cfgs, device):
+        import dataclasses
+        self._cfgs = list(cfgs)
+        super().__init__(dataclasses.replace(self._cfgs[0], n_envs=self._cfgs[0].n_envs * len(self._cfgs)), groups=len(self._cfgs), device=device)
+
+    def _group_cfg(self, g):
+        return self._cfgs[g]
+
+
 class Env:
     """Drop-in for the reference's `Env` (ENV:42): same constructor, methods, return types."""
 

@@ -243,6 +243,124 @@ def evaluate(env, agent, episodes_per_env=1, max_launches=100000):
     return stats
 
 
+class DeviceEvaluator:
+    """evaluate() for J jobs at once with the bookkeeping on the device (include/crowdnav.h, cn_eval_create): a job is one greedy actor
+    in one world with its own environment handle, and one launch of the evaluation is three enqueues whatever J is -- ONE
+    cn_actor_pop_forward (the f32-MFMA actor training acts with, no noise), ONE cn_step_multi, ONE cn_eval_record -- with nothing read
+    back until the end.  Every environment contributes exactly its first `quota` episodes, evaluate()'s rule.
+    jobs: [(Config, ped_init | None, ped_preset_vel | None, agent, group)], at most 64, all with the same n_envs and observation width;
+    agent: a td3 / ddpg Agent on `device` (several jobs may name the same agent); group: whose fitness the job feeds (finish()).
+    The agents' noise counters (_fused_calls) are not touched: an evaluation leaves a training run's noise stream where it was."""
+
+    def __init__(self, jobs, device=0, n_groups=None):
+        from . import _abi
+        from ._fused import FusedPopulationActor, mlp_of
+        from .env import MemberEnvs
+        jobs = [tuple(j) for j in jobs]
+        if not 1 <= len(jobs) <= _abi.CN_EVAL_MAX:
+            raise ValueError("an evaluation takes 1 ... %d jobs, not %d" % (_abi.CN_EVAL_MAX, len(jobs)))
+        cfgs = [j[0] for j in jobs]
+        if any(c.n_envs != cfgs[0].n_envs or c.obs_dim != cfgs[0].obs_dim for c in cfgs):
+            raise ValueError("the jobs of an evaluation agree in n_envs and in the observation's width")
+        self.jobs, self.J, self.agents, self.groups = jobs, len(jobs), [j[3] for j in jobs], [int(j[4]) for j in jobs]
+        self.G = max(self.groups) + 1 if n_groups is None else int(n_groups)
+        self.envs = envs = MemberEnvs(cfgs, device)
+        self.device = envs.device
+        for e, (_, init, vel, _, _) in zip(envs.envs, jobs):
+            if init is not None:
+                e.set_ped_init(init)
+            if vel is not None:
+                e.set_ped_preset_vel(vel)
+        self.n, self.max_steps = envs.n, max(c.max_steps for c in cfgs)
+        self.step_seconds = [(c.dt_ms + c.scan_latency_ms) / 1000.0 for c in cfgs]
+        self.rows = [envs.rows(j) for j in range(self.J)]
+        self.act = torch.zeros((envs.N, 2), dtype=torch.float32, device=self.device)
+        self._step_all = envs.bind_step_all(self.act, auto_reset="next")
+        dev = self.agents[0]._dev_index
+        members = [_abi.CnActorPopMember(actor=mlp_of(a.actor), obs=envs.obs[r].data_ptr(), action=self.act[r].data_ptr(), n=self.n, reserved=0,
+                                         max_v=a.max_v, max_w=a.max_w, sigma=a.explore_sigma, reserved_f=0.0, seed=a._noise_seed)
+                   for a, r in zip(self.agents, self.rows)]
+        self._actors = FusedPopulationActor(members, envs.D, self.device, dev, keep=(envs.obs, self.act, self.agents))
+        self._actors.pack()
+        self._zeros = [0] * self.J
+        self._fitness = torch.zeros(self.G, dtype=torch.float32, device=self.device)
+        self._eval = self._quota = self.logs = None
+
+    def _bind(self, quota):
+        """The cn_eval handle for this quota (a job's quota is fixed at create) and the jobs' logs, with room for every counted episode."""
+        from . import _abi
+        from ._fused import FusedEvaluator
+        from .train import DeviceEpisodeLog
+        quota = int(quota)
+        if self._quota != quota:
+            self.logs = [DeviceEpisodeLog(self.device, self.n * quota) for _ in range(self.J)]
+            structs = [_abi.CnEvalJob(env=e.h.value, counters=None, last_return=None, done=self.envs.done[r].data_ptr(),
+                                      log=_abi.CnEpisodeLog(rows=lg.rows.data_ptr(), max_rows=lg.max_rows, n_dev=lg.n.data_ptr(), tot_dev=lg.tot.data_ptr()),
+                                      n=self.n, quota=quota, group=g, reserved=0)
+                       for e, r, lg, g in zip(self.envs.envs, self.rows, self.logs, self.groups)]
+            self._eval = FusedEvaluator(structs, self.G, self.device, self.agents[0]._dev_index, keep=(self.envs, self.logs))
+            self._quota = quota
+        return self._eval
+
+    def launch_bound(self, quota):
+        """Launches after which every environment has finished `quota` episodes: under the next-step reset convention an episode ends
+        within max_steps launches (the step counter is 1-based and a step at max_steps is a time-out) and its environment spends one
+        more launch on its reset, so episode q is over by launch q (max_steps + 1) - 1."""
+        return int(quota) * (self.max_steps + 1)
+
+    def repack(self):
+        """Re-pack the jobs' actors from their nn.Linear storages (one launch); call after the weights change."""
+        self._actors.pack()
+
+    @torch.no_grad()
+    def run(self, quota=1, poll=16, max_launches=None):
+        """Reset the environments and the counts, then launch until every environment of every job has finished `quota` episodes.
+        poll > 0: the host reads `remaining` once every `poll` launches and stops when all are 0; poll = 0: launch_bound(quota)
+        launches with no read at all.  Returns the launches enqueued."""
+        ev, envs = self._bind(quota), self.envs
+        envs.reset()
+        ev.reset()
+        bound = self.launch_bound(quota) if max_launches is None else min(self.launch_bound(quota), int(max_launches))
+        it = 0
+        while it < bound:
+            it += 1
+            self._actors.forward(self._zeros, add_noise=False)
+            envs.fork()                                                # the jobs' steps wait for the actions ...
+            self._step_all()
+            envs.join()                                                # ... and the record for the steps
+            ev.record(it)
+            if poll and it % poll == 0 and not bool(ev.remaining_dev.any()):
+                break
+        return it
+
+    def remaining(self):
+        """Environments of every job still below the quota, [J] on the host (one read)."""
+        return self._eval.remaining_dev.cpu()
+
+    def finish(self, metric="success"):
+        """cn_eval_finish: the jobs' summaries and the groups' fitness [n_groups] (float32, on the device, this evaluator's buffer: the
+        next finish() overwrites it), ready for Population.exploit.  metric: "success" | "return"."""
+        from . import _abi
+        self._eval.finish(_abi.EVAL_METRIC[metric] if isinstance(metric, str) else int(metric), self._fitness)
+        return self._fitness
+
+    def summary(self):
+        """The [J, 8] table of the last finish() -- episodes, success / failure / time-out rate, mean return, mean steps, mean ego and
+        social score -- on the host (one read)."""
+        return self._eval.summary_dev.cpu()
+
+    def stats(self, j):
+        """Job j's counted episodes as an EpisodeStats in evaluate()'s row order (one read)."""
+        from .train import DeviceEpisodeLog
+        lg, st = self.logs[j], EpisodeStats()
+        for row in lg.rows[:min(int(lg.n.item()), lg.max_rows)].cpu().tolist():
+            st.add_from_counters(row, row[2], step_seconds=self.step_seconds[j], cols=DeviceEpisodeLog.COLS)
+        return st
+
+    def close(self):
+        self.envs.close()
+
+
 class GraphedRollout:
     """Actor-in-the-loop stepping captured once into a HIP graph (torch.cuda.CUDAGraph): the actor's three
     GEMMs, the exploration noise, the clip and the fused env-step kernel replay as ONE graph launch per

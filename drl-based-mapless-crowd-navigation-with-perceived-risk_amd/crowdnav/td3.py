@@ -558,7 +558,10 @@ class Population:
     same per-agent noise counter, so the two may be mixed.
     Recording: bind_record(...) once, then record(launch) is ONE call of two launches for all members (cn_pop_record) in place of P x
     (DeviceReplay.add_masked, VecEnv.counters, VecEnv.returns, DeviceEpisodeLog.add) and the copies around them; rings and logs are,
-    bit for bit, what those leave."""
+    bit for bit, what those leave.
+    Evaluating: bind_eval(worlds, quota, metric) once, then evaluate() runs every member's greedy actor in every world -- three
+    enqueues per launch for all of them (crowdnav.rollout.DeviceEvaluator, cn_eval_record) -- and returns the fitness [P] on the
+    device, which exploit(fitness) takes; the members' noise counters do not move."""
 
     def __init__(self, agents, replay_sample=None):
         agents = list(agents)
@@ -758,6 +761,39 @@ class Population:
             a.opt_a.param_groups[0]["lr"] = a.actor_lr
             a.opt_q1.param_groups[0]["lr"] = a.opt_q2.param_groups[0]["lr"] = a.critic_lr
         return dict(calls=int(st.calls), applied=int(st.applied), members=members)
+
+    # ---- evaluation on the device: cn_eval_* (include/crowdnav.h) through crowdnav.rollout.DeviceEvaluator -------------------------
+    def bind_eval(self, specs, quota=1, metric="success"):
+        """Set up evaluate(): specs is a list of worlds (Config, ped_init | None, ped_preset_vel | None); job (p, s) is member p's
+        greedy actor in world s and feeds group p, so every member is measured in the same worlds with the same seeds.  At most 64
+        jobs.  quota: episodes counted per environment; metric: "success" | "return", what the fitness averages over a member's
+        worlds."""
+        from . import _abi
+        from .rollout import DeviceEvaluator
+        specs = [tuple(s) for s in specs]
+        if not specs:
+            raise ValueError("bind_eval takes at least one world")
+        if metric not in _abi.EVAL_METRIC:
+            raise ValueError("metric must be 'success' or 'return', not %r" % (metric,))
+        jobs = [(cfg, init, vel, a, p) for p, a in enumerate(self.agents) for (cfg, init, vel) in specs]
+        self._evaluator = DeviceEvaluator(jobs, self.agents[0]._dev_index, n_groups=len(self.agents))
+        self._eval_quota, self._eval_metric, self.eval_worlds = int(quota), metric, len(specs)
+        return self
+
+    def evaluate(self, poll=16):
+        """Every member's greedy actor in every bound world (three enqueues per launch for all of them: DeviceEvaluator.run) -> the
+        fitness [P] on the device, float32, ready for exploit(fitness).  The actors are re-packed from the current weights first; the
+        members' noise counters are not touched.  evaluator().summary() / .stats(p * worlds + s) hold the details."""
+        if getattr(self, "_evaluator", None) is None:
+            raise RuntimeError("Population.bind_eval(specs, quota, metric) first")
+        ev = self._evaluator
+        ev.repack()
+        ev.run(self._eval_quota, poll=poll)
+        return ev.finish(self._eval_metric)
+
+    def evaluator(self):
+        """The DeviceEvaluator bind_eval built: job p * eval_worlds + s is member p in world s."""
+        return getattr(self, "_evaluator", None)
 
     def set_replay_sample(self, replay_sample):
         self._fused.set_replay_sample(replay_sample)

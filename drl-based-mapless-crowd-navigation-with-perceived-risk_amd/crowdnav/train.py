@@ -2,6 +2,11 @@
 
     python -m crowdnav.train --scenario training_as_logged --waypoint-reward 0 --envs 16 --updates 16 --launches 25000 --csv --out runs/td3
     python -m crowdnav.train --evaluate --load runs/td3 --load-episode latest --scenario crossing_8
+    python -m crowdnav.train --evaluate --evaluate-on device --load runs/td3 --eval-scenarios crossing_8,towards_8,random_8
+
+`--evaluate-on device` (td3 / ddpg) runs the evaluation with its bookkeeping on the device (rollout.DeviceEvaluator: the f32-MFMA
+actor, cn_eval_record, no host read until the end), all worlds of --eval-scenarios in one run; `--population P --eval-every L`
+evaluates all members that way while they train (<out>/eval_log.csv) and `--pbt-fitness eval` ranks population-based training by it.
 
 Checkpoints are labelled with the episode count the weights really have behind them (N envs finish episodes in batches, so the
 count at a log interval is rarely a round number); every save also rewrites `latest_checkpoint.txt` with that count, and
@@ -59,8 +64,8 @@ import torch
 
 from . import presets
 from .config import Config
-from .env import VecEnv, VecEnvGroups
-from .rollout import EpisodeStats, evaluate
+from .env import MemberEnvs, VecEnv
+from .rollout import DeviceEvaluator, EpisodeStats, evaluate
 from . import ddpg, dqn, sac, tabular, td3
 
 TABULAR = dict(qlearn=tabular.QLearn, sarsa=tabular.Sarsa)
@@ -551,22 +556,11 @@ def train(a):
     return collect(a, env, SOLO[a.algo](a, env))
 
 
-class MemberEnvs(VecEnvGroups):
-    """The environments of a population: group p is member p's own environment handle -- its own seed, the same env indices as a solo
-    run's -- instead of a slice of one configuration, so cn_step_multi steps all members with one call and member p sees the
-    trajectory of VecEnv(cfgs[p])."""
-
-    def __init__(self, cfgs, device):
-        import dataclasses
-        self._cfgs = list(cfgs)
-        super().__init__(dataclasses.replace(self._cfgs[0], n_envs=self._cfgs[0].n_envs * len(self._cfgs)), groups=len(self._cfgs), device=device)
-
-    def _group_cfg(self, g):
-        return self._cfgs[g]
-
-
 PBT_CSV_COLUMNS = ("launch", "call", "member", "src", "generation", "fitness", "lr_actor", "lr_critic", "gamma", "noise_std", "noise_clip")
 PBT_HYPERS = PBT_CSV_COLUMNS[6:]
+EVAL_POPULATION_FLAGS = ("eval_every", "eval_envs", "eval_episodes", "eval_max_steps", "eval_seed", "eval_metric")      # refused without --population
+EVAL_SUMMARY_COLUMNS = ("episodes", "success_rate", "failure_rate", "timeout_rate", "mean_return", "mean_steps", "mean_ego", "mean_social")
+EVAL_CSV_COLUMNS = ("launch", "member", "world") + EVAL_SUMMARY_COLUMNS
 
 
 def _mix64(z):
@@ -604,7 +598,13 @@ def train_population(a):
     call, copy the best members' networks and optimizer state over the worst --pbt-fraction of them, and perturb the hyper-parameters
     of --pbt-explore by one of --pbt-factor -- then one read of the PBT state (the only host read PBT adds), whose rows go to
     <out>/pbt_log.csv.  --pbt-spread S > 0 starts member p with lr_actor, lr_critic and noise_std multiplied by a keyed log-uniform
-    factor in [1/S, S]: the sweep PBT then acts on."""
+    factor in [1/S, S]: the sweep PBT then acts on.
+    --eval-every L > 0: after the updates and the re-pack of every L-th launch, ONE evaluation of all members on the device
+    (Population.evaluate: every member's greedy actor in the --eval-scenarios worlds with --eval-seed, --eval-envs environments and
+    --eval-episodes episodes each; three enqueues per evaluation launch for all of them) and one read of its summaries, whose rows go
+    to <out>/eval_log.csv.  It has its own environment and actor handles and draws no noise, so the training run is, bit for bit, the
+    run without it.  --pbt-fitness eval: every exploit is preceded by such an evaluation and ranks by its fitness (--eval-metric)
+    instead of the training episodes' returns."""
     fill_defaults(a)
     dev = a.device
     P = a.population
@@ -664,6 +664,29 @@ def train_population(a):
         pbt_csv = open(os.path.join(a.out, "pbt_log.csv"), "a")
         if pbt_csv.tell() == 0:
             pbt_csv.write(",".join(PBT_CSV_COLUMNS) + "\n")
+    eval_fitness = bool(a.pbt_every) and a.pbt_fitness == "eval"
+    eval_csv, eval_runs, eval_seconds = None, 0, 0.0
+    if a.eval_every or eval_fitness:
+        # the same worlds with the same seed for every member: job (p, w) is member p's greedy actor in world w, on its own handle
+        pop.bind_eval([scenario_config(s, a.eval_envs, a.eval_max_steps, a.eval_seed, a.ped_vmax, **env_switches(a)) for s in a.eval_scenarios],
+                      quota=a.eval_episodes, metric=a.eval_metric)
+        os.makedirs(a.out, exist_ok=True)
+        eval_csv = open(os.path.join(a.out, "eval_log.csv"), "a")
+        if eval_csv.tell() == 0:
+            eval_csv.write(",".join(EVAL_CSV_COLUMNS) + "\n")
+
+    def evaluate_population(it):
+        """One evaluation of all members -> their fitness [P] on the device; the summaries' rows go to eval_log.csv (the one host read)."""
+        nonlocal eval_runs, eval_seconds
+        t = time.time()
+        fitness = pop.evaluate()
+        for j, row in enumerate(pop.evaluator().summary().tolist()):
+            eval_csv.write(",".join(["%d" % it, "%d" % (j // len(a.eval_scenarios)), a.eval_scenarios[j % len(a.eval_scenarios)]] +
+                                    ["%.9g" % v for v in row]) + "\n")
+        eval_csv.flush()
+        eval_runs, eval_seconds = eval_runs + 1, eval_seconds + time.time() - t
+        return fitness
+
     for it in range(1, a.launches + 1):
         if one_launch:
             pop.act(add_noise=True)
@@ -698,19 +721,23 @@ def train_population(a):
             else:
                 for ag in agents:
                     ag.sync_fused_weights()
-            if a.pbt_every and it % a.pbt_every == 0:
-                torch.add(pbt_flushed, torch.stack([e.tot for e in elogs]), out=pbt_tot)
-                pop.exploit()                                          # (re-packs the bound actors)
-                if not one_launch:
-                    for ag in agents:
-                        ag.sync_fused_weights()
-                st = pop.pbt_state()                                   # the one host read PBT adds: once per --pbt-every launches
-                if st["applied"] > pbt_applied:
-                    pbt_applied = st["applied"]
-                    for p, m in enumerate(st["members"]):
-                        pbt_csv.write(",".join(["%d" % it, "%d" % (st["calls"] - 1), "%d" % p, "%d" % m["src"], "%d" % m["generation"]] +
-                                               ["%.9g" % m[k] for k in PBT_CSV_COLUMNS[5:]]) + "\n")
-                    pbt_csv.flush()
+        exploiting = learning and a.pbt_every and it % a.pbt_every == 0
+        fitness = None
+        if (a.eval_every and it % a.eval_every == 0) or (exploiting and eval_fitness):
+            fitness = evaluate_population(it)                          # after the updates and the re-pack; its own handles and no noise draw
+        if exploiting:
+            torch.add(pbt_flushed, torch.stack([e.tot for e in elogs]), out=pbt_tot)
+            pop.exploit(fitness if eval_fitness else None)             # (re-packs the bound actors)
+            if not one_launch:
+                for ag in agents:
+                    ag.sync_fused_weights()
+            st = pop.pbt_state()                                       # the one host read PBT adds: once per --pbt-every launches
+            if st["applied"] > pbt_applied:
+                pbt_applied = st["applied"]
+                for p, m in enumerate(st["members"]):
+                    pbt_csv.write(",".join(["%d" % it, "%d" % (st["calls"] - 1), "%d" % p, "%d" % m["src"], "%d" % m["generation"]] +
+                                           ["%.9g" % m[k] for k in PBT_CSV_COLUMNS[5:]]) + "\n")
+                pbt_csv.flush()
         last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
         if it % a.log_every == 0 or last_launch:
             if a.pbt_every:
@@ -721,14 +748,56 @@ def train_population(a):
                 break
     if a.pbt_every:
         pbt_csv.close()
+    if eval_csv is not None:
+        eval_csv.close()
+        print("evaluation: %d runs of %d jobs, %.1f s of %.1f s (host clock, from the first enqueue to the summary's read)"
+              % (eval_runs, len(pop.evaluator().jobs), eval_seconds, time.time() - t0))
+        pop.evaluator().close()
     for run in runs:
         run.finish(updates_done)
     return agents, [run.episodes for run in runs]
 
 
+def report_evaluation(a, scenario, st):
+    """--evaluate's printed line and CSV for one world."""
+    n = len(st.rows)
+    print("%s: %d episodes, success %.3f, failure %.3f, mean return %.1f, mean steps %.1f, ego %.3f, social %.3f" % (
+        scenario, n, sum(r[1] for r in st.rows) / n, sum(r[2] for r in st.rows) / n, sum(r[3] for r in st.rows) / n, sum(r[4] for r in st.rows) / n,
+        sum(r[5] for r in st.rows if r[5] == r[5]) / max(1, sum(1 for r in st.rows if r[5] == r[5])),
+        sum(r[6] for r in st.rows if r[6] == r[6]) / max(1, sum(1 for r in st.rows if r[6] == r[6]))))
+    if a.out:
+        print("wrote", st.write_csv(a.out, "%s_training_test_%s" % (a.algo, scenario)))
+
+
+def run_evaluation_device(a):
+    """--evaluate --evaluate-on device: the loaded actor in every world of --eval-scenarios (default: --scenario) as ONE
+    DeviceEvaluator run, a job per world -> the worlds' EpisodeStats."""
+    specs = [scenario_config(s, a.envs, a.max_steps, a.seed, a.ped_vmax, **env_switches(a)) for s in a.eval_scenarios]
+    agent = make_agent(a, specs[0][0].obs_dim, "cuda:%d" % a.device, memory_size=16)
+    load_checkpoint(agent, a)
+    ev = DeviceEvaluator([(cfg, init, vel, agent, w) for w, (cfg, init, vel) in enumerate(specs)], a.device)
+    ev.run(a.episodes_per_env)
+    ev.finish("success")
+    table = ev.summary().tolist()
+    stats = [ev.stats(w) for w in range(len(specs))]
+    for s, st in zip(a.eval_scenarios, stats):
+        report_evaluation(a, s, st)
+    if a.out and a.eval_summary:
+        path = os.path.join(a.out, "eval_summary.csv")
+        with open(path, "w") as fp:
+            fp.write(",".join(("world",) + EVAL_SUMMARY_COLUMNS) + "\n")
+            for s, row in zip(a.eval_scenarios, table):
+                fp.write(",".join([s] + ["%.9g" % v for v in row]) + "\n")
+        print("wrote", path)
+    ev.close()
+    return stats[0] if len(stats) == 1 else stats
+
+
 def run_evaluation(a):
     fill_defaults(a)
     torch.cuda.set_device(a.device)
+    if a.evaluate_on == "device":
+        return run_evaluation_device(a)
     env = make_env(a.scenario, a.envs, a.max_steps, a.seed, a.device, a.ped_vmax, **env_switches(a))
     if a.algo == "dqn":           # greedy: Agent.act(add_noise=False) takes epsilon = 0
         agent = make_dqn_agent(a, env.D, "cuda:%d" % a.device, 16)
@@ -738,13 +807,7 @@ def run_evaluation(a):
         agent = make_agent(a, env.D, "cuda:%d" % a.device, memory_size=16)
         load_checkpoint(agent, a)
     st = evaluate(env, agent, episodes_per_env=a.episodes_per_env)
-    n = len(st.rows)
-    print("%s: %d episodes, success %.3f, failure %.3f, mean return %.1f, mean steps %.1f, ego %.3f, social %.3f" % (
-        a.scenario, n, sum(r[1] for r in st.rows) / n, sum(r[2] for r in st.rows) / n, sum(r[3] for r in st.rows) / n, sum(r[4] for r in st.rows) / n,
-        sum(r[5] for r in st.rows if r[5] == r[5]) / max(1, sum(1 for r in st.rows if r[5] == r[5])),
-        sum(r[6] for r in st.rows if r[6] == r[6]) / max(1, sum(1 for r in st.rows if r[6] == r[6]))))
-    if a.out:
-        print("wrote", st.write_csv(a.out, "%s_training_test_%s" % (a.algo, a.scenario)))
+    report_evaluation(a, a.scenario, st)
     return st
 
 
@@ -829,6 +892,25 @@ def build_parser():
                     "finished fewer than this many episodes since the last one that applied (default 10)")
     ap.add_argument("--pbt-spread", type=float, default=None, help="--population only: S > 0 = member p starts with lr_actor, lr_critic and "
                     "noise_std multiplied by a keyed log-uniform factor in [1/S, S] (default 0 = all members start alike)")
+    ap.add_argument("--pbt-fitness", default=None, choices=["log", "eval"], help="--pbt-every only: what an exploit ranks the members by.  log "
+                    "(default) = the mean return of the exploration-noise training episodes each finished since the last applied exploit; eval = "
+                    "every exploit is preceded by one evaluation on the device (greedy actors, identical worlds: the --eval-* flags) and is "
+                    "called with its fitness")
+    ap.add_argument("--evaluate-on", default=None, choices=["host", "device"], help="--evaluate with --algo td3 / ddpg: host (default) = "
+                    "rollout.evaluate, the PyTorch actor and one host read per launch; device = rollout.DeviceEvaluator, the f32-MFMA actor "
+                    "and cn_eval_record, three enqueues per launch and no read until the end (the same CSV file name and printed line)")
+    ap.add_argument("--eval-scenarios", default=None, help="comma-separated worlds.  With --evaluate --evaluate-on device: all of them in one run, "
+                    "one CSV per world and <out>/eval_summary.csv with one row per world (default: --scenario alone, no summary file).  With "
+                    "--population: the worlds every member is evaluated in (default crossing_8)")
+    ap.add_argument("--eval-every", type=int, default=None, help="--population only: L > 0 = after the updates of every L-th launch all members "
+                    "are evaluated once on the device; rows launch, member, world and the 8 summary columns go to <out>/eval_log.csv (one "
+                    "host read per evaluation).  Default 0 = off")
+    ap.add_argument("--eval-envs", type=int, default=None, help="--population only: environments per member and world of an evaluation (default 16)")
+    ap.add_argument("--eval-episodes", type=int, default=None, help="--population only: episodes counted per evaluation environment (default 1)")
+    ap.add_argument("--eval-max-steps", type=int, default=None, help="--population only: nsteps of the evaluation worlds (default: --max-steps)")
+    ap.add_argument("--eval-seed", type=int, default=None, help="--population only: the evaluation worlds' seed, one for all members (default: --seed)")
+    ap.add_argument("--eval-metric", default=None, choices=["success", "return"], help="--population only: what a member's fitness averages over "
+                    "its worlds: the success rate (default) or the mean return")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="default: runs/<algo>")
     ap.add_argument("--csv", action="store_true", help="one CSV row per finished episode in the reference's 8-column schema (recorded on the device, appended to the file at "
@@ -914,6 +996,33 @@ def parse_args(argv=None):
         if a.pbt_n_replace > a.population // 2:
             ap.error("--pbt-fraction %g of --population %d replaces %d members: at most half (%d) can be replaced, the others are the sources"
                      % (a.pbt_fraction, a.population, a.pbt_n_replace, a.population // 2))
+    if a.pbt_fitness is not None and not a.pbt_every:
+        ap.error("--pbt-fitness selects what an exploit ranks by: it needs --pbt-every")
+    if a.pbt_fitness is None:
+        a.pbt_fitness = "log"
+    if a.evaluate_on is not None and not (a.evaluate and a.algo in ("td3", "ddpg")):
+        ap.error("--evaluate-on selects how --evaluate runs a td3 / ddpg actor: it needs --evaluate with --algo td3 or ddpg")
+    if a.evaluate_on is None:
+        a.evaluate_on = "host"
+    eval_given = [k for k in EVAL_POPULATION_FLAGS if getattr(a, k) is not None]
+    if eval_given and not a.population:
+        ap.error("%s: the evaluation of a population during its training: it needs --population" % ", ".join("--" + k.replace("_", "-") for k in eval_given))
+    if a.eval_scenarios is not None and not (a.population or a.evaluate_on == "device"):
+        ap.error("--eval-scenarios names the worlds of an evaluation on the device: it needs --population or --evaluate --evaluate-on device")
+    a.eval_summary = a.eval_scenarios is not None and a.evaluate_on == "device"      # (eval_summary.csv: only when the worlds were listed)
+    if a.eval_scenarios is None:
+        a.eval_scenarios = a.scenario if a.evaluate_on == "device" else "crossing_8"
+    a.eval_scenarios = tuple(s for s in a.eval_scenarios.split(",") if s)
+    for k, v in (("eval_every", 0), ("eval_envs", 16), ("eval_episodes", 1), ("eval_max_steps", a.max_steps), ("eval_seed", a.seed), ("eval_metric", "success")):
+        if getattr(a, k) is None:
+            setattr(a, k, v)
+    if a.eval_every < 0 or a.eval_envs < 1 or a.eval_episodes < 1 or a.eval_max_steps < 1:
+        ap.error("--eval-every must be >= 0 and --eval-envs, --eval-episodes and --eval-max-steps >= 1")
+    if not a.eval_scenarios or len(set(a.eval_scenarios)) != len(a.eval_scenarios):
+        ap.error("--eval-scenarios: at least one world, each named once")
+    if max(1, a.population) * len(a.eval_scenarios) > 64:
+        ap.error("--eval-scenarios: %d worlds for %d actor(s) are %d jobs: one evaluation takes at most 64"
+                 % (len(a.eval_scenarios), max(1, a.population), max(1, a.population) * len(a.eval_scenarios)))
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     if a.ou_act is not None and not a.ou_noise:

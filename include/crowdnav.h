@@ -789,6 +789,72 @@ int cn_pop_record_members(cn_pop_record_handle h);
 uint8_t* cn_pop_record_resetting(cn_pop_record_handle h, int member);        /* dev [n_member] bytes, owned by the handle */
 int cn_pop_record(cn_pop_record_handle h, float launch, void* stream);        /* at most TWO launches */
 
+/* Evaluation on the device: J jobs at once, a job being one greedy actor in one world with its own environment handle.  One step of an
+ * evaluation is three enqueues whatever J is -- cn_actor_pop_forward, cn_step_multi, cn_eval_record -- and nothing is read back until
+ * the end: every environment contributes exactly its FIRST `quota` episodes (short episodes would otherwise be over-represented), the
+ * handle counts them per environment, and cn_eval_finish turns the sums into per-job summaries and a per-group fitness that
+ * cn_td3_pop_exploit takes as it stands.  Job j rides in the grid's z dimension; its row of a device table is built and uploaded once by
+ * cn_eval_create.  Per job: done [n] bytes, its episode log, where the counters and the last return come from (env, or env == NULL and
+ * explicit counters [n][CN_COUNTER_COLS] and last_return [n], as cn_pop_record_member), the quota, and the group whose fitness it feeds.
+ * The handle owns, per job, finished [n] int32 (episodes counted per environment) and the byte scratch counted [n], and one
+ * cn_eval_state (cn_eval_state_dev: device, read-only for the caller, alive as long as the handle).  At create the state is what
+ * cn_eval_reset leaves and summary / fitness are zero.
+ * Statement, for every job j, whatever n_jobs and j are:
+ * cn_eval_reset(h, stream), ONE launch: finished_j = 0, sums[j] = 0, remaining[j] = n_j, *log_j.n_dev = 0, log_j.tot_dev[0..4] = 0;
+ *     summary and fitness are not touched.
+ * cn_eval_record(h, launch, stream), ONE launch, grid (1, 1, J) x 1024:
+ *   - counted[i] = done_j[i] != 0 && finished_j[i] < quota_j, evaluated for all i < n_j before anything is written;
+ *   - log_j (rows below max_rows, *n_dev, tot_dev[5]) is BIT FOR BIT what cn_episode_log_add(&log_j, counted, counters, 14, last_return,
+ *     counted, launch, n_j, ...) leaves, counters / last_return being what cn_get_counters / cn_get_returns of env_j return at that
+ *     point, or the explicit arrays (the kernel instantiates cn_episode_log_add's code on the counted bytes);
+ *   - sums[j][k] += the float64 sum over the counted rows, in cn_episode_log_add's order (thread t of 1024 adds its rows i = t mod 1024
+ *     in ascending order, the 64 lanes of a wavefront combine by the xor butterfly 32, 16, ..., 1, the 16 wave totals are added in
+ *     order), of -- with success, failure, ret, steps, ego, social, obst the log row's columns 0 ... 6 --
+ *       k = 0: 1 (episodes)        1: success              2: failure          3: 1 where success == 0 and failure == 0 (time-outs)
+ *           4: ret                 5: steps                6: 1.0 - (double)ego / (double)obst where obst > 0, else nothing
+ *           7: 1.0 - (double)social / (double)obst where obst > 0   8: 1 where obst > 0     9: steps where success != 0
+ *       k = 10, 11: nothing (they stay 0).  A row that is not counted adds 0.0.
+ *   - then finished_j[i] += counted[i] and remaining[j] = #{i < n_j : finished_j[i] < quota_j};
+ *   - a job whose remaining[j] was 0 before the call, or with n_j == 0, changes nothing at all; rows at and beyond n_j of any buffer are
+ *     not touched.  If every n_j is 0, no launch is made.
+ * cn_eval_finish(h, metric, fitness_dev, stream), ONE launch of a single workgroup: with s = sums[j], summary[j] = {s0, s1 / s0,
+ *     s2 / s0, s3 / s0, s4 / s0, s5 / s0, s6 / s8, s7 / s8} = {episodes, success rate, failure rate, time-out rate, mean return, mean
+ *     steps, mean ego score, mean social score}: the quotients in float64, then cast to float; 0 / 0 gives NaN.  fitness[g], g <
+ *     n_groups, = (float) of the float64 mean, over the jobs with group == g in job order, of summary[j][1] (CN_EVAL_SUCCESS_RATE) or
+ *     summary[j][4] (CN_EVAL_MEAN_RETURN); a group without jobs gives NaN (cn_td3_pop_exploit ranks NaN last).  The same n_groups values
+ *     go to fitness_dev when it is not NULL.  fitness at and beyond n_groups is not touched.
+ * All three are enqueue-only: no host read, no copy, `launch` by value; capturable on one stream.  No atomics: every job's outputs
+ * belong to its own workgroup.
+ * Refused before any device work, text in cn_last_error naming the field and the job.  CN_ERR_ARG: a NULL handle / jobs / out; n_jobs or
+ * n_groups outside 1 ... CN_EVAL_MAX; group outside 0 ... n_groups - 1; n < 0; quota < 1; a NULL done with n > 0; neither env nor both
+ * explicit arrays with n > 0; n different from the env's n_envs; an incomplete log; log.max_rows < 0; an unknown metric.
+ * CN_ERR_CONFIG: two jobs naming the same log rows, n_dev or tot_dev (they would race inside a launch). */
+#define CN_EVAL_MAX 64
+#define CN_EVAL_COLS 12
+enum { CN_EVAL_SUCCESS_RATE = 0, CN_EVAL_MEAN_RETURN = 1 };
+typedef struct cn_eval_job {
+    cn_handle env;               /* or NULL: then counters [n][CN_COUNTER_COLS] and last_return [n], as cn_pop_record_member */
+    const int32_t* counters; const float* last_return;
+    const uint8_t* done;         /* dev [n] */
+    cn_episode_log log;          /* the job's counted episodes */
+    int32_t n, quota;            /* n >= 0, quota >= 1 */
+    int32_t group, reserved;     /* 0 ... n_groups-1: whose fitness this job feeds */
+} cn_eval_job;
+typedef struct cn_eval_state {   /* device, read-only for the caller */
+    int32_t remaining[CN_EVAL_MAX];            /* envs of job j still below quota */
+    double  sums[CN_EVAL_MAX][CN_EVAL_COLS];
+    float   summary[CN_EVAL_MAX][8];           /* by cn_eval_finish */
+    float   fitness[CN_EVAL_MAX];              /* by group, by cn_eval_finish */
+} cn_eval_state;
+typedef struct cn_eval_s* cn_eval_handle;
+int  cn_eval_create(const cn_eval_job* jobs, int n_jobs, int n_groups, int device, cn_eval_handle* out);
+void cn_eval_destroy(cn_eval_handle h);
+int  cn_eval_jobs(cn_eval_handle h);
+int  cn_eval_reset(cn_eval_handle h, void* stream);                       /* ONE launch */
+int  cn_eval_record(cn_eval_handle h, float launch, void* stream);        /* ONE launch, grid (1,1,J) x 1024 */
+int  cn_eval_finish(cn_eval_handle h, int metric, float* fitness_dev /* [n_groups] or NULL */, void* stream);  /* ONE launch */
+const cn_eval_state* cn_eval_state_dev(cn_eval_handle h);
+
 /* Population-based training on a cn_td3_pop handle: every so often the n_replace worst members take over the networks and the
  * optimizer state of members among the n_replace best (exploit) and perturb the hyper-parameters they inherit (explore).  The
  * hyper-parameters lie by value in the device tables that cn_td3_pop_create built; cn_td3_pop_exploit rewrites them there, so
