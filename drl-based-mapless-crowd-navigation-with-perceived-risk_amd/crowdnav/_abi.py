@@ -43,6 +43,8 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_td3_pop_create", "cn_td3_pop_destroy", "cn_td3_pop_update", "cn_td3_pop_members", "cn_td3_pop_loss_dev",
            "cn_td3_pop_batch_dev", "cn_td3_pop_set_replay_sample",
            "cn_td3_pop_pbt_bind", "cn_td3_pop_exploit", "cn_td3_pop_pbt_state_dev",
+           "cn_td3_state_size", "cn_td3_state_save", "cn_td3_state_load", "cn_td3_state_segment_dev",
+           "cn_td3_pop_state_size", "cn_td3_pop_state_save", "cn_td3_pop_state_load", "cn_td3_pop_state_segment_dev",
            "cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", "cn_actor_pop_pack", "cn_actor_pop_forward",
            "cn_actor_pop_weights",
            "cn_pop_record_create", "cn_pop_record_destroy", "cn_pop_record_members", "cn_pop_record_resetting", "cn_pop_record",
@@ -56,6 +58,8 @@ CN_ACTOR_POP_MAX = 64       # include/crowdnav.h: cn_actor_pop_create's n_member
 CN_POP_RECORD_MAX = 64      # include/crowdnav.h: cn_pop_record_create's n_members is 1 ... 64
 CN_PBT_HYPER_NAMES = ("lr_actor", "lr_critic", "gamma", "noise_std", "noise_clip")      # include/crowdnav.h: CN_PBT_LR_ACTOR ... in order
 CN_PBT_HYPERS = len(CN_PBT_HYPER_NAMES)
+CN_STATE_MAGIC, CN_STATE_VERSION, CN_STATE_FAMILY_TD3 = 0x0045544154534E43, 1, 1      # include/crowdnav.h: cn_state_header
+CN_STATE_KIND_NAMES = ("param", "moment", "adam", "steps", "pw", "counter", "loss", "hyper", "pbt", "pbt_last")      # CN_STATE_PARAM ... in order
 CN_SAMPLE_WITH_REPLACEMENT, CN_SAMPLE_DISTINCT = 0, 1      # include/crowdnav.h: cn_*_set_replay_sample
 REPLAY_SAMPLE = {"with": CN_SAMPLE_WITH_REPLACEMENT, "without": CN_SAMPLE_DISTINCT}
 
@@ -271,6 +275,18 @@ class CnTd3PbtMember(C.Structure):
     _fields_ = [("src", C.c_int32), ("generation", C.c_int32), ("fitness", C.c_float), ("hyper", C.c_float * CN_PBT_HYPERS)]
 
 
+class CnStateHeader(C.Structure):
+    """Mirror of `cn_state_header` (include/crowdnav.h)."""
+    _fields_ = [("magic", C.c_uint64), ("version", C.c_int32), ("family", C.c_int32), ("n_members", C.c_int32), ("obs_dim", C.c_int32),
+                ("hidden", C.c_int32), ("batch", C.c_int32), ("pbt_bound", C.c_int32), ("n_segments", C.c_int32), ("total_bytes", C.c_uint64)]
+
+
+class CnStateSegment(C.Structure):
+    """Mirror of `cn_state_segment` (include/crowdnav.h)."""
+    _fields_ = [("member", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("reserved", C.c_int32), ("offset", C.c_uint64),
+                ("bytes", C.c_uint64)]
+
+
 class CnTd3PbtState(C.Structure):
     """Mirror of `cn_td3_pbt_state` (include/crowdnav.h)."""
     _fields_ = [("calls", C.c_uint64), ("applied", C.c_uint64), ("member", CnTd3PbtMember * CN_TD3_POP_MAX)]
@@ -419,6 +435,11 @@ def lib():
         L.cn_td3_pop_pbt_bind.argtypes = [vp, C.POINTER(CnTd3PbtConfig), C.POINTER(CnEpisodeLog)]      # logs: an array of n_members, or None
         L.cn_td3_pop_exploit.argtypes = [vp, vp, vp]
         L.cn_td3_pop_pbt_state_dev.argtypes = [vp]; L.cn_td3_pop_pbt_state_dev.restype = vp
+        for pre in ("cn_td3_state_", "cn_td3_pop_state_"):
+            getattr(L, pre + "size").argtypes = [vp]; getattr(L, pre + "size").restype = C.c_size_t
+            getattr(L, pre + "save").argtypes = [vp, vp, C.c_size_t, vp]
+            getattr(L, pre + "load").argtypes = [vp, vp, C.c_size_t, vp]
+            getattr(L, pre + "segment_dev").argtypes = [vp, C.c_int, C.POINTER(CnStateSegment)]; getattr(L, pre + "segment_dev").restype = vp
         L.cn_actor_pop_create.argtypes = [C.POINTER(CnActorPopMember), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]      # an array of members
         L.cn_actor_pop_destroy.argtypes = [vp]; L.cn_actor_pop_destroy.restype = None
         L.cn_actor_pop_members.argtypes = [vp]

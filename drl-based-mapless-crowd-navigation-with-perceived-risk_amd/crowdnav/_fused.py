@@ -26,7 +26,54 @@ def _device_view(ptr, shape, dtype, device):
     return torch.as_tensor(_Arr(), device=device).reshape(tuple(shape))
 
 
-class FusedLearner:
+class _StateBlob:
+    """cn_<...>_state_size / _save / _load of a handle (include/crowdnav.h): the learner's whole state as one blob, out and in by one
+    launch each.  The host class gives `_state_fn(what)` (the library function), `h`, `device`, `_check`."""
+
+    def state_size(self):
+        """Bytes of this handle's state blob; the first call builds the launch's job table (it synchronises)."""
+        n = int(self._state_fn("size")(self.h))
+        if n == 0:
+            self._check("state_size", -1)
+        return n
+
+    def _state_buffers(self):
+        n = self.state_size()
+        if getattr(self, "_state_dev", None) is None or self._state_dev.numel() != n:
+            self._state_dev = torch.empty(n, dtype=torch.uint8, device=self.device)
+            self._state_host = torch.empty(n, dtype=torch.uint8).pin_memory()
+        return self._state_dev, self._state_host
+
+    def save_state(self, wait=True):
+        """One launch into the handle's device buffer, then one asynchronous copy to its pinned host buffer, both on torch's current
+        stream: a consistent picture at this point of the stream.  Returns the pinned uint8 tensor, which the next save_state
+        overwrites; wait=False leaves the waiting (for the stream) to the caller."""
+        dev, host = self._state_buffers()
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._check("state_save", self._state_fn("save")(self.h, C.c_void_p(dev.data_ptr()), dev.numel(), st))
+        host.copy_(dev, non_blocking=True)
+        if wait:
+            torch.cuda.current_stream(self.device).synchronize()
+        return host
+
+    def load_state(self, blob):
+        """The state of a save_state blob (uint8 tensor or array-like of state_size() bytes) into this handle: one small synchronous
+        read of header and directory, then one launch on torch's current stream.  A blob of another shape is refused and nothing
+        is written."""
+        dev, _ = self._state_buffers()
+        b = torch.as_tensor(blob).reshape(-1)
+        if b.dtype != torch.uint8:
+            raise ValueError("a state blob is uint8")
+        if b.numel() == dev.numel():
+            dev.copy_(b)
+            src, n = dev, dev.numel()
+        else:                                      # the library words the refusal
+            src, n = b.to(self.device).contiguous(), b.numel()
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._check("state_load", self._state_fn("load")(self.h, C.c_void_p(src.data_ptr()), n, st))
+
+
+class FusedLearner(_StateBlob):
     """Owns one learner handle of libcrowdnav: family = "td3", "ddpg" or "dqn" names cn_<family>_create / _update / _destroy /
     _loss_dev / _batch_dev.  An error raises CrowdNavError("<function>: <cn_td3_last_error>")."""
 
@@ -44,6 +91,11 @@ class FusedLearner:
 
     def _fn(self, what):
         return getattr(self._L, "cn_%s_%s" % (self.family, what))
+
+    def _state_fn(self, what):
+        if self.family != "td3":
+            raise _abi.CrowdNavError("cn_%s_state_%s: only the TD3 learners' state can be saved and loaded" % (self.family, what))
+        return self._fn("state_" + what)
 
     def _check(self, what, rc):
         if rc != 0:
@@ -80,7 +132,7 @@ class FusedLearner:
             pass
 
 
-class FusedPopulation:
+class FusedPopulation(_StateBlob):
     """Owns one cn_td3_pop handle: P TD3 learners updated by the launches of one (include/crowdnav.h, cn_td3_pop_create).  cfgs: the
     members' CnTd3Config, in member order.  The sibling of FusedLearner for the population calls; errors raise the same way."""
 
@@ -99,6 +151,9 @@ class FusedPopulation:
     def _check(self, what, rc):
         if rc != 0:
             raise _abi.CrowdNavError("cn_td3_pop_%s: %s" % (what, self._L.cn_td3_last_error().decode()))
+
+    def _state_fn(self, what):
+        return getattr(self._L, "cn_td3_pop_state_" + what)
 
     def update(self, do_actor):
         """cn_td3_pop_update on torch's current stream: enqueue-only.  Returns the P losses as a fresh tensor (one small

@@ -547,6 +547,54 @@ class Agent(FusedActorMixin):
         torch.save(self.q1_t.state_dict(), os.path.join(outdir, "td3_critic1_model_ep%d.pt" % ep))
         torch.save(self.q2_t.state_dict(), os.path.join(outdir, "td3_critic2_model_ep%d.pt" % ep))
 
+    # ---- the whole training state, for a bit-for-bit resume (cn_td3_state_save / _load, include/crowdnav.h) ---------------------------
+    def _side_state(self):
+        """What the library does not own: the replay ring's live rows, position, fill level and host bounds, and the noise position."""
+        import numpy as np
+        m = self.memory
+        n = int(m.size_dev.item())
+        out = {"replay_" + k: getattr(m, k)[:n].cpu().numpy() for k in ("s", "a", "r", "s2", "d")}
+        out.update(replay_pos=np.int64(m.pos_dev.item()), replay_size=np.int64(n), replay_sample_calls=np.int64(m.sample_calls),
+                   replay_bounds=np.array([m._lb, m._ub], dtype=np.int64), replay_cap=np.int64(m.cap),
+                   noise_state=np.array(self.noise_state(), dtype=np.uint64))
+        return out
+
+    def _load_side_state(self, z):
+        m = self.memory
+        n = int(z["replay_size"])
+        if int(z["replay_cap"]) != m.cap or z["replay_s"].shape != (n, m.obs_dim):
+            raise ValueError("the saved replay ring is %d x %d of capacity %d; this agent's is %d wide of capacity %d"
+                             % (z["replay_s"].shape + (int(z["replay_cap"]), m.obs_dim, m.cap)))
+        for k in ("s", "a", "r", "s2", "d"):
+            getattr(m, k)[:n].copy_(torch.from_numpy(z["replay_" + k]))
+        m.pos_dev.fill_(int(z["replay_pos"])); m.size_dev.fill_(n)
+        m.sample_calls = int(z["replay_sample_calls"])
+        m._lb, m._ub = (int(x) for x in z["replay_bounds"])
+        self.set_noise_state(*(int(x) for x in z["noise_state"]))
+
+    def save_state(self, path):
+        """Everything a fused run continues from, as one .npz at `path`: the learner's blob (networks, Adam's moments, step counters,
+        bias-correction products, update counter, loss: one launch), the replay ring's live rows [0, size) with its position, fill
+        level, sample counter and host bounds, and the fused actor's noise position.  Needs enable_fused_update()."""
+        import numpy as np
+        if not getattr(self, "_fused", None):
+            raise RuntimeError("Agent.save_state saves the fused learner's state: enable_fused_update() first")
+        blob = self._fused.save_state().numpy().copy()
+        with open(path, "wb") as f:
+            np.savez(f, blob=blob, **self._side_state())
+
+    def load_state(self, path):
+        """Continue, bit for bit, where save_state(path) stood: the same Agent arguments and enable_fused_update() first.  The packed
+        actor is re-packed when it exists."""
+        import numpy as np
+        if not getattr(self, "_fused", None):
+            raise RuntimeError("Agent.load_state loads the fused learner's state: enable_fused_update() first")
+        with np.load(path) as z:
+            self._fused.load_state(z["blob"])
+            self._load_side_state(z)
+        if hasattr(self, "_fw_struct"):
+            self.sync_fused_weights()
+
 
 class Population:
     """P TD3 agents on one device whose updates run as ONE chain of 7 (+ 5) launches (cn_td3_pop_update): member p's update is, bit
@@ -761,6 +809,37 @@ class Population:
             a.opt_a.param_groups[0]["lr"] = a.actor_lr
             a.opt_q1.param_groups[0]["lr"] = a.opt_q2.param_groups[0]["lr"] = a.critic_lr
         return dict(calls=int(st.calls), applied=int(st.applied), members=members)
+
+    # ---- the whole training state, for a bit-for-bit resume (cn_td3_pop_state_save / _load, include/crowdnav.h) ---------------------
+    def save_state(self, outdir):
+        """Everything the population continues from, into the directory `outdir`: learner.npz (the blob of all members -- networks,
+        Adam's state, counters, losses, the hyper-parameters as the device tables hold them, and the PBT state when bind_pbt was
+        called: one launch) and member<p>.npz (member p's replay ring and noise position, as Agent.save_state)."""
+        import os
+        import numpy as np
+        os.makedirs(outdir, exist_ok=True)
+        blob = self._fused.save_state().numpy().copy()
+        with open(os.path.join(outdir, "learner.npz"), "wb") as f:
+            np.savez(f, blob=blob)
+        for p, a in enumerate(self.agents):
+            with open(os.path.join(outdir, "member%d.npz" % p), "wb") as f:
+                np.savez(f, **a._side_state())
+
+    def load_state(self, outdir):
+        """Continue, bit for bit, where save_state(outdir) stood: a population built from the same agents' arguments, with bind_pbt
+        called (or not) as it was.  Re-packs the bound actors; with PBT bound, the agents' Python-side hyper-parameters follow the
+        loaded ones (pbt_state())."""
+        import os
+        import numpy as np
+        with np.load(os.path.join(outdir, "learner.npz")) as z:
+            self._fused.load_state(z["blob"])
+        for p, a in enumerate(self.agents):
+            with np.load(os.path.join(outdir, "member%d.npz" % p)) as z:
+                a._load_side_state(z)
+        if self._actors is not None:
+            self.sync_actors()
+        if getattr(self._fused, "_pbt_state", None) is not None:
+            self.pbt_state()
 
     # ---- evaluation on the device: cn_eval_* (include/crowdnav.h) through crowdnav.rollout.DeviceEvaluator -------------------------
     def bind_eval(self, specs, quota=1, metric="success"):

@@ -8,6 +8,15 @@
 actor, cn_eval_record, no host read until the end), all worlds of --eval-scenarios in one run; `--population P --eval-every L`
 evaluates all members that way while they train (<out>/eval_log.csv) and `--pbt-fitness eval` ranks population-based training by it.
 
+`--state-every L` (--algo td3 --learner fused, solo or --population) writes the run's WHOLE state at the end of every L-th launch --
+the learner's blob (cn_td3_state_save / cn_td3_pop_state_save: networks, Adam's moments and counters, the update counter, a
+population's hyper-parameters and PBT state, one launch), the replays, the environments, the loop's tensors, logs and counts -- into
+<out>/state/launch<it>/, and `--resume DIR` with the same command line continues that run at the next launch, bit for bit: the CSVs,
+the checkpoints and pbt_log.csv are those of the run that was never stopped.
+
+    python -m crowdnav.train --learner fused --population 8 --envs 64 --pbt-every 500 --csv --state-every 1000 --out runs/pop
+    python -m crowdnav.train --learner fused --population 8 --envs 64 --pbt-every 500 --csv --state-every 1000 --resume runs/pop
+
 Checkpoints are labelled with the episode count the weights really have behind them (N envs finish episodes in batches, so the
 count at a log interval is rarely a round number); every save also rewrites `latest_checkpoint.txt` with that count, and
 `--load-episode latest` (the default) reads it -- resume / evaluate commands can be written before the run exists.
@@ -60,6 +69,7 @@ import argparse
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import presets
@@ -176,6 +186,93 @@ def write_latest(outdir, episodes):
     os.replace(tmp, os.path.join(outdir, "latest_checkpoint.txt"))
 
 
+# ---- --state-every / --resume: the whole state of a fused TD3 run or population, for a bit-for-bit continuation -------------------
+# <out>/state/launch<it>/ holds what the run at the end of launch `it` consists of: the learner's blob and the replays (Agent.save_state
+# -> agent.npz; Population.save_state -> learner.npz, member<p>.npz), every environment handle's snapshot (env<g>.npy) and loop.npz:
+# the loop's device tensors, every episode log's unflushed rows, n, totals and flushed count, PBT's running totals, the host scalars
+# and the byte sizes of the files the run appends to.  A directory is written under another name and renamed when complete;
+# <out>/state/latest then names it (replaced atomically, as write_latest), and only then are older directories pruned.
+STATE_DIR = "state"
+
+
+def resolve_resume(run_dir):
+    """--resume DIR -> the state directory DIR/state/latest names."""
+    pointer = os.path.join(run_dir, STATE_DIR, "latest")
+    if not os.path.exists(pointer):
+        raise FileNotFoundError("--resume %s: %s does not exist (no --state-every run wrote a complete state there)" % (run_dir, pointer))
+    path = os.path.join(run_dir, STATE_DIR, open(pointer).read().split()[0])
+    if not os.path.isdir(path):
+        raise FileNotFoundError("--resume %s: the latest pointer names %s, which does not exist" % (run_dir, path))
+    return path
+
+
+def elog_state(e, key):
+    n = min(int(e.n.item()), e.max_rows)
+    return {key + "_n": np.int64(e.n.item()), key + "_flushed": np.int64(e._flushed), key + "_tot": e.tot.cpu().numpy(),
+            key + "_rows": e.rows[e._flushed:n].cpu().numpy()}
+
+
+def set_elog_state(e, z, key):
+    rows = torch.from_numpy(z[key + "_rows"])
+    e._flushed = int(z[key + "_flushed"])
+    e.n.fill_(int(z[key + "_n"]))
+    e.tot.copy_(torch.from_numpy(z[key + "_tot"]))
+    e.rows[e._flushed:e._flushed + rows.shape[0]].copy_(rows)
+
+
+def write_state(a, it, save_learner, env_handles, tensors, runs, scalars, files):
+    """One complete <out>/state/launch<it>/, then the `latest` pointer, then the pruning (--state-keep).  save_learner(dir) writes the
+    learner's files; tensors: name -> device tensor; scalars: name -> host number; files: the files this run appends to."""
+    import re
+    import shutil
+    root = os.path.join(a.out, STATE_DIR)
+    final = os.path.join(root, "launch%d" % it)
+    tmp = final + ".tmp%d" % os.getpid()
+    shutil.rmtree(tmp, ignore_errors=True)
+    os.makedirs(tmp)
+    torch.cuda.synchronize()
+    save_learner(tmp)
+    for g, e in enumerate(env_handles):
+        np.save(os.path.join(tmp, "env%d.npy" % g), e.snapshot())
+    loop = {"t_" + k: t.cpu().numpy() for k, t in tensors.items()}
+    loop.update({"s_" + k: np.asarray(v) for k, v in scalars.items()})
+    for p, run in enumerate(runs):
+        loop.update(elog_state(run.elog, "elog%d" % p))
+        loop["run%d" % p] = np.array([run.episodes, run.env_steps, run.next_ckpt], dtype=np.int64)
+    loop["file_names"] = np.array([os.path.relpath(f, a.out) for f in files])
+    loop["file_sizes"] = np.array([os.path.getsize(f) if os.path.exists(f) else 0 for f in files], dtype=np.int64)
+    with open(os.path.join(tmp, "loop.npz"), "wb") as f:
+        np.savez(f, **loop)
+    shutil.rmtree(final, ignore_errors=True)
+    os.rename(tmp, final)
+    pointer = os.path.join(root, ".latest.%d" % os.getpid())
+    open(pointer, "w").write("launch%d\n" % it)
+    os.replace(pointer, os.path.join(root, "latest"))
+    kept = sorted((int(m.group(1)), d) for d in os.listdir(root) for m in [re.fullmatch(r"launch(\d+)", d)] if m)
+    for _, d in kept[:-max(1, getattr(a, "state_keep", 1))]:
+        if d != "launch%d" % it:
+            shutil.rmtree(os.path.join(root, d), ignore_errors=True)
+
+
+def read_state(a, path, env_handles, tensors, runs):
+    """What write_state wrote at `path`, but the learner's files, back into the environments, the tensors and the runs -> the scalars.
+    The files the run appends to are cut back to the sizes they had when the state was written (a run killed after it may have
+    appended more)."""
+    for g, e in enumerate(env_handles):
+        e.restore(np.load(os.path.join(path, "env%d.npy" % g)))
+    with np.load(os.path.join(path, "loop.npz")) as z:
+        for k, t in tensors.items():
+            t.copy_(torch.from_numpy(z["t_" + k]))
+        for p, run in enumerate(runs):
+            set_elog_state(run.elog, z, "elog%d" % p)
+            run.episodes, run.env_steps, run.next_ckpt = (int(x) for x in z["run%d" % p])
+        for name, size in zip(z["file_names"].tolist(), z["file_sizes"].tolist()):
+            f = os.path.join(a.out, name)
+            if os.path.exists(f) and os.path.getsize(f) > size:
+                os.truncate(f, size)
+        return {k[2:]: z[k] for k in z.files if k.startswith("s_")}
+
+
 def save_checkpoint(agent, outdir, episodes):
     """TRAIN:150-154's checkpoint + the exploration-noise stream's position + the `latest` pointer."""
     agent.save(outdir, episodes)
@@ -234,7 +331,8 @@ class Learner:
         self.learn = agent.learn      # TRAIN:133-136; bound here: the loop calls it --updates times per launch
         self.csv_name = "%s_training" % a.algo
         # a run continued into the directory it was loaded from appends to that run's CSV (as progress.txt always did)
-        self.resume = bool(a.load) and os.path.abspath(a.load) == os.path.abspath(a.out)
+        # (--resume continues the run of --out: it appends as well)
+        self.resume = (bool(a.load) and os.path.abspath(a.load) == os.path.abspath(a.out)) or bool(getattr(a, "resume", None))
 
     def load(self):
         """--load: the networks, and the exploration-noise stream continued instead of replayed."""
@@ -516,7 +614,18 @@ def collect(a, env, learner, elog=None):
     updates_done = 0
     late = learner.consume_after_log
     learner.start(obs, elog)
-    for it in range(1, a.launches + 1):
+    first = 1
+    state_every, resume = getattr(a, "state_every", 0), getattr(a, "resume", None)      # (a Namespace built by hand has neither: Args)
+    stateful = state_every or resume                                   # (--algo td3 --learner fused --reset-mode next: parse_args)
+    if stateful:
+        files = [os.path.join(a.out, learner.csv_name + ".csv")] if a.csv else []
+        loop_tensors = lambda: dict(obs=obs, prev=prev, reward=env.reward, done=env.done, resetting=resetting)
+    if resume:
+        path = resolve_resume(resume)
+        sc = read_state(a, path, [env], loop_tensors(), [run])
+        learner.agent.load_state(os.path.join(path, "agent.npz"))      # (re-packs the actor)
+        first, updates_done, learning = int(sc["it"]) + 1, int(sc["updates_done"]), bool(sc["learning"])
+    for it in range(first, a.launches + 1):
         act = learner.act(obs, it)
         prev.copy_(obs)
         if same:
@@ -542,8 +651,11 @@ def collect(a, env, learner, elog=None):
         last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - run.t0 > a.time_limit)
         if it % a.log_every == 0 or last_launch:
             run.log(it, updates_done)
-            if last_launch:
-                break
+        if state_every and it % state_every == 0:
+            write_state(a, it, lambda d: learner.agent.save_state(os.path.join(d, "agent.npz")), [env], dict(loop_tensors(), act=act), [run],
+                        dict(it=it, updates_done=updates_done, learning=learning), files)
+        if last_launch:
+            break
     run.finish(updates_done)
     return learner.agent, run.episodes
 
@@ -608,11 +720,12 @@ def train_population(a):
     fill_defaults(a)
     dev = a.device
     P = a.population
+    state_every, resume = getattr(a, "state_every", 0), getattr(a, "resume", None)      # (a Namespace built by hand has neither: Args)
     torch.cuda.set_device(dev)
     members = []
     for p in range(P):
         m = argparse.Namespace(**vars(a))
-        m.seed, m.out = a.seed + p, os.path.join(a.out, "member%d" % p)
+        m.seed, m.out, m.resume = a.seed + p, os.path.join(a.out, "member%d" % p), resume      # (resume: the member's CSV is appended to)
         members.append(m)
     specs = [scenario_config(a.scenario, a.envs, a.max_steps, m.seed, a.ped_vmax, **env_switches(a)) for m in members]
     envs = MemberEnvs([sp[0] for sp in specs], dev)
@@ -687,7 +800,27 @@ def train_population(a):
         eval_runs, eval_seconds = eval_runs + 1, eval_seconds + time.time() - t
         return fitness
 
-    for it in range(1, a.launches + 1):
+    first = 1
+    stateful = state_every or resume                                   # (parse_args: not with an evaluation's handles)
+    if stateful:
+        files = [os.path.join(m.out, r.learner.csv_name + ".csv") for m, r in zip(members, runs)] if a.csv else []
+        files += [os.path.join(a.out, "pbt_log.csv")] if a.pbt_every else []
+
+        def loop_tensors():
+            t = dict(obs=obs, prev=prev, act=act, reward=reward, done=done, resetting=resetting)
+            t.update({"record_resetting%d" % p: pop.resetting(p) for p in range(P)} if one_call else {})
+            t.update(dict(pbt_flushed=pbt_flushed, pbt_tot=pbt_tot) if a.pbt_every else {})
+            return t
+    if resume:
+        path = resolve_resume(resume)
+        sc = read_state(a, path, envs.envs, loop_tensors(), runs)
+        pop.load_state(path)                                           # (re-packs the bound actors; the agents' hyper-parameters follow)
+        if not one_launch:
+            for ag in agents:
+                ag.sync_fused_weights()
+        first, updates_done, learning = int(sc["it"]) + 1, int(sc["updates_done"]), bool(sc["learning"])
+        pbt_applied = int(sc["pbt_applied"]) if a.pbt_every else 0
+    for it in range(first, a.launches + 1):
         if one_launch:
             pop.act(add_noise=True)
         else:
@@ -744,8 +877,11 @@ def train_population(a):
                 pbt_flushed.add_(torch.stack([e.tot for e in elogs]))     # (RunLog.log flushes: the totals restart)
             for run in runs:
                 run.log(it, updates_done)
-            if last_launch:
-                break
+        if state_every and it % state_every == 0:
+            write_state(a, it, pop.save_state, envs.envs, loop_tensors(), runs,
+                        dict(it=it, updates_done=updates_done, learning=learning, pbt_applied=pbt_applied if a.pbt_every else 0), files)
+        if last_launch:
+            break
     if a.pbt_every:
         pbt_csv.close()
     if eval_csv is not None:
@@ -919,15 +1055,41 @@ def build_parser():
     ap.add_argument("--max-csv-rows", type=int, default=2_000_000)
     ap.add_argument("--load", default=None)
     ap.add_argument("--load-episode", default="latest", help="the <N> of td3_*_model_ep<N>.pt, or `latest` = the count in <load>/latest_checkpoint.txt")
+    ap.add_argument("--state-every", type=int, default=0, help="L > 0: at the end of every L-th launch the run's whole state goes to "
+                    "<out>/state/launch<it>/ (the learner's blob -- networks, Adam's state, counters, a population's hyper-parameters and PBT "
+                    "state: one launch -- the replays, the environments' snapshots, the loop's tensors, logs and counts) and <out>/state/latest "
+                    "names it; --algo td3 --learner fused, solo or --population, --reset-mode next, without --eval-every / --pbt-fitness eval")
+    ap.add_argument("--state-keep", type=int, default=1, help="--state-every: how many state directories stay (older ones are removed once the "
+                    "new one is complete)")
+    ap.add_argument("--resume", default=None, metavar="DIR", help="continue the run whose --out was DIR from the state DIR/state/latest names, "
+                    "at the launch after it, bit for bit: give the command line of that run (--launches may be larger); CSVs and pbt_log.csv "
+                    "are appended, checkpoint labels go on growing.  --out defaults to DIR")
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--episodes-per-env", type=int, default=1)
     return ap
 
 
+class Args(argparse.Namespace):
+    """What parse_args returns.  The state switches (--state-every, --state-keep, --resume) are attributes like every other switch, but
+    they are held beside vars(): the namespace vars() gives for a command line stays, key for key, what it was before these switches
+    (tests/test_eval_layout.py holds it to a record), and a Namespace built by hand or copied from vars() simply has none --
+    getattr(a, "state_every", 0) -- so the members of a population are handed `resume` by name."""
+    __slots__ = ("_state",)
+    STATE = dict(state_every=0, state_keep=1, resume=None)
+
+    def __init__(self, **kw):
+        object.__setattr__(self, "_state", dict(self.STATE))
+        super().__init__(**kw)
+
+
+for _name in Args.STATE:
+    setattr(Args, _name, property(lambda self, n=_name: self._state[n], lambda self, v, n=_name: self._state.__setitem__(n, v)))
+
+
 def parse_args(argv=None):
     """The command line with the algorithm's defaults resolved (max_steps, obs_layout, out)."""
     ap = build_parser()
-    a = ap.parse_args(argv)
+    a = ap.parse_args(argv, namespace=Args())
     tab = a.algo in TABULAR
     if tab:           # flags of the replay learners: rejected when given, whatever their value
         probe = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
@@ -941,7 +1103,7 @@ def parse_args(argv=None):
     if a.epsilon_discount is None:
         a.epsilon_discount = 0.9986 if tab else 0.995
     if a.out is None:
-        a.out = "runs/%s" % a.algo
+        a.out = a.resume if a.resume else "runs/%s" % a.algo
     if a.max_steps is None:
         a.max_steps = 250 if a.algo == "dqn" else 200 if tab else 1000
     if (a.algo in ("dqn", "sac") or tab) and a.obs_layout is None:
@@ -960,7 +1122,8 @@ def parse_args(argv=None):
         if a.evaluate:
             ap.error("--population does not apply to --evaluate (evaluate a member's checkpoints from <out>/member<p>)")
         if a.load:
-            ap.error("--population starts its members fresh: --load is not supported")
+            ap.error("--population starts its members fresh: --load is not supported (a population continues from its whole state: "
+                     "--state-every while it runs, then --resume)")
         if a.reset_mode != "next":
             ap.error("--population collects with the next-step reset only (--reset-mode next)")
     if a.population_act is not None and not a.population:
@@ -1023,6 +1186,30 @@ def parse_args(argv=None):
     if max(1, a.population) * len(a.eval_scenarios) > 64:
         ap.error("--eval-scenarios: %d worlds for %d actor(s) are %d jobs: one evaluation takes at most 64"
                  % (len(a.eval_scenarios), max(1, a.population), max(1, a.population) * len(a.eval_scenarios)))
+    if a.state_every or a.resume or a.state_keep != 1:
+        which = "--resume" if a.resume else "--state-every" if a.state_every else "--state-keep"
+        if a.state_every < 0 or a.state_keep < 1:
+            ap.error("--state-every must be >= 0 and --state-keep >= 1")
+        if not (a.state_every or a.resume):
+            ap.error("--state-keep says how many --state-every directories stay: it needs --state-every")
+        if a.algo != "td3":
+            ap.error("%s saves and loads the fused TD3 learner's state (--algo td3), not --algo %s" % (which, a.algo))
+        if a.learner != "fused":
+            ap.error("%s is cn_td3_state_save / _load, the fused learner's state: it needs --learner fused" % which)
+        if a.evaluate:
+            ap.error("%s continues a training run: it does not apply to --evaluate" % which)
+        if a.eval_every or a.pbt_fitness == "eval":
+            ap.error("%s does not cover an evaluation's handles (--eval-every, --pbt-fitness eval): they keep their simulator clock "
+                     "across resets, which no state holds yet" % which)
+        if a.reset_mode != "next":
+            ap.error("%s holds the next-step reset's loop (--reset-mode next), not --reset-mode %s" % (which, a.reset_mode))
+        if a.resume and a.load:
+            ap.error("--resume restores the networks with everything else: --load does not apply")
+        if a.resume:
+            try:
+                resolve_resume(a.resume)
+            except FileNotFoundError as ex:
+                ap.error(str(ex))
     if a.ou_noise and a.algo != "ddpg":
         ap.error("--ou-noise is DDPG's exploration (--algo ddpg)")
     if a.ou_act is not None and not a.ou_noise:

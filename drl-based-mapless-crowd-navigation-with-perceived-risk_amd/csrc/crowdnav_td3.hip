@@ -30,6 +30,7 @@
 #include "../../include/crowdnav.h"
 #include "crowdnav_device.h"
 #include "crowdnav_learner.h"
+#include "crowdnav_state.h"
 
 namespace {
 // The two emitters of td3_chain (after the handle): how the launches of one update, which the chain names in order, are used.
@@ -164,6 +165,8 @@ struct cn_td3_s : ActorCritic {
     float *c_h1[4], *c_h2[4];               // q1, q2, q1_t, q2_t
     float *dq[2];                           // the critics' loss gradients per row (td3_dgrad_kernel's head-backward mode)
     float *dz2[2], *dz1[2];
+    StateTable* state_tab = nullptr;        // cn_td3_state_*: built on first use (crowdnav_state.hip)
+    ~cn_td3_s() { state_table_free(state_tab); }
     void layout(Pool& p)
     {
         const size_t b = B, Dc = D + 2, h = H;
@@ -303,9 +306,14 @@ struct cn_td3_pop_s {
     const PbtTensor* pbt_tensors = nullptr;
     int pbt_chunks = 0;
     bool pbt_logs = false;
+    StateTable* state_tab = nullptr;               // cn_td3_pop_state_*: built on first use, dropped by a bind (crowdnav_state.hip)
     cn_td3_pop_s() = default;
     cn_td3_pop_s(const cn_td3_pop_s&) = delete;
-    ~cn_td3_pop_s() { if (tables || pbt) { DeviceScope scope(device); (void)hipFree(tables); (void)hipFree(pbt); } }
+    ~cn_td3_pop_s()
+    {
+        state_table_free(state_tab);
+        if (tables || pbt) { DeviceScope scope(device); (void)hipFree(tables); (void)hipFree(pbt); }
+    }
 };
 
 extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int device, cn_td3_pop_handle* out)
@@ -541,6 +549,8 @@ extern "C" int cn_td3_pop_pbt_bind(cn_td3_pop_handle h, const cn_td3_pbt_config*
     if (e != hipSuccess) { (void)hipFree(block); return td3_fail(CN_ERR_HIP, f + ": " + hipGetErrorString(e)); }
     if (h->pbt) (void)hipFree(h->pbt);
     h->pbt = block;
+    state_table_free(h->state_tab);                // the state blob gains (or moves) the PBT segments
+    h->state_tab = nullptr;
     h->pbt_cfg = c; h->pbt_logs = logs != nullptr; h->pbt_tensors = tensd;
     h->pbt_chunks = (int)std::min<uint32_t>(64u, std::max<uint32_t>(1u, (longest + 4095u) / 4096u));
     PbtPlanArgs& a = h->pbt_args;
@@ -568,4 +578,50 @@ extern "C" int cn_td3_pop_exploit(cn_td3_pop_handle h, const float* fitness_dev,
 extern "C" const cn_td3_pbt_state* cn_td3_pop_pbt_state_dev(cn_td3_pop_handle h)
 {
     return (h && h->pbt) ? h->pbt_args.state : nullptr;
+}
+
+// ---- the state blob's view of a handle (crowdnav_state.h; the statement: include/crowdnav.h, cn_td3_state_*) ----------------------
+// Member p's segments in the blob's order: the tensors of PbtTensor's table (cn_td3_pop_pbt_bind), then the counter and the loss.
+static void td3_member_state(cn_td3_s* m, int p, std::vector<StateSeg>& s)
+{
+    const cn_td3_mlp* nets[6] = {&m->cfg.actor, &m->cfg.actor_t, &m->cfg.q1, &m->cfg.q1_t, &m->cfg.q2, &m->cfg.q2_t};
+    for (int net = 0; net < 6; ++net) {
+        const float* w[6] = {nets[net]->w1, nets[net]->b1, nets[net]->w2, nets[net]->b2, nets[net]->w3, nets[net]->b3};
+        for (int j = 0; j < 6; ++j)
+            s.push_back({(void*)w[j], p, CN_STATE_PARAM, net * 6 + j, (uint32_t)param_count(net < 2 ? m->D : m->D + 2, net < 2 ? 2 : 1, m->H, j)});
+    }
+    for (int net = 0; net < 3; ++net) for (int j = 0; j < 6; ++j) for (int k = 0; k < 2; ++k)
+        s.push_back({m->mom[net][j][k], p, CN_STATE_MOMENT, (net * 6 + j) * 2 + k, (uint32_t)param_count(net == 0 ? m->D : m->D + 2, net == 0 ? 2 : 1, m->H, j)});
+    s.push_back({m->adam, p, CN_STATE_ADAM, 0, 4}); s.push_back({m->steps, p, CN_STATE_STEPS, 0, 2}); s.push_back({m->pw, p, CN_STATE_PW, 0, 8});
+    s.push_back({m->counter, p, CN_STATE_COUNTER, 0, 2}); s.push_back({m->loss, p, CN_STATE_LOSS, 0, 1});
+}
+void td3_state_view(cn_td3_handle h, bool full, StateView& v)
+{
+    v.family = CN_STATE_FAMILY_TD3; v.P = 1; v.obs_dim = h->D; v.hidden = h->H; v.batch = h->B; v.pbt_bound = 0; v.device = h->device;
+    v.table = &h->state_tab;
+    if (full) td3_member_state(h, 0, v.seg);
+}
+void td3_pop_state_view(cn_td3_pop_handle h, bool full, StateView& v)
+{
+    const cn_td3_s* m0 = h->mem[0].get();
+    v.family = CN_STATE_FAMILY_TD3; v.P = h->P; v.obs_dim = m0->D; v.hidden = m0->H; v.batch = h->B; v.pbt_bound = h->pbt ? 1 : 0; v.device = h->device;
+    v.table = &h->state_tab;
+    if (!full) return;
+    const int P = h->P, n_gamma = (int)(h->gamma_jobs.size() / (size_t)P);
+    for (int p = 0; p < P; ++p) {
+        td3_member_state(h->mem[p].get(), p, v.seg);
+        v.seg.push_back({nullptr, p, CN_STATE_HYPER, 0, CN_PBT_HYPERS});
+        for (int q = 0; q < 2; ++q) {              // where td3_pbt_plan_kernel writes them: both chains' tick tables, both modes' prep tables
+            TickArgs* tk = const_cast<TickArgs*>(h->tick[q]) + p;
+            PrepArgs* pr = const_cast<PrepArgs*>(h->prep[q]) + p;
+            v.scatter.push_back({&tk->lr_actor, p, CN_PBT_LR_ACTOR}); v.scatter.push_back({&tk->lr_critic, p, CN_PBT_LR_CRITIC});
+            v.scatter.push_back({&pr->noise_std, p, CN_PBT_NOISE_STD}); v.scatter.push_back({&pr->noise_clip, p, CN_PBT_NOISE_CLIP});
+        }
+        for (int g = 0; g < n_gamma; ++g)
+            v.scatter.push_back({&(const_cast<GemmJob*>(h->jobs) + h->gamma_jobs[(size_t)p * n_gamma + g])->hb_gamma, p, CN_PBT_GAMMA});
+    }
+    if (h->pbt) {
+        v.seg.push_back({h->pbt_args.state, -1, CN_STATE_PBT, 0, (uint32_t)(sizeof(cn_td3_pbt_state) / 4)});
+        v.seg.push_back({h->pbt_args.last, -1, CN_STATE_PBT_LAST, 0, (uint32_t)(4 * P)});
+    }
 }

@@ -912,6 +912,76 @@ int cn_td3_pop_pbt_bind(cn_td3_pop_handle h, const cn_td3_pbt_config* cfg, const
 int cn_td3_pop_exploit(cn_td3_pop_handle h, const float* fitness_dev /* [n_members], or NULL = from the bound logs */, void* stream);
 const cn_td3_pbt_state* cn_td3_pop_pbt_state_dev(cn_td3_pop_handle h);
 
+/* A learner's whole state as one blob in device memory, out and in by ONE launch each (csrc/crowdnav_state.hip), whatever the number
+ * of members.  Statement: a handle that loads a blob continues, BIT FOR BIT, as the handle that saved it would have -- every
+ * cn_td3_update / cn_td3_pop_update / cn_td3_pop_exploit after the load writes the bytes it would have written after the save.  (The
+ * replay ring, the seed and the configuration are the caller's: the same ring contents and the same configuration are assumed.)
+ * Blob = cn_state_header | cn_state_segment directory[n_segments] | payload.  Every segment's offset is a multiple of 16; a segment
+ * holds `bytes` bytes and the bytes up to the next multiple of 16 are ZERO, so equal states give equal blobs.  The payload's first
+ * segment starts at sizeof(cn_state_header) + n_segments * sizeof(cn_state_segment) (a multiple of 16); the segments follow each other
+ * in directory order without other gaps; total_bytes = the last segment's offset + its bytes rounded up to 16.
+ * Segments, in this order.  Per member p = 0 .. n_members-1 (a solo handle is member 0):
+ *   CN_STATE_PARAM    index 0..35: network (actor, actor_t, q1, q1_t, q2, q2_t) x tensor (w1, b1, w2, b2, w3, b3), float32 -- the
+ *                     nn.Linear storages that the configuration names, so the blob is self-contained
+ *   CN_STATE_MOMENT   index 0..35: optimised network (actor, q1, q2) x tensor x (m, v), float32, the sizes of the parameters
+ *   CN_STATE_ADAM     float32[4]    CN_STATE_STEPS  float32[2]    CN_STATE_PW  float64[4]   (the tick's: bias corrections, step
+ *                     counters, running beta products)
+ *   CN_STATE_COUNTER  uint64: the update counter that keys the replay sampling (cn_td3_pop_exploit never copies it)
+ *   CN_STATE_LOSS     float32: the first critic's MSE of the last update
+ *   CN_STATE_HYPER    populations only: float32[CN_PBT_HYPERS] in CN_PBT_* order, as the device tables of cn_td3_pop_update hold them
+ *                     NOW (a solo handle trains with its configuration's values and has no such segment)
+ * then, member = -1, only when cn_td3_pop_pbt_bind was called (header.pbt_bound = 1):
+ *   CN_STATE_PBT      cn_td3_pbt_state, whole          CN_STATE_PBT_LAST  float64[n_members][2], the log-fed fitness' `last`
+ * The workspace (the gathered batch, activations, partial sums) is not part of the state: every update rewrites what it reads of it.
+ * cn_td3_state_size / cn_td3_pop_state_size: total_bytes for this handle (0 for a NULL handle or on an error, text in
+ *   cn_td3_last_error).  The first call builds the launch's job table in device memory (it allocates and synchronises); it is kept
+ *   until the handle ends or cn_td3_pop_pbt_bind is called.  Call it before capturing a save into a graph.
+ * _save(h, blob_dev, bytes, stream): ONE launch, enqueue-only, no host read, capturable.  Writes header, directory, payload and the
+ *   zero padding -- every byte of [blob_dev, blob_dev + bytes) and none outside: a consistent picture at its point in the stream.
+ * _load(h, blob_dev, bytes, stream): waits for `stream`, reads header and directory to the host (one small synchronous copy), then ONE
+ *   launch.  A population's load writes each hyper-parameter to every place the update reads it (both chains' tick tables, both
+ *   sampling modes' prep tables, every job that carries gamma); with PBT bound, the PBT state and `last` as well.
+ * Both: the launch is one workgroup per piece of at most 4096 words of a segment; plain vector loads and stores, 16 bytes wide where
+ *   the live tensor and its place in the blob reach a 16-byte boundary together, 4 bytes otherwise: any 4-byte alignment of the live
+ *   tensors and of blob_dev works.
+ * Refused, nothing written, text in cn_td3_last_error -- CN_ERR_ARG: a NULL handle or blob_dev; blob_dev not 4-byte aligned; bytes
+ *   other than the handle's size; (load) a wrong magic or version.  CN_ERR_CONFIG: (load) a header whose family, n_members, obs_dim,
+ *   hidden, batch, pbt_bound, n_segments or total_bytes, or a directory entry, differs from the handle's (the text names the field).
+ * cn_td3_state_segment_dev / cn_td3_pop_state_segment_dev(h, i, seg_out): directory entry i of this handle (seg_out may be NULL) and
+ *   the live device address its bytes are copied from, read-only for the caller (tests and tools); NULL for i out of range (seg_out
+ *   is then left alone) and for CN_STATE_HYPER, whose values live scattered in the tables (seg_out is filled in). */
+#define CN_STATE_MAGIC 0x0045544154534E43ull      /* "CNSTATE" little-endian */
+#define CN_STATE_VERSION 1
+enum { CN_STATE_FAMILY_TD3 = 1 };                 /* (DDPG, SAC, DQN: later lists of the same table) */
+enum { CN_STATE_PARAM = 0, CN_STATE_MOMENT, CN_STATE_ADAM, CN_STATE_STEPS, CN_STATE_PW, CN_STATE_COUNTER, CN_STATE_LOSS,
+       CN_STATE_HYPER, CN_STATE_PBT, CN_STATE_PBT_LAST, CN_STATE_KINDS };
+typedef struct cn_state_header {
+    uint64_t magic;            /* CN_STATE_MAGIC */
+    int32_t  version;          /* CN_STATE_VERSION */
+    int32_t  family;           /* CN_STATE_FAMILY_* */
+    int32_t  n_members;        /* 1 for a solo handle */
+    int32_t  obs_dim, hidden, batch;
+    int32_t  pbt_bound;        /* 1: the CN_STATE_PBT and CN_STATE_PBT_LAST segments are present */
+    int32_t  n_segments;
+    uint64_t total_bytes;      /* header + directory + payload, padding included */
+} cn_state_header;
+typedef struct cn_state_segment {
+    int32_t  member;           /* 0 .. n_members-1, or -1 for the population's own segments */
+    int32_t  kind;             /* CN_STATE_* */
+    int32_t  index;            /* within the kind */
+    int32_t  reserved;         /* 0 */
+    uint64_t offset;           /* from the blob's start; a multiple of 16 */
+    uint64_t bytes;            /* without the padding */
+} cn_state_segment;
+size_t cn_td3_state_size(cn_td3_handle h);
+int cn_td3_state_save(cn_td3_handle h, void* blob_dev, size_t bytes, void* stream);
+int cn_td3_state_load(cn_td3_handle h, const void* blob_dev, size_t bytes, void* stream);
+const void* cn_td3_state_segment_dev(cn_td3_handle h, int i, cn_state_segment* seg_out);
+size_t cn_td3_pop_state_size(cn_td3_pop_handle h);
+int cn_td3_pop_state_save(cn_td3_pop_handle h, void* blob_dev, size_t bytes, void* stream);
+int cn_td3_pop_state_load(cn_td3_pop_handle h, const void* blob_dev, size_t bytes, void* stream);
+const void* cn_td3_pop_state_segment_dev(cn_td3_pop_handle h, int i, cn_state_segment* seg_out);
+
 /* n_steps calls of cn_step (auto_reset = 2, the next-step reset convention) with OPEN-LOOP actions -- scripted or recorded
  * actions, action repeat, the uniform-random warm-up phase of an off-policy learner -- as ONE launch: a wavefront keeps its
  * environment for the whole launch and walks its steps at its own pace (no launch boundary and no device-wide join between
