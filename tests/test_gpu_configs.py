@@ -828,8 +828,8 @@ def test_one_launch_paths_of_the_other_simulators_equal_step_by_step(world):
     not fit one CU's LDS: there the policy kernel runs 8 environments per workgroup.  Round 6: and for the contact ticks and the two
     older observation layouts (363 / 370 actor inputs), so every configuration cn_create accepts has both forms.  Each leaves exactly what T calls of cn_step (resp. T pairs of cn_actor_forward, cn_step) leave: every period's
     actions / observations / rewards / done flags / indices, the final state record, counters and returns, across two calls,
-    with an env count that is not a multiple of the workgroup size.  (The step-by-step kernels of these worlds are pinned
-    against the oracle by tests/test_gpu_parity.py.)"""
+    with an env count that is not a multiple of the workgroup size.  (The step-by-step kernels of these worlds, and these sequence
+    and policy kernels themselves, are pinned against the oracle by name in tests/test_gpu_kernel_matrix.py.)"""
     import torch
     import crowdnav
     from crowdnav import Config

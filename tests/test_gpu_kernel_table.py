@@ -1,7 +1,9 @@
 """Every row of the kernel table (csrc/crowdnav_variants.h) on a live handle (`-m gpu`): one world per row of
 tests/kernel_table_ref.py with three environments -- fewer than one workgroup of every launch geometry, and no multiple of 4, 8 or
 16 -- names the table's kernel for every call, and every call launches: the function the table holds under a name is the
-launchable kernel of that name.  (What the kernels compute is pinned by tests/test_gpu_parity.py and tests/test_gpu_configs.py.)"""
+launchable kernel of that name.  (What each kernel computes is pinned, kernel by kernel and by name, by tests/test_gpu_kernel_matrix.py:
+one case per kernel of the table against the CPU oracle.  tests/test_gpu_parity.py and tests/test_gpu_configs.py hold the larger and
+the full-size runs, whose kernel depends on the launch.)"""
 import pytest
 
 import kernel_table_ref as T

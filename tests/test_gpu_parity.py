@@ -51,8 +51,10 @@ def _pair(oracle_mod, arbitration="auto", **kw):
     return torch, env, orc
 
 
-def _compare_rollout(oracle_mod, steps, seed, reset_mode=True, **kw):
+def _compare_rollout(oracle_mod, steps, seed, reset_mode=True, kernel=None, **kw):
     torch, env, orc = _pair(oracle_mod, seed=seed, **kw)
+    if kernel is not None:
+        assert env.kernel_name("step" if reset_mode == "next" else "same") == kernel
     N = env.N
     env.reset(); torch.cuda.synchronize()
     oc = orc.reset()
@@ -103,21 +105,30 @@ def test_rollout_parity_train_config(oracle_mod):
 @pytest.mark.parametrize("arbitration", ["oldest_first", "fair"])
 def test_rollout_parity_next_step_reset_mode(oracle_mod, arbitration):
     # auto_reset = 2: a finished env spends the next call on its reset (action ignored, reward 0, done 0); on both kernels
-    # of cn_set_arbitration (cn_env_kernel / cn_env_kernel_fair: s_setprio changes when instructions issue, not what they compute)
-    n_done, frac = _compare_rollout(oracle_mod, steps=150, seed=4, reset_mode="next", n_envs=64, n_peds=20, max_steps=50,
-                                    arbitration=arbitration)
+    # of cn_set_arbitration (cn_env_kernel / cn_env_kernel_fair: s_setprio changes when instructions issue, not what they compute).
+    # 300 rays, 12 pedestrians, K = 6: the generic world -- the 360-ray shape would run cn_env_kernel_s360_x2 for both at 64 envs
+    n_done, frac = _compare_rollout(oracle_mod, steps=150, seed=4, reset_mode="next", n_envs=64, n_peds=12, n_rays=300, k_obstacles=6,
+                                    max_steps=50, arbitration=arbitration,
+                                    kernel={"oldest_first": "cn_env_kernel", "fair": "cn_env_kernel_fair"}[arbitration])
     assert n_done > 20 and frac == 1.0
 
 
-def test_arbitration_switch_rule_and_identical_results():
+def test_arbitration_switch_rule_and_identical_results(monkeypatch):
     """cn_set_arbitration / cn_get_arbitration (include/crowdnav.h): the auto rule (fair from two wavefronts per SIMD = 8 x
     compute units environments, oldest-first below and for configurations without a fair kernel), the error path, and that the
-    two kernels leave the same outputs AND the same state records behind, byte for byte, over 120 steps of 2048 environments."""
+    two kernels leave the same outputs AND the same state records behind, byte for byte, over 120 steps of 2048 environments.
+    The two handles of that comparison are created with CN_X2=0 and CN_WPB=0: left to the grid size, both would run
+    cn_env_kernel_s360_x2 at 8 x compute units environments, whatever their arbitration."""
     import torch
     from crowdnav import Config, _abi
     from crowdnav.env import VecEnv, VecEnvGroups
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    small, big = VecEnv(Config(n_envs=8 * ncu - 1)), VecEnv(Config(n_envs=8 * ncu, max_steps=40))
+    small = VecEnv(Config(n_envs=8 * ncu - 1))
+    with monkeypatch.context() as m:
+        m.setenv("CN_X2", "0"); m.setenv("CN_WPB", "0")
+        big = VecEnv(Config(n_envs=8 * ncu, max_steps=40))
+        other = VecEnv(Config(n_envs=8 * ncu, max_steps=40), arbitration="oldest_first")
+    assert big.kernel_name("step") == "cn_env_kernel_fair_s360" and other.kernel_name("step") == "cn_env_kernel_s360"
     assert small.arbitration == "oldest_first" and big.arbitration == "fair"
     small.set_arbitration("fair"); assert small.arbitration == "fair"
     for kw in (dict(obs_layout=1), dict(risk_mode=1), dict(ped_contact=1), dict(ped_mode=2)):
@@ -129,7 +140,6 @@ def test_arbitration_switch_rule_and_identical_results():
         small.set_arbitration("youngest")
     assert small.L.cn_set_arbitration(small.h, 7) == -1 and b"CN_ARB" in small.L.cn_last_error()
     small.close()
-    other = VecEnv(Config(n_envs=8 * ncu, max_steps=40), arbitration="oldest_first")
     assert other.arbitration == "oldest_first"
     big.reset(); other.reset()
     g = torch.Generator(device="cuda").manual_seed(5)

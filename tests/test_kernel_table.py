@@ -37,22 +37,19 @@ int main()
 """
 
 
-@pytest.fixture(scope="module")
-def selection(tmp_path_factory):
-    """{query: kernel name}, ("kernel", name): compile unit, "counts": the table's sizes -- one compile, one run."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    lines = []
-    for w, row in T.WORLDS.items():
-        facts = ", ".join(str(f) for f in row[0])
-        lines.append("    { const int w = cn_world_index(%s);" % facts)
-        launches = [QUIET, LOUD] + (GRID if w in T.PLAIN_TRACKER else [])
-        for form, cform in FORMS:
-            for L in (launches if form == "step" else launches[:2]):
-                lines.append('      { const CnLaunchFacts f = {%d, %s, %d, %d, %d, %d, %d}; printf("select %s %s %s %%s\\n", name_of(cn_select_kernel(w, %s, f))); }'
-                             % (L[0], "true" if L[1] else "false", L[2], L[3], L[4], L[5], L[6], w, form, "/".join(map(str, L)), cform))
-        lines.append("    }")
-    tmp = tmp_path_factory.mktemp("kernel_table")
+def query_lines(w, launches_of):
+    """the program lines that ask cn_select_kernel about world `w`: launches_of(form) = the launch facts to ask each form with"""
+    lines = ["    { const int w = cn_world_index(%s);" % ", ".join(str(f) for f in T.WORLDS[w][0])]
+    for form, cform in FORMS:
+        for L in launches_of(form):
+            lines.append('      { const CnLaunchFacts f = {%d, %s, %d, %d, %d, %d, %d}; printf("select %s %s %s %%s\\n", name_of(cn_select_kernel(w, %s, f))); }'
+                         % (L[0], "true" if L[1] else "false", L[2], L[3], L[4], L[5], L[6], w, form, "/".join(map(str, L)), cform))
+    return lines + ["    }"]
+
+
+def walk(tmp, lines):
+    """Compile PROGRAM with `lines` as its queries (g++, the header alone) and run it: {(world, form, launch facts): kernel name},
+    "kernels": [(name, compile unit)], "counts": the table's sizes."""
     src, exe = tmp / "walk.cpp", tmp / "walk"
     src.write_text(PROGRAM.replace("@QUERIES@", "\n".join(lines)))
     subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(PKG, "csrc"), "-o", str(exe), str(src)], check=True)
@@ -66,6 +63,18 @@ def selection(tmp_path_factory):
         else:
             out[(f[1], f[2], tuple(int(x) for x in f[3].split("/")))] = None if f[4] == "NULL" else f[4]
     return out
+
+
+@pytest.fixture(scope="module")
+def selection(tmp_path_factory):
+    """{query: kernel name}, ("kernel", name): compile unit, "counts": the table's sizes -- one compile, one run."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    lines = []
+    for w in T.WORLDS:
+        launches = [QUIET, LOUD] + (GRID if w in T.PLAIN_TRACKER else [])
+        lines += query_lines(w, lambda form: launches if form == "step" else launches[:2])
+    return walk(tmp_path_factory.mktemp("kernel_table"), lines)
 
 
 def test_every_world_and_form_selects_the_tables_kernel(selection):
