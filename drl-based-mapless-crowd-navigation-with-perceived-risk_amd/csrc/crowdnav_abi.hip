@@ -15,6 +15,7 @@
 #include "crowdnav_actor.h"
 #include "crowdnav_lds.h"
 #include "crowdnav_variants.h"
+#include "crowdnav_snapshot_check.h"
 
 // every kernel that takes CnKParams, from the table (crowdnav_variants.h): declarations, then the functions in cn_kernel_info's order --
 // [0, CN_K_N_DYNAMIC) are launched with cn_create's dynamic LDS size, [CN_K_N_DYNAMIC, CN_K_COUNT) are the policy kernels (both ranges
@@ -729,6 +730,24 @@ extern "C" int cn_restore(cn_handle h, const void* buf, size_t size)
         return fail(CN_ERR_CONFIG, std::string("cn_restore: the snapshot was taken under another configuration: cn_config.") + f +
                                    " differs (a state only means something under the configuration that produced it)");
     if (hd.total_bytes != cn_snapshot_size(h) || size < hd.total_bytes) return fail(CN_ERR_SIZE, "cn_restore: truncated snapshot");
+    // the payload's records, before anything is synchronised or copied: a refused blob leaves the handle as it was
+    {
+        const size_t N = h->cfg.n_envs, P = h->cfg.n_peds;
+        const char* q = (const char*)buf + sizeof(hd);
+        CnRecordSections sec;
+        sec.sd = (const double*)q; q += N * CN_SD_COUNT * 8;
+        sec.si = (const int32_t*)q; q += N * CN_SI_COUNT * 4;
+        sec.ped_p = (const double*)q; q += N * P * 16;
+        sec.ped_v = (const double*)q; q += N * P * 16;
+        sec.trk = (const double*)q;
+        const CnRecordVerdict v = cn_check_records(h->cfg, h->trk_cap, h->max_conf, (int)N, sec);
+        if (!v.ok) {
+            char text[160];
+            cn_record_verdict_text(v, text, sizeof(text));
+            return fail(CN_ERR_CONFIG, std::string("cn_restore: the snapshot holds a record no run produces: ") + text +
+                                       " (csrc/crowdnav_snapshot_check.h states the ranges); nothing was restored");
+        }
+    }
     DeviceScope scope(h->device);
     CN_HIPCHK(fail, hipDeviceSynchronize());
     return snapshot_copy(h, (char*)buf + sizeof(hd), true);      // (only read from)

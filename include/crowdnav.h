@@ -1058,7 +1058,13 @@ int cn_near_separate(int n_rays, int n_peds, int k, int max_conf, int track_capa
  * (ped_aux: goal x, y and goal counter of ped_mode 2; zeros otherwise).  The header carries the ABI version and the FULL cn_config of the handle
  * that wrote it (env_index_base, seed, layout and mode switches included): cn_restore refuses a blob whose header does not
  * match the restoring handle field for field (CN_ERR_CONFIG, the message names the first field that differs) -- a state only
- * means something under the configuration that produced it.  crowdnav.env.VecEnv.save_snapshot / load_snapshot wrap the blob
+ * means something under the configuration that produced it.  Then it checks the payload's records (csrc/crowdnav_snapshot_check.h
+ * states the rule): every stored field that a kernel uses as a count, an index, a loop bound or a flag -- CN_SI_NTRACKS, CN_SI_DQ_LEN,
+ * CN_TF_DQLEN, the done / pending flags, CN_SI_EP_STEP, CN_SI_NCONF / CN_SI_NENTRIES, the crowd clock's sign, with risk_mode gt the
+ * pedestrian id in CN_TF_T -- must be in the range the simulator produces, and poses, pedestrians and live track fields finite and
+ * inside the room (odometry from cn_observe_external or poses from cn_set_ped_init outside room_half: clamp them before the call);
+ * otherwise CN_ERR_CONFIG, the message names environment and field, and nothing is written to the handle.
+ * crowdnav.env.VecEnv.save_snapshot / load_snapshot wrap the blob
  * in an .npz with the header spelled out; oracle/ (test infrastructure) loads that file into the CPU oracle. */
 #define CN_SNAPSHOT_MAGIC 0x50414E534E43ull       /* "CNSNAP" little-endian */
 typedef struct cn_snapshot_header {

@@ -1365,6 +1365,7 @@ static void orig_get_state(const cno_sim* s, env_t* e, const double* ranges, dou
     }
     state[n] = head; state[n + 1] = dist;
     state[n + 2] = cno_py_round(px, 3); state[n + 3] = cno_py_round(py, 3); /* ORIG:315 */
+    e->n_confirmed = 0; e->n_entries = 0;                                 /* no confirmed-object or entry table in this layout: as the kernel stores them */
     *done_out = e->done;
 }
 
