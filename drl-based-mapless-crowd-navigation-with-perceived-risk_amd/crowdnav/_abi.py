@@ -42,6 +42,7 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_replay_sample_indices", "cn_replay_write", "cn_episode_log_add",
            "cn_td3_pop_create", "cn_td3_pop_destroy", "cn_td3_pop_update", "cn_td3_pop_members", "cn_td3_pop_loss_dev",
            "cn_td3_pop_batch_dev", "cn_td3_pop_set_replay_sample",
+           "cn_td3_pop_set_replay_source", "cn_td3_pop_batch_src_dev", "cn_replay_sample_shared",
            "cn_td3_pop_pbt_bind", "cn_td3_pop_exploit", "cn_td3_pop_pbt_state_dev",
            "cn_td3_state_size", "cn_td3_state_save", "cn_td3_state_load", "cn_td3_state_segment_dev",
            "cn_td3_pop_state_size", "cn_td3_pop_state_save", "cn_td3_pop_state_load", "cn_td3_pop_state_segment_dev",
@@ -62,6 +63,8 @@ CN_STATE_MAGIC, CN_STATE_VERSION, CN_STATE_FAMILY_TD3 = 0x0045544154534E43, 1, 1
 CN_STATE_KIND_NAMES = ("param", "moment", "adam", "steps", "pw", "counter", "loss", "hyper", "pbt", "pbt_last")      # CN_STATE_PARAM ... in order
 CN_SAMPLE_WITH_REPLACEMENT, CN_SAMPLE_DISTINCT = 0, 1      # include/crowdnav.h: cn_*_set_replay_sample
 REPLAY_SAMPLE = {"with": CN_SAMPLE_WITH_REPLACEMENT, "without": CN_SAMPLE_DISTINCT}
+CN_REPLAY_OWN, CN_REPLAY_SHARED = 0, 1      # include/crowdnav.h: cn_td3_pop_set_replay_source
+REPLAY_SOURCE = {"own": CN_REPLAY_OWN, "shared": CN_REPLAY_SHARED}
 
 
 def replay_sample_mode(name):
@@ -70,6 +73,14 @@ def replay_sample_mode(name):
         return REPLAY_SAMPLE[name]
     except (KeyError, TypeError):
         raise ValueError("replay_sample must be 'with' or 'without', not %r" % (name,))
+
+
+def replay_source(name):
+    """"own" | "shared" -> CN_REPLAY_*; anything else is a ValueError."""
+    try:
+        return REPLAY_SOURCE[name]
+    except (KeyError, TypeError):
+        raise ValueError("replay_source must be 'own' or 'shared', not %r" % (name,))
 
 
 class CnStepIO(C.Structure):
@@ -432,6 +443,9 @@ def lib():
         L.cn_td3_pop_loss_dev.argtypes = [vp]; L.cn_td3_pop_loss_dev.restype = vp
         L.cn_td3_pop_batch_dev.argtypes = [vp, C.c_int, C.c_int]; L.cn_td3_pop_batch_dev.restype = vp
         L.cn_td3_pop_set_replay_sample.argtypes = [vp, C.c_int]
+        L.cn_td3_pop_set_replay_source.argtypes = [vp, C.c_int]
+        L.cn_td3_pop_batch_src_dev.argtypes = [vp, C.c_int]; L.cn_td3_pop_batch_src_dev.restype = vp
+        L.cn_replay_sample_shared.argtypes = [C.c_uint64, C.c_uint64, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
         L.cn_td3_pop_pbt_bind.argtypes = [vp, C.POINTER(CnTd3PbtConfig), C.POINTER(CnEpisodeLog)]      # logs: an array of n_members, or None
         L.cn_td3_pop_exploit.argtypes = [vp, vp, vp]
         L.cn_td3_pop_pbt_state_dev.argtypes = [vp]; L.cn_td3_pop_pbt_state_dev.restype = vp

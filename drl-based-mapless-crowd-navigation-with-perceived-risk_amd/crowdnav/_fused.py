@@ -136,8 +136,9 @@ class FusedPopulation(_StateBlob):
     """Owns one cn_td3_pop handle: P TD3 learners updated by the launches of one (include/crowdnav.h, cn_td3_pop_create).  cfgs: the
     members' CnTd3Config, in member order.  The sibling of FusedLearner for the population calls; errors raise the same way."""
 
-    def __init__(self, cfgs, device, dev_index, replay_sample="with"):
+    def __init__(self, cfgs, device, dev_index, replay_sample="with", replay_source="own"):
         mode = _abi.replay_sample_mode(replay_sample)
+        source = _abi.replay_source(replay_source)
         self._L = L = _abi.lib()
         self.device, self.P = device, len(cfgs)
         self.cfgs = (_abi.CnTd3Config * self.P)(*cfgs)
@@ -147,6 +148,9 @@ class FusedPopulation(_StateBlob):
         self.replay_sample = "with"
         if mode != _abi.CN_SAMPLE_WITH_REPLACEMENT:
             self.set_replay_sample(replay_sample)
+        self.replay_source = "own"
+        if source != _abi.CN_REPLAY_OWN:
+            self.set_replay_source(replay_source)
 
     def _check(self, what, rc):
         if rc != 0:
@@ -166,6 +170,20 @@ class FusedPopulation(_StateBlob):
         """cn_td3_pop_set_replay_sample: "with" | "without", for all members, for the updates enqueued from now on."""
         self._check("set_replay_sample", self._L.cn_td3_pop_set_replay_sample(self.h, _abi.replay_sample_mode(replay_sample)))
         self.replay_sample = replay_sample
+
+    def set_replay_source(self, replay_source):
+        """cn_td3_pop_set_replay_source: "own" (every member samples its own ring, the default) | "shared" (every member samples
+        the union of all members' rings), for the updates enqueued from now on; a captured update keeps its source."""
+        self._check("set_replay_source", self._L.cn_td3_pop_set_replay_source(self.h, _abi.replay_source(replay_source)))
+        self.replay_source = replay_source
+
+    def batch_src(self, member, batch):
+        """An int64 view [batch, 2] of {ring, row} of `member`'s rows in the last shared update (cn_td3_pop_batch_src_dev), valid
+        until the next one."""
+        ptr = self._L.cn_td3_pop_batch_src_dev(self.h, int(member))
+        if not ptr:
+            raise _abi.CrowdNavError("cn_td3_pop_batch_src_dev: member %r out of range, or no shared update yet" % (member,))
+        return _device_view(ptr, (int(batch), 2), torch.int64, self.device)
 
     def batch_dev(self, member, what, shape, dtype=torch.float32):
         """A view of what the last update gathered for `member` (cn_td3_pop_batch_dev), valid until the next update."""

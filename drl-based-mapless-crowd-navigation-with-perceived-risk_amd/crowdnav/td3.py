@@ -609,9 +609,11 @@ class Population:
     bit for bit, what those leave.
     Evaluating: bind_eval(worlds, quota, metric) once, then evaluate() runs every member's greedy actor in every world -- three
     enqueues per launch for all of them (crowdnav.rollout.DeviceEvaluator, cn_eval_record) -- and returns the fitness [P] on the
-    device, which exploit(fitness) takes; the members' noise counters do not move."""
+    device, which exploit(fitness) takes; the members' noise counters do not move.
+    replay_source: "own" (member p's batch comes from its own ring) | "shared" (from the union of all members' rings, uniformly over
+    its live rows: include/crowdnav.h, cn_td3_pop_set_replay_source; the rings stay where they are and the recorder is the same)."""
 
-    def __init__(self, agents, replay_sample=None):
+    def __init__(self, agents, replay_sample=None, replay_source="own"):
         agents = list(agents)
         if not agents:
             raise ValueError("a population needs at least one agent")
@@ -622,16 +624,30 @@ class Population:
             raise ValueError("an agent of a population is not updated on its own (enable_fused_update / enable_graphs were called)")
         self.agents, self.device, self.policy_delay, self.batch_size = agents, a0.device, a0.policy_delay, a0.batch_size
         self._fused = FusedPopulation([a.fused_config() for a in agents], self.device, a0._dev_index,
-                                      replay_sample=a0.replay_sample if replay_sample is None else replay_sample)
+                                      replay_sample=a0.replay_sample if replay_sample is None else replay_sample,
+                                      replay_source=replay_source)
         self._actors = self._act_io = self._act_key = None
         self._recorder = None
 
     def __len__(self):
         return len(self.agents)
 
+    @property
+    def replay_source(self):
+        return self._fused.replay_source
+
     def ready(self):
-        """Every member's ring holds more than a batch (a host read only while a member's bounds straddle it)."""
-        return all(a.memory.ready(self.batch_size) for a in self.agents)
+        """Every member's ring holds more than a batch (a host read only while a member's bounds straddle it).  Shared source: the
+        rings together hold more than a batch -- DeviceReplay.ready's inequality on the sum of the live sizes, from the sums of the
+        rings' bounds, with host reads only while those straddle it.  All members start together either way."""
+        if self.replay_source != "shared":
+            return all(a.memory.ready(self.batch_size) for a in self.agents)
+        n, mems = self.batch_size, [a.memory for a in self.agents]
+        if sum(m._lb for m in mems) > n:
+            return True
+        if sum(m._ub for m in mems) <= n:
+            return False
+        return sum(m.sync_len() for m in mems) > n
 
     def learn(self, step):
         """One update of every member; the actor and the targets move when step % policy_delay == 0, as in Agent.learn.  Enqueue-only.
@@ -876,6 +892,13 @@ class Population:
 
     def set_replay_sample(self, replay_sample):
         self._fused.set_replay_sample(replay_sample)
+
+    def set_replay_source(self, replay_source):
+        self._fused.set_replay_source(replay_source)
+
+    def batch_src(self, member):
+        """{ring, row} [batch, 2] (int64, a view) of `member`'s rows in the last shared update."""
+        return self._fused.batch_src(member, self.batch_size)
 
     def batch_dev(self, member, what, shape):
         return self._fused.batch_dev(member, what, shape)

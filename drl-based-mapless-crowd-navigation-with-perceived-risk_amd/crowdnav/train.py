@@ -66,6 +66,7 @@ observation a finished env returns is the terminal one, so it is the transition'
 CSV rows accumulate in device tensors and are read once per `--log-every` launches.  `--reset-mode same` keeps the older
 path (same-call reset + final_obs) for A/B runs."""
 import argparse
+import json
 import os
 import time
 
@@ -716,11 +717,16 @@ def train_population(a):
     --eval-episodes episodes each; three enqueues per evaluation launch for all of them) and one read of its summaries, whose rows go
     to <out>/eval_log.csv.  It has its own environment and actor handles and draws no noise, so the training run is, bit for bit, the
     run without it.  --pbt-fitness eval: every exploit is preceded by such an evaluation and ranks by its fitness (--eval-metric)
-    instead of the training episodes' returns."""
+    instead of the training episodes' returns.
+    --population-replay shared: every member's update samples the union of all members' rings (Population(replay_source="shared"));
+    the updates begin once the rings together hold more than a batch.  Nothing else in the loop changes: the rings are written and
+    saved per member as before, so --state-every / --resume hold a shared run as they hold any other (give the switch again on
+    --resume, like --replay-sample).  <out>/run.json records the switch."""
     fill_defaults(a)
     dev = a.device
     P = a.population
     state_every, resume = getattr(a, "state_every", 0), getattr(a, "resume", None)      # (a Namespace built by hand has neither: Args)
+    replay_source = getattr(a, "population_replay", None) or "own"
     torch.cuda.set_device(dev)
     members = []
     for p in range(P):
@@ -741,7 +747,12 @@ def train_population(a):
             m.lr_actor, m.lr_critic = (a.lr_actor or 3e-4) * f[0], (a.lr_critic or 3e-4) * f[1]
             spread[p] = dict(noise_std=0.2 * f[2])
     agents = [make_agent(m, envs.D, "cuda:%d" % dev, memory_size=a.memory, actor_final_init=a.actor_final_init, **kw) for m, kw in zip(members, spread)]
-    pop = td3.Population(agents)
+    pop = td3.Population(agents, replay_source=replay_source)
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, "run.json"), "w") as f:             # the switches that shape a population's run
+        json.dump(dict(population=P, population_replay=replay_source, population_act=a.population_act, population_record=a.population_record,
+                       replay_sample=a.replay_sample), f, indent=1, sort_keys=True)
+        f.write("\n")
     obs = envs.reset()
     step_s = (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0
     runs = [RunLog(m, m.out, DeviceEpisodeLog(obs.device, a.max_csv_rows), step_s, Member(m, ag), prefix="member %2d  " % p)
@@ -844,7 +855,7 @@ def train_population(a):
                 elogs[p].add(done[r], cnt[p], ret[p], it, keep[r])
             resetting = done.bool()
         if not learning:
-            learning = pop.ready()                                     # every member: the update counters stay aligned
+            learning = pop.ready()                                     # all members start together: the update counters stay aligned
         if learning:
             for u in range(a.updates):
                 updates_done += 1
@@ -1014,6 +1025,10 @@ def build_parser():
     ap.add_argument("--population-record", default=None, choices=["one-call", "per-member"], help="--population only: one-call (default) = all "
                     "members' replay writes and episode logs in one cn_pop_record (two launches) per training launch; per-member = one "
                     "cn_replay_write, cn_get_counters, cn_get_returns and cn_episode_log_add per member.  Same results, bit for bit")
+    ap.add_argument("--population-replay", default=None, choices=["own", "shared"], help="--population only: own (default) = every member's "
+                    "update samples its own replay ring; shared = every member samples the union of all members' rings, uniformly over its "
+                    "live rows (cn_td3_pop_set_replay_source: the rings stay where they are, only the update's first launch reads "
+                    "differently); the updates begin once the rings together hold more than a batch.  <out>/run.json records it")
     ap.add_argument("--pbt-every", type=int, default=None, help="--population only: L > 0 = population-based training, one Population.exploit() "
                     "(cn_td3_pop_exploit) after the updates of every L-th launch once learning has begun: the worst members copy the best "
                     "members' networks and optimizer state and perturb their hyper-parameters, on the device; rows go to <out>/pbt_log.csv.  "
@@ -1070,12 +1085,12 @@ def build_parser():
 
 
 class Args(argparse.Namespace):
-    """What parse_args returns.  The state switches (--state-every, --state-keep, --resume) are attributes like every other switch, but
-    they are held beside vars(): the namespace vars() gives for a command line stays, key for key, what it was before these switches
-    (tests/test_eval_layout.py holds it to a record), and a Namespace built by hand or copied from vars() simply has none --
-    getattr(a, "state_every", 0) -- so the members of a population are handed `resume` by name."""
+    """What parse_args returns.  The state switches (--state-every, --state-keep, --resume) and --population-replay are attributes like
+    every other switch, but they are held beside vars(): the namespace vars() gives for a command line stays, key for key, what it was
+    before these switches (tests/test_eval_layout.py holds it to a record), and a Namespace built by hand or copied from vars() simply
+    has none -- getattr(a, "state_every", 0) -- so the members of a population are handed `resume` by name."""
     __slots__ = ("_state",)
-    STATE = dict(state_every=0, state_keep=1, resume=None)
+    STATE = dict(state_every=0, state_keep=1, resume=None, population_replay=None)
 
     def __init__(self, **kw):
         object.__setattr__(self, "_state", dict(self.STATE))
@@ -1134,6 +1149,10 @@ def parse_args(argv=None):
         ap.error("--population-record selects how a --population records its transitions: it needs --population")
     if a.population_record is None:
         a.population_record = "one-call"
+    if a.population_replay is not None and not a.population:
+        ap.error("--population-replay selects whose replay rings a --population's updates sample: it needs --population")
+    if a.population_replay is None:
+        a.population_replay = "own"
     pbt_given = [k for k in ("pbt_every", "pbt_fraction", "pbt_factor", "pbt_explore", "pbt_min_episodes", "pbt_spread") if getattr(a, k) is not None]
     if pbt_given and not a.population:
         ap.error("%s: population-based training acts on a --population: it needs --population" % ", ".join("--" + k.replace("_", "-") for k in pbt_given))

@@ -1,7 +1,7 @@
 // crowdnav_gemm.hip -- the kernels that every fused learner launches (gfx950), and the only unit that defines or instantiates them:
 // the three MFMA GEMM kernels F / G / H in their GATE / POP instantiations with the tick that rides in F, and td3_prep_kernel (the
-// replay sample and gather).  The other units reach them through the launchers at the end of this file (crowdnav_learner.h declares
-// them next to the argument structs): TD3 and its population (crowdnav_td3.hip), DDPG (crowdnav_ddpg.hip), SAC (crowdnav_sac.hip)
+// replay sample and gather) with td3_prep_shared_kernel, a population's gather from all members' rings.  The other units reach them
+// through the launchers at the end of this file (crowdnav_learner.h declares them next to the argument structs): TD3 and its population (crowdnav_td3.hip), DDPG (crowdnav_ddpg.hip), SAC (crowdnav_sac.hip)
 // launch the GATE = false instantiations, DQN (crowdnav_dqn.hip) alone GATE = true, the population alone POP = true.
 // The learners' error channel (cn_td3_last_error) is defined here too.
 #include <hip/hip_runtime.h>
@@ -494,6 +494,47 @@ __global__ void __launch_bounds__(256) td3_prep_kernel(typename td3_prep_in<POP>
     if (tid == 2) p.r[m] = p.rr[row];
     if (tid == 3) p.d[m] = p.rd[row];
 }
+// A population whose members draw from ALL members' rings (CN_REPLAY_SHARED; the statement: include/crowdnav.h).  Grid (B, P) over the
+// same tables as td3_prep_kernel<true>: the outputs, counter, seed and noise parameters of row p = blockIdx.y, the ring of row q*.  The
+// first wavefront reads the P live sizes (lane q: ring q's), finds {q*, row} (cn_replay_row_shared) and hands it to the other three
+// through LDS; lane 0 also writes it to src [P][B][2].  The gather and the noise are td3_prep_kernel's.
+__global__ void __launch_bounds__(256) td3_prep_shared_kernel(PrepSharedArgs in)
+{
+    __shared__ unsigned long long pick[2];
+    const PrepArgs& p = in.table[blockIdx.y];
+    const int m = blockIdx.x, tid = threadIdx.x, Dc = p.D + 2, P = in.P;
+    const unsigned long long cnt = *p.counter;
+    if (tid < 64) {
+        unsigned long long n = 0;
+        if (tid < P) { const int64_t live = *in.table[tid].size_dev; n = live > 0 ? (unsigned long long)live : 0ull; }
+        const CnSharedRow at = cn_replay_row_shared(p.seed, cnt, m, n, P, (int)blockIdx.y, p.mode);
+        if (tid == 0) {
+            pick[0] = (unsigned long long)at.ring; pick[1] = at.row;
+            int64_t* out = in.src + ((size_t)blockIdx.y * gridDim.x + m) * 2;
+            out[0] = (int64_t)at.ring; out[1] = (int64_t)at.row;
+        }
+    }
+    __syncthreads();
+    const PrepArgs& from = in.table[pick[0]];
+    const size_t row = (size_t)pick[1];
+    const float* s = from.rs + row * (size_t)p.D;
+    const float* s2 = from.rs2 + row * (size_t)p.D;
+    for (int c = tid; c < p.D; c += blockDim.x) {
+        p.xs[(size_t)m * Dc + c] = s[c];
+        p.x2[(size_t)m * Dc + c] = s2[c];
+    }
+    if (tid < 2) {
+        p.xs[(size_t)m * Dc + p.D + tid] = from.ra[row * 2 + tid];
+        const uint64_t h = cn_mix64(cn_mix64(p.seed ^ cn_mix64(cnt ^ 0x5bd1e995u)) ^ (uint64_t)(uint32_t)m);      // as td3_prep_kernel
+        const float u1 = ((float)(uint32_t)(h >> 40) + 1.0f) * (1.0f / 16777217.0f);
+        const float u2 = (float)(uint32_t)((h >> 8) & 0xffffffu) * (1.0f / 16777216.0f);
+        const float rr = sqrtf(-2.0f * logf(u1));
+        const float z = tid == 0 ? rr * cosf(6.28318530718f * u2) : rr * sinf(6.28318530718f * u2);
+        p.noise[(size_t)m * 2 + tid] = fminf(fmaxf(z * p.noise_std, -p.noise_clip), p.noise_clip);
+    }
+    if (tid == 2) p.r[m] = from.rr[row];
+    if (tid == 3) p.d[m] = from.rd[row];
+}
 // The actor-loss chain -mean Q1(s, pi(s)) (TD3:268-269) has no kernel of its own: its first link (d/dh2 of the critic) is
 // td3_fwd_kernel's dz epilogue; through the critic's first layer to the action (the two action columns of W1) = per-tile partial
 // sums in td3_dgrad_kernel's da epilogue; through the heads' derivatives and the actor's linear3 = the same kernel's ab mode on
@@ -542,3 +583,7 @@ void launch_gemm_pop(int mode, const PopGemmArgs& ga, dim3 grid, hipStream_t st)
 }
 void launch_prep(const PrepArgs& pa, hipStream_t st) { launch(td3_prep_kernel<false>, dim3(pa.B), pa, st); }
 void launch_prep_pop(const PrepArgs* table, int B, int P, hipStream_t st) { launch(td3_prep_kernel<true>, dim3(B, P), table, st); }
+void launch_prep_shared(const PrepArgs* table, int64_t* src, int B, int P, hipStream_t st)
+{
+    launch(td3_prep_shared_kernel, dim3(B, P), PrepSharedArgs{table, src, P}, st);
+}

@@ -101,6 +101,9 @@ struct PrepArgs {
     float noise_std, noise_clip;
     int mode;                                      // CN_SAMPLE_*: how the replay rows are drawn
 };
+// td3_prep_shared_kernel's arguments: a population's prep table of the sampling mode, where {ring, row} of every batch row goes
+// ([P][B][2]), and P
+struct PrepSharedArgs { const PrepArgs* table; int64_t* src; int P; };
 
 // ---- the launchers (crowdnav_gemm.hip): the mode is chosen on the host, once per launch ------------------------------------------
 // grid x, y of a launch of `njobs` jobs in GEMM_F / G / H: the widest job's tiles of C.  The tile sizes are written there, once.
@@ -113,6 +116,8 @@ void launch_gemm_pop(int mode, const PopGemmArgs& ga, dim3 grid, hipStream_t st)
 // td3_prep_kernel: one workgroup per batch row; a population's on the grid (B, P) over a table of P PrepArgs in device memory
 void launch_prep(const PrepArgs& pa, hipStream_t st);
 void launch_prep_pop(const PrepArgs* table, int B, int P, hipStream_t st);
+// td3_prep_shared_kernel on the same grid and table: every member's rows from the union of all members' rings (CN_REPLAY_SHARED)
+void launch_prep_shared(const PrepArgs* table, int64_t* src, int B, int P, hipStream_t st);
 
 // the learners' error channel: the thread's cn_td3_last_error() string (crowdnav_gemm.hip); returns `code`
 int td3_fail(int code, const std::string& msg);

@@ -1,6 +1,7 @@
 // crowdnav_learner_device.h -- device code that more than one unit of the fused learners uses (gfx950): the MFMA operand vectors and
 // their edge loads (the GEMM kernels, crowdnav_gemm.hip; the act kernels of crowdnav_dqn.hip and crowdnav_sac.hip), the 16-row layer
-// those two act kernels share, the soft update, and the replay-row draw (td3_prep_kernel, dqn_prep_kernel, cn_replay_indices_kernel).
+// those two act kernels share, the soft update, and the replay-row draw (td3_prep_kernel, dqn_prep_kernel, cn_replay_indices_kernel;
+// over the union of a population's rings: td3_prep_shared_kernel, cn_replay_shared_kernel).
 // Everything here is __device__ __forceinline__: no kernel is defined in a header.  A header of its own rather than part of
 // crowdnav_device.h: the step kernels' units include that one and keep compiling from unchanged text.
 #pragma once
@@ -100,10 +101,44 @@ __device__ __forceinline__ uint64_t cn_replay_row_distinct(uint64_t seed, uint64
     }
     return x % n;                                  // (never expected: a pass lands at or above n with probability <= 1/4)
 }
-// ring row of batch row m of update `cnt`: the draw with replacement, or the bijection above (mode: the handle's, CN_SAMPLE_*)
+// row of batch row m of update `cnt` among `size` >= 1 live rows: the draw with replacement, or the bijection above (mode: the
+// handle's, CN_SAMPLE_*)
+__device__ __forceinline__ size_t cn_replay_row_of(uint64_t seed, unsigned long long cnt, int m, unsigned long long size, int mode)
+{
+    if (mode == CN_SAMPLE_DISTINCT) return (size_t)cn_replay_row_distinct(seed, cnt, (uint64_t)(uint32_t)m, size);
+    return (size_t)(cn_mix64(cn_mix64(seed ^ cn_mix64(cnt)) ^ (uint64_t)(uint32_t)m) % size);
+}
+// ... of one ring, whose live size is read here
 __device__ __forceinline__ size_t cn_replay_row(uint64_t seed, unsigned long long cnt, int m, const int64_t* size_dev, int mode)
 {
     const unsigned long long size = (unsigned long long)(*size_dev > 0 ? *size_dev : 1);
-    if (mode == CN_SAMPLE_DISTINCT) return (size_t)cn_replay_row_distinct(seed, cnt, (uint64_t)(uint32_t)m, size);
-    return (size_t)(cn_mix64(cn_mix64(seed ^ cn_mix64(cnt)) ^ (uint64_t)(uint32_t)m) % size);
+    return cn_replay_row_of(seed, cnt, m, size, mode);
+}
+
+// The shared replay source (CN_REPLAY_SHARED; the statement is in include/crowdnav.h next to cn_td3_pop_update): batch row m of member
+// `self` is drawn from the union of P <= 64 rings laid end to end.  ONE whole wavefront calls this, lane q holding n = ring q's live
+// size (0 for a negative size and in the lanes at and above P).  The prefix sums are a shuffle scan (integers: the order is free), the
+// total leaves the vector registers so that the draw stays wavefront-uniform, a ballot finds the ring.  Every lane returns the same
+// {ring, row}.  (Lanes at and above P hold the total as their prefix: they pass the test only when a lane below P does.)
+struct CnSharedRow { int ring; unsigned long long row; };
+__device__ __forceinline__ CnSharedRow cn_replay_row_shared(uint64_t seed, unsigned long long cnt, int m, unsigned long long n, int P, int self, int mode)
+{
+    const int lane = (int)(threadIdx.x & 63u);
+    unsigned long long incl = n;                   // pre_{lane + 1}
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned long long up = __shfl_up(incl, (unsigned)d, 64);
+        if (lane >= d) incl += up;
+    }
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(incl & 0xffffffffull), P - 1);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(incl >> 32), P - 1);
+    const unsigned long long total = ((unsigned long long)hi << 32) | lo;
+    const unsigned long long x = cn_replay_row_of(seed, cnt, m, total > 0 ? total : 1ull, mode);
+    const unsigned long long below = __ballot(x < incl);
+    CnSharedRow out = {self, 0ull};                // every ring empty
+    if (below) {
+        out.ring = __ffsll((long long)below) - 1;
+        out.row = x - __shfl(incl - n, out.ring, 64);
+    }
+    return out;
 }

@@ -1,5 +1,5 @@
 // crowdnav_replay.hip -- the collection loop's bookkeeping for one learner, and the replay draw without an update: cn_replay_write,
-// cn_episode_log_add, cn_replay_sample_indices (include/crowdnav.h): four small kernels and their entry points.  Errors go to
+// cn_episode_log_add, cn_replay_sample_indices, cn_replay_sample_shared (include/crowdnav.h): five small kernels and their entry points.  Errors go to
 // the learners' channel (cn_td3_last_error, crowdnav_learner.h).  The bodies of the write and log kernels are crowdnav_record.h's,
 // shared with cn_pop_record's kernels (crowdnav_pop_record.hip) so that both are the same text; the row draw is
 // crowdnav_learner_device.h's, the one td3_prep_kernel and dqn_prep_kernel gather by.
@@ -18,6 +18,17 @@ __global__ void __launch_bounds__(256) cn_replay_indices_kernel(uint64_t seed, u
 {
     const int m = blockIdx.x * 256 + threadIdx.x;
     if (m < B) rows[m] = (int64_t)cn_replay_row(seed, cnt, m, size_dev, mode);
+}
+// ... and the {ring, row} pairs a shared update of member `self` would gather: cn_replay_sample_shared.  One wavefront per batch row,
+// lane q reading ring q's live size, as the first wavefront of td3_prep_shared_kernel does.
+__global__ void __launch_bounds__(64) cn_replay_shared_kernel(uint64_t seed, unsigned long long cnt, const int64_t* const* __restrict__ size_dev,
+                                                              int P, int self, int mode, int64_t* __restrict__ rows)
+{
+    const int m = blockIdx.x, lane = threadIdx.x;
+    unsigned long long n = 0;
+    if (lane < P) { const int64_t live = *size_dev[lane]; n = live > 0 ? (unsigned long long)live : 0ull; }
+    const CnSharedRow at = cn_replay_row_shared(seed, cnt, m, n, P, self, mode);
+    if (lane == 0) { rows[2 * (size_t)m] = (int64_t)at.ring; rows[2 * (size_t)m + 1] = (int64_t)at.row; }
 }
 __global__ void __launch_bounds__(1024) cn_replay_slot_kernel(const uint8_t* __restrict__ keep, int n, int64_t cap, int64_t* pos_dev,
                                                               int64_t* size_dev, int32_t* __restrict__ slot)
@@ -50,6 +61,22 @@ extern "C" int cn_replay_sample_indices(uint64_t seed, uint64_t counter, int B, 
     DeviceScope scope(device);
     hipLaunchKernelGGL(cn_replay_indices_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, seed, (unsigned long long)counter, B,
                        size_dev, mode, rows_dev);
+    CN_HIPCHK(td3_fail, hipGetLastError());
+    return CN_OK;
+}
+
+extern "C" int cn_replay_sample_shared(uint64_t seed, uint64_t counter, int B, const int64_t* const* size_dev_table, int P, int self, int mode,
+                                       int64_t* rows_dev, int device, void* stream)
+{
+    if (!size_dev_table || !rows_dev) return td3_fail(CN_ERR_ARG, "cn_replay_sample_shared: null argument");
+    if (B < 1) return td3_fail(CN_ERR_ARG, "cn_replay_sample_shared: B < 1");
+    if (P < 1 || P > 64) return td3_fail(CN_ERR_ARG, "cn_replay_sample_shared: P must be 1 ... 64");
+    if (self < 0 || self >= P) return td3_fail(CN_ERR_ARG, "cn_replay_sample_shared: self must be 0 ... P - 1");
+    if (mode != CN_SAMPLE_WITH_REPLACEMENT && mode != CN_SAMPLE_DISTINCT)
+        return td3_fail(CN_ERR_ARG, "cn_replay_sample_shared: mode must be CN_SAMPLE_WITH_REPLACEMENT (0) or CN_SAMPLE_DISTINCT (1)");
+    DeviceScope scope(device);
+    hipLaunchKernelGGL(cn_replay_shared_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, seed, (unsigned long long)counter, size_dev_table, P, self,
+                       mode, rows_dev);
     CN_HIPCHK(td3_fail, hipGetLastError());
     return CN_OK;
 }

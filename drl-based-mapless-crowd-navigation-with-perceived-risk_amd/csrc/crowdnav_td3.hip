@@ -290,9 +290,12 @@ extern "C" int cn_td3_update(cn_td3_handle h, int do_actor, const cn_td3_batch* 
 struct cn_td3_pop_s {
     int device = 0, P = 0, B = 0;
     int sample_mode = CN_SAMPLE_WITH_REPLACEMENT;
+    int replay_source = CN_REPLAY_OWN;             // cn_td3_pop_set_replay_source: read on the host when an update is enqueued
+    bool shared_ran = false;                       // a shared update was enqueued: batch_src holds its {ring, row}
+    int64_t* batch_src = nullptr;                  // [P][B][2], written by td3_prep_shared_kernel alone
     float beta1 = 0.f, beta2 = 0.f, eps = 0.f, tau = 0.f;
     std::vector<std::unique_ptr<cn_td3_s>> mem;    // the members' workspaces and Adam state: solo handles that are never updated alone
-    void* tables = nullptr;                        // one allocation: losses [P], prep tables [2 modes][P], tick tables [2 chains][P], jobs
+    void* tables = nullptr;                        // one allocation: losses [P], prep tables [2 modes][P], tick tables [2 chains][P], jobs, batch_src
     float* loss = nullptr;
     const PrepArgs* prep[2] = {nullptr, nullptr};
     const TickArgs* tick[2] = {nullptr, nullptr};
@@ -370,11 +373,13 @@ extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int d
     }
     Pool count{nullptr};
     float* loss = nullptr; PrepArgs* prep[2] = {nullptr, nullptr}; TickArgs* tick[2] = {nullptr, nullptr}; GemmJob* jobs = nullptr;
+    int64_t* batch_src = nullptr;
     auto layout = [&](Pool& pl) {
         pl.take(loss, (size_t)P);
         for (int q = 0; q < 2; ++q) pl.take(prep[q], (size_t)P);
         for (int q = 0; q < 2; ++q) pl.take(tick[q], (size_t)P);
         pl.take(jobs, njobs_all);
+        pl.take(batch_src, (size_t)P * c0.batch * 2);
     };
     layout(count);
     hipError_t e = hipMalloc(&h->tables, count.size);
@@ -426,7 +431,7 @@ extern "C" int cn_td3_pop_create(const cn_td3_config* cfgs, int n_members, int d
     }
     e = hipMemcpy(jobs, hjobs.data(), sizeof(GemmJob) * hjobs.size(), hipMemcpyHostToDevice);
     if (e != hipSuccess) return td3_fail(CN_ERR_HIP, f + ": hipMemcpy: " + hipGetErrorString(e));
-    h->loss = loss; h->jobs = jobs;
+    h->loss = loss; h->jobs = jobs; h->batch_src = batch_src;
     *out = h.release();
     return CN_OK;
 }
@@ -438,6 +443,18 @@ extern "C" const float* cn_td3_pop_batch_dev(cn_td3_pop_handle h, int member, in
     return (h && member >= 0 && member < h->P) ? batch_dev(h->mem[member].get(), what) : nullptr;
 }
 extern "C" int cn_td3_pop_set_replay_sample(cn_td3_pop_handle h, int mode) { return set_replay_sample("cn_td3_pop_set_replay_sample", h, mode); }
+extern "C" int cn_td3_pop_set_replay_source(cn_td3_pop_handle h, int source)
+{
+    if (!h) return td3_fail(CN_ERR_ARG, "cn_td3_pop_set_replay_source: null handle");
+    if (source != CN_REPLAY_OWN && source != CN_REPLAY_SHARED)
+        return td3_fail(CN_ERR_ARG, "cn_td3_pop_set_replay_source: source must be CN_REPLAY_OWN (0) or CN_REPLAY_SHARED (1); the handle keeps its source");
+    h->replay_source = source;
+    return CN_OK;
+}
+extern "C" const int64_t* cn_td3_pop_batch_src_dev(cn_td3_pop_handle h, int member)
+{
+    return (h && member >= 0 && member < h->P && h->shared_ran) ? h->batch_src + (size_t)member * h->B * 2 : nullptr;
+}
 
 extern "C" int cn_td3_pop_update(cn_td3_pop_handle h, int do_actor, void* stream)
 {
@@ -445,7 +462,10 @@ extern "C" int cn_td3_pop_update(cn_td3_pop_handle h, int do_actor, void* stream
     DeviceScope scope(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int a = do_actor ? 1 : 0;
-    launch_prep_pop(h->prep[h->sample_mode], h->B, h->P, st);
+    if (h->replay_source == CN_REPLAY_SHARED) {    // the same tables; only this launch reads differently
+        launch_prep_shared(h->prep[h->sample_mode], h->batch_src, h->B, h->P, st);
+        h->shared_ran = true;
+    } else launch_prep_pop(h->prep[h->sample_mode], h->B, h->P, st);
     for (const PopStep& s : h->chain[a]) {
         const PopGemmArgs ga{h->jobs + s.first, h->tick[a], s.njobs, h->beta1, h->beta2, h->eps, h->tau, s.do_tick};
         launch_gemm_pop(s.mode, ga, dim3(s.gx, s.gy, h->P * s.njobs), st);

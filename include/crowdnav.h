@@ -437,6 +437,42 @@ int cn_td3_pop_members(cn_td3_pop_handle h);
 const float* cn_td3_pop_loss_dev(cn_td3_pop_handle h);                        /* [n_members] */
 const float* cn_td3_pop_batch_dev(cn_td3_pop_handle h, int member, int what); /* as cn_td3_batch_dev */
 int cn_td3_pop_set_replay_sample(cn_td3_pop_handle h, int mode);
+/* The replay source of a population: whose rings a member's batch is drawn from.  CN_REPLAY_OWN (what a fresh handle has): member p
+ * samples its own ring, the statement above.  CN_REPLAY_SHARED: every member samples the UNION of all members' rings, laid end to
+ * end in member order -- the rings stay where they are, nothing is copied, and only the update's first launch (the sample and
+ * gather, td3_prep_shared_kernel in place of td3_prep_kernel) reads differently; the 6 + 5 GEMM launches are the same.
+ * cn_td3_pop_set_replay_source(h, source) stores the source in the handle on the host, like the sampling mode: the next update
+ * enqueued uses it, an update already captured into a hipGraph keeps the source it was captured with.  Any other value: CN_ERR_ARG
+ * (text in cn_td3_last_error) and the handle keeps its source.
+ * Batch row m of member p at its update number c (member p's own counter) in CN_REPLAY_SHARED -- all integers unsigned 64-bit,
+ * everything read on the device when the launch runs:
+ *   n_q   = max(*replay_size_dev of member q, 0)          q = 0 .. P-1
+ *   pre_q = n_0 + ... + n_{q-1}                            (pre_0 = 0)
+ *   N     = max(pre_P, 1)
+ *   x     = the row that cn_td3_batch_dev's statement gives for (seed_p, c, m) with N in place of the ring's live size: the hash for
+ *           CN_SAMPLE_WITH_REPLACEMENT, the keyed bijection for CN_SAMPLE_DISTINCT, unchanged
+ *   q*    = the least q with x < pre_{q+1};  if there is none (every ring empty): q* = p
+ *   row   = x - pre_{q*}                                   (0 when every ring is empty)
+ * Row m of member p's batch is row `row` of member q*'s ring (s, a, r, s2, d).  The target-policy noise is what it is with
+ * CN_REPLAY_OWN: keyed by (seed_p, c, m), scaled and clipped with member p's noise_std / noise_clip.  The draw is uniform over the
+ * union's live rows.  In CN_SAMPLE_DISTINCT with batch <= N the pairs (q*, row) of one update are distinct, and at batch == N a
+ * permutation of the union.  With P == 1 the shared source gathers the rows the own source gathers.
+ * Statement: after any sequence of shared updates, member p equals a solo handle made by cn_td3_create from cfgs[p] and given, at
+ * each update, cn_td3_update(h, do_actor, &batch, stream) with the explicit batch of the rows named above and target_noise = NULL:
+ * the six networks, Adam's state, the loss and cn_td3_pop_batch_dev(h, p, 0..4), BIT FOR BIT.  It does not depend on P, or on p
+ * beyond what the rule says.  The launch reads the same device tables as the own source's, so what cn_td3_pop_exploit and
+ * cn_td3_pop_state_load rewrite in them holds for both.  No atomics, no host read, no copy; capturable on one stream.
+ * cn_td3_pop_batch_src_dev(h, member): device int64 [batch][2], {q*, row} of the member's rows in the last shared update; NULL for
+ * a bad handle or member, or before the first shared update is enqueued.
+ * cn_replay_sample_shared: the [B][2] pairs {q*, row} that a shared update of member `self` with this seed, at update counter
+ * `counter`, in this mode would gather, from the P live sizes that size_dev_table (a DEVICE array of P device pointers) names -- the
+ * same device function, without any rings, as cn_replay_sample_indices is for one ring.  One launch, enqueue-only.  B < 1, P outside
+ * 1 ... 64, self outside 0 ... P-1, an unknown mode or a NULL pointer: CN_ERR_ARG, text in cn_td3_last_error. */
+enum { CN_REPLAY_OWN = 0, CN_REPLAY_SHARED = 1 };
+int cn_td3_pop_set_replay_source(cn_td3_pop_handle h, int source);
+const int64_t* cn_td3_pop_batch_src_dev(cn_td3_pop_handle h, int member);
+int cn_replay_sample_shared(uint64_t seed, uint64_t counter, int B, const int64_t* const* size_dev_table, int P, int self, int mode,
+                            int64_t* rows_dev, int device, void* stream);
 
 /* The DDPG update -- Agent.learn of the reference's ddpg.py:198-243, the baseline learner of start_ddpg_training.py -- on the
  * same GEMM kernels as cn_td3_update (crowdnav_gemm.hip; the update: crowdnav_ddpg.hip), 8 launches per update.  One critic and one target critic, no policy

@@ -6,7 +6,9 @@ eager update only: the captured PyTorch update draws with replacement).  --sampl
 max of N samples of 400 updates instead of one mean.  --algo dqn: cn_dqn_update at (361 of 363, 300, batch) in the same way (fused only).
 --population P: P solo cn_td3_update handles updated one after another on one stream against ONE cn_td3_pop_update of P members
 (crowdnav.td3.Population) on the same build -- the medians of 7 samples of 400 updates, their spread and the ratio; the solo line
-(one handle) is the figure to hold against the parent commit."""
+(one handle) is the figure to hold against the parent commit.  --replay-source {own,shared,both} (with --population): whose rings
+the population's updates sample (cn_td3_pop_set_replay_source); both = one population, its 7 samples of 400 updates taken in turn
+with the own and the shared source (the switch is a host flag), and the difference of the medians: the prep launch is all that differs."""
 import argparse, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "drl-based-mapless-crowd-navigation-with-perceived-risk_amd"))
@@ -18,6 +20,7 @@ ap.add_argument("--replay-sample", default="with", choices=["with", "without"])
 ap.add_argument("--algo", default="td3", choices=["td3", "dqn"])
 ap.add_argument("--samples", type=int, default=0)
 ap.add_argument("--population", type=int, default=0)
+ap.add_argument("--replay-source", default="own", choices=["own", "shared", "both"])
 args = ap.parse_args()
 RS = args.replay_sample
 
@@ -64,9 +67,21 @@ def population_bench(B, P):
     seq = samples_of(lambda i: [a.learn(i) for a in solo])
     print("batch %5d: %s" % (B, line("%d solo handles in sequence" % P, seq)), flush=True)
     del solo
-    pop = Population(agents())
+    pop = Population(agents(), replay_source="own" if args.replay_source == "both" else args.replay_source)
+    if args.replay_source == "both":
+        ms = {"own": [], "shared": []}
+        for j in range(7):
+            for source in ("own", "shared"):
+                pop.set_replay_source(source)
+                ms[source].append(timed(pop.learn, warm=50 if j == 0 else 10))
+        own, shared = [(statistics.median(v), min(v), max(v)) for v in (ms["own"], ms["shared"])]
+        print("batch %5d: %s" % (B, line("population of %d, replay source own   " % P, own)), flush=True)
+        print("batch %5d: %s" % (B, line("population of %d, replay source shared" % P, shared)), flush=True)
+        print("batch %5d: population %d: shared - own = %+.4f ms per update (%+.2f %%), alternated sample by sample" % (
+            B, P, shared[0] - own[0], 100.0 * (shared[0] - own[0]) / own[0]), flush=True)
+        pop.set_replay_source("own")
     tog = samples_of(pop.learn)
-    print("batch %5d: %s" % (B, line("population of %d" % P, tog)), flush=True)
+    print("batch %5d: %s" % (B, line("population of %d%s" % (P, ", replay source shared" if args.replay_source == "shared" else ""), tog)), flush=True)
     print("batch %5d: population %d: %.4f ms against %.4f ms in sequence: ratio %.3f (%.4f ms per member and update)" % (
         B, P, tog[0], seq[0], tog[0] / seq[0], tog[0] / P), flush=True)
 
