@@ -49,7 +49,10 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", "cn_actor_pop_pack", "cn_actor_pop_forward",
            "cn_actor_pop_weights",
            "cn_pop_record_create", "cn_pop_record_destroy", "cn_pop_record_members", "cn_pop_record_resetting", "cn_pop_record",
-           "cn_eval_create", "cn_eval_destroy", "cn_eval_jobs", "cn_eval_reset", "cn_eval_record", "cn_eval_finish", "cn_eval_state_dev"]
+           "cn_eval_create", "cn_eval_destroy", "cn_eval_jobs", "cn_eval_reset", "cn_eval_record", "cn_eval_finish", "cn_eval_state_dev",
+           "cn_step_group_create", "cn_step_group_step", "cn_step_group_reset", "cn_step_group_jobs", "cn_step_group_kernel_name",
+           "cn_step_group_destroy"]
+CN_STEP_GROUP_MAX = 64      # include/crowdnav.h: cn_step_group_create's n is 1 ... 64
 CN_EVAL_MAX = 64            # include/crowdnav.h: cn_eval_create's n_jobs and n_groups are 1 ... 64
 CN_EVAL_COLS = 12           # include/crowdnav.h: the columns of cn_eval_state.sums[j]
 CN_EVAL_SUCCESS_RATE, CN_EVAL_MEAN_RETURN = 0, 1      # include/crowdnav.h: cn_eval_finish's metric
@@ -415,6 +418,12 @@ def lib():
         L.cn_reset.argtypes = [vp, vp, vp, vp, vp]
         L.cn_step.argtypes = [vp, C.POINTER(CnStepIO), vp]
         L.cn_step_multi.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(CnStepIO), C.POINTER(vp)]
+        L.cn_step_group_create.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(CnStepIO), C.POINTER(vp)]
+        L.cn_step_group_step.argtypes = [vp, vp]
+        L.cn_step_group_reset.argtypes = [vp, C.POINTER(vp), vp]
+        L.cn_step_group_jobs.argtypes = [vp]
+        L.cn_step_group_kernel_name.argtypes = [vp]; L.cn_step_group_kernel_name.restype = C.c_char_p
+        L.cn_step_group_destroy.argtypes = [vp]; L.cn_step_group_destroy.restype = None
         L.cn_set_arbitration.argtypes = [vp, C.c_int]
         L.cn_get_arbitration.argtypes = [vp]
         L.cn_observe_external.argtypes = [vp, C.POINTER(CnExternalIO), vp]

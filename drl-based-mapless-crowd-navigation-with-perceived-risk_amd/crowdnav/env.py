@@ -116,6 +116,13 @@ def multi_io(envs, actions, auto_reset="next", want_final=False):
     return (n, hs, ios, sts), keep
 
 
+def group_io(envs, action, auto_reset="next"):
+    """cn_step_group_create's arguments (n, handles, ios) and what they point into: job g is one step of envs[g], reading its
+    consecutive row slice (envs[g].N rows) of the [N_total, 2] action tensor, into envs[g]'s own output buffers."""
+    (n, hs, ios, _), keep = multi_io(envs, [action], auto_reset, False)
+    return (n, hs, ios), keep
+
+
 def _enqueuer(fn, args, keep):
     """A zero-argument callable that only enqueues fn(*args): everything resolved here, `keep` alive as long as the callable."""
     check = _abi.check
@@ -698,6 +705,69 @@ class MemberEnvs(VecEnvGroups):
 
     def _group_cfg(self, g):
         return self._cfgs[g]
+
+    # ---- all members in ONE launch: cn_step_group_* (include/crowdnav.h) ------------------------------------------------------------
+    def _current_stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _step_group(self, action, auto_reset="next"):
+        """The cn_step_group handle of all members stepping from `action` ([N, 2], each member reads its rows); built once per
+        (action buffer, auto_reset) and kept until close().  What the library refuses (members of different worlds, auto_reset
+        "same", ...) raises with its message."""
+        groups = self.__dict__.setdefault("_step_groups", {})
+        key = (action.data_ptr(), AUTO_RESET.get(auto_reset, auto_reset))
+        if key not in groups:
+            (n, hs, ios), keep = group_io(self.envs, action, auto_reset)
+            L, g = self.envs[0].L, C.c_void_p()
+            _abi.check(L.cn_step_group_create(n, hs, ios, C.byref(g)))
+            groups[key] = (g, keep)
+        return groups[key][0]
+
+    def bind_step_group(self, action, auto_reset="next"):
+        """bind_step_all's step as ONE launch whatever the member count: member p rides in the grid's z dimension.  Returns a
+        zero-argument callable that enqueues it on the stream current at bind time -- no fork(), no join(): the step is ordered like
+        any other work of that stream, and the members' own streams are not involved.  Outputs land in each member's obs / reward /
+        done, bit for bit what bind_step_all's callable leaves.  auto_reset: "next" or False (the same-call reset has no group form)."""
+        L = self.envs[0].L
+        g = self._step_group(action, auto_reset)
+        return _enqueuer(L.cn_step_group_step, (g, self._current_stream()), (self, action))
+
+    def step_group_kernel(self, action, auto_reset="next"):
+        """Name of the kernel bind_step_group(action, auto_reset)'s callable launches."""
+        return self.envs[0].L.cn_step_group_kernel_name(self._step_group(action, auto_reset)).decode()
+
+    def reset(self, group=False, masks=None):
+        """Env.reset() of every member -> obs.  group=True: ONE launch on the current stream (cn_step_group_reset) instead of one per
+        member between fork() and join(); masks: None, or per member None (= all of its environments) or a uint8 [n] device tensor."""
+        if not group:
+            assert masks is None
+            return super().reset()
+        if not self.__dict__.get("_step_groups"):
+            self._group_action = torch.zeros((self.N, 2), dtype=torch.float32, device=self.device)
+            self._step_group(self._group_action)
+        g = next(iter(self._step_groups.values()))[0]
+        ptrs = None
+        if masks is not None:
+            assert len(masks) == self.G and all(m is None or (m.dtype == torch.uint8 and m.is_contiguous() and m.numel() == e.N and m.device == e.device)
+                                                for m, e in zip(masks, self.envs))
+            ptrs = (C.c_void_p * self.G)(*[m.data_ptr() if m is not None else None for m in masks])
+        _abi.check(self.envs[0].L.cn_step_group_reset(g, ptrs, self._current_stream()))
+        self._keep_group_reset = masks        # alive until the next call: the launch is asynchronous
+        return self.obs
+
+    def _destroy_step_groups(self):
+        for g, _ in self.__dict__.pop("_step_groups", {}).values():
+            self.envs[0].L.cn_step_group_destroy(g)
+
+    def close(self):
+        self._destroy_step_groups()            # a group goes before its handles
+        super().close()
+
+    def __del__(self):
+        try:
+            self._destroy_step_groups()
+        except Exception:
+            pass
 
 
 class Env:

@@ -248,15 +248,21 @@ class DeviceEvaluator:
     in one world with its own environment handle, and one launch of the evaluation is three enqueues whatever J is -- ONE
     cn_actor_pop_forward (the f32-MFMA actor training acts with, no noise), ONE cn_step_multi, ONE cn_eval_record -- with nothing read
     back until the end.  Every environment contributes exactly its first `quota` episodes, evaluate()'s rule.
+    step: "multi" (the default: cn_step_multi, one step kernel per job on the job's stream, between fork() and join()) | "group" (ONE
+    cn_step_group_step for all jobs on the current stream, no stream waits; the jobs' worlds must then share one kernel -- otherwise
+    this raises with the library's message).  The same logs and summaries either way.
     jobs: [(Config, ped_init | None, ped_preset_vel | None, agent, group)], at most 64, all with the same n_envs and observation width;
     agent: a td3 / ddpg Agent on `device` (several jobs may name the same agent); group: whose fitness the job feeds (finish()).
     The agents' noise counters (_fused_calls) are not touched: an evaluation leaves a training run's noise stream where it was."""
 
-    def __init__(self, jobs, device=0, n_groups=None):
+    def __init__(self, jobs, device=0, n_groups=None, step="multi"):
         from . import _abi
         from ._fused import FusedPopulationActor, mlp_of
         from .env import MemberEnvs
         jobs = [tuple(j) for j in jobs]
+        if step not in ("multi", "group"):
+            raise ValueError("step must be 'multi' or 'group', not %r" % (step,))
+        self.step = step
         if not 1 <= len(jobs) <= _abi.CN_EVAL_MAX:
             raise ValueError("an evaluation takes 1 ... %d jobs, not %d" % (_abi.CN_EVAL_MAX, len(jobs)))
         cfgs = [j[0] for j in jobs]
@@ -275,7 +281,7 @@ class DeviceEvaluator:
         self.step_seconds = [(c.dt_ms + c.scan_latency_ms) / 1000.0 for c in cfgs]
         self.rows = [envs.rows(j) for j in range(self.J)]
         self.act = torch.zeros((envs.N, 2), dtype=torch.float32, device=self.device)
-        self._step_all = envs.bind_step_all(self.act, auto_reset="next")
+        self._step_all = envs.bind_step_group(self.act, auto_reset="next") if step == "group" else envs.bind_step_all(self.act, auto_reset="next")
         dev = self.agents[0]._dev_index
         members = [_abi.CnActorPopMember(actor=mlp_of(a.actor), obs=envs.obs[r].data_ptr(), action=self.act[r].data_ptr(), n=self.n, reserved=0,
                                          max_v=a.max_v, max_w=a.max_w, sigma=a.explore_sigma, reserved_f=0.0, seed=a._noise_seed)
@@ -317,17 +323,20 @@ class DeviceEvaluator:
         """Reset the environments and the counts, then launch until every environment of every job has finished `quota` episodes.
         poll > 0: the host reads `remaining` once every `poll` launches and stops when all are 0; poll = 0: launch_bound(quota)
         launches with no read at all.  Returns the launches enqueued."""
-        ev, envs = self._bind(quota), self.envs
-        envs.reset()
+        ev, envs, multi = self._bind(quota), self.envs, self.step == "multi"
+        envs.reset(group=not multi)
         ev.reset()
         bound = self.launch_bound(quota) if max_launches is None else min(self.launch_bound(quota), int(max_launches))
         it = 0
         while it < bound:
             it += 1
             self._actors.forward(self._zeros, add_noise=False)
-            envs.fork()                                                # the jobs' steps wait for the actions ...
-            self._step_all()
-            envs.join()                                                # ... and the record for the steps
+            if multi:
+                envs.fork()                                            # the jobs' steps wait for the actions ...
+                self._step_all()
+                envs.join()                                            # ... and the record for the steps
+            else:
+                self._step_all()                                       # one launch, on this stream
             ev.record(it)
             if poll and it % poll == 0 and not bool(ev.remaining_dev.any()):
                 break

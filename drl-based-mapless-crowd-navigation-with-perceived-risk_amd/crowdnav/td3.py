@@ -858,11 +858,11 @@ class Population:
             self.pbt_state()
 
     # ---- evaluation on the device: cn_eval_* (include/crowdnav.h) through crowdnav.rollout.DeviceEvaluator -------------------------
-    def bind_eval(self, specs, quota=1, metric="success"):
+    def bind_eval(self, specs, quota=1, metric="success", step="multi"):
         """Set up evaluate(): specs is a list of worlds (Config, ped_init | None, ped_preset_vel | None); job (p, s) is member p's
         greedy actor in world s and feeds group p, so every member is measured in the same worlds with the same seeds.  At most 64
         jobs.  quota: episodes counted per environment; metric: "success" | "return", what the fitness averages over a member's
-        worlds."""
+        worlds.  step: "multi" | "group", how the jobs' environments are stepped (DeviceEvaluator)."""
         from . import _abi
         from .rollout import DeviceEvaluator
         specs = [tuple(s) for s in specs]
@@ -871,7 +871,7 @@ class Population:
         if metric not in _abi.EVAL_METRIC:
             raise ValueError("metric must be 'success' or 'return', not %r" % (metric,))
         jobs = [(cfg, init, vel, a, p) for p, a in enumerate(self.agents) for (cfg, init, vel) in specs]
-        self._evaluator = DeviceEvaluator(jobs, self.agents[0]._dev_index, n_groups=len(self.agents))
+        self._evaluator = DeviceEvaluator(jobs, self.agents[0]._dev_index, n_groups=len(self.agents), step=step)
         self._eval_quota, self._eval_metric, self.eval_worlds = int(quota), metric, len(specs)
         return self
 

@@ -721,12 +721,16 @@ def train_population(a):
     --population-replay shared: every member's update samples the union of all members' rings (Population(replay_source="shared"));
     the updates begin once the rings together hold more than a batch.  Nothing else in the loop changes: the rings are written and
     saved per member as before, so --state-every / --resume hold a shared run as they hold any other (give the switch again on
-    --resume, like --replay-sample).  <out>/run.json records the switch."""
+    --resume, like --replay-sample).  <out>/run.json records the switch.
+    --population-step one-launch: the members' environments step in ONE launch on the loop's stream (MemberEnvs.bind_step_group,
+    cn_step_group_step) instead of one step kernel per member between two rounds of stream waits, and so do the jobs of the bound
+    evaluation; with the one-call recorder the loop is act, step, record with no stream wait at all.  The same run, bit for bit."""
     fill_defaults(a)
     dev = a.device
     P = a.population
     state_every, resume = getattr(a, "state_every", 0), getattr(a, "resume", None)      # (a Namespace built by hand has neither: Args)
     replay_source = getattr(a, "population_replay", None) or "own"
+    group_step = (getattr(a, "population_step", None) or "per-member") == "one-launch"
     torch.cuda.set_device(dev)
     members = []
     for p in range(P):
@@ -751,9 +755,11 @@ def train_population(a):
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, "run.json"), "w") as f:             # the switches that shape a population's run
         json.dump(dict(population=P, population_replay=replay_source, population_act=a.population_act, population_record=a.population_record,
-                       replay_sample=a.replay_sample), f, indent=1, sort_keys=True)
+                       population_step="one-launch" if group_step else "per-member", replay_sample=a.replay_sample), f, indent=1, sort_keys=True)
         f.write("\n")
-    obs = envs.reset()
+    act = torch.zeros((envs.N, 2), dtype=torch.float32, device=envs.device)
+    step_all = envs.bind_step_group(act, auto_reset="next") if group_step else envs.bind_step_all(act, auto_reset="next")
+    obs = envs.reset(group=group_step)                                 # (one-launch: the reset is the group's, one launch too)
     step_s = (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0
     runs = [RunLog(m, m.out, DeviceEpisodeLog(obs.device, a.max_csv_rows), step_s, Member(m, ag), prefix="member %2d  " % p)
             for p, (m, ag) in enumerate(zip(members, agents))]
@@ -761,8 +767,6 @@ def train_population(a):
     N, rows = envs.N, [envs.rows(p) for p in range(P)]
     resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
     prev = torch.empty_like(obs)
-    act = torch.zeros((N, 2), dtype=torch.float32, device=obs.device)
-    step_all = envs.bind_step_all(act, auto_reset="next")
     elogs = [r.elog for r in runs]
     learning = False
     updates_done = 0
@@ -793,7 +797,7 @@ def train_population(a):
     if a.eval_every or eval_fitness:
         # the same worlds with the same seed for every member: job (p, w) is member p's greedy actor in world w, on its own handle
         pop.bind_eval([scenario_config(s, a.eval_envs, a.eval_max_steps, a.eval_seed, a.ped_vmax, **env_switches(a)) for s in a.eval_scenarios],
-                      quota=a.eval_episodes, metric=a.eval_metric)
+                      quota=a.eval_episodes, metric=a.eval_metric, step="group" if group_step else "multi")
         os.makedirs(a.out, exist_ok=True)
         eval_csv = open(os.path.join(a.out, "eval_log.csv"), "a")
         if eval_csv.tell() == 0:
@@ -837,15 +841,21 @@ def train_population(a):
         else:
             for ag, r in zip(agents, rows):
                 ag.act_mfma(obs[r], out=act[r], add_noise=True)
-        if one_call:
+        if one_call and group_step:
+            step_all()                                                 # one launch on this stream: no wait before it, none behind it
+            pop.record(it)
+        elif one_call:
             envs.fork()                                                # the members' steps wait for the actions ...
             step_all()
             envs.join()                                                # ... and everything below for the steps
             pop.record(it)
         else:
             prev.copy_(obs)
-            envs.fork()
-            step_all()
+            if group_step:
+                step_all()
+            envs.fork()                                                # (one-launch: the members' streams wait for the step)
+            if not group_step:
+                step_all()
             cnt = [e.counters() for e in envs.envs]
             ret = [e.returns()[0] for e in envs.envs]
             envs.join()
@@ -1029,6 +1039,10 @@ def build_parser():
                     "update samples its own replay ring; shared = every member samples the union of all members' rings, uniformly over its "
                     "live rows (cn_td3_pop_set_replay_source: the rings stay where they are, only the update's first launch reads "
                     "differently); the updates begin once the rings together hold more than a batch.  <out>/run.json records it")
+    ap.add_argument("--population-step", default=None, choices=["per-member", "one-launch"], help="--population only: per-member (default) = "
+                    "one step kernel per member on the member's stream (cn_step_multi) between two rounds of stream waits; one-launch = "
+                    "all members' environments in ONE launch on the loop's stream (cn_step_group_step), for the training members and for "
+                    "the jobs of --eval-every / --pbt-fitness eval.  Same results, bit for bit.  <out>/run.json records it")
     ap.add_argument("--pbt-every", type=int, default=None, help="--population only: L > 0 = population-based training, one Population.exploit() "
                     "(cn_td3_pop_exploit) after the updates of every L-th launch once learning has begun: the worst members copy the best "
                     "members' networks and optimizer state and perturb their hyper-parameters, on the device; rows go to <out>/pbt_log.csv.  "
@@ -1085,12 +1099,12 @@ def build_parser():
 
 
 class Args(argparse.Namespace):
-    """What parse_args returns.  The state switches (--state-every, --state-keep, --resume) and --population-replay are attributes like
+    """What parse_args returns.  The state switches (--state-every, --state-keep, --resume), --population-replay and --population-step are attributes like
     every other switch, but they are held beside vars(): the namespace vars() gives for a command line stays, key for key, what it was
     before these switches (tests/test_eval_layout.py holds it to a record), and a Namespace built by hand or copied from vars() simply
     has none -- getattr(a, "state_every", 0) -- so the members of a population are handed `resume` by name."""
     __slots__ = ("_state",)
-    STATE = dict(state_every=0, state_keep=1, resume=None, population_replay=None)
+    STATE = dict(state_every=0, state_keep=1, resume=None, population_replay=None, population_step=None)
 
     def __init__(self, **kw):
         object.__setattr__(self, "_state", dict(self.STATE))
@@ -1153,6 +1167,10 @@ def parse_args(argv=None):
         ap.error("--population-replay selects whose replay rings a --population's updates sample: it needs --population")
     if a.population_replay is None:
         a.population_replay = "own"
+    if a.population_step is not None and not a.population:
+        ap.error("--population-step selects how a --population's environments are stepped: it needs --population")
+    if a.population_step is None:
+        a.population_step = "per-member"
     pbt_given = [k for k in ("pbt_every", "pbt_fraction", "pbt_factor", "pbt_explore", "pbt_min_episodes", "pbt_spread") if getattr(a, k) is not None]
     if pbt_given and not a.population:
         ap.error("%s: population-based training acts on a --population: it needs --population" % ", ".join("--" + k.replace("_", "-") for k in pbt_given))

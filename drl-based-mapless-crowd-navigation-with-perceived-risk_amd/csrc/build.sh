@@ -12,7 +12,8 @@
 # crowdnav_kernel.hip (the environment's step, sequence and policy kernels) is compiled as five units (-DCN_TU=n).  Which kernel is
 # defined in which unit is a column of the kernel table, crowdnav_variants.h: unit 1 holds every one-step kernel, units 2-5 the sequence
 # and policy kernels (their rows name the unit), compiled with -mllvm -disable-machine-licm: see the note above the kernel definitions.
-# The units only spread the compile over processes and flags.  crowdnav_stages.h is the one table of the step kernel's stage stamps
+# The units only spread the compile over processes and flags.  crowdnav_step_group.hip includes the same file for its group-only
+# section (cn_step_group_*'s kernels: one launch for several handles), so unit 1 compiles what it always did.  crowdnav_stages.h is the one table of the step kernel's stage stamps
 # (timing slots, the FAIR kernels' s_setprio levels; the profiling tools parse it).  crowdnav_lds.h holds every size of an environment's LDS working
 # set once: the kernels carve with them, crowdnav_abi.hip sizes the launches from cn_lds_map, which composes them.  crowdnav_abi.hip is the environment's host side; the other files each
 # hold a subsystem's kernels next to the host code that launches them: the TD3 actor and the population's actors, the tabular
@@ -34,6 +35,7 @@ UNITS=(         # object, source, flags of its own
   "k3    crowdnav_kernel.hip      -DCN_TU=3 -mllvm -disable-machine-licm"
   "k4    crowdnav_kernel.hip      -DCN_TU=4 -mllvm -disable-machine-licm"
   "k5    crowdnav_kernel.hip      -DCN_TU=5 -mllvm -disable-machine-licm"
+  "kgrp  crowdnav_step_group.hip"
   "abi   crowdnav_abi.hip"
   "actor crowdnav_actor.hip"
   "gemm  crowdnav_gemm.hip"

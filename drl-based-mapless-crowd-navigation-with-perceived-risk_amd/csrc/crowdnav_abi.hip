@@ -29,6 +29,15 @@ static const cn_kernel_fn kKernelFn[] = { CN_DYNAMIC_LDS_KERNELS CN_POLICY_KERNE
 #undef CN_KERNEL
 static_assert(sizeof(kKernelFn) / sizeof(kKernelFn[0]) == CN_K_COUNT && CN_K_N_DYNAMIC == 53 && CN_K_COUNT - CN_K_N_DYNAMIC == 15,
               "the table's 53 dynamic-LDS kernels and 15 policy kernels");
+// the group kernels (CN_GROUP_KERNELS: cn_step_group_*), in cn_group_kernel_info's order
+typedef void (*cn_group_fn)(const CnKParams*);
+#define CN_KERNEL(NAME, TU, COMPACT, GEOMETRY) extern "C" __global__ void NAME(const CnKParams* jobs);
+CN_GROUP_KERNELS
+#undef CN_KERNEL
+#define CN_KERNEL(NAME, TU, COMPACT, GEOMETRY) NAME,
+static const cn_group_fn kGroupFn[] = { CN_GROUP_KERNELS };
+#undef CN_KERNEL
+static_assert(sizeof(kGroupFn) / sizeof(kGroupFn[0]) == CN_G_COUNT, "the table's group kernels");
 extern "C" __global__ void cn_bbox_kernel(CnKParams p, double* out);
 extern "C" __global__ void cn_gather_kernel(CnKParams p, float* last_ret, float* run_ret, int32_t* counters);
 
@@ -348,7 +357,10 @@ extern "C" int cn_create(const cn_config* cfg, int device, cn_handle* out)
         }
     }
     if (h->lds > 64 * 1024)
+    {
         for (int id = 0; id < CN_K_N_DYNAMIC; ++id) CN_HIPCHK(fail, hipFuncSetAttribute((const void*)kKernelFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
+        for (int id = 0; id < CN_G_COUNT; ++id) CN_HIPCHK(fail, hipFuncSetAttribute((const void*)kGroupFn[id], hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds));
+    }
     {   // cn_rollout_policy: 16 (or 8) environments per workgroup, their working sets 16-byte aligned one after the other (the
         // actor's 16-row tile is laid out compactly over them between two steps), + the workgroup's actions
         // (this world's policy kernel: the 720-ray shape's has the compact layout)
@@ -516,6 +528,146 @@ extern "C" int cn_step_multi(int n, const cn_handle* handles, const cn_step_io* 
     }
     return CN_OK;
 }
+
+// ---- cn_step_group_*: J handles' environments in ONE launch ----------------------------------------------------------------------------
+// Job j rides in the grid's z dimension and reads row j of a device table where cn_step's kernel reads its kernel-argument segment
+// (env_kernel_body, JOBS).  cn_step_group_create marshals the rows exactly as step_one / cn_reset + launch() do and uploads them once:
+// the step table is never written again; the reset table only by cn_step_group_reset, ahead of its own launch on the same stream.
+struct cn_step_group_s {
+    int n = 0, device = 0, kernel = 0;      // jobs; the handles' device; index into cn_group_kernel_info
+    std::vector<cn_handle> handles;
+    char* d_tables = nullptr;               // [2][n] rows, CN_JOB_ROW_BYTES apart: the step table, then the reset table
+    char* reset_rows = nullptr;             // the reset table as the device holds it (pinned host memory: the source of an async copy)
+    hipEvent_t copied = nullptr;            // behind the last such copy: the host rows are not touched before it
+    bool copy_pending = false;
+    unsigned grid_x = 0, threads = 64;
+    size_t lds = 0;
+};
+
+static void destroy_group(cn_step_group_s* g)
+{
+    if (!g) return;
+    DeviceScope scope(g->device);
+    (void)hipFree(g->d_tables); (void)hipHostFree(g->reset_rows);
+    if (g->copied) (void)hipEventDestroy(g->copied);
+    delete g;
+}
+
+extern "C" int cn_step_group_create(int n, const cn_handle* handles, const cn_step_io* ios, cn_step_group_handle* out)
+{
+    if (n < 1 || n > CN_STEP_GROUP_MAX)
+        return fail(CN_ERR_ARG, "cn_step_group_create: " + std::to_string(n) + " jobs; a group holds 1 ... " + std::to_string(CN_STEP_GROUP_MAX));
+    if (!handles || !ios || !out) return fail(CN_ERR_ARG, "cn_step_group_create: null argument");
+    auto job = [](int j) { return "cn_step_group_create: job " + std::to_string(j) + ": "; };
+    int64_t total = 0;
+    for (int j = 0; j < n; ++j) {
+        const cn_env_s* h = handles[j];
+        const cn_step_io& io = ios[j];
+        if (!h) return fail(CN_ERR_ARG, job(j) + "null handle");
+        if (!io.action || !io.obs || !io.reward || !io.done) return fail(CN_ERR_ARG, job(j) + "null action, obs, reward or done");
+        if (io.auto_reset == 1)
+            return fail(CN_ERR_ARG, job(j) + "auto_reset 1 (reset inside the same call) has no group kernel; use 0 or 2");
+        if (h->kp.timing || h->kp.ablate) return fail(CN_ERR_ARG, job(j) + "the handle has stage timing or an ablation mask set");
+        if (h->device != handles[0]->device)
+            return fail(CN_ERR_ARG, job(j) + "on device " + std::to_string(h->device) + ", job 0 on device " + std::to_string(handles[0]->device));
+        for (int i = 0; i < j; ++i)
+            if (handles[i] == h) return fail(CN_ERR_ARG, job(j) + "the same handle as job " + std::to_string(i));
+        total += h->cfg.n_envs;
+    }
+    const cn_env_s* h0 = handles[0];
+    const int kernel = cn_select_group_kernel(h0->world, total, h0->n_cus, h0->x2);
+    for (int j = 1; j < n; ++j) {
+        const cn_env_s* h = handles[j];
+        const int kj = cn_select_group_kernel(h->world, total, h->n_cus, h->x2);
+        if (h->world != h0->world || kj != kernel)
+            return fail(CN_ERR_CONFIG, job(j) + "its group kernel is " + cn_group_kernel_info[kj].name + ", job 0's is " +
+                                       cn_group_kernel_info[kernel].name + "; one launch runs one kernel");
+    }
+    const CnKernelInfo& ki = cn_group_kernel_info[kernel];
+    const bool x2 = ki.geometry == CN_GEO_X2;
+    std::unique_ptr<cn_step_group_s, void (*)(cn_step_group_s*)> guard(new cn_step_group_s(), destroy_group);
+    cn_step_group_s* g = guard.get();
+    g->n = n; g->device = h0->device; g->kernel = kernel; g->handles.assign(handles, handles + n);
+    g->threads = x2 ? 128 : 64;
+    const size_t row = CN_JOB_ROW_BYTES;
+    std::vector<char> step_rows((size_t)n * row, 0);
+    DeviceScope scope(g->device);
+    CN_HIPCHK(fail, hipHostMalloc(&g->reset_rows, (size_t)n * row));
+    CN_HIPCHK(fail, hipEventCreateWithFlags(&g->copied, hipEventDisableTiming));
+    memset(g->reset_rows, 0, (size_t)n * row);
+    for (int j = 0; j < n; ++j) {
+        const cn_env_s* h = handles[j];
+        const cn_step_io& io = ios[j];
+        const size_t lds = ki.compact ? h->lds_shape : h->lds;
+        CnKParams kp = h->kp;       // step_one
+        kp.mode = CN_MODE_STEP; kp.auto_reset = io.auto_reset;
+        kp.action = io.action; kp.step_counter = io.step_counter; kp.obs = io.obs; kp.final_obs = io.final_obs;
+        kp.obs_f64 = io.obs_f64; kp.reward = io.reward; kp.done = io.done; kp.topk_idx = io.topk_idx;
+        if (x2) kp.wave_lds = (int32_t)((lds + 15) & ~(size_t)15);      // launch()
+        memcpy(&step_rows[(size_t)j * row], &kp, sizeof(kp));
+        CnKParams kr = h->kp;       // cn_reset
+        kr.mode = CN_MODE_RESET; kr.mask = nullptr; kr.obs = io.obs; kr.obs_f64 = io.obs_f64;
+        if (x2) kr.wave_lds = kp.wave_lds;
+        memcpy(g->reset_rows + (size_t)j * row, &kr, sizeof(kr));
+        const size_t need = x2 ? (size_t)kp.wave_lds + 256 : lds;
+        if (need > g->lds) g->lds = need;
+        if ((unsigned)h->cfg.n_envs > g->grid_x) g->grid_x = (unsigned)h->cfg.n_envs;
+    }
+    CN_HIPCHK(fail, hipMalloc(&g->d_tables, 2 * (size_t)n * row));      // (hipMalloc: 256-byte aligned)
+    CN_HIPCHK(fail, hipMemcpy(g->d_tables, step_rows.data(), step_rows.size(), hipMemcpyHostToDevice));
+    CN_HIPCHK(fail, hipMemcpy(g->d_tables + (size_t)n * row, g->reset_rows, (size_t)n * row, hipMemcpyHostToDevice));
+    if (g->lds > 64 * 1024)
+        CN_HIPCHK(fail, hipFuncSetAttribute((const void*)kGroupFn[kernel], hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->lds));
+    *out = guard.release();
+    return CN_OK;
+}
+
+static int group_launch(cn_step_group_s* g, const char* table, void* stream)
+{
+    hipLaunchKernelGGL(kGroupFn[g->kernel], dim3(g->grid_x, 1, (unsigned)g->n), dim3(g->threads), g->lds, (hipStream_t)stream, (const CnKParams*)table);
+    CN_HIPCHK(fail, hipGetLastError());
+    return CN_OK;
+}
+
+extern "C" int cn_step_group_step(cn_step_group_handle g, void* stream)
+{
+    if (!g) return fail(CN_ERR_ARG, "cn_step_group_step: null group");
+    DeviceScope scope(g->device);
+    return group_launch(g, g->d_tables, stream);
+}
+
+extern "C" int cn_step_group_reset(cn_step_group_handle g, const uint8_t* const* masks, void* stream)
+{
+    if (!g) return fail(CN_ERR_ARG, "cn_step_group_reset: null group");
+    DeviceScope scope(g->device);
+    const size_t row = CN_JOB_ROW_BYTES, bytes = (size_t)g->n * row;
+    auto mask_at = [&](int j) { return g->reset_rows + (size_t)j * row + offsetof(CnKParams, mask); };
+    bool changed = false;
+    for (int j = 0; j < g->n && !changed; ++j) {
+        const uint8_t* had;
+        memcpy(&had, mask_at(j), sizeof(had));
+        changed = had != (masks ? masks[j] : nullptr);
+    }
+    if (changed) {
+        // the masks' addresses go into the rows ahead of the launch, on its stream: behind every earlier launch of the group there
+        if (g->copy_pending) CN_HIPCHK(fail, hipEventSynchronize(g->copied));
+        for (int j = 0; j < g->n; ++j) { const uint8_t* m = masks ? masks[j] : nullptr; memcpy(mask_at(j), &m, sizeof(m)); }
+        CN_HIPCHK(fail, hipMemcpyAsync(g->d_tables + bytes, g->reset_rows, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+        CN_HIPCHK(fail, hipEventRecord(g->copied, (hipStream_t)stream));
+        g->copy_pending = true;
+    }
+    return group_launch(g, g->d_tables + bytes, stream);
+}
+
+extern "C" int cn_step_group_jobs(cn_step_group_handle g) { return g ? g->n : fail(CN_ERR_ARG, "cn_step_group_jobs: null group"); }
+
+extern "C" const char* cn_step_group_kernel_name(cn_step_group_handle g)
+{
+    if (!g) { fail(CN_ERR_ARG, "cn_step_group_kernel_name: null group"); return nullptr; }
+    return cn_group_kernel_info[g->kernel].name;
+}
+
+extern "C" void cn_step_group_destroy(cn_step_group_handle g) { destroy_group(g); }
 
 extern "C" int cn_observe_external(cn_handle h, const cn_external_io* io, void* stream)
 {

@@ -80,6 +80,8 @@ struct CnKParams {
     int32_t pol_envs, pol_act_off;    // environments per workgroup (16 or 8); byte offset of the workgroup's [pol_envs][2] actions in its LDS
     long long* timing;      // profiling build only: [N, 32] s_memtime stamps
 };
+// cn_step_group_*: a job's argument block is one row of a device table (256-byte aligned), the rows whole 64-byte lines apart
+#define CN_JOB_ROW_BYTES ((sizeof(CnKParams) + 63) / 64 * 64)
 
 // cn_actor_pop_kernel / cn_actor_pop_pack_kernel: one row per member in device memory, written once by cn_actor_pop_create
 struct CnActorPopJob {

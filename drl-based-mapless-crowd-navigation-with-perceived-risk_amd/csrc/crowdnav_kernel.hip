@@ -2712,9 +2712,9 @@ __device__ __forceinline__ double compute_reward(KP p, const Poly& pg, EnvRegs& 
 // step, `t` steps into its launch, with the step's actions / outputs at slot t of the caller's buffers.  `act_here`: this
 // environment's (v, w) where the policy kernel's actor left it (LDS) instead of the caller's action array.
 template <bool EXT, bool TWO, int LAYOUT, bool GT = false, int SIM = 0, bool FUSED = false, bool FAIR = false, int SHAPE = 0, bool X2 = false,
-          bool WIDE = false>
+          bool WIDE = false, bool JOBS = false>
 __device__ __forceinline__ void env_kernel_body(const int env, const int lane, char* const smem, const long long t = 0,
-                                                const float* const act_here = nullptr, const int wv = 0)
+                                                const float* const act_here = nullptr, const int wv = 0, const CnKParams* const jobs = nullptr)
 {
     static_assert(!X2 || (!EXT && !TWO && LAYOUT == 0 && !GT && SIM == 0 && !FUSED), "two wavefronts per environment: the plain step kernel");
     // WIDE (cn_config.track_capacity 128 ... 1024): the tracker / entry table stays in HBM (observe, tracker_stage_wide) -- region A
@@ -2722,7 +2722,13 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
     static_assert(!WIDE || (LAYOUT == 0 && !GT && SIM == 0 && SHAPE == 0 && !X2), "the wide tracker table: generic bodies, plain simulator");
     // (round 6: the oldest-first 360-ray step kernels as well -- 26 scalar spills without the fences, see tools/kernel_resources.sh)
     constexpr bool SFENCE = (SHAPE == 720 || SHAPE == 360) && !FAIR && !FUSED;
-    KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+    // JOBS (the _grp kernels, cn_step_group_*): job blockIdx.z of the launch; its argument block is row z of `jobs`, a device table the
+    // host wrote before any launch and never writes while one is in flight -- which is what lets the body read it as it reads the
+    // kernel-argument segment: in place, through the constant address space.
+    static_assert(!JOBS || (!EXT && !TWO && !FUSED && !FAIR), "one launch for several handles: the plain step kernels");
+    KP p;
+    if constexpr (JOBS) p = (KP)((unsigned long long)jobs + (unsigned long long)blockIdx.z * CN_JOB_ROW_BYTES);
+    else p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
     if constexpr (FUSED) {
         // Inside the multi-step kernel's step loop everything below is loop-invariant as far as the compiler can see, and it
         // hoists it: ~100 kernel parameters and every lane-derived mask would stay live across the whole step (hundreds of VGPR
@@ -3231,9 +3237,9 @@ __device__ __forceinline__ void env_kernel_body(const int env, const int lane, c
     CN_T(CN_STG_STORE);
 }
 // env_kernel_body's instantiation by name: a world's five template facts (the columns of crowdnav_variants.h) and the form as flags
-enum : unsigned { CN_F_EXT = 1, CN_F_SAME = 2, CN_F_FUSED = 4, CN_F_FAIR = 8, CN_F_X2 = 16 };
+enum : unsigned { CN_F_EXT = 1, CN_F_SAME = 2, CN_F_FUSED = 4, CN_F_FAIR = 8, CN_F_X2 = 16, CN_F_JOBS = 32 };
 #define CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, FORM) \
-    env_kernel_body<((FORM) & CN_F_EXT) != 0, ((FORM) & CN_F_SAME) != 0, LAYOUT, GT, SIM, ((FORM) & CN_F_FUSED) != 0, ((FORM) & CN_F_FAIR) != 0, SHAPE, ((FORM) & CN_F_X2) != 0, WIDE>
+    env_kernel_body<((FORM) & CN_F_EXT) != 0, ((FORM) & CN_F_SAME) != 0, LAYOUT, GT, SIM, ((FORM) & CN_F_FUSED) != 0, ((FORM) & CN_F_FAIR) != 0, SHAPE, ((FORM) & CN_F_X2) != 0, WIDE, ((FORM) & CN_F_JOBS) != 0>
 
 
 // The product kernel (simulated sensors) and its sibling for externally supplied /scan + /odom.  Two
@@ -3248,6 +3254,12 @@ enum : unsigned { CN_F_EXT = 1, CN_F_SAME = 2, CN_F_FUSED = 4, CN_F_FAIR = 8, CN
 // the 720-ray shape: 13.2 KB of LDS per environment puts 12 wavefronts on a CU (3 per SIMD) whatever the register count, so the
 // allocator may use the 168 VGPRs that occupancy allows instead of squeezing into 128 (cn_env_kernel_s720: 66 -> SGPR spills below)
 #define CN_S720_BOUNDS __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
+#endif
+// (the two-wavefront geometry of the headline shape, cn_env_kernel_s360_x2 and its group form)
+#ifdef CN_TIMING
+#define CN_X2_BOUNDS __launch_bounds__(128)
+#else
+#define CN_X2_BOUNDS __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4)))
 #endif
 // The kernels are the rows of CN_WORLDS (crowdnav_variants.h): each family below -- step, sequence, policy -- is one macro that
 // expands a row to its definitions, and the row names the compile unit of each (csrc/build.sh: -DCN_TU=1 ... 5;
@@ -3339,11 +3351,6 @@ CN_W4_KERNEL(cn_env_kernel_s360_w4, 0)
 CN_W4_KERNEL(cn_env_kernel_fair_s360_w4, CN_F_FAIR)
 // TWO wavefronts per environment (128 threads): small grids -- up to two wavefronts per SIMD would be resident anyway (cn_create: n_envs
 // <= 8 x CUs, BASELINE configs[3]'s 2048-env shard, the N = 1 `Env`) -- where a step is as long as ONE wavefront's dependent chain
-#ifdef CN_TIMING
-#define CN_X2_BOUNDS __launch_bounds__(128)
-#else
-#define CN_X2_BOUNDS __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4)))
-#endif
 extern "C" __global__ void CN_X2_BOUNDS cn_env_kernel_s360_x2(CnKParams p) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; CN_STEP_BODY(0, false, 0, false, 360, CN_F_X2)(blockIdx.x, threadIdx.x & 63, cn_smem, 0, nullptr, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); }
 
 // cn_create: bbox_size() at the spawn pose, evaluated once by the same device code the step kernel would run
@@ -3376,6 +3383,19 @@ extern "C" __global__ void cn_gather_kernel(CnKParams p, float* last_ret, float*
 }
 
 #endif   // CN_TU 1
+#if !defined(CN_TU) || defined(CN_STEP_GROUP_UNIT)
+// ---- cn_step_group_*: J handles' environments in one launch --------------------------------------------------------------------------
+// The kernels of CN_GROUP_KERNELS (crowdnav_variants.h): every world's step kernel once more with the JOBS flag -- grid (max_j N_j, 1, J),
+// job blockIdx.z takes row z of `jobs` for its argument block (env_kernel_body: rows past a job's N_j return at once) -- and the
+// headline shape's two-wavefront form.  The same bounds as the world's step kernel.  A unit of their own
+// (csrc/crowdnav_step_group.hip includes this file for this section alone), so that unit 1 compiles what it compiled.
+#define CN_GROUP_KERNEL(BOUNDS, NAME, ...) \
+    extern "C" __global__ void BOUNDS NAME(const CnKParams* jobs) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; __VA_ARGS__(blockIdx.x, threadIdx.x, cn_smem, 0, nullptr, 0, jobs); }
+#define CN_DEF_GROUP(ID, LAYOUT, GT, SIM, WIDE, SHAPE, BOUNDS, COMPACT, STEP, SAME_HAS, SAME, EXT_HAS, EXT, SEQ, SEQ_TU, POL, POL_TU, POL_BOUND) \
+    CN_GROUP_KERNEL(BOUNDS, STEP##_grp, CN_STEP_BODY(LAYOUT, GT, SIM, WIDE, SHAPE, CN_F_JOBS))
+CN_WORLDS(CN_DEF_GROUP)
+extern "C" __global__ void CN_X2_BOUNDS cn_env_kernel_s360_x2_grp(const CnKParams* jobs) { extern __shared__ __attribute__((aligned(16))) char cn_smem[]; CN_STEP_BODY(0, false, 0, false, 360, CN_F_X2 | CN_F_JOBS)(blockIdx.x, threadIdx.x & 63, cn_smem, 0, nullptr, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), jobs); }
+#endif   // the group kernels
 #if !defined(CN_TU) || CN_TU == 2 || CN_TU == 4 || CN_TU == 5
 // ---- cn_rollout_policy: T control periods per launch with the POLICY IN THE LOOP --------------------------------------------
 // A workgroup = 16 environments = 16 wavefronts (one CU's worth at 4 per SIMD).  Per control period: the first eight waves run

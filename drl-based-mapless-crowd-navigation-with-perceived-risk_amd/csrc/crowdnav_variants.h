@@ -144,3 +144,26 @@ static inline int cn_select_kernel(int world, int form, const CnLaunchFacts& f)
     if (!fair) return w.step;
     return world == CN_W_S360 ? CN_K_cn_env_kernel_fair_s360 : world == CN_W_S720 ? CN_K_cn_env_kernel_fair_s720 : CN_K_cn_env_kernel_fair;
 }
+
+// ---- the group kernels: J handles' environments in ONE launch (cn_step_group_*) -----------------------------------------------------
+// A list of its own, beside the 53 + 15 above: every world's STEP kernel as <STEP>_grp(const CnKParams* jobs) -- job blockIdx.z reads
+// row z of a device table where the kernels above read their kernel-argument segment -- with the row's BOUNDS, and the headline
+// shape's two-wavefront geometry.  csrc/crowdnav_step_group.hip compiles them (the group-only section of crowdnav_kernel.hip); TU 0
+// below says "none of that file's units 1-5".  A world's group kernel has the world's index; the _x2_grp kernel follows the rows.
+#define CN_ROW_GROUP_(ID, LAYOUT, GT, SIM, WIDE, SHAPE, BOUNDS, COMPACT, STEP, SAME_HAS, SAME, EXT_HAS, EXT, SEQ, SEQ_TU, POL, POL_TU, POL_BOUND) \
+    CN_KERNEL(STEP##_grp, 0, COMPACT, ONE)
+#define CN_GROUP_KERNELS CN_WORLDS(CN_ROW_GROUP_) CN_KERNEL(cn_env_kernel_s360_x2_grp, 0, false, X2)
+#define CN_KERNEL(NAME, TU, COMPACT, GEOMETRY) CN_G_##NAME,
+enum { CN_GROUP_KERNELS CN_G_COUNT };
+#undef CN_KERNEL
+static_assert(CN_G_COUNT == CN_W_COUNT + 1 && CN_G_COUNT == 16, "one group kernel per world and the headline shape's x2 form");
+#define CN_KERNEL(NAME, TU, COMPACT, GEOMETRY) {#NAME, TU, COMPACT, CN_GEO_##GEOMETRY},
+static constexpr CnKernelInfo cn_group_kernel_info[CN_G_COUNT] = { CN_GROUP_KERNELS };
+#undef CN_KERNEL
+// The kernel (index into cn_group_kernel_info) a group of handles of `world` launches.  total_envs: the environments of all its jobs --
+// cn_select_kernel's x2 rule with resident = their sum; x2: the handles' CN_X2 (-1 unset, 0 / 1).
+static inline int cn_select_group_kernel(int world, int64_t total_envs, int n_cus, int x2)
+{
+    if (world == CN_W_S360 && (x2 == 1 || (x2 < 0 && total_envs <= 8 * (int64_t)n_cus))) return CN_G_cn_env_kernel_s360_x2_grp;
+    return world;
+}

@@ -264,6 +264,27 @@ int cn_device_clock(int64_t* out_dev, int span_us, int device, void* stream);
  * independent stream groups, DESIGN.md section 6: the launches are the same, the host thread pays the foreign-call
  * overhead once per step instead of once per group).  Stops at the first error and returns it. */
 int cn_step_multi(int n, const cn_handle* handles, const cn_step_io* ios, void* const* streams);
+/* n handles' environments in ONE launch, whatever n is: job j = handles[j] stepping with ios[j] rides in the grid's z dimension and
+ * reads its argument block from row j of a device table that cn_step_group_create builds and uploads once (so the buffers of ios[j]
+ * are bound for the group's life).  After cn_step_group_step every job's outputs and its whole state record are, bit for bit, what
+ * cn_step(handles[j], &ios[j], stream) leaves; after cn_step_group_reset what cn_reset(handles[j], masks[j], ios[j].obs,
+ * ios[j].obs_f64, stream) leaves (masks NULL, or masks[j] NULL: every environment of the job; masks[j]: dev [N_j]).  The handles
+ * stay usable on their own between the group's calls; the caller orders a group's calls among themselves and against the handles'
+ * own (one stream, or streams that wait for each other): cn_step_group_reset writes the masks' addresses into its table with a small
+ * copy ahead of its launch.  cn_step_group_create refuses, before any device work and naming the job: n outside 1 ...
+ * CN_STEP_GROUP_MAX, a null handle or null action / obs / reward / done, auto_reset 1 (the same-call reset has no group kernel),
+ * handles on different devices, of different worlds or group kernels (one launch runs one kernel: cn_step_group_kernel_name; the
+ * headline shape takes its two-wavefront kernel while all jobs' environments together are at most 8 x compute units), the same
+ * handle twice, a handle with the profiling build's stage timing or ablation mask set.  No fair, four-per-workgroup, same-call-reset,
+ * external, sequence or policy form.  Destroy a group BEFORE its handles. */
+typedef struct cn_step_group_s* cn_step_group_handle;
+#define CN_STEP_GROUP_MAX 64
+int cn_step_group_create(int n, const cn_handle* handles, const cn_step_io* ios, cn_step_group_handle* out);
+int cn_step_group_step(cn_step_group_handle g, void* stream);                     /* ONE launch */
+int cn_step_group_reset(cn_step_group_handle g, const uint8_t* const* masks, void* stream);   /* ONE launch; masks NULL or per job NULL = all */
+int cn_step_group_jobs(cn_step_group_handle g);
+const char* cn_step_group_kernel_name(cn_step_group_handle g);
+void cn_step_group_destroy(cn_step_group_handle g);
 int cn_observe_external(cn_handle h, const cn_external_io* io, void* stream);
 
 /* The actor's output stage as one launch (no handle needed): action = clip(heads(logits) + N(0, sigma)).

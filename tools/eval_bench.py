@@ -4,7 +4,9 @@ cn_eval_record per launch, `remaining` read every 16 launches) against the host 
 actor, cn_step, one host read per launch), run once per job in sequence at the same environments per job.  Medians (min - max) of
 --samples samples of --launches evaluation launches on the host clock, enqueue included, one box and one build; per launch of ALL J
 jobs.  Then the record launch alone against what it replaces per job: cn_get_counters + cn_get_returns + cn_episode_log_add.
-The quota is set out of reach, so neither side stops early and both run the same number of launches."""
+The quota is set out of reach, so neither side stops early and both run the same number of launches.
+--step group: the jobs' environments step in ONE launch (cn_step_group_step) instead of cn_step_multi; --step both: two evaluators,
+one of each, their samples alternating, and only the device figures (no host loop, no record-alone legs)."""
 import argparse, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "drl-based-mapless-crowd-navigation-with-perceived-risk_amd"))
@@ -21,6 +23,7 @@ ap.add_argument("--samples", type=int, default=7)
 ap.add_argument("--launches", type=int, default=400)
 ap.add_argument("--scenario", default="crossing_8")
 ap.add_argument("--max-steps", type=int, default=50)
+ap.add_argument("--step", default="multi", choices=["multi", "group", "both"])
 args = ap.parse_args()
 K, QUOTA = args.launches, 1000
 
@@ -40,7 +43,22 @@ for n in [int(x) for x in args.envs.split(",")]:
     for J in [int(x) for x in args.jobs.split(",")]:
         agents = [Agent(obs_dim=398, device="cuda:0", seed=p, memory_size=16) for p in range(min(J, 4))]
         specs = [train.scenario_config(args.scenario, n, args.max_steps, 100 + j) for j in range(J)]
-        ev = DeviceEvaluator([(cfg, init, vel, agents[j % len(agents)], j) for j, (cfg, init, vel) in enumerate(specs)], 0)
+        jobs = [(cfg, init, vel, agents[j % len(agents)], j) for j, (cfg, init, vel) in enumerate(specs)]
+        if args.step == "both":
+            evs = {st: DeviceEvaluator(jobs, 0, step=st) for st in ("multi", "group")}
+            us = {st: [] for st in evs}
+            for e in evs.values():
+                e.run(QUOTA, poll=16, max_launches=50)                               # warm-up
+            for _ in range(args.samples):
+                for st, e in evs.items():
+                    us[st].append(clock(lambda: e.run(QUOTA, poll=16, max_launches=K)))
+            print("J %2d x %3d envs: device, cn_step_multi %s  device, cn_step_group_step %s  ratio %.3f  (%d samples of %d launches, alternated, per launch of all jobs)"
+                  % (J, n, spread(us["multi"]), spread(us["group"]), statistics.median(us["group"]) / statistics.median(us["multi"]), args.samples, K), flush=True)
+            for e in evs.values():
+                e.close()
+            del evs
+            continue
+        ev = DeviceEvaluator(jobs, 0, step=args.step)
         ev.run(QUOTA, poll=16, max_launches=50)                                      # warm-up
         dev = [clock(lambda: ev.run(QUOTA, poll=16, max_launches=K)) for _ in range(args.samples)]
         # the record launch alone, on the state the last run left
