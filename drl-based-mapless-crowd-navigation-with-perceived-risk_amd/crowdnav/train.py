@@ -221,9 +221,9 @@ def set_elog_state(e, z, key):
     e.rows[e._flushed:e._flushed + rows.shape[0]].copy_(rows)
 
 
-def write_state(a, it, save_learner, env_handles, tensors, runs, scalars, files):
+def write_state(a, it, save_learner, runs, counts, env_handles, tensors, scalars, files):
     """One complete <out>/state/launch<it>/, then the `latest` pointer, then the pruning (--state-keep).  save_learner(dir) writes the
-    learner's files; tensors: name -> device tensor; scalars: name -> host number; files: the files this run appends to."""
+    learner's files; tensors: name -> device tensor; counts, scalars: name -> host number; files: the files this run appends to."""
     import re
     import shutil
     root = os.path.join(a.out, STATE_DIR)
@@ -236,7 +236,7 @@ def write_state(a, it, save_learner, env_handles, tensors, runs, scalars, files)
     for g, e in enumerate(env_handles):
         np.save(os.path.join(tmp, "env%d.npy" % g), e.snapshot())
     loop = {"t_" + k: t.cpu().numpy() for k, t in tensors.items()}
-    loop.update({"s_" + k: np.asarray(v) for k, v in scalars.items()})
+    loop.update({"s_" + k: np.asarray(v) for k, v in dict(counts, **scalars).items()})
     for p, run in enumerate(runs):
         loop.update(elog_state(run.elog, "elog%d" % p))
         loop["run%d" % p] = np.array([run.episodes, run.env_steps, run.next_ckpt], dtype=np.int64)
@@ -536,7 +536,7 @@ class Tabular(Learner):
 
 
 class Member(Learner):
-    """Member p of a --population: train_population acts, stores and learns for all members at once; this is its log-time side."""
+    """Member p of a --population: PopulationSide acts, stores and learns for all members at once; this is its log-time side."""
 
     def summary(self, run, last, updates, t):
         return "  | %d updates, %.0f updates/s (x %d members)" % (updates, updates / max(1e-9, t), self.a.population)
@@ -600,65 +600,99 @@ class RunLog:
         self.file.close()
 
 
-def collect(a, env, learner, elog=None):
-    """The collection loop of every solo run (TRAIN:104-168 for N environments): per launch act -> env.step -> the learner consumes
-    the transition -> episode log -> `--updates` updates once the learner is ready; every --log-every launches RunLog.log().
-    Enqueue-only between log intervals.  elog: the episode log (default: DeviceEpisodeLog on the observation's device)."""
-    obs = env.reset()
-    run = RunLog(a, a.out, elog or DeviceEpisodeLog(obs.device, a.max_csv_rows), (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0, learner)
-    elog = run.elog
-    same = a.reset_mode == "same"
-    resetting = torch.zeros(env.N, dtype=torch.bool, device=obs.device)   # envs whose NEXT launch is their Env.reset
-    all_rows = torch.ones(env.N, dtype=torch.bool, device=obs.device)
-    prev = torch.empty_like(obs)
-    learning = False
-    updates_done = 0
-    late = learner.consume_after_log
-    learner.start(obs, elog)
-    first = 1
-    state_every, resume = getattr(a, "state_every", 0), getattr(a, "resume", None)      # (a Namespace built by hand has neither: Args)
-    stateful = state_every or resume                                   # (--algo td3 --learner fused --reset-mode next: parse_args)
-    if stateful:
-        files = [os.path.join(a.out, learner.csv_name + ".csv")] if a.csv else []
-        loop_tensors = lambda: dict(obs=obs, prev=prev, reward=env.reward, done=env.done, resetting=resetting)
+def open_csv(path, columns):
+    """A CSV file the run appends to; the header goes in while the file is still empty."""
+    f = open(path, "a")
+    if f.tell() == 0:
+        f.write(",".join(columns) + "\n")
+    return f
+
+
+def run_loop(a, side):
+    """The training loop of every run; `side` (SoloSide, PopulationSide) answers what differs.  Per launch side.launch(it) -- act ->
+    step -> record --, then, once side.ready() has turned true (it is not asked again), `--updates` side.learn(n), n = 1, 2, 3 ..., and
+    side.after_updates(); then side.after_launch(it, learning).  Every --log-every launches and at the last one (--time-limit is
+    checked there) side.before_log() and side.runs' log(); at the end side.close() and their finish().  --state-every writes
+    side.state() -> (env handles, loop tensors, extra scalars, files appended to) and side.save_state(dir); --resume is read_state,
+    the side's load_state(dir, scalars), then the loop's three scalars.  Enqueue-only between log intervals.  -> side"""
+    state_every, resume = getattr(a, "state_every", 0), getattr(a, "resume", None)     # (collect() takes Namespaces built by hand, which have neither: Args)
+    first, updates_done, learning = 1, 0, False
     if resume:
         path = resolve_resume(resume)
-        sc = read_state(a, path, [env], loop_tensors(), [run])
-        learner.agent.load_state(os.path.join(path, "agent.npz"))      # (re-packs the actor)
+        sc = read_state(a, path, *side.state()[:2], side.runs)
+        side.load_state(path, sc)
         first, updates_done, learning = int(sc["it"]) + 1, int(sc["updates_done"]), bool(sc["learning"])
     for it in range(first, a.launches + 1):
-        act = learner.act(obs, it)
-        prev.copy_(obs)
-        if same:
-            obs, reward, done = env.step(act, auto_reset="same", want_final=True)
-            keep, nxt = all_rows, env.final_obs
-        else:
-            obs, reward, done = env.step(act, auto_reset="next")
-            keep, nxt = ~resetting, obs
-        if not late:
-            learner.consume(prev, act, reward, nxt, done, keep)
-        if not same:
-            resetting = done.bool()
-        elog.add(done, env.counters(), env.returns()[0], it, keep)
-        if late:
-            learner.consume(prev, act, reward, nxt, done, keep)
+        side.launch(it)
         if not learning:
-            learning = learner.ready()
+            learning = side.ready()
         if learning:
             for u in range(a.updates):
                 updates_done += 1
-                learner.learn(updates_done)
-            learner.after_updates()
-        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - run.t0 > a.time_limit)
+                side.learn(updates_done)
+            side.after_updates()
+        side.after_launch(it, learning)
+        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - side.runs[0].t0 > a.time_limit)
         if it % a.log_every == 0 or last_launch:
-            run.log(it, updates_done)
+            side.before_log()
+            for run in side.runs:
+                run.log(it, updates_done)
         if state_every and it % state_every == 0:
-            write_state(a, it, lambda d: learner.agent.save_state(os.path.join(d, "agent.npz")), [env], dict(loop_tensors(), act=act), [run],
-                        dict(it=it, updates_done=updates_done, learning=learning), files)
+            write_state(a, it, side.save_state, side.runs, dict(it=it, updates_done=updates_done, learning=learning), *side.state())
         if last_launch:
             break
-    run.finish(updates_done)
-    return learner.agent, run.episodes
+    side.close()
+    for run in side.runs:
+        run.finish(updates_done)
+    return side
+
+
+class SoloSide:
+    """One environment handle and one learner (TRAIN:104-168 for N environments): per launch act -> env.step -> the learner consumes
+    the transition -> episode log.  elog: the episode log (default: DeviceEpisodeLog on the observation's device)."""
+    after_launch = before_log = close = staticmethod(lambda *args: None)      # (what follows the updates: a population's business)
+
+    def __init__(self, a, env, learner, elog=None):
+        self.a, self.env, self.learner = a, env, learner
+        self.obs = obs = env.reset()
+        self.runs = [RunLog(a, a.out, elog or DeviceEpisodeLog(obs.device, a.max_csv_rows), (env.cfg.dt_ms + env.cfg.scan_latency_ms) / 1000.0, learner)]
+        self.same, self.late = a.reset_mode == "same", learner.consume_after_log
+        self.resetting = torch.zeros(env.N, dtype=torch.bool, device=obs.device)   # envs whose NEXT launch is their Env.reset
+        self.all_rows = torch.ones(env.N, dtype=torch.bool, device=obs.device)
+        self.prev, self.act = torch.empty_like(obs), None
+        self.ready, self.learn, self.after_updates = learner.ready, getattr(learner, "learn", None), learner.after_updates   # (Tabular: never ready, no learn)
+        self.save_state = lambda d: learner.agent.save_state(os.path.join(d, "agent.npz"))
+        self.load_state = lambda d, scalars: learner.agent.load_state(os.path.join(d, "agent.npz"))      # (re-packs the actor)
+        learner.start(obs, self.runs[0].elog)
+
+    def launch(self, it):
+        env, learner, obs = self.env, self.learner, self.obs
+        act = self.act = learner.act(obs, it)
+        self.prev.copy_(obs)
+        if self.same:
+            obs, reward, done = env.step(act, auto_reset="same", want_final=True)
+            keep, nxt = self.all_rows, env.final_obs
+        else:
+            obs, reward, done = env.step(act, auto_reset="next")
+            keep, nxt = ~self.resetting, obs
+        if not self.late:
+            learner.consume(self.prev, act, reward, nxt, done, keep)
+        if not self.same:
+            self.resetting = done.bool()
+        self.runs[0].elog.add(done, env.counters(), env.returns()[0], it, keep)
+        if self.late:
+            learner.consume(self.prev, act, reward, nxt, done, keep)
+        self.obs = obs
+
+    def state(self):                                                   # (parse_args: --algo td3 --learner fused --reset-mode next)
+        t = dict(obs=self.obs, prev=self.prev, reward=self.env.reward, done=self.env.done, resetting=self.resetting,
+                 **({} if self.act is None else dict(act=self.act)))     # (act: for the record; every launch computes its own)
+        return [self.env], t, {}, [os.path.join(self.a.out, self.learner.csv_name + ".csv")] if self.a.csv else []
+
+
+def collect(a, env, learner, elog=None):
+    """The collection loop of every solo run: run_loop around (env, learner) -> (the learner's agent, finished episodes)."""
+    return learner.agent, run_loop(a, SoloSide(a, env, learner, elog)).runs[0].episodes
 
 
 def train(a):
@@ -691,228 +725,192 @@ def pbt_spread_factors(seed, member, spread):
     return [float(spread) ** (2.0 * ((_mix64(key ^ (8 * member + k)) >> 11) * 2.0 ** -53) - 1.0) for k in range(3)]
 
 
-def train_population(a):
-    """--population P: P independent TD3 runs, seeds a.seed ... a.seed + P - 1, whose updates are ONE cn_td3_pop_update per update
-    (crowdnav.td3.Population) instead of P processes.  Member p has what `train()` with --seed <seed + p> has -- its environment
-    handle of --envs environments, its Agent, replay, RunLog -- and writes what that run writes into
-    <out>/member<p>/.  Per launch: ONE act launch for all members (--population-act one-launch, Population.act; per-member: P
-    act_mfma calls), one grouped environment step (cn_step_multi), ONE record call of two launches for all members' replay writes and
-    episode logs (--population-record one-call, Population.record; per-member: P x (add_masked, counters, returns, log add) and the
-    copies around them); once EVERY member's replay holds more than a batch, --updates population updates and ONE re-pack of the P
-    actors (per-member: P sync_fused_weights, 4 launches each).
-    The two --population-act values give the same run, bit for bit, and so do the two --population-record values.
-    While PBT is off (--pbt-every 0, --pbt-spread 0: the default), member p's run IS the solo run --seed <seed + p> --learner fused
-    (same parameters, same CSV rows) as long as the members' rings pass
-    the batch size on the same launch: a member whose ring is not ready yet (it lost rows to reset launches) holds the others back, so
-    that the update counters -- which key the sampling and drive policy_delay -- stay aligned; from then on that member's solo run
-    would have started its updates earlier.
-    --pbt-every L > 0 (population-based training): after the updates of every L-th launch, once learning has begun, ONE
-    Population.exploit() -- two launches that rank the members by the mean return of the episodes each finished since the last applied
-    call, copy the best members' networks and optimizer state over the worst --pbt-fraction of them, and perturb the hyper-parameters
-    of --pbt-explore by one of --pbt-factor -- then one read of the PBT state (the only host read PBT adds), whose rows go to
-    <out>/pbt_log.csv.  --pbt-spread S > 0 starts member p with lr_actor, lr_critic and noise_std multiplied by a keyed log-uniform
-    factor in [1/S, S]: the sweep PBT then acts on.
-    --eval-every L > 0: after the updates and the re-pack of every L-th launch, ONE evaluation of all members on the device
-    (Population.evaluate: every member's greedy actor in the --eval-scenarios worlds with --eval-seed, --eval-envs environments and
-    --eval-episodes episodes each; three enqueues per evaluation launch for all of them) and one read of its summaries, whose rows go
-    to <out>/eval_log.csv.  It has its own environment and actor handles and draws no noise, so the training run is, bit for bit, the
-    run without it.  --pbt-fitness eval: every exploit is preceded by such an evaluation and ranks by its fitness (--eval-metric)
-    instead of the training episodes' returns.
-    --population-replay shared: every member's update samples the union of all members' rings (Population(replay_source="shared"));
-    the updates begin once the rings together hold more than a batch.  Nothing else in the loop changes: the rings are written and
-    saved per member as before, so --state-every / --resume hold a shared run as they hold any other (give the switch again on
-    --resume, like --replay-sample).  <out>/run.json records the switch.
-    --population-step one-launch: the members' environments step in ONE launch on the loop's stream (MemberEnvs.bind_step_group,
-    cn_step_group_step) instead of one step kernel per member between two rounds of stream waits, and so do the jobs of the bound
-    evaluation; with the one-call recorder the loop is act, step, record with no stream wait at all.  The same run, bit for bit."""
-    fill_defaults(a)
-    dev = a.device
-    P = a.population
-    state_every, resume = getattr(a, "state_every", 0), getattr(a, "resume", None)      # (a Namespace built by hand has neither: Args)
-    replay_source = getattr(a, "population_replay", None) or "own"
-    group_step = (getattr(a, "population_step", None) or "per-member") == "one-launch"
-    torch.cuda.set_device(dev)
-    members = []
-    for p in range(P):
-        m = argparse.Namespace(**vars(a))
-        m.seed, m.out, m.resume = a.seed + p, os.path.join(a.out, "member%d" % p), resume      # (resume: the member's CSV is appended to)
-        members.append(m)
+def build_members(a):
+    """-> (members, envs, agents, pop) of --population P: per member its Namespace (seed + p, <out>/member<p>/), its handle in one
+    MemberEnvs and its Agent; pop: their td3.Population.  --pbt-spread S > 0 starts member p with lr_actor, lr_critic and noise_std
+    multiplied by a keyed log-uniform factor in [1/S, S]: the sweep PBT then acts on.  --population-replay shared: every update
+    samples the union of all members' rings (replay_source="shared") and the updates begin once the rings together hold more than a
+    batch; the rings are written and saved per member as before, so --state-every / --resume hold a shared run as any other (give the
+    switch again on --resume, like --replay-sample).  <out>/run.json records the switches that shape the run."""
+    members = [argparse.Namespace(**dict(vars(a), seed=a.seed + p, out=os.path.join(a.out, "member%d" % p), resume=a.resume))
+               for p in range(a.population)]                          # (resume, by name: the member's CSV is appended to)
     specs = [scenario_config(a.scenario, a.envs, a.max_steps, m.seed, a.ped_vmax, **env_switches(a)) for m in members]
-    envs = MemberEnvs([sp[0] for sp in specs], dev)
+    envs = MemberEnvs([sp[0] for sp in specs], a.device)
     for e, (_, init, vel) in zip(envs.envs, specs):
         if init is not None:
             e.set_ped_init(init)
         if vel is not None:
             e.set_ped_preset_vel(vel)
     spread = [{} for _ in members]
-    if a.pbt_spread > 0:
-        for p, m in enumerate(members):
-            f = pbt_spread_factors(a.seed, p, a.pbt_spread)
-            m.lr_actor, m.lr_critic = (a.lr_actor or 3e-4) * f[0], (a.lr_critic or 3e-4) * f[1]
-            spread[p] = dict(noise_std=0.2 * f[2])
-    agents = [make_agent(m, envs.D, "cuda:%d" % dev, memory_size=a.memory, actor_final_init=a.actor_final_init, **kw) for m, kw in zip(members, spread)]
-    pop = td3.Population(agents, replay_source=replay_source)
+    for p, m in enumerate(members if a.pbt_spread > 0 else []):
+        f = pbt_spread_factors(a.seed, p, a.pbt_spread)
+        m.lr_actor, m.lr_critic = (a.lr_actor or 3e-4) * f[0], (a.lr_critic or 3e-4) * f[1]
+        spread[p] = dict(noise_std=0.2 * f[2])
+    agents = [make_agent(m, envs.D, "cuda:%d" % a.device, memory_size=a.memory, actor_final_init=a.actor_final_init, **kw) for m, kw in zip(members, spread)]
+    pop = td3.Population(agents, replay_source=a.population_replay)
     os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, "run.json"), "w") as f:             # the switches that shape a population's run
-        json.dump(dict(population=P, population_replay=replay_source, population_act=a.population_act, population_record=a.population_record,
-                       population_step="one-launch" if group_step else "per-member", replay_sample=a.replay_sample), f, indent=1, sort_keys=True)
+    with open(os.path.join(a.out, "run.json"), "w") as f:
+        json.dump({k: getattr(a, k) for k in ("population", "population_replay", "population_act", "population_record", "population_step",
+                                              "replay_sample")}, f, indent=1, sort_keys=True)
         f.write("\n")
-    act = torch.zeros((envs.N, 2), dtype=torch.float32, device=envs.device)
-    step_all = envs.bind_step_group(act, auto_reset="next") if group_step else envs.bind_step_all(act, auto_reset="next")
-    obs = envs.reset(group=group_step)                                 # (one-launch: the reset is the group's, one launch too)
-    step_s = (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0
-    runs = [RunLog(m, m.out, DeviceEpisodeLog(obs.device, a.max_csv_rows), step_s, Member(m, ag), prefix="member %2d  " % p)
-            for p, (m, ag) in enumerate(zip(members, agents))]
-    t0 = runs[0].t0
-    N, rows = envs.N, [envs.rows(p) for p in range(P)]
-    resetting = torch.zeros(N, dtype=torch.bool, device=obs.device)
-    prev = torch.empty_like(obs)
-    elogs = [r.elog for r in runs]
-    learning = False
-    updates_done = 0
-    one_launch = a.population_act == "one-launch"
-    if one_launch:
-        pop.bind_act([obs[r] for r in rows], [act[r] for r in rows])      # (packs the actors)
-    else:
-        for ag in agents:
-            ag.sync_fused_weights()
-    reward, done = envs.reward, envs.done
-    one_call = a.population_record == "one-call"
-    if one_call:
-        prev.copy_(obs)                                                # once: every record() leaves the new observation in prev
-        pop.bind_record(envs.envs, *[[x[r] for r in rows] for x in (prev, obs, act, reward, done)], elogs)
-    if a.pbt_every:
-        # the logs' totals restart at every flush; PBT ranks on totals that never do: what was flushed so far + the running ones
-        pbt_flushed = torch.zeros((P, 5), dtype=torch.float64, device=obs.device)
-        pbt_tot = torch.zeros((P, 5), dtype=torch.float64, device=obs.device)
-        pop.bind_pbt(a.pbt_n_replace, factor=a.pbt_factor, explore=a.pbt_explore, min_episodes=a.pbt_min_episodes, seed=a.seed,
-                     elogs=[argparse.Namespace(rows=e.rows, max_rows=e.max_rows, n=e.n, tot=pbt_tot[p]) for p, e in enumerate(elogs)])
-        pbt_applied = 0
-        os.makedirs(a.out, exist_ok=True)
-        pbt_csv = open(os.path.join(a.out, "pbt_log.csv"), "a")
-        if pbt_csv.tell() == 0:
-            pbt_csv.write(",".join(PBT_CSV_COLUMNS) + "\n")
-    eval_fitness = bool(a.pbt_every) and a.pbt_fitness == "eval"
-    eval_csv, eval_runs, eval_seconds = None, 0, 0.0
-    if a.eval_every or eval_fitness:
-        # the same worlds with the same seed for every member: job (p, w) is member p's greedy actor in world w, on its own handle
-        pop.bind_eval([scenario_config(s, a.eval_envs, a.eval_max_steps, a.eval_seed, a.ped_vmax, **env_switches(a)) for s in a.eval_scenarios],
-                      quota=a.eval_episodes, metric=a.eval_metric, step="group" if group_step else "multi")
-        os.makedirs(a.out, exist_ok=True)
-        eval_csv = open(os.path.join(a.out, "eval_log.csv"), "a")
-        if eval_csv.tell() == 0:
-            eval_csv.write(",".join(EVAL_CSV_COLUMNS) + "\n")
+    return members, envs, agents, pop
 
-    def evaluate_population(it):
-        """One evaluation of all members -> their fitness [P] on the device; the summaries' rows go to eval_log.csv (the one host read)."""
-        nonlocal eval_runs, eval_seconds
+
+class Pbt:
+    """--pbt-every L > 0 (population-based training): after the updates of every L-th launch, once learning has begun, ONE
+    Population.exploit() -- two launches that rank the members by the mean return of the episodes each finished since the last applied
+    call, copy the best members' networks and optimizer state over the worst --pbt-fraction of them, and perturb the hyper-parameters
+    of --pbt-explore by one of --pbt-factor -- then one read of the PBT state (the only host read PBT adds), rows to <out>/pbt_log.csv.
+    The logs' totals restart at every flush; PBT ranks on totals that never do: what was flushed so far + the running ones."""
+
+    def __init__(self, a, pop, elogs, sync_unbound):
+        self.pop, self.elogs, self.sync_unbound, self.applied, self.path = pop, elogs, sync_unbound, 0, os.path.join(a.out, "pbt_log.csv")
+        self.flushed, self.tot = (torch.zeros((len(elogs), 5), dtype=torch.float64, device=elogs[0].tot.device) for _ in range(2))
+        pop.bind_pbt(a.pbt_n_replace, factor=a.pbt_factor, explore=a.pbt_explore, min_episodes=a.pbt_min_episodes, seed=a.seed,
+                     elogs=[argparse.Namespace(rows=e.rows, max_rows=e.max_rows, n=e.n, tot=self.tot[p]) for p, e in enumerate(elogs)])
+        open_csv(self.path, PBT_CSV_COLUMNS).close()                   # (a run without an applied exploit leaves the header)
+
+    def exploit(self, it, fitness):
+        torch.add(self.flushed, torch.stack([e.tot for e in self.elogs]), out=self.tot)
+        self.pop.exploit(fitness)                                      # (re-packs the bound actors)
+        self.sync_unbound()
+        st = self.pop.pbt_state()                                      # the one host read PBT adds: once per --pbt-every launches
+        if st["applied"] > self.applied:
+            self.applied = st["applied"]
+            with open_csv(self.path, PBT_CSV_COLUMNS) as f:
+                for p, m in enumerate(st["members"]):
+                    f.write(",".join(["%d" % it, "%d" % (st["calls"] - 1), "%d" % p, "%d" % m["src"], "%d" % m["generation"]] +
+                                     ["%.9g" % m[k] for k in PBT_CSV_COLUMNS[5:]]) + "\n")
+
+    def before_log(self):
+        self.flushed.add_(torch.stack([e.tot for e in self.elogs]))     # (RunLog.log flushes: the totals restart)
+
+
+class Evaluation:
+    """--eval-every L > 0: after the updates and the re-pack of every L-th launch, ONE evaluation of all members on the device
+    (Population.evaluate: every member's greedy actor in the --eval-scenarios worlds with --eval-seed, --eval-envs environments and
+    --eval-episodes episodes each, job (p, w) on its own handle; three enqueues per evaluation launch for all of them) and one read of
+    its summaries, whose rows go to <out>/eval_log.csv.  It has its own environment and actor handles and draws no noise, so the
+    training run is, bit for bit, the run without it.  --pbt-fitness eval: every exploit is preceded by such an evaluation and ranks
+    by its fitness (--eval-metric) instead of the training episodes' returns."""
+
+    def __init__(self, a, pop, step):
+        self.pop, self.worlds, self.runs, self.seconds, self.path = pop, a.eval_scenarios, 0, 0.0, os.path.join(a.out, "eval_log.csv")
+        pop.bind_eval([scenario_config(s, a.eval_envs, a.eval_max_steps, a.eval_seed, a.ped_vmax, **env_switches(a)) for s in a.eval_scenarios],
+                      quota=a.eval_episodes, metric=a.eval_metric, step=step)
+        open_csv(self.path, EVAL_CSV_COLUMNS).close()
+
+    def run(self, it):
         t = time.time()
-        fitness = pop.evaluate()
-        for j, row in enumerate(pop.evaluator().summary().tolist()):
-            eval_csv.write(",".join(["%d" % it, "%d" % (j // len(a.eval_scenarios)), a.eval_scenarios[j % len(a.eval_scenarios)]] +
-                                    ["%.9g" % v for v in row]) + "\n")
-        eval_csv.flush()
-        eval_runs, eval_seconds = eval_runs + 1, eval_seconds + time.time() - t
+        fitness = self.pop.evaluate()                                  # [P], on the device; the summary below is the one host read
+        with open_csv(self.path, EVAL_CSV_COLUMNS) as f:
+            for j, row in enumerate(self.pop.evaluator().summary().tolist()):
+                f.write(",".join(["%d" % it, "%d" % (j // len(self.worlds)), self.worlds[j % len(self.worlds)]] + ["%.9g" % v for v in row]) + "\n")
+        self.runs, self.seconds = self.runs + 1, self.seconds + time.time() - t
         return fitness
 
-    first = 1
-    stateful = state_every or resume                                   # (parse_args: not with an evaluation's handles)
-    if stateful:
-        files = [os.path.join(m.out, r.learner.csv_name + ".csv") for m, r in zip(members, runs)] if a.csv else []
-        files += [os.path.join(a.out, "pbt_log.csv")] if a.pbt_every else []
-
-        def loop_tensors():
-            t = dict(obs=obs, prev=prev, act=act, reward=reward, done=done, resetting=resetting)
-            t.update({"record_resetting%d" % p: pop.resetting(p) for p in range(P)} if one_call else {})
-            t.update(dict(pbt_flushed=pbt_flushed, pbt_tot=pbt_tot) if a.pbt_every else {})
-            return t
-    if resume:
-        path = resolve_resume(resume)
-        sc = read_state(a, path, envs.envs, loop_tensors(), runs)
-        pop.load_state(path)                                           # (re-packs the bound actors; the agents' hyper-parameters follow)
-        if not one_launch:
-            for ag in agents:
-                ag.sync_fused_weights()
-        first, updates_done, learning = int(sc["it"]) + 1, int(sc["updates_done"]), bool(sc["learning"])
-        pbt_applied = int(sc["pbt_applied"]) if a.pbt_every else 0
-    for it in range(first, a.launches + 1):
-        if one_launch:
-            pop.act(add_noise=True)
-        else:
-            for ag, r in zip(agents, rows):
-                ag.act_mfma(obs[r], out=act[r], add_noise=True)
-        if one_call and group_step:
-            step_all()                                                 # one launch on this stream: no wait before it, none behind it
-            pop.record(it)
-        elif one_call:
-            envs.fork()                                                # the members' steps wait for the actions ...
-            step_all()
-            envs.join()                                                # ... and everything below for the steps
-            pop.record(it)
-        else:
-            prev.copy_(obs)
-            if group_step:
-                step_all()
-            envs.fork()                                                # (one-launch: the members' streams wait for the step)
-            if not group_step:
-                step_all()
-            cnt = [e.counters() for e in envs.envs]
-            ret = [e.returns()[0] for e in envs.envs]
-            envs.join()
-            keep = ~resetting
-            for p, (ag, r) in enumerate(zip(agents, rows)):
-                ag.memory.add_masked(prev[r], act[r], reward[r], obs[r], done[r], keep[r])
-                elogs[p].add(done[r], cnt[p], ret[p], it, keep[r])
-            resetting = done.bool()
-        if not learning:
-            learning = pop.ready()                                     # all members start together: the update counters stay aligned
-        if learning:
-            for u in range(a.updates):
-                updates_done += 1
-                pop.learn(updates_done)
-            if one_launch:
-                pop.sync_actors()
-            else:
-                for ag in agents:
-                    ag.sync_fused_weights()
-        exploiting = learning and a.pbt_every and it % a.pbt_every == 0
-        fitness = None
-        if (a.eval_every and it % a.eval_every == 0) or (exploiting and eval_fitness):
-            fitness = evaluate_population(it)                          # after the updates and the re-pack; its own handles and no noise draw
-        if exploiting:
-            torch.add(pbt_flushed, torch.stack([e.tot for e in elogs]), out=pbt_tot)
-            pop.exploit(fitness if eval_fitness else None)             # (re-packs the bound actors)
-            if not one_launch:
-                for ag in agents:
-                    ag.sync_fused_weights()
-            st = pop.pbt_state()                                       # the one host read PBT adds: once per --pbt-every launches
-            if st["applied"] > pbt_applied:
-                pbt_applied = st["applied"]
-                for p, m in enumerate(st["members"]):
-                    pbt_csv.write(",".join(["%d" % it, "%d" % (st["calls"] - 1), "%d" % p, "%d" % m["src"], "%d" % m["generation"]] +
-                                           ["%.9g" % m[k] for k in PBT_CSV_COLUMNS[5:]]) + "\n")
-                pbt_csv.flush()
-        last_launch = it == a.launches or (a.time_limit and it % a.log_every == 0 and time.time() - t0 > a.time_limit)
-        if it % a.log_every == 0 or last_launch:
-            if a.pbt_every:
-                pbt_flushed.add_(torch.stack([e.tot for e in elogs]))     # (RunLog.log flushes: the totals restart)
-            for run in runs:
-                run.log(it, updates_done)
-        if state_every and it % state_every == 0:
-            write_state(a, it, pop.save_state, envs.envs, loop_tensors(), runs,
-                        dict(it=it, updates_done=updates_done, learning=learning, pbt_applied=pbt_applied if a.pbt_every else 0), files)
-        if last_launch:
-            break
-    if a.pbt_every:
-        pbt_csv.close()
-    if eval_csv is not None:
-        eval_csv.close()
+    def close(self, t0):
         print("evaluation: %d runs of %d jobs, %.1f s of %.1f s (host clock, from the first enqueue to the summary's read)"
-              % (eval_runs, len(pop.evaluator().jobs), eval_seconds, time.time() - t0))
-        pop.evaluator().close()
-    for run in runs:
-        run.finish(updates_done)
-    return agents, [run.episodes for run in runs]
+              % (self.runs, len(self.pop.evaluator().jobs), self.seconds, time.time() - t0))
+        self.pop.evaluator().close()
+
+
+class PopulationSide:
+    """What build_members built, bound for run_loop: every switch is resolved here, once, into the calls a launch makes, and the two
+    values of each give the same run, bit for bit.  --population-act one-launch: ONE act launch for all members (Population.act) and
+    ONE re-pack of the P actors (sync_actors); per-member: P act_mfma calls and P sync_fused_weights, 4 launches each.
+    --population-record one-call: ONE record call of two launches for all members' replay writes and episode logs (Population.record);
+    per-member: P x (add_masked, counters, returns, log add) and the copies around them.  --population-step per-member: one grouped
+    step (cn_step_multi), a kernel per member on its stream between two rounds of stream waits; one-launch: ONE launch on the loop's
+    stream (MemberEnvs.bind_step_group, cn_step_group_step), for the jobs of the bound evaluation too.  The start gate: the updates
+    begin once EVERY member's replay holds more than a batch -- a member whose ring is not ready yet (it lost rows to reset launches)
+    holds the others back, so that the update counters, which key the sampling and drive policy_delay, stay aligned."""
+
+    def __init__(self, a, members, envs, agents, pop):
+        self.a, self.envs, self.agents, self.pop = a, envs, agents, pop
+        group_step, self.one_call = a.population_step == "one-launch", a.population_record == "one-call"
+        self.act = act = torch.zeros((envs.N, 2), dtype=torch.float32, device=envs.device)
+        step_all = envs.bind_step_group(act, auto_reset="next") if group_step else envs.bind_step_all(act, auto_reset="next")
+        self.obs = obs = envs.reset(group=group_step)                  # (one-launch: the reset is the group's, one launch too)
+        self.runs = [RunLog(m, m.out, DeviceEpisodeLog(obs.device, a.max_csv_rows), (envs.cfg.dt_ms + envs.cfg.scan_latency_ms) / 1000.0, Member(m, ag),
+                            prefix="member %2d  " % p) for p, (m, ag) in enumerate(zip(members, agents))]
+        self.rows = rows = [envs.rows(p) for p in range(len(agents))]
+        self.resetting = torch.zeros(envs.N, dtype=torch.bool, device=obs.device)
+        self.prev = prev = torch.empty_like(obs)
+        self.elogs = [r.elog for r in self.runs]
+        if a.population_act == "one-launch":
+            pop.bind_act([obs[r] for r in rows], [act[r] for r in rows])  # (packs the actors)
+            act_all, self.sync_all, self.sync_unbound = (lambda: pop.act(add_noise=True)), pop.sync_actors, (lambda: None)
+        else:
+            act_all = lambda: [ag.act_mfma(obs[r], out=act[r], add_noise=True) for ag, r in zip(agents, rows)]
+            self.sync_all = self.sync_unbound = lambda: [ag.sync_fused_weights() for ag in agents]    # (unbound: those Population does not re-pack itself)
+            self.sync_all()
+        keep_prev = lambda: prev.copy_(obs)
+        if self.one_call:
+            keep_prev()                                                # once: every record() leaves the new observation in prev
+            pop.bind_record(envs.envs, *[[x[r] for r in rows] for x in (prev, obs, act, envs.reward, envs.done)], self.elogs)
+        # a launch: these calls, then record(it).  fork: the members' streams wait for the loop's (the actions, or the group's step);
+        # join: the loop's waits for theirs (record_members joins after its reads on their streams)
+        self.calls = [act_all] + {(True, True): [step_all],            # one launch on this stream: no wait before it, none behind it
+                                  (True, False): [envs.fork, step_all, envs.join],
+                                  (False, True): [keep_prev, step_all, envs.fork],
+                                  (False, False): [keep_prev, envs.fork, step_all]}[self.one_call, group_step]
+        self.record = pop.record if self.one_call else self.record_members
+        self.pbt = Pbt(a, pop, self.elogs, self.sync_unbound) if a.pbt_every else None
+        self.eval_fitness = bool(a.pbt_every) and a.pbt_fitness == "eval"
+        self.evaluation = Evaluation(a, pop, "group" if group_step else "multi") if a.eval_every or self.eval_fitness else None
+        self.ready, self.learn, self.after_updates, self.save_state = pop.ready, pop.learn, self.sync_all, pop.save_state
+        self.before_log = self.pbt.before_log if self.pbt else (lambda: None)
+        self.close = (lambda: self.evaluation.close(self.runs[0].t0)) if self.evaluation else (lambda: None)
+
+    def launch(self, it):
+        for call in self.calls:
+            call()
+        self.record(it)
+
+    def record_members(self, it):
+        envs, reward, done = self.envs, self.envs.reward, self.envs.done
+        cnt = [e.counters() for e in envs.envs]
+        ret = [e.returns()[0] for e in envs.envs]
+        envs.join()
+        keep = ~self.resetting
+        for p, (ag, r) in enumerate(zip(self.agents, self.rows)):
+            ag.memory.add_masked(self.prev[r], self.act[r], reward[r], self.obs[r], done[r], keep[r])
+            self.elogs[p].add(done[r], cnt[p], ret[p], it, keep[r])
+        self.resetting = done.bool()
+
+    def after_launch(self, it, learning):                              # the evaluation, if due or if the exploit ranks by it; then the exploit
+        exploiting = learning and self.a.pbt_every and it % self.a.pbt_every == 0
+        due = (self.a.eval_every and it % self.a.eval_every == 0) or (exploiting and self.eval_fitness)
+        fitness = self.evaluation.run(it) if due else None             # (its own handles and no noise draw)
+        if exploiting:
+            self.pbt.exploit(it, fitness if self.eval_fitness else None)
+
+    def state(self):                                                   # (parse_args: not with an evaluation's handles)
+        t = dict(obs=self.obs, prev=self.prev, act=self.act, reward=self.envs.reward, done=self.envs.done, resetting=self.resetting)
+        t.update({"record_resetting%d" % p: self.pop.resetting(p) for p in range(len(self.agents))} if self.one_call else {})
+        t.update(dict(pbt_flushed=self.pbt.flushed, pbt_tot=self.pbt.tot) if self.pbt else {})
+        files = [os.path.join(r.out, r.learner.csv_name + ".csv") for r in self.runs] if self.a.csv else []
+        return self.envs.envs, t, dict(pbt_applied=self.pbt.applied if self.pbt else 0), files + ([self.pbt.path] if self.pbt else [])
+
+    def load_state(self, d, scalars):
+        self.pop.load_state(d)                                         # (re-packs the bound actors; the agents' hyper-parameters follow)
+        self.sync_unbound()
+        if self.pbt:
+            self.pbt.applied = int(scalars["pbt_applied"])
+
+
+def train_population(a):
+    """--population P: P independent TD3 runs, seeds a.seed ... a.seed + P - 1, whose updates are ONE cn_td3_pop_update per update
+    (crowdnav.td3.Population) instead of P processes.  Member p has what `train()` with --seed <seed + p> has -- its environment
+    handle of --envs environments, its Agent, replay, RunLog -- and writes what that run writes into <out>/member<p>/.  While PBT is
+    off (--pbt-every 0, --pbt-spread 0: the default), member p's run IS the solo run --seed <seed + p> --learner fused (same parameters,
+    same CSV rows) as long as the members' rings pass the batch size on the same launch (PopulationSide's start gate); from then on a
+    member that was held back would, solo, have started its updates earlier."""
+    fill_defaults(a)
+    torch.cuda.set_device(a.device)
+    side = run_loop(a, PopulationSide(a, *build_members(a)))
+    return side.agents, [run.episodes for run in side.runs]
 
 
 def report_evaluation(a, scenario, st):

@@ -333,25 +333,14 @@ SWITCHES = ["--algo", "td3", "--learner", "fused", "--scenario", "training_as_lo
             "--max-steps", "9", "--memory", "64", "--batch", "8", "--population", "3", "--seed", "31"]
 
 
-def _side():
-    """P = 3 members of 4 environments as train_population builds them: environments, agents, the one-launch actor, episode logs."""
-    from crowdnav import td3, train
-    a = train.parse_args(SWITCHES)
+def _side(out):
+    """P = 3 members of 4 environments as train_population builds them (train.build_members): environments, agents, the one-launch
+    actor, episode logs."""
+    from crowdnav import train
+    a = train.parse_args(SWITCHES + ["--out", str(out)])
     train.fill_defaults(a)
     P = a.population
-    specs = [train.scenario_config(a.scenario, a.envs, a.max_steps, a.seed + p, a.ped_vmax, **train.env_switches(a)) for p in range(P)]
-    envs = train.MemberEnvs([sp[0] for sp in specs], 0)
-    for e, (_, init, vel) in zip(envs.envs, specs):
-        if init is not None:
-            e.set_ped_init(init)
-        if vel is not None:
-            e.set_ped_preset_vel(vel)
-    agents = []
-    for p in range(P):
-        a.seed += p
-        agents.append(train.make_agent(a, envs.D, "cuda:0", memory_size=a.memory, actor_final_init=a.actor_final_init))
-        a.seed -= p
-    pop = td3.Population(agents)
+    _, envs, agents, pop = train.build_members(a)
     obs = envs.reset()
     rows = [envs.rows(p) for p in range(P)]
     act = torch.zeros((envs.N, 2), dtype=torch.float32, device=obs.device)
@@ -361,11 +350,11 @@ def _side():
                 step_all=envs.bind_step_all(act, auto_reset="next"))
 
 
-def test_real_environments_forty_launches_against_the_per_member_path():
+def test_real_environments_forty_launches_against_the_per_member_path(tmp_path):
     """Twin handles of the same seeds: act, step, then one side records with Population.record and the other with the per-member
     sequence train_population ran before (prev.copy_, P x (add_masked, counters, returns, log add), ~resetting, done.bool()).  Rings,
     logs and the flushed rows are equal; episodes ended and reset launches were left out, so both branches ran."""
-    one, per = _side(), _side()
+    one, per = _side(tmp_path / "one"), _side(tmp_path / "per")
     P = 3
     one["prev"].copy_(one["obs"])
     one["pop"].bind_record(one["envs"].envs, *[[x[r] for r in one["rows"]] for x in
