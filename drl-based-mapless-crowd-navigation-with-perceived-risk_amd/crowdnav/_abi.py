@@ -49,6 +49,8 @@ EXPORTS = ["cn_abi_version", "cn_last_error", "cn_create", "cn_destroy", "cn_obs
            "cn_actor_pop_create", "cn_actor_pop_destroy", "cn_actor_pop_members", "cn_actor_pop_pack", "cn_actor_pop_forward",
            "cn_actor_pop_weights",
            "cn_pop_record_create", "cn_pop_record_destroy", "cn_pop_record_members", "cn_pop_record_resetting", "cn_pop_record",
+           "cn_nstep_record_create", "cn_nstep_record_destroy", "cn_nstep_record_members", "cn_nstep_record_resetting",
+           "cn_nstep_record_pending", "cn_nstep_record", "cn_nstep_discount",
            "cn_eval_create", "cn_eval_destroy", "cn_eval_jobs", "cn_eval_reset", "cn_eval_record", "cn_eval_finish", "cn_eval_state_dev",
            "cn_step_group_create", "cn_step_group_step", "cn_step_group_reset", "cn_step_group_jobs", "cn_step_group_kernel_name",
            "cn_step_group_destroy"]
@@ -60,6 +62,7 @@ EVAL_METRIC = {"success": CN_EVAL_SUCCESS_RATE, "return": CN_EVAL_MEAN_RETURN}
 CN_TD3_POP_MAX = 64         # include/crowdnav.h: cn_td3_pop_create's n_members is 1 ... 64
 CN_ACTOR_POP_MAX = 64       # include/crowdnav.h: cn_actor_pop_create's n_members is 1 ... 64
 CN_POP_RECORD_MAX = 64      # include/crowdnav.h: cn_pop_record_create's n_members is 1 ... 64
+CN_NSTEP_MAX = 16           # include/crowdnav.h: cn_nstep_record_create's n_step is 1 ... 16
 CN_PBT_HYPER_NAMES = ("lr_actor", "lr_critic", "gamma", "noise_std", "noise_clip")      # include/crowdnav.h: CN_PBT_LR_ACTOR ... in order
 CN_PBT_HYPERS = len(CN_PBT_HYPER_NAMES)
 CN_STATE_MAGIC, CN_STATE_VERSION, CN_STATE_FAMILY_TD3 = 0x0045544154534E43, 1, 1      # include/crowdnav.h: cn_state_header
@@ -313,6 +316,17 @@ class CnPopRecordMember(C.Structure):
                 ("n", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CnNstepMember(C.Structure):
+    """Mirror of `cn_nstep_member` (include/crowdnav.h): one member of cn_nstep_record_create."""
+    _fields_ = [("rec", CnPopRecordMember), ("gamma", C.c_float), ("reserved_f", C.c_float)]
+
+
+class CnNstepPending(C.Structure):
+    """Mirror of `cn_nstep_pending` (include/crowdnav.h): a member's pending store, device pointers owned by the handle."""
+    _fields_ = [("s", C.c_void_p), ("a", C.c_void_p), ("ret", C.c_void_p), ("count", C.c_void_p), ("clock", C.c_void_p),
+                ("n", C.c_int32), ("n_step", C.c_int32), ("obs_dim", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CnEvalJob(C.Structure):
     """Mirror of `cn_eval_job` (include/crowdnav.h): one job of cn_eval_create."""
     _fields_ = [("env", C.c_void_p), ("counters", C.c_void_p), ("last_return", C.c_void_p), ("done", C.c_void_p), ("log", CnEpisodeLog),
@@ -474,6 +488,13 @@ def lib():
         L.cn_pop_record_members.argtypes = [vp]
         L.cn_pop_record_resetting.argtypes = [vp, C.c_int]; L.cn_pop_record_resetting.restype = vp
         L.cn_pop_record.argtypes = [vp, C.c_float, vp]
+        L.cn_nstep_record_create.argtypes = [C.POINTER(CnNstepMember), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.cn_nstep_record_destroy.argtypes = [vp]; L.cn_nstep_record_destroy.restype = None
+        L.cn_nstep_record_members.argtypes = [vp]
+        L.cn_nstep_record_resetting.argtypes = [vp, C.c_int]; L.cn_nstep_record_resetting.restype = vp
+        L.cn_nstep_record_pending.argtypes = [vp, C.c_int, C.POINTER(CnNstepPending)]
+        L.cn_nstep_record.argtypes = [vp, C.c_float, vp]
+        L.cn_nstep_discount.argtypes = [C.c_float, C.c_int]; L.cn_nstep_discount.restype = C.c_float
         L.cn_eval_create.argtypes = [C.POINTER(CnEvalJob), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]      # an array of jobs
         L.cn_eval_destroy.argtypes = [vp]; L.cn_eval_destroy.restype = None
         L.cn_eval_jobs.argtypes = [vp]

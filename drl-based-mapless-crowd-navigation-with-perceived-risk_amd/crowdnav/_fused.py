@@ -287,6 +287,7 @@ class FusedPopulationRecorder:
     """Owns one cn_pop_record handle: every member's replay write and episode log as two launches (include/crowdnav.h,
     cn_pop_record_create).  members: the CnPopRecordMember of every member, in member order; keep: whatever their pointers point into
     (the handle holds them for its lifetime).  Errors raise CrowdNavError("<function>: <cn_last_error>")."""
+    _prefix = "cn_pop_record"
 
     def __init__(self, members, obs_dim, device, dev_index, keep=None):
         self._L = L = _abi.lib()
@@ -295,21 +296,27 @@ class FusedPopulationRecorder:
         self.h = C.c_void_p()
         self._check("_create", L.cn_pop_record_create(self.members, self.P, self.obs_dim, dev_index, C.byref(self.h)))
 
+    def _fn(self, what):
+        return getattr(self._L, self._prefix + what)
+
     def _check(self, what, rc):
         if rc != 0:
-            raise _abi.CrowdNavError("cn_pop_record%s: %s" % (what, self._L.cn_last_error().decode()))
+            raise _abi.CrowdNavError("%s%s: %s" % (self._prefix, what, self._L.cn_last_error().decode()))
+
+    def _rows(self, member):
+        return int(self.members[int(member)].n)
 
     def record(self, launch):
         """cn_pop_record on torch's current stream: at most two launches; `launch` is the index the finished episodes' rows carry."""
-        self._check("", self._L.cn_pop_record(self.h, float(launch), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._check("", self._fn("")(self.h, float(launch), C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
     def resetting(self, member):
         """A uint8 view [n_member] of the handle's flags of `member` (cn_pop_record_resetting), alive as long as the handle: row i's
         next record is its environment's reset launch, not a transition."""
-        ptr = self._L.cn_pop_record_resetting(self.h, int(member))
+        ptr = self._fn("_resetting")(self.h, int(member))
         if not ptr:
-            raise _abi.CrowdNavError("cn_pop_record_resetting: %s" % self._L.cn_last_error().decode())
-        n = int(self.members[int(member)].n)
+            raise _abi.CrowdNavError("%s_resetting: %s" % (self._prefix, self._L.cn_last_error().decode()))
+        n = self._rows(member)
         if n == 0:
             return torch.zeros(0, dtype=torch.uint8, device=self.device)
 
@@ -320,10 +327,39 @@ class FusedPopulationRecorder:
     def __del__(self):
         try:
             if self.h:
-                self._L.cn_pop_record_destroy(self.h)
+                self._fn("_destroy")(self.h)
                 self.h = None
         except Exception:
             pass
+
+
+class FusedNStepRecorder(FusedPopulationRecorder):
+    """Owns one cn_nstep_record handle: FusedPopulationRecorder's job with n-step rows (include/crowdnav.h, cn_nstep_record_create).
+    members: the CnNstepMember of every member (its CnPopRecordMember and its one-step gamma), in member order; n_step: the window,
+    one for all.  record(launch) is cn_nstep_record, resetting(member) the handle's flags; pending(member) its pending store."""
+    _prefix = "cn_nstep_record"
+    PENDING = ("s", "a", "ret", "count", "clock")
+
+    def __init__(self, members, n_step, obs_dim, device, dev_index, keep=None):
+        self._L = L = _abi.lib()
+        self.device, self.P, self.n_step, self.obs_dim, self._keep = device, len(members), int(n_step), int(obs_dim), keep
+        self.members = (_abi.CnNstepMember * self.P)(*members)
+        self.h = C.c_void_p()
+        self._check("_create", L.cn_nstep_record_create(self.members, self.P, self.n_step, self.obs_dim, dev_index, C.byref(self.h)))
+
+    def _rows(self, member):
+        return int(self.members[int(member)].rec.n)
+
+    def pending(self, member):
+        """Views (s [n, W, obs_dim], a [n, W, 2], ret [n, W] float32; count [n], clock [n] int32) of `member`'s pending store
+        (cn_nstep_record_pending), alive as long as the handle; with resetting(member) they are the handle's whole state."""
+        pd = _abi.CnNstepPending()
+        self._check("_pending", self._L.cn_nstep_record_pending(self.h, int(member), C.byref(pd)))
+        n, W, D = int(pd.n), int(pd.n_step), int(pd.obs_dim)
+        shapes = (((n, W, D), torch.float32), ((n, W, 2), torch.float32), ((n, W), torch.float32), ((n,), torch.int32), ((n,), torch.int32))
+        if n == 0:
+            return tuple(torch.zeros(sh, dtype=dt, device=self.device) for sh, dt in shapes)
+        return tuple(_device_view(getattr(pd, k), sh, dt, self.device) for k, (sh, dt) in zip(self.PENDING, shapes))
 
 
 class FusedEvaluator:

@@ -339,7 +339,7 @@ class Agent(FusedActorMixin):
 
     def __init__(self, obs_dim=398, hidden=256, actor_lr=3e-4, critic_lr=3e-4, batch_size=128, memory_size=1_000_000,
                  gamma=0.99, tau=0.005, max_v=0.22, max_w=2.0, noise_std=0.2, noise_clip=0.5, policy_delay=2,
-                 explore_sigma=1.0, device="cuda", seed=0, actor_final_init=None, replay_sample="with"):
+                 explore_sigma=1.0, device="cuda", seed=0, actor_final_init=None, replay_sample="with", n_step=1):
         from . import _abi
         _abi.replay_sample_mode(replay_sample)      # "with" (replacement) | "without" (distinct rows, the reference's random.sample)
         self.replay_sample = replay_sample
@@ -365,11 +365,25 @@ class Agent(FusedActorMixin):
         self.opt_q2 = torch.optim.Adam(self.q2.parameters(), lr=critic_lr, **kw)
         self.memory = DeviceReplay(memory_size, obs_dim, self.device)
         self.batch_size, self.gamma, self.tau = batch_size, gamma, tau
+        # n_step = W > 1: the replay holds W-step rows (an n-step recorder: Population.bind_record(n_step=W), cn_nstep_record), so the
+        # target bootstraps with the recorder's gamma^W; gamma stays the one-step discount
+        if not 1 <= int(n_step) <= _abi.CN_NSTEP_MAX:
+            raise ValueError("n_step must be 1 ... %d, not %r" % (_abi.CN_NSTEP_MAX, n_step))
+        self.n_step = int(n_step)
         self.max_v, self.max_w = max_v, max_w
         self.noise_std, self.noise_clip, self.policy_delay = noise_std, noise_clip, policy_delay
         self.explore_sigma = explore_sigma
         self.gen = torch.Generator(device=self.device).manual_seed(seed)
         self._init_fused_actor(seed)
+
+    @property
+    def bootstrap_gamma(self):
+        """The discount on the target critics' value: gamma itself for one-step rows, cn_nstep_discount(gamma, n_step) -- the n-step
+        recorder's own gamma^n_step, float64 products cast once -- for n-step rows."""
+        if self.n_step == 1:
+            return self.gamma
+        from . import _abi
+        return float(_abi.lib().cn_nstep_discount(self.gamma, self.n_step))
 
     @torch.no_grad()
     def act(self, obs, add_noise=True):
@@ -385,7 +399,7 @@ class Agent(FusedActorMixin):
             noise = (target_noise * self.noise_std).clamp(-self.noise_clip, self.noise_clip)
             a2 = self.actor_t(s2) + noise                       # not re-clipped to the action bounds (TD3:244-247)
             q_t = torch.min(self.q1_t(s2, a2), self.q2_t(s2, a2))
-            y = r + (1.0 - d) * self.gamma * q_t
+            y = r + (1.0 - d) * self.bootstrap_gamma * q_t
         l1 = F.mse_loss(self.q1(s, a), y)
         l2 = F.mse_loss(self.q2(s, a), y)
         self.opt_q1.zero_grad(set_to_none=True); l1.backward(); self.opt_q1.step()
@@ -480,7 +494,7 @@ class Agent(FusedActorMixin):
         from . import _abi
         og = self.opt_a.param_groups[0]
         return _abi.CnTd3Config(obs_dim=self.actor.linear1.in_features, hidden=self.actor.linear1.out_features, batch=self.batch_size,
-                                policy_delay=self.policy_delay, gamma=self.gamma, tau=self.tau, lr_actor=og["lr"],
+                                policy_delay=self.policy_delay, gamma=self.bootstrap_gamma, tau=self.tau, lr_actor=og["lr"],
                                 lr_critic=self.opt_q1.param_groups[0]["lr"], beta1=og["betas"][0], beta2=og["betas"][1], eps=og["eps"],
                                 noise_std=self.noise_std, noise_clip=self.noise_clip, max_v=self.max_v, max_w=self.max_w, reserved=0.0,
                                 actor=mlp_of(self.actor), actor_t=mlp_of(self.actor_t), q1=mlp_of(self.q1), q1_t=mlp_of(self.q1_t),
@@ -596,7 +610,88 @@ class Agent(FusedActorMixin):
             self.sync_fused_weights()
 
 
-class Population:
+class RecorderMixin:
+    """bind_record / record / resetting / record_pending over self.agents on self.device: the transitions and finished episodes of
+    every agent's environments in one call of two launches (cn_pop_record; cn_nstep_record for n-step rows)."""
+    _recorder = None
+
+    def bind_record(self, envs, prev, obs, act, reward, done, elogs, n_step=1):
+        """Create the cn_pop_record handle -- n_step = W > 1: the cn_nstep_record handle, whose ring rows are W-step transitions with
+        member p's returns discounted by agents[p].gamma; every agent's n_step must then be W, so that its target bootstraps with
+        gamma^W -- for fixed buffers.  Per member p: envs[p] its VecEnv (the finished episodes' counters and
+        returns are read straight from its state records), prev[p] / obs[p] [n_p, obs_dim], act[p] [n_p, 2], reward[p] [n_p]
+        (contiguous float32), done[p] [n_p] (uint8), all on the population's device, and elogs[p] its episode log (rows [>= max_rows,
+        8] float32, n int64, tot [5] float64, max_rows: crowdnav.train.DeviceEpisodeLog).  The transitions go to agents[p].memory.
+        prev[p] must hold the observation the first record()'s actions are computed from; every record() leaves obs[p] in it."""
+        from . import _abi
+        from ._fused import FusedNStepRecorder, FusedPopulationRecorder
+        lists = [list(x) for x in (envs, prev, obs, act, reward, done, elogs)]
+        if any(len(x) != len(self.agents) for x in lists):
+            raise ValueError("bind_record takes one environment, one buffer of each kind and one episode log per member")
+        n_step = int(n_step)
+        differ = [p for p, a in enumerate(self.agents) if a.n_step != n_step]
+        if differ:
+            raise ValueError("bind_record(n_step=%d): member(s) %s were built with another n_step (%s): their targets would bootstrap "
+                             "with another power of gamma than the rows span" % (n_step, differ, [self.agents[p].n_step for p in differ]))
+        D, dev = self.agents[0].actor.linear1.in_features, self.agents[0]._dev_index
+        members = []
+        for p, (ag, e, pv, o, u, r, d, lg) in enumerate(zip(self.agents, *lists)):
+            n = o.shape[0]
+            f32 = [(pv, (n, D)), (o, (n, D)), (u, (n, 2)), (r, (n,))]
+            ok = (all(tuple(t.shape) == sh and t.dtype == torch.float32 for t, sh in f32) and tuple(d.shape) == (n,) and d.dtype == torch.uint8
+                  and all(t.is_contiguous() and t.is_cuda and t.get_device() == dev for t in (pv, o, u, r, d))
+                  and lg.rows.dtype == torch.float32 and lg.rows.is_contiguous() and lg.rows.shape[0] >= lg.max_rows and lg.rows.shape[1] == 8
+                  and lg.n.dtype == torch.int64 and lg.tot.dtype == torch.float64 and lg.tot.numel() == 5
+                  and ag.memory.obs_dim == D and e.N == n)
+            if not ok:
+                raise ValueError("member %d: prev / obs must be [n, %d], act [n, 2], reward [n] (contiguous float32), done [n] (uint8) on %s "
+                                 "for an environment of n rows, and the log a DeviceEpisodeLog's tensors" % (p, D, self.device))
+            log = _abi.CnEpisodeLog(rows=lg.rows.data_ptr(), max_rows=lg.max_rows, n_dev=lg.n.data_ptr(), tot_dev=lg.tot.data_ptr())
+            members.append(_abi.CnPopRecordMember(env=e.h.value, counters=None, last_return=None, prev=pv.data_ptr(), obs=o.data_ptr(),
+                                                  action=u.data_ptr(), reward=r.data_ptr(), done=d.data_ptr(), ring=ag.memory.ring_struct(),
+                                                  log=log, n=n, reserved=0))
+        if n_step > 1:
+            members = [_abi.CnNstepMember(rec=m, gamma=a.gamma, reserved_f=0.0) for m, a in zip(members, self.agents)]
+            self._recorder = FusedNStepRecorder(members, n_step, D, self.device, dev, keep=lists)
+        else:
+            self._recorder = FusedPopulationRecorder(members, D, self.device, dev, keep=lists)
+        self._record_n = [e.N * n_step for e in lists[0]]         # the most ring rows a call writes: every episode ends with a full window
+        return self
+
+    def record(self, launch):
+        """Every member's transition and finished episodes of this launch as ONE call of two launches (cn_pop_record; cn_nstep_record
+        when bound with n_step > 1) on torch's current stream: the replay write of the rows that are not reset launches, the episode
+        log, prev <- obs.  Moves each member's host-side bound on its ring's fill level as DeviceReplay.add_masked does (by the most
+        rows the call can have written: n, or n * n_step), so ready() / len() stay right."""
+        if self._recorder is None:
+            raise RuntimeError("Population.bind_record(envs, prev, obs, act, reward, done, elogs) first: the recorder works on fixed buffers")
+        self._recorder.record(launch)
+        for a, n in zip(self.agents, self._record_n):
+            a.memory._ub = min(a.memory.cap, a.memory._ub + n)
+
+    def resetting(self, p):
+        """The recorder's flags of member p (uint8 [n_p], a view): set where the member's next record is a reset launch."""
+        if self._recorder is None:
+            raise RuntimeError("Population.bind_record first")
+        return self._recorder.resetting(p)
+
+    def record_pending(self, p):
+        """The n-step recorder's pending store of member p -- views (s [n_p, W, obs_dim], a [n_p, W, 2], ret [n_p, W], count [n_p], clock
+        [n_p]) -- which with resetting(p) is the recorder's whole state; () for the one-step recorder, which holds nothing back."""
+        if self._recorder is None:
+            raise RuntimeError("Population.bind_record first")
+        return self._recorder.pending(p) if hasattr(self._recorder, "pending") else ()
+
+
+class SoloRecorder(RecorderMixin):
+    """The recorder of one agent that is updated on its own (Agent.learn): a population's record() for a population of one, which
+    crowdnav.train's solo loop uses for n-step rows."""
+
+    def __init__(self, agent):
+        self.agents, self.device = [agent], agent.device
+
+
+class Population(RecorderMixin):
     """P TD3 agents on one device whose updates run as ONE chain of 7 (+ 5) launches (cn_td3_pop_update): member p's update is, bit
     for bit, the update agents[p].enable_fused_update() would run alone.  The agents keep their networks, replay rings, seeds,
     learning rates, gamma and target-noise parameters; they must agree in obs_dim, hidden, batch_size, policy_delay, tau, max_v,
@@ -606,7 +701,8 @@ class Population:
     same per-agent noise counter, so the two may be mixed.
     Recording: bind_record(...) once, then record(launch) is ONE call of two launches for all members (cn_pop_record) in place of P x
     (DeviceReplay.add_masked, VecEnv.counters, VecEnv.returns, DeviceEpisodeLog.add) and the copies around them; rings and logs are,
-    bit for bit, what those leave.
+    bit for bit, what those leave.  bind_record(..., n_step=W) for agents built with n_step=W records W-step rows instead
+    (cn_nstep_record: include/crowdnav.h), whose windows record_pending(p) shows.
     Evaluating: bind_eval(worlds, quota, metric) once, then evaluate() runs every member's greedy actor in every world -- three
     enqueues per launch for all of them (crowdnav.rollout.DeviceEvaluator, cn_eval_record) -- and returns the fitness [P] on the
     device, which exploit(fitness) takes; the members' noise counters do not move.
@@ -627,7 +723,6 @@ class Population:
                                       replay_sample=a0.replay_sample if replay_sample is None else replay_sample,
                                       replay_source=replay_source)
         self._actors = self._act_io = self._act_key = None
-        self._recorder = None
 
     def __len__(self):
         return len(self.agents)
@@ -711,54 +806,6 @@ class Population:
         population's binding lives."""
         return self._bound().weights(p)
 
-    def bind_record(self, envs, prev, obs, act, reward, done, elogs):
-        """Create the cn_pop_record handle for fixed buffers.  Per member p: envs[p] its VecEnv (the finished episodes' counters and
-        returns are read straight from its state records), prev[p] / obs[p] [n_p, obs_dim], act[p] [n_p, 2], reward[p] [n_p]
-        (contiguous float32), done[p] [n_p] (uint8), all on the population's device, and elogs[p] its episode log (rows [>= max_rows,
-        8] float32, n int64, tot [5] float64, max_rows: crowdnav.train.DeviceEpisodeLog).  The transitions go to agents[p].memory.
-        prev[p] must hold the observation the first record()'s actions are computed from; every record() leaves obs[p] in it."""
-        from . import _abi
-        from ._fused import FusedPopulationRecorder
-        lists = [list(x) for x in (envs, prev, obs, act, reward, done, elogs)]
-        if any(len(x) != len(self.agents) for x in lists):
-            raise ValueError("bind_record takes one environment, one buffer of each kind and one episode log per member")
-        D, dev = self.agents[0].actor.linear1.in_features, self.agents[0]._dev_index
-        members = []
-        for p, (ag, e, pv, o, u, r, d, lg) in enumerate(zip(self.agents, *lists)):
-            n = o.shape[0]
-            f32 = [(pv, (n, D)), (o, (n, D)), (u, (n, 2)), (r, (n,))]
-            ok = (all(tuple(t.shape) == sh and t.dtype == torch.float32 for t, sh in f32) and tuple(d.shape) == (n,) and d.dtype == torch.uint8
-                  and all(t.is_contiguous() and t.is_cuda and t.get_device() == dev for t in (pv, o, u, r, d))
-                  and lg.rows.dtype == torch.float32 and lg.rows.is_contiguous() and lg.rows.shape[0] >= lg.max_rows and lg.rows.shape[1] == 8
-                  and lg.n.dtype == torch.int64 and lg.tot.dtype == torch.float64 and lg.tot.numel() == 5
-                  and ag.memory.obs_dim == D and e.N == n)
-            if not ok:
-                raise ValueError("member %d: prev / obs must be [n, %d], act [n, 2], reward [n] (contiguous float32), done [n] (uint8) on %s "
-                                 "for an environment of n rows, and the log a DeviceEpisodeLog's tensors" % (p, D, self.device))
-            log = _abi.CnEpisodeLog(rows=lg.rows.data_ptr(), max_rows=lg.max_rows, n_dev=lg.n.data_ptr(), tot_dev=lg.tot.data_ptr())
-            members.append(_abi.CnPopRecordMember(env=e.h.value, counters=None, last_return=None, prev=pv.data_ptr(), obs=o.data_ptr(),
-                                                  action=u.data_ptr(), reward=r.data_ptr(), done=d.data_ptr(), ring=ag.memory.ring_struct(),
-                                                  log=log, n=n, reserved=0))
-        self._recorder = FusedPopulationRecorder(members, D, self.device, dev, keep=lists)
-        self._record_n = [m.n for m in members]
-        return self
-
-    def record(self, launch):
-        """Every member's transition and finished episodes of this launch as ONE call of two launches (cn_pop_record) on torch's
-        current stream: the replay write of the rows that are not reset launches, the episode log, prev <- obs.  Moves each member's
-        host-side bound on its ring's fill level as DeviceReplay.add_masked does, so ready() / len() stay right."""
-        if self._recorder is None:
-            raise RuntimeError("Population.bind_record(envs, prev, obs, act, reward, done, elogs) first: the recorder works on fixed buffers")
-        self._recorder.record(launch)
-        for a, n in zip(self.agents, self._record_n):
-            a.memory._ub = min(a.memory.cap, a.memory._ub + n)
-
-    def resetting(self, p):
-        """The recorder's flags of member p (uint8 [n_p], a view): set where the member's next record is a reset launch."""
-        if self._recorder is None:
-            raise RuntimeError("Population.bind_record first")
-        return self._recorder.resetting(p)
-
     # ---- population-based training: cn_td3_pop_pbt_bind / cn_td3_pop_exploit (include/crowdnav.h) -----------------------------------
     PBT_BOUNDS = dict(lr_actor=(1e-5, 1e-2), lr_critic=(1e-5, 1e-2), gamma=(0.9, 0.9999), noise_std=(0.02, 1.0), noise_clip=(0.05, 2.0))
 
@@ -776,6 +823,9 @@ class Population:
         unknown = [n for n in tuple(explore) + tuple(bounds or ()) if n not in names]
         if unknown:
             raise ValueError("unknown hyper-parameter(s) %s: population-based training knows %s" % (", ".join(map(repr, unknown)), ", ".join(names)))
+        if "gamma" in explore and any(a.n_step > 1 for a in self.agents):
+            raise ValueError("gamma cannot be explored with n_step > 1: the device tables hold the bootstrap discount gamma^n_step, "
+                             "and the recorder's window weights would not follow it")
         start = [self._pbt_hypers(a) for a in self.agents]
         lo, hi = [], []
         for k, n in enumerate(names):
@@ -799,7 +849,7 @@ class Population:
     @staticmethod
     def _pbt_hypers(a):
         """An agent's five hyper-parameters in CN_PBT_* order, as fused_config() hands them to the library."""
-        return [a.opt_a.param_groups[0]["lr"], a.opt_q1.param_groups[0]["lr"], a.gamma, a.noise_std, a.noise_clip]
+        return [a.opt_a.param_groups[0]["lr"], a.opt_q1.param_groups[0]["lr"], a.bootstrap_gamma, a.noise_std, a.noise_clip]
 
     def exploit(self, fitness=None):
         """One exploit / explore step (cn_td3_pop_exploit: two launches on torch's current stream, no host read), then sync_actors()
@@ -821,7 +871,10 @@ class Population:
             row = dict(src=int(m.src), generation=int(m.generation), fitness=float(m.fitness))
             row.update({n: float(m.hyper[k]) for k, n in enumerate(_abi.CN_PBT_HYPER_NAMES)})
             members.append(row)
+            gamma = a.gamma
             a.actor_lr, a.critic_lr, a.gamma, a.noise_std, a.noise_clip = (row[n] for n in _abi.CN_PBT_HYPER_NAMES)
+            if a.n_step > 1:                       # the table's (and the row's) gamma is the bootstrap discount, which is not explored
+                a.gamma = gamma
             a.opt_a.param_groups[0]["lr"] = a.actor_lr
             a.opt_q1.param_groups[0]["lr"] = a.opt_q2.param_groups[0]["lr"] = a.critic_lr
         return dict(calls=int(st.calls), applied=int(st.applied), members=members)

@@ -17,6 +17,11 @@ the checkpoints and pbt_log.csv are those of the run that was never stopped.
     python -m crowdnav.train --learner fused --population 8 --envs 64 --pbt-every 500 --csv --state-every 1000 --out runs/pop
     python -m crowdnav.train --learner fused --population 8 --envs 64 --pbt-every 500 --csv --state-every 1000 --resume runs/pop
 
+`--n-step W` (--algo td3, --reset-mode next; solo, or --population with the one-call recorder) fills the replay with W-step rows --
+the discounted sum of W rewards and the observation W steps on, accumulated on the device by cn_nstep_record (two launches per
+training launch); rows that an episode's end cuts short carry d = 1 -- and the target bootstraps with gamma^W.  W = 1, the default,
+is the run without the switch.
+
 Checkpoints are labelled with the episode count the weights really have behind them (N envs finish episodes in batches, so the
 count at a log interval is rarely a round number); every save also rewrites `latest_checkpoint.txt` with that count, and
 `--load-episode latest` (the default) reads it -- resume / evaluate commands can be written before the run exists.
@@ -306,7 +311,7 @@ def make_agent(a, obs_dim, device, **kw):
                          soft_update=a.sac_soft_update.replace("-", "_"), deterministic=a.sac_deterministic, **over)
     if a.algo == "ddpg":
         return ddpg.Agent(obs_dim=obs_dim, device=device, seed=a.seed, n_envs=a.envs, **over)
-    return td3.Agent(obs_dim=obs_dim, device=device, seed=a.seed, **over)
+    return td3.Agent(obs_dim=obs_dim, device=device, seed=a.seed, n_step=getattr(a, "n_step", 1), **over)
 
 
 def load_checkpoint(agent, a):
@@ -647,9 +652,14 @@ def run_loop(a, side):
     return side
 
 
+PENDING_NAMES = ("s", "a", "ret", "count", "clock")      # Population.record_pending's tensors, as a state names them
+
+
 class SoloSide:
     """One environment handle and one learner (TRAIN:104-168 for N environments): per launch act -> env.step -> the learner consumes
-    the transition -> episode log.  elog: the episode log (default: DeviceEpisodeLog on the observation's device)."""
+    the transition -> episode log.  elog: the episode log (default: DeviceEpisodeLog on the observation's device).  --n-step W > 1: the
+    transition and the episode log are ONE call of a one-member n-step recorder (td3.SoloRecorder, cn_nstep_record) on fixed buffers,
+    which also keeps `prev` and the reset-launch flags."""
     after_launch = before_log = close = staticmethod(lambda *args: None)      # (what follows the updates: a population's business)
 
     def __init__(self, a, env, learner, elog=None):
@@ -663,7 +673,19 @@ class SoloSide:
         self.ready, self.learn, self.after_updates = learner.ready, getattr(learner, "learn", None), learner.after_updates   # (Tabular: never ready, no learn)
         self.save_state = lambda d: learner.agent.save_state(os.path.join(d, "agent.npz"))
         self.load_state = lambda d, scalars: learner.agent.load_state(os.path.join(d, "agent.npz"))      # (re-packs the actor)
+        self.rec = None
+        if getattr(a, "n_step", 1) > 1:                                 # (parse_args: --algo td3 --reset-mode next)
+            self.prev.copy_(obs)                                       # once: every record() leaves the new observation in prev
+            self.act = torch.zeros((env.N, 2), dtype=torch.float32, device=obs.device)
+            self.rec = td3.SoloRecorder(learner.agent).bind_record([env], [self.prev], [obs], [self.act], [env.reward], [env.done],
+                                                                  [self.runs[0].elog], n_step=a.n_step)
+            self.launch = self.launch_nstep
         learner.start(obs, self.runs[0].elog)
+
+    def launch_nstep(self, it):
+        self.learner.agent.act_mfma(self.obs, out=self.act, add_noise=True)
+        self.env.step(self.act, auto_reset="next")
+        self.rec.record(it)
 
     def launch(self, it):
         env, learner, obs = self.env, self.learner, self.obs
@@ -687,6 +709,8 @@ class SoloSide:
     def state(self):                                                   # (parse_args: --algo td3 --learner fused --reset-mode next)
         t = dict(obs=self.obs, prev=self.prev, reward=self.env.reward, done=self.env.done, resetting=self.resetting,
                  **({} if self.act is None else dict(act=self.act)))     # (act: for the record; every launch computes its own)
+        if self.rec:                                                   # the recorder's flags in place of the loop's, and its pending store
+            t.update(resetting=self.rec.resetting(0), **{"record_pending_" + k: v for k, v in zip(PENDING_NAMES, self.rec.record_pending(0))})
         return [self.env], t, {}, [os.path.join(self.a.out, self.learner.csv_name + ".csv")] if self.a.csv else []
 
 
@@ -732,8 +756,8 @@ def build_members(a):
     samples the union of all members' rings (replay_source="shared") and the updates begin once the rings together hold more than a
     batch; the rings are written and saved per member as before, so --state-every / --resume hold a shared run as any other (give the
     switch again on --resume, like --replay-sample).  <out>/run.json records the switches that shape the run."""
-    members = [argparse.Namespace(**dict(vars(a), seed=a.seed + p, out=os.path.join(a.out, "member%d" % p), resume=a.resume))
-               for p in range(a.population)]                          # (resume, by name: the member's CSV is appended to)
+    members = [argparse.Namespace(**dict(vars(a), seed=a.seed + p, out=os.path.join(a.out, "member%d" % p), resume=a.resume, n_step=getattr(a, "n_step", 1)))
+               for p in range(a.population)]                          # (resume, by name: the member's CSV is appended to; n_step: the member's Agent)
     specs = [scenario_config(a.scenario, a.envs, a.max_steps, m.seed, a.ped_vmax, **env_switches(a)) for m in members]
     envs = MemberEnvs([sp[0] for sp in specs], a.device)
     for e, (_, init, vel) in zip(envs.envs, specs):
@@ -751,7 +775,7 @@ def build_members(a):
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, "run.json"), "w") as f:
         json.dump({k: getattr(a, k) for k in ("population", "population_replay", "population_act", "population_record", "population_step",
-                                              "replay_sample")}, f, indent=1, sort_keys=True)
+                                              "replay_sample", "n_step")}, f, indent=1, sort_keys=True)
         f.write("\n")
     return members, envs, agents, pop
 
@@ -848,7 +872,8 @@ class PopulationSide:
         keep_prev = lambda: prev.copy_(obs)
         if self.one_call:
             keep_prev()                                                # once: every record() leaves the new observation in prev
-            pop.bind_record(envs.envs, *[[x[r] for r in rows] for x in (prev, obs, act, envs.reward, envs.done)], self.elogs)
+            pop.bind_record(envs.envs, *[[x[r] for r in rows] for x in (prev, obs, act, envs.reward, envs.done)], self.elogs,
+                            **(dict(n_step=a.n_step) if getattr(a, "n_step", 1) > 1 else {}))      # (--n-step 1: the call as it always was)
         # a launch: these calls, then record(it).  fork: the members' streams wait for the loop's (the actions, or the group's step);
         # join: the loop's waits for theirs (record_members joins after its reads on their streams)
         self.calls = [act_all] + {(True, True): [step_all],            # one launch on this stream: no wait before it, none behind it
@@ -889,6 +914,8 @@ class PopulationSide:
     def state(self):                                                   # (parse_args: not with an evaluation's handles)
         t = dict(obs=self.obs, prev=self.prev, act=self.act, reward=self.envs.reward, done=self.envs.done, resetting=self.resetting)
         t.update({"record_resetting%d" % p: self.pop.resetting(p) for p in range(len(self.agents))} if self.one_call else {})
+        if getattr(self.a, "n_step", 1) > 1:                           # the n-step recorder's pending store
+            t.update({"record_pending%d_%s" % (p, k): v for p in range(len(self.agents)) for k, v in zip(PENDING_NAMES, self.pop.record_pending(p))})
         t.update(dict(pbt_flushed=self.pbt.flushed, pbt_tot=self.pbt.tot) if self.pbt else {})
         files = [os.path.join(r.out, r.learner.csv_name + ".csv") for r in self.runs] if self.a.csv else []
         return self.envs.envs, t, dict(pbt_applied=self.pbt.applied if self.pbt else 0), files + ([self.pbt.path] if self.pbt else [])
@@ -1033,6 +1060,12 @@ def build_parser():
     ap.add_argument("--population-record", default=None, choices=["one-call", "per-member"], help="--population only: one-call (default) = all "
                     "members' replay writes and episode logs in one cn_pop_record (two launches) per training launch; per-member = one "
                     "cn_replay_write, cn_get_counters, cn_get_returns and cn_episode_log_add per member.  Same results, bit for bit")
+    ap.add_argument("--n-step", type=int, default=1, help="W > 1: the replay holds W-step transitions -- R = sum_{k<W} gamma^k r_{t+k} and the "
+                    "observation W steps on, accumulated on the device by cn_nstep_record (two launches per training launch) -- and the TD3 "
+                    "target bootstraps with gamma^W; rows that an episode's end cuts short carry d = 1.  1 ... 16, default 1 = one-step rows, "
+                    "the calls and the results of a run without the switch.  --algo td3 with --reset-mode next; solo runs, and --population "
+                    "with --population-record one-call; not with gamma in --pbt-explore.  --memory must hold --envs * W rows.  Give it "
+                    "again on --resume")
     ap.add_argument("--population-replay", default=None, choices=["own", "shared"], help="--population only: own (default) = every member's "
                     "update samples its own replay ring; shared = every member samples the union of all members' rings, uniformly over its "
                     "live rows (cn_td3_pop_set_replay_source: the rings stay where they are, only the update's first launch reads "
@@ -1097,12 +1130,12 @@ def build_parser():
 
 
 class Args(argparse.Namespace):
-    """What parse_args returns.  The state switches (--state-every, --state-keep, --resume), --population-replay and --population-step are attributes like
+    """What parse_args returns.  The state switches (--state-every, --state-keep, --resume), --population-replay, --population-step and --n-step are attributes like
     every other switch, but they are held beside vars(): the namespace vars() gives for a command line stays, key for key, what it was
     before these switches (tests/test_eval_layout.py holds it to a record), and a Namespace built by hand or copied from vars() simply
     has none -- getattr(a, "state_every", 0) -- so the members of a population are handed `resume` by name."""
     __slots__ = ("_state",)
-    STATE = dict(state_every=0, state_keep=1, resume=None, population_replay=None, population_step=None)
+    STATE = dict(state_every=0, state_keep=1, resume=None, population_replay=None, population_step=None, n_step=1)
 
     def __init__(self, **kw):
         object.__setattr__(self, "_state", dict(self.STATE))
@@ -1194,6 +1227,20 @@ def parse_args(argv=None):
         if a.pbt_n_replace > a.population // 2:
             ap.error("--pbt-fraction %g of --population %d replaces %d members: at most half (%d) can be replaced, the others are the sources"
                      % (a.pbt_fraction, a.population, a.pbt_n_replace, a.population // 2))
+    if a.n_step != 1:
+        if not 1 <= a.n_step <= 16:
+            ap.error("--n-step must be 1 ... 16 (CN_NSTEP_MAX)")
+        if a.algo != "td3":
+            ap.error("--n-step records n-step rows for TD3's target (--algo td3), not --algo %s" % a.algo)
+        if a.reset_mode != "next":
+            ap.error("--n-step accumulates along the next-step reset's loop (--reset-mode next), not --reset-mode %s" % a.reset_mode)
+        if a.population and a.population_record != "one-call":
+            ap.error("--n-step is cn_nstep_record, the one-call recorder's sibling: it needs --population-record one-call, not %s" % a.population_record)
+        if a.pbt_every and "gamma" in a.pbt_explore:
+            ap.error("--n-step does not go with gamma in --pbt-explore: the learner's tables hold gamma^W, which an explore step would move "
+                     "away from the recorder's window weights")
+        if a.memory < a.envs * a.n_step:
+            ap.error("--n-step %d: a launch can write --envs * W = %d rows, more than --memory %d holds" % (a.n_step, a.envs * a.n_step, a.memory))
     if a.pbt_fitness is not None and not a.pbt_every:
         ap.error("--pbt-fitness selects what an exploit ranks by: it needs --pbt-every")
     if a.pbt_fitness is None:

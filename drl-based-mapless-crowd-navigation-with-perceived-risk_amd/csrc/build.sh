@@ -18,7 +18,7 @@
 # set once: the kernels carve with them, crowdnav_abi.hip sizes the launches from cn_lds_map, which composes them.  crowdnav_abi.hip is the environment's host side; the other files each
 # hold a subsystem's kernels next to the host code that launches them: the TD3 actor and the population's actors, the tabular
 # learners, the population's recorder (its bodies, crowdnav_record.h, are shared with crowdnav_replay.hip's kernels: one learner's
-# replay writes and episode log; crowdnav_eval.hip, the evaluator of many jobs, instantiates the episode log's body a third time), a learner's
+# replay writes and episode log, and with crowdnav_nstep.hip's, the recorder of n-step rows; crowdnav_record_host.h holds the members' checks of both recorders; crowdnav_eval.hip, the evaluator of many jobs, instantiates the episode log's body a third time), a learner's
 # state as one blob (crowdnav_state.hip: one copy kernel; crowdnav_state.h is what it asks of a learner's unit), and the fused learners, a unit each -- crowdnav_td3.hip (with the population), crowdnav_ddpg.hip,
 # crowdnav_dqn.hip, crowdnav_sac.hip -- around crowdnav_gemm.hip, the only unit that defines the GEMM and prep kernels they all
 # launch: it exports host launchers (crowdnav_learner.h, with the learners' host scaffold; crowdnav_learner_device.h holds the
@@ -46,6 +46,7 @@ UNITS=(         # object, source, flags of its own
   "replay crowdnav_replay.hip"
   "tab   crowdnav_tab.hip"
   "rec   crowdnav_pop_record.hip"
+  "nstep crowdnav_nstep.hip"
   "eval  crowdnav_eval.hip"
   "state crowdnav_state.hip"
 )

@@ -11,6 +11,7 @@
 
 #include "crowdnav_host.h"
 #include "crowdnav_record.h"
+#include "crowdnav_record_host.h"
 
 // Launch A, grid (1, 1, P) x 1024: member z's cn_replay_slot_kernel with keep = !resetting, then its cn_episode_log_kernel with the
 // same flags as `transitions`, then resetting <- done.  Thread t reads and writes the flags of rows i = t (mod 1024) only, and the
@@ -61,49 +62,13 @@ struct cn_pop_record_s {
 extern "C" int cn_pop_record_create(const cn_pop_record_member* members, int n_members, int obs_dim, int device, cn_pop_record_handle* out)
 {
     const std::string f("cn_pop_record_create");
-    if (!members) return fail(CN_ERR_ARG, f + ": members is null");
-    if (!out) return fail(CN_ERR_ARG, f + ": out is null");
-    if (n_members < 1 || n_members > CN_POP_RECORD_MAX) return fail(CN_ERR_ARG, f + ": n_members must be 1 ... 64");
-    if (obs_dim < 1) return fail(CN_ERR_CONFIG, f + ": obs_dim must be at least 1");
+    if (int rc = cn_record_check_call(f, members, out, n_members, obs_dim)) return rc;
     const int P = n_members;
-    struct Named { const void* ptr; const char* name; int member; };
-    std::vector<Named> written;                            // what a launch writes, per member: no two members may share any of it
+    std::vector<CnRecordNamed> written;                    // what a launch writes, per member: no two members may share any of it
     int max_n = 0;
     for (int p = 0; p < P; ++p) {
-        const cn_pop_record_member& m = members[p];
-        const std::string who = ": member " + std::to_string(p) + ": ";
-        if (m.n < 0) return fail(CN_ERR_ARG, f + who + "n is negative");
-        if (m.n > 0) {
-            if (!m.env && !(m.counters && m.last_return))
-                return fail(CN_ERR_ARG, f + who + "neither env nor both counters and last_return are given");
-            if (m.env && m.n != m.env->cfg.n_envs)
-                return fail(CN_ERR_ARG, f + who + "n is " + std::to_string(m.n) + " but env has n_envs " + std::to_string(m.env->cfg.n_envs));
-            const void* const rp[5] = {m.prev, m.obs, m.action, m.reward, m.done};
-            static const char* const rn[5] = {"prev", "obs", "action", "reward", "done"};
-            for (int i = 0; i < 5; ++i)
-                if (!rp[i]) return fail(CN_ERR_ARG, f + who + rn[i] + " is null");
-        }
-        const cn_replay_ring& r = m.ring;
-        if (!r.s || !r.a || !r.r || !r.s2 || !r.d || !r.pos_dev || !r.size_dev || r.capacity < 1 || r.obs_dim < 1)
-            return fail(CN_ERR_ARG, f + who + "incomplete ring");
-        if (!m.log.rows || !m.log.n_dev || !m.log.tot_dev) return fail(CN_ERR_ARG, f + who + "incomplete log");
-        if (m.log.max_rows < 0) return fail(CN_ERR_ARG, f + who + "log.max_rows is negative");
-        if ((int64_t)m.n > r.capacity)
-            return fail(CN_ERR_ARG, f + who + "n exceeds ring.capacity (two rows of one call would share a slot)");
-        if (r.obs_dim != obs_dim)
-            return fail(CN_ERR_CONFIG, f + who + "ring.obs_dim is " + std::to_string(r.obs_dim) + ", obs_dim " + std::to_string(obs_dim));
-        const Named mine[11] = {{r.s, "ring.s", p}, {r.a, "ring.a", p}, {r.r, "ring.r", p}, {r.s2, "ring.s2", p}, {r.d, "ring.d", p},
-                                {r.pos_dev, "ring.pos_dev", p}, {r.size_dev, "ring.size_dev", p}, {m.log.rows, "log.rows", p},
-                                {m.log.n_dev, "log.n_dev", p}, {m.log.tot_dev, "log.tot_dev", p}, {m.prev, "prev", p}};
-        for (const Named& x : mine) {
-            if (!x.ptr) continue;                          // (prev of a member without rows)
-            for (const Named& y : written)
-                if (y.ptr == x.ptr)
-                    return fail(CN_ERR_CONFIG, f + who + x.name + " is also member " + std::to_string(y.member) + "'s " + y.name +
-                                               " (they would race inside a launch)");
-        }
-        written.insert(written.end(), mine, mine + 11);
-        max_n = std::max(max_n, (int)m.n);
+        if (int rc = cn_record_check_member(f, members[p], p, obs_dim, 1, written)) return rc;
+        max_n = std::max(max_n, (int)members[p].n);
     }
     std::unique_ptr<cn_pop_record_s> h(new (std::nothrow) cn_pop_record_s());
     if (!h) return fail(CN_ERR_ARG, f + ": out of memory");

@@ -846,6 +846,59 @@ int cn_pop_record_members(cn_pop_record_handle h);
 uint8_t* cn_pop_record_resetting(cn_pop_record_handle h, int member);        /* dev [n_member] bytes, owned by the handle */
 int cn_pop_record(cn_pop_record_handle h, float launch, void* stream);        /* at most TWO launches */
 
+/* The n-step recorder: cn_pop_record's job -- replay write, episode log, prev <- obs, resetting <- done, for n_members <=
+ * CN_POP_RECORD_MAX members in TWO launches -- but the ring rows it writes are n-step transitions: (s_t, a_t, R, s_{t+m}, d) with
+ * R = sum_{k<m} gamma^k r_{t+k}, m = n_step for a row with d = 0 and m <= n_step for the rows an episode's end flushes (d = 1).
+ * Window and discount: n_step = W, 1 ... CN_NSTEP_MAX, is one value for the handle; gamma is per member.  cn_nstep_discount(gamma, k)
+ * starts with acc = 1.0 in float64, multiplies k times by (double)gamma and casts to float (no pow); it is host code and needs no
+ * device.  w[k] = cn_nstep_discount(gamma_p, k), and the bootstrap discount a learner must use with this recorder's rows is
+ * cn_nstep_discount(gamma_p, W).
+ * Pending store: per member and environment e the handle owns W slots, all zero at create -- s [n][W][obs_dim], a [n][W][2], ret [n][W],
+ * count [n] (the entries pending) and clock [n] (the pushes since the last flush).  An entry pushed at local time tau lies in slot
+ * tau mod W.  cn_nstep_record_pending gives the device pointers, so that a caller may save and restore them (with
+ * cn_nstep_record_resetting's flags they are the handle's whole state).
+ * Statement: cn_nstep_record(h, launch, stream) does, for every member p and every row e < n_p, with keep = !resetting_p[e] as it
+ * stood before the call:
+ *   1. not kept (the environment's reset launch): nothing is pushed and nothing emitted, whatever done_p[e] is; count and clock stay.
+ *   2. kept, in this order: every pending entry of age k >= 1 (pushed k calls of kept rows ago: 1 <= k <= count) takes
+ *      ret = ret + w[k] * reward_p[e], the float32 product and the float32 sum rounded separately (no FMA); then the new entry
+ *      (prev_p[e], action_p[e], ret = reward_p[e]) is pushed -- its return is ASSIGNED, so a -0.0f survives --; count and clock advance.
+ *   3. emission into ring_p, at consecutive slots from *pos_dev modulo capacity, rows ordered by e ascending and oldest first within
+ *      an environment: if done_p[e], all count entries, each as (s, a, ret, s2 = obs_p[e], d = 1), then count = clock = 0; else if
+ *      count == W, the oldest entry as (s, a, ret, s2 = obs_p[e], d = 0), then count = W - 1.  *pos_dev advances by the rows emitted
+ *      and *size_dev grows by them up to capacity, as in cn_replay_write.  An entry emitted by the call that pushes it (an episode's
+ *      last, or every entry when W = 1) goes from prev straight into the ring: the store's slot for it is not written.
+ *   4. the episode log, resetting_p <- done_p and prev_p <- obs_p are exactly cn_pop_record's; tot_dev[4] counts the kept rows.
+ *   5. rows at and beyond n_p, ring rows that receive nothing and pending slots that hold no entry are not touched (the slot of an
+ *      emitted entry keeps what it held, with the returns as step 2 left them).  If every n_p is 0, no launch is made.
+ * Consequences: with W = 1 the ring, log, prev and resetting are byte for byte what cn_pop_record leaves.  A row with d = 0 always
+ * spans exactly W steps, which is why one bootstrap discount per member suffices; a row with d = 1 is never bootstrapped from.  A call
+ * emits at most n_p * W rows per member, hence the refusal below.
+ * Launch A (plan), grid (1, 1, P) x 1024: per row the returns' update (at most W - 1 multiply-adds), the number of emitted rows and
+ * their scan into first slots, a descriptor {first slot, rows emitted, the pre-call count and clock} for launch B, count and clock,
+ * the ring's position and fill level, the episode log, resetting <- done.  Launch B (copy), grid (max n_p, W, P) x 256: workgroup
+ * (e, 0) takes the new entry from prev into the ring or into its slot of the store (the one free slot: count <= W - 1 before the push)
+ * and then runs prev <- obs for the row; workgroup (e, j >= 1) copies the (j - 1)-th oldest pending entry into its ring slot if it is
+ * emitted.  Launch A writes nothing that B reads in its pre-call form.  Enqueue-only, capturable on one stream.
+ * Refused before any device work, text in cn_last_error naming the field and the member: everything cn_pop_record_create refuses,
+ * with its codes and words; CN_ERR_ARG: n_step outside 1 ... CN_NSTEP_MAX; a member's gamma not finite or outside (0, 1];
+ * n * n_step > ring.capacity (a call could overrun itself); a NULL pending `out`. */
+#define CN_NSTEP_MAX 16
+typedef struct cn_nstep_member { cn_pop_record_member rec; float gamma, reserved_f; } cn_nstep_member;
+typedef struct cn_nstep_pending {
+    float *s, *a, *ret;          /* dev [n][n_step][obs_dim], [n][n_step][2], [n][n_step] */
+    int32_t *count, *clock;      /* dev [n] */
+    int32_t n, n_step, obs_dim, reserved;
+} cn_nstep_pending;
+typedef struct cn_nstep_record_s* cn_nstep_record_handle;
+int cn_nstep_record_create(const cn_nstep_member* members, int n_members, int n_step, int obs_dim, int device, cn_nstep_record_handle* out);
+void cn_nstep_record_destroy(cn_nstep_record_handle h);
+int cn_nstep_record_members(cn_nstep_record_handle h);
+uint8_t* cn_nstep_record_resetting(cn_nstep_record_handle h, int member);    /* dev [n_member] bytes, owned by the handle */
+int cn_nstep_record_pending(cn_nstep_record_handle h, int member, cn_nstep_pending* out);   /* device pointers, owned by the handle */
+int cn_nstep_record(cn_nstep_record_handle h, float launch, void* stream);    /* at most TWO launches */
+float cn_nstep_discount(float gamma, int k);                                  /* host only, no device */
+
 /* Evaluation on the device: J jobs at once, a job being one greedy actor in one world with its own environment handle.  One step of an
  * evaluation is three enqueues whatever J is -- cn_actor_pop_forward, cn_step_multi, cn_eval_record -- and nothing is read back until
  * the end: every environment contributes exactly its FIRST `quota` episodes (short episodes would otherwise be over-represented), the
